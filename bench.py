@@ -20,7 +20,12 @@ How the N ranks are split (tools/scaling_model.py): N = 2 -
 forward on the blocked-layout kernels); `--cfg-parallel` / `--no-cfg-parallel` / `--sequential-cfg` select the other splits.
 Timing: barrier + synchronize on both sides, MAX over ranks.
 
-The JSON line carries:
+A plain run sets up, warms up, times the K steps and prints ONE line: metric, value, unit, higher_is_better, dtype, ms_per_step and
+the figures derived from the timed steps alone.  Every leg listed below runs only with `--full` (without it their keys are null or absent).
+`--dump-outputs DIR` writes what the last timed step computed - the fp32 latents it leaves, rank 0's - as DIR/latents.npy; weights and
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+With --full, the JSON line also carries:
   roofline         the single largest kernel launch shape (the batched self-attention at 7200 tokens), algorithmic FLOPs / mean
                    launch duration measured with HIP events on the launch stream in one extra profiled step after the timed
                    region, vs 2.5 PFLOP/s dense bf16; `traffic` from the committed rocprofv3 --pmc passes under profiles/;
@@ -31,7 +36,7 @@ The JSON line carries:
                    oracle/_ref/transformer_ref.bin: "kind": "reference"; the oracle port beside it, and alone - "kind": "port" - where that file
                    was not built) timed on this host's granted cores on ONE transformer block at the same token count (rank 0, at every N; one
                    warm-up + median of three, a single bounded run at 28 800 tokens), extrapolated to steps/sec; cpu_config0 = BASELINE configs[0];
-  N > 1            `python bench.py --gpus N` without a launcher re-executes itself under torch.distributed.run; the headline is printed at once in a
+  N > 1            `python bench.py --gpus N` without a launcher runs itself under torch.distributed.run (a child process); the headline is printed at once in a
                    "preliminary" line, the complete line (sharded sec/edit of the temporal-reasoning edits, cpu_baseline, rccl.model_prediction) last;
   sec_per_edit     MEASURED end to end through ChronoEditPipeline for configs[2] (8-step distilled schedule, guidance 1) and,
                    with --full-edit, configs[1] (50 steps); the composed 50-step figure is labelled as composed.
@@ -115,6 +120,12 @@ def parse():
                     help="with --fp8: the round-1..3 GEMM contract (one fp32 scale per token row / output channel) instead of OCP-MX block scales")
     ap.add_argument("--attn-kernel", type=int, default=0,
                     help="(tuning) self-attention kernel knob of ce_set_attention_waves: 0 auto, 8 plain, 64 sw-pipelined")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (profiled step and roofline, power sample, host enqueue time, context-cache / "
+                         "fp8 / configs[4] rates, VAE, encoders, measured edits, CPU baselines; N > 1: exchange timings, sharded-vs-single "
+                         "check, one-GPU and replica figures, sharded edits).  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step (the fp32 latents, rank 0) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -386,6 +397,23 @@ def _kernel_symbol(label: str, work: float):
     return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(path: str, arrays: dict) -> None:
+    """Each tensor as `path`/<name>.npy in float32.  A tensor larger than its equal share of DUMP_LIMIT_BYTES is replaced by a fixed,
+    seeded sample of its flattened elements (the same indices on every run and build), so that the whole stays within the limit."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    per_array = DUMP_LIMIT_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        x = t.detach().to(torch.float32).cpu()
+        if x.numel() > per_array:
+            idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:per_array].sort().values
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), x.numpy())
+
+
 def _baseline_config_name(a, T) -> str:
     """Which BASELINE.json configuration the chosen shape corresponds to (label only)."""
     if (a.width, a.height) == (1280, 720) and T == 2:
@@ -416,10 +444,11 @@ class Workload:
 
 
 def _self_launch(n: int):
-    """`python bench.py --gpus N` without a launcher (no WORLD_SIZE in the environment): re-execute this very command line under
+    """`python bench.py --gpus N` without a launcher (no WORLD_SIZE in the environment): run this very command line under
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>` - the form the driver
-    uses for N > 1 - so the same verb works at every N.  Replaces the process (exit code and stdout are the launcher's).  A box with fewer
-    than N GPUs gets ONE parsable error line and exit code 2 instead of N ranks dying in set_device."""
+    uses for N > 1 - so the same verb works at every N.  The launcher runs as a child process sharing this one's stdout / stderr, and this
+    process exits with its exit code.  A box with fewer than N GPUs gets ONE parsable error line and exit code 2 instead of N ranks dying
+    in set_device."""
     if os.environ.get("CE_BENCH_SELF_LAUNCHED"):
         raise RuntimeError("bench.py re-launched itself but still sees no WORLD_SIZE: torch.distributed.run did not set the rank environment")
     have = torch.cuda.device_count()
@@ -436,7 +465,8 @@ def _self_launch(n: int):
            "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execve(sys.executable, cmd, env)
+    import subprocess
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def main():
@@ -570,7 +600,8 @@ def main():
         sync_all()
         return max_over_ranks(time.perf_counter() - t0)
 
-    total = a.warmup + a.steps + (0 if a.no_profile else 2)
+    total = a.warmup + a.steps + (0 if a.no_profile else 2)  # (the schedule's length, so a plain run computes what --full computes)
+    profile = a.full and not a.no_profile  # the legs of one more step each: host enqueue time, power sample, per-kernel profile
 
     def all_ranks_ok(ok: bool) -> bool:
         """Did EVERY rank get here without an exception?  (host-side vote on the control group)"""
@@ -599,6 +630,7 @@ def main():
     sched = new_sched(total)
     dt = finite = host_enqueue_ms = rccl = exchange_us = verify = None
     one_step = eager_step = None
+    dump = {} if a.dump_outputs and rank == 0 else None  # what the timed path computed in its last timed step
 
     def headline_leg():
         nonlocal dt, finite, host_enqueue_ms, rccl, one_step, eager_step, exchange_us, verify
@@ -610,9 +642,11 @@ def main():
                 raise RuntimeError("injected failure of the sharded leg (CE_BENCH_INJECT_SHARDED_FAILURE; tests/test_bench_multirank_gpu.py)")
         dt = timed(one_step, a.warmup, a.steps)
         finite = bool(torch.isfinite(wl.latents).all().item())
+        if dump is not None:
+            dump["latents"] = wl.latents.clone()  # (the legs below step the same latents further)
         # how long the host needs to ISSUE one eager step (no wait): the margin by which a launch-per-kernel loop stays GPU-bound
         # (why the sharded loop, which cannot be hipGraph-captured on this stack, loses nothing by running eagerly)
-        if not a.no_profile:
+        if profile:
             sync_all()
             t0h = time.perf_counter()
             eager_step(a.warmup + a.steps)
@@ -631,6 +665,9 @@ def main():
                     "exchange": ("k|v all-to-all overlapped with the q projection; q; attention output (K-segmented operand of the out-projection)"
                                  if model._sp.world > 1 else "none inside a forward: each GPU runs one guidance pass whole") +
                                 ("; one all_gather of the two predictions per step" if a.cfg_parallel else "")}
+            if not a.full:  # exchange timings, scaling prediction and the sharded-vs-single check are --full legs
+                rccl["exchange_us_per_layer"] = None
+                return
             exchange_us = time_exchanges()
             rccl["exchange_us_per_layer"] = exchange_us
             # what the scaling model (tools/scaling_model.py) predicts for every split of these ranks - the pair batched in
@@ -721,14 +758,14 @@ def main():
         headline_leg()
 
     power = None
-    if world == 1 and not one_rank_sp and not a.no_profile and not a.graph and total >= a.warmup + a.steps + 2:
+    if world == 1 and not one_rank_sp and profile and not a.graph and total >= a.warmup + a.steps + 2:
         # (its own seeded inputs and scheduler: the timed workload's latents and schedule are left as the timed region left them)
         power = _power_sample(make_stepper(Workload(dev, T, h, w, 4343), new_sched(8), sequential=a.sequential_cfg), 0)
     # ---- per-kernel HIP-event profile of ONE more step (outside the timed region) -> roofline of the dominant kernel
     roofline = roofline_family = breakdown = None
-    if not a.no_profile and ulysses and rank != 0:
+    if profile and ulysses and rank != 0:
         eager_step(a.warmup + a.steps + 1)  # the step has collectives: every rank must take part
-    if not a.no_profile and rank == 0:
+    if profile and rank == 0:
         with ops.profile() as prof:
             eager_step(a.warmup + a.steps + 1)
         summ = prof.summary()
@@ -788,18 +825,18 @@ def main():
                                "launches": sum(d["n"] for d in big.values()), "total_ms": round(fam_ms, 3), "share_of_step": round(fam_ms / tot, 4)}
 
     single = dict(cached_rate=None, fp8_rate=None, fp8_config4=None, fp8_policies=None, vae_s=None, enc_s=None, edit8=None, edit50=None, edit_reasoning=None)
-    if world == 1 and rank == 0 and not one_rank_sp:
+    if a.full and world == 1 and rank == 0 and not one_rank_sp:
         _single_gpu_secondaries(a, model, wl, new_sched, make_stepper, dev, T, h, w, single)
 
     # ---- N > 1: the headline is measured; say it NOW in a line marked preliminary (the legs below run whole edits and CPU baselines for minutes -
     # should one of them take the process down, the timed figure of this run is already on stdout), then measure sec/edit with the DiT sharded
-    if world > 1 and rank == 0 and dt is not None:
+    if a.full and world > 1 and rank == 0 and dt is not None:
         print(json.dumps({"metric": "denoising-steps/sec", "value": round(a.steps / dt * (1 if ulysses else world), 4), "n_gpus": world, "steps": a.steps,
                           "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 2), "scaling": "strong" if ulysses else "weak", "preliminary": True,
                           "note": "headline of this run, printed before the secondary legs; the COMPLETE line (same value + roofline, cpu_baseline, sec/edit) is the last line"}),
               flush=True)
     sharded_edit = None
-    if ulysses and a.reasoning_edit and not a.no_edit and not a.no_vae and T == 8:
+    if a.full and ulysses and a.reasoning_edit and not a.no_edit and not a.no_vae and T == 8:
         try:
             sharded_edit = _sharded_edit_leg(a, model, dev, world, max_over_ranks, test_backend)
         except Exception as e:  # noqa: BLE001 - reported, never fatal to the line
@@ -808,7 +845,7 @@ def main():
     # ---- N > 1, Ulysses headline: the same workload on ONE GPU (rank 0) and the replica (weak-scaling) figure, both outside
     # the timed region, so the line is self-contained
     single_same = replica = None
-    if ulysses and not a.no_secondary:
+    if a.full and ulysses and not a.no_secondary:
         sp, cfgp = model._sp, model._cfgp
         model._sp = model._cfgp = None
         model.engine()._ws = {}
@@ -904,10 +941,11 @@ def main():
             "sec_per_edit_temporal_reasoning": single.get("edit_reasoning") if world == 1 else sharded_edit,
             "steps_per_sec_fp8_config4": single.get("fp8_config4"),
             "fp8_policies": single.get("fp8_policies"),
+            "full": a.full,
         }
         if a.layers != 40:
             out["invalid"] = "reduced depth (debug run)"
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             try:  # (rank 0 at every N, after the timed region; at N = 28 800 one call of the block is ~1 min of host time: a bounded single-run sample)
                 out["cpu_baseline"] = cpu_baseline(N, fwd_per_step, grid=(T, h // 2, w // 2))
             except Exception as e:  # the baseline must never take the bench line down
@@ -917,6 +955,8 @@ def main():
                     out["cpu_config0"] = cpu_config0(with_reference=True, depths=(1, 2))  # (1, 2, 4): bench.py --cpu-only
             except Exception as e:
                 out["cpu_config0"] = {"error": repr(e)}
+        if dump:
+            _dump_outputs(a.dump_outputs, dump)
         print(json.dumps(out), flush=True)
     if world > 1 or one_rank_sp:
         try:

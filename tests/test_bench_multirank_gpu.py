@@ -37,7 +37,7 @@ def _run(world, extra=(), env_extra=None, timeout=900, bare=False):
         env.pop(k, None)
     env.update(env_extra or {})
     bench_args = [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "1",
-                  "--layers", "2", "--height", "352", "--width", "640", "--no-profile", *extra]
+                  "--layers", "2", "--height", "352", "--width", "640", "--no-profile", "--full", *extra]
     if bare:  # `python bench.py --gpus N`, no launcher: bench.py re-executes itself under torch.distributed.run
         cmd = [sys.executable, *bench_args]
     else:     # the driver's form
@@ -139,7 +139,7 @@ def test_one_rank_rccl_owned_comm_flags(graph):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "CE_BENCH_TEST_BACKEND", "CE_BENCH_SELF_LAUNCHED"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--layers", "2", "--height", "352", "--width", "640",
-           "--no-profile", "--no-secondary", "--no-cpu-baseline", "--no-reasoning-edit", "--owned-comm", *(["--graph"] if graph else [])]
+           "--no-profile", "--no-secondary", "--no-cpu-baseline", "--no-reasoning-edit", "--owned-comm", "--full", *(["--graph"] if graph else [])]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, f"stdout tail: {r.stdout[-1500:]}\nstderr tail: {r.stderr[-3000:]}"
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.strip().startswith("{") and ln.strip().endswith("}")]

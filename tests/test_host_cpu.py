@@ -288,27 +288,29 @@ def test_head_conv_row_packing_reproduces_the_convolution(KT, T, H, W, Cout):
 
 
 def test_bench_bare_gpus_n_relaunches_itself_under_torch_distributed_run(monkeypatch, capsys):
-    """`python bench.py --gpus 8` without a launcher (VERDICT r4 #1a): the process is replaced by the driver's own launch form - same script,
-    same arguments, 127.0.0.1 rendezvous on a free port, dmabuf IPC kept - instead of raising; a box with fewer GPUs gets one parsable
-    error line and exit code 2; a second re-launch (the launcher did not set WORLD_SIZE) is refused."""
+    """`python bench.py --gpus 8` without a launcher (VERDICT r4 #1a): the driver's own launch form runs as a child process - same script,
+    same arguments, 127.0.0.1 rendezvous on a free port, dmabuf IPC kept - instead of raising, and its exit code is this process's; a box
+    with fewer GPUs gets one parsable error line and exit code 2; a second re-launch (the launcher did not set WORLD_SIZE) is refused."""
     import json
     import os
+    import subprocess
     import sys
 
     import bench
     seen = {}
 
-    def fake_execve(exe, cmd, env):
-        seen.update(exe=exe, cmd=cmd, env=env)
-        raise SystemExit(0)
+    def fake_call(cmd, env):
+        seen.update(exe=cmd[0], cmd=cmd, env=env)
+        return 3
 
-    monkeypatch.setattr(os, "execve", fake_execve)
+    monkeypatch.setattr(subprocess, "call", fake_call)
     monkeypatch.setattr(torch.cuda, "device_count", lambda: 8)
     monkeypatch.delenv("CE_BENCH_SELF_LAUNCHED", raising=False)
     monkeypatch.delenv("CE_BENCH_TEST_BACKEND", raising=False)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "3", "--warmup", "1"])
-    with pytest.raises(SystemExit):
+    with pytest.raises(SystemExit) as ei:
         bench._self_launch(8)
+    assert ei.value.code == 3  # the launcher's exit code
     cmd = seen["cmd"]
     assert seen["exe"] == sys.executable and cmd[:3] == [sys.executable, "-m", "torch.distributed.run"]
     assert "--nnodes=1" in cmd and "--nproc-per-node=8" in cmd and cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"

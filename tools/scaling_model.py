@@ -90,7 +90,7 @@ def predict(W: int, link_GBps: float = 55.0, latency_us: float = 25.0) -> dict:
 
 
 def expected_wall_s(W: int, step_ms: float, steps: int = 20, warmup: int = 5, reasoning_steps=(10, 50)) -> dict:
-    """How long the DEFAULT `bench.py --gpus W --steps 20 --warmup 5` line should take end to end on W real GPUs: the
+    """How long the `bench.py --gpus W --steps 20 --warmup 5 --full` line should take end to end on W real GPUs: the
     legs of bench.py priced with the model's sharded step time and the one-GPU measurements of profiles/r05_bench.json - so that a first
     multi-GPU run that exceeds it by more than ~2x can be called a hang and not a slow run.  Seconds; an estimate (+-30 %)."""
     sp_up = 2103.0 / step_ms                      # the model's strong-scaling speed-up at 8 latent frames
