@@ -1600,12 +1600,7 @@ static int attention_vt_launch(const void* Q, const void* K, const void* Vt, int
     (void)hipFuncSetAttribute((const void*)attn_fwd_sp_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes(false));
     done = true;
   }
-  static int cus_[CE_MAX_DEVICES] = {};
-  int& cus = cus_[ce_device_slot()];
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  }
+  const int cus = ce_device_cus();
   const int items = nqb * H * batch;
 #ifdef CE_DIAGNOSTICS
   if (g_attn_nwave == 16 && blk_rows == 0) {  // the 16 x 16 x 32 geometry (plain layout; unaligned operands fall through to the default body)
@@ -1673,12 +1668,7 @@ static int attention_2seg_vt_launch(const void* Q, const void* K1, const void* V
   const BlkRows blk{0, vt_cols2, 0u, vt_cols1, (unsigned char*)O8, (unsigned char*)S8, ldo8};  // plain rows; the two column strides
   // persistent like the single-segment V^T launch: two workgroups per CU walk the work order (an item is 13 key tiles here: -3 % against
   // one workgroup per item, profiles/r04_cross_attention_persistent_ab.txt; 3 and 4 per CU are level with 2)
-  static int cus2_[CE_MAX_DEVICES] = {};
-  int& cus = cus2_[ce_device_slot()];
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  }
+  const int cus = ce_device_cus();
   const int items = nqb * H * batch;
   const int grid = items <= 2 * cus ? items : ((2 * cus) & ~7);
   if (O8)

@@ -1138,8 +1138,7 @@ CE_API int ce_attention_1head_bf16(const void* Q, const void* K, const void* Vt,
   if ((C != 128 && C != 384) || (ldq & 7) || (ldk & 7) || (ldvt & 7) || (ldo & 3) || ldvt < (Nk + 63) / 64 * 64) return CE_ERR_SHAPE;
   const float sl2 = softmax_scale * 1.4426950408889634f;
   const int blocks = (Nq + 127) / 128, ntiles = (Nk + 31) / 32;  // 32-key tiles
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const int cus = ce_device_cus();
   // key split: as many splits (<= 4, >= 16 key tiles each) as fill the chip, if the caller's workspace holds the fp32 partial results
   int nsplit = 1;
   if (ws != nullptr && blocks * 4 < cus * 3)

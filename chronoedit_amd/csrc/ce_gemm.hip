@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_128(const bf16* __restrict__ A,
     const int cur = kt & 1;
     if (kt + 1 < KT) {
       const int koff = (kt + 1) * BK;
-      // segmented A (ce_gemm_aseg_bf16): every a_seg_tiles K-tiles the source jumps a_seg_extra elements further
+      // segmented A (a_seg_k of ce_gemm_bf16): every a_seg_tiles K-tiles the source jumps a_seg_extra elements further
       const long long koff_a = koff + (a_seg_tiles > 0 ? ((kt + 1) / a_seg_tiles) * a_seg_extra : 0ll);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -227,18 +227,22 @@ __global__ __launch_bounds__(256) void gemm_bf16_128(const bf16* __restrict__ A,
 extern "C" int ce_gemm256_supported(int M, int N, int K, int lda, int ldw);
 extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
                                  const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, hipStream_t stream);
+                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
+                                 hipStream_t stream);
 
 extern "C" void ce_gemm256_set_staggered(int on);
 extern "C" int ce_gemm384_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
                                  const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, hipStream_t stream);
+                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
+                                 hipStream_t stream);
 extern "C" int ce_gemm288_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
                                  const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, hipStream_t stream);
+                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
+                                 hipStream_t stream);
 extern "C" int ce_gemm256w4_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
                                    const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                                   int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, int nsa, hipStream_t stream);
+                                   int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, int nsa, float* ws,
+                                   size_t ws_bytes, hipStream_t stream);
 
 // kernel selection: -1 = automatic (for large shapes the one-wave-per-SIMD LDS-DMA kernels, macro tile 384 x 256 or 256 x 256 by
 // the round count of the shape: ce_gemm_bf16_tile_rows), 0 = always the
@@ -254,14 +258,6 @@ CE_API int ce_set_gemm_variant(int v) {
   return old;
 }
 #endif
-
-// Column k of A lives at A + (k / a_seg_k) * a_seg_stride + m * lda + k % a_seg_k: the layout an all-to-all leaves the
-// attention output in ([source rank][local row][D / W], chronoedit_amd/parallel.py), consumed by the out-projection
-// without a gather pass.  a_seg_k == 0 (or >= K): plain row-major A.
-// ... and the same for W (w_seg_k, w_seg_stride): weights re-packed K-slab-major ([K/64][N][64]) so that every 16 KiB
-// half-tile of the LDS-DMA stream is one contiguous block (tools/probes/l2_pattern_probe.hip: 21.7 vs 18.3 TB/s for the
-// row-strided form).  Segmented W needs the 256-tile kernel (CE_ERR_SHAPE otherwise).
-extern "C" void ce_gemm256_workspace(hipStream_t stream, float** ws, size_t* bytes, int* cus);
 
 // Which macro tile for a large GEMM: 384 x 256 (ce_gemm384.hip) or 256 x 256 (ce_gemm256w4.hip)?  Their main loops run at the same
 // rate per flop within 1 % (profiles/r03_gemm_variants_ab.txt); what differs is how the tile count falls on the 256 CUs.  Cost model:
@@ -291,12 +287,7 @@ CE_API int ce_gemm_bf16_tile_rows(int M, int N, int K, int cus, long long ws_byt
     const double c = bm == 256 ? 1.40 : bm == 288 ? 1.40 * 1.125 * 0.985 * llc : 1.40 * 1.5 * 0.96 * llc;
     double t = (double)full * kt * c;
     if (tail > 0) {
-      int split = 1;
-      for (int sp = cus / tail < 8 ? cus / tail : 8; sp >= 2; --sp)
-        if (kt % (2 * sp) == 0 && (long long)tail * sp * bm * 256 * (long long)sizeof(float) <= ws_bytes) {
-          split = sp;
-          break;
-        }
+      const int split = ce_split_k(tail, kt, cus, bm * 256 * (long long)sizeof(float), ws_bytes);
       if (split > 1) t += (double)kt / split * c + (double)tail * split * bm * 256.0 * 8.0 / 6.0e6;
       else t += (double)kt * c * pow((double)tail / cus, 0.3);
     }
@@ -318,18 +309,20 @@ CE_API int ce_gemm_bf16_tile_rows(int M, int N, int K, int cus, long long ws_byt
   return c384 <= c256 ? 384 : 256;
 }
 
-static int auto_tile_rows(int M, int N, int K, hipStream_t stream) {
-  float* ws = nullptr;
-  size_t ws_bytes = 0;
-  int cus = 256;
-  ce_gemm256_workspace(stream, &ws, &ws_bytes, &cus);
-  return ce_gemm_bf16_tile_rows(M, N, K, cus, ws != nullptr ? (long long)ws_bytes : 0);
-}
-
-CE_API int ce_gemm_seg_bf16(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                                int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, hipStream_t stream) {
+// Column k of A lives at A + (k / a_seg_k) * a_seg_stride + m * lda + k % a_seg_k: the layout an all-to-all leaves the
+// attention output in ([source rank][local row][D / W], chronoedit_amd/parallel.py), consumed by the out-projection
+// without a gather pass.  a_seg_k == 0 (or >= K): plain row-major A.
+// ... and the same for W (w_seg_k, w_seg_stride): weights re-packed K-slab-major ([K/64][N][64]) so that every 16 KiB
+// half-tile of the LDS-DMA stream is one contiguous block (tools/probes/l2_pattern_probe.hip: 21.7 vs 18.3 TB/s for the
+// row-strided form).  Segmented W needs the 256-tile kernel (CE_ERR_SHAPE otherwise).
+CE_API int ce_gemm_bf16(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
+                        const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                        int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, void* ws, size_t ws_bytes,
+                        hipStream_t stream) {
   if (!A || !W || !C) return CE_ERR_ARG;
+  float* const slabs = static_cast<float*>(ws);
+  const long long scratch_bytes = ws ? (long long)ws_bytes : 0;  // what the split-K tail may use (tile choice)
+  const int cus = ce_device_cus();
   if (epilogue == EPI_BIAS_T) {
     // C^T is stored (C is [N][ldc]).  Mathematically the EPI_BIAS_ROW product with the operands swapped; run as written - M the token count -
     // on the 384- / 288-row kernel when that is what the dispatcher would give (M, N, K) anyway and its last round runs whole (the transposed
@@ -339,21 +332,17 @@ CE_API int ce_gemm_seg_bf16(const void* A, const void* W, void* C, const float* 
     const bool plain = (a_seg_k <= 0 || a_seg_k >= K) && (w_seg_k <= 0 || w_seg_k >= K);
     if (plain && (M & 7) == 0 && (N & 7) == 0 && (long long)M * N >= 256ll * 256 * 128 && (long long)N * ldc * 2 < (1ll << 32) &&
         ce_gemm256_supported(M, N, K, lda, ldw) && (g_gemm_variant == -1 || g_gemm_variant == 6 || g_gemm_variant == 7)) {
-      float* ws = nullptr;
-      size_t ws_bytes = 0;
-      int cus = 256;
-      ce_gemm256_workspace(stream, &ws, &ws_bytes, &cus);
-      const int rows = g_gemm_variant == 6 ? 384 : g_gemm_variant == 7 ? 288 : ce_gemm_bf16_tile_rows(M, N, K, cus, ws != nullptr ? (long long)ws_bytes : 0);
+      const int rows = g_gemm_variant == 6 ? 384 : g_gemm_variant == 7 ? 288 : ce_gemm_bf16_tile_rows(M, N, K, cus, scratch_bytes);
       if (rows == 384 || rows == 288) {
         const long long nwg = (long long)((M + rows - 1) / rows) * ((N + 255) / 256);
         const int tail = (int)(nwg % cus);
         if (g_gemm_variant != -1 || tail == 0 || tail * 10 >= cus * 9)
           return (rows == 384 ? ce_gemm384_launch : ce_gemm288_launch)(A, W, C, bias, EPI_BIAS_T, nullptr, nullptr, M, N, K, lda, ldw, ldc, 0, 0, 0, 0, 0, 0,
-                                                                      stream);
+                                                                      slabs, ws_bytes, stream);
       }
     }
     if (!plain) return CE_ERR_SHAPE;
-    return ce_gemm_seg_bf16(W, A, C, bias, EPI_BIAS_ROW, nullptr, nullptr, N, M, K, ldw, lda, ldc, 0, 0, 0, 0, 0, 0, stream);
+    return ce_gemm_bf16(W, A, C, bias, EPI_BIAS_ROW, nullptr, nullptr, N, M, K, ldw, lda, ldc, 0, 0, 0, 0, 0, 0, ws, ws_bytes, stream);
   }
   if (w_seg_k < 0 || (w_seg_k > 0 && w_seg_k < K && ((w_seg_k % BK) || (K % w_seg_k) || (w_seg_stride & 7)))) return CE_ERR_SHAPE;
   if (w_seg_k >= K) w_seg_k = 0;
@@ -369,18 +358,18 @@ CE_API int ce_gemm_seg_bf16(const void* A, const void* W, void* C, const float* 
     if ((want || w_seg_k) && ce_gemm256_supported(M, N, K, lda, ldw)) {
       // the 256-tile kernel has two main loops: one wave per SIMD (ce_gemm256w4.hip; the default: +3...5 % on the step's shapes,
       // profiles/r03_gemm_variants_ab.txt) and the 8-wave / 8-phase loop of ce_gemm256.hip (variants 1, 2)
-      const int rows_auto = g_gemm_variant == -1 ? auto_tile_rows(M, N, K, stream) : 0;
+      const int rows_auto = g_gemm_variant == -1 ? ce_gemm_bf16_tile_rows(M, N, K, cus, scratch_bytes) : 0;
       if (g_gemm_variant == 6 || rows_auto == 384)  // the 384 x 256 macro tile (ce_gemm384.hip)
         return ce_gemm384_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride,
-                                 w_seg_k, w_seg_stride, stream);
+                                 w_seg_k, w_seg_stride, slabs, ws_bytes, stream);
       if (g_gemm_variant == 7 || rows_auto == 288)  // the 288 x 256 macro tile (the same kernel, 144 x 128 wave tiles)
         return ce_gemm288_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride,
-                                 w_seg_k, w_seg_stride, stream);
+                                 w_seg_k, w_seg_stride, slabs, ws_bytes, stream);
       if (g_gemm_variant == 1 || g_gemm_variant == 2)
         return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride,
-                                 w_seg_k, w_seg_stride, stream);
+                                 w_seg_k, w_seg_stride, slabs, ws_bytes, stream);
       return ce_gemm256w4_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride,
-                                 w_seg_k, w_seg_stride, g_gemm_variant == 3 ? 3 : g_gemm_variant == 5 ? 1 : 2, stream);
+                                 w_seg_k, w_seg_stride, g_gemm_variant == 3 ? 3 : g_gemm_variant == 5 ? 1 : 2, slabs, ws_bytes, stream);
     }
   }
   if (w_seg_k) return CE_ERR_SHAPE;
@@ -404,18 +393,6 @@ CE_API int ce_gemm_seg_bf16(const void* A, const void* W, void* C, const float* 
   }
 #undef CE_LAUNCH
   return (int)hipGetLastError();
-}
-
-CE_API int ce_gemm_aseg_bf16(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                                 int a_seg_k, long long a_seg_stride, hipStream_t stream) {
-  return ce_gemm_seg_bf16(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, 0, 0, stream);
-}
-
-CE_API int ce_gemm_bf16(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                            const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                            hipStream_t stream) {
-  return ce_gemm_seg_bf16(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, 0, 0, 0, 0, stream);
 }
 
 // batch0 x batch1 independent products with two-level element strides (e.g. head within sample): operand z = (z0, z1) is

@@ -26,10 +26,6 @@
 //    leaves the two most recent half-tiles in flight, LDS-DMA is never drained inside the loop.
 //  * Epilogue: the accumulators go through LDS in two 128-row passes so that bias/GELU/gated-residual
 //    math and the global stores run on 16-B row-contiguous chunks (same rounding points as ce_gemm.hip).
-#include <algorithm>
-
-#include <mutex>
-
 #include "ce_common.h"
 #include "ce_gemm_epi.h"
 
@@ -57,13 +53,13 @@ struct Stager {
   const char* w_base;
   int wave;              // wave-uniform
   int kt_last;
-  // Segmented A (Ulysses receive layout, ce_gemm_aseg_bf16): K-tile t of A starts a_seg_extra bytes further for every
+  // Segmented A (Ulysses receive layout, a_seg_k of ce_gemm_bf16): K-tile t of A starts a_seg_extra bytes further for every
   // a_seg_tiles tiles passed, i.e. at t*128 + (t / a_seg_tiles) * a_seg_extra; t / a_seg_tiles = (t * a_seg_magic) >> 16
   // (checked on the host for every tile index of the launch).  a_seg_extra == 0: plain row-major A.
   int kt0;               // first K-tile of this block (split-K tail pieces start past 0)
   uint32_t a_seg_magic;
   uint32_t a_seg_extra;  // bytes
-  uint32_t w_seg_magic;  // the same for W (ce_gemm_seg_bf16: weights re-packed K-slab-major)
+  uint32_t w_seg_magic;  // the same for W (w_seg_k of ce_gemm_bf16: weights re-packed K-slab-major)
   uint32_t w_seg_extra;
 };
 
@@ -454,113 +450,28 @@ extern "C" void ce_gemm256_set_staggered(int on) { staggered = on != 0; }
 static constexpr bool staggered = false;
 #endif
 
-// Scratch for the split-K tail (fp32 slabs); without it every tile runs whole.  Host-side registry, not on the data path: one DEFAULT
-// scratch per device (ce_set_gemm_workspace, registered for the current device) and, for callers that run GEMMs on several streams of
-// one device at once, one scratch per (device, stream) (ce_set_gemm_workspace_stream) - a launch uses its stream's own scratch when one
-// is registered and the device default otherwise, so two streams never share slabs unless the caller registered nothing for them.
-namespace {
-struct WsSlot {
-  float* ptr = nullptr;
-  size_t bytes = 0;
-};
-struct WsStream {
-  int dev = -1;
-  hipStream_t stream = nullptr;
-  WsSlot ws;
-};
-constexpr int WS_STREAMS = 32;
-WsSlot g_ws_dev[CE_MAX_DEVICES];
-WsStream g_ws_stream[WS_STREAMS];
-int g_ws_stream_next = 0;
-int g_cus_dev[CE_MAX_DEVICES] = {};
-std::mutex g_ws_mutex;
-int device_cus(int slot) {
-  if (g_cus_dev[slot] == 0) {
-    int dev = 0, cus = 0;
-    g_cus_dev[slot] = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) ? cus : 256;
-  }
-  return g_cus_dev[slot];
-}
-}  // namespace
-
-CE_API int ce_set_gemm_workspace(void* ptr, size_t bytes) {
-  std::lock_guard<std::mutex> lock(g_ws_mutex);
-  const int slot = ce_device_slot();
-  g_ws_dev[slot].ptr = reinterpret_cast<float*>(ptr);
-  g_ws_dev[slot].bytes = ptr ? bytes : 0;
-  (void)device_cus(slot);
-  return CE_OK;
-}
-
-CE_API int ce_set_gemm_workspace_stream(hipStream_t stream, void* ptr, size_t bytes) {
-  std::lock_guard<std::mutex> lock(g_ws_mutex);
-  const int slot = ce_device_slot();
-  int at = -1;
-  for (int i = 0; i < WS_STREAMS; ++i)
-    if (g_ws_stream[i].dev == slot && g_ws_stream[i].stream == stream) at = i;
-  if (ptr == nullptr) {  // unregister: the stream falls back to the device default
-    if (at >= 0) g_ws_stream[at] = WsStream{};
-    return CE_OK;
-  }
-  if (at < 0) {
-    for (int i = 0; i < WS_STREAMS && at < 0; ++i)
-      if (g_ws_stream[i].dev < 0) at = i;
-    if (at < 0) at = g_ws_stream_next++ % WS_STREAMS;  // full: the oldest registration makes room (its stream uses the default again)
-  }
-  g_ws_stream[at].dev = slot;
-  g_ws_stream[at].stream = stream;
-  g_ws_stream[at].ws = WsSlot{reinterpret_cast<float*>(ptr), bytes};
-  (void)device_cus(slot);
-  return CE_OK;
-}
-
-// the scratch a launch on `stream` (current device) may use - for every large-tile main loop (this file, ce_gemm256w4.hip, ce_gemm384.hip,
-// ce_gemm_fp8w4.hip) and for the tile choice of ce_gemm.hip
-extern "C" void ce_gemm256_workspace(hipStream_t stream, float** ws, size_t* bytes, int* cus) {
-  std::lock_guard<std::mutex> lock(g_ws_mutex);
-  const int slot = ce_device_slot();
-  WsSlot w = g_ws_dev[slot];
-  for (int i = 0; i < WS_STREAMS; ++i)
-    if (g_ws_stream[i].dev == slot && g_ws_stream[i].stream == stream) w = g_ws_stream[i].ws;
-  *ws = w.ptr;
-  *bytes = w.bytes;
-  *cus = device_cus(slot);
-}
-
 extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
                                  const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, hipStream_t stream) {
+                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
+                                 hipStream_t stream) {
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const int nwg = tiles_m * tiles_n, kt = K / BK;
   // segmented operand: column k lives at base + (k / seg_k) * seg_stride + row * ld + k % seg_k (elements)
   uint32_t a_seg_magic = 0, a_seg_extra = 0, w_seg_magic = 0, w_seg_extra = 0;
   auto seg = [&](int seg_k, long long seg_stride, uint32_t& magic, uint32_t& extra_out) -> int {
     if (seg_k <= 0 || seg_k >= K) return CE_OK;
-    if (seg_k % BK) return CE_ERR_SHAPE;
-    const int tps = seg_k / BK;
-    magic = 65536u / (uint32_t)tps + 1u;
-    for (int t = 0; t < kt; ++t)
-      if ((int)(((uint32_t)t * magic) >> 16) != t / tps) return CE_ERR_SHAPE;
+    magic = ce_seg_magic(seg_k, BK, kt);
     const long long extra = (seg_stride - seg_k) * 2;  // bytes on top of the contiguous advance
-    if (extra < 0 || extra * (K / seg_k) >= (1ll << 32)) return CE_ERR_SHAPE;
+    if (!magic || extra < 0 || extra * (K / seg_k) >= (1ll << 32)) return CE_ERR_SHAPE;
     extra_out = (uint32_t)extra;
     return CE_OK;
   };
   if (int rc = seg(a_seg_k, a_seg_stride, a_seg_magic, a_seg_extra)) return rc;
   if (int rc = seg(w_seg_k, w_seg_stride, w_seg_magic, w_seg_extra)) return rc;
   // split-K only for the tail of the last, partially filled round of workgroups
-  float* g_ws = nullptr;
-  size_t g_ws_bytes = 0;
-  int g_cus = 256;
-  ce_gemm256_workspace(stream, &g_ws, &g_ws_bytes, &g_cus);
-  int tail = nwg % g_cus, split = 1;
-  if (tail > 0 && g_ws != nullptr) {
-    for (int s = std::min(g_cus / tail, 8); s >= 2; --s)
-      if (kt % (2 * s) == 0 && (size_t)tail * s * BM * BN * sizeof(float) <= g_ws_bytes) {
-        split = s;
-        break;
-      }
-  }
+  const int cus = ce_device_cus();
+  int tail = nwg % cus;
+  const int split = ce_split_k(tail, kt, cus, BM * BN * sizeof(float), ws ? (long long)ws_bytes : 0);
   if (split == 1) tail = 0;
   const int t_full2 = nwg - tail;
   dim3 grid(t_full2 + tail * split), block(512);
@@ -577,14 +488,14 @@ extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const fl
     if (staggered)                                                                                                    \
       hipLaunchKernelGGL((gemm_bf16_256<E, true>), grid, block, LDS_BYTES, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, \
                          bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n,    \
-                         t_full2, split, g_ws, a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra);                                             \
+                         t_full2, split, ws, a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra);                                             \
     else                                                                                                              \
       hipLaunchKernelGGL((gemm_bf16_256<E, false>), grid, block, LDS_BYTES, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, \
                          bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n,    \
-                         t_full2, split, g_ws, a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra);                                             \
+                         t_full2, split, ws, a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra);                                             \
     if (tail)                                                                                                         \
       hipLaunchKernelGGL((gemm256_reduce<E>), dim3(4 * tail), block, 128 * QROW, stream, (bf16*)C, bias, gate,        \
-                         (const bf16*)res, M, N, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, g_ws);      \
+                         (const bf16*)res, M, N, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws);      \
   } while (0)
   switch (epilogue) {
     case EPI_BIAS: CE_LAUNCH(EPI_BIAS); break;

@@ -21,8 +21,6 @@
 //    Hazards: a stage is overwritten only after a barrier that every wave reaches with its reads of that stage complete
 //    (the lgkmcnt(0) closing unit (t-1,1) precedes the barrier opening (t,0)); a stage is read only after the barrier that follows
 //    every wave's counted vmcnt for it.  Every piece has >= 2 units (NSA = 3: A pieces >= 3) between issue and first use.
-#include <algorithm>
-
 #include "ce_common.h"
 #include "ce_gemm_epi.h"
 
@@ -511,16 +509,16 @@ __global__ __launch_bounds__(256) void gemm256w4_reduce(bf16* __restrict__ C, co
 
 }  // namespace
 
-extern "C" void ce_gemm256_workspace(hipStream_t stream, float** ws, size_t* bytes, int* cus);
-
 // nsa: 3 = A ring of three K-tile stages (160 KiB of LDS), 2 = two (128 KiB), 1 = three stages and ONE barrier per K-tile
 extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
                                  const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, hipStream_t stream);
+                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
+                                 hipStream_t stream);
 
 static int w4_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate, const void* res, int M, int N,
                      int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int a_seg_k, long long a_seg_stride, int w_seg_k,
-                     long long w_seg_stride, int a_seg2_k, long long a_seg2_stride, int nsa, int ng, hipStream_t stream) {
+                     long long w_seg_stride, int a_seg2_k, long long a_seg2_stride, int nsa, int ng, float* ws, size_t ws_bytes,
+                     hipStream_t stream) {
   const bool seg2 = a_seg2_k > 0;
   if ((ng != 8 && ng != 4 && ng != 3) || (ng != 8 && !seg2)) return CE_ERR_ARG;
   if (seg2 && (a_seg_k <= 0 || a_seg2_k % a_seg_k || (epilogue != EPI_BIAS && epilogue != EPI_GATE_RES) || nsa != 2 ||
@@ -530,24 +528,20 @@ static int w4_launch(const void* A, const void* W, void* C, const float* bias, i
   // ... and stores through a 32-bit-offset buffer descriptor
   if (epilogue == EPI_GATE_RES && ((gate != nullptr && gate_rows > 0 && gate_rows < BM) || (long long)M * ldc * 2 >= (1ll << 32)))
     return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, w_seg_k,
-                             w_seg_stride, stream);
+                             w_seg_stride, ws, ws_bytes, stream);
   // (the register-direct epilogue of the plain 256 x 256 tile stores through 32-bit buffer offsets and reads four row biases at once)
   if (ng == 8 && ((long long)M * ldc * 2 >= (1ll << 32) || (epilogue == EPI_BIAS_ROW && (M & 3))))
     return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, w_seg_k,
-                             w_seg_stride, stream);
+                             w_seg_stride, ws, ws_bytes, stream);
   const int bn = 32 * ng;
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + bn - 1) / bn;
   const int nwg = tiles_m * tiles_n, kt = K / BK;
   uint32_t a_seg_magic = 0, a_seg_extra = 0, w_seg_magic = 0, w_seg_extra = 0;
   auto seg = [&](int seg_k, long long seg_stride, uint32_t& magic, uint32_t& extra_out) -> int {
     if (seg_k <= 0 || seg_k >= K) return CE_OK;
-    if (seg_k % BK) return CE_ERR_SHAPE;
-    const int tps = seg_k / BK;
-    magic = 65536u / (uint32_t)tps + 1u;
-    for (int t = 0; t < kt; ++t)
-      if ((int)(((uint32_t)t * magic) >> 16) != t / tps) return CE_ERR_SHAPE;
+    magic = ce_seg_magic(seg_k, BK, kt);
     const long long extra = (seg_stride - seg_k) * 2;
-    if (extra < 0 || extra * ((K + seg_k - 1) / seg_k) + (long long)K * 2 >= (1ll << 31)) return CE_ERR_SHAPE;  // the K-tile offset is a signed scalar
+    if (!magic || extra < 0 || extra * ((K + seg_k - 1) / seg_k) + (long long)K * 2 >= (1ll << 31)) return CE_ERR_SHAPE;  // the K-tile offset is a signed scalar
     extra_out = (uint32_t)extra;
     return CE_OK;
   };
@@ -555,28 +549,16 @@ static int w4_launch(const void* A, const void* W, void* C, const float* bias, i
   if (int rc = seg(w_seg_k, w_seg_stride, w_seg_magic, w_seg_extra)) return rc;
   uint32_t a_seg2_magic = 0, a_seg2_extra = 0;
   if (seg2 && a_seg2_k < K) {  // second level: every a_seg2_k columns the source jumps to a_seg2_stride (both in elements), nested in the first
-    if (a_seg2_k % BK) return CE_ERR_SHAPE;
-    const int tps = a_seg2_k / BK;
-    a_seg2_magic = 65536u / (uint32_t)tps + 1u;
-    for (int t = 0; t < kt; ++t)
-      if ((int)(((uint32_t)t * a_seg2_magic) >> 16) != t / tps) return CE_ERR_SHAPE;
+    a_seg2_magic = ce_seg_magic(a_seg2_k, BK, kt);
+    if (!a_seg2_magic) return CE_ERR_SHAPE;
     const long long extra = (a_seg2_stride - (long long)(a_seg2_k / a_seg_k) * a_seg_stride) * 2;
     const long long reach = ((long long)(K - 1) / a_seg2_k) * a_seg2_stride * 2 + (long long)(a_seg2_k / a_seg_k) * a_seg_stride * 2 + (long long)a_seg_k * 2;
     if (extra < 0 || reach >= (1ll << 31)) return CE_ERR_SHAPE;
     a_seg2_extra = (uint32_t)extra;
   }
-  float* g_ws = nullptr;
-  size_t g_ws_bytes = 0;
-  int g_cus = 256;
-  ce_gemm256_workspace(stream, &g_ws, &g_ws_bytes, &g_cus);
-  int tail = nwg % g_cus, split = 1;
-  if (tail > 0 && g_ws != nullptr && !seg2) {
-    for (int s = std::min(g_cus / tail, 8); s >= 2; --s)
-      if (kt % (2 * s) == 0 && (size_t)tail * s * BM * BN * sizeof(float) <= g_ws_bytes) {
-        split = s;
-        break;
-      }
-  }
+  const int cus = ce_device_cus();
+  int tail = nwg % cus;
+  const int split = seg2 ? 1 : ce_split_k(tail, kt, cus, BM * BN * sizeof(float), ws ? (long long)ws_bytes : 0);
   if (split == 1) tail = 0;
   const int t_full2 = nwg - tail;
   dim3 grid(t_full2 + tail * split), block(256);
@@ -598,7 +580,7 @@ static int w4_launch(const void* A, const void* W, void* C, const float* bias, i
     }
 #define CE_LAUNCH_SEG2(E, NGV, LDS)                                                                                                     \
   hipLaunchKernelGGL((gemm_bf16_w4<E, 2, false, true, NGV>), grid, block, LDS, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                     (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, g_ws, a_seg_magic,   \
+                     (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws, a_seg_magic,   \
                      a_seg_extra, w_seg_magic, w_seg_extra, a_seg2_magic, a_seg2_extra)
     if (epilogue == EPI_BIAS) {
       if (ng == 8) CE_LAUNCH_SEG2(EPI_BIAS, 8, lds2); else if (ng == 4) CE_LAUNCH_SEG2(EPI_BIAS, 4, lds2n); else CE_LAUNCH_SEG2(EPI_BIAS, 3, lds2m);
@@ -621,19 +603,19 @@ static int w4_launch(const void* A, const void* W, void* C, const float* bias, i
     }                                                                                                                      \
     if (nsa == 1)                                                                                                          \
       hipLaunchKernelGGL((gemm_bf16_w4<E, 3, true>), grid, block, lds3, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, g_ws, \
+                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws, \
                          a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra, 0u, 0u);                                      \
     else if (nsa == 3)                                                                                                     \
       hipLaunchKernelGGL((gemm_bf16_w4<E, 3, false>), grid, block, lds3, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, g_ws, \
+                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws, \
                          a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra, 0u, 0u);                                      \
     else                                                                                                                   \
       hipLaunchKernelGGL((gemm_bf16_w4<E, 2, false>), grid, block, lds2, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, g_ws, \
+                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws, \
                          a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra, 0u, 0u);                                      \
     if (tail)                                                                                                              \
       hipLaunchKernelGGL((gemm256w4_reduce<E>), dim3(4 * tail), block, 128 * QROW, stream, (bf16*)C, bias, gate,           \
-                         (const bf16*)res, M, N, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, g_ws);           \
+                         (const bf16*)res, M, N, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws);           \
   } while (0)
   switch (epilogue) {
     case EPI_BIAS: CE_LAUNCH(EPI_BIAS); break;
@@ -649,9 +631,10 @@ static int w4_launch(const void* A, const void* W, void* C, const float* bias, i
 
 extern "C" int ce_gemm256w4_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
                                    const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                                   int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, int nsa, hipStream_t stream) {
+                                   int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, int nsa, float* ws,
+                                   size_t ws_bytes, hipStream_t stream) {
   return w4_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, w_seg_k, w_seg_stride,
-                   0, 0, nsa, 8, stream);
+                   0, 0, nsa, 8, ws, ws_bytes, stream);
 }
 
 // A with TWO nested segment levels: column k of row m lives at A + (k / a_seg2_k) a_seg2_stride + ((k % a_seg2_k) / a_seg_k) a_seg_stride +
@@ -661,7 +644,7 @@ extern "C" int ce_gemm256w4_seg2_launch(const void* A, const void* W, void* C, c
                                         int K, int lda, int ldw, int ldc, int ldres, int a_seg_k, long long a_seg_stride, int a_seg2_k,
                                         long long a_seg2_stride, int n_tile, hipStream_t stream) {
   return w4_launch(A, W, C, bias, epilogue, nullptr, res, M, N, K, lda, ldw, ldc, ldres, 0, a_seg_k, a_seg_stride, 0, 0, a_seg2_k, a_seg2_stride,
-                   2, n_tile / 32, stream);
+                   2, n_tile / 32, nullptr, 0, stream);
 }
 
 // The split-K reduce of this file's slab layout for another producer (ce_gemm_fp8w4.hip: the same wave tiles and raster, slabs already

@@ -17,8 +17,6 @@
 //    The ONE barrier of a tile sits between groups 20 and 21, behind `vmcnt(0)` + `lgkmcnt(0)`: every fragment read of tile t has
 //    been issued and has completed by then (=> stage t % 2 may be overwritten by tile t + 2 from here on), and tile t + 1 has landed
 //    (its last piece was issued seven groups = ~900 MFMA cycles earlier) (=> its fragments may be read from here on).
-#include <algorithm>
-
 #include "ce_common.h"
 #include "ce_gemm_epi.h"
 
@@ -461,15 +459,15 @@ __global__ __launch_bounds__(256) void gemm384_reduce(bf16* __restrict__ C, cons
 
 }  // namespace
 
-extern "C" void ce_gemm256_workspace(hipStream_t stream, float** ws, size_t* bytes, int* cus);
 extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
                                  const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, hipStream_t stream);
+                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
+                                 hipStream_t stream);
 
 template <int NF>
 static int gemm384_launch_impl(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate, const void* res, int M, int N,
                                int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int a_seg_k, long long a_seg_stride, int w_seg_k,
-                               long long w_seg_stride, hipStream_t stream) {
+                               long long w_seg_stride, float* ws, size_t ws_bytes, hipStream_t stream) {
   constexpr int BM = T384<NF>::BM, STAGE = T384<NF>::STAGE;
   if (epilogue == EPI_BIAS_T) {  // (C is [N][ldc]; no other kernel stores the transpose: the dispatcher only comes here with a shape this one takes)
     if ((M & 7) || (long long)N * ldc * 2 >= (1ll << 32) || !bias) return CE_ERR_SHAPE;
@@ -477,36 +475,24 @@ static int gemm384_launch_impl(const void* A, const void* W, void* C, const floa
   if ((epilogue == EPI_GATE_RES && gate != nullptr && gate_rows > 0 && gate_rows < BM) || (long long)M * ldc * 2 >= (1ll << 32) ||
       (epilogue == EPI_BIAS_ROW && (M & 3)))  // (the register-direct epilogue stores through 32-bit buffer offsets and reads four row biases at once)
     return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, w_seg_k,
-                             w_seg_stride, stream);
+                             w_seg_stride, ws, ws_bytes, stream);
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const int nwg = tiles_m * tiles_n, kt = K / BK;
   uint32_t a_seg_magic = 0, a_seg_extra = 0, w_seg_magic = 0, w_seg_extra = 0;
   auto seg = [&](int seg_k, long long seg_stride, uint32_t& magic, uint32_t& extra_out) -> int {
     if (seg_k <= 0 || seg_k >= K) return CE_OK;
-    if (seg_k % BK) return CE_ERR_SHAPE;
-    const int tps = seg_k / BK;
-    magic = 65536u / (uint32_t)tps + 1u;
-    for (int t = 0; t < kt; ++t)
-      if ((int)(((uint32_t)t * magic) >> 16) != t / tps) return CE_ERR_SHAPE;
+    magic = ce_seg_magic(seg_k, BK, kt);
     const long long extra = (seg_stride - seg_k) * 2;
-    if (extra < 0 || extra * (K / seg_k) + (long long)K * 2 >= (1ll << 31)) return CE_ERR_SHAPE;
+    if (!magic || extra < 0 || extra * (K / seg_k) + (long long)K * 2 >= (1ll << 31)) return CE_ERR_SHAPE;
     extra_out = (uint32_t)extra;
     return CE_OK;
   };
   if (int rc = seg(a_seg_k, a_seg_stride, a_seg_magic, a_seg_extra)) return rc;
   if (int rc = seg(w_seg_k, w_seg_stride, w_seg_magic, w_seg_extra)) return rc;
-  float* g_ws = nullptr;
-  size_t g_ws_bytes = 0;
-  int g_cus = 256;
-  ce_gemm256_workspace(stream, &g_ws, &g_ws_bytes, &g_cus);
-  int tail = nwg % g_cus, split = 1;
-  if (tail > 0 && g_ws != nullptr && epilogue != EPI_BIAS_T) {  // (the transposed store has no reduce form: its last round runs whole)
-    for (int s = std::min(g_cus / tail, 8); s >= 2; --s)
-      if (kt % (2 * s) == 0 && (size_t)tail * s * BM * BN * sizeof(float) <= g_ws_bytes) {
-        split = s;
-        break;
-      }
-  }
+  const int cus = ce_device_cus();
+  int tail = nwg % cus;
+  // (the transposed store has no reduce form: its last round runs whole)
+  const int split = epilogue == EPI_BIAS_T ? 1 : ce_split_k(tail, kt, cus, BM * BN * sizeof(float), ws ? (long long)ws_bytes : 0);
   if (split == 1) tail = 0;
   const int t_full2 = nwg - tail;
   dim3 grid(t_full2 + tail * split), block(256);
@@ -521,11 +507,11 @@ static int gemm384_launch_impl(const void* A, const void* W, void* C, const floa
       attr_done[E] = true;                                                                                                 \
     }                                                                                                                      \
     hipLaunchKernelGGL((gemm_bf16_384<E, NF>), grid, block, lds, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                       (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, g_ws, \
+                       (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws, \
                        a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra);                                                \
     if (tail)                                                                                                              \
       hipLaunchKernelGGL((gemm384_reduce<E, NF>), dim3(4 * tail), block, 16 * NF * QROW, stream, (bf16*)C, bias, gate,     \
-                         (const bf16*)res, M, N, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, g_ws);           \
+                         (const bf16*)res, M, N, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws);           \
   } while (0)
   switch (epilogue) {
     case EPI_BIAS: CE_LAUNCH(EPI_BIAS); break;
@@ -541,7 +527,7 @@ static int gemm384_launch_impl(const void* A, const void* W, void* C, const floa
         t_done = true;
       }
       hipLaunchKernelGGL((gemm_bf16_384<EPI_BIAS_T, NF>), grid, block, lds, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, (const bf16*)res,
-                         M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, g_ws, a_seg_magic, a_seg_extra, w_seg_magic,
+                         M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws, a_seg_magic, a_seg_extra, w_seg_magic,
                          w_seg_extra);
       break;
     }
@@ -553,15 +539,17 @@ static int gemm384_launch_impl(const void* A, const void* W, void* C, const floa
 
 extern "C" int ce_gemm384_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
                                  const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, hipStream_t stream) {
+                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
+                                 hipStream_t stream) {
   return gemm384_launch_impl<12>(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, w_seg_k,
-                                 w_seg_stride, stream);
+                                 w_seg_stride, ws, ws_bytes, stream);
 }
 
 // the 288 x 256 macro tile (NF = 9): same kernel, 144 x 128 wave tiles
 extern "C" int ce_gemm288_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
                                  const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, hipStream_t stream) {
+                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
+                                 hipStream_t stream) {
   return gemm384_launch_impl<9>(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, w_seg_k,
-                                w_seg_stride, stream);
+                                w_seg_stride, ws, ws_bytes, stream);
 }

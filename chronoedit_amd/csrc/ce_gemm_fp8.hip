@@ -382,7 +382,7 @@ CE_API int ce_quant_rows_fp8(const void* x, void* q, float* scale, int M, int K,
 
 extern "C" int ce_gemm_fp8w4_launch(const void* Aq, const void* Wq, void* C, const float* sa, const float* sw, const float* bias,
                                     int epilogue, const float* gate, const void* res, int M, int N, int K, int lda, int ldw, int ldc,
-                                    int ldres, int gate_rows, hipStream_t stream);
+                                    int ldres, int gate_rows, float* ws, size_t ws_bytes, hipStream_t stream);
 
 // main loop of ce_gemm_fp8: 1 = one wave per SIMD (ce_gemm_fp8w4.hip; the default: +2 ... +8 % on the step's shapes,
 // profiles/r03_gemm_fp8_variants_ab.txt), 0 = the 8-wave / 4-phase loop of this file
@@ -397,7 +397,7 @@ CE_API int ce_set_gemm_fp8_variant(int v) {
 
 CE_API int ce_gemm_fp8(const void* Aq, const void* Wq, void* C, const float* sa, const float* sw, const float* bias, int epilogue,
                            const float* gate, const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres,
-                           int gate_rows, hipStream_t stream) {
+                           int gate_rows, void* ws, size_t ws_bytes, hipStream_t stream) {
   if (!Aq || !Wq || !C || !sa || !sw) return CE_ERR_ARG;
   if (M <= 0 || N <= 0 || K <= 0 || (K % (2 * BKB)) || (N & 7)) return CE_ERR_SHAPE;
   if ((lda & 15) || (ldw & 15) || (ldc & 7)) return CE_ERR_ALIGN;
@@ -406,7 +406,8 @@ CE_API int ce_gemm_fp8(const void* Aq, const void* Wq, void* C, const float* sa,
   // (the one-wave-per-SIMD loop's gated-residual epilogue holds ONE or TWO samples' gate rows per tile and stores through 32-bit offsets)
   const bool w4_gate_ok = epilogue != EPI_GATE_RES || ((gate == nullptr || gate_rows == 0 || gate_rows >= BM) && (long long)M * ldc * 2 < (1ll << 32));
   if (g_fp8_variant == 1 && w4_gate_ok && (epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_GATE_RES))
-    return ce_gemm_fp8w4_launch(Aq, Wq, C, sa, sw, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, stream);
+    return ce_gemm_fp8w4_launch(Aq, Wq, C, sa, sw, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, static_cast<float*>(ws), ws_bytes,
+                                stream);
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   dim3 grid(tiles_m * tiles_n), block(512);
   static bool attr_done_[CE_MAX_DEVICES][3] = {};

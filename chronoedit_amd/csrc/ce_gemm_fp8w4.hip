@@ -30,8 +30,6 @@
 // 8-byte load per lane, operand and K-tile (512 contiguous bytes per wave) brings all its scales, and op_sel picks fragment F & 3 out of
 // register F >> 2 - 0.8 % of the operand bytes, fetched one K-tile ahead into 8 registers.  (A first form - [row][4][K / 128], one dword
 // per fragment covering four K-tiles - needed 32 registers and spilled.)
-#include <algorithm>
-
 #include "ce_common.h"
 #include "ce_gemm_epi.h"
 
@@ -860,14 +858,23 @@ __global__ __launch_bounds__(256) void gemm_fp8w4_reduce_gelu_q(unsigned char* _
 
 }  // namespace
 
-extern "C" void ce_gemm256_workspace(hipStream_t stream, float** ws, size_t* bytes, int* cus);
 extern "C" int ce_gemm256w4_reduce_launch(int epilogue, void* C, const float* bias, const float* gate, const void* res, int M, int N, int ldc,
                                           int ldres, int gate_rows, int tiles_m, int tiles_n, int t_full, int split, const float* ws, int tail,
                                           hipStream_t stream);
 
+// The split-K plan of ce_split_k, kept only where it pays.  An fp8 round is short (1.7 us per K-tile): cutting the last round only pays when
+// the time it saves clearly exceeds what the slabs cost (256 KiB written and read back per piece at ~4 TB/s, plus the reduce launch).
+// Measured: 116 tail tiles of a K = 5120 product cut in two were 1.5 % SLOWER than run whole; 6 tiles cut in eight, or K = 13824, gain 3 %.
+static int fp8_split_k(int tail, int kt, const void* ws, size_t ws_bytes) {
+  const int split = ce_split_k(tail, kt, ce_device_cus(), BM * BN * sizeof(float), ws ? (long long)ws_bytes : 0);
+  if (split == 1) return 1;
+  const double saving_us = (1.0 - 1.0 / split) * kt * 1.7, slabs_us = (double)tail * split * 0.128 + 8.0;
+  return saving_us < 1.5 * slabs_us ? 1 : split;
+}
+
 static int fp8w4_launch(bool mx, const void* Aq, const void* Wq, void* C, const float* sa, const float* sw, const float* bias,
                         int epilogue, const float* gate, const void* res, int M, int N, int K, int lda, int ldw, int ldc,
-                        int ldres, int gate_rows, hipStream_t stream) {
+                        int ldres, int gate_rows, float* ws, size_t ws_bytes, hipStream_t stream) {
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const int nwg = tiles_m * tiles_n, kt = K / BKB;
   // (the prefetched gated-residual epilogue holds ONE or TWO samples' gate rows per tile and stores through 32-bit offsets)
@@ -877,25 +884,8 @@ static int fp8w4_launch(bool mx, const void* Aq, const void* Wq, void* C, const 
   // (register-direct epilogue: every form stores through a buffer descriptor's 32-bit offsets when C fits them)
   const bool gate_prefetch = (long long)M * ldc * 2 < (1ll << 32) && (epilogue != EPI_GATE_RES || gate == nullptr || gate_rows <= 0 || gate_rows >= BM);
 #endif
-  float* g_ws = nullptr;
-  size_t g_ws_bytes = 0;
-  int g_cus = 256;
-  ce_gemm256_workspace(stream, &g_ws, &g_ws_bytes, &g_cus);
-  int tail = nwg % g_cus, split = 1;
-  if (tail > 0 && g_ws != nullptr) {
-    for (int sp = std::min(g_cus / tail, 8); sp >= 2; --sp)
-      if (kt % (2 * sp) == 0 && (size_t)tail * sp * BM * BN * sizeof(float) <= g_ws_bytes) {
-        split = sp;
-        break;
-      }
-    // An fp8 round is short (1.7 us per K-tile): cutting the last round only pays when the time it saves clearly exceeds what the
-    // slabs cost (256 KiB written and read back per piece at ~4 TB/s, plus the reduce launch).  Measured: 116 tail tiles of a
-    // K = 5120 product cut in two were 1.5 % SLOWER than run whole; 6 tiles cut in eight, or K = 13824, gain 3 %.
-    if (split > 1) {
-      const double saving_us = (1.0 - 1.0 / split) * kt * 1.7, slabs_us = (double)tail * split * 0.128 + 8.0;
-      if (saving_us < 1.5 * slabs_us) split = 1;
-    }
-  }
+  int tail = nwg % ce_device_cus();
+  const int split = fp8_split_k(tail, kt, ws, ws_bytes);
   if (split == 1) tail = 0;
   const int t_full = nwg - tail;
   dim3 grid(t_full + tail * split), block(256);
@@ -912,13 +902,13 @@ static int fp8w4_launch(bool mx, const void* Aq, const void* Wq, void* C, const 
     }                                                                                                                         \
     if (mx && !gate_prefetch)                                                                                                 \
       hipLaunchKernelGGL((gemm_fp8_w4<E, true, false>), grid, block, lds, stream, (const unsigned char*)Aq, (const unsigned char*)Wq, (bf16*)C, sa, sw, \
-                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, g_ws, nullptr); \
+                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, ws, nullptr); \
     else if (mx)                                                                                                              \
       hipLaunchKernelGGL((gemm_fp8_w4<E, true>), grid, block, lds, stream, (const unsigned char*)Aq, (const unsigned char*)Wq, (bf16*)C, sa, sw, \
-                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, g_ws, nullptr); \
+                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, ws, nullptr); \
     else                                                                                                                      \
       hipLaunchKernelGGL((gemm_fp8_w4<E>), grid, block, lds, stream, (const unsigned char*)Aq, (const unsigned char*)Wq, (bf16*)C, sa, sw, \
-                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, g_ws, nullptr); \
+                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, ws, nullptr); \
   } while (0)
   switch (epilogue) {
     case EPI_BIAS: F8_LAUNCH(EPI_BIAS); break;
@@ -928,7 +918,7 @@ static int fp8w4_launch(bool mx, const void* Aq, const void* Wq, void* C, const 
   }
 #undef F8_LAUNCH
   if (tail) {
-    const int rc = ce_gemm256w4_reduce_launch(epilogue, C, bias, gate, res, M, N, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, g_ws,
+    const int rc = ce_gemm256w4_reduce_launch(epilogue, C, bias, gate, res, M, N, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, ws,
                                               tail, stream);
     if (rc != CE_OK) return rc;
   }
@@ -937,8 +927,8 @@ static int fp8w4_launch(bool mx, const void* Aq, const void* Wq, void* C, const 
 
 extern "C" int ce_gemm_fp8w4_launch(const void* Aq, const void* Wq, void* C, const float* sa, const float* sw, const float* bias,
                                     int epilogue, const float* gate, const void* res, int M, int N, int K, int lda, int ldw, int ldc,
-                                    int ldres, int gate_rows, hipStream_t stream) {
-  return fp8w4_launch(false, Aq, Wq, C, sa, sw, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, stream);
+                                    int ldres, int gate_rows, float* ws, size_t ws_bytes, hipStream_t stream) {
+  return fp8w4_launch(false, Aq, Wq, C, sa, sw, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, ws, ws_bytes, stream);
 }
 
 /* The MX form (header of this file): Aq [M][lda], Wq [N][ldw] e4m3 bytes; sa8 / sw8 E8M0 bytes in the tiled order
@@ -946,7 +936,7 @@ extern "C" int ce_gemm_fp8w4_launch(const void* Aq, const void* Wq, void* C, con
  * (r / 16) % 8 = exponent + 127), as ce_quant_rows_mxfp8 / ce_ln_affine_mxfp8 write them. */
 CE_API int ce_gemm_mxfp8(const void* Aq, const void* Wq, void* C, const void* sa8, const void* sw8, const float* bias, int epilogue,
                              const float* gate, const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                             hipStream_t stream) {
+                             void* ws, size_t ws_bytes, hipStream_t stream) {
   if (!Aq || !Wq || !C || !sa8 || !sw8) return CE_ERR_ARG;
   if (M <= 0 || N <= 0 || K <= 0 || (K % (2 * BKB)) || (N & 7)) return CE_ERR_SHAPE;
   if ((lda & 15) || (ldw & 15) || (ldc & 7)) return CE_ERR_ALIGN;
@@ -954,35 +944,21 @@ CE_API int ce_gemm_mxfp8(const void* Aq, const void* Wq, void* C, const void* sa
   if (epilogue == EPI_GATE_RES && (!res || (ldres & 7))) return CE_ERR_ARG;
   if (epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU && epilogue != EPI_GATE_RES) return CE_ERR_ARG;
   return fp8w4_launch(true, Aq, Wq, C, reinterpret_cast<const float*>(sa8), reinterpret_cast<const float*>(sw8), bias, epilogue, gate, res, M, N, K,
-                      lda, ldw, ldc, ldres, gate_rows, stream);
+                      lda, ldw, ldc, ldres, gate_rows, static_cast<float*>(ws), ws_bytes, stream);
 }
 
 /* bias + tanh GELU with the MX quantisation of the result fused into the epilogue (include/chronoedit_hip.h); the split-K tail of a
  * partially filled last round goes through gemm_fp8w4_reduce_gelu_q. */
 CE_API int ce_gemm_mxfp8_gelu_quant(const void* Aq, const void* Wq, const void* sa8, const void* sw8, const float* bias, void* q_out, void* qs_out,
-                                        int M, int N, int K, int lda, int ldw, int ldq, hipStream_t stream) {
+                                        int M, int N, int K, int lda, int ldw, int ldq, void* ws, size_t ws_bytes, hipStream_t stream) {
   if (!Aq || !Wq || !sa8 || !sw8 || !q_out || !qs_out) return CE_ERR_ARG;
   if (M <= 0 || N <= 0 || K <= 0 || (K % (2 * BKB)) || (N & 127)) return CE_ERR_SHAPE;
   if ((lda & 15) || (ldw & 15) || (ldq & 7)) return CE_ERR_ALIGN;
   if ((long long)M * lda >= (1ll << 32) || (long long)N * ldw >= (1ll << 32)) return CE_ERR_SHAPE;
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const int nwg = tiles_m * tiles_n, kt = K / BKB;
-  float* g_ws = nullptr;
-  size_t g_ws_bytes = 0;
-  int g_cus = 256;
-  ce_gemm256_workspace(stream, &g_ws, &g_ws_bytes, &g_cus);
-  int tail = nwg % g_cus, split = 1;
-  if (tail > 0 && g_ws != nullptr) {  // (the heuristics of fp8w4_launch)
-    for (int sp = std::min(g_cus / tail, 8); sp >= 2; --sp)
-      if (kt % (2 * sp) == 0 && (size_t)tail * sp * BM * BN * sizeof(float) <= g_ws_bytes) {
-        split = sp;
-        break;
-      }
-    if (split > 1) {
-      const double saving_us = (1.0 - 1.0 / split) * kt * 1.7, slabs_us = (double)tail * split * 0.128 + 8.0;
-      if (saving_us < 1.5 * slabs_us) split = 1;
-    }
-  }
+  int tail = nwg % ce_device_cus();
+  const int split = fp8_split_k(tail, kt, ws, ws_bytes);
   if (split == 1) tail = 0;
   const int t_full = nwg - tail;
   static bool done_[CE_MAX_DEVICES] = {};
@@ -995,14 +971,14 @@ CE_API int ce_gemm_mxfp8_gelu_quant(const void* Aq, const void* Wq, const void* 
   if ((long long)M * ldq < (1ll << 32))
     hipLaunchKernelGGL((gemm_fp8_w4<EPI_BIAS_GELU_Q, true>), dim3(t_full + tail * split), dim3(256), LDS_BYTES, stream, (const unsigned char*)Aq,
                        (const unsigned char*)Wq, (bf16*)q_out, reinterpret_cast<const float*>(sa8), reinterpret_cast<const float*>(sw8), bias, nullptr,
-                       nullptr, M, N, K, lda, ldw, ldq, 0, 0, tiles_m, tiles_n, t_full, split, g_ws, (unsigned char*)qs_out);
+                       nullptr, M, N, K, lda, ldw, ldq, 0, 0, tiles_m, tiles_n, t_full, split, static_cast<float*>(ws), (unsigned char*)qs_out);
   else  // (a q_out beyond 32-bit byte offsets: 64-bit store addresses)
     hipLaunchKernelGGL((gemm_fp8_w4<EPI_BIAS_GELU_Q, true, false>), dim3(t_full + tail * split), dim3(256), LDS_BYTES, stream, (const unsigned char*)Aq,
                        (const unsigned char*)Wq, (bf16*)q_out, reinterpret_cast<const float*>(sa8), reinterpret_cast<const float*>(sw8), bias, nullptr,
-                       nullptr, M, N, K, lda, ldw, ldq, 0, 0, tiles_m, tiles_n, t_full, split, g_ws, (unsigned char*)qs_out);
+                       nullptr, M, N, K, lda, ldw, ldq, 0, 0, tiles_m, tiles_n, t_full, split, static_cast<float*>(ws), (unsigned char*)qs_out);
   if (tail)
     hipLaunchKernelGGL(gemm_fp8w4_reduce_gelu_q, dim3(4 * tail), dim3(256), 0, stream, (unsigned char*)q_out, (unsigned char*)qs_out, bias, M, N, ldq,
-                       tiles_m, tiles_n, t_full, split, g_ws);
+                       tiles_m, tiles_n, t_full, split, static_cast<const float*>(ws));
   return (int)hipGetLastError();
 }
 

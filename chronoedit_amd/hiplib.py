@@ -2,7 +2,7 @@
 
 The library is built in-tree (``chronoedit_amd/lib/``) with ``hipcc --offload-arch=gfx950`` so that
 it travels with the source tree; nothing is JIT-compiled at run time.  Loading fails loudly when
-the library is missing or lacks a symbol declared in include/chronoedit_hip.h.
+the library is missing or its exported entry points are not exactly those of include/chronoedit_hip.h.
 """
 from __future__ import annotations
 
@@ -35,9 +35,7 @@ _P, _I, _F = _c.c_void_p, _c.c_int, _c.c_float
 SIGNATURES: Dict[str, List] = {
     "ce_ln_affine_bf16": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P],
     "ce_rmsnorm_rope_bf16": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
-    "ce_gemm_bf16": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ce_gemm_aseg_bf16": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _c.c_longlong, _P],
-    "ce_gemm_seg_bf16": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _c.c_longlong, _I, _c.c_longlong, _P],
+    "ce_gemm_bf16": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _c.c_longlong, _I, _c.c_longlong, _P, _c.c_size_t, _P],
     "ce_rmsnorm_rope_mxfp8": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _F, _P],
     "ce_v_mxfp8_transpose": [_P, _I, _P, _P, _I, _I, _I, _I, _P],
     "ce_attention_mxfp8": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -45,8 +43,6 @@ SIGNATURES: Dict[str, List] = {
     "ce_attention_mxfp8_add": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "ce_rope_scatter_bf16": [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _F, _I, _P],
     "ce_patchify_rows_bf16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ce_set_gemm_workspace": [_P, ctypes.c_size_t],
-    "ce_set_gemm_workspace_stream": [_P, _P, ctypes.c_size_t],
     "ce_comm_load": [ctypes.c_char_p],
     "ce_comm_unique_id": [_P],
     "ce_comm_init": [ctypes.POINTER(ctypes.c_void_p), _P, _I, _I],
@@ -55,12 +51,12 @@ SIGNATURES: Dict[str, List] = {
     "ce_comm_all_gather": [_P, _P, _P, ctypes.c_size_t, _P],
     "ce_ln_affine_fp8": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P],
     "ce_quant_rows_fp8": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "ce_gemm_fp8": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "ce_gemm_fp8": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
     "ce_quant_rows_mxfp8": [_P, _P, _P, _I, _I, _I, _I, _P],
     "ce_quant_rows_mxfp8_w": [_P, _P, _P, _I, _I, _I, _I, _P],
     "ce_ln_affine_mxfp8": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P],
-    "ce_gemm_mxfp8": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ce_gemm_mxfp8_gelu_quant": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ce_gemm_mxfp8": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
+    "ce_gemm_mxfp8_gelu_quant": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
     "ce_gemm_batched_bf16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I] + [ctypes.c_longlong] * 6 + [_P],
     "ce_im2col_patch2d_bf16": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "ce_gather_rows_bf16": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -181,15 +177,20 @@ def _open(path: str, diag: bool) -> ctypes.CDLL:
     # DT_NEEDED then resolves to that copy.  Loaded the other way round (this library before `import torch`) the process holds
     # two runtimes, and a kernel launched through one on a stream of the other fails with hipErrorNoDevice (100).
     import torch  # noqa: F401
+    # exactly the header's entry points: a build of another ABI (e.g. a stale one loaded through CE_HIPLIB_PATH) may export the same names
+    # with other argument lists, and would be called with shifted arguments.  (The selectors of a diagnostic build are no other ABI: load()
+    # refuses that build as the product unless asked for it.)
+    declared, selectors = set(header_symbols()), set(header_symbols(diag=True))
+    if diag:
+        declared |= selectors
+    exported = {s for s in exported_symbols(path) if s.startswith("ce_")}
+    missing, unknown = declared - exported, exported - declared - selectors
+    if missing or unknown:
+        raise RuntimeError(f"{path} does not match include/chronoedit_hip{'_diag' if diag else ''}.h: missing {sorted(missing)}, "
+                           f"not declared {sorted(unknown)}")
     lib = ctypes.CDLL(path)
-    sigs = dict(SIGNATURES, **(DIAG_SIGNATURES if diag else {}))
-    for name in header_symbols() + (header_symbols(diag=True) if diag else []):
-        if not hasattr(lib, name):
-            raise RuntimeError(f"{path} does not export {name} declared in include/chronoedit_hip{'_diag' if diag else ''}.h")
-    for name, argtypes in sigs.items():
-        fn = getattr(lib, name, None)
-        if fn is None:
-            raise RuntimeError(f"{path} does not export {name}")
+    for name, argtypes in dict(SIGNATURES, **(DIAG_SIGNATURES if diag else {})).items():
+        fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = _c.c_int
     return lib

@@ -53,7 +53,6 @@ def force_diagnostics(on: bool = True) -> None:
     want = hiplib.load_diagnostics() if (_force_diag or any(_knobs[k] != _KNOB_DEFAULTS[k] for k in _knobs)) else _product
     if want is not _lib:
         _lib = want
-        _gemm_ws.pop("active", None)
 
 
 def attention_exact_route_hits(reset: bool = True):
@@ -72,7 +71,6 @@ def _set_knob(symbol: str, v: int) -> int:
     want = diag if (_force_diag or any(_knobs[k] != _KNOB_DEFAULTS[k] for k in _knobs)) else _product
     if want is not _lib:
         _lib = want
-        _gemm_ws.pop("active", None)  # the split-K scratch registry is per library: re-register with the one launches now go through
     return prev
 
 
@@ -192,7 +190,7 @@ def rmsnorm_rope_(x: torch.Tensor, w: torch.Tensor, cos_sin: Optional[torch.Tens
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
          epilogue: int = EPI_BIAS, gate: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, gate_rows: int = 0):
     """out[M,N] = epilogue(a[M,K] @ w[N,K]^T + bias).  gate [N] or, with gate_rows > 0, [M/gate_rows, N] (one per sample).
-    a may be a 3-D [S, M, K/S] tensor (contiguous): the K-segmented operand an all-to-all leaves behind (ce_gemm_aseg_bf16).
+    a may be a 3-D [S, M, K/S] tensor (contiguous): the K-segmented operand an all-to-all leaves behind (a_seg_k of ce_gemm_bf16).
     epilogue EPI_BIAS_T: out is [N, M] and receives the TRANSPOSE of a @ w^T + bias[n] (CE_EPI_BIAS_T)."""
     _dev(a, torch.bfloat16, "a"), _dev(w, torch.bfloat16, "w")
     a_seg_k, a_seg_stride = 0, 0
@@ -224,10 +222,10 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: Op
         if gate is not None:
             _dev(gate, torch.float32, "gate")
             assert gate.is_contiguous() and gate.numel() == (N if gate_rows <= 0 else (M + gate_rows - 1) // gate_rows * N)
-    ensure_gemm_workspace(a.device)
+    ws, ws_bytes = _gemm_scratch(a.device)
     st = _prof_begin()
-    _check(lib().ce_gemm_aseg_bf16(_ptr(a), _ptr(w), _ptr(out), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K, lda, ldw, ldc,
-                                   ldres, int(gate_rows), int(a_seg_k), int(a_seg_stride), _stream()), "ce_gemm_bf16")
+    _check(lib().ce_gemm_bf16(_ptr(a), _ptr(w), _ptr(out), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K, lda, ldw, ldc, ldres,
+                              int(gate_rows), int(a_seg_k), int(a_seg_stride), 0, 0, ws, ws_bytes, _stream()), "ce_gemm_bf16")
     _prof_end(st, f"gemm_{M}x{N}x{K}_epi{epilogue}", 2.0 * M * N * K)
     return out
 
@@ -262,56 +260,49 @@ def rope_scatter(x: torch.Tensor, cols, weights, D: int, world: int, cos_sin: Op
     return out
 
 
-_gemm_ws = {}
 _gemm_split = True
 GEMM_WS_BYTES = 256 * 384 * 256 * 4  # one fp32 slab of the LARGEST macro tile (384 x 256) per CU: any split-K tail the dispatcher may choose fits (96 MiB; round 6 - with 64 MiB the
 # 384-row tile could not cut its tail at M = 7 200 and lost FFN-down by 13 %: profiles/r06_gemm_tile_choice_m7200.txt)
 
 
-GEMM_WS_STREAMS = 8  # streams per device that get a scratch of their own; further ones share the device default
+GEMM_WS_STREAMS = 8  # streams per device that get a scratch of their own; further ones evict the least recently used
+_gemm_default = {}  # device index -> (the first stream a GEMM ran on, that device's default scratch)
+_gemm_own = {}      # (device index, stream) -> the scratch of a further stream, least recently used first (dicts keep insertion order)
 
 
-def ensure_gemm_workspace(device: torch.device) -> None:
-    """Hand the library its split-K scratch: one default buffer per device (allocated once, outside any graph capture) and, for every
-    further stream GEMMs are launched on, a buffer of that stream's own (ce_set_gemm_workspace_stream) - concurrent streams never share
-    slabs.  A stream that is capturing a graph uses the default (nothing is allocated under capture; captures of one device do not
-    overlap in this package)."""
+def _gemm_scratch(device: torch.device):
+    """The split-K scratch (pointer, bytes) a GEMM launched now on the current stream of `device` is given - (None, 0) turns the split off.
+    The first stream of a device uses the device's default buffer; every further stream gets a buffer of its own, so concurrent streams
+    never share slabs.  A stream that is capturing a graph and has no buffer of its own uses the default (nothing is allocated under capture;
+    captures of one device do not overlap in this package)."""
+    if not _gemm_split:
+        return None, 0
     dev = device.index if device.index is not None else torch.cuda.current_device()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    key = (dev, _gemm_split, stream)
-    if _gemm_ws.get("active") == key:
-        return
-    if _gemm_split:
-        buf = _gemm_ws.get(dev)
-        first = _gemm_ws.get(("first_stream", dev))
-        if buf is None:
-            buf = torch.empty(GEMM_WS_BYTES, dtype=torch.uint8, device=device)
-            _gemm_ws[dev] = buf
-            _gemm_ws[("first_stream", dev)] = first = stream
-        with torch.cuda.device(dev):
-            _check(lib().ce_set_gemm_workspace(buf.data_ptr(), buf.numel()), "ce_set_gemm_workspace")
-            if stream != first and (dev, stream) in _gemm_ws:
-                _gemm_ws[(dev, stream)] = _gemm_ws.pop((dev, stream))  # most recently used last (dicts keep insertion order)
-            elif stream != first and not torch.cuda.is_current_stream_capturing():
-                mine = [k for k in _gemm_ws if isinstance(k, tuple) and len(k) == 2 and k[0] == dev]  # (dev, stream) keys, least recently used first
-                if len(mine) >= GEMM_WS_STREAMS:
-                    # the cap is reached: the LEAST RECENTLY USED stream is unregistered (it falls back to the device default if it ever comes
-                    # back) and its scratch is DROPPED, not handed on: split-K partials of GEMMs still queued on that stream may be in it, and
-                    # nothing orders the new stream behind them.  The caching allocator returns the block to the pool of the stream it was
-                    # allocated on, so whatever reuses it is ordered behind that stream's queued work.
-                    oldest = mine[0]
-                    del _gemm_ws[oldest]
-                    _check(lib().ce_set_gemm_workspace_stream(oldest[1], None, 0), "ce_set_gemm_workspace_stream")
-                own = torch.empty(GEMM_WS_BYTES, dtype=torch.uint8, device=device)
-                _gemm_ws[(dev, stream)] = own
-                _check(lib().ce_set_gemm_workspace_stream(stream, own.data_ptr(), own.numel()), "ce_set_gemm_workspace_stream")
+    first = _gemm_default.get(dev)
+    if first is not None and first[0] == stream:
+        buf = first[1]
+    elif (dev, stream) in _gemm_own:
+        buf = _gemm_own[(dev, stream)] = _gemm_own.pop((dev, stream))  # most recently used last
     else:
         with torch.cuda.device(dev):
-            _check(lib().ce_set_gemm_workspace(None, 0), "ce_set_gemm_workspace")
-            for k in [k for k in _gemm_ws if isinstance(k, tuple) and len(k) == 2 and k[0] == dev]:
-                _check(lib().ce_set_gemm_workspace_stream(k[1], None, 0), "ce_set_gemm_workspace_stream")
-                del _gemm_ws[k]
-    _gemm_ws["active"] = key
+            capturing = torch.cuda.is_current_stream_capturing()
+        if capturing:
+            if first is None:
+                return None, 0
+            buf = first[1]
+        elif first is None:
+            buf = torch.empty(GEMM_WS_BYTES, dtype=torch.uint8, device=dev)
+            _gemm_default[dev] = (stream, buf)
+        else:
+            mine = [k for k in _gemm_own if k[0] == dev]
+            if len(mine) >= GEMM_WS_STREAMS:
+                # the LEAST RECENTLY USED stream's scratch is DROPPED, not handed on: split-K partials of GEMMs still queued on that stream
+                # may be in it, and nothing orders the new stream behind them.  The caching allocator returns the block to the pool of the
+                # stream it was allocated on, so whatever reuses it is ordered behind that stream's queued work.
+                del _gemm_own[mine[0]]
+            buf = _gemm_own[(dev, stream)] = torch.empty(GEMM_WS_BYTES, dtype=torch.uint8, device=dev)
+    return buf.data_ptr(), buf.numel()
 
 
 def set_gemm_split(on: bool) -> bool:
@@ -742,8 +733,9 @@ def gemm_f32(a: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = Non
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
     _, _, ldc = _rows(out, "out")
-    _check(lib().ce_gemm_bf16(_ptr(a), _ptr(w), _ptr(out), _ptr(None), 4, _ptr(None), _ptr(None), M, N, K, lda, ldw, ldc, 0, 0,
-                              _stream()), "ce_gemm_bf16(f32)")
+    ws, ws_bytes = _gemm_scratch(a.device)
+    _check(lib().ce_gemm_bf16(_ptr(a), _ptr(w), _ptr(out), _ptr(None), 4, _ptr(None), _ptr(None), M, N, K, lda, ldw, ldc, 0, 0, 0, 0, 0, 0,
+                              ws, ws_bytes, _stream()), "ce_gemm_bf16(f32)")
     return out
 
 
@@ -925,7 +917,6 @@ def gemm_mxfp8(aq: torch.Tensor, sa: torch.Tensor, wq: torch.Tensor, sw: torch.T
         out = torch.empty((M, N), dtype=torch.bfloat16, device=aq.device)
     _dev(out, torch.bfloat16, "out")
     _, _, ldc = _rows(out, "out")
-    ensure_gemm_workspace(aq.device)
     ldres = 0
     if epilogue == EPI_GATE_RES:
         if res is None:
@@ -934,9 +925,10 @@ def gemm_mxfp8(aq: torch.Tensor, sa: torch.Tensor, wq: torch.Tensor, sw: torch.T
         _, _, ldres = _rows(res, "res")
         if gate is not None:
             _dev(gate, torch.float32, "gate")
+    ws, ws_bytes = _gemm_scratch(aq.device)
     st = _prof_begin()
     _check(lib().ce_gemm_mxfp8(_ptr(aq), _ptr(wq), _ptr(out), _ptr(sa), _ptr(sw), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K, lda, ldw,
-                               ldc, ldres, int(gate_rows), _stream()), "ce_gemm_mxfp8")
+                               ldc, ldres, int(gate_rows), ws, ws_bytes, _stream()), "ce_gemm_mxfp8")
     _prof_end(st, f"gemm_mxfp8_{M}x{N}x{K}_epi{epilogue}", 2.0 * M * N * K)
     return out
 
@@ -954,10 +946,10 @@ def gemm_mxfp8_gelu_quant(aq: torch.Tensor, sa: torch.Tensor, wq: torch.Tensor, 
         raise ValueError("gemm_mxfp8_gelu_quant: operand / scale shapes do not match")
     if bias is not None:
         _dev(bias, torch.float32, "bias")
-    ensure_gemm_workspace(aq.device)  # (its launcher cuts the last round along K like the others: the stream's own scratch must be registered)
+    ws, ws_bytes = _gemm_scratch(aq.device)
     st = _prof_begin()
     _check(lib().ce_gemm_mxfp8_gelu_quant(_ptr(aq), _ptr(wq), _ptr(sa), _ptr(sw), _ptr(bias), _ptr(out), _ptr(scale), M, N, K, lda, ldw, ldq,
-                                          _stream()), "ce_gemm_mxfp8_gelu_quant")
+                                          ws, ws_bytes, _stream()), "ce_gemm_mxfp8_gelu_quant")
     _prof_end(st, f"gemm_mxfp8_{M}x{N}x{K}_gelu_quant", 2.0 * M * N * K)
     return out, scale
 
@@ -982,7 +974,6 @@ def gemm_fp8(aq: torch.Tensor, sa: torch.Tensor, wq: torch.Tensor, sw: torch.Ten
         out = torch.empty((M, N), dtype=torch.bfloat16, device=aq.device)
     _dev(out, torch.bfloat16, "out")
     _, _, ldc = _rows(out, "out")
-    ensure_gemm_workspace(aq.device)  # the one-wave-per-SIMD loop cuts a partially filled last round of tiles along K (as ce_gemm_bf16)
     ldres = 0
     if epilogue == EPI_GATE_RES:
         if res is None:
@@ -991,9 +982,10 @@ def gemm_fp8(aq: torch.Tensor, sa: torch.Tensor, wq: torch.Tensor, sw: torch.Ten
         _, _, ldres = _rows(res, "res")
         if gate is not None:
             _dev(gate, torch.float32, "gate")
+    ws, ws_bytes = _gemm_scratch(aq.device)  # the one-wave-per-SIMD loop cuts a partially filled last round of tiles along K (as ce_gemm_bf16)
     st = _prof_begin()
     _check(lib().ce_gemm_fp8(_ptr(aq), _ptr(wq), _ptr(out), _ptr(sa), _ptr(sw), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K,
-                             lda, ldw, ldc, ldres, int(gate_rows), _stream()), "ce_gemm_fp8")
+                             lda, ldw, ldc, ldres, int(gate_rows), ws, ws_bytes, _stream()), "ce_gemm_fp8")
     _prof_end(st, f"gemm_fp8_{M}x{N}x{K}_epi{epilogue}", 2.0 * M * N * K)
     return out
 

@@ -15,7 +15,7 @@ MI355X layout (no permute().contiguous() passes anywhere on the path):
     rank-ordered), so the attention kernel reads q / k / v as strided views of it;
   * the attention output [global token][D/W] is already the send buffer of the second exchange (chunk t = rows of rank t);
   * its receive buffer [src rank = head group][local row][D/W] is consumed in place by the out-projection GEMM as a
-    K-segmented A operand (`ce_gemm_aseg_bf16`).
+    K-segmented A operand (`a_seg_k` of `ce_gemm_bf16`).
 Several samples per forward (the guidance pair batched, B = 2): local rows are [sample][local token], so the receive buffers are
 [src rank][sample][local token] - token g of sample b in row (g // n) * B * n + b * n + g % n.  The attention kernel and the V
 transposer take that BLOCKED layout as it is (`ce_attention_vt_blocked_bf16`, `ce_v_transpose_blocked_bf16`: one scalar

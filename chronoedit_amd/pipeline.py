@@ -168,7 +168,7 @@ class GraphedDenoiser:
             # lazy initialisations (packed weights, workspaces, function attributes) must not happen under capture: run the CURRENT step
             # eagerly, for real, on a side stream as torch asks of anything that precedes a capture
             saved = None if keep_warmup_step else (latents.clone(), [m.clone() for m in scheduler.model_outputs], scheduler.last_sample.clone())
-            side = _warmup_stream(dev)  # ONE long-lived side stream per device: every stream GEMMs run on gets a split-K scratch of its own (ops.ensure_gemm_workspace)
+            side = _warmup_stream(dev)  # ONE long-lived side stream per device: every stream GEMMs run on gets a split-K scratch of its own (ops._gemm_scratch)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 self._body()

@@ -673,7 +673,7 @@ class DiTEngine:
         if "o1" in self.fp8_set:  # the row quantiser wants plain rows: secondary mode, one gather pass
             ws.att.copy_(sp.merge_heads_reference(y))
             return ws.att
-        return y  # K-segmented A operand of the out-projection (ce_gemm_aseg_bf16)
+        return y  # K-segmented A operand of the out-projection (a_seg_k of ce_gemm_bf16)
 
     # -- workspaces --------------------------------------------------------------------
     def _workspace(self, N: int):

@@ -61,51 +61,33 @@ int ce_rmsnorm_rope_bf16(void* x, const float* w, void* x2, const float* w2, con
 /* C[M,N] = epilogue(A[M,K] . W[N,K]^T + bias[N]); bf16 in/out, fp32 accumulate on MFMA.
  * K % 64 == 0, N % 8 == 0; res may alias C.  gate_rows > 0: row m uses gate[(m / gate_rows) * N + n] (one gate
  * vector per sample when several samples' tokens are stacked along M); gate_rows == 0: one gate vector.  Replaces every nn.Linear on the path
- * (transformer_chronoedit.py:58-60,84-86,106, FeedForward :262, patch_embedding :429, proj_out :461). */
+ * (transformer_chronoedit.py:58-60,84-86,106, FeedForward :262, patch_embedding :429, proj_out :461).
+ * K-SEGMENTED A operand: column k of A lives at A + (k / a_seg_k) * a_seg_stride + m * lda + k % a_seg_k (elements; a_seg_k % 64 == 0,
+ * K % a_seg_k == 0; a_seg_k == 0: plain row-major A).  This is the layout the second Ulysses all-to-all leaves the attention output in -
+ * [source rank = head group][local token][D / W] - so the out-projection reads it in place instead of a gather pass (reference design:
+ * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355; the reference's xfuser path materialises the gathered tensor).
+ * K-segmented W likewise (w_seg_k, w_seg_stride).  seg_k = 64 and ld = 64 is the K-slab-major packing [K/64][rows][64]: every 16 KiB
+ * half-tile the 256-tile kernel streams by LDS-DMA is then ONE contiguous block (measured L2->LDS stream rate 21.7 vs 18.3 TB/s for the
+ * row-strided form, profiles/r02_l2_pattern_probe.txt).  Segmented W needs the 256-tile kernel (K % 128 == 0), else CE_ERR_SHAPE.
+ * ws / ws_bytes: the split-K scratch.  The large-tile kernels cut the tiles that would run as a partially filled last round of workgroups
+ * along K into fp32 slabs (256 KiB each for a 256 x 256 tile, 384 KiB for 384 x 256, at most one per CU), which a second launch sums and
+ * applies the epilogue to.  ws == NULL: no split, every tile runs whole; otherwise ws_bytes bounds the split (and enters the macro-tile
+ * choice, ce_gemm_bf16_tile_rows).  ws is device memory owned by the caller; the library never allocates and keeps no state a launch
+ * reads except its read-only tables.  The caller guarantees that no other stream uses ws while the launch is queued. */
 int ce_gemm_bf16(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate, const void* res,
-                 int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, hipStream_t stream);
-
-/* ce_gemm_bf16 with a K-SEGMENTED A operand: column k of A lives at A + (k / a_seg_k) * a_seg_stride + m * lda + k % a_seg_k
- * (elements; a_seg_k % 64 == 0, K % a_seg_k == 0; a_seg_k == 0 is ce_gemm_bf16).  This is the layout the second Ulysses
- * all-to-all leaves the attention output in - [source rank = head group][local token][D / W] - so the out-projection reads
- * it in place instead of a gather pass (reference design: chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355; the
- * reference's xfuser path materialises the gathered tensor). */
-int ce_gemm_aseg_bf16(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate, const void* res,
-                      int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int a_seg_k,
-                      long long a_seg_stride, hipStream_t stream);
-
-/* ... with BOTH operands K-segmented (w_seg_k, w_seg_stride as for A).  seg_k = 64 and ld = 64 is the K-slab-major packing
- * [K/64][rows][64]: every 16 KiB half-tile the 256-tile kernel streams by LDS-DMA is then ONE contiguous block (measured
- * L2->LDS stream rate 21.7 vs 18.3 TB/s for the row-strided form, profiles/r02_l2_pattern_probe.txt).  Segmented W needs the
- * 256-tile kernel (K % 128 == 0), else CE_ERR_SHAPE. */
-int ce_gemm_seg_bf16(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate, const void* res,
-                     int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int a_seg_k, long long a_seg_stride,
-                     int w_seg_k, long long w_seg_stride, hipStream_t stream);
+                 int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int a_seg_k, long long a_seg_stride,
+                 int w_seg_k, long long w_seg_stride, void* ws, size_t ws_bytes, hipStream_t stream);
 
 /* ---- The alternative kernel bodies (A/B partners of the measurement tools and the body-equivalence tests) are NOT selectable through this
- * library: libchronoedit_hip.so picks every kernel from the call's own shape and keeps no state a launch reads except the caller-registered
- * split-K scratch below.  The selectors live in a second build of the same sources, libchronoedit_hip_diag.so
- * (include/chronoedit_hip_diag.h, -DCE_DIAGNOSTICS), which tools/ and tests/ load beside this one. ---- */
+ * library: libchronoedit_hip.so picks every kernel from the call's own shape and keeps no state a launch reads.  The
+ * selectors live in a second build of the same sources, libchronoedit_hip_diag.so (include/chronoedit_hip_diag.h, -DCE_DIAGNOSTICS), which
+ * tools/ and tests/ load beside this one. ---- */
 
 
 /* Which macro tile ce_gemm_bf16 runs a LARGE product on when the choice is automatic: 384 or 288 (x 256, ce_gemm384.hip) or 256 (x 256,
  * ce_gemm256w4.hip) rows - the one whose tile count falls better on `cus` compute units (full rounds + the last round, which is cut
  * along K when the split-K workspace of `ws_bytes` bytes allows it).  A pure function: no device is touched.  0: invalid arguments. */
 int ce_gemm_bf16_tile_rows(int M, int N, int K, int cus, long long ws_bytes);
-
-/* Scratch for the split-K tail of ce_gemm_bf16's 256-tile kernel: the tiles that would run as a partially filled last
- * round of workgroups are cut along K into fp32 slabs (256 KiB each, at most one per CU) and summed by a second
- * launch that applies the epilogue.  ptr is device memory owned by the caller (NULL switches the split off; that is
- * the default); the library never allocates.  Registers the DEFAULT scratch of the CURRENT device (one per device: two devices
- * in one process never share slabs).  Host-side knob, returns CE_OK. */
-int ce_set_gemm_workspace(void* ptr, size_t bytes);
-
-/* The same for ONE stream of the current device: a launch on `stream` uses this scratch instead of the device default, so GEMMs
- * running concurrently on several streams of a device do not meet in one buffer (the library keeps no other state a launch writes).
- * ptr == NULL unregisters (the stream falls back to the device default).  At most 32 registrations are kept per process; a 33rd
- * replaces the oldest.  SURVEY section 8(b): "workspace passed by caller, library stateless" - the registry is caller-owned memory
- * keyed by the caller's own stream handles.  Returns CE_OK. */
-int ce_set_gemm_workspace_stream(hipStream_t stream, void* ptr, size_t bytes);
 
 /* O = softmax(Q K1^T * scale) V1 [ + softmax(Q K2^T * scale) V2 ], per head, head_dim == 128, bf16.
  * Each segment's result is rounded to bf16 before the add (SDPA output dtype).
@@ -319,10 +301,10 @@ int ce_ln_affine_fp8(const void* x, void* q, float* scale, const float* a, const
                      int ab_rows, int ab_stride, hipStream_t stream);
 
 /* C = epilogue(sa[m] * sw[n] * (Aq Wq^T)[m][n] + bias[n]); Aq [M][lda], Wq [N][ldw] fp8 e4m3 bytes, C bf16; K % 256 == 0.
- * Epilogues 0 (bias), 1 (bias + tanh GELU), 2 (gated residual) as ce_gemm_bf16. */
+ * Epilogues 0 (bias), 1 (bias + tanh GELU), 2 (gated residual) and the split-K scratch ws / ws_bytes as ce_gemm_bf16. */
 int ce_gemm_fp8(const void* Aq, const void* Wq, void* C, const float* sa, const float* sw, const float* bias, int epilogue,
                 const float* gate, const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
-                hipStream_t stream);
+                void* ws, size_t ws_bytes, hipStream_t stream);
 
 /* ---- the MX form of the fp8 GEMMs (round 4; BASELINE.json configs[4] "fp8 weights"): OCP MXFP8 operands - e4m3 elements with one E8M0
  * scale per 32 consecutive K elements of a row, scale = the smallest power of two with amax / scale <= 448 (2^-126 for an all-zero block:
@@ -349,16 +331,18 @@ int ce_ln_affine_mxfp8(const void* x, void* q, void* scale8, const float* a, con
 
 /* C = epilogue(sum_blocks 2^(ea + ew) (Aq Wq^T)_block + bias[n]); Aq [M][lda], Wq [N][ldw] e4m3 bytes with their scale buffers sa8 (A order) / sw8 (W order),
  * C bf16; K % 256 == 0, N % 8 == 0.  Epilogues 0 (bias), 1 (bias + tanh GELU), 2 (gated residual; gate rows per sample >= 256 or one gate)
- * as ce_gemm_bf16; the one-wave-per-SIMD main loop of csrc/ce_gemm_fp8w4.hip, split-K tail through the ce_set_gemm_workspace scratch. */
+ * as ce_gemm_bf16; the one-wave-per-SIMD main loop of csrc/ce_gemm_fp8w4.hip, split-K tail through ws / ws_bytes as ce_gemm_bf16. */
 int ce_gemm_mxfp8(const void* Aq, const void* Wq, void* C, const void* sa8, const void* sw8, const float* bias, int epilogue, const float* gate,
-                  const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, hipStream_t stream);
+                  const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, void* ws, size_t ws_bytes,
+                  hipStream_t stream);
 
 /* The FFN-up form: q_out / qs_out = ce_quant_rows_mxfp8( bf16( gelu_tanh( bf16( Aq Wq^T + bias ) ) ) ) - the bias + GELU epilogue emits the
  * NEXT GEMM's MX operand directly (bit-identical to ce_gemm_mxfp8 with epilogue 1 followed by ce_quant_rows_mxfp8; the bf16 matrix is
  * never written: an MX block is 32 consecutive output columns = four adjacent 16-byte chunks of the staged row, so its scale needs no
- * row-wide reduction).  q_out e4m3 bytes [M][ldq], qs_out the tiled scales of an [M][N] operand.  N % 128 == 0, K % 256 == 0. */
+ * row-wide reduction).  q_out e4m3 bytes [M][ldq], qs_out the tiled scales of an [M][N] operand.  N % 128 == 0, K % 256 == 0.
+ * Split-K scratch ws / ws_bytes as ce_gemm_bf16. */
 int ce_gemm_mxfp8_gelu_quant(const void* Aq, const void* Wq, const void* sa8, const void* sw8, const float* bias, void* q_out, void* qs_out,
-                             int M, int N, int K, int lda, int ldw, int ldq, hipStream_t stream);
+                             int M, int N, int K, int lda, int ldw, int ldq, void* ws, size_t ws_bytes, hipStream_t stream);
 
 
 /* ---- MXFP8 self-attention of the fp8 mode ("fp8 weights+attn", BASELINE.json configs[4]).  Contract (csrc/ce_attn_fp8.hip,

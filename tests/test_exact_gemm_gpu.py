@@ -74,6 +74,44 @@ def test_gemm_split_k_tails_are_exact_both_ways(M, N, K, variant_, split):
         ops.set_gemm_variant(old)
 
 
+def test_gemm_split_k_on_two_concurrent_streams_is_exact(split):
+    """Two side streams queue split-K products before any synchronisation, each with operands of its own: every stream is handed a scratch of
+    its own (ops._gemm_scratch), so neither meets the other's slabs - through the product library, with a selector forced (the diagnostic
+    library) and again after the reset, a stream keeping its scratch across the switches."""
+    from chronoedit_amd import ops
+    dev = torch.device("cuda", torch.cuda.current_device())
+    cases = []
+    for M, N, K in [(7200, 13824, 5120), (7200, 5120, 13824)]:  # both cut their last round along K, on the 384- and on the 256-row tile
+        g = _gen(M + N + K + 2)
+        a, w = int_rows(M, K, g), int_rows(N, K, g)
+        bias = int_vector(N, g)
+        cases.append((a, w, bias, bf16_rne(linear_f64(a, w, bias)), f"{M}x{N}x{K}"))
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    scratch = []
+    for variant_ in (-1, 4, -1):  # product library, a selector away from its default (diagnostic library), reset
+        old = ops.set_gemm_variant(variant_)
+        try:
+            ptrs = []
+            for s in streams:
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    ptrs.append(ops._gemm_scratch(dev)[0])
+            assert None not in ptrs and ptrs[0] != ptrs[1], ptrs
+            scratch.append(ptrs)
+            outs = []
+            for _ in range(3):
+                for s, (a, w, bias, _, _) in zip(streams, cases):
+                    with torch.cuda.stream(s):
+                        outs.append(ops.gemm(a, w, bias))
+            torch.cuda.synchronize()
+            for i, out in enumerate(outs):
+                _, _, _, want, name = cases[i % 2]
+                assert_exact(out, want, f"stream {i % 2}, launch {i // 2}, variant {variant_}: {name}")
+        finally:
+            ops.set_gemm_variant(old)
+    assert scratch[0] == scratch[1] == scratch[2], scratch
+
+
 @pytest.mark.parametrize("M,N,K", [(289, 520, 320), (7200, 1032, 5120), (128, 136, 64)])
 def test_gemm_row_bias_and_transposed_store_are_exact_with_sentinel_padding(M, N, K, variant):
     from chronoedit_amd import ops
@@ -216,7 +254,7 @@ def test_gemm_mul_and_f32_epilogues_are_exact(M, N, K):
 
 @pytest.mark.parametrize("M,N,K,S", [(7200, 1032, 5120, 4), (300, 264, 640, 2), (14400, 5120, 5120, 8)])
 def test_gemm_k_segmented_operand_is_exact(M, N, K, S, variant):
-    """a as [S, M, K/S] (the all-to-all's receive layout, ce_gemm_aseg_bf16) == the product with the segments side by side along K."""
+    """a as [S, M, K/S] (the all-to-all's receive layout, a_seg_k of ce_gemm_bf16) == the product with the segments side by side along K."""
     from chronoedit_amd import ops
     g = _gen(M + N + K + S)
     a = int_rows(M, K, g)

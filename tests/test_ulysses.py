@@ -186,7 +186,7 @@ def test_rope_scatter_equals_rmsnorm_rope_plus_layout(M, H, W):
 @pytest.mark.parametrize("M,N,K,S,epi", [(100, 264, 512, 4, 0), (900, 5120, 5120, 8, 2), (3600, 5120, 5120, 8, 2), (7200, 5120, 5120, 2, 0),
                                           (3600, 5120, 5120, 4, 0)])
 def test_gemm_with_k_segmented_operand(M, N, K, S, epi):
-    """ce_gemm_aseg_bf16: A given as [S, M, K/S] (what the output all-to-all leaves) == the same GEMM on the merged [M, K]
+    """ce_gemm_bf16 with a_seg_k: A given as [S, M, K/S] (what the output all-to-all leaves) == the same GEMM on the merged [M, K]
     operand, bit for bit, in the 128-tile kernel, the 256-tile kernel and its split-K tail."""
     from chronoedit_amd import ops
     dev = torch.device("cuda:0")

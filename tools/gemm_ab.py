@@ -15,8 +15,7 @@ def bind(path):
     P, I = ctypes.c_void_p, ctypes.c_int
     f = lib.ce_gemm_bf16
     f.restype = I
-    f.argtypes = [P, P, P, P, I, P, P] + [I] * 8 + [P]
-    lib.ce_set_gemm_workspace.argtypes = [P, ctypes.c_size_t]
+    f.argtypes = [P, P, P, P, I, P, P] + [I] * 9 + [ctypes.c_longlong, I, ctypes.c_longlong, P, ctypes.c_size_t, P]
     return lib, f
 
 
@@ -24,9 +23,7 @@ def main():
     libs = [bind(p) for p in sys.argv[1:]]
     names = [p.split("/")[-1].replace("lib", "").replace(".so", "") for p in sys.argv[1:]]
     dev = torch.device("cuda:0")
-    ws = torch.empty(96 * 1024 * 1024, dtype=torch.uint8, device=dev)  # the engine's scratch size (ops.GEMM_WS_BYTES)
-    for lib, _ in libs:
-        lib.ce_set_gemm_workspace(ws.data_ptr(), ws.numel())
+    ws = torch.empty(96 * 1024 * 1024, dtype=torch.uint8, device=dev)  # the engine's split-K scratch size (ops.GEMM_WS_BYTES)
     g = torch.Generator().manual_seed(0)
     st = torch.cuda.current_stream().cuda_stream
     for (M, N, K, epi) in [(14400, 10240, 5120, 0), (14400, 13824, 5120, 1), (14400, 5120, 13824, 2), (14400, 5120, 5120, 2), (14400, 5120, 5120, 0), (5120, 14400, 5120, 6),
@@ -41,7 +38,7 @@ def main():
 
         def run(f, o):
             rc = f(a.data_ptr(), w.data_ptr(), o.data_ptr(), b.data_ptr(), epi, gate.data_ptr() if epi == 2 else None,
-                   res.data_ptr() if epi == 2 else None, M, N, K, K, K, N, N, 0, st)
+                   res.data_ptr() if epi == 2 else None, M, N, K, K, K, N, N, 0, 0, 0, 0, 0, ws.data_ptr(), ws.numel(), st)
             assert rc == 0, rc
 
         def timeit(f, o, iters=10):

@@ -14,7 +14,7 @@ def bind(path):
     P, I = ctypes.c_void_p, ctypes.c_int
     f = lib.ce_gemm_fp8
     f.restype = I
-    f.argtypes = [P, P, P, P, P, P, I, P, P] + [I] * 8 + [P]
+    f.argtypes = [P, P, P, P, P, P, I, P, P] + [I] * 8 + [P, ctypes.c_size_t, P]
     q = lib.ce_quant_rows_fp8
     q.restype = I
     q.argtypes = [P, P, P, I, I, I, I, P]
@@ -42,7 +42,7 @@ def main():
 
         def run(f, o):
             rc = f(aq.data_ptr(), wq.data_ptr(), o.data_ptr(), sa.data_ptr(), sw.data_ptr(), b.data_ptr(), epi, gate.data_ptr() if epi == 2 else None,
-                   res.data_ptr() if epi == 2 else None, M, N, K, K, K, N, N, 0, st)
+                   res.data_ptr() if epi == 2 else None, M, N, K, K, K, N, N, 0, None, 0, st)  # (no split-K scratch)
             assert rc == 0, rc
 
         def timeit(f, o, iters=10):

@@ -17,23 +17,20 @@ def bind(path):
     P, I = ctypes.c_void_p, ctypes.c_int
     g = lib.ce_gemm_mxfp8
     g.restype = I
-    g.argtypes = [P, P, P, P, P, P, I, P, P] + [I] * 8 + [P]
+    g.argtypes = [P, P, P, P, P, P, I, P, P] + [I] * 8 + [P, ctypes.c_size_t, P]
     gq = lib.ce_gemm_mxfp8_gelu_quant
     gq.restype = I
-    gq.argtypes = [P, P, P, P, P, P, P] + [I] * 6 + [P]
+    gq.argtypes = [P, P, P, P, P, P, P] + [I] * 6 + [P, ctypes.c_size_t, P]
     q = lib.ce_quant_rows_mxfp8
     q.restype = I
     q.argtypes = [P, P, P, I, I, I, I, P]
-    ws = lib.ce_set_gemm_workspace
-    ws.restype = I
-    ws.argtypes = [P, ctypes.c_size_t]
     # round 6: the register-direct epilogue takes the W scales in the W order (ce_quant_rows_mxfp8_w); a -DF8_EPI_LDS=1 build (ce_build_info bit 2)
     # or a library from before round 6 (no ce_build_info / no _w entry) takes them in the A order
     lib.w_order = hasattr(lib, "ce_quant_rows_mxfp8_w") and not (lib.ce_build_info() & 4)
     if lib.w_order:
         lib.ce_quant_rows_mxfp8_w.restype = I
         lib.ce_quant_rows_mxfp8_w.argtypes = q.argtypes
-    return lib, g, gq, q, ws
+    return lib, g, gq, q
 
 
 def scale_bytes(rows, K):
@@ -55,8 +52,6 @@ def main():
     g = torch.Generator().manual_seed(0)
     st = torch.cuda.current_stream().cuda_stream
     scratch = [torch.empty(96 << 20, dtype=torch.uint8, device=dev) for _ in libs]
-    for (_, _, _, _, ws), buf in zip(libs, scratch):
-        assert ws(buf.data_ptr(), buf.numel()) == 0
     u8 = lambda *s: torch.empty(s, dtype=torch.uint8, device=dev)
     total = [0.0] * len(libs)
     shapes = [("q|k|v", 14400, 15360, 5120, 0, 1), ("cross q", 14400, 5120, 5120, 0, 1), ("out-proj x2", 14400, 5120, 5120, 2, 2),
@@ -86,14 +81,16 @@ def main():
             outs = [torch.empty(M, N, dtype=BF, device=dev) for _ in libs]
 
         def run(i):
-            _, f, fq, _, _ = libs[i]
+            _, f, fq, _ = libs[i]
+            ws = scratch[i]
             turn[0] = (turn[0] + 1) % ncopy
             wq_, sw_ = wqs[turn[0]], (sws_w if libs[i][0].w_order else sws)[turn[0]]
             if epi == 7:
-                rc = fq(aq.data_ptr(), wq_.data_ptr(), sa.data_ptr(), sw_.data_ptr(), b.data_ptr(), outs[i].data_ptr(), osc[i].data_ptr(), M, N, K, K, K, N, st)
+                rc = fq(aq.data_ptr(), wq_.data_ptr(), sa.data_ptr(), sw_.data_ptr(), b.data_ptr(), outs[i].data_ptr(), osc[i].data_ptr(), M, N, K, K, K, N,
+                        ws.data_ptr(), ws.numel(), st)
             else:
                 rc = f(aq.data_ptr(), wq_.data_ptr(), outs[i].data_ptr(), sa.data_ptr(), sw_.data_ptr(), b.data_ptr(), epi, gate.data_ptr() if epi == 2 else None,
-                       res.data_ptr() if epi == 2 else None, M, N, K, K, K, N, N, 0, st)
+                       res.data_ptr() if epi == 2 else None, M, N, K, K, K, N, N, 0, ws.data_ptr(), ws.numel(), st)
             assert rc == 0, rc
 
         def timeit(i, iters=iters_default):

@@ -20,7 +20,7 @@ def slab(x):  # [R, K] -> [K/64, R, 64] contiguous
 def main():
     dev = torch.device("cuda:0")
     lib = ops.lib()
-    ops.ensure_gemm_workspace(dev)
+    ws, ws_bytes = ops._gemm_scratch(dev)
     g = torch.Generator().manual_seed(0)
     st = torch.cuda.current_stream().cuda_stream
     for (M, N, K, epi) in [(14400, 15360, 5120, 0), (14400, 13824, 5120, 1), (14400, 5120, 13824, 2), (14400, 5120, 5120, 2)]:
@@ -35,8 +35,8 @@ def main():
         def run(name, out):
             A, lda, ask, ass = (a_s, 64, 64, M * 64) if "A" in name else (a, K, 0, 0)
             W, ldw, wsk, wss = (w_s, 64, 64, N * 64) if "W" in name else (w, K, 0, 0)
-            rc = lib.ce_gemm_seg_bf16(A.data_ptr(), W.data_ptr(), out.data_ptr(), b.data_ptr(), epi, gate.data_ptr() if epi == 2 else None,
-                                      res.data_ptr() if epi == 2 else None, M, N, K, lda, ldw, N, N, 0, ask, ass, wsk, wss, st)
+            rc = lib.ce_gemm_bf16(A.data_ptr(), W.data_ptr(), out.data_ptr(), b.data_ptr(), epi, gate.data_ptr() if epi == 2 else None,
+                                  res.data_ptr() if epi == 2 else None, M, N, K, lda, ldw, N, N, 0, ask, ass, wsk, wss, ws, ws_bytes, st)
             assert rc == 0, (name, rc)
 
         def timeit(name, out, iters=10):
