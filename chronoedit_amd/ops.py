@@ -1110,3 +1110,62 @@ def attention_mxfp8(q8: torch.Tensor, sq: torch.Tensor, k8: torch.Tensor, sk: to
                                     batch, _stream()), "ce_attention_mxfp8")
     _prof_end(st, f"attention_mxfp8_{nq}x{nkv}_h{heads}" + (f"_b{batch}" if batch > 1 else ""), 4.0 * nq * nkv * 128 * heads * batch)
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# weight-side LoRA merge (csrc/ce_lora.hip)
+# ------------------------------------------------------------------------------------------
+LORA_RANK_MULT = 32   # ce_lora_merge_bf16 walks the rank in chunks of one MFMA contraction
+LORA_MAX_RANK = 512
+LORA_MAX_ADAPTERS = 8
+
+
+def lora_pad_rank(a: torch.Tensor, b: torch.Tensor):
+    """(A [r, K], B [N, r]) -> the same pair with r zero-padded to the next multiple of 32 (zero ranks add exact zeros to the
+    product), contiguous.  A pair that already fits is returned as it is."""
+    r = a.shape[0]
+    rp = (r + LORA_RANK_MULT - 1) // LORA_RANK_MULT * LORA_RANK_MULT
+    if rp == r:
+        return a.contiguous(), b.contiguous()
+    a2 = torch.zeros((rp, a.shape[1]), dtype=a.dtype, device=a.device)
+    a2[:r] = a
+    b2 = torch.zeros((b.shape[0], rp), dtype=b.dtype, device=b.device)
+    b2[:, :r] = b
+    return a2, b2
+
+
+def lora_merge(w0: torch.Tensor, adapters, out: Optional[torch.Tensor] = None):
+    """out[N,K] = bf16(fp32(w0) + sum_i scale_i * (b_i @ a_i)) for adapters = [(a_i [r_i, K], b_i [N, r_i], scale_i), ...], all bf16 on
+    the GPU: the rank products accumulate in fp32 on the MFMA, each is multiplied by its scale and added onto fp32(w0) in list order,
+    one rounding (the contract of ce_lora_merge_bf16).  out may be w0 itself or a row view of a taller buffer; an empty list copies w0.
+    Ranks that are no multiple of 32 are zero-padded here (callers that switch often pad once with lora_pad_rank)."""
+    _dev(w0, torch.bfloat16, "w0")
+    N, K, ldw0 = _rows(w0, "w0")
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.bfloat16, device=w0.device)
+    _dev(out, torch.bfloat16, "out")
+    No, Ko, ldw = _rows(out, "out")
+    if (No, Ko) != (N, K) or out.device != w0.device:
+        raise ValueError(f"lora_merge: out is {tuple(out.shape)} on {out.device}, w0 {tuple(w0.shape)} on {w0.device}")
+    adapters = list(adapters)
+    if len(adapters) > LORA_MAX_ADAPTERS:
+        raise ValueError(f"lora_merge: {len(adapters)} adapters in one merge (at most {LORA_MAX_ADAPTERS})")
+    keep, ranks, scales = [], [], []
+    for i, (a, b, s) in enumerate(adapters):
+        _dev(a, torch.bfloat16, f"a[{i}]"), _dev(b, torch.bfloat16, f"b[{i}]")
+        if a.dim() != 2 or b.dim() != 2 or a.shape[1] != K or b.shape[0] != N or a.shape[0] != b.shape[1]:
+            raise ValueError(f"lora_merge: adapter {i} has A {tuple(a.shape)} / B {tuple(b.shape)} for a [{N}, {K}] weight")
+        if a.device != w0.device or b.device != w0.device:
+            raise ValueError(f"lora_merge: adapter {i} is not on {w0.device}")
+        a, b = lora_pad_rank(a, b)
+        if a.shape[0] > LORA_MAX_RANK:
+            raise ValueError(f"lora_merge: adapter {i} has rank {a.shape[0]} (at most {LORA_MAX_RANK})")
+        keep.append((a, b))
+        ranks.append(a.shape[0])
+        scales.append(float(s))
+    n = len(keep)
+    st = _prof_begin()
+    _check(lib().ce_lora_merge_bf16(_ptr(w0), ldw0, _ptr(out), ldw, N, K, n, _ptr_array([b for _, b in keep]), _ptr_array([a for a, _ in keep]),
+                                    (ctypes.c_int * max(n, 1))(*ranks), (ctypes.c_float * max(n, 1))(*scales), _stream()), "ce_lora_merge_bf16")
+    _prof_end(st, f"lora_merge_{N}x{K}_r{sum(ranks)}", 4.0 * N * K)
+    return out

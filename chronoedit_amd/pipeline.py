@@ -7,6 +7,7 @@ on the device for the whole trajectory; the CFG combine and the UniPC update are
 """
 from __future__ import annotations
 
+import contextlib
 import html
 import re
 from dataclasses import dataclass
@@ -632,6 +633,38 @@ class ChronoEditPipeline:
         self.transformer.fuse_lora(adapter_names=adapter_names, lora_scale=lora_scale)
         return self
 
+    # switching adapters between edits (diffusers' LoraBaseMixin surface; weights.LoraMixin has the semantics and the memory cost)
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        self.transformer.set_adapters(adapter_names, adapter_weights)
+        return self
+
+    def disable_lora(self):
+        self.transformer.disable_lora()
+        return self
+
+    def enable_lora(self):
+        self.transformer.enable_lora()
+        return self
+
+    def unfuse_lora(self):
+        self.transformer.unfuse_lora()
+        return self
+
+    def delete_adapters(self, adapter_names):
+        self.transformer.delete_adapters(adapter_names)
+        return self
+
+    def get_active_adapters(self) -> List[str]:
+        return self.transformer.get_active_adapters()
+
+    def get_list_adapters(self) -> Dict[str, List[str]]:
+        """{component: loaded adapter names}, as diffusers returns it; the adapters target the transformer only."""
+        return {"transformer": self.transformer.get_list_adapters()}
+
+    def unload_lora_weights(self):
+        self.transformer.unload_lora_weights()
+        return self
+
     # -- image pre / post processing (diffusers VideoProcessor, pipeline_chronoedit.py:673,801) ---------------------------
     @staticmethod
     def preprocess_image(image, height: int, width: int) -> torch.Tensor:
@@ -743,26 +776,30 @@ class ChronoEditPipeline:
         # sample's tensors; returned `latents`, `prompt_embeds`, `negative_prompt_embeds` are honoured (:741-749).
         self._num_timesteps = num_inference_steps
         done = []
-        for b in range(B):
-            embeds = {"prompt_embeds": prompt_embeds[b:b + 1], "negative_prompt_embeds": None if negative_prompt_embeds is None else negative_prompt_embeds[b:b + 1]}
+        # attention_kwargs={"scale": s} (diffusers' per-call LoRA scale): the active adapters times s for this call's denoising only
+        lora_scale = getattr(self.transformer, "lora_scale", None)
+        scaled = lora_scale((attention_kwargs or {}).get("scale")) if lora_scale is not None else contextlib.nullcontext()
+        with scaled:
+            for b in range(B):
+                embeds = {"prompt_embeds": prompt_embeds[b:b + 1], "negative_prompt_embeds": None if negative_prompt_embeds is None else negative_prompt_embeds[b:b + 1]}
 
-            def on_step_end(i, t, lat, embeds=embeds):
-                self._current_timestep = t
-                if callback_on_step_end is None:
-                    return None
-                pool = {"latents": lat, **embeds}
-                outs = callback_on_step_end(self, i, t, {k: pool[k] for k in callback_on_step_end_tensor_inputs})
-                if not outs:
-                    return None
-                new = {k: outs[k] for k in ("latents", "prompt_embeds", "negative_prompt_embeds") if k in outs and outs[k] is not pool[k]}
-                embeds.update({k: v for k, v in new.items() if k != "latents"})
-                return new or None
+                def on_step_end(i, t, lat, embeds=embeds):
+                    self._current_timestep = t
+                    if callback_on_step_end is None:
+                        return None
+                    pool = {"latents": lat, **embeds}
+                    outs = callback_on_step_end(self, i, t, {k: pool[k] for k in callback_on_step_end_tensor_inputs})
+                    if not outs:
+                        return None
+                    new = {k: outs[k] for k in ("latents", "prompt_embeds", "negative_prompt_embeds") if k in outs and outs[k] is not pool[k]}
+                    embeds.update({k: v for k, v in new.items() if k != "latents"})
+                    return new or None
 
-            done.append(denoise(self.transformer, self.scheduler, latents[b:b + 1], condition[b:b + 1], embeds["prompt_embeds"],
-                                embeds["negative_prompt_embeds"] if self.do_classifier_free_guidance else None, image_embeds[b:b + 1],
-                                num_inference_steps, guidance_scale, enable_temporal_reasoning, num_temporal_reasoning_steps,
-                                use_graph=self.use_graph, on_step_end=on_step_end, interrupted=lambda: self._interrupt,
-                                graph_warm=self._graph_warm))
+                done.append(denoise(self.transformer, self.scheduler, latents[b:b + 1], condition[b:b + 1], embeds["prompt_embeds"],
+                                    embeds["negative_prompt_embeds"] if self.do_classifier_free_guidance else None, image_embeds[b:b + 1],
+                                    num_inference_steps, guidance_scale, enable_temporal_reasoning, num_temporal_reasoning_steps,
+                                    use_graph=self.use_graph, on_step_end=on_step_end, interrupted=lambda: self._interrupt,
+                                    graph_warm=self._graph_warm))
         latents = done[0] if B == 1 else torch.cat(done, dim=0)
         if offload_model and self.transformer is not None:
             self.transformer.cpu()

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import inspect
 import math
+import re
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Any, Dict, Optional, Tuple, Union
@@ -381,13 +382,54 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
 
     def _apply(self, fn, *a, **kw):  # .to() / .cuda() / .cpu() re-create storages
         self._engine = None
-        return super()._apply(fn, *a, **kw)
+        out = super()._apply(fn, *a, **kw)
+        self._lora_moved(fn)  # (the base store of switchable adapters is no parameter: it follows by hand)
+        return out
 
     def load_state_dict(self, *a, **kw):
         self._engine = None
         return super().load_state_dict(*a, **kw)
 
+    # Linear of a block -> the engine operand that shares its storage (DiTEngine.__init__): w_<slot> of the block's pack, or the all-layer
+    # context buffers w_<slot>_all.  Every other Linear reaches the kernels as a padded or repacked copy (_pad_k / _pad_n, fp32 islands).
+    _LORA_SLOTS = {"attn1.to_q": "qkv", "attn1.to_k": "qkv", "attn1.to_v": "qkv", "attn1.to_out.0": "o1", "attn2.to_q": "q2", "attn2.to_out.0": "o2",
+                   "ffn.net.0.proj": "f1", "ffn.net.2": "f2", "attn2.to_k": "k_t", "attn2.to_v": "v_t", "attn2.add_k_proj": "k_i", "attn2.add_v_proj": "v_i"}
+    _LORA_CONTEXT_SLOTS = ("k_t", "v_t", "k_i", "v_i")
+
+    def _lora_weights_changed(self, modules):
+        """An adapter switch rewrote these Linears' weights in place (weights.LoraMixin._lora_apply).  The packed engine stays: its block
+        operands ARE the parameters' storage (the fused q|k|v and context buffers through the re-pointed row views).  What is derived from
+        them is refreshed - the fp8 copies of the touched Linears, into their existing buffers, and the per-prompt context cache when a
+        context projection changed.  A target whose operand is a padded or repacked copy drops the engine instead (re-packed by the next forward)."""
+        eng = self._engine
+        if eng is None:
+            return
+        own = dict(self.named_modules())
+        requant, context = set(), False
+        for m in modules:
+            mt = re.match(r"^blocks\.(\d+)\.(.+)$", m)
+            slot = self._LORA_SLOTS.get(mt.group(2)) if mt else None
+            if slot is None:
+                return self.invalidate()
+            li = int(mt.group(1))
+            op = getattr(eng, f"w_{slot}_all", None) if slot in self._LORA_CONTEXT_SLOTS else getattr(eng.blk[li], "w_" + slot, None)
+            if op is None or op.untyped_storage().data_ptr() != own[m].weight.untyped_storage().data_ptr():
+                return self.invalidate()
+            context |= slot in self._LORA_CONTEXT_SLOTS
+            if slot in eng.fp8_set:
+                requant.add((li, slot))
+        for li, slot in sorted(requant):
+            p = eng.blk[li]
+            q, s = getattr(p, "q_" + slot)
+            (ops.quant_rows_mxfp8(getattr(p, "w_" + slot), out=q, scale=s, w_order=True) if eng.mx else
+             ops.quant_rows_fp8(getattr(p, "w_" + slot), out=q, scale=s))
+        if context:
+            eng.clear_context_cache()
+
     def engine(self) -> "DiTEngine":
+        rt = getattr(self, "_lora_rt", None)
+        if rt is not None and rt.dirty:  # an adapter switch asked for before the model reached the GPU
+            self._lora_apply()
         if self._engine is None:
             self._engine = DiTEngine(self)
             self._gen = next(_GENERATION)

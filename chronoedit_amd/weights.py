@@ -9,9 +9,11 @@ Host-side, one-off work; nothing here is on the per-step path.
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 import re
+from types import SimpleNamespace
 from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
@@ -286,7 +288,16 @@ def parse_lora(sd: Dict[str, torch.Tensor]) -> Dict[str, Tuple[torch.Tensor, tor
 class LoraMixin:
     """``load_lora_weights`` / ``fuse_lora`` of the reference pipeline (PEFT through diffusers), on the plain parameter
     tree: adapters are kept on the host until fused; fusing edits the Linear weights in place and drops the packed
-    engine so that the next forward re-packs (fused QKV etc.) from the new weights."""
+    engine so that the next forward re-packs (fused QKV etc.) from the new weights.
+
+    Switching between edits (diffusers' ``set_adapters`` / ``disable_lora`` / ``enable_lora`` / ``unfuse_lora`` /
+    ``delete_adapters``): the adapters are merged on the WEIGHT side by ``ops.lora_merge`` (csrc/ce_lora.hip) - the step path
+    sees nothing but a weight matrix at the address it had before, so the packed engine, its workspaces and captured shapes
+    stay valid and a step costs what it cost without adapters.  The first activation keeps a device-side copy of the current
+    bf16 weight of every targeted Linear (the base store); every later switch computes ``bf16(base + sum_i s_i B_i A_i)`` from
+    that copy into the parameter's storage, so ``disable_lora()`` gives the base back bit for bit.  Memory: one extra copy of
+    the TARGETED weights only - an adapter on every block Linear of the 14B model (the distillation LoRA) costs at most one
+    more copy of the block weights, 30 GiB, plus the adapters' A / B in bf16; ``unfuse_lora()`` frees both."""
 
     def _lora_store(self) -> Dict[str, Dict]:
         if not hasattr(self, "_lora_adapters"):
@@ -315,7 +326,13 @@ class LoraMixin:
     @torch.no_grad()
     def fuse_lora(self, adapter_names: Optional[List[str]] = None, lora_scale: float = 1.0) -> "LoraMixin":
         """W += lora_scale * (alpha / r) * B @ A for every target of the named adapters (all loaded ones by default);
-        the product is formed in fp32 and rounded once into the weight dtype."""
+        the product is formed in fp32 and rounded once into the weight dtype.
+        Raises RuntimeError while switchable adapters hold a base store of the weights (from the first set_adapters() until
+        unfuse_lora(), also after disable_lora()): the next switch recomputes every targeted weight from that store and would wipe
+        the fused delta out.  Fuse first and switch afterwards, or call unfuse_lora() before fusing."""
+        rt = getattr(self, "_lora_rt", None)
+        if rt is not None and (rt.base is not None or rt.dirty):
+            raise RuntimeError("fuse_lora: switchable adapters hold a base store of these weights (set_adapters); call unfuse_lora() first")
         store = self._lora_store()
         names = list(store) if adapter_names is None else list(adapter_names)
         modules = dict(self.named_modules())
@@ -337,6 +354,201 @@ class LoraMixin:
         return self
 
     def unload_lora_weights(self) -> "LoraMixin":
-        """Forget adapters that were loaded (fused deltas stay in the weights, as with diffusers after fuse_lora)."""
+        """Forget adapters that were loaded (fused deltas stay in the weights, as with diffusers after fuse_lora; adapters that
+        are merged switchably are taken out of the weights first)."""
+        rt = getattr(self, "_lora_rt", None)
+        if rt is not None:
+            self.unfuse_lora()
+            if rt.merged:  # (the model left the GPU with adapters merged: they can only be taken out there)
+                raise RuntimeError("unload_lora_weights: adapters are still merged into the weights; move the model to the GPU first")
+            rt.active, rt.weights = [], {}
         self._lora_store().clear()
         return self
+
+    # -- switchable adapters ---------------------------------------------------------------------------------------------
+    def _lora_runtime(self) -> SimpleNamespace:
+        """active / weights: the adapter set last asked for (names in order, weight per name); enabled: disable_lora() clears it;
+        merged: the (name, weight) pairs whose deltas the weights hold right now; base: {module: bf16 copy of its weight without
+        them} (None: nothing kept); dev: {(adapter, module): (A, B)} in bf16 on the device, rank padded for the kernel;
+        dirty: a switch asked for while the model was not on the GPU, merged when the engine is next built."""
+        rt = getattr(self, "_lora_rt", None)
+        if rt is None:
+            rt = self._lora_rt = SimpleNamespace(active=[], weights={}, enabled=True, merged=(), base=None, dev={}, dirty=False)
+        return rt
+
+    @staticmethod
+    def _lora_not_capturing(what: str) -> None:
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{what}: adapters cannot be switched while a hipGraph is being captured on this stream "
+                               "(the merge would be recorded into the graph and replayed with every step)")
+
+    @staticmethod
+    def lora_effective_scale(adapter_weight: float, alpha: Optional[float], rank: int) -> float:
+        """adapter_weight * (alpha / r), or adapter_weight alone for an adapter without alpha (PEFT's scaling rule; the rule of fuse_lora)."""
+        return float(adapter_weight) * ((float(alpha) / rank) if alpha is not None else 1.0)
+
+    def set_adapters(self, adapter_names, adapter_weights=None) -> "LoraMixin":
+        """Make exactly the named adapters active, each times its weight (diffusers' forms: a name or a list of names; None = 1.0 for
+        all, one number for all, or one number per name).  The result depends on the set and the weights only, not on what was active
+        before.  Issues work on the current stream only (no synchronisation); not allowed under graph capture.  See the class docstring
+        for the base store this keeps."""
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        if adapter_weights is None:
+            wts = [1.0] * len(names)
+        elif isinstance(adapter_weights, (int, float)):
+            wts = [float(adapter_weights)] * len(names)
+        else:
+            wts = list(adapter_weights)
+            if len(wts) != len(names):
+                raise ValueError(f"set_adapters: {len(names)} adapter names but {len(wts)} adapter weights")
+            if any(w is not None and not isinstance(w, (int, float)) for w in wts):
+                raise TypeError("set_adapters: adapter weights are numbers (per-block weight dicts are not supported)")
+            wts = [1.0 if w is None else float(w) for w in wts]
+        store, fused = self._lora_store(), getattr(self, "_lora_fused", set())
+        if len(set(names)) != len(names):
+            raise ValueError(f"set_adapters: adapter named twice in {names}")
+        for n in names:
+            if n not in store:
+                raise KeyError(f"no adapter named {n!r} (loaded: {sorted(store)})")
+            if n in fused:
+                raise ValueError(f"adapter {n!r} is fused into the weights (fuse_lora): it is part of the base and cannot be activated on top of itself")
+        self._lora_not_capturing("set_adapters")
+        self._lora_check_targets(sorted({m for n in names for m in store[n]}))  # (before the record changes: a refused set is not reported active)
+        rt = self._lora_runtime()
+        rt.active, rt.weights, rt.enabled = names, dict(zip(names, wts)), True
+        self._lora_apply()
+        return self
+
+    def _lora_check_targets(self, targets: List[str]) -> None:
+        """What ce_lora_merge_bf16 takes: bf16 weights with in_features % 64 == 0 and out_features % 8 == 0."""
+        modules = dict(self.named_modules())
+        for m in targets:
+            p = modules[m].weight
+            if p.dtype != torch.bfloat16 or p.shape[1] % 64 or p.shape[0] % 8:
+                raise NotImplementedError(f"{m}: switchable adapters need a bf16 weight with in_features % 64 == 0 and out_features % 8 == 0, "
+                                          f"got {p.dtype} {tuple(p.shape)} (fuse_lora has no such limit)")
+
+    def disable_lora(self) -> "LoraMixin":
+        """Take every switchable adapter out of the weights: each targeted weight is bit-identical to its base afterwards.  The base
+        store and the device copies of the adapters stay for enable_lora() / the next set_adapters()."""
+        self._lora_not_capturing("disable_lora")
+        self._lora_runtime().enabled = False
+        self._lora_apply()
+        return self
+
+    def enable_lora(self) -> "LoraMixin":
+        """Merge the set that was active before disable_lora() / unfuse_lora() again."""
+        self._lora_not_capturing("enable_lora")
+        self._lora_runtime().enabled = True
+        self._lora_apply()
+        return self
+
+    def unfuse_lora(self) -> "LoraMixin":
+        """disable_lora() and give the memory back: the base store and the adapters' device copies are dropped (the adapters stay
+        loaded on the host; enable_lora() / set_adapters() start over with a fresh snapshot)."""
+        self.disable_lora()
+        rt = self._lora_runtime()
+        if not rt.dirty:
+            rt.base, rt.dev = None, {}
+        return self
+
+    def delete_adapters(self, adapter_names) -> "LoraMixin":
+        """Forget the named adapters (a name or a list); active ones are taken out of the weights first.  A fused one stays in the weights."""
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        store = self._lora_store()
+        for n in names:
+            if n not in store:
+                raise KeyError(f"no adapter named {n!r} (loaded: {sorted(store)})")
+        rt = self._lora_runtime()
+        if any(n in rt.active for n in names):
+            self._lora_not_capturing("delete_adapters")
+            rt.active = [n for n in rt.active if n not in names]
+            rt.weights = {n: w for n, w in rt.weights.items() if n in rt.active}
+            self._lora_apply()
+        for n in names:
+            if any(mn == n for mn, _ in rt.merged):  # (the switch is still pending on a model that is not on the GPU)
+                raise RuntimeError(f"adapter {n!r} is still merged into the weights; move the model to the GPU before deleting it")
+            del store[n]
+        rt.dev = {k: v for k, v in rt.dev.items() if k[0] not in names}
+        return self
+
+    def get_active_adapters(self) -> List[str]:
+        """The adapters whose deltas are in effect, in the order given to set_adapters ([] after disable_lora / unfuse_lora)."""
+        rt = getattr(self, "_lora_rt", None)
+        return list(rt.active) if rt is not None and rt.enabled else []
+
+    def get_list_adapters(self) -> List[str]:
+        """Every loaded adapter (active, inactive or fused), in load order."""
+        return list(self._lora_store())
+
+    @contextlib.contextmanager
+    def lora_scale(self, scale: Optional[float]):
+        """``attention_kwargs={"scale": s}`` of a diffusers call: inside the block the active adapters' weights are multiplied by
+        ``scale``; the weights they had come back on the way out, also when the block raises.  None, 1.0 or no active adapter: nothing
+        is merged."""
+        rt = getattr(self, "_lora_rt", None)
+        if scale is None or float(scale) == 1.0 or rt is None or not rt.enabled or not rt.active:
+            yield self
+            return
+        self._lora_not_capturing("attention_kwargs scale")
+        saved = dict(rt.weights)
+        rt.weights = {n: w * float(scale) for n, w in saved.items()}
+        try:
+            self._lora_apply()
+            yield self
+        finally:
+            rt.weights = saved
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                # the block raised inside a capture: merging now would raise over that exception (and be recorded into the graph);
+                # the weights it had are merged back by the next engine() call instead
+                rt.dirty = True
+            else:
+                self._lora_apply()
+
+    def _lora_weights_changed(self, modules: List[str]) -> None:
+        """The weights of these modules were rewritten in place.  The transformer overrides this to keep its packed engine."""
+        self.invalidate()
+
+    def _lora_moved(self, fn) -> None:
+        """The parameters went through ``fn`` (.to / .cuda / .cpu): the base store and the adapters' device copies follow."""
+        rt = getattr(self, "_lora_rt", None)
+        if rt is not None:
+            if rt.base is not None:
+                rt.base = {m: fn(t) for m, t in rt.base.items()}
+            rt.dev = {k: (fn(a), fn(b)) for k, (a, b) in rt.dev.items()}
+
+    @torch.no_grad()
+    def _lora_apply(self) -> None:
+        """Bring the weights to the state the runtime record asks for: every Linear targeted by what is merged now or by what is wanted
+        is recomputed from its base copy by one ops.lora_merge into the parameter's own storage."""
+        from . import ops
+        rt = self._lora_runtime()
+        want = tuple((n, rt.weights[n]) for n in rt.active) if rt.enabled else ()
+        if want == rt.merged:
+            rt.dirty = False
+            return
+        modules = dict(self.named_modules())
+        store = self._lora_store()
+        touched = sorted({m for n, _ in want + rt.merged for m in store[n]})
+        params = [modules[m].weight for m in touched]
+        if any(p.device.type != "cuda" for p in params):
+            rt.dirty = True  # merged when the model is on the GPU (engine())
+            return
+        self._lora_not_capturing("adapter switch")
+        self._lora_check_targets(touched)
+        if rt.base is None:
+            rt.base = {}
+        for m, p in zip(touched, params):
+            if m not in rt.base:  # (not targeted by anything merged so far: the weight IS its base)
+                rt.base[m] = p.detach().clone()
+            adapters = []
+            for n, wt in want:
+                if m not in store[n]:
+                    continue
+                a, b, alpha = store[n][m]
+                if (n, m) not in rt.dev:
+                    rt.dev[(n, m)] = ops.lora_pad_rank(a.to(device=p.device, dtype=torch.bfloat16), b.to(device=p.device, dtype=torch.bfloat16))
+                adapters.append(rt.dev[(n, m)] + (self.lora_effective_scale(wt, alpha, a.shape[0]),))
+            ops.lora_merge(rt.base[m], adapters, out=p.detach())
+        rt.merged, rt.dirty = want, False
+        self._lora_weights_changed(touched)

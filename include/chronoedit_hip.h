@@ -411,6 +411,19 @@ int ce_rmsnorm_bf16(const void* x, void* y, const void* w, int M, int D, int ldx
 int ce_softmax_t5_bf16(const float* scores, void* probs, int batch, int heads, int Lq, int Lk, int ld, int ldp,
                        const int* bucket_lut, const float* table, const int* valid_len, hipStream_t stream);
 
+/* Weight-side LoRA merge (csrc/ce_lora.hip): what switching adapters between edits costs instead of reloading the weights.
+ *   W[n,k] = bf16_rne( fp32(W0[n,k]) + sum_i scales[i] * dot_i[n,k] ),   dot_i[n,k] = sum_r B_i[n,r] * A_i[r,k]
+ * dot_i is the fp32-accumulated sum of the bf16 products over adapter i's rank (bf16 MFMA); each dot_i is multiplied by its fp32 scale
+ * and the terms are added onto fp32(W0) in adapter order (a multiply and an add each); the result is rounded to bf16 once.
+ * W0 = the pristine base, bf16 [N, K] (row stride ldw0); W = the destination, bf16 [N, K] (row stride ldw) - it may alias W0 (every
+ * element is read before it is written) or be a row view of a taller buffer.  B[i] = bf16 [N, ranks[i]], A[i] = bf16 [ranks[i], K],
+ * both row-major and contiguous, 16-byte aligned.  B, A (arrays of device pointers), ranks and scales are HOST arrays, read before the
+ * call returns; the library keeps no state.  n_adapters == 0 copies W0 into W; at most 8 adapters per call.
+ * K % 64 == 0, N % 8 == 0 (as ce_gemm_bf16); ranks multiples of 32 and <= 512 (the caller zero-pads others); ldw0, ldw multiples of 8.
+ * Replaces PEFT's merge behind pipe.fuse_lora / set_adapters (scripts/run_inference_diffusers.py:349-376) on the switchable path. */
+int ce_lora_merge_bf16(const void* W0, int ldw0, void* W, int ldw, int N, int K, int n_adapters, const void* const* B,
+                       const void* const* A, const int* ranks, const float* scales, hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
