@@ -569,6 +569,47 @@ def cfg_unipc_step(v_cond: torch.Tensor, v_uncond: Optional[torch.Tensor], x: to
     return x
 
 
+# ---- TeaCache step skipping (csrc/ce_tea.hip) ------------------------------------------------------------------------
+def tea_rel_l1(rows: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """rows bf16 [S, n] (one time-projection row per scheduled step) -> fp32 [S, 2]: per step i >= 1 the sums of |bf16(row_i - row_{i-1})|
+    and of |row_{i-1}|; row 0 is zeros."""
+    _dev(rows, torch.bfloat16, "rows")
+    if rows.dim() != 2 or not rows.is_contiguous():
+        raise ValueError(f"rows: need a contiguous 2-D tensor, got shape {tuple(rows.shape)} stride {rows.stride()}")
+    S, n = rows.shape
+    if out is None:
+        out = torch.empty((S, 2), dtype=torch.float32, device=rows.device)
+    _dev(out, torch.float32, "out")
+    assert out.is_contiguous() and out.shape == (S, 2)
+    _check(lib().ce_tea_rel_l1_bf16(_ptr(rows), S, n, _ptr(out), _stream()), "ce_tea_rel_l1_bf16")
+    return out
+
+
+def _tea_pair(x: torch.Tensor, r: torch.Tensor):
+    _dev(x, torch.bfloat16, "x"), _dev(r, torch.bfloat16, "r")
+    if not (x.is_contiguous() and r.is_contiguous()) or x.numel() != r.numel():
+        raise ValueError(f"x / r: need two contiguous tensors of one size, got {tuple(x.shape)} and {tuple(r.shape)}")
+    return x.numel()
+
+
+def tea_store_(x: torch.Tensor, r: torch.Tensor):
+    """r <- bf16(x - r), in place: r enters as the tokens saved in front of the block stack and leaves as the stack's residual."""
+    n = _tea_pair(x, r)
+    st = _prof_begin()
+    _check(lib().ce_tea_store_bf16(_ptr(x), _ptr(r), n, _stream()), "ce_tea_store_bf16")
+    _prof_end(st, f"tea_store_{n}", 6.0 * n)
+    return r
+
+
+def tea_apply_(x: torch.Tensor, r: torch.Tensor):
+    """x <- bf16(x + r), in place: the cached residual added to the patch-embedded tokens of a skipped step."""
+    n = _tea_pair(x, r)
+    st = _prof_begin()
+    _check(lib().ce_tea_apply_bf16(_ptr(x), _ptr(r), n, _stream()), "ce_tea_apply_bf16")
+    _prof_end(st, f"tea_apply_{n}", 6.0 * n)
+    return x
+
+
 # ---- Wan VAE ------------------------------------------------------------------------------------------------------
 def conv3d_gemm(in_stack: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], out_stack: torch.Tensor,
                 res_stack: Optional[torch.Tensor], *, T_out: int, H: int, W: int, Cin: int, Cout: int, KT: int, n_tile: int = 0):

@@ -125,10 +125,12 @@ class GraphedDenoiser:
     `step(i)` raises RuntimeError when the object was built at one step index with keep_warmup_step=True (that step ran eagerly in the
     constructor) and the first `step()` asks for another index: build it at the index it starts from.  Between construction and the last
     `step()` the transformer's modes (fp8, sequence parallelism, cache_context) must not change; other forwards of the same transformer
-    are allowed (the lazy capture re-primes its context entry)."""
+    are allowed (the lazy capture re-primes its context entry).
+    With a TeaCache plan (`tea_plan`, chronoedit_amd/teacache.py: one bool per step of the schedule, True = compute) the computed steps replay
+    one graph and the skipped steps a second one, captured lazily at the first skipped step; both address the engine's one residual buffer."""
 
     def __init__(self, transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
-                 guidance_scale: float, batch_cfg: bool = True, warm: bool = False, keep_warmup_step: bool = True):
+                 guidance_scale: float, batch_cfg: bool = True, warm: bool = False, keep_warmup_step: bool = True, tea_plan=None):
         """warm: this process has already run a step of exactly this shape / guidance form through `transformer` (packed weights,
         workspaces, kernel attributes exist), so no un-captured step is needed in front of the capture; only the step-invariant context
         projections are computed eagerly so that the graph holds the cache HIT (`cache_context`), not the projections.
@@ -154,6 +156,9 @@ class GraphedDenoiser:
         self.guided = guidance_scale > 1.0 and negative_prompt_embeds is not None
         if self.guided and batch_cfg:
             self.cfg_inputs = make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds)
+        self.tea_plan = None if tea_plan is None else [bool(c) for c in tea_plan]
+        if self.tea_plan is not None and self.guided and self.cfg_inputs is None:
+            raise NotImplementedError("TeaCache needs the guidance pair as ONE batched forward (one residual buffer covers both samples)")
         self.t_buf = torch.zeros((), dtype=torch.int64, device=dev)
         self.coef_buf = torch.zeros(10, dtype=torch.float32, device=dev)
         scheduler._ensure_state(latents)
@@ -172,7 +177,7 @@ class GraphedDenoiser:
             side = _warmup_stream(dev)  # ONE long-lived side stream per device: every stream GEMMs run on gets a split-K scratch of its own (ops._gemm_scratch)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._body()
+                self._body(self._skips(idx0 or 0))
             torch.cuda.current_stream().wait_stream(side)
             if keep_warmup_step:
                 self._done_index = idx0 or 0
@@ -186,9 +191,10 @@ class GraphedDenoiser:
         # The capture: at once when every step() must be a replay (warm shape, or keep_warmup_step=False); LAZILY - at the first step() that needs a
         # replay - when the constructor already ran the trajectory's current step eagerly: if that was the last step of this shape (truncation lands
         # there, or a callback replaces the latents every step) nothing is ever replayed and a whole capture would be thrown away
-        self.graph = None
+        self.graph = None       # the step that runs the whole model (with TeaCache: the computed steps)
+        self.skip_graph = None  # TeaCache: the skipped steps
         if self._done_index is None:
-            self._capture()
+            self._capture(self._skips(idx0 or 0))
         scheduler._step_index = idx0  # step_cfg counts on the host, also while being captured
 
     def _prime_context(self):
@@ -201,24 +207,46 @@ class GraphedDenoiser:
             elif not self.guided:
                 tr.prime_context(self.prompt, self.image)
 
-    def _capture(self):
+    def _skips(self, i: int) -> bool:
+        return self.tea_plan is not None and not self.tea_plan[i]
+
+    def _capture(self, skip: bool = False):
         # The LAZY capture (first replayed step()) runs at an arbitrary later point of the caller's program: another forward of the same
         # transformer in between (another conditioning of the same shape) may have replaced the context-cache entry and the engine-owned
         # context buffers the eager step left, so the entry is re-primed here (a hit costs nothing) - ADVICE r5.  torch.cuda.graph() itself
         # synchronises the device and runs a gc pass: callers that cannot afford that inside their loop build with keep_warmup_step=False
         # (capture in the constructor).
         self._prime_context()
+        if self.tea_plan is not None:  # the residual buffer both graphs address exists before either is captured
+            self.tr.engine().tea_reserve(self.latents.shape[0] * (2 if self.cfg_inputs is not None else 1) * self._tokens())
         idx = self.sch._step_index
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):  # (a capture executes nothing: the device state stays what the eager step left)
-            self._body()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):  # (a capture executes nothing: the device state stays what the eager step left)
+            self._body(skip)
         self.sch._step_index = idx
+        if skip:
+            self.skip_graph = graph
+        else:
+            self.graph = graph
+
+    def _tokens(self) -> int:
+        _, _, T, h, w = self.latents.shape
+        return T * (h // 2) * (w // 2)
 
     def _stage(self, i):
         self.t_buf.copy_(self.sch.timesteps[i])
         self.coef_buf.copy_(self.sch.coef_row(i, self.g, self.latents.device))
 
-    def _body(self):
+    def _body(self, skip: bool = False):
+        if self.tea_plan is None:
+            return self._step_body()
+        self.tr._tea_mode = "skip" if skip else "compute"
+        try:
+            return self._step_body()
+        finally:
+            self.tr._tea_mode = None  # a forward outside the loop runs the whole model
+
+    def _step_body(self):
         inp = torch.cat([self.latents.to(torch.bfloat16), self.condition], dim=1)
         B = inp.shape[0]
         ts = self.t_buf.expand(B)
@@ -241,10 +269,11 @@ class GraphedDenoiser:
             self._done_index = None
             self.sch._step_index = i + 1
             return self.latents
-        if self.graph is None:
-            self._capture()
+        skip = self._skips(i)
+        if (self.skip_graph if skip else self.graph) is None:
+            self._capture(skip)
         self._stage(i)
-        self.graph.replay()
+        (self.skip_graph if skip else self.graph).replay()
         self.sch._step_index = i + 1
         return self.latents
 
@@ -252,7 +281,8 @@ class GraphedDenoiser:
 @torch.no_grad()
 def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
             num_inference_steps: int, guidance_scale: float = 5.0, enable_temporal_reasoning: bool = False,
-            num_temporal_reasoning_steps: int = 0, use_graph: bool = False, on_step_end=None, interrupted=None, graph_warm=None):
+            num_temporal_reasoning_steps: int = 0, use_graph: bool = False, on_step_end=None, interrupted=None, graph_warm=None,
+            teacache=None):
     """The whole loop, including the temporal-reasoning truncation 8 -> 2 latent frames (pipeline_chronoedit.py:700-709).
     on_step_end(i, t, latents) -> replacement latents, a dict with any of latents / prompt_embeds / negative_prompt_embeds, or None
     (the reference's callback_on_step_end hook, :741-749); graph_warm: a set the caller keeps across edits - shapes already run once in
@@ -260,7 +290,10 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     interrupted() -> True skips the remaining steps (`self.interrupt`, :697-698).  With the tokens sharded over ranks
     (Ulysses) every rank holds the replicated latents and scheduler history, so the truncation is a local slice on every
     rank (the reference all-gathers and re-shards: chronoedit_14b_edit_model.py:168-186) and the next forward simply shards
-    the shorter sequence."""
+    the shorter sequence.
+    teacache: a teacache.TeaCacheConfig for this call; None = whatever `transformer.enable_teacache()` set (nothing: no step is skipped).
+    The compute / skip plan of the whole edit is made here, before the first step (the truncation step always computes: the 8-frame
+    residual does not fit 2-frame tokens); afterwards `transformer.teacache_report` holds {"plan", "computed", "skipped", "ratios"}."""
     scheduler.set_timesteps(num_inference_steps, device=latents.device)
     latents = latents.to(torch.float32).contiguous()
     sharded = getattr(transformer, "_cfgp", None) is not None or (_token_sharded(transformer) and not _sharded_batchable(transformer))
@@ -269,6 +302,18 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
         cfg_inputs = make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds)
     if hasattr(transformer, "clear_context_cache"):
         transformer.clear_context_cache()  # a new edit: nothing of the previous edit's conditioning may be reused
+    tea = teacache if teacache is not None else getattr(transformer, "_teacache", None)
+    tea_plan = None
+    if tea is not None:
+        from . import teacache as _tea
+        if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
+            raise NotImplementedError("TeaCache with the tokens sharded over ranks or with CFG parallelism is not implemented "
+                                      "(the cached residual is row-local; nothing sharded has been tested with it)")
+        forced = {int(num_temporal_reasoning_steps)} if enable_temporal_reasoning else ()
+        ratios = transformer.teacache_ratios(scheduler.timesteps)  # the one device-to-host read of the edit
+        tea_plan = _tea.plan_from_ratios(ratios, len(scheduler.timesteps), tea.rel_l1_thresh, tea.coefficients, forced)
+        transformer.teacache_report = _tea.report(tea_plan, ratios)
+        transformer.engine().tea_drop()  # nothing of the previous edit's residual may be reused
     graphed = None
     if use_graph and not _capturable(transformer):
         use_graph = False  # a step with torch.distributed exchanges runs eagerly (GraphedDenoiser says why); the pipeline default stays use_graph=True
@@ -295,15 +340,23 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                     gen = transformer.engine_generation() if hasattr(transformer, "engine_generation") else id(transformer)
                     # (the scheduler object is not part of the key: everything a step reads from it is created eagerly by GraphedDenoiser
                     # before the capture - _ensure_state, the staged timestep / coefficient row - so a fresh scheduler per edit stays warm)
-                    return (tuple(latents.shape), guidance_scale > 1.0 and negative_prompt_embeds is not None, gen)
+                    return (tuple(latents.shape), guidance_scale > 1.0 and negative_prompt_embeds is not None, gen, tea_plan is not None)
                 graphed = GraphedDenoiser(transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds,
-                                          image_embeds, guidance_scale, batch_cfg=not sharded, warm=graph_warm is not None and warm_key() in graph_warm)
+                                          image_embeds, guidance_scale, batch_cfg=not sharded, warm=graph_warm is not None and warm_key() in graph_warm,
+                                          tea_plan=tea_plan)
                 if graph_warm is not None:
                     graph_warm.add(warm_key())  # (taken AFTER the construction: the first step of a process creates the engine)
             latents = graphed.step(i)
-        else:
+        elif tea_plan is None:
             latents = denoise_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds,
                                    image_embeds, guidance_scale, batch_cfg=not sharded, cfg_inputs=cfg_inputs)
+        else:
+            transformer._tea_mode = "compute" if tea_plan[i] else "skip"
+            try:
+                latents = denoise_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds,
+                                       image_embeds, guidance_scale, batch_cfg=True, cfg_inputs=cfg_inputs)
+            finally:
+                transformer._tea_mode = None  # a forward outside the loop runs the whole model
         if on_step_end is not None:
             new = on_step_end(i, t, latents)
             if isinstance(new, dict):  # the reference's callback may also replace the conditioning (pipeline_chronoedit.py:747-749)
@@ -640,6 +693,15 @@ class ChronoEditPipeline:
 
     def disable_lora(self):
         self.transformer.disable_lora()
+        return self
+
+    # TeaCache step skipping (chronoedit_amd/teacache.py): a switch on the pipeline, `__call__` keeps the reference's signature
+    def enable_teacache(self, rel_l1_thresh: float, coefficients=(1.0, 0.0)):
+        self.transformer.enable_teacache(rel_l1_thresh, coefficients)
+        return self
+
+    def disable_teacache(self):
+        self.transformer.disable_teacache()
         return self
 
     def enable_lora(self):

@@ -1,0 +1,80 @@
+"""TeaCache step skipping for the denoising loop (the reference's `TeaCache`, wan_video_new_chronoedit.py:1190-1239).
+
+On a step whose timestep modulation has moved little since the last step, the block stack is not run: the residual it added on the
+last computed step (tokens behind the stack minus tokens in front of it) is added to this step's patch-embedded tokens instead.
+
+The quantity the rule watches is the time-projection output of the step - a function of the timestep and the weights alone, not of
+the latents, the prompt or the guidance branch.  So the whole compute / skip plan of an edit is a function of the schedule: it is
+computed here BEFORE the loop (one device-to-host read per edit, none per step), the conditional and unconditional passes share it,
+and a hipGraph-replayed loop needs just a second captured graph for the skipped steps (pipeline.GraphedDenoiser).
+
+Host side only: `plan_from_ratios` and the bf16 arithmetic of the ratios need no device; the device passes are csrc/ce_tea.hip."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Iterable, List, Sequence, Tuple
+
+import numpy as np
+
+
+@dataclass(frozen=True)
+class TeaCacheConfig:
+    """rel_l1_thresh: a step is skipped while the accumulated (rescaled) relative L1 distance stays below it.  coefficients: the
+    rescaling polynomial, highest power first (np.poly1d order).  The default is the identity, poly(r) = r: no polynomial has been
+    fitted for ChronoEdit; callers pass the one published for their model family."""
+    rel_l1_thresh: float
+    coefficients: Tuple[float, ...] = (1.0, 0.0)
+
+
+def bf16_round(v: float) -> float:
+    """v rounded to fp32, then to bf16 (round to nearest even), as a Python float: what `torch.tensor(v).bfloat16()` holds."""
+    with np.errstate(over="ignore"):
+        bits = int(np.asarray(v, dtype=np.float32).view(np.uint32))
+    if (bits & 0x7F800000) == 0x7F800000:  # inf stays inf; a NaN keeps its sign and becomes quiet
+        bits = bits & 0xFFFF0000 if not bits & 0x007FFFFF else (bits & 0xFFFF0000) | 0x00400000
+    else:
+        bits = (bits + 0x7FFF + ((bits >> 16) & 1)) & 0xFFFF0000
+    return float(np.asarray(bits, dtype=np.uint32).view(np.float32))
+
+
+def ratios_from_sums(sums, n: int) -> List[float]:
+    """The relative L1 distance of every step to the step before it, from ce_tea_rel_l1_bf16's fp32 sums [S, 2] over rows of n
+    elements, in the reference's bf16 arithmetic (:1219 - both means and their quotient are bf16 tensors):
+    m1 = bf16(sum|d| / n), m0 = bf16(sum|prev| / n), ratio = bf16(m1 / m0), each division in fp32.  Entry 0 is 0.0 (never looked at)."""
+    sums = np.asarray(sums, dtype=np.float32).reshape(-1, 2)
+    out = [0.0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for s1, s0 in sums[1:]:
+            m1 = np.float32(bf16_round(float(s1 / np.float32(n))))
+            m0 = np.float32(bf16_round(float(s0 / np.float32(n))))
+            out.append(bf16_round(float(m1 / m0)))
+    return out
+
+
+def plan_from_ratios(ratios: Sequence[float], num_steps: int, rel_l1_thresh: float, coefficients: Sequence[float],
+                     forced: Iterable[int] = ()) -> List[bool]:
+    """The compute (True) / skip (False) decision of every step of an edit.
+
+    ratios[i] compares step i with step i - 1 whether or not step i - 1 was computed.  The first and the last step compute.  On every
+    other step the rescaled ratio - polyval(coefficients, ratios[i]) in float64, highest power first - is added to an accumulator; the
+    step is skipped while the accumulator is below rel_l1_thresh, otherwise it computes.  Every computed step zeroes the accumulator.
+    Steps in `forced` compute whatever the accumulator says (a step whose token count differs from the cached residual's)."""
+    forced = {int(f) for f in forced}
+    coef = np.asarray(coefficients, dtype=np.float64)
+    plan, acc = [], 0.0
+    for i in range(num_steps):
+        compute = i == 0 or i == num_steps - 1 or i in forced
+        if not compute:
+            with np.errstate(all="ignore"):  # (a NaN or infinite ratio: the comparison below then fails and the step computes)
+                acc += float(np.polyval(coef, np.float64(ratios[i])))
+            compute = not acc < rel_l1_thresh
+        if compute:
+            acc = 0.0
+        plan.append(compute)
+    return plan
+
+
+def report(plan: Sequence[bool], ratios: Sequence[float]) -> dict:
+    """What `denoise` leaves on `transformer.teacache_report` after an edit."""
+    plan = [bool(c) for c in plan]
+    return {"plan": plan, "computed": sum(plan), "skipped": len(plan) - sum(plan), "ratios": [float(r) for r in ratios]}

@@ -208,6 +208,9 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         self.cross_vt = True        # cross-attention takes V^T of the text / image context straight from the context projections (LDS-DMA kernel)
         self._sp = None             # Ulysses sequence parallelism (chronoedit_amd.parallel), off by default
         self._cfgp = None           # CFG parallelism on top of it (two Ulysses groups), off by default
+        self._teacache = None       # TeaCache step skipping (chronoedit_amd.teacache): a TeaCacheConfig once enable_teacache() was called
+        self._tea_mode = None       # per forward, set by the denoising loop: None = off (the full forward), "compute" or "skip"
+        self.teacache_report = None  # {"plan", "computed", "skipped", "ratios"} of the last edit that ran with TeaCache
 
     # -- reference-compatible helpers --------------------------------------------------
     @property
@@ -372,6 +375,43 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         self.fp8_cross = bool(on and cross)
         self._engine = None  # (the context operands and the workspaces depend on it)
         return self
+
+    def enable_teacache(self, rel_l1_thresh: float, coefficients=(1.0, 0.0)):
+        """TeaCache step skipping in `pipeline.denoise` (chronoedit_amd/teacache.py): a step is skipped - the cached residual of the block
+        stack added to its patch-embedded tokens instead of running the blocks - while the accumulated relative L1 distance of the time
+        modulation, rescaled by the polynomial `coefficients` (highest power first), stays below rel_l1_thresh.  The default polynomial
+        is the identity: none has been fitted for ChronoEdit, callers pass the one published for their model family.  Only the loop
+        skips; a direct forward call always runs the whole model.  Not available with the tokens sharded or with CFG parallelism."""
+        from .teacache import TeaCacheConfig
+        coefficients = tuple(float(c) for c in coefficients)
+        if not coefficients:
+            raise ValueError("enable_teacache: `coefficients` is empty")
+        self._teacache = TeaCacheConfig(float(rel_l1_thresh), coefficients)
+        return self
+
+    def disable_teacache(self):
+        self._teacache = None
+        self._tea_mode = None
+        if self._engine is not None:
+            self._engine.tea_release()
+        return self
+
+    @torch.no_grad()
+    def teacache_ratios(self, timesteps: torch.Tensor):
+        """Relative L1 distance of every scheduled step's time modulation to that of the step before it (entry 0 is 0.0): the time
+        projections of all timesteps through the kernels the step itself uses, one reduction launch, ONE device-to-host read."""
+        from .teacache import ratios_from_sums
+        rows = self.engine().tea_tproj_rows(timesteps)
+        return ratios_from_sums(ops.tea_rel_l1(rows).cpu().numpy(), rows.shape[1])
+
+    def teacache_plan(self, timesteps: torch.Tensor, forced=()):
+        """The compute (True) / skip (False) decision for every step of the schedule `timesteps` under the enabled threshold and
+        polynomial; steps in `forced` compute."""
+        from .teacache import plan_from_ratios
+        if self._teacache is None:
+            raise RuntimeError("teacache_plan: call enable_teacache(rel_l1_thresh) first")
+        return plan_from_ratios(self.teacache_ratios(timesteps), int(timesteps.numel()), self._teacache.rel_l1_thresh,
+                                self._teacache.coefficients, forced)
 
     def attention_path(self) -> str:
         """The self-attention arithmetic the next forward will actually run: "mxfp8" only when enable_fp8_attention() is on AND the
@@ -627,6 +667,8 @@ class DiTEngine:
         self._ctx_key = None
         self._ctx = None
         self._ctx_refs = None
+        self._tea_res = None      # TeaCache: the block stack's residual of the last computed step, bf16 [rows, D] (engine-owned)
+        self._tea_valid = False   # ... and whether a computed step of THIS edit has written it
 
     def _fuse(self, linears) -> torch.Tensor:
         """cat the [out,in] weights into one buffer and re-point the module parameters at its rows."""
@@ -882,6 +924,40 @@ class DiTEngine:
         """Drop the cached conditioning-side results (called by the pipeline at the start of every edit)."""
         self._ctx_key = self._ctx = self._ctx_refs = None
 
+    # -- TeaCache (chronoedit_amd/teacache.py) ---------------------------------------------
+    def tea_reserve(self, rows: int) -> torch.Tensor:
+        """The residual buffer for `rows` token rows (all samples of a forward).  Re-allocated - and its content dropped - when the row
+        count changes; never under a hipGraph capture (the compute and the skip graph of a loop share its address):
+        pipeline.GraphedDenoiser reserves it in front of every capture."""
+        if self._tea_res is None or self._tea_res.shape[0] != rows:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"TeaCache: no residual buffer of {rows} rows exists and none can be allocated under a hipGraph capture")
+            self._tea_res = None
+            self._tea_res = torch.empty((rows, self.D), dtype=torch.bfloat16, device=self.dev)
+            self._tea_valid = False
+        return self._tea_res
+
+    def tea_drop(self):
+        """Forget the cached residual (a new edit starts); the buffer stays."""
+        self._tea_valid = False
+
+    def tea_release(self):
+        self._tea_res = None
+        self._tea_valid = False
+
+    def tea_tproj_rows(self, timesteps: torch.Tensor) -> torch.Tensor:
+        """bf16 [S, 6*D]: the time projection (K2 of the forward: sinusoid -> time_embedder -> silu -> time_proj) of every timestep, by
+        the very launches a step makes - bit-identical to the `tproj` the step computes."""
+        ts = timesteps.reshape(-1)
+        ts = ts.to(device=self.dev, dtype=torch.float32 if ts.is_floating_point() else torch.int64).contiguous()
+        rows = torch.empty((ts.numel(), 6 * self.D), dtype=torch.float32, device=self.dev)
+        for i in range(ts.numel()):
+            sin = ops.timestep_sinusoid(ts[i : i + 1], self.cfg.freq_dim)
+            h1 = ops.gemv(self.te_w1, sin, self.te_b1, flags=2)
+            temb = ops.gemv(self.te_w2, h1, self.te_b2, flags=4)
+            ops.gemv(self.tp_w, temb, self.tp_b, flags=1 | 4, out=rows[i])
+        return rows.to(torch.bfloat16)  # (exact: flag 4 left bf16 values in the fp32 rows)
+
     # -- the forward (transformer_chronoedit.py:397-476) ---------------------------------
     def forward(self, hidden: torch.Tensor, timestep: torch.Tensor, text: torch.Tensor, image: Optional[torch.Tensor]):
         """hidden [B,C,T,H,W], timestep [B], text [B,Tt,text_dim], image [B,Ti,image_dim] -> [B,Cout,T,H,W] (bf16).
@@ -931,17 +1007,39 @@ class DiTEngine:
                 ops.patchify(hidden[b], self.kpatch, out=ws.cols[rows[b]], row0=sp.rank * Nl, nrows=Nl)
         ops.gemm(ws.cols, self.w_patch, self.b_patch, out=ws.x)
 
+        # TeaCache (per-call mode, set by the denoising loop; None = off: the launch sequence below is exactly the plain forward's).  compute: the
+        # tokens in front of the blocks are saved, and turned into the stack's residual behind them.  skip: that residual is added to
+        # this step's tokens and the forward continues at the head (K18): no AdaLN block tables, no context, no block.
+        tea = self.model._tea_mode
+        if tea is not None:
+            if tea not in ("compute", "skip"):
+                raise ValueError(f"unknown TeaCache mode {tea!r}")
+            if sp is not None:
+                raise NotImplementedError("TeaCache with the tokens sharded over ranks is not implemented")
+            if tea == "skip":
+                if self._tea_res is None or self._tea_res.shape[0] != B * Nl or not self._tea_valid:
+                    raise RuntimeError(f"TeaCache: a skipped step needs the residual of a computed step with the same {B * Nl} token rows")
+                ops.tea_apply_(ws.x, self._tea_res)
+            else:
+                self.tea_reserve(B * Nl).copy_(ws.x)
+        skip = tea == "skip"
+
         # K2 per sample: sinusoid -> time_embedder (fp32) -> temb (bf16-rounded) -> silu -> time_proj -> AdaLN tables
         mods, gates1, gates2, mods_out = [], [], [], []
         for b in range(B):
             sin = ops.timestep_sinusoid(timestep[b : b + 1], cfg.freq_dim)
             h1 = ops.gemv(self.te_w1, sin, self.te_b1, flags=2)
             temb = ops.gemv(self.te_w2, h1, self.te_b2, flags=4)
-            tproj = ops.gemv(self.tp_w, temb, self.tp_b, flags=1 | 4)  # [6*D]
-            mods.append(ops.modulation(self.tables, tproj.view(6, D), one_mask=0b010010))  # [L,6,D]: shift,1+scale,gate,...
+            if not skip:
+                tproj = ops.gemv(self.tp_w, temb, self.tp_b, flags=1 | 4)  # [6*D]
+                mods.append(ops.modulation(self.tables, tproj.view(6, D), one_mask=0b010010))  # [L,6,D]: shift,1+scale,gate,...
             mods_out.append(ops.modulation(self.table_out, temb.view(1, D), one_mask=0b10))  # [1,2,D]: shift, 1+scale
-        mod = torch.stack(mods, dim=1).contiguous()  # [L, B, 6, D]: per-sample AdaLN rows (ab_rows / gate_rows = tokens per sample)
+        if not skip:
+            mod = torch.stack(mods, dim=1).contiguous()  # [L, B, 6, D]: per-sample AdaLN rows (ab_rows / gate_rows = tokens per sample)
         mod_out = torch.stack(mods_out, dim=0).contiguous()  # [B, 1, 2, D]
+        x = ws.x
+        if skip:
+            return self._head(ws, x, mod_out, sp, B, T, Hh, Ww, N, Nl, rows)
         if B > 1:  # per-sample gate vectors, stacked [L, B, D] for the GEMM epilogue
             gate_msa = mod[:, :, 2].contiguous()
             gate_ffn = mod[:, :, 5].contiguous()
@@ -952,7 +1050,6 @@ class DiTEngine:
         Tt, Ti = ctx.Tt, ctx.Ti
         grow = Nl if B > 1 else 0
 
-        x = ws.x
         fuse_o = self.mx and self.fuse_attn_quant and D % 128 == 0  # MX: both attention kernels emit the out-projections' fp8 operands themselves
         fuse_o1, fuse_o2 = fuse_o and "o1" in self.fp8_set, fuse_o and "o2" in self.fp8_set  # (only for an out-projection that runs in fp8)
         for li, p in enumerate(self.blk):
@@ -1044,6 +1141,13 @@ class DiTEngine:
                 self._linear(ws, ws.ffn, p, "f2", x, epilogue=ops.EPI_GATE_RES, gate=gate_ffn[li] if B > 1 else mods[0][li, 5],
                              res=x, gate_rows=grow)
 
+        if tea is not None:  # the saved tokens become the residual of this (computed) step
+            ops.tea_store_(x, self._tea_res)
+            self._tea_valid = True
+        return self._head(ws, x, mod_out, sp, B, T, Hh, Ww, N, Nl, rows)
+
+    def _head(self, ws, x, mod_out, sp, B, T, Hh, Ww, N, Nl, rows):
+        cfg, D, eps = self.cfg, self.D, self.cfg.eps
         # K18
         ops.ln_affine(x, mod_out[0, 0, 1], mod_out[0, 0, 0], eps, out=ws.h, ab_rows=Nl, ab_stride=2 * D)
         ops.gemm(ws.h, self.w_out, self.b_out, out=ws.head)

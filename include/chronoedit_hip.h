@@ -424,6 +424,18 @@ int ce_softmax_t5_bf16(const float* scores, void* probs, int batch, int heads, i
 int ce_lora_merge_bf16(const void* W0, int ldw0, void* W, int ldw, int N, int K, int n_adapters, const void* const* B,
                        const void* const* A, const int* ranks, const float* scales, hipStream_t stream);
 
+/* ---- TeaCache step skipping (csrc/ce_tea.hip; wan_video_new_chronoedit.py:1190-1239, chronoedit_amd/teacache.py) ----
+ * ce_tea_rel_l1_bf16: T = bf16 [S, n], one time-projection row per scheduled step (contiguous, 16-byte aligned); out = fp32 [S, 2]:
+ *   out[i][0] = sum_j |bf16(T[i][j] - T[i-1][j])|,  out[i][1] = sum_j |T[i-1][j]|  for i >= 1,  out[0] = {0, 0}.
+ * fp32 accumulation in a fixed order (one workgroup per row): bit-identical from run to run.  n % 8 == 0, otherwise -2.
+ * ce_tea_store_bf16: r[k] <- bf16(float(x[k]) - float(r[k])) - on entry r holds the tokens saved in front of the block stack, x the
+ *   tokens behind it; afterwards r is the stack's residual (TeaCache.store, :1233).
+ * ce_tea_apply_bf16: x[k] <- bf16(float(x[k]) + float(r[k])) (TeaCache.update, :1237).
+ * Both: bf16, `count` elements, count % 8 == 0 (otherwise -2), x and r 16-byte aligned (otherwise -3), round to nearest even. */
+int ce_tea_rel_l1_bf16(const void* T, int S, int n, float* out, hipStream_t stream);
+int ce_tea_store_bf16(const void* x, void* r, long long count, hipStream_t stream);
+int ce_tea_apply_bf16(void* x, const void* r, long long count, hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
