@@ -70,6 +70,11 @@ struct BlkRows {
   unsigned char* q8;  // e4m3 [batch Nq][ld8]
   unsigned char* s8;  // E8M0 block scales, tiled layout of ce_gemm_mxfp8
   int ld8;
+  // two-segment V^T form only: the samples' strides in rows of Q and of each segment's K (0: every sample reads the same rows; the V^T column
+  // strides above - vt_cols, stride - are 0 with them).  O is always per sample.
+  int q_rows;
+  int k0_rows;
+  int k1_rows;
 };
 
 template <bool TWO_SEG, int NWAVE>
@@ -406,6 +411,11 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_sp_kernel(const bf16* __restr
       O += (size_t)bz * blk.rows * ldo;
       seg0.k += (size_t)bz * blk.rows * seg0.ldk;
       seg0.v += (size_t)bz * blk.vt_cols;
+    } else if (TWO_SEG && VT) {  // explicit sample strides: an operand with stride 0 is one tensor shared by all samples
+      Q += (size_t)bz * blk.q_rows * ldq;
+      O += (size_t)bz * Nq * ldo;
+      seg0.k += (size_t)bz * blk.k0_rows * seg0.ldk;
+      seg0.v += (size_t)bz * blk.vt_cols;
     } else {
       Q += (size_t)bz * Nq * ldq;
       O += (size_t)bz * Nq * ldo;
@@ -414,7 +424,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_sp_kernel(const bf16* __restr
       seg0.v += VT ? (size_t)bz * (TWO_SEG ? blk.vt_cols : seg0.len) : (size_t)bz * seg0.len * seg0.ldv;
     }
     if (TWO_SEG) {
-      seg1.k += (size_t)bz * seg1.len * seg1.ldk;
+      seg1.k += (size_t)bz * (VT ? blk.k1_rows : seg1.len) * seg1.ldk;
       seg1.v += VT ? (size_t)bz * blk.stride : (size_t)bz * seg1.len * seg1.ldv;
     }
   }
@@ -1648,11 +1658,16 @@ CE_API int ce_attention_vt_blocked_bf16(const void* Q, const void* K, const void
 static int attention_2seg_vt_launch(const void* Q, const void* K1, const void* V1t, int len1, int ldk1, int ldv1t, int vt_cols1,
                                     const void* K2, const void* V2t, int len2, int ldk2, int ldv2t, int vt_cols2, void* O, int Nq,
                                     int H, int head_dim, int ldq, int ldo, float softmax_scale, int batch, void* O8, void* S8, int ldo8,
-                                    hipStream_t stream) {
+                                    int q_rows, int k1_rows, int k2_rows, hipStream_t stream) {
   if (!Q || !K1 || !V1t || !K2 || !V2t || (!O && !O8)) return CE_ERR_ARG;
+  // sample strides in rows: 0 = the operand is shared by all samples, otherwise at least one sample's rows
+  if ((q_rows != 0 && q_rows < Nq) || (k1_rows != 0 && k1_rows < len1) || (k2_rows != 0 && k2_rows < len2)) return CE_ERR_SHAPE;
+  if (k1_rows == 0) vt_cols1 = 0;  // (a shared segment's V^T is shared with its K)
+  if (k2_rows == 0) vt_cols2 = 0;
   if (head_dim != HD || Nq <= 0 || H <= 0 || len1 <= 0 || len2 <= 0 || batch <= 0 || batch > 65535) return CE_ERR_SHAPE;
   const int c1 = (len1 + KVB - 1) / KVB * KVB, c2 = (len2 + KVB - 1) / KVB * KVB;
-  if (vt_cols1 < len1 || vt_cols2 < len2 || ldv1t < (batch - 1) * vt_cols1 + c1 || ldv2t < (batch - 1) * vt_cols2 + c2) return CE_ERR_SHAPE;
+  if ((k1_rows != 0 && vt_cols1 < len1) || (k2_rows != 0 && vt_cols2 < len2) || ldv1t < (batch - 1) * vt_cols1 + c1 || ldv2t < (batch - 1) * vt_cols2 + c2)
+    return CE_ERR_SHAPE;
   if ((ldq & 7) || (ldo & 7) || (ldk1 & 7) || (ldk2 & 7) || (ldv1t & 7) || (ldv2t & 7) || (vt_cols1 & 1) || (vt_cols2 & 1)) return CE_ERR_ALIGN;
   KVSeg s0{(const bf16*)K1, (const bf16*)V1t, len1, ldk1, ldv1t};
   KVSeg s1{(const bf16*)K2, (const bf16*)V2t, len2, ldk2, ldv2t};
@@ -1665,7 +1680,7 @@ static int attention_2seg_vt_launch(const void* Q, const void* K1, const void* V
     (void)hipFuncSetAttribute((const void*)attn_fwd_sp_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes(true));
     done = true;
   }
-  const BlkRows blk{0, vt_cols2, 0u, vt_cols1, (unsigned char*)O8, (unsigned char*)S8, ldo8};  // plain rows; the two column strides
+  const BlkRows blk{0, vt_cols2, 0u, vt_cols1, (unsigned char*)O8, (unsigned char*)S8, ldo8, q_rows, k1_rows, k2_rows};  // plain rows; the column and row strides
   // persistent like the single-segment V^T launch: two workgroups per CU walk the work order (an item is 13 key tiles here: -3 % against
   // one workgroup per item, profiles/r04_cross_attention_persistent_ab.txt; 3 and 4 per CU are level with 2)
   const int cus = ce_device_cus();
@@ -1685,7 +1700,20 @@ CE_API int ce_attention_2seg_vt_bf16(const void* Q, const void* K1, const void* 
                                          int H, int head_dim, int ldq, int ldo, float softmax_scale, int batch, hipStream_t stream) {
   if (!O) return CE_ERR_ARG;
   return attention_2seg_vt_launch(Q, K1, V1t, len1, ldk1, ldv1t, vt_cols1, K2, V2t, len2, ldk2, ldv2t, vt_cols2, O, Nq, H, head_dim, ldq, ldo,
-                                  softmax_scale, batch, nullptr, nullptr, 0, stream);
+                                  softmax_scale, batch, nullptr, nullptr, 0, Nq, len1, len2, stream);
+}
+
+/* ce_attention_2seg_vt_bf16 with the samples' strides given: q_rows rows of Q between samples (Nq = stacked, 0 = every sample reads the same
+ * Nq query rows), k1_rows / k2_rows rows of K1 / K2 between samples (>= len, or 0 = the segment - its K and its V^T - is one tensor for all
+ * samples; vt_cols of a shared segment is ignored).  O is always [batch Nq][ldo].  The guidance pair shares its image context (k2_rows = 0) and,
+ * in front of the first cross-attention, its queries (q_rows = 0).  Same products in the same order as the stacked form on duplicated operands. */
+CE_API int ce_attention_2seg_vt_strided_bf16(const void* Q, const void* K1, const void* V1t, int len1, int ldk1, int ldv1t, int vt_cols1,
+                                                 const void* K2, const void* V2t, int len2, int ldk2, int ldv2t, int vt_cols2, void* O, int Nq,
+                                                 int H, int head_dim, int ldq, int ldo, float softmax_scale, int batch, int q_rows, int k1_rows,
+                                                 int k2_rows, hipStream_t stream) {
+  if (!O) return CE_ERR_ARG;
+  return attention_2seg_vt_launch(Q, K1, V1t, len1, ldk1, ldv1t, vt_cols1, K2, V2t, len2, ldk2, ldv2t, vt_cols2, O, Nq, H, head_dim, ldq, ldo,
+                                  softmax_scale, batch, nullptr, nullptr, 0, q_rows, k1_rows, k2_rows, stream);
 }
 
 /* The same attention with the output written as the MX fp8 operand of the out-projection that follows it in the fp8 mode: o8 e4m3
@@ -1697,5 +1725,5 @@ CE_API int ce_attention_2seg_vt_quant_bf16(const void* Q, const void* K1, const 
                                                hipStream_t stream) {
   if (!o8 || !scale8 || (ldo8 & 15) || ((H * head_dim) & 127)) return CE_ERR_ARG;
   return attention_2seg_vt_launch(Q, K1, V1t, len1, ldk1, ldv1t, vt_cols1, K2, V2t, len2, ldk2, ldv2t, vt_cols2, nullptr, Nq, H, head_dim, ldq,
-                                  8, softmax_scale, batch, o8, scale8, ldo8, stream);
+                                  8, softmax_scale, batch, o8, scale8, ldo8, Nq, len1, len2, stream);
 }

@@ -44,7 +44,7 @@ template <int EPI>
 __global__ __launch_bounds__(256) void gemm_bf16_128(const bf16* __restrict__ A, const bf16* __restrict__ W,
                                                      bf16* __restrict__ C, const float* __restrict__ bias,
                                                      const float* __restrict__ gate, const bf16* __restrict__ res, int M,
-                                                     int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                                                     int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                                      int tiles_m, int tiles_n, int batch0, long long sA0, long long sA1,
                                                      long long sW0, long long sW1, long long sC0, long long sC1,
                                                      int a_seg_tiles, long long a_seg_extra) {
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_128(const bf16* __restrict__ A,
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = pack_bf16(bf16lo(rv[q]) * bf16lo(v[q]), bf16hi(rv[q]) * bf16hi(v[q]));
       } else if (EPI == EPI_GATE_RES) {
-        const u32x4 rv = *reinterpret_cast<const u32x4*>(res + (size_t)m * ldres + n);
+        const u32x4 rv = *reinterpret_cast<const u32x4*>(res + (size_t)(res_rows > 0 ? m % res_rows : m) * ldres + n);
         float g[8];
         if (gate != nullptr) {
           const float* gp = gate + (gate_rows > 0 ? (size_t)(m / gate_rows) * N : 0) + n;  // per-sample gate rows
@@ -226,21 +226,21 @@ __global__ __launch_bounds__(256) void gemm_bf16_128(const bf16* __restrict__ A,
 
 extern "C" int ce_gemm256_supported(int M, int N, int K, int lda, int ldw);
 extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                  int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
                                  hipStream_t stream);
 
 extern "C" void ce_gemm256_set_staggered(int on);
 extern "C" int ce_gemm384_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                  int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
                                  hipStream_t stream);
 extern "C" int ce_gemm288_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                  int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
                                  hipStream_t stream);
 extern "C" int ce_gemm256w4_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                   const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                                   const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                    int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, int nsa, float* ws,
                                    size_t ws_bytes, hipStream_t stream);
 
@@ -315,8 +315,8 @@ CE_API int ce_gemm_bf16_tile_rows(int M, int N, int K, int cus, long long ws_byt
 // ... and the same for W (w_seg_k, w_seg_stride): weights re-packed K-slab-major ([K/64][N][64]) so that every 16 KiB
 // half-tile of the LDS-DMA stream is one contiguous block (tools/probes/l2_pattern_probe.hip: 21.7 vs 18.3 TB/s for the
 // row-strided form).  Segmented W needs the 256-tile kernel (CE_ERR_SHAPE otherwise).
-CE_API int ce_gemm_bf16(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                        const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+CE_API int ce_gemm_bf16_res(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
+                        const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                         int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, void* ws, size_t ws_bytes,
                         hipStream_t stream) {
   if (!A || !W || !C) return CE_ERR_ARG;
@@ -337,12 +337,12 @@ CE_API int ce_gemm_bf16(const void* A, const void* W, void* C, const float* bias
         const long long nwg = (long long)((M + rows - 1) / rows) * ((N + 255) / 256);
         const int tail = (int)(nwg % cus);
         if (g_gemm_variant != -1 || tail == 0 || tail * 10 >= cus * 9)
-          return (rows == 384 ? ce_gemm384_launch : ce_gemm288_launch)(A, W, C, bias, EPI_BIAS_T, nullptr, nullptr, M, N, K, lda, ldw, ldc, 0, 0, 0, 0, 0, 0,
+          return (rows == 384 ? ce_gemm384_launch : ce_gemm288_launch)(A, W, C, bias, EPI_BIAS_T, nullptr, nullptr, M, N, K, lda, ldw, ldc, 0, 0, 0, 0, 0, 0, 0,
                                                                       slabs, ws_bytes, stream);
       }
     }
     if (!plain) return CE_ERR_SHAPE;
-    return ce_gemm_bf16(W, A, C, bias, EPI_BIAS_ROW, nullptr, nullptr, N, M, K, ldw, lda, ldc, 0, 0, 0, 0, 0, 0, ws, ws_bytes, stream);
+    return ce_gemm_bf16_res(W, A, C, bias, EPI_BIAS_ROW, nullptr, nullptr, N, M, K, ldw, lda, ldc, 0, 0, 0, 0, 0, 0, 0, ws, ws_bytes, stream);
   }
   if (w_seg_k < 0 || (w_seg_k > 0 && w_seg_k < K && ((w_seg_k % BK) || (K % w_seg_k) || (w_seg_stride & 7)))) return CE_ERR_SHAPE;
   if (w_seg_k >= K) w_seg_k = 0;
@@ -351,6 +351,7 @@ CE_API int ce_gemm_bf16(const void* A, const void* W, void* C, const float* bias
   if (M <= 0 || N <= 0 || K <= 0 || (K % BK) || (N & 7)) return CE_ERR_SHAPE;
   if ((lda & 7) || (ldw & 7) || (ldc & 7)) return CE_ERR_ALIGN;
   if ((epilogue == EPI_GATE_RES || epilogue == EPI_MUL) && (!res || (ldres & 7))) return CE_ERR_ARG;
+  if (res_rows < 0 || (res_rows > 0 && epilogue != EPI_GATE_RES)) return CE_ERR_ARG;  // (the row period exists for the gated residual only)
   if (epilogue < 0 || epilogue > 6 || (epilogue == EPI_BIAS_ROW && !bias)) return CE_ERR_ARG;
   if (epilogue != EPI_F32 && epilogue != EPI_MUL) {
     const bool big = (long long)M * N >= 256ll * 256 * 128;  // enough 256x256 tiles to fill half the chip
@@ -360,15 +361,15 @@ CE_API int ce_gemm_bf16(const void* A, const void* W, void* C, const float* bias
       // profiles/r03_gemm_variants_ab.txt) and the 8-wave / 8-phase loop of ce_gemm256.hip (variants 1, 2)
       const int rows_auto = g_gemm_variant == -1 ? ce_gemm_bf16_tile_rows(M, N, K, cus, scratch_bytes) : 0;
       if (g_gemm_variant == 6 || rows_auto == 384)  // the 384 x 256 macro tile (ce_gemm384.hip)
-        return ce_gemm384_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride,
+        return ce_gemm384_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, a_seg_k, a_seg_stride,
                                  w_seg_k, w_seg_stride, slabs, ws_bytes, stream);
       if (g_gemm_variant == 7 || rows_auto == 288)  // the 288 x 256 macro tile (the same kernel, 144 x 128 wave tiles)
-        return ce_gemm288_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride,
+        return ce_gemm288_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, a_seg_k, a_seg_stride,
                                  w_seg_k, w_seg_stride, slabs, ws_bytes, stream);
       if (g_gemm_variant == 1 || g_gemm_variant == 2)
-        return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride,
+        return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, a_seg_k, a_seg_stride,
                                  w_seg_k, w_seg_stride, slabs, ws_bytes, stream);
-      return ce_gemm256w4_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride,
+      return ce_gemm256w4_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, a_seg_k, a_seg_stride,
                                  w_seg_k, w_seg_stride, g_gemm_variant == 3 ? 3 : g_gemm_variant == 5 ? 1 : 2, slabs, ws_bytes, stream);
     }
   }
@@ -379,7 +380,7 @@ CE_API int ce_gemm_bf16(const void* A, const void* W, void* C, const float* bias
   dim3 grid(tiles_m * tiles_n), block(256);
 #define CE_LAUNCH(E)                                                                                              \
   hipLaunchKernelGGL(gemm_bf16_128<E>, grid, block, 0, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                     (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, 1, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll, \
+                     (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, 1, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll, \
                      a_seg_tiles, a_seg_extra)
   switch (epilogue) {
     case EPI_BIAS: CE_LAUNCH(EPI_BIAS); break;
@@ -393,6 +394,15 @@ CE_API int ce_gemm_bf16(const void* A, const void* W, void* C, const float* bias
   }
 #undef CE_LAUNCH
   return (int)hipGetLastError();
+}
+
+// The entry point as it was before the residual row period existed: every output row reads its own residual row.
+CE_API int ce_gemm_bf16(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
+                        const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                        int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, void* ws, size_t ws_bytes,
+                        hipStream_t stream) {
+  return ce_gemm_bf16_res(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, 0, a_seg_k, a_seg_stride, w_seg_k,
+                          w_seg_stride, ws, ws_bytes, stream);
 }
 
 // batch0 x batch1 independent products with two-level element strides (e.g. head within sample): operand z = (z0, z1) is
@@ -411,7 +421,7 @@ CE_API int ce_gemm_batched_bf16(const void* A, const void* W, void* C, const flo
   dim3 grid(tiles_m * tiles_n, batch0 * batch1), block(256);
 #define CE_LAUNCH(E)                                                                                                 \
   hipLaunchKernelGGL(gemm_bf16_128<E>, grid, block, 0, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, nullptr, \
-                     nullptr, M, N, K, lda, ldw, ldc, 0, 0, tiles_m, tiles_n, batch0, sA0, sA1, sW0, sW1, sC0, sC1, 0, 0ll)
+                     nullptr, M, N, K, lda, ldw, ldc, 0, 0, 0, tiles_m, tiles_n, batch0, sA0, sA1, sW0, sW1, sC0, sC1, 0, 0ll)
   if (epilogue == EPI_BIAS) CE_LAUNCH(EPI_BIAS); else CE_LAUNCH(EPI_F32);
 #undef CE_LAUNCH
   return (int)hipGetLastError();

@@ -131,7 +131,7 @@ template <int EPI>
 __device__ __forceinline__ void epilogue256(const f32x4 (&acc)[2][2][4][2], unsigned char* smem, int tid, int wm, int wn,
                                             int fr, int fg, int m0, int n0, bf16* __restrict__ C,
                                             const float* __restrict__ bias, const float* __restrict__ gate,
-                                            const bf16* __restrict__ res, int M, int N, int ldc, int ldres, int gate_rows) {
+                                            const bf16* __restrict__ res, int M, int N, int ldc, int ldres, int gate_rows, int res_rows) {
   // column bias of this lane's four (j, g) column groups, the same for both passes: four 16-B loads issued together, on clamped
   // addresses and without a per-lane guard (a guarded load compiles to its own branch with a vmcnt(0) behind it - seven serial
   // round trips per tile before this was hoisted); n is a multiple of 4 and N of 8, so "n < N" covers all four columns
@@ -169,7 +169,7 @@ __device__ __forceinline__ void epilogue256(const f32x4 (&acc)[2][2][4][2], unsi
       }
     __syncthreads();
     epi_chunks<EPI, 8>(smem, CROW, [&](int tt, int& rl, int& cc, int& mr) { const int c = tid + 512 * tt; rl = mr = c >> 5; cc = c & 31; },
-                       m0 + i * 128, n0, C, gate, res, M, N, ldc, ldres, gate_rows);
+                       m0 + i * 128, n0, C, gate, res, M, N, ldc, ldres, gate_rows, res_rows);
   }
 }
 
@@ -177,7 +177,7 @@ template <int EPI, bool STAG>
 __global__ __launch_bounds__(512) void gemm_bf16_256(const bf16* __restrict__ A, const bf16* __restrict__ W,
                                                      bf16* __restrict__ C, const float* __restrict__ bias,
                                                      const float* __restrict__ gate, const bf16* __restrict__ res, int M,
-                                                     int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                                                     int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                                      int tiles_m, int tiles_n, int t_full, int split,
                                                      float* __restrict__ ws, uint32_t a_seg_magic, uint32_t a_seg_extra,
                                                      uint32_t w_seg_magic, uint32_t w_seg_extra) {
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_256(const bf16* __restrict__ A,
             *reinterpret_cast<f32x4*>(slab + ((((i * 2 + j) * 4 + f) * 2 + g) * 512 + tid) * 4) = acc[i][j][f][g];
     return;
   }
-  epilogue256<EPI>(acc, smem, tid, wm, wn, fr, fg, m0, n0, C, bias, gate, res, M, N, ldc, ldres, gate_rows);
+  epilogue256<EPI>(acc, smem, tid, wm, wn, fr, fg, m0, n0, C, bias, gate, res, M, N, ldc, ldres, gate_rows, res_rows);
 }
 
 // Sums the `split` fp32 slabs of one QUADRANT (128 x 128) of a tail tile - same thread <-> accumulator mapping as the GEMM
@@ -399,7 +399,7 @@ constexpr int QROW = 128 * 2 + 16;  // padded staging row of a quadrant (272 B)
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm256_reduce(bf16* __restrict__ C, const float* __restrict__ bias,
                                                       const float* __restrict__ gate, const bf16* __restrict__ res, int M,
-                                                      int N, int ldc, int ldres, int gate_rows, int tiles_m, int tiles_n,
+                                                      int N, int ldc, int ldres, int gate_rows, int res_rows, int tiles_m, int tiles_n,
                                                       int t_full, int split, const float* __restrict__ ws) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -430,7 +430,7 @@ __global__ __launch_bounds__(512) void gemm256_reduce(bf16* __restrict__ C, cons
   }
   __syncthreads();
   epi_chunks<EPI, 4>(smem, QROW, [&](int tt, int& rl, int& cc, int& mr) { const int c = tid + 512 * tt; rl = mr = c >> 4; cc = c & 15; }, m0, n0, C,
-                     gate, res, M, N, ldc, ldres, gate_rows);
+                     gate, res, M, N, ldc, ldres, gate_rows, res_rows);
 }
 
 }  // namespace
@@ -451,7 +451,7 @@ static constexpr bool staggered = false;
 #endif
 
 extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                  int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
                                  hipStream_t stream) {
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
@@ -487,15 +487,15 @@ extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const fl
     }                                                                                                                 \
     if (staggered)                                                                                                    \
       hipLaunchKernelGGL((gemm_bf16_256<E, true>), grid, block, LDS_BYTES, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, \
-                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n,    \
+                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n,    \
                          t_full2, split, ws, a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra);                                             \
     else                                                                                                              \
       hipLaunchKernelGGL((gemm_bf16_256<E, false>), grid, block, LDS_BYTES, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, \
-                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n,    \
+                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n,    \
                          t_full2, split, ws, a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra);                                             \
     if (tail)                                                                                                         \
       hipLaunchKernelGGL((gemm256_reduce<E>), dim3(4 * tail), block, 128 * QROW, stream, (bf16*)C, bias, gate,        \
-                         (const bf16*)res, M, N, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws);      \
+                         (const bf16*)res, M, N, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws);      \
   } while (0)
   switch (epilogue) {
     case EPI_BIAS: CE_LAUNCH(EPI_BIAS); break;

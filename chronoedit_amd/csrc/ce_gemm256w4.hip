@@ -78,7 +78,7 @@ template <int EPI, int NSA, bool ONEBAR, bool SEG2 = false, int NG = 8>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_bf16_w4(
     const bf16* __restrict__ A, const bf16* __restrict__ W, bf16* __restrict__ C, const float* __restrict__ bias,
     const float* __restrict__ gate, const bf16* __restrict__ res, int M, int N, int K, int lda, int ldw, int ldc, int ldres,
-    int gate_rows, int tiles_m, int tiles_n, int t_full, int split, float* __restrict__ ws, uint32_t a_seg_magic,
+    int gate_rows, int res_rows, int tiles_m, int tiles_n, int t_full, int split, float* __restrict__ ws, uint32_t a_seg_magic,
     uint32_t a_seg_extra, uint32_t w_seg_magic, uint32_t w_seg_extra, uint32_t a_seg2_magic, uint32_t a_seg2_extra) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int BN = 32 * NG;          // tile width
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       for (int f = 0; f < 8; ++f)
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj)
-          rv[f][jj] = *reinterpret_cast<const u32x4*>(res + (size_t)min(row_base + f * 16 + jj, M - 1) * ldres + colc);
+          rv[f][jj] = *reinterpret_cast<const u32x4*>(res + (size_t)res_row(min(row_base + f * 16 + jj, M - 1), res_wrap(m0, res_rows)) * ldres + colc);
     }
 #pragma unroll
     for (int f = 0; f < 8; ++f) {
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         bool ok;
         const int rl = chunk_row(tt, ok);
         const int m = min(m0 + (rl >> 5) * 128 + p * 32 + (rl & 31), M - 1);
-        rv[p][tt] = *reinterpret_cast<const u32x4*>(res + (size_t)m * ldres + my_nc);
+        rv[p][tt] = *reinterpret_cast<const u32x4*>(res + (size_t)res_row(m, res_wrap(m0, res_rows)) * ldres + my_nc);
       }
   }
 #pragma unroll
@@ -464,7 +464,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                            cc = my_cc;
                            mr = ok ? (rl >> 5) * 128 + p * 32 + (rl & 31) : (1 << 28);  // (no such chunk: row past M, the store is skipped)
                          },
-                         m0, n0, C, gate, res, M, N, ldc, ldres, gate_rows);
+                         m0, n0, C, gate, res, M, N, ldc, ldres, gate_rows, res_rows);
     }
   }
 }
@@ -473,7 +473,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // grid = 4 x the number of tail tiles, 256 threads: thread (w, lane) takes accumulator rows f = 2w, 2w+1 of the quadrant.
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm256w4_reduce(bf16* __restrict__ C, const float* __restrict__ bias, const float* __restrict__ gate,
-                                                        const bf16* __restrict__ res, int M, int N, int ldc, int ldres, int gate_rows,
+                                                        const bf16* __restrict__ res, int M, int N, int ldc, int ldres, int gate_rows, int res_rows,
                                                         int tiles_m, int tiles_n, int t_full, int split, const float* __restrict__ ws) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -504,19 +504,19 @@ __global__ __launch_bounds__(256) void gemm256w4_reduce(bf16* __restrict__ C, co
   }
   __syncthreads();
   epi_chunks<EPI, 8>(smem, QROW, [&](int tt, int& rl, int& cc, int& mr) { const int c = tid + 256 * tt; rl = mr = c >> 4; cc = c & 15; }, m0, n0,
-                     C, gate, res, M, N, ldc, ldres, gate_rows);
+                     C, gate, res, M, N, ldc, ldres, gate_rows, res_rows);
 }
 
 }  // namespace
 
 // nsa: 3 = A ring of three K-tile stages (160 KiB of LDS), 2 = two (128 KiB), 1 = three stages and ONE barrier per K-tile
 extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                  int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
                                  hipStream_t stream);
 
 static int w4_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate, const void* res, int M, int N,
-                     int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int a_seg_k, long long a_seg_stride, int w_seg_k,
+                     int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows, int a_seg_k, long long a_seg_stride, int w_seg_k,
                      long long w_seg_stride, int a_seg2_k, long long a_seg2_stride, int nsa, int ng, float* ws, size_t ws_bytes,
                      hipStream_t stream) {
   const bool seg2 = a_seg2_k > 0;
@@ -526,12 +526,12 @@ static int w4_launch(const void* A, const void* W, void* C, const float* bias, i
     return CE_ERR_ARG;
   // the prefetched gated-residual epilogue holds ONE or TWO samples' gate rows per tile: gate rows shorter than a tile -> 8-wave kernel
   // ... and stores through a 32-bit-offset buffer descriptor
-  if (epilogue == EPI_GATE_RES && ((gate != nullptr && gate_rows > 0 && gate_rows < BM) || (long long)M * ldc * 2 >= (1ll << 32)))
-    return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, w_seg_k,
+  if (epilogue == EPI_GATE_RES && ((gate != nullptr && gate_rows > 0 && gate_rows < BM) || (res_rows > 0 && res_rows < BM) || (long long)M * ldc * 2 >= (1ll << 32)))
+    return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, a_seg_k, a_seg_stride, w_seg_k,
                              w_seg_stride, ws, ws_bytes, stream);
   // (the register-direct epilogue of the plain 256 x 256 tile stores through 32-bit buffer offsets and reads four row biases at once)
   if (ng == 8 && ((long long)M * ldc * 2 >= (1ll << 32) || (epilogue == EPI_BIAS_ROW && (M & 3))))
-    return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, w_seg_k,
+    return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, a_seg_k, a_seg_stride, w_seg_k,
                              w_seg_stride, ws, ws_bytes, stream);
   const int bn = 32 * ng;
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + bn - 1) / bn;
@@ -580,7 +580,7 @@ static int w4_launch(const void* A, const void* W, void* C, const float* bias, i
     }
 #define CE_LAUNCH_SEG2(E, NGV, LDS)                                                                                                     \
   hipLaunchKernelGGL((gemm_bf16_w4<E, 2, false, true, NGV>), grid, block, LDS, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                     (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws, a_seg_magic,   \
+                     (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws, a_seg_magic,   \
                      a_seg_extra, w_seg_magic, w_seg_extra, a_seg2_magic, a_seg2_extra)
     if (epilogue == EPI_BIAS) {
       if (ng == 8) CE_LAUNCH_SEG2(EPI_BIAS, 8, lds2); else if (ng == 4) CE_LAUNCH_SEG2(EPI_BIAS, 4, lds2n); else CE_LAUNCH_SEG2(EPI_BIAS, 3, lds2m);
@@ -603,19 +603,19 @@ static int w4_launch(const void* A, const void* W, void* C, const float* bias, i
     }                                                                                                                      \
     if (nsa == 1)                                                                                                          \
       hipLaunchKernelGGL((gemm_bf16_w4<E, 3, true>), grid, block, lds3, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws, \
+                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws, \
                          a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra, 0u, 0u);                                      \
     else if (nsa == 3)                                                                                                     \
       hipLaunchKernelGGL((gemm_bf16_w4<E, 3, false>), grid, block, lds3, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws, \
+                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws, \
                          a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra, 0u, 0u);                                      \
     else                                                                                                                   \
       hipLaunchKernelGGL((gemm_bf16_w4<E, 2, false>), grid, block, lds2, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws, \
+                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws, \
                          a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra, 0u, 0u);                                      \
     if (tail)                                                                                                              \
       hipLaunchKernelGGL((gemm256w4_reduce<E>), dim3(4 * tail), block, 128 * QROW, stream, (bf16*)C, bias, gate,           \
-                         (const bf16*)res, M, N, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws);           \
+                         (const bf16*)res, M, N, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws);           \
   } while (0)
   switch (epilogue) {
     case EPI_BIAS: CE_LAUNCH(EPI_BIAS); break;
@@ -630,10 +630,10 @@ static int w4_launch(const void* A, const void* W, void* C, const float* bias, i
 }
 
 extern "C" int ce_gemm256w4_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                   const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                                   const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                    int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, int nsa, float* ws,
                                    size_t ws_bytes, hipStream_t stream) {
-  return w4_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, w_seg_k, w_seg_stride,
+  return w4_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, a_seg_k, a_seg_stride, w_seg_k, w_seg_stride,
                    0, 0, nsa, 8, ws, ws_bytes, stream);
 }
 
@@ -643,14 +643,14 @@ extern "C" int ce_gemm256w4_launch(const void* A, const void* W, void* C, const 
 extern "C" int ce_gemm256w4_seg2_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const void* res, int M, int N,
                                         int K, int lda, int ldw, int ldc, int ldres, int a_seg_k, long long a_seg_stride, int a_seg2_k,
                                         long long a_seg2_stride, int n_tile, hipStream_t stream) {
-  return w4_launch(A, W, C, bias, epilogue, nullptr, res, M, N, K, lda, ldw, ldc, ldres, 0, a_seg_k, a_seg_stride, 0, 0, a_seg2_k, a_seg2_stride,
+  return w4_launch(A, W, C, bias, epilogue, nullptr, res, M, N, K, lda, ldw, ldc, ldres, 0, 0, a_seg_k, a_seg_stride, 0, 0, a_seg2_k, a_seg2_stride,
                    2, n_tile / 32, nullptr, 0, stream);
 }
 
 // The split-K reduce of this file's slab layout for another producer (ce_gemm_fp8w4.hip: the same wave tiles and raster, slabs already
 // scaled): sums the `split` slabs of each of the `tail` tiles, adds the bias, applies the epilogue.
 extern "C" int ce_gemm256w4_reduce_launch(int epilogue, void* C, const float* bias, const float* gate, const void* res, int M, int N, int ldc,
-                                          int ldres, int gate_rows, int tiles_m, int tiles_n, int t_full, int split, const float* ws, int tail,
+                                          int ldres, int gate_rows, int res_rows, int tiles_m, int tiles_n, int t_full, int split, const float* ws, int tail,
                                           hipStream_t stream) {
   static bool done_[CE_MAX_DEVICES][8] = {};
   bool* done = done_[ce_device_slot()];
@@ -661,7 +661,7 @@ extern "C" int ce_gemm256w4_reduce_launch(int epilogue, void* C, const float* bi
       done[E] = true;                                                                                                        \
     }                                                                                                                        \
     hipLaunchKernelGGL((gemm256w4_reduce<E>), dim3(4 * tail), dim3(256), 128 * QROW, stream, (bf16*)C, bias, gate, (const bf16*)res, M, N, \
-                       ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, ws);                                          \
+                       ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full, split, ws);                                          \
   } while (0)
   switch (epilogue) {
     case EPI_BIAS: CE_RED(EPI_BIAS); break;

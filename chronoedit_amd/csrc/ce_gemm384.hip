@@ -68,7 +68,7 @@ template <int EPI, int NF = 12>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_bf16_384(
     const bf16* __restrict__ A, const bf16* __restrict__ W, bf16* __restrict__ C, const float* __restrict__ bias,
     const float* __restrict__ gate, const bf16* __restrict__ res, int M, int N, int K, int lda, int ldw, int ldc, int ldres,
-    int gate_rows, int tiles_m, int tiles_n, int t_full, int split, float* __restrict__ ws, uint32_t a_seg_magic,
+    int gate_rows, int res_rows, int tiles_m, int tiles_n, int t_full, int split, float* __restrict__ ws, uint32_t a_seg_magic,
     uint32_t a_seg_extra, uint32_t w_seg_magic, uint32_t w_seg_extra) {
   constexpr int BM = T384<NF>::BM, A_TILE = T384<NF>::A_TILE, STAGE = T384<NF>::STAGE, NG = T384<NF>::NG, NP = T384<NF>::NP;
   static_assert(NF >= 9 && NF <= 12, "the W fragments of the second k-step are read in groups 1..8 of the first; rows 8.. of the accumulator live in 128 VGPRs");
@@ -352,9 +352,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   int g_switch = 0x7fffffff;
   constexpr int RA = 2;  // row fragments of residual in flight ahead of the one being finished (4 x 16 B per lane each)
   u32x4 rv[RA + 1][4];
+  const ResWrap rwrap = res_wrap(m0, res_rows);
   auto res_load = [&](int f, u32x4* dst) __attribute__((always_inline)) {
 #pragma unroll
-    for (int jj = 0; jj < 4; ++jj) dst[jj] = *reinterpret_cast<const u32x4*>(res + (size_t)min(row_base + f * 16 + jj, M - 1) * ldres + colc);
+    for (int jj = 0; jj < 4; ++jj) dst[jj] = *reinterpret_cast<const u32x4*>(res + (size_t)res_row(min(row_base + f * 16 + jj, M - 1), rwrap) * ldres + colc);
   };
   if (EPI == EPI_GATE_RES) {
     gA[0] = gA[1] = gB[0] = gB[1] = f32x4{1.f, 1.f, 1.f, 1.f};
@@ -421,7 +422,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // grid = 4 x the number of tail tiles, 256 threads: thread (w, lane) takes accumulator rows f = 3w .. 3w + 2 of the quadrant.
 template <int EPI, int NF = 12>
 __global__ __launch_bounds__(256) void gemm384_reduce(bf16* __restrict__ C, const float* __restrict__ bias, const float* __restrict__ gate,
-                                                      const bf16* __restrict__ res, int M, int N, int ldc, int ldres, int gate_rows,
+                                                      const bf16* __restrict__ res, int M, int N, int ldc, int ldres, int gate_rows, int res_rows,
                                                       int tiles_m, int tiles_n, int t_full, int split, const float* __restrict__ ws) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -454,27 +455,27 @@ __global__ __launch_bounds__(256) void gemm384_reduce(bf16* __restrict__ C, cons
   }
   __syncthreads();
   epi_chunks<EPI, NF>(smem, QROW, [&](int tt, int& rl, int& cc, int& mr) { const int c = tid + 256 * tt; rl = mr = c >> 4; cc = c & 15; }, m0, n0,
-                      C, gate, res, M, N, ldc, ldres, gate_rows);
+                      C, gate, res, M, N, ldc, ldres, gate_rows, res_rows);
 }
 
 }  // namespace
 
 extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                  int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
                                  hipStream_t stream);
 
 template <int NF>
 static int gemm384_launch_impl(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate, const void* res, int M, int N,
-                               int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int a_seg_k, long long a_seg_stride, int w_seg_k,
+                               int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows, int a_seg_k, long long a_seg_stride, int w_seg_k,
                                long long w_seg_stride, float* ws, size_t ws_bytes, hipStream_t stream) {
   constexpr int BM = T384<NF>::BM, STAGE = T384<NF>::STAGE;
   if (epilogue == EPI_BIAS_T) {  // (C is [N][ldc]; no other kernel stores the transpose: the dispatcher only comes here with a shape this one takes)
     if ((M & 7) || (long long)N * ldc * 2 >= (1ll << 32) || !bias) return CE_ERR_SHAPE;
   } else
-  if ((epilogue == EPI_GATE_RES && gate != nullptr && gate_rows > 0 && gate_rows < BM) || (long long)M * ldc * 2 >= (1ll << 32) ||
+  if ((epilogue == EPI_GATE_RES && gate != nullptr && gate_rows > 0 && gate_rows < BM) || (res_rows > 0 && res_rows < BM) || (long long)M * ldc * 2 >= (1ll << 32) ||
       (epilogue == EPI_BIAS_ROW && (M & 3)))  // (the register-direct epilogue stores through 32-bit buffer offsets and reads four row biases at once)
-    return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, w_seg_k,
+    return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, a_seg_k, a_seg_stride, w_seg_k,
                              w_seg_stride, ws, ws_bytes, stream);
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const int nwg = tiles_m * tiles_n, kt = K / BK;
@@ -507,11 +508,11 @@ static int gemm384_launch_impl(const void* A, const void* W, void* C, const floa
       attr_done[E] = true;                                                                                                 \
     }                                                                                                                      \
     hipLaunchKernelGGL((gemm_bf16_384<E, NF>), grid, block, lds, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                       (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws, \
+                       (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws, \
                        a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra);                                                \
     if (tail)                                                                                                              \
       hipLaunchKernelGGL((gemm384_reduce<E, NF>), dim3(4 * tail), block, 16 * NF * QROW, stream, (bf16*)C, bias, gate,     \
-                         (const bf16*)res, M, N, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws);           \
+                         (const bf16*)res, M, N, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws);           \
   } while (0)
   switch (epilogue) {
     case EPI_BIAS: CE_LAUNCH(EPI_BIAS); break;
@@ -527,7 +528,7 @@ static int gemm384_launch_impl(const void* A, const void* W, void* C, const floa
         t_done = true;
       }
       hipLaunchKernelGGL((gemm_bf16_384<EPI_BIAS_T, NF>), grid, block, lds, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, (const bf16*)res,
-                         M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full2, split, ws, a_seg_magic, a_seg_extra, w_seg_magic,
+                         M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws, a_seg_magic, a_seg_extra, w_seg_magic,
                          w_seg_extra);
       break;
     }
@@ -538,18 +539,18 @@ static int gemm384_launch_impl(const void* A, const void* W, void* C, const floa
 }
 
 extern "C" int ce_gemm384_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                  int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
                                  hipStream_t stream) {
-  return gemm384_launch_impl<12>(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, w_seg_k,
+  return gemm384_launch_impl<12>(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, a_seg_k, a_seg_stride, w_seg_k,
                                  w_seg_stride, ws, ws_bytes, stream);
 }
 
 // the 288 x 256 macro tile (NF = 9): same kernel, 144 x 128 wave tiles
 extern "C" int ce_gemm288_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows,
+                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                  int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
                                  hipStream_t stream) {
-  return gemm384_launch_impl<9>(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, a_seg_k, a_seg_stride, w_seg_k,
+  return gemm384_launch_impl<9>(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, a_seg_k, a_seg_stride, w_seg_k,
                                 w_seg_stride, ws, ws_bytes, stream);
 }

@@ -17,6 +17,25 @@
 
 namespace {
 
+// Residual row period of the gated-residual epilogue (res_rows of ce_gemm_bf16_res): output row m reads residual row m % res_rows, 0 = row m
+// itself - one residual shared by the samples stacked along M.  The register-direct epilogues of the large tiles take the remainder once
+// per tile: with res_rows >= the tile height (what their launchers admit; shorter periods go to the 8-wave kernel, like short gate
+// rows) a tile's rows span at most two periods, so a row is the tile's base remainder plus its offset, less one period if it wraps.
+struct ResWrap {
+  int base;  // m0 - m0 % res_rows (0 without a period)
+  int per;   // res_rows (INT_MAX without a period: never wraps)
+};
+__device__ __forceinline__ ResWrap res_wrap(int m0, int res_rows) {
+  ResWrap w;
+  w.base = res_rows > 0 ? (m0 / res_rows) * res_rows : 0;
+  w.per = res_rows > 0 ? res_rows : 0x7fffffff;
+  return w;
+}
+__device__ __forceinline__ int res_row(int m, ResWrap w) {
+  const int r = m - w.base;
+  return r >= w.per ? r - w.per : r;
+}
+
 // The second half of an epilogue pass for NCH 16-byte chunks per thread (8 bf16 of one row each, already "acc + bias" rounded
 // to bf16, staged row-contiguous in LDS): activation or gated residual, then the global store.  The residual and gate loads
 // of ALL the thread's chunks are issued first, unconditionally, on clamped addresses, and only the stores are predicated:
@@ -25,7 +44,7 @@ namespace {
 template <int EPI, int NCH, bool HAS_GATE, typename RowCol>
 __device__ __forceinline__ void epi_chunks_impl(const unsigned char* smem, int row_bytes, RowCol rowcol, int m0, int n0,
                                                 bf16* __restrict__ C, const float* __restrict__ gate, const bf16* __restrict__ res,
-                                                int M, int N, int ldc, int ldres, int gate_rows) {
+                                                int M, int N, int ldc, int ldres, int gate_rows, int res_rows) {
   u32x4 v[NCH], rv[NCH];
   f32x4 g0[NCH], g1[NCH];
   int ms[NCH], ns[NCH];
@@ -38,7 +57,7 @@ __device__ __forceinline__ void epi_chunks_impl(const unsigned char* smem, int r
     v[t] = *reinterpret_cast<const u32x4*>(smem + rl * row_bytes + cc * 16);
     if (EPI == EPI_GATE_RES) {
       const int mc = min(ms[t], M - 1), nc = min(ns[t], N - 8);
-      rv[t] = *reinterpret_cast<const u32x4*>(res + (size_t)mc * ldres + nc);
+      rv[t] = *reinterpret_cast<const u32x4*>(res + (size_t)(res_rows > 0 ? mc % res_rows : mc) * ldres + nc);  // residual row period
       if (HAS_GATE) {
         const float* gp = gate + (gate_rows > 0 ? (size_t)(mc / gate_rows) * N : 0) + nc;  // per-sample gate rows
         g0[t] = *reinterpret_cast<const f32x4*>(gp);
@@ -72,11 +91,11 @@ __device__ __forceinline__ void epi_chunks_impl(const unsigned char* smem, int r
 template <int EPI, int NCH, typename RowCol>
 __device__ __forceinline__ void epi_chunks(const unsigned char* smem, int row_bytes, RowCol rowcol, int m0, int n0,
                                            bf16* __restrict__ C, const float* __restrict__ gate, const bf16* __restrict__ res,
-                                           int M, int N, int ldc, int ldres, int gate_rows) {
+                                           int M, int N, int ldc, int ldres, int gate_rows, int res_rows = 0) {
   if (EPI == EPI_GATE_RES && gate != nullptr)
-    epi_chunks_impl<EPI, NCH, true>(smem, row_bytes, rowcol, m0, n0, C, gate, res, M, N, ldc, ldres, gate_rows);
+    epi_chunks_impl<EPI, NCH, true>(smem, row_bytes, rowcol, m0, n0, C, gate, res, M, N, ldc, ldres, gate_rows, res_rows);
   else
-    epi_chunks_impl<EPI, NCH, false>(smem, row_bytes, rowcol, m0, n0, C, gate, res, M, N, ldc, ldres, gate_rows);
+    epi_chunks_impl<EPI, NCH, false>(smem, row_bytes, rowcol, m0, n0, C, gate, res, M, N, ldc, ldres, gate_rows, res_rows);
 }
 
 }  // namespace

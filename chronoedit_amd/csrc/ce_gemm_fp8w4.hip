@@ -859,7 +859,7 @@ __global__ __launch_bounds__(256) void gemm_fp8w4_reduce_gelu_q(unsigned char* _
 }  // namespace
 
 extern "C" int ce_gemm256w4_reduce_launch(int epilogue, void* C, const float* bias, const float* gate, const void* res, int M, int N, int ldc,
-                                          int ldres, int gate_rows, int tiles_m, int tiles_n, int t_full, int split, const float* ws, int tail,
+                                          int ldres, int gate_rows, int res_rows, int tiles_m, int tiles_n, int t_full, int split, const float* ws, int tail,
                                           hipStream_t stream);
 
 // The split-K plan of ce_split_k, kept only where it pays.  An fp8 round is short (1.7 us per K-tile): cutting the last round only pays when
@@ -918,7 +918,7 @@ static int fp8w4_launch(bool mx, const void* Aq, const void* Wq, void* C, const 
   }
 #undef F8_LAUNCH
   if (tail) {
-    const int rc = ce_gemm256w4_reduce_launch(epilogue, C, bias, gate, res, M, N, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, ws,
+    const int rc = ce_gemm256w4_reduce_launch(epilogue, C, bias, gate, res, M, N, ldc, ldres, gate_rows, 0, tiles_m, tiles_n, t_full, split, ws,
                                               tail, stream);
     if (rc != CE_OK) return rc;
   }

@@ -188,8 +188,11 @@ def rmsnorm_rope_(x: torch.Tensor, w: torch.Tensor, cos_sin: Optional[torch.Tens
 
 
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
-         epilogue: int = EPI_BIAS, gate: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, gate_rows: int = 0):
+         epilogue: int = EPI_BIAS, gate: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, gate_rows: int = 0,
+         res_rows: int = 0):
     """out[M,N] = epilogue(a[M,K] @ w[N,K]^T + bias).  gate [N] or, with gate_rows > 0, [M/gate_rows, N] (one per sample).
+    res_rows > 0 (EPI_GATE_RES): res is [res_rows, N] and output row m adds residual row m % res_rows - samples stacked along M that share
+    one residual (ce_gemm_bf16_res); res must not overlap out then.
     a may be a 3-D [S, M, K/S] tensor (contiguous): the K-segmented operand an all-to-all leaves behind (a_seg_k of ce_gemm_bf16).
     epilogue EPI_BIAS_T: out is [N, M] and receives the TRANSPOSE of a @ w^T + bias[n] (CE_EPI_BIAS_T)."""
     _dev(a, torch.bfloat16, "a"), _dev(w, torch.bfloat16, "w")
@@ -218,12 +221,25 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: Op
         if res is None:
             raise ValueError("EPI_GATE_RES / EPI_MUL need res")
         _dev(res, torch.bfloat16, "res")
-        _, _, ldres = _rows(res, "res")
+        Mr, _, ldres = _rows(res, "res")
         if gate is not None:
             _dev(gate, torch.float32, "gate")
             assert gate.is_contiguous() and gate.numel() == (N if gate_rows <= 0 else (M + gate_rows - 1) // gate_rows * N)
+        if res_rows > 0:
+            if epilogue != EPI_GATE_RES or Mr < min(res_rows, M):
+                raise ValueError(f"gemm: res_rows={res_rows} needs EPI_GATE_RES and a residual of at least that many rows (got {Mr})")
+            lo, hi = res.data_ptr(), res.data_ptr() + ((min(res_rows, M) - 1) * ldres + N) * 2
+            if lo < out.data_ptr() + ((M - 1) * ldc + N) * 2 and out.data_ptr() < hi:
+                raise ValueError("gemm: a residual with a row period must not overlap the output")
+    elif res_rows > 0:
+        raise ValueError("gemm: res_rows needs EPI_GATE_RES")
     ws, ws_bytes = _gemm_scratch(a.device)
     st = _prof_begin()
+    if res_rows > 0:
+        _check(lib().ce_gemm_bf16_res(_ptr(a), _ptr(w), _ptr(out), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K, lda, ldw, ldc, ldres,
+                                      int(gate_rows), int(res_rows), int(a_seg_k), int(a_seg_stride), 0, 0, ws, ws_bytes, _stream()), "ce_gemm_bf16_res")
+        _prof_end(st, f"gemm_{M}x{N}x{K}_epi{epilogue}_res{res_rows}", 2.0 * M * N * K)
+        return out
     _check(lib().ce_gemm_bf16(_ptr(a), _ptr(w), _ptr(out), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K, lda, ldw, ldc, ldres,
                               int(gate_rows), int(a_seg_k), int(a_seg_stride), 0, 0, ws, ws_bytes, _stream()), "ce_gemm_bf16")
     _prof_end(st, f"gemm_{M}x{N}x{K}_epi{epilogue}", 2.0 * M * N * K)
@@ -443,6 +459,41 @@ def attention_2seg_vt(q: torch.Tensor, k1: torch.Tensor, v1t: torch.Tensor, len1
                                            len2, ldk2, v2t.stride(0), int(cols2), _ptr(out), nq, heads, 128, ldq, ldo,
                                            float(scale), batch, _stream()), "ce_attention_2seg_vt_bf16")
     _prof_end(st, f"attention_{nq}x{len1}+{len2}_h{heads}" + (f"_b{batch}" if batch > 1 else ""), 4.0 * nq * (len1 + len2) * 128 * heads * batch)
+    return out
+
+
+def attention_2seg_vt_shared(q: torch.Tensor, k1: torch.Tensor, v1t: torch.Tensor, len1: int, k2: torch.Tensor, v2t: torch.Tensor, len2: int,
+                             heads: int, out: torch.Tensor, batch: int, share_q: bool = False, share1: bool = False, share2: bool = False,
+                             cols1: Optional[int] = None, cols2: Optional[int] = None, scale: Optional[float] = None):
+    """`attention_2seg_vt` for `batch` samples of which some operands are ONE tensor for all samples (ce_attention_2seg_vt_strided_bf16):
+    share_q: q is [nq, H*128] (else [batch*nq, ...]); share1 / share2: the segment's k is [len, H*128] and its v^T holds one sample's keys
+    from column 0 (else stacked as in `attention_2seg_vt`, column stride cols).  out is [batch*nq, H*128], always per sample.  Bit-equal
+    to `attention_2seg_vt` on physically duplicated operands."""
+    for n, t in (("q", q), ("k1", k1), ("v1t", v1t), ("k2", k2), ("v2t", v2t), ("out", out)):
+        _dev(t, torch.bfloat16, n)
+    Nq, Dq, ldq = _rows(q, "q")
+    _, _, ldk1 = _rows(k1, "k1")
+    _, _, ldk2 = _rows(k2, "k2")
+    No, Do, ldo = _rows(out, "out")
+    nq = Nq if share_q else Nq // batch
+    assert Dq == heads * 128 and Do == Dq and v1t.shape[0] == Dq and v2t.shape[0] == Dq and v1t.stride(1) == 1 and v2t.stride(1) == 1
+    assert No == batch * nq and (share_q or Nq == batch * nq), (No, Nq, batch)
+    assert k1.shape[0] == (1 if share1 else batch) * len1 and k2.shape[0] == (1 if share2 else batch) * len2
+    pad = lambda n: (n + 63) // 64 * 64
+    if cols1 is None:
+        cols1 = 0 if share1 else v1t.shape[1] // batch
+    if cols2 is None:
+        cols2 = 0 if share2 else v2t.shape[1] // batch
+    assert v1t.shape[1] >= (0 if share1 else (batch - 1) * cols1) + pad(len1) and v2t.shape[1] >= (0 if share2 else (batch - 1) * cols2) + pad(len2)
+    if scale is None:
+        scale = 128 ** -0.5
+    st = _prof_begin()
+    _check(lib().ce_attention_2seg_vt_strided_bf16(_ptr(q), _ptr(k1), _ptr(v1t), len1, ldk1, v1t.stride(0), int(cols1), _ptr(k2), _ptr(v2t),
+                                                   len2, ldk2, v2t.stride(0), int(cols2), _ptr(out), nq, heads, 128, ldq, ldo, float(scale), batch,
+                                                   0 if share_q else nq, 0 if share1 else len1, 0 if share2 else len2, _stream()),
+           "ce_attention_2seg_vt_strided_bf16")
+    tag = ("_sq" if share_q else "") + ("_s1" if share1 else "") + ("_s2" if share2 else "")
+    _prof_end(st, f"attention_{nq}x{len1}+{len2}_h{heads}" + (f"_b{batch}" if batch > 1 else "") + tag, 4.0 * nq * (len1 + len2) * 128 * heads * batch)
     return out
 
 

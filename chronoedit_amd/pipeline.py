@@ -47,6 +47,22 @@ def make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds):
     return text2, image2
 
 
+@contextlib.contextmanager
+def _shared_inputs(transformer):
+    """Declare, for the forwards inside, that the two halves of the batch carry the same latents, timestep and image embedding and differ in the
+    text context only - what `make_cfg_inputs` and the loops below build.  The engine then runs the pair's common work once
+    (ChronoEditTransformer3DModel.enable_shared_guidance); a transformer without the attribute is left alone.  Cleared on the way out: a
+    forward from anywhere else never shares."""
+    if not hasattr(transformer, "_shared_inputs"):
+        yield
+        return
+    transformer._shared_inputs = True
+    try:
+        yield
+    finally:
+        transformer._shared_inputs = None
+
+
 def _token_sharded(transformer) -> bool:
     sp = getattr(transformer, "_sp", None)
     return sp is not None and sp.sharded
@@ -91,8 +107,9 @@ def denoise_step(transformer: ChronoEditTransformer3DModel, scheduler: FlowUniPC
             # the conditional and unconditional passes (pipeline_chronoedit.py:715-735) as ONE forward over 2B samples:
             # identical per-sample arithmetic, but every weight streams from HBM once and the GEMM grids fill the chip
             text2, image2 = cfg_inputs if cfg_inputs is not None else make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds)
-            out = transformer(torch.cat([latent_model_input, latent_model_input], 0), torch.cat([timestep, timestep], 0),
-                              text2, image2, return_dict=False)[0]
+            with _shared_inputs(transformer):  # both halves of the batch: the same latents, timestep and image embedding (built right here)
+                out = transformer(torch.cat([latent_model_input, latent_model_input], 0), torch.cat([timestep, timestep], 0),
+                                  text2, image2, return_dict=False)[0]
             noise_pred, noise_uncond = out[:B].contiguous(), out[B:].contiguous()
         else:
             noise_pred = transformer(latent_model_input, timestep, prompt_embeds, image_embeds, return_dict=False)[0]
@@ -203,7 +220,8 @@ class GraphedDenoiser:
         tr = self.tr
         if getattr(tr, "cache_context", False) and hasattr(tr, "prime_context"):
             if self.cfg_inputs is not None:
-                tr.prime_context(self.cfg_inputs[0], self.cfg_inputs[1])
+                with _shared_inputs(tr):  # (the entry the captured forward will look up)
+                    tr.prime_context(self.cfg_inputs[0], self.cfg_inputs[1])
             elif not self.guided:
                 tr.prime_context(self.prompt, self.image)
 
@@ -251,7 +269,8 @@ class GraphedDenoiser:
         B = inp.shape[0]
         ts = self.t_buf.expand(B)
         if self.cfg_inputs is not None:
-            out = self.tr(torch.cat([inp, inp], 0), torch.cat([ts, ts], 0), self.cfg_inputs[0], self.cfg_inputs[1], return_dict=False)[0]
+            with _shared_inputs(self.tr):
+                out = self.tr(torch.cat([inp, inp], 0), torch.cat([ts, ts], 0), self.cfg_inputs[0], self.cfg_inputs[1], return_dict=False)[0]
             c, u = out[:B].contiguous(), out[B:].contiguous()
         elif self.guided:
             c = self.tr(inp, ts, self.prompt, self.image, return_dict=False)[0]

@@ -211,6 +211,8 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         self._teacache = None       # TeaCache step skipping (chronoedit_amd.teacache): a TeaCacheConfig once enable_teacache() was called
         self._tea_mode = None       # per forward, set by the denoising loop: None = off (the full forward), "compute" or "skip"
         self.teacache_report = None  # {"plan", "computed", "skipped", "ratios"} of the last edit that ran with TeaCache
+        self.shared_guidance = True  # run what the two samples of a guidance pair share once (enable_shared_guidance; needs _shared_inputs)
+        self._shared_inputs = None  # per forward, set by the denoising loop: True = the two samples have the same latents, timestep and image context
 
     # -- reference-compatible helpers --------------------------------------------------
     @property
@@ -300,7 +302,9 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         """Compute the step-invariant conditioning work for exactly these tensors now, so that the next forward
         that receives them - e.g. the one a hipGraph capture records - finds the cache entry (only with `cache_context`)."""
         if self.cache_context:
-            self.engine()._context(encoder_hidden_states, encoder_hidden_states_image)
+            eng = self.engine()
+            eng._context(encoder_hidden_states, encoder_hidden_states_image,
+                         share_image=eng._share_image(encoder_hidden_states, encoder_hidden_states_image))
 
     def invalidate(self):
         """Call after changing parameters in place (LoRA fuse, load_state_dict): re-packs on next forward."""
@@ -358,6 +362,18 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         summation order inside a key tile."""
         self.cross_vt = bool(on)
         self._engine = None
+        return self
+
+    def enable_shared_guidance(self, on: bool = True):
+        """The guidance pair's common work run once (default on).  `pipeline.denoise_step` / `GraphedDenoiser` feed both samples of the
+        batched pair the same latents, timestep and image embedding and say so per call (`_shared_inputs`); the engine then runs the patch
+        embedding, the modulation tables and block 0 up to its cross-attention on ONE sample's rows, projects the image context once, and
+        fans out at block 0's cross-attention (shared-operand strides of the two-segment attention, residual row period of the GEMM).  Off =
+        the stacked sequence for everything (A/B partner).  Only the unsharded bf16 path with the transposed-V cross-attention shares;
+        every other mode runs the stacked sequence whatever this says.  A direct forward() never shares: nothing is inferred from tensors."""
+        self.shared_guidance = bool(on)
+        if self._engine is not None:
+            self._engine.clear_context_cache()  # (a cached context was projected for the other form)
         return self
 
     def enable_fp8_attention(self, on: bool = True, cross: bool = False):
@@ -483,7 +499,7 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         eng = self._engine
         sp = self._sp
         return (self._gen, None if eng is None else eng.ws_generation, self.gemm_dtype, self.fp8_linears, self.attn_dtype, self.v_transposed, self.cross_vt,
-                self.sp_batch_cfg, bool(getattr(self, "rope_plain_temporal", False)), self.cache_context,
+                self.sp_batch_cfg, bool(getattr(self, "rope_plain_temporal", False)), self.cache_context, self.shared_guidance,
                 None if sp is None else (sp.world, sp.rank), self._cfgp is not None)
 
     @torch.no_grad()
@@ -669,6 +685,7 @@ class DiTEngine:
         self._ctx_refs = None
         self._tea_res = None      # TeaCache: the block stack's residual of the last computed step, bf16 [rows, D] (engine-owned)
         self._tea_valid = False   # ... and whether a computed step of THIS edit has written it
+        self._tap = None          # tests: a dict here receives copies of intermediates of eager (not captured) forwards ("x_pre_cross0": block 0's stream in front of its cross-attention)
 
     def _fuse(self, linears) -> torch.Tensor:
         """cat the [out,in] weights into one buffer and re-point the module parameters at its rows."""
@@ -811,19 +828,41 @@ class DiTEngine:
         return (B * N) in self._ws and (T, Hh // 2, Ww // 2, plain) in self._rope
 
     # -- K3 + K13: conditioning-side work (step-invariant) -------------------------------
-    def _context(self, text: torch.Tensor, image: Optional[torch.Tensor]):
-        """text [B, Tt, text_dim], image [B, Ti, image_dim] -> per-layer cross-attention K/V, samples stacked along rows."""
+    def _cross_fp8(self) -> bool:
+        """Does the cross-attention run under the MXFP8 contract (enable_fp8_attention(cross=True), unsharded)?"""
+        m = self.model
+        return bool(self.fp8_cross and (m._sp is None or not m._sp.sharded) and getattr(m, "_cfgp", None) is None)
+
+    def _cross_vt_form(self, Tt: int, image_given: bool) -> bool:
+        """Does the cross-attention take V^T from the context projections (ce_attention_2seg_vt_bf16)?  ONE predicate for `_context`, which
+        builds the operands, and `_share_image`, which may only share a segment in this form."""
+        return bool(self.cross_vt and image_given and self.has_image and self.all_img and Tt % 8 == 0 and not self._cross_fp8())
+
+    def _share_image(self, text: torch.Tensor, image: Optional[torch.Tensor]) -> bool:
+        """Does this forward project the image context ONCE for its two samples?  Only when the caller declared the pair's inputs shared
+        (model._shared_inputs; never inferred from the tensors) and the launch sequence is the one that can express it: two samples, bf16,
+        unsharded, the transposed-V cross-attention kernel.  Everything else keeps the stacked sequence, silently."""
+        m = self.model
+        return bool(m._shared_inputs and m.shared_guidance and image is not None and text.shape[0] == 2 and image.shape[0] == 2
+                    and self._cross_vt_form(text.shape[1], True) and not self.fp8 and not self.fp8_attn
+                    and self.v_transposed and (m._sp is None or not m._sp.sharded) and getattr(m, "_cfgp", None) is None)
+
+    def _context(self, text: torch.Tensor, image: Optional[torch.Tensor], share_image: bool = False):
+        """text [B, Tt, text_dim], image [B, Ti, image_dim] -> per-layer cross-attention K/V, samples stacked along rows.
+        share_image (_share_image): image[0] stands for every sample - the image embedder and the image K / V^T projections run on its rows only."""
         key = None
         if self.model.cache_context:
             # The entry keeps the keyed tensors alive (self._ctx_refs): an address can then not be handed out again for another
             # edit's conditioning while the entry exists, so (data_ptr, _version, shape) identifies the CONTENT, not just a slot.
             key = (text.data_ptr(), text._version, tuple(text.shape), text.dtype,
-                   None if image is None else (image.data_ptr(), image._version, tuple(image.shape), image.dtype))
+                   None if image is None else (image.data_ptr(), image._version, tuple(image.shape), image.dtype), bool(share_image))
             if key == self._ctx_key:
                 return self._ctx
         keyed = (text, image)
         D = self.D
         B, Tt = text.shape[0], text.shape[1]
+        share_image = bool(share_image and B == 2 and self._cross_vt_form(Tt, image is not None))  # (any other form: stacked, silently)
+        Bi = 1 if share_image else B  # samples of image context actually projected
         text = text.to(torch.bfloat16).reshape(B * Tt, -1)
         if text.shape[1] != self.tx_w1.shape[1]:
             tp = torch.zeros((text.shape[0], self.tx_w1.shape[1]), dtype=torch.bfloat16, device=self.dev)
@@ -837,7 +876,9 @@ class DiTEngine:
             if not self.has_image:
                 raise ValueError("encoder_hidden_states_image given but the model has no image_embedder (image_dim=None)")
             Ti = image.shape[1]
-            image = image.to(torch.bfloat16).reshape(B * Ti, -1).contiguous()
+            if share_image:
+                image = image[:1]
+            image = image.to(torch.bfloat16).reshape(Bi * Ti, -1).contiguous()
             w, b, eps = self.im_n1
             h = ops.ln_affine(image, w, b, eps)
             if h.shape[1] != self.im_w1.shape[1]:
@@ -861,8 +902,8 @@ class DiTEngine:
         eps = self.cfg.eps
         hd = self.cfg.attention_head_dim
         L = self.L
-        f8 = self.fp8_cross and (self.model._sp is None or not self.model._sp.sharded) and getattr(self.model, "_cfgp", None) is None
-        use_vt = self.cross_vt and enc_i is not None and self.all_img and Tt % 8 == 0 and not f8
+        f8 = self._cross_fp8()
+        use_vt = self._cross_vt_form(Tt, enc_i is not None)
         k_t_all = ops.gemm(enc_t, self.w_k_t_all, self.b_k_t_all)  # [B*Tt, L*D]
         k_i_all = v_t_all = v_i_all = v1t = v2t = None
         c1 = c2 = 0
@@ -871,23 +912,23 @@ class DiTEngine:
         if use_vt:
             c1, c2 = Tt, (Ti + 7) // 8 * 8
             ld1 = ((B - 1) * c1 + (Tt + 63) // 64 * 64 + 7) // 8 * 8
-            ld2 = ((B - 1) * c2 + (Ti + 63) // 64 * 64 + 7) // 8 * 8
-            bufs = self._ctx_bufs.get((B, Tt, Ti))
+            ld2 = ((Bi - 1) * c2 + (Ti + 63) // 64 * 64 + 7) // 8 * 8
+            bufs = self._ctx_bufs.get((B, Bi, Tt, Ti))
             if bufs is None:  # zero-filled once: the padding rows / columns are never written afterwards.  Engine-owned (not per call):
                 # a captured step that computes the projections (cache_context off) replays into the same addresses
                 z = lambda *sh: torch.zeros(sh, dtype=torch.bfloat16, device=self.dev)
-                bufs = SimpleNamespace(enc_i_pad=z(B * c2, D), v1t=z(L * D, ld1), v2t=z(L * D, ld2))
-                self._ctx_bufs = dict(list(self._ctx_bufs.items())[-1:] + [((B, Tt, Ti), bufs)])  # the guided pair and the single sample
+                bufs = SimpleNamespace(enc_i_pad=z(Bi * c2, D), v1t=z(L * D, ld1), v2t=z(L * D, ld2))
+                self._ctx_bufs = dict(list(self._ctx_bufs.items())[-1:] + [((B, Bi, Tt, Ti), bufs)])  # the guided pair and the single sample
             v1t, v2t = bufs.v1t, bufs.v2t
             # these engine-owned buffers are about to be rewritten in place, and a cached context of the same shape holds VIEWS into them
             # (its K tensors are its own): whatever was cached is stale from here on - drop it, so a later hit cannot pair the old K with
             # another conditioning's V^T (a call with cache_context off, key None, would otherwise leave the cached key standing)
             self._ctx_key = self._ctx = self._ctx_refs = None
             w, b, eps_i = self.im_n2
-            for bi in range(B):
+            for bi in range(Bi):
                 ops.ln_affine(h_img[bi * Ti:(bi + 1) * Ti], w, b, eps_i, out=bufs.enc_i_pad[bi * c2: bi * c2 + Ti])
             ops.gemm(self.w_v_t_all, enc_t, self.b_v_t_all, out=v1t[:, : B * Tt], epilogue=ops.EPI_BIAS_ROW)
-            ops.gemm(self.w_v_i_all, bufs.enc_i_pad, self.b_v_i_all, out=v2t[:, : B * c2], epilogue=ops.EPI_BIAS_ROW)
+            ops.gemm(self.w_v_i_all, bufs.enc_i_pad, self.b_v_i_all, out=v2t[:, : Bi * c2], epilogue=ops.EPI_BIAS_ROW)
         else:
             v_t_all = ops.gemm(enc_t, self.w_v_t_all, self.b_v_t_all)
             if k_i_all is not None:
@@ -915,7 +956,7 @@ class DiTEngine:
                 if k_i_all is not None:
                     seg_i = ops.rmsnorm_rope_mxfp8(k_i_all[:, cols], p.nk_i, None, hd, eps) + ops.v_mxfp8_transpose(v_i_all[:, cols], Ti, B, self.H)
                 kv.append((seg_t, seg_i))
-        ctx = SimpleNamespace(kv=kv, Tt=Tt, Ti=Ti, vt=use_vt, c1=c1, c2=c2, f8=f8)
+        ctx = SimpleNamespace(kv=kv, Tt=Tt, Ti=Ti, vt=use_vt, c1=c1, c2=c2, f8=f8, img_shared=bool(share_image))
         if key is not None:
             self._ctx_key, self._ctx, self._ctx_refs = key, ctx, keyed
         return ctx
@@ -998,14 +1039,30 @@ class DiTEngine:
         timestep = timestep.to(device=self.dev, dtype=torch.float32 if timestep.is_floating_point() else torch.int64).contiguous()
         rows = [slice(b * Nl, (b + 1) * Nl) for b in range(B)]
 
+        # The guidance pair with shared inputs (model._shared_inputs, declared by the denoising loop): the image context is projected once
+        # (share_img: every block's cross-attention reads one image segment), and everything in front of block 0's cross-attention - patch
+        # embedding, modulation tables, block 0's self-attention half - runs on ONE sample's N rows (share), in `xs`.  xs borrows the head of
+        # the FFN hidden buffer, which nothing uses before block 0's FFN: the out-projection of block 0's cross-attention reads it as the residual
+        # of BOTH samples (row period N) while it writes the stacked stream ws.x - the fan-out, without a copy.  A skipped TeaCache step has
+        # no block 0: it runs as before.
+        if text.shape[0] != B or (image is not None and image.shape[0] != B):
+            raise ValueError("encoder_hidden_states / encoder_hidden_states_image batch size must match hidden_states")
+        share_img = sp is None and B == 2 and self._share_image(text, image)
+        share = share_img and N % 8 == 0 and 2 * self.F >= D and self.model._tea_mode != "skip"
+        xs = ws.ffn.view(-1)[: N * D].view(N, D) if share else None
+
         # K1
-        if sp is None:
+        if share:
+            ops.patchify(hidden[0], self.kpatch, out=ws.cols[rows[0]])
+            ops.gemm(ws.cols[rows[0]], self.w_patch, self.b_patch, out=xs)
+        elif sp is None:
             for b in range(B):
                 ops.patchify(hidden[b], self.kpatch, out=ws.cols[rows[b]])
         else:  # only this rank's token rows (zero rows past the last token: wan_video_new_chronoedit.py:1450-1453)
             for b in range(B):
                 ops.patchify(hidden[b], self.kpatch, out=ws.cols[rows[b]], row0=sp.rank * Nl, nrows=Nl)
-        ops.gemm(ws.cols, self.w_patch, self.b_patch, out=ws.x)
+        if not share:
+            ops.gemm(ws.cols, self.w_patch, self.b_patch, out=ws.x)
 
         # TeaCache (per-call mode, set by the denoising loop; None = off: the launch sequence below is exactly the plain forward's).  compute: the
         # tokens in front of the blocks are saved, and turned into the stack's residual behind them.  skip: that residual is added to
@@ -1020,13 +1077,17 @@ class DiTEngine:
                 if self._tea_res is None or self._tea_res.shape[0] != B * Nl or not self._tea_valid:
                     raise RuntimeError(f"TeaCache: a skipped step needs the residual of a computed step with the same {B * Nl} token rows")
                 ops.tea_apply_(ws.x, self._tea_res)
+            elif share:  # the residual buffer stays [2 N, D]: both samples' tokens in front of the blocks are xs
+                tr = self.tea_reserve(B * Nl)
+                tr[rows[0]].copy_(xs)
+                tr[rows[1]].copy_(xs)
             else:
                 self.tea_reserve(B * Nl).copy_(ws.x)
         skip = tea == "skip"
 
         # K2 per sample: sinusoid -> time_embedder (fp32) -> temb (bf16-rounded) -> silu -> time_proj -> AdaLN tables
         mods, gates1, gates2, mods_out = [], [], [], []
-        for b in range(B):
+        for b in range(1 if share else B):
             sin = ops.timestep_sinusoid(timestep[b : b + 1], cfg.freq_dim)
             h1 = ops.gemv(self.te_w1, sin, self.te_b1, flags=2)
             temb = ops.gemv(self.te_w2, h1, self.te_b2, flags=4)
@@ -1034,6 +1095,8 @@ class DiTEngine:
                 tproj = ops.gemv(self.tp_w, temb, self.tp_b, flags=1 | 4)  # [6*D]
                 mods.append(ops.modulation(self.tables, tproj.view(6, D), one_mask=0b010010))  # [L,6,D]: shift,1+scale,gate,...
             mods_out.append(ops.modulation(self.table_out, temb.view(1, D), one_mask=0b10))  # [1,2,D]: shift, 1+scale
+        if share:  # one timestep: one set of tables, stacked twice for the per-sample row strides of the launches behind the fan-out
+            mods, mods_out = mods * B, mods_out * B
         if not skip:
             mod = torch.stack(mods, dim=1).contiguous()  # [L, B, 6, D]: per-sample AdaLN rows (ab_rows / gate_rows = tokens per sample)
         mod_out = torch.stack(mods_out, dim=0).contiguous()  # [B, 1, 2, D]
@@ -1044,15 +1107,37 @@ class DiTEngine:
             gate_msa = mod[:, :, 2].contiguous()
             gate_ffn = mod[:, :, 5].contiguous()
 
-        if text.shape[0] != B or (image is not None and image.shape[0] != B):
-            raise ValueError("encoder_hidden_states / encoder_hidden_states_image batch size must match hidden_states")
-        ctx = self._context(text, image)
+        ctx = self._context(text, image, share_image=share_img)
         Tt, Ti = ctx.Tt, ctx.Ti
         grow = Nl if B > 1 else 0
 
         fuse_o = self.mx and self.fuse_attn_quant and D % 128 == 0  # MX: both attention kernels emit the out-projections' fp8 operands themselves
         fuse_o1, fuse_o2 = fuse_o and "o1" in self.fp8_set, fuse_o and "o2" in self.fp8_set  # (only for an out-projection that runs in fp8)
+
+        def ffn(li, p):  # 3. feed-forward
+            if self.mx and self.fuse_quant and "f1" in self.fp8_set and "f2" in self.fp8_set:
+                # MX: the up-projection's bias + GELU epilogue emits the down-projection's fp8 operand and its block scales directly (a
+                # block = 32 consecutive output columns: no row-wide reduction) - no bf16 [N, F] matrix, no quantisation pass
+                aq = ws.a8[:, :D]
+                ops.ln_affine_mxfp8(x, mod[li, 0, 4], mod[li, 0, 3], eps, out=aq, scale=ws.s8, ab_rows=Nl, ab_stride=6 * D)
+                ops.gemm_mxfp8_gelu_quant(aq, ws.s8, *p.q_f1, p.b_f1, out=ws.a8b, scale=ws.s8b)
+                ops.gemm_mxfp8(ws.a8b, ws.s8b, *p.q_f2, p.b_f2, out=x, epilogue=ops.EPI_GATE_RES,
+                               gate=gate_ffn[li] if B > 1 else mods[0][li, 5], res=x, gate_rows=grow)
+            else:
+                self._ln_linear(ws, x, mod[li, 0, 4], mod[li, 0, 3], p, "f1", ws.ffn, ab_rows=Nl, ab_stride=6 * D, epilogue=ops.EPI_BIAS_GELU)
+                self._linear(ws, ws.ffn, p, "f2", x, epilogue=ops.EPI_GATE_RES, gate=gate_ffn[li] if B > 1 else mods[0][li, 5],
+                             res=x, gate_rows=grow)
+
         for li, p in enumerate(self.blk):
+            if share and li == 0:
+                # block 0 up to its cross-attention on the one shared sample (the B = 1 launches on N rows), then the fan-out: queries shared,
+                # text keys per sample, image keys shared, output per sample; the out-projection adds the shared residual to both
+                self._block0_shared_prefix(ws, xs, p, mods[0], cs, N)
+                k_t, v_t, k_i, v_i = ctx.kv[0]
+                ops.attention_2seg_vt_shared(ws.q2[:N], k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, share_q=True, share2=True, cols1=ctx.c1)
+                ops.gemm(ws.att, p.w_o2, p.b_o2, out=x, epilogue=ops.EPI_GATE_RES, gate=None, res=xs, res_rows=N)
+                ffn(li, p)
+                continue
             q_o1 = False
             # 1. self-attention
             if sp is None and self.fp8_attn:  # MXFP8: the norm / RoPE pass and a V^T pass write the quantised operands
@@ -1092,6 +1177,8 @@ class DiTEngine:
                 att = self._self_attention_ulysses(ws, sp, x, mod[li, 0, 1], mod[li, 0, 0], p, cs, N, Nl, B)
             self._linear(ws, att, p, "o1", x, quantised=q_o1, epilogue=ops.EPI_GATE_RES, gate=gate_msa[li] if B > 1 else mods[0][li, 2],
                          res=x, gate_rows=grow)
+            if self._tap is not None and li == 0 and not torch.cuda.is_current_stream_capturing():
+                self._tap["x_pre_cross0"] = x.clone()
             # 2. cross-attention (text + image segments)
             if p.n2w is not None:
                 self._ln_linear(ws, x, p.n2w, p.n2b, p, "q2", ws.q2)
@@ -1119,6 +1206,8 @@ class DiTEngine:
                 pass
             elif ctx.vt and fuse_o2:
                 ops.attention_2seg_vt(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, batch=B, cols1=ctx.c1, cols2=ctx.c2, out8=ws.a8[:, :D], scale8=ws.s8)
+            elif ctx.img_shared:  # one image segment for both samples
+                ops.attention_2seg_vt_shared(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, share2=True, cols1=ctx.c1)
             elif ctx.vt:  # both segments' K and V^T tiles by LDS-DMA (v_t / v_i are V^T row blocks of this layer)
                 ops.attention_2seg_vt(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, cols1=ctx.c1, cols2=ctx.c2)
             elif k_i is not None:
@@ -1127,24 +1216,41 @@ class DiTEngine:
                 ops.attention(ws.q2, k_t, v_t, H, out=ws.att, batch=B)
             if k_t is not None:
                 self._linear(ws, ws.att, p, "o2", x, quantised=q_o2, epilogue=ops.EPI_GATE_RES, gate=None, res=x)
-            # 3. feed-forward
-            if self.mx and self.fuse_quant and "f1" in self.fp8_set and "f2" in self.fp8_set:
-                # MX: the up-projection's bias + GELU epilogue emits the down-projection's fp8 operand and its block scales directly (a
-                # block = 32 consecutive output columns: no row-wide reduction) - no bf16 [N, F] matrix, no quantisation pass
-                aq = ws.a8[:, :D]
-                ops.ln_affine_mxfp8(x, mod[li, 0, 4], mod[li, 0, 3], eps, out=aq, scale=ws.s8, ab_rows=Nl, ab_stride=6 * D)
-                ops.gemm_mxfp8_gelu_quant(aq, ws.s8, *p.q_f1, p.b_f1, out=ws.a8b, scale=ws.s8b)
-                ops.gemm_mxfp8(ws.a8b, ws.s8b, *p.q_f2, p.b_f2, out=x, epilogue=ops.EPI_GATE_RES,
-                               gate=gate_ffn[li] if B > 1 else mods[0][li, 5], res=x, gate_rows=grow)
-            else:
-                self._ln_linear(ws, x, mod[li, 0, 4], mod[li, 0, 3], p, "f1", ws.ffn, ab_rows=Nl, ab_stride=6 * D, epilogue=ops.EPI_BIAS_GELU)
-                self._linear(ws, ws.ffn, p, "f2", x, epilogue=ops.EPI_GATE_RES, gate=gate_ffn[li] if B > 1 else mods[0][li, 5],
-                             res=x, gate_rows=grow)
+            ffn(li, p)
 
         if tea is not None:  # the saved tokens become the residual of this (computed) step
             ops.tea_store_(x, self._tea_res)
             self._tea_valid = True
         return self._head(ws, x, mod_out, sp, B, T, Hh, Ww, N, Nl, rows)
+
+    def _block0_shared_prefix(self, ws, xs, p, mods0, cs, N: int):
+        """Block 0 from its first LayerNorm to the normed cross-attention queries for ONE sample's N rows (the guidance pair's shared prefix):
+        the launches a B = 1 forward makes, on the first N rows of the workspaces; xs [N, D] is updated in place, ws.q2[:N] receives the queries."""
+        D, H, hd, eps = self.D, self.H, self.cfg.attention_head_dim, self.cfg.eps
+        h, qkv = ws.h[:N], ws.qkv[:N]
+        # V^T goes into sample 0's columns [0, N) of the stacked pair's buffer.  When N % 64 != 0 the kernel's last key strip also reads columns
+        # [N, pad64(N)): zeros after the fill below, sample 1's V^T of the previous stacked block from then on.  That is exactly what sample 0 of
+        # every stacked launch meets (ce_attention_vt_bf16: columns past a sample's keys are finite and meet P = 0), so the result is bit-equal
+        # to a B = 1 forward's, whose strip holds zeros - as long as those columns are finite, which zeros and projected values are.
+        if getattr(ws, "vt", None) is None:
+            ws.vt = torch.zeros((D, ops.vt_columns(2 * N)), dtype=torch.bfloat16, device=self.dev)
+        ops.ln_affine(xs, mods0[0, 1], mods0[0, 0], eps, out=h, ab_rows=N, ab_stride=6 * D)
+        ops.gemm(h, p.w_qkv[: 2 * D], p.b_qkv[: 2 * D], out=qkv[:, : 2 * D])
+        if _VT_GEMM_SWAPPED:
+            ops.gemm(p.w_qkv[2 * D :], h, p.b_qkv[2 * D :], out=ws.vt[:, :N], epilogue=ops.EPI_BIAS_ROW)
+        else:
+            ops.gemm(h, p.w_qkv[2 * D :], p.b_qkv[2 * D :], out=ws.vt[:, :N], epilogue=ops.EPI_BIAS_T)
+        ops.rmsnorm_rope_(qkv[:, :D], p.nq1, cs, hd, eps, x2=qkv[:, D : 2 * D], w2=p.nk1)
+        ops.attention_vt(qkv[:, :D], qkv[:, D : 2 * D], ws.vt, H, out=ws.att[:N], batch=1)
+        ops.gemm(ws.att[:N], p.w_o1, p.b_o1, out=xs, epilogue=ops.EPI_GATE_RES, gate=mods0[0, 2], res=xs)
+        if self._tap is not None and not torch.cuda.is_current_stream_capturing():
+            self._tap["x_pre_cross0"] = xs.clone()
+        if p.n2w is not None:
+            ops.ln_affine(xs, p.n2w, p.n2b, eps, out=h)
+            ops.gemm(h, p.w_q2, p.b_q2, out=ws.q2[:N])
+        else:
+            ops.gemm(xs, p.w_q2, p.b_q2, out=ws.q2[:N])
+        ops.rmsnorm_rope_(ws.q2[:N], p.nq2, None, hd, eps)
 
     def _head(self, ws, x, mod_out, sp, B, T, Hh, Ww, N, Nl, rows):
         cfg, D, eps = self.cfg, self.D, self.cfg.eps

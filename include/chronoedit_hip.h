@@ -78,6 +78,15 @@ int ce_gemm_bf16(const void* A, const void* W, void* C, const float* bias, int e
                  int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int a_seg_k, long long a_seg_stride,
                  int w_seg_k, long long w_seg_stride, void* ws, size_t ws_bytes, hipStream_t stream);
 
+/* ce_gemm_bf16 with a ROW PERIOD on the residual of CE_EPI_GATE_RES: output row m reads residual row m % res_rows (res is [res_rows][ldres];
+ * res_rows == 0: row m, i.e. ce_gemm_bf16 itself; other epilogues take res_rows == 0 only).  Samples stacked along M that share one residual
+ * - the guidance pair in front of its first cross-attention - fan out here without a copy: M = 2 n rows of A, n rows of res, 2 n rows of C.
+ * res must NOT alias C then (a row of C would be written while another tile still reads it as the second sample's residual).  The
+ * register-direct epilogues of the large tiles take res_rows >= their tile height; a shorter period runs on the 8-wave 256-tile kernel. */
+int ce_gemm_bf16_res(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate, const void* res,
+                     int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows, int a_seg_k,
+                     long long a_seg_stride, int w_seg_k, long long w_seg_stride, void* ws, size_t ws_bytes, hipStream_t stream);
+
 /* ---- The alternative kernel bodies (A/B partners of the measurement tools and the body-equivalence tests) are NOT selectable through this
  * library: libchronoedit_hip.so picks every kernel from the call's own shape and keeps no state a launch reads.  The
  * selectors live in a second build of the same sources, libchronoedit_hip_diag.so (include/chronoedit_hip_diag.h, -DCE_DIAGNOSTICS), which
@@ -121,6 +130,17 @@ int ce_attention_vt_bf16(const void* Q, const void* K, const void* Vt, int len, 
 int ce_attention_2seg_vt_bf16(const void* Q, const void* K1, const void* V1t, int len1, int ldk1, int ldv1t, int vt_cols1, const void* K2,
                               const void* V2t, int len2, int ldk2, int ldv2t, int vt_cols2, void* O, int Nq, int H, int head_dim, int ldq,
                               int ldo, float softmax_scale, int batch, hipStream_t stream);
+
+/* ce_attention_2seg_vt_bf16 with the samples' strides spelled out, so that an operand can be ONE tensor for all samples: q_rows = rows of Q
+ * between consecutive samples (>= Nq; ce_attention_2seg_vt_bf16 passes Nq) or 0 = every sample reads the same Nq query rows; k1_rows /
+ * k2_rows = rows of K1 / K2 between samples (>= len; the stacked form passes len) or 0 = the segment - K and V^T - is shared (its vt_cols
+ * is ignored, ldv*t >= 64*ceil(len/64)).  O is always per sample, [batch*Nq][ldo].  The two forwards of a guidance step share the image
+ * context in every block (k2_rows = 0) and, in front of the first cross-attention, the queries (q_rows = 0).  Same products in the same
+ * order as the stacked form run on physically duplicated operands: bit-equal results. */
+int ce_attention_2seg_vt_strided_bf16(const void* Q, const void* K1, const void* V1t, int len1, int ldk1, int ldv1t, int vt_cols1,
+                                      const void* K2, const void* V2t, int len2, int ldk2, int ldv2t, int vt_cols2, void* O, int Nq, int H,
+                                      int head_dim, int ldq, int ldo, float softmax_scale, int batch, int q_rows, int k1_rows, int k2_rows,
+                                      hipStream_t stream);
 
 /* ce_attention_2seg_vt_bf16 with its output written as the MX fp8 operand of the out-projection that follows it in the fp8 mode
  * (transformer_chronoedit.py:106 `attn.to_out[0]`; no counterpart in the reference): o8 e4m3 [batch Nq][ldo8] (ldo8 % 16 == 0) + one
