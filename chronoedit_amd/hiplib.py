@@ -93,6 +93,7 @@ SIGNATURES: Dict[str, List] = {
     "ce_tea_rel_l1_bf16": [_P, _I, _I, _P, _P],
     "ce_tea_store_bf16": [_P, _P, _c.c_longlong, _P],
     "ce_tea_apply_bf16": [_P, _P, _c.c_longlong, _P],
+    "ce_tea_store_dist_bf16": [_P, _P, _P, _P, _P, _c.c_longlong, _c.c_longlong, _P],
     "ce_build_info": [],
 }
 # the selectors only libchronoedit_hip_diag.so exports (include/chronoedit_hip_diag.h)

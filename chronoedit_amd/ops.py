@@ -652,6 +652,29 @@ def tea_store_(x: torch.Tensor, r: torch.Tensor):
     return r
 
 
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    pa, pb = a.data_ptr(), b.data_ptr()
+    return pa < pb + b.numel() * b.element_size() and pb < pa + a.numel() * a.element_size()
+
+
+def tea_store_dist_(x: torch.Tensor, r: torch.Tensor, prev: torch.Tensor, sums: torch.Tensor):
+    """tea_store_ (the same bits in r) that also measures the new residual against the previous step's: sums (fp32 [2]) receives
+    sum |r_new - prev| and sum |prev| over all elements, accumulated in fp32 in a fixed order.  prev is only read and overlaps neither r nor x."""
+    n = _tea_pair(x, r)
+    _dev(prev, torch.bfloat16, "prev"), _dev(sums, torch.float32, "sums")
+    if not prev.is_contiguous() or prev.numel() != n:
+        raise ValueError(f"prev: need a contiguous tensor of the size of x / r, got {tuple(prev.shape)} for {n} elements")
+    if not sums.is_contiguous() or sums.numel() != 2:
+        raise ValueError(f"sums: need two contiguous fp32 elements, got shape {tuple(sums.shape)} stride {sums.stride()}")
+    if _overlap(prev, r) or _overlap(prev, x):
+        raise ValueError("prev: the previous residual must not alias r or x (it is read after r has been written)")
+    scratch = torch.empty(2 * 2048, dtype=torch.float32, device=x.device)  # one pair per workgroup, at most 2048 of them (csrc/ce_tea.hip)
+    st = _prof_begin()
+    _check(lib().ce_tea_store_dist_bf16(_ptr(x), _ptr(r), _ptr(prev), _ptr(sums), _ptr(scratch), scratch.numel() * 4, n, _stream()), "ce_tea_store_dist_bf16")
+    _prof_end(st, f"tea_store_dist_{n}", 8.0 * n)
+    return r
+
+
 def tea_apply_(x: torch.Tensor, r: torch.Tensor):
     """x <- bf16(x + r), in place: the cached residual added to the patch-embedded tokens of a skipped step."""
     n = _tea_pair(x, r)

@@ -301,7 +301,7 @@ class GraphedDenoiser:
 def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
             num_inference_steps: int, guidance_scale: float = 5.0, enable_temporal_reasoning: bool = False,
             num_temporal_reasoning_steps: int = 0, use_graph: bool = False, on_step_end=None, interrupted=None, graph_warm=None,
-            teacache=None):
+            teacache=None, teacache_measure: bool = False):
     """The whole loop, including the temporal-reasoning truncation 8 -> 2 latent frames (pipeline_chronoedit.py:700-709).
     on_step_end(i, t, latents) -> replacement latents, a dict with any of latents / prompt_embeds / negative_prompt_embeds, or None
     (the reference's callback_on_step_end hook, :741-749); graph_warm: a set the caller keeps across edits - shapes already run once in
@@ -312,7 +312,13 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     the shorter sequence.
     teacache: a teacache.TeaCacheConfig for this call; None = whatever `transformer.enable_teacache()` set (nothing: no step is skipped).
     The compute / skip plan of the whole edit is made here, before the first step (the truncation step always computes: the 8-frame
-    residual does not fit 2-frame tokens); afterwards `transformer.teacache_report` holds {"plan", "computed", "skipped", "ratios"}."""
+    residual does not fit 2-frame tokens); afterwards `transformer.teacache_report` holds {"plan", "computed", "skipped", "ratios"}.
+    teacache_measure (or `transformer.calibrate_teacache` around the call): calibration instead of skipping.  Every step computes - the
+    latents are the plain loop's - and the pass that stores the block stack's residual also measures its relative L1 distance to the previous
+    step's residual, on the device, into a table read back once after the last step: afterwards `transformer.teacache_measurement` holds
+    {"ratios": teacache_ratios(timesteps), "distances": per step, NaN for step 0 and for the first step after the truncation} - the points
+    teacache.fit_calibration fits.  A measured edit always runs eagerly (`use_graph` is ignored: the table row changes per step, and
+    calibration is offline).  Together with a skip plan (`teacache=` or an enabled TeaCache) it is a ValueError."""
     scheduler.set_timesteps(num_inference_steps, device=latents.device)
     latents = latents.to(torch.float32).contiguous()
     sharded = getattr(transformer, "_cfgp", None) is not None or (_token_sharded(transformer) and not _sharded_batchable(transformer))
@@ -322,6 +328,10 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     if hasattr(transformer, "clear_context_cache"):
         transformer.clear_context_cache()  # a new edit: nothing of the previous edit's conditioning may be reused
     tea = teacache if teacache is not None else getattr(transformer, "_teacache", None)
+    measure = bool(teacache_measure or getattr(transformer, "_tea_measure", False))
+    if measure and tea is not None:
+        raise ValueError("TeaCache: measuring (teacache_measure / calibrate_teacache) and a skip plan (teacache= / enable_teacache) "
+                         "exclude each other: disable_teacache() first")
     tea_plan = None
     if tea is not None:
         from . import teacache as _tea
@@ -333,6 +343,13 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
         tea_plan = _tea.plan_from_ratios(ratios, len(scheduler.timesteps), tea.rel_l1_thresh, tea.coefficients, forced)
         transformer.teacache_report = _tea.report(tea_plan, ratios)
         transformer.engine().tea_drop()  # nothing of the previous edit's residual may be reused
+    if measure:
+        if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
+            raise NotImplementedError("TeaCache with the tokens sharded over ranks or with CFG parallelism is not implemented "
+                                      "(the cached residual is row-local; nothing sharded has been tested with it)")
+        use_graph = False
+        tea_ratios = transformer.teacache_ratios(scheduler.timesteps)
+        transformer.engine().tea_measure_begin(len(scheduler.timesteps))
     graphed = None
     if use_graph and not _capturable(transformer):
         use_graph = False  # a step with torch.distributed exchanges runs eagerly (GraphedDenoiser says why); the pipeline default stays use_graph=True
@@ -366,11 +383,13 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                 if graph_warm is not None:
                     graph_warm.add(warm_key())  # (taken AFTER the construction: the first step of a process creates the engine)
             latents = graphed.step(i)
-        elif tea_plan is None:
+        elif tea_plan is None and not measure:
             latents = denoise_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds,
                                    image_embeds, guidance_scale, batch_cfg=not sharded, cfg_inputs=cfg_inputs)
         else:
-            transformer._tea_mode = "compute" if tea_plan[i] else "skip"
+            if measure:
+                transformer.engine()._tea_row = i  # the row of the sums table this step's forward writes
+            transformer._tea_mode = "measure" if measure else "compute" if tea_plan[i] else "skip"
             try:
                 latents = denoise_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds,
                                        image_embeds, guidance_scale, batch_cfg=True, cfg_inputs=cfg_inputs)
@@ -390,6 +409,10 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
             if new is not None and new is not latents:
                 graphed = None  # the graph is tied to the latents' storage
                 latents = new.to(torch.float32).contiguous()
+    if measure:
+        from .teacache import distances_from_sums
+        sums = transformer.engine().tea_measure_end()  # the one read of the table, after the last step
+        transformer.teacache_measurement = {"ratios": [float(r) for r in tea_ratios], "distances": distances_from_sums(sums.numpy())}
     return latents
 
 
@@ -722,6 +745,22 @@ class ChronoEditPipeline:
     def disable_teacache(self):
         self.transformer.disable_teacache()
         return self
+
+    def calibrate_teacache(self, edits, num_inference_steps: int, guidance_scale: float = 5.0, degree: int = 4, **call_kwargs):
+        """Fit TeaCache's rescaling polynomial on the loaded checkpoint (after `set_adapters`: LoRA changes the network).  edits: a list of
+        keyword dicts, each one edit - the arguments of `edit_tensors` when it carries prompt_embeds, negative_prompt_embeds and image_embeds
+        and nothing `edit_tensors` does not take, of `__call__` otherwise; call_kwargs are added to every edit.  Each edit runs measured (`denoise`: every step computes, eagerly; no frames are
+        decoded), the (ratio, distance) points of all of them are pooled and fitted.  Returns the teacache.TeaCacheCalibration, whose
+        `.coefficients` `enable_teacache(thresh, coefficients)` takes as they are; TeaCache itself is NOT switched on."""
+        import inspect
+        tensor_args = set(inspect.signature(self.edit_tensors).parameters)
+        embeds = {"prompt_embeds", "negative_prompt_embeds", "image_embeds"}
+
+        def runner(kw):
+            kw = dict(call_kwargs, **kw, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, output_type="latent")
+            return lambda: (self.edit_tensors if embeds <= set(kw) <= tensor_args else self.__call__)(**kw)
+
+        return self.transformer.calibrate_teacache([runner(kw) for kw in edits], degree=degree)
 
     def enable_lora(self):
         self.transformer.enable_lora()

@@ -8,7 +8,8 @@ the latents, the prompt or the guidance branch.  So the whole compute / skip pla
 computed here BEFORE the loop (one device-to-host read per edit, none per step), the conditional and unconditional passes share it,
 and a hipGraph-replayed loop needs just a second captured graph for the skipped steps (pipeline.GraphedDenoiser).
 
-Host side only: `plan_from_ratios` and the bf16 arithmetic of the ratios need no device; the device passes are csrc/ce_tea.hip."""
+Host side only: `plan_from_ratios`, the bf16 arithmetic of the ratios and the fit of the rescaling polynomial (`fit_calibration`, from the
+points a measured edit yields) need no device; the device passes are csrc/ce_tea.hip."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -20,8 +21,8 @@ import numpy as np
 @dataclass(frozen=True)
 class TeaCacheConfig:
     """rel_l1_thresh: a step is skipped while the accumulated (rescaled) relative L1 distance stays below it.  coefficients: the
-    rescaling polynomial, highest power first (np.poly1d order).  The default is the identity, poly(r) = r: no polynomial has been
-    fitted for ChronoEdit; callers pass the one published for their model family."""
+    rescaling polynomial, highest power first (np.poly1d order).  The default is the identity, poly(r) = r: no polynomial ships for
+    ChronoEdit; callers pass the one published for their model family, or the one `calibrate_teacache` fits on the loaded checkpoint."""
     rel_l1_thresh: float
     coefficients: Tuple[float, ...] = (1.0, 0.0)
 
@@ -78,3 +79,67 @@ def report(plan: Sequence[bool], ratios: Sequence[float]) -> dict:
     """What `denoise` leaves on `transformer.teacache_report` after an edit."""
     plan = [bool(c) for c in plan]
     return {"plan": plan, "computed": sum(plan), "skipped": len(plan) - sum(plan), "ratios": [float(r) for r in ratios]}
+
+
+# ---- calibration: the rescaling polynomial fitted on the loaded checkpoint ---------------------------------------------------------
+# The polynomial maps what the rule watches (ratios: the relative L1 change of the time projection, a function of the schedule) to what
+# a skipped step gets wrong (distances: the relative L1 change of the block stack's residual, which a skipped step reuses unchanged).
+# A measured edit (pipeline.denoise(teacache_measure=True)) yields one (ratio, distance) point per step; the fit is least squares.
+@dataclass(frozen=True)
+class TeaCacheCalibration:
+    """coefficients: highest power first, what `enable_teacache(thresh, coefficients)` and TeaCacheConfig take.  degree: the degree
+    fitted (lower than asked for when the points hold too few distinct ratios).  points: the (ratio, distance) pairs used.
+    max_residual / rms_residual: the largest and the root-mean-square |polyval(coefficients, ratio) - distance| over the points."""
+    coefficients: Tuple[float, ...]
+    degree: int
+    points: Tuple[Tuple[float, float], ...]
+    max_residual: float
+    rms_residual: float
+
+
+def _is_edit_list(v) -> bool:
+    return len(v) > 0 and not np.isscalar(v[0]) and np.ndim(v[0]) >= 1
+
+
+def fit_calibration(ratios, distances, degree: int = 4) -> TeaCacheCalibration:
+    """ratios / distances: the per-step lists of ONE measured edit, or a list of such lists (several edits, pooled).  Entry 0 of every edit
+    (no step before it) and every point with a non-finite member (a step whose residual had no predecessor: the first one after the
+    temporal-reasoning truncation) are dropped.  np.polyfit in float64; with fewer than degree + 1 distinct ratios the degree drops to
+    distinct - 1.  Fewer than 2 usable points: ValueError."""
+    if int(degree) < 0:
+        raise ValueError(f"fit_coefficients: degree {degree} is negative")
+    if not _is_edit_list(ratios):
+        ratios, distances = [ratios], [distances]
+    if len(ratios) != len(distances):
+        raise ValueError(f"fit_coefficients: {len(ratios)} ratio lists for {len(distances)} distance lists")
+    xs, ys = [], []
+    for r, d in zip(ratios, distances):
+        r, d = np.asarray(r, dtype=np.float64).reshape(-1), np.asarray(d, dtype=np.float64).reshape(-1)
+        if r.shape != d.shape:
+            raise ValueError(f"fit_coefficients: {r.size} ratios for {d.size} distances in one edit")
+        keep = np.isfinite(r) & np.isfinite(d)
+        keep[:1] = False
+        xs.append(r[keep])
+        ys.append(d[keep])
+    x, y = np.concatenate(xs), np.concatenate(ys)
+    if x.size < 2:
+        raise ValueError(f"fit_coefficients: {x.size} usable (ratio, distance) points, at least 2 are needed")
+    deg = max(min(int(degree), np.unique(x).size - 1), 0)
+    coef = np.polyfit(x, y, deg)
+    res = np.abs(np.polyval(coef, x) - y)
+    return TeaCacheCalibration(tuple(float(c) for c in coef), deg, tuple((float(a), float(b)) for a, b in zip(x, y)),
+                               float(res.max()), float(np.sqrt(np.mean(res * res))))
+
+
+def fit_coefficients(ratios, distances, degree: int = 4) -> Tuple[float, ...]:
+    """The coefficients of fit_calibration alone: highest power first, the order plan_from_ratios and TeaCacheConfig use."""
+    return fit_calibration(ratios, distances, degree).coefficients
+
+
+def distances_from_sums(sums) -> List[float]:
+    """ce_tea_store_dist_bf16's fp32 sums [steps, 2] -> sum|r_i - r_{i-1}| / sum|r_{i-1}| per step in float64; NaN where nothing was
+    measured (the table starts as NaN) or the previous residual was all zeros."""
+    sums = np.asarray(sums, dtype=np.float64).reshape(-1, 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = sums[:, 0] / sums[:, 1]
+    return [float(v) if np.isfinite(v) else float("nan") for v in d]

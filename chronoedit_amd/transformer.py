@@ -209,8 +209,10 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         self._sp = None             # Ulysses sequence parallelism (chronoedit_amd.parallel), off by default
         self._cfgp = None           # CFG parallelism on top of it (two Ulysses groups), off by default
         self._teacache = None       # TeaCache step skipping (chronoedit_amd.teacache): a TeaCacheConfig once enable_teacache() was called
-        self._tea_mode = None       # per forward, set by the denoising loop: None = off (the full forward), "compute" or "skip"
+        self._tea_mode = None       # per forward, set by the denoising loop: None = off (the full forward), "compute", "skip" or "measure"
         self.teacache_report = None  # {"plan", "computed", "skipped", "ratios"} of the last edit that ran with TeaCache
+        self._tea_measure = False   # calibrate_teacache(): the loop measures every edit instead of skipping steps
+        self.teacache_measurement = None  # {"ratios", "distances"} of the last measured edit (pipeline.denoise(teacache_measure=True))
         self.shared_guidance = True  # run what the two samples of a guidance pair share once (enable_shared_guidance; needs _shared_inputs)
         self._shared_inputs = None  # per forward, set by the denoising loop: True = the two samples have the same latents, timestep and image context
 
@@ -413,6 +415,27 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         return self
 
     @torch.no_grad()
+    def calibrate_teacache(self, run_edits, degree: int = 4):
+        """Fit the rescaling polynomial `enable_teacache` takes on THIS network (the loaded checkpoint with its active adapters).
+        run_edits: callables, each running one edit through `pipeline.denoise` with this transformer; while they run the loop measures
+        (every step computes, the latents are those of the plain loop) how far the block stack's residual moves from step to step - what
+        a skipped step gets wrong.  The (ratio, distance) points of all edits are pooled and fitted (teacache.fit_calibration); returns
+        the TeaCacheCalibration.  TeaCache itself is not switched on; an enabled TeaCache is refused by the loop."""
+        from .teacache import fit_calibration
+        ratios, distances = [], []
+        self._tea_measure = True
+        try:
+            for run in run_edits:
+                self.teacache_measurement = None
+                run()
+                if self.teacache_measurement is None:
+                    raise RuntimeError("calibrate_teacache: the edit did not go through pipeline.denoise with this transformer")
+                ratios.append(self.teacache_measurement["ratios"])
+                distances.append(self.teacache_measurement["distances"])
+        finally:
+            self._tea_measure = False
+        return fit_calibration(ratios, distances, degree)
+
     def teacache_ratios(self, timesteps: torch.Tensor):
         """Relative L1 distance of every scheduled step's time modulation to that of the step before it (entry 0 is 0.0): the time
         projections of all timesteps through the kernels the step itself uses, one reduction launch, ONE device-to-host read."""
@@ -685,6 +708,9 @@ class DiTEngine:
         self._ctx_refs = None
         self._tea_res = None      # TeaCache: the block stack's residual of the last computed step, bf16 [rows, D] (engine-owned)
         self._tea_valid = False   # ... and whether a computed step of THIS edit has written it
+        self._tea_prev = None     # measuring only: the second residual buffer (the step before's residual; the two alternate)
+        self._tea_sums = None     # measuring only: fp32 [steps, 2], row i = the two distance sums of step i (NaN: nothing measured)
+        self._tea_row = 0         # ... and the row the next measured forward writes (set by the loop)
         self._tap = None          # tests: a dict here receives copies of intermediates of eager (not captured) forwards ("x_pre_cross0": block 0's stream in front of its cross-attention)
 
     def _fuse(self, linears) -> torch.Tensor:
@@ -983,8 +1009,33 @@ class DiTEngine:
         self._tea_valid = False
 
     def tea_release(self):
-        self._tea_res = None
+        self._tea_res = self._tea_prev = self._tea_sums = None
         self._tea_valid = False
+
+    def tea_measure_begin(self, steps: int):
+        """A measured edit starts: the sums table, nothing of an earlier edit's residual to compare with."""
+        self._tea_sums = torch.full((steps, 2), float("nan"), dtype=torch.float32, device=self.dev)
+        self._tea_prev = None
+        self._tea_row = 0
+        self._tea_valid = False
+
+    def tea_measure_end(self) -> torch.Tensor:
+        """The sums table on the host (the one device-to-host read of a measured edit); the second residual buffer is given back."""
+        sums, self._tea_sums, self._tea_prev = self._tea_sums, None, None
+        return sums.cpu()
+
+    def _tea_measure_buffers(self, rows: int):
+        """(buffer for this step's saved tokens, previous step's residual or None).  The two buffers alternate: this step's residual is
+        written where the residual of two steps ago was, while the previous one is read.  A change of row count drops the previous residual."""
+        if self._tea_sums is None:
+            raise RuntimeError("TeaCache: a measured step outside a measured edit (pipeline.denoise(teacache_measure=True))")
+        prev = self._tea_res if self._tea_valid and self._tea_res is not None and self._tea_res.shape[0] == rows else None
+        if prev is None:
+            self._tea_prev = None
+            return self.tea_reserve(rows), None
+        cur = self._tea_prev if self._tea_prev is not None else torch.empty_like(prev)
+        self._tea_res, self._tea_prev = cur, prev
+        return cur, prev
 
     def tea_tproj_rows(self, timesteps: torch.Tensor) -> torch.Tensor:
         """bf16 [S, 6*D]: the time projection (K2 of the forward: sinusoid -> time_embedder -> silu -> time_proj) of every timestep, by
@@ -1069,7 +1120,7 @@ class DiTEngine:
         # this step's tokens and the forward continues at the head (K18): no AdaLN block tables, no context, no block.
         tea = self.model._tea_mode
         if tea is not None:
-            if tea not in ("compute", "skip"):
+            if tea not in ("compute", "skip", "measure"):
                 raise ValueError(f"unknown TeaCache mode {tea!r}")
             if sp is not None:
                 raise NotImplementedError("TeaCache with the tokens sharded over ranks is not implemented")
@@ -1077,12 +1128,14 @@ class DiTEngine:
                 if self._tea_res is None or self._tea_res.shape[0] != B * Nl or not self._tea_valid:
                     raise RuntimeError(f"TeaCache: a skipped step needs the residual of a computed step with the same {B * Nl} token rows")
                 ops.tea_apply_(ws.x, self._tea_res)
-            elif share:  # the residual buffer stays [2 N, D]: both samples' tokens in front of the blocks are xs
-                tr = self.tea_reserve(B * Nl)
-                tr[rows[0]].copy_(xs)
-                tr[rows[1]].copy_(xs)
             else:
-                self.tea_reserve(B * Nl).copy_(ws.x)
+                # measure: a computed step whose residual is also compared with the previous step's (below), in the other of two buffers
+                tr, tea_prev = self._tea_measure_buffers(B * Nl) if tea == "measure" else (self.tea_reserve(B * Nl), None)
+                if share:  # the residual buffer stays [2 N, D]: both samples' tokens in front of the blocks are xs
+                    tr[rows[0]].copy_(xs)
+                    tr[rows[1]].copy_(xs)
+                else:
+                    tr.copy_(ws.x)
         skip = tea == "skip"
 
         # K2 per sample: sinusoid -> time_embedder (fp32) -> temb (bf16-rounded) -> silu -> time_proj -> AdaLN tables
@@ -1219,7 +1272,10 @@ class DiTEngine:
             ffn(li, p)
 
         if tea is not None:  # the saved tokens become the residual of this (computed) step
-            ops.tea_store_(x, self._tea_res)
+            if tea == "measure" and tea_prev is not None:
+                ops.tea_store_dist_(x, self._tea_res, tea_prev, self._tea_sums[self._tea_row])
+            else:
+                ops.tea_store_(x, self._tea_res)
             self._tea_valid = True
         return self._head(ws, x, mod_out, sp, B, T, Hh, Ww, N, Nl, rows)
 

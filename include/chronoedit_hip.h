@@ -451,10 +451,19 @@ int ce_lora_merge_bf16(const void* W0, int ldw0, void* W, int ldw, int N, int K,
  * ce_tea_store_bf16: r[k] <- bf16(float(x[k]) - float(r[k])) - on entry r holds the tokens saved in front of the block stack, x the
  *   tokens behind it; afterwards r is the stack's residual (TeaCache.store, :1233).
  * ce_tea_apply_bf16: x[k] <- bf16(float(x[k]) + float(r[k])) (TeaCache.update, :1237).
- * Both: bf16, `count` elements, count % 8 == 0 (otherwise -2), x and r 16-byte aligned (otherwise -3), round to nearest even. */
+ * Both: bf16, `count` elements, count % 8 == 0 (otherwise -2), x and r 16-byte aligned (otherwise -3), round to nearest even.
+ * ce_tea_store_dist_bf16: ce_tea_store_bf16 (the same bits in r) that also measures, for calibrating the rescaling polynomial,
+ *   sums[0] = sum_k |float(r_new[k]) - float(prev[k])|,  sums[1] = sum_k |prev[k]|  (fp32; the difference is not rounded to bf16).
+ *   prev = bf16 [count], the previous step's residual: only read, 16-byte aligned, must overlap neither r nor x (otherwise -1).
+ *   The sums are accumulated in fp32 in an order that `count` alone decides (lane-serial, butterfly within a wave, the waves in order,
+ *   one pair per workgroup into `scratch`, the pairs added by a second small launch): no atomics, the same bits on every run.
+ *   scratch: caller-owned, 4-byte aligned, at least 8 bytes per workgroup = 8 * min(2048, ceil(count / 2048)) bytes (16 KiB always
+ *   suffices; a smaller one returns -1); the library keeps no state.  On any error nothing is launched. */
 int ce_tea_rel_l1_bf16(const void* T, int S, int n, float* out, hipStream_t stream);
 int ce_tea_store_bf16(const void* x, void* r, long long count, hipStream_t stream);
 int ce_tea_apply_bf16(void* x, const void* r, long long count, hipStream_t stream);
+int ce_tea_store_dist_bf16(const void* x, void* r, const void* prev, float* sums, float* scratch, long long scratch_bytes, long long count,
+                           hipStream_t stream);
 
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
