@@ -75,6 +75,9 @@ struct BlkRows {
   int q_rows;
   int k0_rows;
   int k1_rows;
+  // weighted form only (ce_attention_2seg_vt_weighted_bf16): per sample, the keys of segment 0 that count and the log2-weight of the last of them
+  const int* valid0;  // [batch], 1 <= valid0[b] <= seg0.len
+  const float* w0;    // [batch], added to the (exp2-domain) logit of key valid0[b] - 1
 };
 
 template <bool TWO_SEG, int NWAVE>
@@ -360,7 +363,9 @@ constexpr int SP_V0 = 2 * PK_TILE;                       // V^T buffers follow t
 constexpr int SP_TILE_BYTES = 2 * PK_TILE + 3 * PV_TILE;  // 90112 (also holds the 69632-B O staging)
 constexpr int sp_smem_bytes(bool two_seg) { return two_seg ? SP_TILE_BYTES + 8 * QW * OST_ROW : SP_TILE_BYTES; }
 
-template <bool TWO_SEG, bool VT = false, bool QOUT = false>  // QOUT: the output as an MX fp8 operand (two-segment V^T form only)
+// WGT (two-segment V^T form only): segment 0 ends at blk.valid0[sample] keys and its last key's logit carries + blk.w0[sample] - a key that
+// stands for 2^w0 identical ones (the zero-padded tail of a text context)
+template <bool TWO_SEG, bool VT = false, bool QOUT = false, bool WGT = false>  // QOUT: the output as an MX fp8 operand (two-segment V^T form only)
 __global__ __launch_bounds__(512, 2) void attn_fwd_sp_kernel(const bf16* __restrict__ Q_, bf16* __restrict__ O_, KVSeg seg0_,
                                                               KVSeg seg1_, int Nq, int H, int ldq, int ldo, int nqb,
                                                               float scale_log2e, int batch, BlkRows blk) {
@@ -484,7 +489,12 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_sp_kernel(const bf16* __restr
 
 #pragma unroll
   for (int sidx = 0; sidx < (TWO_SEG ? 2 : 1); ++sidx) {
-    const KVSeg sg = sidx == 0 ? seg0 : seg1;
+    KVSeg sg = sidx == 0 ? seg0 : seg1;
+    float w_last = 0.f;  // WGT: log2-weight of the segment's last key (0: none)
+    if (WGT && sidx == 0) {  // uniform per item: the segment is cut to this sample's valid keys - fewer tiles, the tail mask moves with it
+      sg.len = min(max(blk.valid0[bz], 1), sg.len);
+      w_last = blk.w0[bz];
+    }
     const int ntiles = (sg.len + KVB - 1) / KVB;
     const int k_rows_span = (VT && blk.rows > 0) ? ((sg.len - 1) / blk.rows) * blk.stride + blk.rows : sg.len;  // rows from the first to the last key's
     const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(sg.k + hoff), 0, (k_rows_span - 1) * sg.ldk * 2 + HD * 2, 0x00020000);
@@ -699,6 +709,19 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_sp_kernel(const bf16* __restr
             }
         }
       };
+      auto weigh_last = [&]() {  // WGT: + w_last on the logit of the segment's last key (its tile only), in front of everything that reads S
+        if (WGT && sidx == 0 && t == ntiles - 1 && w_last != 0.f) {
+          int pos = sg.len - 1 - t * KVB - 8 * hh;  // (VT layout: element (f, r) of the lane holds key t KVB + c(f, r) + 8 hh)
+          asm volatile("" : "+v"(pos));             // (as in mask_tail: keeps the compares inside the branch)
+#pragma unroll
+          for (int f = 0; f < 2; ++f)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int c = 32 * f + 16 * (r >> 3) + 4 * ((r >> 2) & 1) + (r & 3);
+              if (c == pos) st[f][r] += w_last;
+            }
+        }
+      };
       auto rebase = [&]() {  // exact tile max of both halves of the row (lane ^ 32 holds the other half): move the offset
         float mx;
         {
@@ -729,6 +752,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_sp_kernel(const bf16* __restr
         ppk[j >> 2][j & 3] = __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, bf16x2));
       };
       mask_tail();
+      weigh_last();
       if (t == 0) rebase();
       // O at the scale of m(t-1) before P(t-1).V(t-1) is added (rare after the first tiles)
       if (__any(alpha_prev != 1.0f)) {
@@ -785,6 +809,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_sp_kernel(const bf16* __restr
 #pragma unroll
           for (int r = 0; r < 16; ++r) st[f][r] -= mc;
         mask_tail();
+        weigh_last();
         rebase();
         psum = 0.f;
 #pragma unroll
@@ -1658,8 +1683,10 @@ CE_API int ce_attention_vt_blocked_bf16(const void* Q, const void* K, const void
 static int attention_2seg_vt_launch(const void* Q, const void* K1, const void* V1t, int len1, int ldk1, int ldv1t, int vt_cols1,
                                     const void* K2, const void* V2t, int len2, int ldk2, int ldv2t, int vt_cols2, void* O, int Nq,
                                     int H, int head_dim, int ldq, int ldo, float softmax_scale, int batch, void* O8, void* S8, int ldo8,
-                                    int q_rows, int k1_rows, int k2_rows, hipStream_t stream) {
+                                    int q_rows, int k1_rows, int k2_rows, hipStream_t stream, const void* valid1 = nullptr,
+                                    const void* w1 = nullptr) {
   if (!Q || !K1 || !V1t || !K2 || !V2t || (!O && !O8)) return CE_ERR_ARG;
+  if ((valid1 != nullptr) != (w1 != nullptr) || (valid1 && O8)) return CE_ERR_ARG;
   // sample strides in rows: 0 = the operand is shared by all samples, otherwise at least one sample's rows
   if ((q_rows != 0 && q_rows < Nq) || (k1_rows != 0 && k1_rows < len1) || (k2_rows != 0 && k2_rows < len2)) return CE_ERR_SHAPE;
   if (k1_rows == 0) vt_cols1 = 0;  // (a shared segment's V^T is shared with its K)
@@ -1678,15 +1705,20 @@ static int attention_2seg_vt_launch(const void* Q, const void* K1, const void* V
   if (!done) {
     (void)hipFuncSetAttribute((const void*)attn_fwd_sp_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes(true));
     (void)hipFuncSetAttribute((const void*)attn_fwd_sp_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes(true));
+    (void)hipFuncSetAttribute((const void*)attn_fwd_sp_kernel<true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes(true));
     done = true;
   }
-  const BlkRows blk{0, vt_cols2, 0u, vt_cols1, (unsigned char*)O8, (unsigned char*)S8, ldo8, q_rows, k1_rows, k2_rows};  // plain rows; the column and row strides
+  const BlkRows blk{0, vt_cols2, 0u, vt_cols1, (unsigned char*)O8, (unsigned char*)S8, ldo8, q_rows, k1_rows, k2_rows,
+                    (const int*)valid1, (const float*)w1};  // plain rows; the column and row strides
   // persistent like the single-segment V^T launch: two workgroups per CU walk the work order (an item is 13 key tiles here: -3 % against
   // one workgroup per item, profiles/r04_cross_attention_persistent_ab.txt; 3 and 4 per CU are level with 2)
   const int cus = ce_device_cus();
   const int items = nqb * H * batch;
   const int grid = items <= 2 * cus ? items : ((2 * cus) & ~7);
-  if (O8)
+  if (valid1)
+    hipLaunchKernelGGL((attn_fwd_sp_kernel<true, true, false, true>), dim3(grid), dim3(512), sp_smem_bytes(true), stream, (const bf16*)Q,
+                       (bf16*)O, s0, s1, Nq, H, ldq, ldo, nqb, sl2, batch, blk);
+  else if (O8)
     hipLaunchKernelGGL((attn_fwd_sp_kernel<true, true, true>), dim3(grid), dim3(512), sp_smem_bytes(true), stream, (const bf16*)Q,
                        (bf16*)O, s0, s1, Nq, H, ldq, ldo, nqb, sl2, batch, blk);
   else
@@ -1714,6 +1746,20 @@ CE_API int ce_attention_2seg_vt_strided_bf16(const void* Q, const void* K1, cons
   if (!O) return CE_ERR_ARG;
   return attention_2seg_vt_launch(Q, K1, V1t, len1, ldk1, ldv1t, vt_cols1, K2, V2t, len2, ldk2, ldv2t, vt_cols2, O, Nq, H, head_dim, ldq, ldo,
                                   softmax_scale, batch, nullptr, nullptr, 0, q_rows, k1_rows, k2_rows, stream);
+}
+
+/* ce_attention_2seg_vt_strided_bf16 with segment 1 cut and weighted per sample: valid1 [batch] int32 on the device, 1 <= valid1[b] <= len1 -
+ * sample b attends keys [0, valid1[b]) of segment 1 only (the key-tile loop ends at ceil(valid1[b] / 64)); w1 [batch] fp32 on the device - the
+ * logit of key valid1[b] - 1 gets + w1[b] in the log2 domain (after the multiplication by softmax_scale log2 e), i.e. that key counts
+ * 2^w1[b] times in the softmax: a run of m identical trailing keys collapses to one with w1 = log2 m.  valid1 = len1 and w1 = 0 give
+ * ce_attention_2seg_vt_strided_bf16 bit for bit.  Both arrays are read by the kernel, not by the host: a captured launch follows their content. */
+CE_API int ce_attention_2seg_vt_weighted_bf16(const void* Q, const void* K1, const void* V1t, int len1, int ldk1, int ldv1t, int vt_cols1,
+                                                  const void* K2, const void* V2t, int len2, int ldk2, int ldv2t, int vt_cols2, void* O, int Nq,
+                                                  int H, int head_dim, int ldq, int ldo, float softmax_scale, int batch, int q_rows, int k1_rows,
+                                                  int k2_rows, const void* valid1, const void* w1, hipStream_t stream) {
+  if (!O || !valid1 || !w1) return CE_ERR_ARG;
+  return attention_2seg_vt_launch(Q, K1, V1t, len1, ldk1, ldv1t, vt_cols1, K2, V2t, len2, ldk2, ldv2t, vt_cols2, O, Nq, H, head_dim, ldq, ldo,
+                                  softmax_scale, batch, nullptr, nullptr, 0, q_rows, k1_rows, k2_rows, stream, valid1, w1);
 }
 
 /* The same attention with the output written as the MX fp8 operand of the out-projection that follows it in the fp8 mode: o8 e4m3

@@ -497,6 +497,43 @@ def attention_2seg_vt_shared(q: torch.Tensor, k1: torch.Tensor, v1t: torch.Tenso
     return out
 
 
+def attention_2seg_vt_weighted(q: torch.Tensor, k1: torch.Tensor, v1t: torch.Tensor, len1: int, k2: torch.Tensor, v2t: torch.Tensor, len2: int,
+                               heads: int, out: torch.Tensor, batch: int, valid1: torch.Tensor, w1: torch.Tensor, share_q: bool = False,
+                               share2: bool = False, cols1: Optional[int] = None, cols2: Optional[int] = None, scale: Optional[float] = None):
+    """`attention_2seg_vt_shared` with segment 1 cut and weighted per sample (ce_attention_2seg_vt_weighted_bf16): valid1 int32 [batch] on the
+    device, 1 <= valid1[b] <= len1 - sample b attends its first valid1[b] keys of segment 1 (the kernel walks ceil(valid1[b] / 64) key tiles of
+    it); w1 fp32 [batch] on the device - the log2 of how many times key valid1[b] - 1 counts in the softmax.  len1 is the row count of the
+    operand as stored.  Neither array is read on the host.  valid1 = len1, w1 = 0: bit-equal to `attention_2seg_vt_shared`."""
+    for n, t in (("q", q), ("k1", k1), ("v1t", v1t), ("k2", k2), ("v2t", v2t), ("out", out)):
+        _dev(t, torch.bfloat16, n)
+    _dev(valid1, torch.int32, "valid1"), _dev(w1, torch.float32, "w1")
+    assert valid1.is_contiguous() and w1.is_contiguous() and valid1.numel() == batch and w1.numel() == batch
+    Nq, Dq, ldq = _rows(q, "q")
+    _, _, ldk1 = _rows(k1, "k1")
+    _, _, ldk2 = _rows(k2, "k2")
+    No, Do, ldo = _rows(out, "out")
+    nq = Nq if share_q else Nq // batch
+    assert Dq == heads * 128 and Do == Dq and v1t.shape[0] == Dq and v2t.shape[0] == Dq and v1t.stride(1) == 1 and v2t.stride(1) == 1
+    assert No == batch * nq and (share_q or Nq == batch * nq), (No, Nq, batch)
+    assert k1.shape[0] == batch * len1 and k2.shape[0] == (1 if share2 else batch) * len2
+    pad = lambda n: (n + 63) // 64 * 64
+    if cols1 is None:
+        cols1 = v1t.shape[1] // batch
+    if cols2 is None:
+        cols2 = 0 if share2 else v2t.shape[1] // batch
+    assert v1t.shape[1] >= (batch - 1) * cols1 + pad(len1) and v2t.shape[1] >= (0 if share2 else (batch - 1) * cols2) + pad(len2)
+    if scale is None:
+        scale = 128 ** -0.5
+    st = _prof_begin()
+    _check(lib().ce_attention_2seg_vt_weighted_bf16(_ptr(q), _ptr(k1), _ptr(v1t), len1, ldk1, v1t.stride(0), int(cols1), _ptr(k2), _ptr(v2t),
+                                                    len2, ldk2, v2t.stride(0), int(cols2), _ptr(out), nq, heads, 128, ldq, ldo, float(scale), batch,
+                                                    0 if share_q else nq, len1, 0 if share2 else len2, _ptr(valid1), _ptr(w1), _stream()),
+           "ce_attention_2seg_vt_weighted_bf16")
+    tag = ("_sq" if share_q else "") + ("_s2" if share2 else "") + "_w"
+    _prof_end(st, f"attention_{nq}x{len1}+{len2}_h{heads}" + (f"_b{batch}" if batch > 1 else "") + tag, 4.0 * nq * (len1 + len2) * 128 * heads * batch)
+    return out
+
+
 def v_transpose_blocked(v: torch.Tensor, heads: int, batch: int, blk_rows: int, n_keys: int, out: Optional[torch.Tensor] = None):
     """v [W * batch * blk_rows, heads*128] in the all-to-all receive layout ([source rank][sample][local token]) -> V^T
     [heads*128, batch * vt_sample_cols] plain per sample (`attention_vt_blocked`); n_keys = valid tokens per sample."""

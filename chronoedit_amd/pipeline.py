@@ -9,9 +9,11 @@ from __future__ import annotations
 
 import contextlib
 import html
+import math
 import re
 from dataclasses import dataclass
-from typing import Any, Callable, Dict, List, Optional, Tuple, Union
+from types import SimpleNamespace
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -39,10 +41,59 @@ def prompt_clean(text: str) -> str:
     return re.sub(r"\s+", " ", text).strip()
 
 
+_INT_OF_SIZE = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def text_real_lengths(text: torch.Tensor) -> torch.Tensor:
+    """text [B, Tt, C] -> int64 [B] (on text's device): per sample, the rows in front of its padding = Tt minus the length of the trailing run
+    of rows that equal the LAST row bit for bit (compared as integers: no tolerance, -0 != +0, a NaN equals itself).  The reference
+    re-pads every prompt with zero rows (pipeline_chronoedit.py:230-237); any constant padding row is found the same way.  A last row that is
+    unlike its predecessor is a run of one: the sample has no padding to speak of."""
+    B, Tt = text.shape[0], text.shape[1]
+    bits = text.contiguous().view(_INT_OF_SIZE[text.element_size()]).reshape(B, Tt, -1)
+    differs = (bits != bits[:, -1:, :]).any(-1)  # [B, Tt]; False at the last row
+    idx = torch.arange(1, Tt + 1, device=text.device).expand(B, Tt)
+    return torch.where(differs, idx, torch.zeros_like(idx)).amax(1)  # one past the last row that differs from the last row
+
+
+def text_compaction_plan(real: Sequence[int], Tt: int):
+    """real = rows in front of the padding per sample -> (Lc, valid, log2 weights) or None when nothing is saved.  Sample b keeps its real
+    rows and ONE padding row that stands for all Tt - real[b] of them (valid = real + 1, weight log2(Tt - real)); a sample whose trailing
+    run is a single row keeps everything (valid = Tt, weight 0).  Lc = the largest valid count rounded up to 8 (the transposed-V projection
+    wants its columns in multiples of 8 with even per-sample strides).  None unless every sample walks at least one 64-key tile less."""
+    valid = [min(int(n) + 1, Tt) for n in real]
+    Lc = (max(valid) + 7) // 8 * 8
+    if Lc > Tt or (max(valid) + 63) // 64 >= (Tt + 63) // 64:
+        return None
+    return Lc, valid, [math.log2(Tt - v + 1) for v in valid]
+
+
+def compact_text_context(text: torch.Tensor):
+    """Find the padding of a text context [B, Tt, C] (one device-to-host read) and hang the compacted form on the tensor as
+    `text._ce_compact`: rows [0, Lc) of every sample (its real rows, the representative padding row, then rows the kernel masks), the valid
+    counts (int32) and log2 weights (fp32) on the device, and the tensor version they were taken at.  The engine picks it up when the SAME
+    tensor object reaches a forward (chronoedit_amd/transformer.py `_context`); a tensor without the attribute is never compacted.  Returns text."""
+    if getattr(text, "_ce_compact", None) is not None and text._ce_compact.version == text._version:
+        return text
+    info = SimpleNamespace(version=text._version, shape=tuple(text.shape), text=None, valid=None, w=None, Lc=0, real=None)
+    if text.dim() == 3 and text.shape[1] > 1 and text.is_floating_point():
+        Tt = text.shape[1]
+        info.real = [int(n) for n in text_real_lengths(text).tolist()]
+        plan = text_compaction_plan(info.real, Tt)
+        if plan is not None:
+            info.Lc, valid, w = plan
+            info.text = text[:, : info.Lc].contiguous()
+            info.valid = torch.tensor(valid, dtype=torch.int32, device=text.device)
+            info.w = torch.tensor(w, dtype=torch.float32, device=text.device)
+    text._ce_compact = info
+    return text
+
+
 def make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds):
     """[cond | uncond] conditioning stacked along the batch axis; build it ONCE per edit so that the transformer's
-    context cache (step-invariant text/image K/V) can recognise the tensors across steps."""
-    text2 = torch.cat([prompt_embeds, negative_prompt_embeds], 0)
+    context cache (step-invariant text/image K/V) can recognise the tensors across steps.  The text padding is found here, once
+    (`compact_text_context`): the stacked text tensor carries its compacted form to the engine."""
+    text2 = compact_text_context(torch.cat([prompt_embeds, negative_prompt_embeds], 0))
     image2 = None if image_embeds is None else torch.cat([image_embeds, image_embeds], 0)
     return text2, image2
 
@@ -115,6 +166,7 @@ def denoise_step(transformer: ChronoEditTransformer3DModel, scheduler: FlowUniPC
             noise_pred = transformer(latent_model_input, timestep, prompt_embeds, image_embeds, return_dict=False)[0]
             noise_uncond = transformer(latent_model_input, timestep, negative_prompt_embeds, image_embeds, return_dict=False)[0]
     else:
+        compact_text_context(prompt_embeds)  # (examined once per tensor version: later steps find the attribute)
         noise_pred = transformer(latent_model_input, timestep, prompt_embeds, image_embeds, return_dict=False)[0]
         noise_uncond = None
     return scheduler.step_cfg(noise_pred, noise_uncond, guidance_scale, latents)
@@ -173,6 +225,8 @@ class GraphedDenoiser:
         self.guided = guidance_scale > 1.0 and negative_prompt_embeds is not None
         if self.guided and batch_cfg:
             self.cfg_inputs = make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds)
+        elif not self.guided:
+            compact_text_context(prompt_embeds)  # (here, not under the capture: it reads the lengths back)
         self.tea_plan = None if tea_plan is None else [bool(c) for c in tea_plan]
         if self.tea_plan is not None and self.guided and self.cfg_inputs is None:
             raise NotImplementedError("TeaCache needs the guidance pair as ONE batched forward (one residual buffer covers both samples)")
@@ -218,7 +272,7 @@ class GraphedDenoiser:
         """With `cache_context`: the step-invariant context projections of THIS conditioning computed eagerly now, so that the capture
         records the cache hit and not the projections."""
         tr = self.tr
-        if getattr(tr, "cache_context", False) and hasattr(tr, "prime_context"):
+        if hasattr(tr, "prime_context"):  # (without `cache_context` it only reserves the buffers of a compacted text context)
             if self.cfg_inputs is not None:
                 with _shared_inputs(tr):  # (the entry the captured forward will look up)
                     tr.prime_context(self.cfg_inputs[0], self.cfg_inputs[1])

@@ -214,6 +214,7 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         self._tea_measure = False   # calibrate_teacache(): the loop measures every edit instead of skipping steps
         self.teacache_measurement = None  # {"ratios", "distances"} of the last measured edit (pipeline.denoise(teacache_measure=True))
         self.shared_guidance = True  # run what the two samples of a guidance pair share once (enable_shared_guidance; needs _shared_inputs)
+        self.text_compaction = True  # attend a text context's padding once, weighted (enable_text_compaction; needs the tensor's `_ce_compact`)
         self._shared_inputs = None  # per forward, set by the denoising loop: True = the two samples have the same latents, timestep and image context
 
     # -- reference-compatible helpers --------------------------------------------------
@@ -302,9 +303,10 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
     @torch.no_grad()
     def prime_context(self, encoder_hidden_states: torch.Tensor, encoder_hidden_states_image: Optional[torch.Tensor]):
         """Compute the step-invariant conditioning work for exactly these tensors now, so that the next forward
-        that receives them - e.g. the one a hipGraph capture records - finds the cache entry (only with `cache_context`)."""
-        if self.cache_context:
-            eng = self.engine()
+        that receives them - e.g. the one a hipGraph capture records - finds the cache entry (with `cache_context`).  Without it, a compacted
+        text context is still projected once here: its engine-owned V^T buffers depend on the prompt's length and must exist before a capture."""
+        eng = self.engine()
+        if self.cache_context or eng._text_compact(encoder_hidden_states, encoder_hidden_states_image) is not None:
             eng._context(encoder_hidden_states, encoder_hidden_states_image,
                          share_image=eng._share_image(encoder_hidden_states, encoder_hidden_states_image))
 
@@ -376,6 +378,19 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         self.shared_guidance = bool(on)
         if self._engine is not None:
             self._engine.clear_context_cache()  # (a cached context was projected for the other form)
+        return self
+
+    def enable_text_compaction(self, on: bool = True):
+        """The padding of a text context attended once, weighted (default on).  The reference re-pads every prompt to 512 rows and attends
+        them unmasked; the embedder and the per-layer K / V projections act row by row, so the padding rows are (Tt - n) copies of ONE key /
+        value pair, and a softmax over them equals one over a single key whose logit carries + ln(Tt - n).  Where the edit's context is built
+        (`pipeline.make_cfg_inputs`, `pipeline.compact_text_context`) the padding is found once and the text tensor carries its compacted
+        form; the engine then projects Lc = n_max + 1 (rounded up to 8) rows per sample and the cross-attention walks ceil((n + 1) / 64) text
+        tiles per sample (`ce_attention_2seg_vt_weighted_bf16`).  Off = the full rows (A/B partner).  Only the unsharded bf16 path with the
+        transposed-V cross-attention compacts; a tensor that was not examined - any direct forward() - never does."""
+        self.text_compaction = bool(on)
+        if self._engine is not None:
+            self._engine.clear_context_cache()
         return self
 
     def enable_fp8_attention(self, on: bool = True, cross: bool = False):
@@ -522,7 +537,7 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         eng = self._engine
         sp = self._sp
         return (self._gen, None if eng is None else eng.ws_generation, self.gemm_dtype, self.fp8_linears, self.attn_dtype, self.v_transposed, self.cross_vt,
-                self.sp_batch_cfg, bool(getattr(self, "rope_plain_temporal", False)), self.cache_context, self.shared_guidance,
+                self.sp_batch_cfg, bool(getattr(self, "rope_plain_temporal", False)), self.cache_context, self.shared_guidance, self.text_compaction,
                 None if sp is None else (sp.world, sp.rank), self._cfgp is not None)
 
     @torch.no_grad()
@@ -873,19 +888,38 @@ class DiTEngine:
                     and self._cross_vt_form(text.shape[1], True) and not self.fp8 and not self.fp8_attn
                     and self.v_transposed and (m._sp is None or not m._sp.sharded) and getattr(m, "_cfgp", None) is None)
 
+    def _text_compact(self, text: torch.Tensor, image: Optional[torch.Tensor]):
+        """The compacted form of this text context (pipeline.compact_text_context hung it on the tensor where the edit's context was built),
+        or None: switched off, a tensor nobody examined or that changed since, nothing to save, or a launch sequence that cannot express it
+        (as `_share_image`: bf16, unsharded, the transposed-V cross-attention kernel).  Never inferred from the tensor's content here."""
+        m = self.model
+        info = getattr(text, "_ce_compact", None)
+        if info is None or info.text is None or not m.text_compaction or info.version != text._version or info.shape != tuple(text.shape):
+            return None
+        if not (image is not None and self._cross_vt_form(text.shape[1], True) and not self.fp8 and not self.fp8_attn and self.v_transposed
+                and (m._sp is None or not m._sp.sharded) and getattr(m, "_cfgp", None) is None):
+            return None
+        return info
+
     def _context(self, text: torch.Tensor, image: Optional[torch.Tensor], share_image: bool = False):
         """text [B, Tt, text_dim], image [B, Ti, image_dim] -> per-layer cross-attention K/V, samples stacked along rows.
-        share_image (_share_image): image[0] stands for every sample - the image embedder and the image K / V^T projections run on its rows only."""
+        share_image (_share_image): image[0] stands for every sample - the image embedder and the image K / V^T projections run on its rows only.
+        A text tensor that carries a compacted form (_text_compact) is projected on its Lc rows per sample instead of Tt: ctx.Tt = Lc, and
+        ctx.valid / ctx.w (device arrays that live with the tensor, hence with the cache entry) go to the weighted cross-attention."""
         key = None
+        cmp = self._text_compact(text, image)
         if self.model.cache_context:
             # The entry keeps the keyed tensors alive (self._ctx_refs): an address can then not be handed out again for another
             # edit's conditioning while the entry exists, so (data_ptr, _version, shape) identifies the CONTENT, not just a slot.
             key = (text.data_ptr(), text._version, tuple(text.shape), text.dtype,
-                   None if image is None else (image.data_ptr(), image._version, tuple(image.shape), image.dtype), bool(share_image))
+                   None if image is None else (image.data_ptr(), image._version, tuple(image.shape), image.dtype), bool(share_image),
+                   cmp is not None)
             if key == self._ctx_key:
                 return self._ctx
         keyed = (text, image)
         D = self.D
+        if cmp is not None:  # rows [0, Lc) of every sample: its real rows, ONE padding row, then rows the kernel masks
+            text = cmp.text
         B, Tt = text.shape[0], text.shape[1]
         share_image = bool(share_image and B == 2 and self._cross_vt_form(Tt, image is not None))  # (any other form: stacked, silently)
         Bi = 1 if share_image else B  # samples of image context actually projected
@@ -942,6 +976,9 @@ class DiTEngine:
             bufs = self._ctx_bufs.get((B, Bi, Tt, Ti))
             if bufs is None:  # zero-filled once: the padding rows / columns are never written afterwards.  Engine-owned (not per call):
                 # a captured step that computes the projections (cache_context off) replays into the same addresses
+                if cmp is not None and torch.cuda.is_current_stream_capturing():  # (their size follows the prompt's length)
+                    raise RuntimeError(f"no context buffers for {(B, Bi, Tt, Ti)} exist and none can be allocated under a hipGraph capture "
+                                       "(prime_context first)")
                 z = lambda *sh: torch.zeros(sh, dtype=torch.bfloat16, device=self.dev)
                 bufs = SimpleNamespace(enc_i_pad=z(Bi * c2, D), v1t=z(L * D, ld1), v2t=z(L * D, ld2))
                 self._ctx_bufs = dict(list(self._ctx_bufs.items())[-1:] + [((B, Bi, Tt, Ti), bufs)])  # the guided pair and the single sample
@@ -982,7 +1019,9 @@ class DiTEngine:
                 if k_i_all is not None:
                     seg_i = ops.rmsnorm_rope_mxfp8(k_i_all[:, cols], p.nk_i, None, hd, eps) + ops.v_mxfp8_transpose(v_i_all[:, cols], Ti, B, self.H)
                 kv.append((seg_t, seg_i))
-        ctx = SimpleNamespace(kv=kv, Tt=Tt, Ti=Ti, vt=use_vt, c1=c1, c2=c2, f8=f8, img_shared=bool(share_image))
+        assert cmp is None or (use_vt and not f8)
+        ctx = SimpleNamespace(kv=kv, Tt=Tt, Ti=Ti, vt=use_vt, c1=c1, c2=c2, f8=f8, img_shared=bool(share_image),
+                              valid=None if cmp is None else cmp.valid, w=None if cmp is None else cmp.w)
         if key is not None:
             self._ctx_key, self._ctx, self._ctx_refs = key, ctx, keyed
         return ctx
@@ -1187,7 +1226,11 @@ class DiTEngine:
                 # text keys per sample, image keys shared, output per sample; the out-projection adds the shared residual to both
                 self._block0_shared_prefix(ws, xs, p, mods[0], cs, N)
                 k_t, v_t, k_i, v_i = ctx.kv[0]
-                ops.attention_2seg_vt_shared(ws.q2[:N], k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, share_q=True, share2=True, cols1=ctx.c1)
+                if ctx.valid is not None:
+                    ops.attention_2seg_vt_weighted(ws.q2[:N], k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, valid1=ctx.valid, w1=ctx.w,
+                                                   share_q=True, share2=True, cols1=ctx.c1)
+                else:
+                    ops.attention_2seg_vt_shared(ws.q2[:N], k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, share_q=True, share2=True, cols1=ctx.c1)
                 ops.gemm(ws.att, p.w_o2, p.b_o2, out=x, epilogue=ops.EPI_GATE_RES, gate=None, res=xs, res_rows=N)
                 ffn(li, p)
                 continue
@@ -1257,6 +1300,9 @@ class DiTEngine:
                 k_t, v_t, k_i, v_i = ctx.kv[li]
             if k_t is None:
                 pass
+            elif ctx.valid is not None:  # compacted text: per-sample valid keys, the padding as one weighted key
+                ops.attention_2seg_vt_weighted(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, valid1=ctx.valid, w1=ctx.w,
+                                               share2=ctx.img_shared, cols1=ctx.c1, cols2=None if ctx.img_shared else ctx.c2)
             elif ctx.vt and fuse_o2:
                 ops.attention_2seg_vt(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, batch=B, cols1=ctx.c1, cols2=ctx.c2, out8=ws.a8[:, :D], scale8=ws.s8)
             elif ctx.img_shared:  # one image segment for both samples

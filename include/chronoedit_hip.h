@@ -142,6 +142,18 @@ int ce_attention_2seg_vt_strided_bf16(const void* Q, const void* K1, const void*
                                       int head_dim, int ldq, int ldo, float softmax_scale, int batch, int q_rows, int k1_rows, int k2_rows,
                                       hipStream_t stream);
 
+/* ce_attention_2seg_vt_strided_bf16 with segment 1 cut and weighted per sample.  valid1: int32 [batch] on the device, 1 <= valid1[b] <= len1 -
+ * sample b attends keys [0, valid1[b]) of segment 1 only, and its key-tile loop ends at ceil(valid1[b] / 64).  w1: fp32 [batch] on the device -
+ * the logit of key valid1[b] - 1 gets + w1[b] in the log2 domain (after the multiplication by softmax_scale log2 e): that key counts 2^w1[b]
+ * times in the softmax, so a run of m identical trailing keys (the zero-padded tail of a text context) is ONE key with w1 = log2 m.  The
+ * kernel reads both arrays (nothing of them on the host): a captured launch follows their content.  valid1[b] = len1 and w1[b] = 0 give
+ * ce_attention_2seg_vt_strided_bf16 bit for bit.  Strides, segment 2 and the shared forms as there; len1 / k1_rows / vt_cols1 describe the
+ * operand as stored. */
+int ce_attention_2seg_vt_weighted_bf16(const void* Q, const void* K1, const void* V1t, int len1, int ldk1, int ldv1t, int vt_cols1,
+                                       const void* K2, const void* V2t, int len2, int ldk2, int ldv2t, int vt_cols2, void* O, int Nq, int H,
+                                       int head_dim, int ldq, int ldo, float softmax_scale, int batch, int q_rows, int k1_rows, int k2_rows,
+                                       const void* valid1, const void* w1, hipStream_t stream);
+
 /* ce_attention_2seg_vt_bf16 with its output written as the MX fp8 operand of the out-projection that follows it in the fp8 mode
  * (transformer_chronoedit.py:106 `attn.to_out[0]`; no counterpart in the reference): o8 e4m3 [batch Nq][ldo8] (ldo8 % 16 == 0) + one
  * E8M0 scale per 32 channels in the tiled layout of ce_gemm_mxfp8 (rows = batch Nq, K = H head_dim, K % 128 == 0) - bit-identical to
