@@ -117,7 +117,8 @@ __global__ __launch_bounds__(256) void softmax_t5_kernel(const float* __restrict
     v[i] = k < nk ? __expf(v[i] - mx) : 0.f;
     sum += v[i];
   }
-  const float inv = 1.0f / wave_sum(sum);
+  sum = wave_sum(sum);
+  const float inv = sum > 0.f ? 1.0f / sum : 0.f;  // no valid key (valid[b] == 0): the row is written as zeros, not 0 * inf
   bf16* pr = probs + (size_t)row * ldp;
 #pragma unroll
   for (int i = 0; i < SM_MAXK; ++i) {

@@ -439,7 +439,8 @@ int ce_rmsnorm_bf16(const void* x, void* y, const void* w, int M, int D, int ldx
 
 /* probs[b][h][q][:] = softmax_k(scores[b][h][q][k] + table[bucket_lut[k - q + Lq - 1]][h]) over keys k < valid_len[b]
  * (fp32 in, bf16 out, columns [Lk, ldp) written as zeros); table / bucket_lut may both be NULL (no bias), valid_len may be
- * NULL (no padding mask).  UMT5Attention: position bias + extended attention mask + softmax in fp32. */
+ * NULL (no padding mask).  A sample with valid_len[b] <= 0 has no key to attend: all its probabilities are written as zeros (never NaN).
+ * UMT5Attention: position bias + extended attention mask + softmax in fp32. */
 int ce_softmax_t5_bf16(const float* scores, void* probs, int batch, int heads, int Lq, int Lk, int ld, int ldp,
                        const int* bucket_lut, const float* table, const int* valid_len, hipStream_t stream);
 

@@ -230,3 +230,215 @@ def needle_margins(q: torch.Tensor, k: torch.Tensor, heads: int, winners: torch.
     if forbidden is None or not forbidden.any():
         fl = torch.full_like(lead, math.inf)
     return lead, fl
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# row kernels (LayerNorm / RMSNorm / RoPE), the scheduler step and the softmaxes: exactly computable data and their fp64 answers
+#
+# `unit_rows`: rows whose sum is 0 and whose sum of squares is exactly D, scaled by a power of two and shifted by a multiple of 1/4.  With
+# eps = 0 the fp32 statistics of a norm kernel are exact in any summation order (mean = mu, var = s^2, rstd = 1 / s) and the normalised values
+# are the integers 0, +-1, +-2 again; what follows (an affine, a weight, a rotation by a DYADIC table) is exact in fp32 and the one rounding
+# to bf16 is the only one.  Every vector the kernels index (a, b, w, cos/sin, bias) differs in every column and row: a wrong index shows.
+# ------------------------------------------------------------------------------------------------------------------------------------
+def dyadic(shape, gen: torch.Generator, lo: int, hi: int, e: int) -> torch.Tensor:
+    """fp32 tensor of integers in [lo, hi] times 2^e."""
+    return torch.randint(lo, hi + 1, tuple(shape), generator=gen, dtype=torch.int32).float() * 2.0 ** e
+
+
+def unit_rows(M: int, D: int, gen: torch.Generator, centred: bool = False):
+    """(x, v): x bf16 [M, D] = mu + s * v, v fp64 [M, D] with n2 entries of +-2 (balanced), 3 * n2 zeros and +-1 (balanced) elsewhere, permuted,
+    n2 random per row; s = 2^e per row, e in [-2, 2]; mu a per-row multiple of 1/4 in [-8, 8] (0 when `centred`: the RMS kernels).
+    sum(v) = 0 and sum(v^2) = D exactly; x is exact in bf16 (a multiple of 1/4 below 32)."""
+    assert D % 8 == 0
+    v = torch.empty(M, D, dtype=torch.float64)
+    for m in range(M):
+        n2 = 2 * int(torch.randint(0, D // 16 + 1, (1,), generator=gen))
+        ones = D - 4 * n2
+        row = torch.cat([torch.full((n2 // 2,), 2.0), torch.full((n2 // 2,), -2.0), torch.zeros(3 * n2), torch.ones(ones // 2),
+                         -torch.ones(ones // 2)]).double()
+        v[m] = row[torch.randperm(D, generator=gen)]
+    assert torch.equal(v.sum(1), torch.zeros(M, dtype=torch.float64)) and torch.equal((v * v).sum(1), torch.full((M,), float(D), dtype=torch.float64))
+    s = torch.exp2(torch.randint(-2, 3, (M, 1), generator=gen).double())
+    mu = torch.zeros(M, 1, dtype=torch.float64) if centred else torch.randint(-32, 33, (M, 1), generator=gen).double() / 4
+    x64 = mu + s * v
+    x = x64.to(BF)
+    assert torch.equal(x.double(), x64)
+    return x, v
+
+
+def affine_vectors(rows: int, D: int, gen: torch.Generator):
+    """(a, b) fp32 [rows, D]: a in units of 2^-8 up to 4 (fine enough that v * a + b needs a real bf16 rounding), b in units of 2^-10 up to 1/4."""
+    return dyadic((rows, D), gen, -1024, 1024, -8), dyadic((rows, D), gen, -256, 256, -10)
+
+
+def sample_of(M: int, ab_rows: int) -> torch.Tensor:
+    """The (a, b) row that row m of a stacked batch uses."""
+    return torch.arange(M) // ab_rows if ab_rows > 0 else torch.zeros(M, dtype=torch.int64)
+
+
+def ln_affine_exact(v: torch.Tensor, a: torch.Tensor, b: torch.Tensor, ab_rows: int = 0, sample=None) -> torch.Tensor:
+    """fp64 v * a[sample(m)] + b[sample(m)] for `unit_rows` data at eps = 0 (a, b [rows, D]); `sample` overrides the row -> sample map."""
+    idx = sample_of(v.shape[0], ab_rows) if sample is None else sample
+    return v * a.double()[idx] + b.double()[idx]
+
+
+def ln_affine_f64(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, eps: float, ab_rows: int = 0) -> torch.Tensor:
+    """The LayerNorm-affine formula in fp64 on any data (biased variance), before the one rounding to bf16."""
+    xd = x.double()
+    mean = xd.mean(1, keepdim=True)
+    var = ((xd - mean) ** 2).mean(1, keepdim=True)
+    idx = sample_of(x.shape[0], ab_rows)
+    return (xd - mean) / torch.sqrt(var + eps) * a.double()[idx] + b.double()[idx]
+
+
+def round_bf16_f64(x64: torch.Tensor) -> torch.Tensor:
+    """An exact-in-fp32 fp64 value rounded to bf16, back in fp64 (an intermediate rounding point of a kernel)."""
+    return bf16_rne(x64).double()
+
+
+def rope_table(R: int, head_dim: int, gen: torch.Generator) -> torch.Tensor:
+    """fp32 [R, head_dim / 2, 2]: (cos, sin) entries that are no rotation - random multiples of 1/8 in [-1, 1], different for every (row, pair) -
+    with true quarter turns ((0, 1), (-1, 0), (0, -1), (1, 0)) on every fifth pair."""
+    cs = dyadic((R, head_dim // 2, 2), gen, -8, 8, -3)
+    turns = torch.tensor([[0.0, 1.0], [-1.0, 0.0], [0.0, -1.0], [1.0, 0.0]])
+    n = cs[:, ::5].shape[1]
+    cs[:, ::5] = turns[torch.randint(0, 4, (R, n), generator=gen)]
+    return cs
+
+
+def rms_rope_exact(v: torch.Tensor, w: torch.Tensor, cs=None, head_dim: int = 0, table_row=None, pair_shift: int = 0) -> torch.Tensor:
+    """bf16 result of RMSNorm * w (+ RoPE) for centred `unit_rows` data at eps = 0: bf16(bf16(v) * w), then the rotation of every (even, odd)
+    pair by (cos, sin) = cs[m % R][pair within the head], rounded once.  `table_row` (int64 [M]) overrides m % R and `pair_shift` moves every
+    pair's table entry to a neighbour's: the deliberately wrong references of the sensitivity checks."""
+    M, D = v.shape
+    t = round_bf16_f64(round_bf16_f64(v) * w.double())
+    if cs is None:
+        return t.to(BF)
+    R, half = cs.shape[0], head_dim // 2
+    rows = torch.arange(M) % R if table_row is None else table_row
+    pair = (torch.arange(D // 2) % half + pair_shift) % half
+    c = cs.double()[rows][:, pair]  # [M, D/2, 2]
+    v0, v1 = t[:, 0::2], t[:, 1::2]
+    out = torch.empty_like(t)
+    out[:, 0::2] = v0 * c[..., 0] - v1 * c[..., 1]
+    out[:, 1::2] = v0 * c[..., 1] + v1 * c[..., 0]
+    return bf16_rne(out)
+
+
+def rms_weights(D: int, gen: torch.Generator) -> torch.Tensor:
+    """fp32 [D] RMSNorm weights in units of 2^-8 up to 4, never 0: the product with 0, +-1, +-2 needs a real bf16 rounding."""
+    w = dyadic((D,), gen, 1, 1024, -8)
+    return w * (torch.randint(0, 2, (D,), generator=gen).float() * 2 - 1)
+
+
+# ---- the fused CFG + UniPC step ----------------------------------------------------------------------------------------------------
+UNIPC_COEF = (4.0, 0.5, 1.0, 0.5, -0.25, 2.0, 1.5, 0.75, -1.5, 0.5)
+
+
+def unipc_state(n: int, gen: torch.Generator):
+    """(v_cond, v_uncond, x, x_last, m0, m1): bf16 integer velocities in [-8, 8], fp32 state in multiples of 1/4 in [-16, 16]."""
+    vc, vu = (torch.randint(-8, 9, (n,), generator=gen).to(BF) for _ in range(2))
+    return (vc, vu) + tuple(dyadic((n,), gen, -64, 64, -2) for _ in range(4))
+
+
+def unipc_exact(vc, vu, x, xl, m0, m1, coef=UNIPC_COEF, flags: int = 0, m1_from_new: bool = False):
+    """One ce_cfg_unipc_step in fp64 with the kernel's documented rounding points; returns fp32 (x, x_last, m0, m1, x0).  Every fp32 value
+    the kernel forms is checked to be exact (`exact_f64`) - the recipe's premise.  `m1_from_new`: the deliberately wrong history shift."""
+    r = (lambda t: round_bf16_f64(t))
+    g, sigma, use_corr = coef[0], coef[1], coef[2] != 0
+    a0, a1, a2, a3, p0, p1, p2 = coef[3:10]
+    v = vc.double()
+    if vu is not None:
+        u = vu.double()
+        v = r(u + r(g * r(v - u)))
+    sv = sigma * v
+    x0 = x.double() - (r(sv) if flags & 1 else exact_f64(sv).double())
+    x0 = r(x0) if flags & 2 else exact_f64(x0).double()
+    xc = x.double()
+    if use_corr:
+        xc = a0 * xl.double() + a1 * m0.double() + a2 * m1.double() + a3 * x0
+    xc = r(xc) if flags & 2 else exact_f64(xc).double()
+    xn = p0 * xc + p1 * x0 + p2 * m0.double()
+    xn_r = r(xn) if flags & 2 else exact_f64(xn).double()
+    rounded = (xn_r != xn).double().mean().item()
+    out = (xn_r.float(), xc.float(), x0.float(), (x0 if m1_from_new else m0.double()).float(), x0.float())
+    return out, rounded
+
+
+# ---- softmax with exact ties ---------------------------------------------------------------------------------------------------------
+TIE_GAP = 200  # exp(-200) = 1.4e-87 is 0 in fp32 (the smallest denormal is 1.4e-45), for libm's expf and for the hardware exp2 alike
+
+
+def tie_targets(rows: int, n: int, valid, gen: torch.Generator) -> torch.Tensor:
+    """int64 [rows, n] score targets: per row 2^k keys (k random in 1..3, as many as fit) tie at 0 - one of them the LAST valid key, so that
+    a mask one key too tight changes the count - every other valid key sits at -TIE_GAP - (0..63), and every key at or past the row's valid
+    length (`valid`: int per row) carries +64: it wins outright if it is read."""
+    t = torch.empty(rows, n, dtype=torch.int64)
+    for r in range(rows):
+        nv = int(valid[r])
+        t[r] = -TIE_GAP - torch.randint(0, 64, (n,), generator=gen)
+        if nv > 0:
+            k = 1 << int(torch.randint(1, 4, (1,), generator=gen))  # (two keys at least: a single winner would survive any bias error)
+            while k > nv:
+                k >>= 1
+            tied = torch.randperm(nv - 1, generator=gen)[:k - 1]
+            t[r, tied] = 0
+            t[r, nv - 1] = 0
+        t[r, nv:] = 64
+    return t
+
+
+def tie_probs(total: torch.Tensor, valid, check: bool = True) -> torch.Tensor:
+    """fp64 [rows, n] softmax of `total` (fp64 scores with every bias added) over each row's first valid[r] keys where the maximum is shared by
+    some keys and every other valid key trails by >= TIE_GAP: 1 / count on the tied keys, 0 elsewhere (all zeros for a row with no valid key).
+    check=False skips the premise (a deliberately wrong reference need not keep it; its near-ties then count as losers, which changes the
+    answer all the same)."""
+    rows, n = total.shape
+    mask = torch.arange(n)[None, :] < torch.as_tensor(valid).view(-1, 1)
+    neg = torch.full_like(total, -math.inf)
+    mx = torch.where(mask, total, neg).amax(1, keepdim=True)
+    tied = mask & (total == mx)
+    cnt = tied.sum(1, keepdim=True)
+    if check:
+        rest = torch.where(mask & ~tied, total, neg).amax(1, keepdim=True)
+        assert bool((((mx - rest) >= TIE_GAP) | (cnt == 0)).all()), "tie recipe: a losing key is closer than TIE_GAP"
+        assert bool(((cnt & (cnt - 1)) == 0).all()), "tie recipe: the tie count is no power of two"
+    return tied.double() / cnt.clamp(min=1).double()
+
+
+def t5_bias(heads: int, Lq: int, Lk: int, gen: torch.Generator):
+    """(table fp32 [Lq + Lk - 1, heads], lut int32 [Lq + Lk - 1]): every offset k - q has a bucket of its own (lut is a permutation) and the
+    integer entry of (bucket, head) is p * heads + h + p * h * nb * heads for a permutation p of the buckets, centred: distinct per
+    (bucket, head), and the DIFFERENCE between two heads' entries is distinct per bucket - the wrong head, or the wrong offset, moves two tied
+    keys by different amounts (at least 1) and so breaks their tie.  All below 2^23: scores = target - bias are exact in fp32."""
+    nb = Lq + Lk - 1
+    p = torch.randperm(nb, generator=gen).view(nb, 1)
+    h = torch.arange(heads).view(1, heads)
+    table = p * heads + h + p * h * nb * heads
+    assert int(table.max()) < 2 ** 23
+    return (table - int(table.max()) // 2).float(), torch.randperm(nb, generator=gen).to(torch.int32)
+
+
+def t5_bias_rows(table: torch.Tensor, lut: torch.Tensor, batch: int, heads: int, Lq: int, Lk: int, head=None) -> torch.Tensor:
+    """fp64 [batch * heads * Lq, Lk]: bias[(b, h, q)][k] = table[lut[k - q + Lq - 1]][h]; `head` overrides h for every row (the wrong reference)."""
+    q = torch.arange(Lq).view(1, 1, Lq, 1)
+    k = torch.arange(Lk).view(1, 1, 1, Lk)
+    h = torch.arange(heads).view(1, heads, 1, 1) if head is None else torch.full((1, heads, 1, 1), head)
+    bk = lut.long()[k - q + Lq - 1].expand(batch, heads, Lq, Lk)
+    return table.double()[bk, h.expand(batch, heads, Lq, Lk)].reshape(batch * heads * Lq, Lk)
+
+
+def softmax_f64(total: torch.Tensor, valid) -> torch.Tensor:
+    """Ordinary fp64 softmax over each row's first valid[r] keys (zeros past them)."""
+    mask = torch.arange(total.shape[1])[None, :] < torch.as_tensor(valid).view(-1, 1)
+    return torch.softmax(total.masked_fill(~mask, -math.inf), dim=1).masked_fill(~mask, 0.0)
+
+
+def unequal_share(got: torch.Tensor, want: torch.Tensor) -> float:
+    """Share of elements that differ at all (the companion figure of every within-1-ulp comparison)."""
+    return mismatches(got, want, 0).double().mean().item()
+
+
+def gemv_bias(N: int, gen: torch.Generator) -> torch.Tensor:
+    """fp32 [N] bias: distinct multiples of 8 (bias[0] for every row shows, also after a rounding to bf16 of a result below 2048)."""
+    return (torch.randperm(N, generator=gen) - N // 2).float() * 8

@@ -1,10 +1,15 @@
 """The exact-test constructions of tests/exact_util.py, checked on the CPU (no GPU): the integer GEMM / conv data keeps every fp32 sum
 exact at the largest K the GPU tests use, the needle inputs have one winner per row, head and sample with the required margin (and every
 forbidden key would win if read), the MX fp8 operands round-trip through the quantisation contract, and assert_exact names a single
-changed element wherever it sits."""
+changed element wherever it sits.
+
+The row / scheduler / softmax recipes (`unit_rows`, `rope_table`, `unipc_state`, `tie_targets`, ...): fp32 evaluation in a scrambled order
+equals the fp64 answer bit for bit (exactness), the asserted share of results needs a real bf16 rounding, and the reference evaluated with
+one deliberately wrong index differs from the right one in every affected row (sensitivity: the data can see that bug)."""
 import pytest
 import torch
 
+import exact_util as X
 from exact_util import (BF, MIN_MARGIN_NATS, assert_exact, bf16_rne, edge_keys, int_rows, int_vector, linear_f64, mx_operand,
                         needle_k, needle_margins, needle_q, winners_for)
 from test_mxfp8_gemm_gpu import _contract, _deq
@@ -87,3 +92,167 @@ def test_assert_exact_names_a_single_changed_element(pos):
     with pytest.raises(AssertionError):
         assert_exact(got, want, "probe", ulps=0)
     assert_exact(got, want, "one ulp", ulps=1)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# row kernels, scheduler step, softmaxes
+# ------------------------------------------------------------------------------------------------------------------------------------
+ROW_DS = (8, 264, 520, 5112, 5120)
+
+
+def _scrambled_sum(t32: torch.Tensor, gen) -> torch.Tensor:
+    """Row sums of fp32 [M, D] taken sequentially in a random order (another association than torch's own reduction)."""
+    acc = torch.zeros(t32.shape[0], dtype=torch.float32)
+    for j in torch.randperm(t32.shape[1], generator=gen).tolist():
+        acc = acc + t32[:, j]
+    return acc
+
+
+def _each_row_differs(a: torch.Tensor, b: torch.Tensor, rows=None) -> bool:
+    d = (a.float() != b.float()).flatten(1).any(1)
+    return bool(d.all() if rows is None else d[rows].all())
+
+
+@pytest.mark.parametrize("D", ROW_DS)
+def test_unit_rows_statistics_are_exact_in_fp32_in_any_order(D):
+    g = torch.Generator().manual_seed(D)
+    M = 5
+    x, v = X.unit_rows(M, D, g)
+    xf = x.float()
+    s = _scrambled_sum(xf, g)
+    mean = s / float(D)
+    mu64 = x.double().mean(1)
+    assert torch.equal(mean.double(), mu64)
+    d = xf - mean[:, None]
+    var = _scrambled_sum(d * d, g) / float(D)
+    assert torch.equal(var.double(), ((x.double() - mu64[:, None]) ** 2).sum(1) / D)
+    rstd = 1.0 / torch.sqrt(var)
+    assert torch.equal((d * rstd[:, None]).double(), v)  # the normalised values are 0, +-1, +-2 again
+    xc, vc = X.unit_rows(M, D, g, centred=True)          # the RMS form: mean(x^2) = s^2
+    ms = _scrambled_sum(xc.float() ** 2, g) / float(D)
+    assert torch.equal((xc.float() * (1.0 / torch.sqrt(ms))[:, None]).double(), vc)
+
+
+@pytest.mark.parametrize("D", ROW_DS)
+def test_ln_affine_recipe_is_exact_rounds_and_sees_a_wrong_sample(D):
+    g = torch.Generator().manual_seed(100 + D)
+    M, ab_rows = 6, 2
+    _, v = X.unit_rows(M, D, g)
+    a, b = X.affine_vectors(3, D, g)
+    want64 = X.ln_affine_exact(v, a, b, ab_rows)
+    idx = X.sample_of(M, ab_rows)
+    f32 = torch.addcmul(b[idx], v.float(), a[idx])  # (one fused rounding) ...
+    assert torch.equal(f32.double(), want64)
+    assert torch.equal((v.float() * a[idx] + b[idx]).double(), want64)  # ... or two: no difference
+    want = bf16_rne(want64)
+    assert (want.double() != want64).double().mean().item() >= 0.25  # the final bf16 rounding is exercised
+    # (a, b) of sample 0 for all samples: every row of samples 1 and 2 changes
+    wrong = bf16_rne(X.ln_affine_exact(v, a, b, sample=torch.zeros(M, dtype=torch.int64)))
+    assert _each_row_differs(want, wrong, rows=torch.arange(ab_rows, M))
+    # b from the neighbouring column: every row changes
+    assert _each_row_differs(want, bf16_rne(X.ln_affine_exact(v, a, b.roll(1, 1), ab_rows)))
+
+
+@pytest.mark.parametrize("D,hd", [(512, 128), (520, 40), (480, 96), (5120, 128), (5120, 40)])
+def test_rms_rope_recipe_is_exact_and_sees_a_wrong_table_row_or_pair(D, hd):
+    g = torch.Generator().manual_seed(200 + D + hd)
+    R, M = 3, 9
+    _, v = X.unit_rows(M, D, g, centred=True)
+    w = X.rms_weights(D, g)
+    cs = X.rope_table(R, hd, g)
+    want = X.rms_rope_exact(v, w, cs, hd)  # (bf16_rne inside asserts that the fp64 rotation is exact in fp32)
+    # the same in fp32, both association orders of the two products
+    t = (v.float() * w).to(BF).float()
+    rows, pair = torch.arange(M) % R, torch.arange(D // 2) % (hd // 2)
+    co, si = cs[rows][:, pair, 0], cs[rows][:, pair, 1]
+    r0 = torch.addcmul(-(t[:, 1::2] * si), t[:, 0::2], co)
+    r1 = t[:, 1::2] * co + t[:, 0::2] * si
+    assert torch.equal(r0.to(BF), want[:, 0::2]) and torch.equal(r1.to(BF), want[:, 1::2])
+    plain = X.rms_rope_exact(v, w)
+    assert (plain.double() != X.round_bf16_f64(v) * w.double()).double().mean().item() >= 0.25
+    # the table row m in place of m % R (a table that goes on with other rows past R): every row m >= R changes
+    ext = torch.cat([cs, X.rope_table(M - R, hd, g)])
+    assert _each_row_differs(want, X.rms_rope_exact(v, w, ext, hd, table_row=torch.arange(M)), rows=torch.arange(R, M))
+    # the neighbouring pair's cos / sin: every row changes
+    assert _each_row_differs(want, X.rms_rope_exact(v, w, cs, hd, pair_shift=1))
+    # the other tensor's weights (the x2 / w2 launch)
+    assert _each_row_differs(plain, X.rms_rope_exact(v, X.rms_weights(D, g)))
+
+
+@pytest.mark.parametrize("K", [64, 1000, 16384])
+def test_gemv_recipe_is_exact_and_sees_bias_zero_for_all_rows(K):
+    g = torch.Generator().manual_seed(300 + K)
+    N = 17
+    w = int_rows(N, K, g, lo=-2, hi=2, emin=0, emax=0)
+    x = X.dyadic((K,), g, -2, 2, 0)
+    bias = X.gemv_bias(N, g)
+    want64 = linear_f64(w, x[None, :], None)[:, 0] + bias.double()
+    prod = w.float() * x[None, :]
+    assert torch.equal((_scrambled_sum(prod, g) + bias).double(), want64)
+    assert bias.unique().numel() == N and want64.abs().max().item() < 2048
+    wrong = want64 - bias.double() + bias.double()[0]
+    assert bool((wrong[1:] != want64[1:]).all())
+    assert bool((bf16_rne(want64)[1:] != bf16_rne(wrong)[1:]).all())  # still seen after the flag-4 rounding
+
+
+@pytest.mark.parametrize("flags", [0, 1, 2, 3])
+@pytest.mark.parametrize("cfg", [True, False])
+def test_unipc_recipe_is_exact_rounds_and_sees_the_wrong_history_shift(flags, cfg):
+    g = torch.Generator().manual_seed(400 + flags)
+    n = 4096
+    vc, vu, x, xl, m0, m1 = X.unipc_state(n, g)
+    vu = vu if cfg else None
+    (xn, xc, m0n, m1n, x0), rounded = X.unipc_exact(vc, vu, x, xl, m0, m1, flags=flags)  # (asserts exactness of every fp32 value inside)
+    if flags & 2:
+        assert rounded >= 0.25, rounded
+    assert torch.equal(m1n, m0) and torch.equal(m0n, x0)
+    # the same in fp32, FMA-contracted like the device compiler may: no difference
+    if not flags & 2 and cfg:
+        c = X.UNIPC_COEF
+        u = vu.float()
+        v = (u + (c[0] * (vc.float() - u).to(BF).float()).to(BF).float()).to(BF).float()
+        x0f = torch.addcmul(x, torch.full_like(x, -c[1]), v)
+        xcf = torch.addcmul(torch.addcmul(torch.addcmul(c[3] * xl, torch.full_like(x, c[4]), m0), torch.full_like(x, c[5]), m1), torch.full_like(x, c[6]), x0f)
+        xnf = c[9] * m0 + (c[8] * x0f + c[7] * xcf)
+        assert torch.equal(x0f, x0) and torch.equal(xcf, xc) and torch.equal(xnf, xn)
+    # a second step on the new state stays exact, and m1 <- NEW m0 differs from the contract's m1 <- old m0 in (nearly) every element
+    vc2, vu2 = X.unipc_state(n, g)[:2]
+    (_, _, m0b, m1b, _), _ = X.unipc_exact(vc2, vu2 if cfg else None, xn, xc, m0n, m1n, flags=flags)
+    (_, _, _, m1w, _), _ = X.unipc_exact(vc2, vu2 if cfg else None, xn, xc, m0n, m1n, flags=flags, m1_from_new=True)
+    assert torch.equal(m1b, m0n) and (m1w != m1b).float().mean() > 0.9
+    assert (m1n != m0n).float().mean() > 0.9  # distinct values: the shift is visible
+
+
+@pytest.mark.parametrize("Lq,Lk", [(5, 5), (7, 100), (64, 65), (3, 1024)])
+def test_softmax_tie_recipe_is_exact_and_sees_a_wrong_head_or_an_ignored_mask(Lq, Lk):
+    g = torch.Generator().manual_seed(500 + Lk)
+    batch, heads = 2, 3
+    rows = batch * heads * Lq
+    valid_b = torch.tensor([max(Lk // 2, 1), 1 if Lk > 5 else Lk])
+    valid = valid_b.repeat_interleave(heads * Lq)
+    target = X.tie_targets(rows, Lk, valid, g)
+    table, lut = X.t5_bias(heads, Lq, Lk, g)
+    bias = X.t5_bias_rows(table, lut, batch, heads, Lq, Lk)
+    scores = (target.double() - bias).float()
+    assert torch.equal(scores.double(), target.double() - bias)
+    total32 = scores + bias.float()
+    assert torch.equal(total32.double(), target.double())
+    want = X.tie_probs(target.double(), valid)
+    # fp32 softmax in a scrambled order gives exactly 2^-k on the tied keys and 0 elsewhere
+    mask = torch.arange(Lk)[None, :] < valid[:, None]
+    e = torch.where(mask, torch.exp(total32 - total32.masked_fill(~mask, -1e30).amax(1, keepdim=True)), torch.zeros(()))
+    assert torch.equal((e / _scrambled_sum(e, g)[:, None]).double(), want)
+    assert want.sum(1).eq(1).all() and (want.amax(1) < 1).any()
+    # head 0's bias column for every head: every row of heads 1.. changes
+    h_of = (torch.arange(rows) // Lq) % heads
+    wrong = X.tie_probs(scores.double() + X.t5_bias_rows(table, lut, batch, heads, Lq, Lk, head=0), valid, check=False)
+    assert _each_row_differs(want, wrong, rows=((h_of > 0) & (valid > 1)).nonzero()[:, 0])
+    # the offset k - q wrong by one (with the 9 buckets of the 5 x 5 case two tied keys may move by the same amount: not asserted there)
+    wrong = X.tie_probs(scores.double() + X.t5_bias_rows(table, lut.roll(1), batch, heads, Lq, Lk), valid, check=False)
+    if Lk > 5:
+        assert _each_row_differs(want, wrong, rows=(valid > 1).nonzero()[:, 0])
+    # valid_len ignored: every row with a masked key changes (the masked keys win); one key too tight: the tie count changes
+    wrong = X.tie_probs(target.double(), torch.full_like(valid, Lk), check=False)
+    assert _each_row_differs(want, wrong, rows=(valid < Lk).nonzero()[:, 0])
+    wrong = X.tie_probs(target.double(), valid - 1, check=False)
+    assert _each_row_differs(want, wrong)
