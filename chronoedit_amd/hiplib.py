@@ -90,6 +90,7 @@ SIGNATURES: Dict[str, List] = {
     "ce_softmax_rows_f32_bf16": [_P, _P, _I, _I, _I, _I, _I, _F, _P],
     "ce_attention_1head_bf16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _c.c_longlong, _P],
     "ce_cfg_unipc_step": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_longlong, _I, _P],
+    "ce_cfg_unipc_step_delta": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_longlong, _I, _I, _I, _P, _c.c_longlong, _P, _I, _P],
     "ce_lora_merge_bf16": [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "ce_tea_rel_l1_bf16": [_P, _I, _I, _P, _P],
     "ce_tea_store_bf16": [_P, _P, _c.c_longlong, _P],

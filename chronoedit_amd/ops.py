@@ -657,6 +657,54 @@ def cfg_unipc_step(v_cond: torch.Tensor, v_uncond: Optional[torch.Tensor], x: to
     return x
 
 
+CFG_MAX_AGE = 4  # the largest ring ce_cfg_unipc_step_delta measures against (csrc/ce_sched.hip)
+
+
+def cfg_unipc_step_delta(v_cond: torch.Tensor, v_uncond: Optional[torch.Tensor], x: torch.Tensor, x_last: torch.Tensor, m0: torch.Tensor,
+                         m1: torch.Tensor, coef: torch.Tensor, delta: torch.Tensor, x0_out: Optional[torch.Tensor] = None,
+                         round_sigma_v: bool = True, bf16_state: bool = False, slot: Optional[int] = None,
+                         table: Optional[torch.Tensor] = None, row: int = 0):
+    """cfg_unipc_step with the guidance direction d = bf16(c - u) kept in `delta` (bf16, contiguous).
+    v_uncond given: STORE - the outputs of cfg_unipc_step bit for bit, and delta (n elements) <- d.
+    v_uncond None: REUSE - delta is only read: u' = bf16(c - d), v = bf16(u' + bf16(g * d)), then as cfg_unipc_step.
+    slot / table given (with v_uncond): MEASURE - delta is a ring [A, n] (A <= 4) whose slot `slot` receives d; before that the pass sums
+    (d - ring[(slot - a) % A])^2 for a = 1..A and d^2 over all elements (fp32, fixed order) into table[row] (table fp32 [rows, A + 1])."""
+    _dev(v_cond, torch.bfloat16, "v_cond"), _dev(delta, torch.bfloat16, "delta")
+    for name, t in (("x", x), ("x_last", x_last), ("m0", m0), ("m1", m1), ("coef", coef)):
+        _dev(t, torch.float32, name)
+        assert t.is_contiguous()
+    if v_uncond is not None:
+        _dev(v_uncond, torch.bfloat16, "v_uncond")
+        assert v_uncond.is_contiguous()
+    assert v_cond.is_contiguous() and delta.is_contiguous() and coef.numel() >= 10
+    n = x.numel()
+    assert v_cond.numel() == n == x_last.numel() == m0.numel() == m1.numel()
+    assert v_uncond is None or v_uncond.numel() == n
+    assert x0_out is None or (x0_out.dtype == torch.float32 and x0_out.is_contiguous() and x0_out.numel() == n)
+    flags = int(round_sigma_v) | (2 if bf16_state else 0)
+    if slot is None and table is None:
+        if delta.numel() != n:
+            raise ValueError(f"delta: need {n} elements, got shape {tuple(delta.shape)}")
+        _check(lib().ce_cfg_unipc_step_delta(_ptr(v_cond), _ptr(v_uncond), _ptr(x), _ptr(x_last), _ptr(m0), _ptr(m1), _ptr(x0_out), _ptr(coef),
+                                             _ptr(delta), n, flags, 0, 0, _ptr(None), 0, _ptr(None), 0, _stream()), "ce_cfg_unipc_step_delta")
+        return x
+    if v_uncond is None or slot is None or table is None:
+        raise ValueError("measuring is an option of the store mode: it needs v_uncond, slot and table")
+    A = delta.shape[0]
+    if delta.dim() < 2 or not 1 <= A <= CFG_MAX_AGE or delta.numel() != A * n:
+        raise ValueError(f"delta: measuring needs a ring [A, {n}] with 1 <= A <= {CFG_MAX_AGE}, got shape {tuple(delta.shape)}")
+    _dev(table, torch.float32, "table")
+    if table.dim() != 2 or table.shape[1] != A + 1 or not table.is_contiguous() or not 0 <= int(row) < table.shape[0]:
+        raise ValueError(f"table: need contiguous fp32 [rows, {A + 1}] with rows > row = {row}, got shape {tuple(table.shape)}")
+    if not 0 <= int(slot) < A:
+        raise ValueError(f"slot {slot} is outside the ring of {A}")
+    scratch = torch.empty((CFG_MAX_AGE + 1) * 2048, dtype=torch.float32, device=x.device)  # five sums per workgroup, at most 2048 of them
+    _check(lib().ce_cfg_unipc_step_delta(_ptr(v_cond), _ptr(v_uncond), _ptr(x), _ptr(x_last), _ptr(m0), _ptr(m1), _ptr(x0_out), _ptr(coef),
+                                         _ptr(delta), n, flags, A, int(slot), _ptr(scratch), scratch.numel() * 4, _ptr(table), int(row), _stream()),
+           "ce_cfg_unipc_step_delta")
+    return x
+
+
 # ---- TeaCache step skipping (csrc/ce_tea.hip) ------------------------------------------------------------------------
 def tea_rel_l1(rows: torch.Tensor, out: Optional[torch.Tensor] = None):
     """rows bf16 [S, n] (one time-projection row per scheduled step) -> fp32 [S, 2]: per step i >= 1 the sums of |bf16(row_i - row_{i-1})|

@@ -141,14 +141,23 @@ def _sharded_batchable(transformer) -> bool:
 def denoise_step(transformer: ChronoEditTransformer3DModel, scheduler: FlowUniPCMultistepScheduler, latents: torch.Tensor,
                  condition: torch.Tensor, t: torch.Tensor, prompt_embeds: torch.Tensor,
                  negative_prompt_embeds: Optional[torch.Tensor], image_embeds: Optional[torch.Tensor],
-                 guidance_scale: float, batch_cfg: bool = True, cfg_inputs=None) -> torch.Tensor:
-    """latents fp32 [B,16,T,h,w] (updated in place), condition bf16 [B,20,T,h,w]  (pipeline_chronoedit.py:711-739)."""
+                 guidance_scale: float, batch_cfg: bool = True, cfg_inputs=None, guidance_kind: Optional[str] = None,
+                 delta: Optional[torch.Tensor] = None, delta_measure=None) -> torch.Tensor:
+    """latents fp32 [B,16,T,h,w] (updated in place), condition bf16 [B,20,T,h,w]  (pipeline_chronoedit.py:711-739).
+    guidance_kind (guidance reuse, chronoedit_amd/guidance.py; needs the bf16 `delta` buffer of the latents' shape): "pair" = the guided
+    step as ever, which also stores the guidance direction in `delta` (delta_measure = (slot, table, row): into that slot of a ring, with
+    the distance sums); "reuse" = the conditional sample alone, guided by the stored direction; "off" = the conditional sample alone,
+    unguided.  None: the plain step."""
+    if guidance_kind not in (None, "pair", "reuse", "off"):
+        raise ValueError(f"denoise_step: guidance_kind {guidance_kind!r} is none of 'pair', 'reuse', 'off'")
+    if guidance_kind in ("pair", "reuse") and (delta is None or not (guidance_scale > 1.0 and negative_prompt_embeds is not None)):
+        raise ValueError(f"denoise_step: a {guidance_kind!r} step needs a guided edit and its delta buffer")
     latent_model_input = torch.cat([latents.to(torch.bfloat16), condition], dim=1)
     B = latents.shape[0]
     timestep = t.expand(B)
     batch_cfg = batch_cfg and (not _token_sharded(transformer) or _sharded_batchable(transformer))
     cfgp = getattr(transformer, "_cfgp", None)
-    if guidance_scale > 1.0 and negative_prompt_embeds is not None:  # do_classifier_free_guidance
+    if guidance_scale > 1.0 and negative_prompt_embeds is not None and guidance_kind not in ("reuse", "off"):  # do_classifier_free_guidance
         if cfgp is not None:
             # CFG parallelism: this rank's Ulysses group runs ONE of the two passes, the predictions are exchanged pairwise
             text = prompt_embeds if cfgp.branch == 0 else negative_prompt_embeds
@@ -169,6 +178,9 @@ def denoise_step(transformer: ChronoEditTransformer3DModel, scheduler: FlowUniPC
         compact_text_context(prompt_embeds)  # (examined once per tensor version: later steps find the attribute)
         noise_pred = transformer(latent_model_input, timestep, prompt_embeds, image_embeds, return_dict=False)[0]
         noise_uncond = None
+    if guidance_kind in ("pair", "reuse"):
+        mode = "reuse" if guidance_kind == "reuse" else "store" if delta_measure is None else "measure"
+        return scheduler.step_cfg(noise_pred, noise_uncond, guidance_scale, latents, delta=delta, delta_mode=mode, delta_measure=delta_measure)
     return scheduler.step_cfg(noise_pred, noise_uncond, guidance_scale, latents)
 
 
@@ -196,10 +208,15 @@ class GraphedDenoiser:
     `step()` the transformer's modes (fp8, sequence parallelism, cache_context) must not change; other forwards of the same transformer
     are allowed (the lazy capture re-primes its context entry).
     With a TeaCache plan (`tea_plan`, chronoedit_amd/teacache.py: one bool per step of the schedule, True = compute) the computed steps replay
-    one graph and the skipped steps a second one, captured lazily at the first skipped step; both address the engine's one residual buffer."""
+    one graph and the skipped steps a second one, captured lazily at the first skipped step; both address the engine's one residual buffer.
+    With a guidance-reuse plan (`guidance_plan`, chronoedit_amd/guidance.py: "pair" / "reuse" / "off" per step, and the loop's `delta` buffer)
+    there is one graph per kind of step the plan contains, each captured lazily at the first step of its kind that is replayed; all of them
+    address the same latents, scheduler history, staging buffers and delta buffer.  "reuse" and "off" run ONE sample where "pair" runs two: the
+    first step of either form on an engine that has not run it yet (`is_warm`) runs eagerly, for real, before that form is captured."""
 
     def __init__(self, transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
-                 guidance_scale: float, batch_cfg: bool = True, warm: bool = False, keep_warmup_step: bool = True, tea_plan=None):
+                 guidance_scale: float, batch_cfg: bool = True, warm: bool = False, keep_warmup_step: bool = True, tea_plan=None,
+                 guidance_plan=None, delta: Optional[torch.Tensor] = None):
         """warm: this process has already run a step of exactly this shape / guidance form through `transformer` (packed weights,
         workspaces, kernel attributes exist), so no un-captured step is needed in front of the capture; only the step-invariant context
         projections are computed eagerly so that the graph holds the cache HIT (`cache_context`), not the projections.
@@ -219,6 +236,7 @@ class GraphedDenoiser:
             raise NotImplementedError("hipGraph capture of a step with torch.distributed exchanges is not usable on this torch / RCCL build: "
                                       "enable_sequence_parallel(owned_comm=True) or run the sharded loop eagerly")
         self.tr, self.sch, self.latents, self.condition = transformer, scheduler, latents, condition
+        self._ran_eagerly = set()  # sample counts (1: the single sample, 2: the stacked pair) this object has run an eager step of
         self.prompt, self.negative, self.image, self.g, self.batch_cfg = prompt_embeds, negative_prompt_embeds, image_embeds, guidance_scale, batch_cfg
         dev = latents.device
         self.cfg_inputs = None
@@ -227,6 +245,15 @@ class GraphedDenoiser:
             self.cfg_inputs = make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds)
         elif not self.guided:
             compact_text_context(prompt_embeds)  # (here, not under the capture: it reads the lengths back)
+        self.guidance_plan = None if guidance_plan is None or not self.guided else [str(k) for k in guidance_plan]
+        self.delta = delta
+        if self.guidance_plan is not None:
+            if tea_plan is not None:
+                raise ValueError("guidance reuse and TeaCache exclude each other")
+            if delta is None or delta.shape != latents.shape or delta.dtype != torch.bfloat16 or not delta.is_contiguous():
+                raise ValueError("guidance reuse: the delta buffer must be a contiguous bf16 tensor of the latents' shape")
+            if any(k != "pair" for k in self.guidance_plan):
+                compact_text_context(prompt_embeds)  # the single-sample steps' context, examined once, outside any capture
         self.tea_plan = None if tea_plan is None else [bool(c) for c in tea_plan]
         if self.tea_plan is not None and self.guided and self.cfg_inputs is None:
             raise NotImplementedError("TeaCache needs the guidance pair as ONE batched forward (one residual buffer covers both samples)")
@@ -237,9 +264,9 @@ class GraphedDenoiser:
             scheduler.last_sample = torch.zeros_like(latents)
         idx0 = scheduler._step_index
         self._stage(idx0 or 0)
-        eng = getattr(transformer, "_engine", None)
-        n_samples = latents.shape[0] * (2 if self.cfg_inputs is not None else 1)
-        warm = bool(warm and eng is not None and hasattr(eng, "is_warm") and eng.is_warm(n_samples, *latents.shape[2:]))
+        kind0 = self._kind(idx0 or 0)
+        self._caller_warm = bool(warm)
+        warm = self._form_warm(kind0)
         self._done_index = None  # the step that already ran eagerly (below); step() does not replay it
         if not warm:
             # lazy initialisations (packed weights, workspaces, function attributes) must not happen under capture: run the CURRENT step
@@ -248,8 +275,9 @@ class GraphedDenoiser:
             side = _warmup_stream(dev)  # ONE long-lived side stream per device: every stream GEMMs run on gets a split-K scratch of its own (ops._gemm_scratch)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._body(self._skips(idx0 or 0))
+                self._body(kind0)
             torch.cuda.current_stream().wait_stream(side)
+            self._ran_eagerly.add(self._n_samples(kind0))
             if keep_warmup_step:
                 self._done_index = idx0 or 0
             else:
@@ -258,48 +286,74 @@ class GraphedDenoiser:
                     m.copy_(sv)
                 scheduler.last_sample.copy_(saved[2])
         else:
-            self._prime_context()
+            self._prime_context(kind0)
         # The capture: at once when every step() must be a replay (warm shape, or keep_warmup_step=False); LAZILY - at the first step() that needs a
         # replay - when the constructor already ran the trajectory's current step eagerly: if that was the last step of this shape (truncation lands
         # there, or a callback replaces the latents every step) nothing is ever replayed and a whole capture would be thrown away
-        self.graph = None       # the step that runs the whole model (with TeaCache: the computed steps)
-        self.skip_graph = None  # TeaCache: the skipped steps
+        self.graphs = {}  # kind of step -> captured graph
         if self._done_index is None:
-            self._capture(self._skips(idx0 or 0))
+            self._capture(kind0)
         scheduler._step_index = idx0  # step_cfg counts on the host, also while being captured
 
-    def _prime_context(self):
-        """With `cache_context`: the step-invariant context projections of THIS conditioning computed eagerly now, so that the capture
-        records the cache hit and not the projections."""
+    @property
+    def graph(self):
+        """The step that runs the whole model on the edit's usual form (with TeaCache: the computed steps; with guidance reuse: "pair")."""
+        return self.graphs.get("compute", self.graphs.get("pair"))
+
+    @property
+    def skip_graph(self):
+        """TeaCache: the skipped steps."""
+        return self.graphs.get("skip")
+
+    def _single(self, kind: str) -> bool:
+        """Does a step of this kind run the conditional sample alone?"""
+        return not self.guided or kind in ("reuse", "off")
+
+    def _n_samples(self, kind: str) -> int:
+        return self.latents.shape[0] * (2 if self.cfg_inputs is not None and not self._single(kind) else 1)
+
+    def _form_warm(self, kind: str) -> bool:
+        """May a step of this kind be captured without an eager step of its form in front?  Yes when this object already ran one, or when the
+        caller vouches for the edit's shape (`warm`) and the engine holds the workspace of exactly this sample count."""
+        n = self._n_samples(kind)
+        if n in self._ran_eagerly:
+            return True
+        eng = getattr(self.tr, "_engine", None)
+        return bool(self._caller_warm and eng is not None and hasattr(eng, "is_warm") and eng.is_warm(n, *self.latents.shape[2:]))
+
+    def _prime_context(self, kind: str = "compute"):
+        """With `cache_context`: the step-invariant context projections of THIS conditioning, in the form a step of this kind looks up,
+        computed eagerly now, so that the capture records the cache hit and not the projections."""
         tr = self.tr
         if hasattr(tr, "prime_context"):  # (without `cache_context` it only reserves the buffers of a compacted text context)
-            if self.cfg_inputs is not None:
+            if self._single(kind):
+                if not self.guided or self.guidance_plan is not None:
+                    tr.prime_context(self.prompt, self.image)
+            elif self.cfg_inputs is not None:
                 with _shared_inputs(tr):  # (the entry the captured forward will look up)
                     tr.prime_context(self.cfg_inputs[0], self.cfg_inputs[1])
-            elif not self.guided:
-                tr.prime_context(self.prompt, self.image)
 
-    def _skips(self, i: int) -> bool:
-        return self.tea_plan is not None and not self.tea_plan[i]
+    def _kind(self, i: int) -> str:
+        """The kind of step i: which graph replays it."""
+        if self.guidance_plan is not None:
+            return self.guidance_plan[i]
+        return "skip" if self.tea_plan is not None and not self.tea_plan[i] else "compute"
 
-    def _capture(self, skip: bool = False):
+    def _capture(self, kind: str = "compute"):
         # The LAZY capture (first replayed step()) runs at an arbitrary later point of the caller's program: another forward of the same
         # transformer in between (another conditioning of the same shape) may have replaced the context-cache entry and the engine-owned
         # context buffers the eager step left, so the entry is re-primed here (a hit costs nothing) - ADVICE r5.  torch.cuda.graph() itself
         # synchronises the device and runs a gc pass: callers that cannot afford that inside their loop build with keep_warmup_step=False
         # (capture in the constructor).
-        self._prime_context()
+        self._prime_context(kind)
         if self.tea_plan is not None:  # the residual buffer both graphs address exists before either is captured
             self.tr.engine().tea_reserve(self.latents.shape[0] * (2 if self.cfg_inputs is not None else 1) * self._tokens())
         idx = self.sch._step_index
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):  # (a capture executes nothing: the device state stays what the eager step left)
-            self._body(skip)
+            self._body(kind)
         self.sch._step_index = idx
-        if skip:
-            self.skip_graph = graph
-        else:
-            self.graph = graph
+        self.graphs[kind] = graph
 
     def _tokens(self) -> int:
         _, _, T, h, w = self.latents.shape
@@ -309,19 +363,26 @@ class GraphedDenoiser:
         self.t_buf.copy_(self.sch.timesteps[i])
         self.coef_buf.copy_(self.sch.coef_row(i, self.g, self.latents.device))
 
-    def _body(self, skip: bool = False):
+    def _body(self, kind: str = "compute"):
         if self.tea_plan is None:
-            return self._step_body()
-        self.tr._tea_mode = "skip" if skip else "compute"
+            return self._step_body(kind)
+        self.tr._tea_mode = "skip" if kind == "skip" else "compute"
         try:
-            return self._step_body()
+            return self._step_body(kind)
         finally:
             self.tr._tea_mode = None  # a forward outside the loop runs the whole model
 
-    def _step_body(self):
+    def _step_body(self, kind: str = "compute"):
         inp = torch.cat([self.latents.to(torch.bfloat16), self.condition], dim=1)
         B = inp.shape[0]
         ts = self.t_buf.expand(B)
+        if self.guided and self._single(kind):  # guidance reuse: the conditional sample alone
+            c = self.tr(inp, ts, self.prompt, self.image, return_dict=False)[0]
+            if kind == "reuse":
+                self.sch.step_cfg(c, None, self.g, self.latents, coef=self.coef_buf, delta=self.delta, delta_mode="reuse")
+            else:
+                self.sch.step_cfg(c, None, self.g, self.latents, coef=self.coef_buf)
+            return
         if self.cfg_inputs is not None:
             with _shared_inputs(self.tr):
                 out = self.tr(torch.cat([inp, inp], 0), torch.cat([ts, ts], 0), self.cfg_inputs[0], self.cfg_inputs[1], return_dict=False)[0]
@@ -331,7 +392,10 @@ class GraphedDenoiser:
             u = self.tr(inp, ts, self.negative, self.image, return_dict=False)[0]
         else:
             c, u = self.tr(inp, ts, self.prompt, self.image, return_dict=False)[0], None
-        self.sch.step_cfg(c, u, self.g, self.latents, coef=self.coef_buf)
+        if kind == "pair":
+            self.sch.step_cfg(c, u, self.g, self.latents, coef=self.coef_buf, delta=self.delta, delta_mode="store")
+        else:
+            self.sch.step_cfg(c, u, self.g, self.latents, coef=self.coef_buf)
 
     def step(self, i: int) -> torch.Tensor:
         if self._done_index is not None:  # the constructor already ran ONE real step (index _done_index) eagerly on the live state
@@ -342,11 +406,24 @@ class GraphedDenoiser:
             self._done_index = None
             self.sch._step_index = i + 1
             return self.latents
-        skip = self._skips(i)
-        if (self.skip_graph if skip else self.graph) is None:
-            self._capture(skip)
+        kind = self._kind(i)
+        if kind not in self.graphs:
+            if not self._form_warm(kind):
+                # this form (the single sample after pairs, or the other way round) has not run on this engine yet: its lazy initialisations
+                # must not happen under capture, so THIS step runs eagerly, on the live state, as the constructor's first step does
+                self._stage(i)
+                self.sch._step_index = i
+                side = _warmup_stream(self.latents.device)
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    self._body(kind)
+                torch.cuda.current_stream().wait_stream(side)
+                self._ran_eagerly.add(self._n_samples(kind))
+                self.sch._step_index = i + 1
+                return self.latents
+            self._capture(kind)
         self._stage(i)
-        (self.skip_graph if skip else self.graph).replay()
+        self.graphs[kind].replay()
         self.sch._step_index = i + 1
         return self.latents
 
@@ -355,7 +432,8 @@ class GraphedDenoiser:
 def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
             num_inference_steps: int, guidance_scale: float = 5.0, enable_temporal_reasoning: bool = False,
             num_temporal_reasoning_steps: int = 0, use_graph: bool = False, on_step_end=None, interrupted=None, graph_warm=None,
-            teacache=None, teacache_measure: bool = False):
+            teacache=None, teacache_measure: bool = False, guidance_reuse=None, guidance_measure: Optional[int] = None,
+            keep_deltas: bool = False):
     """The whole loop, including the temporal-reasoning truncation 8 -> 2 latent frames (pipeline_chronoedit.py:700-709).
     on_step_end(i, t, latents) -> replacement latents, a dict with any of latents / prompt_embeds / negative_prompt_embeds, or None
     (the reference's callback_on_step_end hook, :741-749); graph_warm: a set the caller keeps across edits - shapes already run once in
@@ -372,7 +450,18 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     step's residual, on the device, into a table read back once after the last step: afterwards `transformer.teacache_measurement` holds
     {"ratios": teacache_ratios(timesteps), "distances": per step, NaN for step 0 and for the first step after the truncation} - the points
     teacache.fit_calibration fits.  A measured edit always runs eagerly (`use_graph` is ignored: the table row changes per step, and
-    calibration is offline).  Together with a skip plan (`teacache=` or an enabled TeaCache) it is a ValueError."""
+    calibration is offline).  Together with a skip plan (`teacache=` or an enabled TeaCache) it is a ValueError.
+    guidance_reuse: a guidance.GuidanceReuseConfig for this call; None = whatever `transformer.enable_guidance_reuse()` set (nothing: every
+    guided step runs the pair).  The "pair" / "reuse" / "off" plan of the whole edit is made here, before the first step, from the schedule
+    alone (the truncation step is always a "pair": an 8-frame direction does not fit 2-frame latents); afterwards
+    `transformer.guidance_report` holds {"plan", "pair", "reuse", "off"}.  An edit without guidance ignores the config and its report is
+    None.  The stored direction is one bf16 tensor of the latents' shape that this loop owns: a second edit never sees the first one's.  A
+    callback that replaces the latents keeps it; one that replaces an embedding makes the next guided step a "pair".  With TeaCache (enabled
+    or measuring) it is a ValueError, with sharded tokens or CFG parallelism a NotImplementedError.
+    guidance_measure = A (1..4): every step a "pair" whose store pass also measures, on the device, how far the direction is from those
+    of the 1..A steps before; one read-back after the last step.  The latents are the plain loop's; runs eagerly.  Afterwards
+    `transformer.guidance_measurement` holds {"timesteps", "rel_l2": [steps][A] (NaN where no direction of that age and shape exists)} and,
+    with keep_deltas, "deltas": the per-step directions (bf16, on the CPU)."""
     scheduler.set_timesteps(num_inference_steps, device=latents.device)
     latents = latents.to(torch.float32).contiguous()
     sharded = getattr(transformer, "_cfgp", None) is not None or (_token_sharded(transformer) and not _sharded_batchable(transformer))
@@ -386,6 +475,36 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     if measure and tea is not None:
         raise ValueError("TeaCache: measuring (teacache_measure / calibrate_teacache) and a skip plan (teacache= / enable_teacache) "
                          "exclude each other: disable_teacache() first")
+    # -- guidance reuse: the plan of the edit, and the one buffer that holds the stored direction (loop-owned: dropped with the edit)
+    guided = guidance_scale > 1.0 and negative_prompt_embeds is not None
+    gr = guidance_reuse if guidance_reuse is not None else getattr(transformer, "_guidance_reuse", None)
+    g_plan = delta = g_ring = g_table = None
+    g_forced = {int(num_temporal_reasoning_steps)} if enable_temporal_reasoning else set()
+    g_seen, g_history, g_kept = 0, [0] * len(scheduler.timesteps), []  # measuring: directions of this shape stored so far; per step, how many the ring held
+    if hasattr(transformer, "guidance_report"):
+        transformer.guidance_report = None
+    if guidance_measure is not None and not guided:
+        raise ValueError("guidance_measure needs a guided edit (guidance_scale > 1 and negative_prompt_embeds)")
+    if guided and (gr is not None or guidance_measure is not None):
+        from . import guidance as _gd
+        if tea is not None or measure:
+            raise ValueError("guidance reuse and TeaCache (enabled or measuring) exclude each other: the cached residual has the guidance "
+                             "pair's row count, which a single-sample step does not match")
+        if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
+            raise NotImplementedError("guidance reuse with the tokens sharded over ranks or with CFG parallelism is not implemented "
+                                      "(the stored direction is latent-local; nothing sharded has been tested with it)")
+        if guidance_measure is not None:
+            from . import ops as _ops
+            if guidance_reuse is not None:
+                raise ValueError("guidance_measure measures the plain loop (every step a pair): it takes no guidance_reuse plan")
+            if not 1 <= int(guidance_measure) <= _ops.CFG_MAX_AGE:
+                raise ValueError(f"guidance_measure: max_age must be in 1..{_ops.CFG_MAX_AGE}, got {guidance_measure}")
+            gr = _gd.GuidanceReuseConfig(pair_every=1)
+            use_graph = False  # the table row and the ring slot change per step, and measuring is offline
+            g_table = torch.full((len(scheduler.timesteps), int(guidance_measure) + 1), float("nan"), dtype=torch.float32, device=latents.device)
+        g_plan = _gd.plan(len(scheduler.timesteps), gr, g_forced)
+        transformer.guidance_report = _gd.report(g_plan)
+    delta_valid = False  # has a "pair" step of this edit, at this latent shape and conditioning, written the direction?
     tea_plan = None
     if tea is not None:
         from . import teacache as _tea
@@ -420,6 +539,16 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                     scheduler.model_outputs[j] = mo[:, :, [0, -1]].contiguous()
             if scheduler.last_sample is not None and scheduler.last_sample.shape[-3] != latents.shape[-3]:
                 scheduler.last_sample = scheduler.last_sample[:, :, [0, -1]].contiguous()
+        kind = None if g_plan is None else g_plan[i]
+        if g_plan is not None:
+            if g_table is not None:  # measuring: a ring of the last A directions of this latent shape
+                A = g_table.shape[1] - 1
+                if g_ring is None or g_ring.shape[1:] != latents.shape:
+                    g_ring, g_seen = torch.zeros((A,) + tuple(latents.shape), dtype=torch.bfloat16, device=latents.device), 0
+            elif delta is None or delta.shape != latents.shape:  # (re-made at the truncation; never under a capture)
+                delta, delta_valid = torch.zeros(latents.shape, dtype=torch.bfloat16, device=latents.device), False
+            if kind == "reuse" and not delta_valid:
+                raise RuntimeError(f"guidance reuse: step {i} is planned to reuse a direction no step has stored")
         if use_graph:
             if graphed is None:
                 if scheduler._step_index is None:
@@ -430,13 +559,28 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                     gen = transformer.engine_generation() if hasattr(transformer, "engine_generation") else id(transformer)
                     # (the scheduler object is not part of the key: everything a step reads from it is created eagerly by GraphedDenoiser
                     # before the capture - _ensure_state, the staged timestep / coefficient row - so a fresh scheduler per edit stays warm)
-                    return (tuple(latents.shape), guidance_scale > 1.0 and negative_prompt_embeds is not None, gen, tea_plan is not None)
+                    # (with guidance reuse: which forms - the stacked pair, the single sample - the rest of the plan runs; GraphedDenoiser
+                    # asks the engine per form on top of this)
+                    forms = None if g_plan is None else tuple(sorted({1 if k in ("reuse", "off") else 2 for k in g_plan[i:]}))
+                    return (tuple(latents.shape), guidance_scale > 1.0 and negative_prompt_embeds is not None, gen, tea_plan is not None, forms)
                 graphed = GraphedDenoiser(transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds,
                                           image_embeds, guidance_scale, batch_cfg=not sharded, warm=graph_warm is not None and warm_key() in graph_warm,
-                                          tea_plan=tea_plan)
+                                          tea_plan=tea_plan, guidance_plan=g_plan, delta=delta)
                 if graph_warm is not None:
                     graph_warm.add(warm_key())  # (taken AFTER the construction: the first step of a process creates the engine)
             latents = graphed.step(i)
+        elif g_plan is not None:
+            dm = None
+            if g_table is not None:
+                dm = (g_seen % A, g_table, i)
+                g_history[i] = min(g_seen, A)
+            latents = denoise_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds,
+                                   image_embeds, guidance_scale, batch_cfg=not sharded, cfg_inputs=cfg_inputs, guidance_kind=kind,
+                                   delta=delta if g_table is None else g_ring, delta_measure=dm)
+            if g_table is not None:
+                if keep_deltas:
+                    g_kept.append(g_ring[g_seen % A].clone())
+                g_seen += 1
         elif tea_plan is None and not measure:
             latents = denoise_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds,
                                    image_embeds, guidance_scale, batch_cfg=not sharded, cfg_inputs=cfg_inputs)
@@ -449,6 +593,10 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                                        image_embeds, guidance_scale, batch_cfg=True, cfg_inputs=cfg_inputs)
             finally:
                 transformer._tea_mode = None  # a forward outside the loop runs the whole model
+        if kind == "pair":
+            delta_valid = True
+        elif kind == "off":
+            delta_valid = False
         if on_step_end is not None:
             new = on_step_end(i, t, latents)
             if isinstance(new, dict):  # the reference's callback may also replace the conditioning (pipeline_chronoedit.py:747-749)
@@ -459,6 +607,14 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                     if cfg_inputs is not None:
                         cfg_inputs = make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds)
                     graphed = None  # the graph holds the stacked conditioning it was captured with
+                    if g_plan is not None and g_table is None and i + 1 < len(g_plan):
+                        # the stored direction belongs to the old conditioning: the next guided step runs the pair, the count restarts there
+                        g_forced = g_forced | {i + 1}
+                        g_plan = g_plan[: i + 1] + _gd.plan(len(g_plan), gr, g_forced)[i + 1:]
+                        if g_plan[i + 1] == "reuse":  # (an inside step: forced)
+                            raise RuntimeError("guidance reuse: the re-planned step is not a pair")
+                        transformer.guidance_report = _gd.report(g_plan)
+                        delta_valid = False
                 new = new.get("latents")
             if new is not None and new is not latents:
                 graphed = None  # the graph is tied to the latents' storage
@@ -467,6 +623,12 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
         from .teacache import distances_from_sums
         sums = transformer.engine().tea_measure_end()  # the one read of the table, after the last step
         transformer.teacache_measurement = {"ratios": [float(r) for r in tea_ratios], "distances": distances_from_sums(sums.numpy())}
+    if g_table is not None:
+        m = {"timesteps": [int(v) for v in scheduler.timesteps.tolist()],
+             "rel_l2": _gd.rel_l2_from_sums(g_table.cpu().numpy(), g_table.shape[1] - 1, g_history)}  # the one read of the table
+        if keep_deltas:
+            m["deltas"] = [d.cpu() for d in g_kept]
+        transformer.guidance_measurement = m
     return latents
 
 
@@ -574,6 +736,7 @@ class ChronoEditPipeline:
         if transformer is not None and hasattr(transformer, "cache_context"):
             transformer.cache_context = True
         self._guidance_scale, self._attention_kwargs, self._current_timestep, self._interrupt, self._num_timesteps = 1.0, None, None, False, 0
+        self._guidance_measure = None  # (max_age, keep_deltas) while measure_guidance_reuse runs its edits
 
     # -- properties of the reference pipeline (:458-478) ---------------------------------------------------------------
     @property
@@ -816,6 +979,47 @@ class ChronoEditPipeline:
 
         return self.transformer.calibrate_teacache([runner(kw) for kw in edits], degree=degree)
 
+    # Guidance reuse (chronoedit_amd/guidance.py): the unconditional sample only on planned steps.  Off by default; a switch on the
+    # pipeline, `__call__` keeps the reference's signature and `edit_tensors` honours it too
+    def enable_guidance_reuse(self, pair_every: int = 2, interval=(0.0, 1.0)):
+        self.transformer.enable_guidance_reuse(pair_every, interval)
+        return self
+
+    def disable_guidance_reuse(self):
+        self.transformer.disable_guidance_reuse()
+        return self
+
+    def measure_guidance_reuse(self, edits, num_inference_steps: int, max_age: int = 3, guidance_scale: float = 5.0, keep_deltas: bool = False,
+                               **call_kwargs):
+        """How fast the guidance direction bf16(c - u) moves on the loaded checkpoint: what tells how large `pair_every` may be.  edits: a
+        list of keyword dicts as `calibrate_teacache` takes them.  Each edit runs with every step a "pair" whose store pass also measures
+        (`denoise(guidance_measure=max_age)`: eagerly, one read-back per edit after the last step; the latents are the plain loop's; no frames
+        are decoded).  Returns per edit {"timesteps", "rel_l2": [steps][max_age]} - rel_l2[i][a - 1] = ||d_i - d_(i-a)|| / ||d_i||, NaN
+        where no direction of that age and latent shape exists - plus, with keep_deltas, "deltas" (the per-step directions, on the CPU)
+        and always "latents" (the edit's final latents).  Guidance reuse itself is NOT switched on, and an enabled one is ignored here."""
+        import inspect
+        tensor_args = set(inspect.signature(self.edit_tensors).parameters)
+        embeds = {"prompt_embeds", "negative_prompt_embeds", "image_embeds"}
+        out = []
+        self._guidance_measure = (int(max_age), bool(keep_deltas))
+        try:
+            for kw in edits:
+                kw = dict(call_kwargs, **kw, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, output_type="latent")
+                self.transformer.guidance_measurement = None
+                res = (self.edit_tensors if embeds <= set(kw) <= tensor_args else self.__call__)(**kw)
+                if self.transformer.guidance_measurement is None:
+                    raise RuntimeError("measure_guidance_reuse: the edit was not measured (more than one sample per call, or no guidance)")
+                out.append(dict(self.transformer.guidance_measurement, latents=res if isinstance(res, torch.Tensor) else res.frames))
+        finally:
+            self._guidance_measure = None
+        return out
+
+    def _measure_kwargs(self) -> dict:
+        """What `denoise` gets on top while measure_guidance_reuse runs."""
+        if self._guidance_measure is None:
+            return {}
+        return {"guidance_measure": self._guidance_measure[0], "keep_deltas": self._guidance_measure[1]}
+
     def enable_lora(self):
         self.transformer.enable_lora()
         return self
@@ -973,7 +1177,7 @@ class ChronoEditPipeline:
                                     embeds["negative_prompt_embeds"] if self.do_classifier_free_guidance else None, image_embeds[b:b + 1],
                                     num_inference_steps, guidance_scale, enable_temporal_reasoning, num_temporal_reasoning_steps,
                                     use_graph=self.use_graph, on_step_end=on_step_end, interrupted=lambda: self._interrupt,
-                                    graph_warm=self._graph_warm))
+                                    graph_warm=self._graph_warm, **self._measure_kwargs()))
         latents = done[0] if B == 1 else torch.cat(done, dim=0)
         if offload_model and self.transformer is not None:
             self.transformer.cpu()
@@ -1012,7 +1216,7 @@ class ChronoEditPipeline:
         latents, condition = prepare_latents(self.vae, image, num_frames, latents, generator)
         latents = denoise(self.transformer, self.scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
                           num_inference_steps, guidance_scale, enable_temporal_reasoning, num_temporal_reasoning_steps,
-                          use_graph=self.use_graph, graph_warm=self._graph_warm)
+                          use_graph=self.use_graph, graph_warm=self._graph_warm, **self._measure_kwargs())
         if output_type == "latent":
             return latents
         return decode_latents(self.vae, latents, enable_temporal_reasoning, num_temporal_reasoning_steps)

@@ -10,7 +10,7 @@ truncation.
 MI355X-first design: all scalar work of the reference (`lambda/h/phi/rho`, fm_solvers_unipc.py:
 420-468,560-620 — host `.item()`-style math every step) is done ONCE in `set_timesteps`, in float64,
 into a [n_steps, 10] coefficient table resident on the device.  A step is then one fused HIP
-launch (`ce_cfg_unipc_step`) that also applies classifier-free guidance — no host<->device sync,
+launch (`ce_cfg_unipc_step`, or `ce_cfg_unipc_step_delta` in a loop with guidance reuse) that also applies classifier-free guidance — no host<->device sync,
 so the whole denoising step is hipGraph-capturable.  Latents and history are kept in fp32.
 """
 from __future__ import annotations
@@ -203,10 +203,23 @@ class FlowUniPCMultistepScheduler:
 
     # -- fused fast path -----------------------------------------------------------------
     def step_cfg(self, v_cond: torch.Tensor, v_uncond: Optional[torch.Tensor], guidance_scale: float, sample: torch.Tensor,
-                 coef: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 coef: Optional[torch.Tensor] = None, delta: Optional[torch.Tensor] = None, delta_mode: Optional[str] = None,
+                 delta_measure=None) -> torch.Tensor:
         """One loop tail (pipeline_chronoedit.py:736-739) as a single HIP launch.  `sample` must be fp32 and
         is updated IN PLACE and returned.  `coef`: explicit device coefficient row (hipGraph replay feeds the row of the
-        current step through one fixed buffer); default = this step's row of the table."""
+        current step through one fixed buffer); default = this step's row of the table.
+        delta / delta_mode (guidance reuse, chronoedit_amd/guidance.py; default: the plain launch): `delta` is a bf16 buffer of the
+        sample's size.  "store" (v_uncond given): the plain update, and delta <- bf16(v_cond - v_uncond).  "reuse" (v_uncond None): the
+        guided update with the stored direction standing for the unconditional sample.  "measure": "store" into slot `slot` of a ring
+        delta [A, *sample.shape] that also writes this step's distance sums, delta_measure = (slot, table, row) (ops.cfg_unipc_step_delta)."""
+        if delta_mode not in (None, "store", "reuse", "measure"):
+            raise ValueError(f"step_cfg: delta_mode {delta_mode!r} is none of 'store', 'reuse', 'measure'")
+        if delta_mode is not None and delta is None:
+            raise ValueError(f"step_cfg: delta_mode={delta_mode!r} needs the delta buffer")
+        if (delta_mode == "reuse") != (v_uncond is None) and delta_mode is not None:
+            raise ValueError("step_cfg: 'store' and 'measure' need v_uncond, 'reuse' takes none")
+        if (delta_mode == "measure") != (delta_measure is not None):
+            raise ValueError("step_cfg: delta_measure = (slot, table, row) goes with delta_mode='measure' and with nothing else")
         if self._step_index is None:
             self._step_index = 0
         i = self._step_index
@@ -219,9 +232,15 @@ class FlowUniPCMultistepScheduler:
             m1 = torch.zeros_like(m0)
         if coef is None:
             coef = self._coef_row(i, guidance_scale, sample.device)
-        ops.cfg_unipc_step(v_cond.to(torch.bfloat16).contiguous(), None if v_uncond is None else v_uncond.to(torch.bfloat16).contiguous(),
-                           sample, self.last_sample, m0, m1, coef, round_sigma_v=self.trajectory_dtype == torch.bfloat16,
-                           bf16_state=self.trajectory_dtype == torch.bfloat16)
+        bf16_traj = self.trajectory_dtype == torch.bfloat16
+        v_cond = v_cond.to(torch.bfloat16).contiguous()
+        v_uncond = None if v_uncond is None else v_uncond.to(torch.bfloat16).contiguous()
+        if delta_mode is None:
+            ops.cfg_unipc_step(v_cond, v_uncond, sample, self.last_sample, m0, m1, coef, round_sigma_v=bf16_traj, bf16_state=bf16_traj)
+        else:
+            slot, table, row = delta_measure if delta_measure is not None else (None, None, 0)
+            ops.cfg_unipc_step_delta(v_cond, v_uncond, sample, self.last_sample, m0, m1, coef, delta, round_sigma_v=bf16_traj,
+                                     bf16_state=bf16_traj, slot=slot, table=table, row=row)
         self._step_index = i + 1
         return sample
 

@@ -216,6 +216,9 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         self.shared_guidance = True  # run what the two samples of a guidance pair share once (enable_shared_guidance; needs _shared_inputs)
         self.text_compaction = True  # attend a text context's padding once, weighted (enable_text_compaction; needs the tensor's `_ce_compact`)
         self._shared_inputs = None  # per forward, set by the denoising loop: True = the two samples have the same latents, timestep and image context
+        self._guidance_reuse = None  # guidance reuse (chronoedit_amd.guidance): a GuidanceReuseConfig once enable_guidance_reuse() was called
+        self.guidance_report = None  # {"plan", "pair", "reuse", "off"} of the last guided edit that ran with guidance reuse; None otherwise
+        self.guidance_measurement = None  # {"timesteps", "rel_l2"[, "deltas"]} of the last edit measured with denoise(guidance_measure=)
 
     # -- reference-compatible helpers --------------------------------------------------
     @property
@@ -420,6 +423,19 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         if not coefficients:
             raise ValueError("enable_teacache: `coefficients` is empty")
         self._teacache = TeaCacheConfig(float(rel_l1_thresh), coefficients)
+        return self
+
+    def enable_guidance_reuse(self, pair_every: int = 2, interval=(0.0, 1.0)):
+        """Guidance reuse in `pipeline.denoise` (chronoedit_amd/guidance.py): inside `interval` of the schedule one step in `pair_every`
+        runs the guidance pair and stores the direction bf16(c - u); the others run the conditional sample alone and combine it with the
+        stored direction; outside the interval the conditional sample runs unguided.  An edit without guidance ignores it.  Not together
+        with TeaCache, not with the tokens sharded or with CFG parallelism."""
+        from .guidance import GuidanceReuseConfig
+        self._guidance_reuse = GuidanceReuseConfig(pair_every, tuple(interval))
+        return self
+
+    def disable_guidance_reuse(self):
+        self._guidance_reuse = None
         return self
 
     def disable_teacache(self):
@@ -718,9 +734,11 @@ class DiTEngine:
         self._rope = {}
         self._ws = {}
         self.ws_generation = 0  # bumped when a workspace is evicted (a shape seen before is then "new" again)
-        self._ctx_key = None
-        self._ctx = None
-        self._ctx_refs = None
+        # the context cache: one entry (key, ctx, keyed tensors) per FORM of the forward = its sample count - the stacked guidance pair and the
+        # single sample.  A loop with guidance reuse alternates between the two; with one entry every switch would recompute the projections,
+        # and a graph captured on a hit would replay over K tensors whose owner was dropped
+        self._ctx_cache = {}
+        self.ctx_projections = 0  # context projections computed (cache misses included) since clear_context_cache()
         self._tea_res = None      # TeaCache: the block stack's residual of the last computed step, bf16 [rows, D] (engine-owned)
         self._tea_valid = False   # ... and whether a computed step of THIS edit has written it
         self._tea_prev = None     # measuring only: the second residual buffer (the step before's residual; the two alternate)
@@ -909,14 +927,17 @@ class DiTEngine:
         key = None
         cmp = self._text_compact(text, image)
         if self.model.cache_context:
-            # The entry keeps the keyed tensors alive (self._ctx_refs): an address can then not be handed out again for another
+            # The entry keeps the keyed tensors alive (its third member): an address can then not be handed out again for another
             # edit's conditioning while the entry exists, so (data_ptr, _version, shape) identifies the CONTENT, not just a slot.
             key = (text.data_ptr(), text._version, tuple(text.shape), text.dtype,
                    None if image is None else (image.data_ptr(), image._version, tuple(image.shape), image.dtype), bool(share_image),
                    cmp is not None)
-            if key == self._ctx_key:
-                return self._ctx
+            hit = self._ctx_cache.get(text.shape[0])
+            if hit is not None and hit[0] == key:
+                return hit[1]
         keyed = (text, image)
+        form = text.shape[0]
+        self.ctx_projections += 1
         D = self.D
         if cmp is not None:  # rows [0, Lc) of every sample: its real rows, ONE padding row, then rows the kernel masks
             text = cmp.text
@@ -986,7 +1007,8 @@ class DiTEngine:
             # these engine-owned buffers are about to be rewritten in place, and a cached context of the same shape holds VIEWS into them
             # (its K tensors are its own): whatever was cached is stale from here on - drop it, so a later hit cannot pair the old K with
             # another conditioning's V^T (a call with cache_context off, key None, would otherwise leave the cached key standing)
-            self._ctx_key = self._ctx = self._ctx_refs = None
+            # (the other form's entry lives in buffers of another sample count: it stays)
+            self._ctx_cache.pop(form, None)
             w, b, eps_i = self.im_n2
             for bi in range(Bi):
                 ops.ln_affine(h_img[bi * Ti:(bi + 1) * Ti], w, b, eps_i, out=bufs.enc_i_pad[bi * c2: bi * c2 + Ti])
@@ -1023,12 +1045,21 @@ class DiTEngine:
         ctx = SimpleNamespace(kv=kv, Tt=Tt, Ti=Ti, vt=use_vt, c1=c1, c2=c2, f8=f8, img_shared=bool(share_image),
                               valid=None if cmp is None else cmp.valid, w=None if cmp is None else cmp.w)
         if key is not None:
-            self._ctx_key, self._ctx, self._ctx_refs = key, ctx, keyed
+            self._ctx_cache.pop(form, None)  # (re-inserted last: _ctx_key names the newest entry)
+            self._ctx_cache[form] = (key, ctx, keyed)
+            while len(self._ctx_cache) > 2:  # the pair and the single sample; a third sample count evicts the oldest
+                self._ctx_cache.pop(next(iter(self._ctx_cache)))
         return ctx
 
+    @property
+    def _ctx_key(self):
+        """The key of the newest cache entry, None when nothing is cached."""
+        return next(reversed(self._ctx_cache.values()))[0] if self._ctx_cache else None
+
     def clear_context_cache(self):
-        """Drop the cached conditioning-side results (called by the pipeline at the start of every edit)."""
-        self._ctx_key = self._ctx = self._ctx_refs = None
+        """Drop the cached conditioning-side results of every form (called by the pipeline at the start of every edit)."""
+        self._ctx_cache = {}
+        self.ctx_projections = 0
 
     # -- TeaCache (chronoedit_amd/teacache.py) ---------------------------------------------
     def tea_reserve(self, rows: int) -> torch.Tensor:

@@ -240,6 +240,21 @@ int ce_unpatchify_bf16(const void* y, void* out, int Cout, int T, int H, int W, 
 int ce_cfg_unipc_step(const void* v_cond, const void* v_uncond, float* x, float* x_last, float* m0, float* m1,
                       float* x0_out, const float* coef, const void* reserved, long long n, int flags, hipStream_t stream);
 
+/* ce_cfg_unipc_step for a loop that runs the unconditional sample only on planned steps (chronoedit_amd/guidance.py).  Everything
+ * ce_cfg_unipc_step takes, plus the guidance direction d = bf16(c - u), the intermediate the combine already forms, in `delta` (bf16):
+ *   store   (v_uncond given, ring == 0): the five outputs of ce_cfg_unipc_step bit for bit, and delta[i] = d.  delta: n elements.
+ *   reuse   (v_uncond null,  ring == 0): delta is only read: u' = bf16(c - d), v = bf16(u' + bf16(g * d)) - line :736 applied to
+ *           (c, u') with the stored d standing for bf16(c - u'); from v on as ce_cfg_unipc_step.
+ *   measure (v_uncond given, 1 <= ring <= 4): store mode into slot `slot` of a ring delta[ring][n] that first sums, over all elements,
+ *           (d - ring[(slot - a) mod ring])^2 for every age a = 1..ring (age `ring` is the slot's own old content) and d^2: fp32, per
+ *           workgroup into `scratch` (>= 5 floats per workgroup, at most 2048 workgroups: 40960 bytes always suffice), then by a
+ *           second launch into table[row * (ring + 1) + {0..ring-1: the ages, ring: d^2}].  Fixed summation order, no atomics: the
+ *           same bits on every run.  Which ages hold a direction at all is the caller's knowledge.
+ * scratch / table / slot / row are ignored when ring == 0.  Every scalar comes from coef or the arguments: capturable. */
+int ce_cfg_unipc_step_delta(const void* v_cond, const void* v_uncond, float* x, float* x_last, float* m0, float* m1, float* x0_out,
+                            const float* coef, void* delta, long long n, int flags, int ring, int slot, float* scratch,
+                            long long scratch_bytes, float* table, int row, hipStream_t stream);
+
 /* ---- Wan-2.1 VAE (chronoedit/_src/tokenizers/wan2pt1.py; call sites pipeline_chronoedit.py:442,776-781) ----------
  * Activation frames are channels-last with a 1-pixel zero border: [H+2][W+2][C] bf16. */
 
