@@ -738,7 +738,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_sp_kernel(const bf16* __restr
         const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
         mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
         const float shift = t == 0 ? mx : fmaxf(mx, 0.f);  // the offset only ever rises after the first tile
-        alpha = __builtin_amdgcn_exp2f(-shift);
+        // (first tile: nothing is accumulated yet and l = 0, so there is nothing to rescale - and exp2(-mx) is +inf when the whole tile lies
+        // more than 128 octaves below 0: 0 * inf made the row NaN)
+        alpha = t == 0 ? 1.0f : __builtin_amdgcn_exp2f(-shift);
         mc += shift;
 #pragma unroll
         for (int f = 0; f < 2; ++f)
@@ -1228,7 +1230,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
         mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
         const float shift = t == 0 ? mx : fmaxf(mx, 0.f);
-        alpha[sb] = __builtin_amdgcn_exp2f(-shift);
+        alpha[sb] = t == 0 ? 1.0f : __builtin_amdgcn_exp2f(-shift);  // (first tile: nothing to rescale, and exp2(-mx) may be +inf - see attn_fwd_sp_kernel)
         mc[sb] += shift;
 #pragma unroll
         for (int f = 0; f < 2; ++f)

@@ -148,7 +148,9 @@ int ce_attention_2seg_vt_strided_bf16(const void* Q, const void* K1, const void*
  * times in the softmax, so a run of m identical trailing keys (the zero-padded tail of a text context) is ONE key with w1 = log2 m.  The
  * kernel reads both arrays (nothing of them on the host): a captured launch follows their content.  valid1[b] = len1 and w1[b] = 0 give
  * ce_attention_2seg_vt_strided_bf16 bit for bit.  Strides, segment 2 and the shared forms as there; len1 / k1_rows / vt_cols1 describe the
- * operand as stored. */
+ * operand as stored.  A valid1[b] outside [1, len1] is not reported (the host never sees the array): the kernel clamps it into the range -
+ * 0 or a negative count behaves as 1, a count above len1 as len1 - and never reads a key past len1
+ * (pinned by tests/test_exact_cross_attention_gpu.py). */
 int ce_attention_2seg_vt_weighted_bf16(const void* Q, const void* K1, const void* V1t, int len1, int ldk1, int ldv1t, int vt_cols1,
                                        const void* K2, const void* V2t, int len2, int ldk2, int ldv2t, int vt_cols2, void* O, int Nq, int H,
                                        int head_dim, int ldq, int ldo, float softmax_scale, int batch, int q_rows, int k1_rows, int k2_rows,

@@ -142,14 +142,17 @@ def key_digits(j: torch.Tensor) -> torch.Tensor:
     return torch.stack([(j >> (3 * p)) & 7 for p in range(NEEDLE_DIGITS)], -1).double()
 
 
-def needle_k(n_keys: int, heads: int, sample: int = 0, invalid=None) -> torch.Tensor:
+def needle_k(n_keys: int, heads: int, sample=0, invalid=None, labels=None) -> torch.Tensor:
     """K rows [n_keys, heads*128] (fp64, exact in bf16) of one sample: key j has (d_p, d_p^2) on dims (2p, 2p+1) of every head,
-    +1 on the neighbour-bonus dim 100 + sample % 3, and +1 on dim 103 where `invalid` (bool [n_keys]) is set."""
-    d = key_digits(torch.arange(n_keys))
+    +1 on the neighbour-bonus dim 100 + sample % 3, and +1 on dim 103 where `invalid` (bool [n_keys]) is set.  `labels` (int64 [n_keys]):
+    row j carries the digits of labels[j] in place of j (another row order per sample: a neighbour's rows read instead of the sample's own
+    pick another row); sample=None: no neighbour bonus (an operand that every sample of a launch reads)."""
+    d = key_digits(torch.arange(n_keys) if labels is None else labels)
     kh = torch.zeros(n_keys, 128, dtype=torch.float64)
     kh[:, 0:2 * NEEDLE_DIGITS:2] = d
     kh[:, 1:2 * NEEDLE_DIGITS:2] = d * d
-    kh[:, LEAK_DIM + sample % 3] = 1.0
+    if sample is not None:
+        kh[:, LEAK_DIM + sample % 3] = 1.0
     if invalid is not None:
         kh[invalid, INVALID_DIM] = 1.0
     return kh.repeat(1, heads)
@@ -214,13 +217,16 @@ def poison_v(n: int, D: int, gen: torch.Generator, scale: float = 1.0) -> torch.
 POISON = 3.0e4  # value behind every key that must never be read (finite, exact in bf16)
 
 
-def needle_margins(q: torch.Tensor, k: torch.Tensor, heads: int, winners: torch.Tensor, forbidden=None):
+def needle_margins(q: torch.Tensor, k: torch.Tensor, heads: int, winners: torch.Tensor, forbidden=None, bias=None):
     """(lead, forbidden_lead): per query row and head, the winner's scaled score minus the best other ALLOWED key's, and the best
-    FORBIDDEN key's scaled score minus the winner's (+inf / -inf where there is none).  Both must be >= MIN_MARGIN_NATS."""
+    FORBIDDEN key's scaled score minus the winner's (+inf / -inf where there is none).  Both must be >= MIN_MARGIN_NATS.  `bias` (fp64
+    [n_k], nats): added to every row's scores - a key's softmax weight counted in."""
     allowed = torch.ones(k.shape[0], dtype=torch.bool) if forbidden is None else ~forbidden
     leads, fls = [], []
     for r0 in range(0, q.shape[0], 1024):  # (row chunks: the fp64 score block of 7200 x 14400 keys would not fit comfortably)
         s = needle_scores(q[r0:r0 + 1024], k, heads)                 # [H, rows, nk]
+        if bias is not None:
+            s = s + bias
         wi = winners[r0:r0 + 1024].t().unsqueeze(-1)                 # [H, rows, 1]
         sw = s.gather(-1, wi)
         other = s.masked_fill(~allowed, -math.inf).scatter(-1, wi, -math.inf)
@@ -230,6 +236,330 @@ def needle_margins(q: torch.Tensor, k: torch.Tensor, heads: int, winners: torch.
     if forbidden is None or not forbidden.any():
         fl = torch.full_like(lead, math.inf)
     return lead, fl
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# cross-attention: two key segments on one query row, operands shared between the samples, segment 1 cut per sample and its last
+# readable key weighted (ce_attention_2seg_vt_bf16 / _strided_bf16 / _weighted_bf16 / _quant_bf16)
+#
+# Needle rows: as above, per segment.  Every sample's keys sit in another row order (`needle_k(labels=)`): the neighbour's rows read in
+# place of the sample's own pick another row.  A weight of a few octaves on a key cannot overturn a 65-octave lead: a needle row pins
+# masking, the per-sample cut, strides and positions, never the weight.
+# Flat rows pin the weight: the query is zero on segment 1's digit dims, every readable key of segment 1 scores exactly 0, the last one
+# counts m = 2^w times, and valid - 1 + m = 2^k: the softmax is 1 / 2^k per plain key and m / 2^k for the last, exactly.  V1 is sparse - column
+# c is zero except at ONE key i(c), where it holds +-r 2^(k-3), r in 1..7 - so the segment's output in column c is +-r mult / 8 (mult = m for
+# the weighted key, else 1): three significant bits, and one fp32 ulp of relative error in exp2, the row sum or 1 / l cannot move the
+# rounding to bf16.  Segment 2 of a flat row is a needle with an integer V2 row, scaled so that the final bf16 add is exact.
+# ------------------------------------------------------------------------------------------------------------------------------------
+SEG2_DIM0 = 12  # segment 2's digits sit on dims 12..21 of the one query row and its invalid flag on INVALID_DIM + 1
+LOG2E = 1.4426950408889634
+
+
+def pad64(n: int) -> int:
+    return (n + 63) // 64 * 64
+
+
+def vt_stride(n: int) -> int:
+    """The engine's V^T column stride between samples: the key count rounded up to 8 (16-byte rows), no multiple of the 64-key tile."""
+    return (n + 7) // 8 * 8
+
+
+def seg2_keys(k: torch.Tensor, heads: int) -> torch.Tensor:
+    """Needle keys moved to segment 2's dims: digits 0..9 -> 12..21, the invalid flag -> INVALID_DIM + 1, the neighbour bonus stays."""
+    kh = k.reshape(-1, heads, 128)
+    out = torch.zeros_like(kh)
+    out[:, :, SEG2_DIM0:SEG2_DIM0 + 2 * NEEDLE_DIGITS] = kh[:, :, 0:2 * NEEDLE_DIGITS]
+    out[:, :, LEAK_DIM:LEAK_DIM + 3] = kh[:, :, LEAK_DIM:LEAK_DIM + 3]
+    out[:, :, INVALID_DIM + 1] = kh[:, :, INVALID_DIM]
+    return out.reshape(-1, heads * 128)
+
+
+def two_segment_q(q1: torch.Tensor, q2: torch.Tensor, heads: int) -> torch.Tensor:
+    """One query row for both segments: q1 (segment 1's needle query, with the neighbour-bonus dims) plus q2's digits on dims 12..21 and the
+    invalid weight on INVALID_DIM + 1 as well."""
+    q = q1.clone().reshape(-1, heads, 128)
+    q[:, :, SEG2_DIM0:SEG2_DIM0 + 2 * NEEDLE_DIGITS] = q2.reshape(-1, heads, 128)[:, :, 0:2 * NEEDLE_DIGITS]
+    q[:, :, INVALID_DIM + 1] = q[:, :, INVALID_DIM]
+    return q.reshape(-1, heads * 128)
+
+
+def needle_v(n: int, D: int, gen: torch.Generator, positive: bool = False) -> torch.Tensor:
+    """V rows with |v| in [1, 2): no value near zero (a 1e-20 weight times a neighbour must stay below half an ulp)."""
+    mag = 1.0 + torch.rand(n, D, generator=gen)
+    sign = torch.where(torch.rand(n, D, generator=gen) < 0.5, -1.0, 1.0)
+    return (mag if positive else mag * sign).to(BF)
+
+
+def needle_segment(n_q: int, n_rows: int, valid, heads: int, batch: int, gen: torch.Generator, share_q: bool = False, share_k: bool = False):
+    """One key segment of `batch` samples: (qs, ks, wins).  ks: fp64 [n_rows, heads*128] per sample (one if share_k), rows >= valid[s] flagged
+    invalid, rows < valid[s] in a random order of their own (label l sits in row order[l]; the rows `edge_keys(valid)`, valid - 1 and valid - 2
+    carry the lowest labels).  qs: needle queries [n_q, heads*128] per sample (one if share_q; then the labels stay below min(valid) and the
+    query carries no neighbour bonus); the lowest labels are forced onto the first and last rows.  wins: int64 [batch, n_q, heads], the winning
+    ROW of sample b's keys."""
+    assert len(valid) == batch and (not share_k or len(set(valid)) == 1) and max(valid) <= n_rows and min(valid) >= 1
+    orders, ks = [], []
+    for s in range(1 if share_k else batch):
+        v = int(valid[s])
+        first = [r for r in dict.fromkeys([v - 1, v - 2, 0] + edge_keys(v)) if 0 <= r < v]
+        rest = torch.tensor(sorted(set(range(v)) - set(first)), dtype=torch.int64)
+        order = torch.cat([torch.tensor(first, dtype=torch.int64), rest[torch.randperm(len(rest), generator=gen)]])
+        label = torch.arange(n_rows)
+        label[order] = torch.arange(v)
+        orders.append(order)
+        ks.append(needle_k(n_rows, heads, sample=None if share_k else s, invalid=torch.arange(n_rows) >= v, labels=label))
+    labs = [winners_for(n_q, min(valid) if share_q else int(valid[b]), heads, gen, must=range(72)) for b in range(1 if share_q else batch)]
+    qs = [needle_q(lab, sample=b, batch=1 if share_q else batch) for b, lab in enumerate(labs)]
+    wins = torch.stack([orders[0 if share_k else b][labs[0 if share_q else b]] for b in range(batch)])
+    return qs, ks, wins
+
+
+def flat_wcols(D: int) -> torch.Tensor:
+    """bool [D]: the columns whose one nonzero V1 entry sits at the weighted key (a quarter of them, another phase in every head)."""
+    c = torch.arange(D)
+    return (c + c // 128) % 4 == 0
+
+
+def flat_v1(n_rows: int, valid: int, m: int, D: int, gen: torch.Generator):
+    """(v1 fp64 [n_rows, D], out1 fp64 [D], key int64 [D]) for valid - 1 plain keys and the last one counted m times, valid - 1 + m = 2^k:
+    column c is zero except at key[c] (valid - 1 on `flat_wcols`; elsewhere cycling through edge_keys(valid) and valid - 2; -1: an all-zero
+    column, when the weighted key is the only one), where it holds +-r 2^(k-3); rows >= valid hold POISON.  out1: the segment's exact output
+    of a flat row, +-r mult / 8."""
+    k = int(math.log2(valid - 1 + m))
+    assert 2 ** k == valid - 1 + m and m & (m - 1) == 0 and k >= 3
+    wcol = flat_wcols(D)
+    others = sorted(x for x in (set(edge_keys(valid)) | {valid - 2}) if 0 <= x < valid - 1)
+    key = torch.full((D,), -1, dtype=torch.int64)
+    key[wcol] = valid - 1
+    if others:
+        idx = (~wcol).nonzero()[:, 0]
+        key[idx] = torch.tensor(others)[(torch.arange(len(idx)) + int(torch.randint(0, len(others), (1,), generator=gen))) % len(others)]
+    r = torch.randint(1, 8, (D,), generator=gen).double() * (torch.randint(0, 2, (D,), generator=gen).double() * 2 - 1)
+    v1 = torch.zeros(n_rows, D, dtype=torch.float64)
+    has = key >= 0
+    v1[key[has], has.nonzero()[:, 0]] = r[has] * 2.0 ** (k - 3)
+    v1[valid:] = POISON
+    out1 = torch.where(has, r * torch.where(wcol, float(m), 1.0) / 8, torch.zeros(()).double())
+    return v1, out1, key
+
+
+def flat_v2(n_rows: int, m: int, D: int, gen: torch.Generator) -> torch.Tensor:
+    """fp64 [n_rows, D]: integers 1..15, times m on `flat_wcols`: added to +-r mult / 8 the sum keeps at most seven significant bits."""
+    n = torch.randint(1, 16, (n_rows, D), generator=gen).double()
+    return n * torch.where(flat_wcols(D), float(m), 1.0)
+
+
+def _gather_rows(v: torch.Tensor, win: torch.Tensor, heads: int) -> torch.Tensor:
+    """out[i, h*128:(h+1)*128] = v[win[i, h], h*128:(h+1)*128]."""
+    out = torch.empty(win.shape[0], heads * 128, dtype=v.dtype)
+    for h in range(heads):
+        out[:, h * 128:(h + 1) * 128] = v[win[:, h], h * 128:(h + 1) * 128]
+    return out
+
+
+def _pack_k(ks, extra: int, heads: int, seg2: bool) -> torch.Tensor:
+    tail = needle_k(extra, heads, sample=None, invalid=torch.ones(extra, dtype=torch.bool))
+    k = torch.cat(list(ks) + [tail])
+    return (seg2_keys(k, heads) if seg2 else k).to(BF)
+
+
+def _pack_vt(vs, n: int, cols: int, extra_cols: int) -> torch.Tensor:
+    """V^T [D, (samples - 1) cols + 64 ceil(n / 64) + extra_cols]: sample s at columns [s cols, s cols + n), POISON everywhere else."""
+    vt = torch.full((vs[0].shape[1], (len(vs) - 1) * cols + pad64(n) + extra_cols), POISON, dtype=BF)
+    for s, v in enumerate(vs):
+        vt[:, s * cols:s * cols + n] = v.to(BF).t()
+    return vt
+
+
+class CrossCase:
+    """The operands of one launch (CPU, bf16) and its expected output."""
+
+
+def cross_case(n_q: int, len1: int, len2: int, heads: int, batch: int, seed: int, share_q: bool = False, share1: bool = False,
+               share2: bool = False, valid=None, w=None, m=None, n_flat: int = 0, extra: int = 64, extra_cols: int = 0, extra_q: int = 0):
+    """Needle (and flat) operands of one two-segment launch.  valid (per sample): segment 1 is cut there, rows valid[b] .. len1 - 1 win if read
+    and their V is POISON; w (per sample): the log2-weight of key valid[b] - 1, or m (per sample, powers of two with valid - 1 + m = 2^k):
+    w = log2 m, V1 / V2 the flat recipe's, and the last n_flat query rows of every sample flat.  Buffers: q [(1 | B) n_q + extra_q, D];
+    k [(1 | B) len + extra, D] (the extra rows win if read); v^T at the column stride `vt_stride(len)`, POISON behind each sample's keys and in
+    `extra_cols` more columns; want [B n_q, D] = bf16(bf16(V1[winner 1]) + bf16(V2[winner 2])), flat rows bf16(+-r mult / 8 + V2[winner 2])."""
+    g = torch.Generator().manual_seed(seed)
+    c = CrossCase()
+    D = heads * 128
+    c.n_q, c.len1, c.len2, c.H, c.B, c.n_flat = n_q, len1, len2, heads, batch, n_flat
+    c.share_q, c.share1, c.share2 = share_q, share1, share2
+    c.valid = [int(v) for v in valid] if valid is not None else None
+    assert not (share1 and valid is not None) and (m is None or valid is not None) and (n_flat == 0 or m is not None)
+    if m is not None:
+        assert not share2 or len(set(m)) == 1  # (one V2 for all samples cannot follow a scale per sample)
+        w = [math.log2(x) for x in m]
+    c.w = [float(x) for x in w] if w is not None else None
+    v1 = c.valid if c.valid is not None else [len1] * batch
+    q1s, k1s, c.win1 = needle_segment(n_q, len1, v1, heads, batch, g, share_q, share1)
+    q2s, k2s, c.win2 = needle_segment(n_q, len2, [len2] * batch, heads, batch, g, share_q, share2)
+    qs = []
+    for q1, q2 in zip(q1s, q2s):
+        q = two_segment_q(q1, q2, heads).view(n_q, heads, 128)
+        q[n_q - n_flat:, :, 0:2 * NEEDLE_DIGITS] = 0  # flat rows: nothing on segment 1's digit dims
+        qs.append(q.view(n_q, D))
+    q = torch.cat(qs)
+    behind = q.roll(q.shape[0] // 2 + 1, 0)  # (other queries behind the last sample's: every row another one)
+    c.q = torch.cat([q] + [behind] * ((extra_q + q.shape[0] - 1) // q.shape[0]))[:q.shape[0] + extra_q].to(BF)
+    v1s, v2s, out1 = [], [], []
+    for s in range(1 if share1 else batch):
+        if m is None:
+            v = needle_v(len1, D, g, positive=True).double()
+            v[v1[s]:] = POISON
+        else:
+            v, o, _ = flat_v1(len1, v1[s], int(m[s]), D, g)
+            out1.append(o)
+        v1s.append(v)
+    for s in range(1 if share2 else batch):
+        v2s.append(needle_v(len2, D, g, positive=True).double() if m is None else flat_v2(len2, int(m[s]), D, g))
+    c.c1, c.c2 = vt_stride(len1), vt_stride(len2)
+    c.k1, c.k2 = _pack_k(k1s, extra, heads, False), _pack_k(k2s, extra, heads, True)
+    c.v1t, c.v2t = _pack_vt(v1s, len1, c.c1, extra_cols), _pack_vt(v2s, len2, c.c2, extra_cols)
+    want = torch.empty(batch, n_q, D, dtype=BF)
+    c.flat_exact = True
+    for b in range(batch):
+        o1 = _gather_rows(v1s[0 if share1 else b], c.win1[b], heads)
+        o2 = _gather_rows(v2s[0 if share2 else b], c.win2[b], heads)
+        if n_flat:
+            o1[n_q - n_flat:] = out1[b]
+        want[b] = (o1.to(BF).float() + o2.to(BF).float()).to(BF)
+        c.flat_exact = c.flat_exact and torch.equal(want[b, n_q - n_flat:].double(), (o1 + o2)[n_q - n_flat:])
+    c.want = want.view(batch * n_q, D)
+    return c
+
+
+def cross_margins(c: CrossCase):
+    """(lead, forbidden lead, flat forbidden lead), the minimum over both segments, all samples, needle rows and heads, in nats, the weight
+    counted in; flat rows: every readable key of segment 1 scores exactly 0 (asserted) and the third figure is the worst forbidden key's lead
+    over the weighted key.  Forbidden: every row of the buffer but the sample's own readable ones - except the readable rows of the samples
+    that the neighbour bonus cannot tell from this one (under a shared query all others, else the samples b +- 3, b +- 6, ...): they carry
+    the same labels, and there the row order and V, not the score, tell the samples apart."""
+    lead_min, forb_min, flat_min = math.inf, math.inf, math.inf
+    nn = c.n_q - c.n_flat
+    for seg in (1, 2):
+        k, ln, shared = (c.k1, c.len1, c.share1) if seg == 1 else (c.k2, c.len2, c.share2)
+        win = c.win1 if seg == 1 else c.win2
+        for b in range(c.B):
+            base = 0 if shared else b * ln
+            nv = c.valid[b] if (seg == 1 and c.valid is not None) else ln
+            keep = torch.ones(k.shape[0], dtype=torch.bool)
+            if not shared:
+                for o in range(c.B):
+                    if o != b and (c.share_q or (o - b) % 3 == 0):
+                        keep[o * ln:o * ln + (c.valid[o] if (seg == 1 and c.valid is not None) else ln)] = False
+            sel = keep.nonzero()[:, 0]
+            pos = torch.full((k.shape[0],), -1, dtype=torch.int64)
+            pos[sel] = torch.arange(len(sel))
+            forb = torch.ones(k.shape[0], dtype=torch.bool)
+            forb[base:base + nv] = False
+            bias = torch.zeros(k.shape[0], dtype=torch.float64)
+            if seg == 1 and c.w is not None:
+                bias[base + nv - 1] = c.w[b] * math.log(2.0)
+            qb = c.q[(0 if c.share_q else b) * c.n_q:][:c.n_q]
+            if nn:
+                lead, fl = needle_margins(qb[:nn], k[sel], c.H, pos[win[b][:nn] + base], forb[sel], bias[sel])
+                lead_min, forb_min = min(lead_min, lead.min().item()), min(forb_min, fl.min().item())
+            if c.n_flat:
+                s = needle_scores(qb[nn:], k[sel], c.H)
+                if seg == 1:
+                    assert not s[:, :, ~forb[sel]].any(), "flat rows: a readable key of segment 1 does not score exactly 0"
+                    if forb[sel].any():
+                        flat_min = min(flat_min, (s[:, :, forb[sel]].amin() - bias.max()).item())
+                else:
+                    lead, fl = needle_margins(qb[nn:], k[sel], c.H, pos[win[b][nn:] + base], forb[sel])
+                    lead_min, forb_min = min(lead_min, lead.min().item()), min(forb_min, fl.min().item())
+    return lead_min, forb_min, flat_min
+
+
+# ten (valid, m) pairs with valid <= 200, all different: the launches with more items than workgroups take one per sample
+MANY_PAIRS = [(193, 64), (1, 64), (64, 1), (65, 64), (127, 2), (9, 8), (97, 32), (17, 16), (121, 8), (33, 32)]
+
+
+def n_flat_rows(n_q: int) -> int:
+    """Flat rows at the end of a sample: from the middle of the partial last query block on (it then holds needle rows and flat rows)."""
+    return n_q - (n_q // 256 * 256 + (n_q % 256) // 2)
+
+
+def roomy_cross_case(n_q: int, len1: int, len2: int, heads: int, batch: int, seed: int, **kw):
+    """`cross_case` in roomy buffers - what the GPU tests launch: a wrong sample stride (a stride where an operand is shared, 64 ceil(len / 64)
+    for a V^T column stride) still lands in rows and columns the test owns (winner-if-read keys, POISON, other queries) and gives a wrong
+    answer, not a stray read."""
+    shared_k = kw.get("share1") or kw.get("share2")
+    return cross_case(n_q, len1, len2, heads, batch, seed, extra=64 + ((batch - 1) * max(len1, len2) if shared_k else 0),
+                      extra_cols=(batch - 1) * pad64(max(len1, len2)), extra_q=(batch - 1) * n_q if kw.get("share_q") else 0, **kw)
+
+
+def far_first_tile(n_q: int, n_k: int, heads: int, gen: torch.Generator):
+    """(q, k, v, rows): needle operands (bf16) of ONE sample whose first 64-key tile lies far below every row's winner: rows 0..63 carry the
+    labels 4032 + i (digits (i % 8, i // 8, 7, 7, 0)), rows 64.. the labels 0, 1, ..., and the winners are labels whose two digits are <= 5 -
+    every tile-0 key trails the winner by >= 48 digit units, thousands of octaves, so the first tile's row maximum is far below -128 in the
+    log2 domain and exp2(-maximum) overflows.  An online softmax that rescales by that factor at the first tile (where there is nothing to
+    rescale) turns 0 * inf into a NaN row.  rows: int64 [n_q, heads], the winning key row."""
+    assert n_k >= 64 + 46
+    labels = torch.cat([4032 + torch.arange(64), torch.arange(n_k - 64)])
+    ok = torch.tensor([l for l in range(min(n_k - 64, 64)) if l % 8 <= 5 and l // 8 <= 5])
+    lab = ok[torch.randint(0, len(ok), (n_q, heads), generator=gen)]
+    q = needle_q(lab).to(BF)
+    k = needle_k(n_k, heads, labels=labels).to(BF)
+    return q, k, needle_v(n_k, heads * 128, gen), lab + 64
+
+
+CROSS_MISTAKES = ("weight ignored", "weight on key valid-2", "valid[0] for all samples", "w[0] for all samples", "tail mask at valid+1",
+                  "tail mask at len1", "neighbour's K1 rows", "shared operand at stride len", "V^T column stride 64 ceil(len/64)")
+
+
+def cross_attention_f64(c: CrossCase, mistake=None) -> torch.Tensor:
+    """The two-segment attention of the entry points' contract on the PACKED buffers of `c`, plain fp64 (softmax in the log2 domain: an integer
+    weight is an exact factor), with the kernel's three roundings at the end: bf16(bf16(o1) + bf16(o2)).  `mistake` (one of CROSS_MISTAKES):
+    the same with one deliberately wrong index."""
+    assert mistake is None or mistake in CROSS_MISTAKES
+    H, B, nq, D = c.H, c.B, c.n_q, c.H * 128
+    valid = list(c.valid) if c.valid is not None else [c.len1] * B
+    w = list(c.w) if c.w is not None else [0.0] * B
+    q_rows, k1_rows, k2_rows = (0 if c.share_q else nq), (0 if c.share1 else c.len1), (0 if c.share2 else c.len2)
+    c1, c2 = (0 if c.share1 else c.c1), (0 if c.share2 else c.c2)
+    wpos = [v - 1 for v in valid]
+    k1_of = list(range(B))
+    if mistake == "weight ignored":
+        w = [0.0] * B
+    elif mistake == "weight on key valid-2":
+        wpos = [v - 2 for v in valid]
+    elif mistake == "valid[0] for all samples":
+        valid = [valid[0]] * B
+        wpos = [v - 1 for v in valid]
+    elif mistake == "w[0] for all samples":
+        w = [w[0]] * B
+    elif mistake == "tail mask at valid+1":
+        valid = [v + 1 for v in valid]
+    elif mistake == "tail mask at len1":
+        valid = [c.len1] * B
+    elif mistake == "neighbour's K1 rows":
+        k1_of = [(b + 1) % B for b in range(B)]
+    elif mistake == "shared operand at stride len":
+        q_rows, k1_rows, k2_rows, c1, c2 = nq, c.len1, c.len2, c.c1, c.c2
+    elif mistake == "V^T column stride 64 ceil(len/64)":
+        c1, c2 = (0 if c.share1 else pad64(c.len1)), (0 if c.share2 else pad64(c.len2))
+
+    def seg(qh, k, vt, n, wp, wt):
+        kh = k.double().view(n, H, 128).transpose(0, 1)
+        s = qh @ kh.transpose(1, 2) * (LOG2E / math.sqrt(128.0))
+        if wt != 0.0 and 0 <= wp < n:
+            s[:, :, wp] += wt
+        p = torch.exp2(s - s.amax(-1, keepdim=True))
+        p = p / p.sum(-1, keepdim=True)
+        o = p @ vt.double().view(H, 128, n).transpose(1, 2)
+        return o.transpose(0, 1).reshape(-1, D)
+
+    out = torch.empty(B * nq, D, dtype=BF)
+    for b in range(B):
+        qh = c.q[b * q_rows:b * q_rows + nq].double().view(nq, H, 128).transpose(0, 1)
+        n1 = valid[b]
+        o1 = seg(qh, c.k1[k1_of[b] * k1_rows:][:n1], c.v1t[:, b * c1:b * c1 + n1], n1, wpos[b], w[b])
+        o2 = seg(qh, c.k2[b * k2_rows:][:c.len2], c.v2t[:, b * c2:b * c2 + c.len2], c.len2, -1, 0.0)
+        out[b * nq:(b + 1) * nq] = (o1.float().to(BF).float() + o2.float().to(BF).float()).to(BF)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------

@@ -8,8 +8,8 @@ worst-block checks at the end cover that route on smooth random data, per (sampl
 import pytest
 import torch
 
-from exact_util import (BF, INVALID_DIM, MIN_MARGIN_NATS, POISON, assert_exact, edge_keys, needle_k, needle_margins, needle_q,
-                        winners_for)
+from exact_util import (BF, MIN_MARGIN_NATS, POISON, assert_exact, edge_keys, far_first_tile, needle_k, needle_margins, needle_q, needle_v, seg2_keys,
+                        two_segment_q, winners_for)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,13 +30,6 @@ def vt_body(request):
     ops.set_attention_waves(old)
 
 
-def _v_rows(n, D, g):
-    """V rows with |v| in [1, 2), random signs: no value near zero (a 1e-20 weight times a neighbour must stay below half an ulp)."""
-    mag = 1.0 + torch.rand(n, D, generator=g)
-    sign = torch.where(torch.rand(n, D, generator=g) < 0.5, -1.0, 1.0)
-    return (mag * sign).to(BF)
-
-
 def _stacked(B, n_q, n_k, H, seed, extra_keys=0, positive=False):
     """Needle operands of B stacked samples (CPU): q [B n_q, D], k / v [B n_k + extra_keys, D] (the extra rows: winner-if-read keys
     past the last sample, V = POISON), winners [B, n_q, H]."""
@@ -47,7 +40,7 @@ def _stacked(B, n_q, n_k, H, seed, extra_keys=0, positive=False):
         win = winners_for(n_q, n_k, H, g, must=edge_keys(n_k))
         qs.append(needle_q(win, sample=b, batch=B))
         ks.append(needle_k(n_k, H, sample=b))
-        v = _v_rows(n_k, D, g)
+        v = needle_v(n_k, D, g)
         vs.append(v.abs() if positive else v)
         ws.append(win)
     if extra_keys:
@@ -95,16 +88,8 @@ def test_attention_two_segment_needles(n_q, L1, L2, H, B, attn_waves):
     q1, k1, v1, w1 = _stacked(B, n_q, L1, H, seed=n_q + L1, extra_keys=64, positive=True)
     q2, k2, v2, w2 = _stacked(B, n_q, L2, H, seed=n_q + L2 + 1, extra_keys=64, positive=True)
     # one query row serves both segments: the digit dims of segment 2 move to dims 12..21 (12 + 2p, 13 + 2p), invalid to 104
-    q = q1.float().view(B * n_q, H, 128)
-    k2h = k2.float().view(-1, H, 128)
-    k2s = torch.zeros_like(k2h)
-    k2s[:, :, 12:22] = k2h[:, :, 0:10]
-    k2s[:, :, 100:103] = k2h[:, :, 100:103]
-    k2s[:, :, INVALID_DIM + 1] = k2h[:, :, INVALID_DIM]
-    q[:, :, 12:22] = q2.float().view(B * n_q, H, 128)[:, :, 0:10]
-    q[:, :, INVALID_DIM + 1] = q[:, :, INVALID_DIM]
-    q = q.reshape(B * n_q, H * 128).to(BF)
-    k2 = k2s.reshape(-1, H * 128).to(BF)
+    q = two_segment_q(q1.float(), q2.float(), H).to(BF)
+    k2 = seg2_keys(k2.float(), H).to(BF)
     want = (_expected(v1, w1, L1, H).float() + _expected(v2, w2, L2, H).float()).to(BF)
     out = ops.attention(q.cuda(), k1[:B * L1].cuda(), v1[:B * L1].cuda(), H, k2=k2[:B * L2].cuda(), v2=v2[:B * L2].cuda(), batch=B)
     assert_exact(out, want, f"attention 2-segment needles {n_q}x({L1}+{L2}) H={H} B={B}")
@@ -119,7 +104,10 @@ def test_attention_two_segment_needles(n_q, L1, L2, H, B, attn_waves):
         assert_exact(out, want, f"attention_2seg_vt needles {n_q}x({L1}+{L2}) H={H} B={B}")
 
 
-VT_SHAPES = [(7200, 7200, 2, 2), (333, 258, 3, 3), (1090, 1090, 8, 2), (290, 64, 5, 3), (31, 704, 4, 2), (2000, 200, 16, 3)]
+# the last one: 5 x 24 x 5 = 600 (sample, head, query block) items, more than the launcher's 2 x #CUs workgroups - every workgroup of the
+# persistent forms walks several items and derives sample, head and block again for each
+MANY_ITEMS_VT = (1100, 130, 24, 5)
+VT_SHAPES = [(7200, 7200, 2, 2), (333, 258, 3, 3), (1090, 1090, 8, 2), (290, 64, 5, 3), (31, 704, 4, 2), (2000, 200, 16, 3), MANY_ITEMS_VT]
 
 
 @pytest.mark.parametrize("n_q,n_k,H,B", VT_SHAPES)
@@ -128,12 +116,39 @@ def test_attention_vt_needles(n_q, n_k, H, B, vt_body):
     end or past the buffer wins and brings a 0 or a neighbour's row)."""
     from chronoedit_amd import ops
     q, k, v, win = _stacked(B, n_q, n_k, H, seed=n_q * 3 + n_k + B, extra_keys=128)
+    if (n_q, n_k, H, B) == MANY_ITEMS_VT:  # fails loudly, not vacuously, on a device with more compute units
+        assert (n_q + 255) // 256 * H * B > 2 * torch.cuda.get_device_properties(0).multi_processor_count
     L = B * n_k
     kd = k.cuda()
     vt = ops.v_transpose(v[:L].cuda(), H)
     assert not vt[:, L:].any()
     out = ops.attention_vt(q.cuda(), kd[:L], vt, H, batch=B)
     assert_exact(out, _expected(v, win, n_k, H), f"attention_vt needles {n_q}x{n_k} H={H} B={B}")
+
+
+def _far_case(H):
+    g = torch.Generator().manual_seed(77 + H)
+    q, k, v, rows = far_first_tile(70, 130, H, g)
+    lead, _ = needle_margins(q, k, H, rows)
+    assert lead.min() >= MIN_MARGIN_NATS
+    return q, k, v, _expected(v, rows[None], 130, H)
+
+
+def test_attention_first_tile_far_below_the_winner(attn_waves):
+    """Every key of the first tile lies thousands of octaves below the row's winner, which sits in tile 1 or 2: exp2(-first tile's maximum) is
+    +inf.  The first tile has nothing to rescale; a body that multiplies l = 0 and O = 0 by that factor returns NaN rows (the
+    software-pipelined body did, before alpha = 1 at t == 0)."""
+    from chronoedit_amd import ops
+    q, k, v, want = _far_case(3)
+    assert_exact(ops.attention(q.cuda(), k.cuda(), v.cuda(), 3), want, "attention, first tile far below the winner")
+
+
+def test_attention_vt_first_tile_far_below_the_winner(vt_body):
+    """The same through the V^T bodies: attn_fwd_sp_kernel<.., VT> and both one-wave-per-SIMD forms."""
+    from chronoedit_amd import ops
+    q, k, v, want = _far_case(3)
+    out = ops.attention_vt(q.cuda(), k.cuda(), ops.v_transpose(v.cuda(), 3), 3)
+    assert_exact(out, want, "attention_vt, first tile far below the winner")
 
 
 @pytest.mark.parametrize("N,n,W,H,B", [(300, 128, 3, 2, 3), (7100, 3584, 2, 2, 2), (500, 64, 8, 5, 3), (1000, 256, 4, 8, 2)])
@@ -150,7 +165,7 @@ def test_attention_vt_blocked_needles(N, n, W, H, B, vt_body):
         invalid = torch.arange(T) >= N
         plain[b, :, :D] = needle_q(win, sample=b, batch=B).to(BF)
         plain[b, :, D:2 * D] = needle_k(T, H, sample=b, invalid=invalid).to(BF)
-        plain[b, :, 2 * D:] = _v_rows(T, D, g)
+        plain[b, :, 2 * D:] = needle_v(T, D, g)
         plain[b, N:, 2 * D:] = POISON
         lead, fl = needle_margins(plain[b, :, :D], plain[b, :, D:2 * D], H, win, invalid)
         assert lead.min() >= MIN_MARGIN_NATS and fl.min() >= MIN_MARGIN_NATS
@@ -183,7 +198,7 @@ def test_attention_1head_needles(N, C, split):
     # (scale C^-1/2: at C = 384 the runner-up trails by 512 / sqrt(384) = 26 nats)
     lead, fl = needle_margins(q[:, :128], k[:, :128], 1, win, torch.arange(N + extra) >= N)
     assert (lead * (128 / C) ** 0.5).min() >= MIN_MARGIN_NATS and (fl * (128 / C) ** 0.5).min() >= MIN_MARGIN_NATS
-    v = _v_rows(N, C, g)
+    v = needle_v(N, C, g)
     cols = (N + 63) // 64 * 64
     vt = torch.full((C, cols + 64), POISON, dtype=BF)
     vt[:, :cols] = 0

@@ -6,6 +6,8 @@ changed element wherever it sits.
 The row / scheduler / softmax recipes (`unit_rows`, `rope_table`, `unipc_state`, `tie_targets`, ...): fp32 evaluation in a scrambled order
 equals the fp64 answer bit for bit (exactness), the asserted share of results needs a real bf16 rounding, and the reference evaluated with
 one deliberately wrong index differs from the right one in every affected row (sensitivity: the data can see that bug)."""
+import math
+
 import pytest
 import torch
 
@@ -256,3 +258,139 @@ def test_softmax_tie_recipe_is_exact_and_sees_a_wrong_head_or_an_ignored_mask(Lq
     assert _each_row_differs(want, wrong, rows=(valid < Lk).nonzero()[:, 0])
     wrong = X.tie_probs(target.double(), valid - 1, check=False)
     assert _each_row_differs(want, wrong)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# cross-attention: two segments, shared operands, a cut per sample and a weighted last key
+# ------------------------------------------------------------------------------------------------------------------------------------
+_n_flat = X.n_flat_rows
+
+
+def _rows_differ(a, b, B):
+    """[B, n_q] bool: the rows where two [B n_q, D] tensors differ."""
+    return (a != b).any(1).view(B, -1)
+
+
+def _proved(c, samples=None):
+    """The recipe's expectation is the plain fp64 attention of the packed buffers, rounded where the kernels round; margins; exact flat rows."""
+    lead, forb, flat = X.cross_margins(c)
+    assert min(lead, forb, flat) >= MIN_MARGIN_NATS, (lead, forb, flat)
+    assert c.flat_exact
+    assert_exact(X.cross_attention_f64(c), c.want, "fp64 reference against the recipe's expectation")
+    return c
+
+
+# (len1, valid per sample, m per sample): every (valid, m) pair of the flat recipe
+FLAT_SETS = [(64, (1, 33, 57), (64, 32, 8)), (72, (63, 64, 65), (2, 1, 64)), (200, (97, 127, 193), (32, 2, 64)),
+             (2056, (257, 449, 2049), (256, 64, 2048))]
+CUT_SETS = [(72, (1, 63, 64), (9.0, 5.5, 0.0)), (136, (65, 129, 70), (9.0, 0.0, 3.25)), (200, (200, 1, 199), (0.0, 9.0, 7.0))]
+
+
+@pytest.mark.parametrize("n_q,L1,L2,H,B", [(300, 100, 65, 3, 3), (513, 257, 64, 2, 1), (290, 512, 257, 8, 2)])
+def test_cross_needles_equal_the_fp64_reference(n_q, L1, L2, H, B):
+    c = _proved(X.cross_case(n_q, L1, L2, H, B, seed=n_q + L1 + L2))
+    assert (c.c1, c.c2) == ((L1 + 7) // 8 * 8, (L2 + 7) // 8 * 8) and c.v1t.shape[1] == (B - 1) * c.c1 + X.pad64(L1)
+    for b in range(B):  # the rows edge_keys(len), len - 1 and len - 2 are winners of the first and the last query rows, in every head
+        must = {r for r in [L1 - 1, L1 - 2] + X.edge_keys(L1) if 0 <= r < L1}
+        assert must <= set(c.win1[b, :80, 0].tolist()) and must <= set(c.win1[b, -80:, H - 1].tolist())
+    assert not torch.equal(c.k1[:L1, :10], c.k1[L1:2 * L1, :10]) or B == 1  # another row order per sample
+
+
+def test_cross_needles_margins_at_the_largest_shape():
+    c = X.cross_case(7200, 512, 257, 2, 2, seed=7200 + 512 + 257)
+    lead, forb, _ = X.cross_margins(c)
+    assert min(lead, forb) >= MIN_MARGIN_NATS
+
+
+@pytest.mark.parametrize("share", [(sq, s1, s2) for sq in (False, True) for s1 in (False, True) for s2 in (False, True)])
+def test_cross_shared_operands_equal_the_fp64_reference_and_a_stride_in_place_of_zero_is_seen(share):
+    n_q, L1, L2, H, B = 300, 100, 65, 2, 3
+    sq, s1, s2 = share
+    kw = dict(share_q=sq, share1=s1, share2=s2)
+    _proved(X.cross_case(n_q, L1, L2, H, B, seed=20 + 4 * sq + 2 * s1 + s2, **kw))
+    if sq or s1 or s2:  # the same operands with winner-if-read rows, POISON columns and other queries behind the one sample: read at stride len
+        c = X.cross_case(n_q, L1, L2, H, B, seed=20 + 4 * sq + 2 * s1 + s2, extra=2 * 104 + 64, extra_cols=2 * 104, extra_q=2 * n_q, **kw)
+        assert_exact(X.cross_attention_f64(c), c.want, "fp64 reference, roomy buffers")
+        d = _rows_differ(X.cross_attention_f64(c, "shared operand at stride len"), c.want, B)
+        assert not d[0].any() and d[1].all() and d[2].all()
+
+
+@pytest.mark.parametrize("H", [2, 5])
+@pytest.mark.parametrize("len1,valid,m", FLAT_SETS)
+def test_cross_flat_rows_are_exact_and_see_every_wrong_weight_or_cut(len1, valid, m, H):
+    n_q, L2, B = 300, 65, 3
+    nf = _n_flat(n_q)
+    c = _proved(X.cross_case(n_q, len1, L2, H, B, seed=len1 + H, valid=valid, m=m, n_flat=nf))
+    assert 0 < nf < n_q % 256  # the partial last query block holds needle rows and flat rows
+    flat = c.want.view(B, n_q, -1)[:, n_q - nf:]
+    assert torch.equal(flat.float().to(BF), flat) and bool(((flat.double() * 8) % 1 == 0).all())  # multiples of 1/8, exact in bf16
+    for b in range(B):  # the flat recipe on its own: three significant bits per column
+        v1, out1, key = X.flat_v1(len1, valid[b], m[b], H * 128, torch.Generator().manual_seed(b))
+        assert torch.equal(out1.to(BF).double(), out1) and bool((out1.abs() * 8 / torch.where(X.flat_wcols(H * 128), float(m[b]), 1.0) <= 7).all())
+        assert torch.equal(v1[:valid[b]].to(BF).double(), v1[:valid[b]]) and bool(((v1[:valid[b]] != 0).sum(0) == (key >= 0)).all())
+        assert {valid[b] - 1} | ({valid[b] - 2, 0} if valid[b] > 2 else set()) <= set(key.tolist())
+    is_flat = torch.arange(n_q) >= n_q - nf
+    d = _rows_differ(X.cross_attention_f64(c, "weight ignored"), c.want, B)
+    for b in range(B):
+        assert not d[b, ~is_flat].any()  # a needle row never depends on the weight
+        seen = m[b] > 1 and valid[b] > 1  # (a key that is the only one has the whole softmax, whatever its weight)
+        assert d[b, is_flat].all() == seen and d[b, is_flat].any() == seen
+    d = _rows_differ(X.cross_attention_f64(c, "weight on key valid-2"), c.want, B)
+    for b in range(B):
+        assert d[b, is_flat].all() == (m[b] > 1 and valid[b] > 1)
+    d = _rows_differ(X.cross_attention_f64(c, "w[0] for all samples"), c.want, B)
+    for b in range(B):
+        assert d[b, is_flat].all() == (m[b] != m[0] and valid[b] > 1)
+    d = _rows_differ(X.cross_attention_f64(c, "valid[0] for all samples"), c.want, B)
+    for b in range(B):
+        assert d[b].any() == (valid[b] != valid[0]) and (valid[b] >= valid[0] or d[b].all())  # (a cut too late: a garbage key wins every row)
+    for mistake in ("tail mask at valid+1", "tail mask at len1"):
+        d = _rows_differ(X.cross_attention_f64(c, mistake), c.want, B)
+        for b in range(B):
+            assert d[b].all() or (mistake == "tail mask at len1" and valid[b] == len1)
+    d = _rows_differ(X.cross_attention_f64(c, "neighbour's K1 rows"), c.want, B)
+    assert all(d[b].any() or valid[b] == 1 for b in range(B))
+
+
+@pytest.mark.parametrize("len1,valid,w", CUT_SETS)
+def test_cross_cut_needles_equal_the_fp64_reference_and_see_every_wrong_cut_or_stride(len1, valid, w):
+    n_q, L2, H, B = 300, 257, 2, 3
+    c = _proved(X.cross_case(n_q, len1, L2, H, B, seed=len1, valid=valid, w=w, extra_cols=64))
+    for b in range(B):  # winners from [0, valid[b]), key valid[b] - 1 (the weighted one) among them; the rows behind the cut win if read
+        assert int(c.win1[b].max()) == valid[b] - 1
+        assert bool((c.v1t[:, b * c.c1 + valid[b]:b * c.c1 + len1] == X.POISON).all())
+        assert bool((c.k1[b * len1 + valid[b]:(b + 1) * len1, X.INVALID_DIM] == 1).all())
+    for mistake in ("weight ignored", "weight on key valid-2", "w[0] for all samples"):  # needle rows: the weight decides nothing
+        assert_exact(X.cross_attention_f64(c, mistake), c.want, mistake)
+    d = _rows_differ(X.cross_attention_f64(c, "valid[0] for all samples"), c.want, B)
+    for b in range(B):
+        assert d[b].any() == (valid[b] != valid[0])
+    for mistake in ("tail mask at valid+1", "tail mask at len1"):
+        d = _rows_differ(X.cross_attention_f64(c, mistake), c.want, B)
+        for b in range(B):
+            assert d[b].all() or (mistake == "tail mask at len1" and valid[b] == len1)
+    d = _rows_differ(X.cross_attention_f64(c, "neighbour's K1 rows"), c.want, B)
+    assert all(d[b].any() or valid[b] == 1 for b in range(B))  # (one key: it wins wherever it is read from)
+    d = _rows_differ(X.cross_attention_f64(c, "V^T column stride 64 ceil(len/64)"), c.want, B)
+    assert not d[0].any() and d[1].all() and d[2].all()
+
+
+@pytest.mark.parametrize("n_q,H,B", [(300, 40, 7), (2600, 5, 10)])
+def test_cross_margins_of_the_many_item_shapes(n_q, H, B):
+    """The construction of tests/test_exact_cross_attention_gpu.py's largest launches (the weighted one: ten different (valid, m) pairs)."""
+    MANY_PAIRS = X.MANY_PAIRS
+    c = X.roomy_cross_case(n_q, 200, 65, H, B, seed=n_q + H + len("weighted"), valid=[p[0] for p in MANY_PAIRS[:B]],
+                           m=[p[1] for p in MANY_PAIRS[:B]], n_flat=_n_flat(n_q))
+    assert c.flat_exact and min(X.cross_margins(c)) >= MIN_MARGIN_NATS
+    assert len(set(MANY_PAIRS)) == len(MANY_PAIRS) == 10 and all(v <= 200 and 2 ** round(math.log2(v - 1 + m)) == v - 1 + m for v, m in MANY_PAIRS)
+
+
+def test_far_first_tile_recipe_overflows_the_first_rescale_factor():
+    """`far_first_tile`: margins as for every needle, the winners past tile 0, and the first tile's best score (log2 domain, after the scale)
+    below -128 for every row and head - exp2 of its negative is +inf in fp32, the factor a first-tile rescale would multiply 0 by."""
+    g = torch.Generator().manual_seed(77)
+    q, k, v, rows = X.far_first_tile(70, 130, 3, g)
+    lead, _ = needle_margins(q, k, 3, rows)
+    assert lead.min() >= MIN_MARGIN_NATS and int(rows.min()) >= 64 and len(rows.unique()) > 20
+    first = X.needle_scores(q, k[:64], 3).amax(-1) * X.LOG2E
+    assert first.max().item() < -128 and torch.isinf(torch.exp2(-first.float())).all()
