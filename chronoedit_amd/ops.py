@@ -769,6 +769,71 @@ def tea_apply_(x: torch.Tensor, r: torch.Tensor):
     return x
 
 
+# ---- image pre- / post-processing (csrc/ce_image.hip) ------------------------------------------------------------------
+def image_resample_u8(src: torch.Tensor, axis: int, coeff: torch.Tensor, bounds: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """One 1-D pass of PIL's 8-bit resampler: src uint8 [H, W, 3] -> [H, out, 3] (axis 0, horizontal) or [out, W, 3] (axis 1, vertical),
+    with coeff int32 [out, ksize] (22-bit fixed point) and bounds int32 [out, 2] = (first, count) on the device."""
+    _dev(src, torch.uint8, "src"), _dev(coeff, torch.int32, "coeff"), _dev(bounds, torch.int32, "bounds")
+    if src.dim() != 3 or src.shape[2] != 3 or not src.is_contiguous():
+        raise ValueError(f"src: need a contiguous [H, W, 3] tensor, got shape {tuple(src.shape)} stride {src.stride()}")
+    if axis not in (0, 1):
+        raise ValueError(f"axis: 0 (horizontal) or 1 (vertical), got {axis}")
+    H, W, _ = src.shape
+    n, ksize = coeff.shape
+    if not (coeff.is_contiguous() and bounds.is_contiguous()) or bounds.shape != (n, 2):
+        raise ValueError(f"coeff / bounds: need contiguous [out, ksize] and [out, 2], got {tuple(coeff.shape)} and {tuple(bounds.shape)}")
+    shape = (H, n, 3) if axis == 0 else (n, W, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+    _dev(out, torch.uint8, "out")
+    assert out.is_contiguous() and tuple(out.shape) == shape and out.data_ptr() != src.data_ptr()
+    st = _prof_begin()
+    _check(lib().ce_image_resample_u8(_ptr(src), _ptr(out), axis, H, W, n, _ptr(coeff), _ptr(bounds), ksize, _stream()), "ce_image_resample_u8")
+    _prof_end(st, f"image_resample_{'hv'[axis]}_{H}x{W}_{n}", float(src.numel() + out.numel()))
+    return out
+
+
+def image_u8_lut_planar(src: torch.Tensor, lut: torch.Tensor, out: torch.Tensor, top: int = 0, left: int = 0):
+    """out[c, y, x] = lut[c, src[top + y, left + x, c]]: src uint8 [H, W, 3], lut [3, 256] and out [3, h, w] both bf16 or both fp32."""
+    _dev(src, torch.uint8, "src")
+    if lut.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"lut: expected bfloat16 or float32, got {lut.dtype}")
+    _dev(lut, lut.dtype, "lut"), _dev(out, lut.dtype, "out")
+    if src.dim() != 3 or src.shape[2] != 3 or not src.is_contiguous():
+        raise ValueError(f"src: need a contiguous [H, W, 3] tensor, got shape {tuple(src.shape)} stride {src.stride()}")
+    if tuple(lut.shape) != (3, 256) or not lut.is_contiguous():
+        raise ValueError(f"lut: need a contiguous [3, 256] table, got {tuple(lut.shape)}")
+    if out.dim() != 3 or out.shape[0] != 3 or not out.is_contiguous():
+        raise ValueError(f"out: need a contiguous [3, h, w] tensor, got shape {tuple(out.shape)} stride {out.stride()}")
+    H, W, _ = src.shape
+    h, w = out.shape[1:]
+    if top < 0 or left < 0 or top + h > H or left + w > W:
+        raise ValueError(f"the {h}x{w} crop at ({top}, {left}) does not lie inside the {H}x{W} source")
+    st = _prof_begin()
+    _check(lib().ce_image_u8_lut_planar(_ptr(src), H, W, int(top), int(left), h, w, _ptr(lut), _ptr(out), int(lut.dtype == torch.float32), _stream()),
+           "ce_image_u8_lut_planar")
+    _prof_end(st, f"image_lut_{h}x{w}", float(3 * h * w * (1 + out.element_size())))
+    return out
+
+
+def video_to_u8(video: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """[B, 3, F, H, W] bf16 / fp32 in [-1, 1] -> uint8 [B, F, H, W, 3]: rint(clamp(v * 0.5 + 0.5, 0, 1) * 255), every operation rounded in fp32."""
+    if video.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"video: expected bfloat16 or float32, got {video.dtype}")
+    _dev(video, video.dtype, "video")
+    if video.dim() != 5 or video.shape[1] != 3 or not video.is_contiguous():
+        raise ValueError(f"video: need a contiguous [B, 3, F, H, W] tensor, got shape {tuple(video.shape)} stride {video.stride()}")
+    B, _, F, H, W = video.shape
+    if out is None:
+        out = torch.empty((B, F, H, W, 3), dtype=torch.uint8, device=video.device)
+    _dev(out, torch.uint8, "out")
+    assert out.is_contiguous() and tuple(out.shape) == (B, F, H, W, 3)
+    st = _prof_begin()
+    _check(lib().ce_video_to_u8(_ptr(video), _ptr(out), B, F, H, W, int(video.dtype == torch.float32), _stream()), "ce_video_to_u8")
+    _prof_end(st, f"video_to_u8_{B}x{F}x{H}x{W}", float(video.numel() * (video.element_size() + 1)))
+    return out
+
+
 # ---- Wan VAE ------------------------------------------------------------------------------------------------------
 def conv3d_gemm(in_stack: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], out_stack: torch.Tensor,
                 res_stack: Optional[torch.Tensor], *, T_out: int, H: int, W: int, Cin: int, Cout: int, KT: int, n_tile: int = 0):

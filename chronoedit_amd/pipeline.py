@@ -17,6 +17,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
+from . import image_io
 from .scheduler import FlowUniPCMultistepScheduler
 from .transformer import ChronoEditTransformer3DModel
 
@@ -737,6 +738,9 @@ class ChronoEditPipeline:
             transformer.cache_context = True
         self._guidance_scale, self._attention_kwargs, self._current_timestep, self._interrupt, self._num_timesteps = 1.0, None, None, False, 0
         self._guidance_measure = None  # (max_age, keep_deltas) while measure_guidance_reuse runs its edits
+        # PIL in, PIL out: the resize / normalise passes in front of the encoders and the uint8 packing behind the VAE run on the device
+        # (image_io.py, bit-equal to the host path); arrays, tensors, "np" and "pt" keep the host code.  enable_device_image_io(False): A/B.
+        self.device_image_io = True
 
     # -- properties of the reference pipeline (:458-478) ---------------------------------------------------------------
     @property
@@ -770,6 +774,11 @@ class ChronoEditPipeline:
             if d is not None:
                 return torch.device(d)
         return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+
+    def enable_device_image_io(self, flag: bool = True):
+        """Image pre- / post-processing of `__call__` on the device (default) or, `flag=False`, on the host as before: the same bits."""
+        self.device_image_io = bool(flag)
+        return self
 
     def to(self, device=None, dtype=None):
         """`pipe.to(device)` (run_inference_diffusers.py:386): moves every nn.Module component.  The engine computes in bf16 (the
@@ -882,7 +891,11 @@ class ChronoEditPipeline:
         device = device or self._execution_device
         if self.image_processor is not None and not (isinstance(image, torch.Tensor) and image.dim() == 4 and image.is_floating_point()
                                                      and image.shape[1] == 3 and image.min() < 0):
-            pixel_values = self.image_processor(images=image, return_tensors="pt")["pixel_values"]
+            pixel_values = None
+            if self.device_image_io and torch.device(device).type == "cuda":
+                pixel_values = image_io.clip_pixel_values(self.image_processor, image, device)  # None: not the plain CLIP recipe on PIL input
+            if pixel_values is None:
+                pixel_values = self.image_processor(images=image, return_tensors="pt")["pixel_values"]
         elif isinstance(image, torch.Tensor):
             pixel_values = image
         else:
@@ -1138,7 +1151,10 @@ class ChronoEditPipeline:
         B = batch_size * num_videos_per_prompt
         if hasattr(self.vae, "use_graph"):  # the VAE replays captured graphs from the second edit of a shape on (vae.py)
             self.vae.use_graph = bool(self.use_graph)
-        img = self.preprocess_image(image, height, width).to(device=device, dtype=torch.bfloat16)
+        if self.device_image_io and device.type == "cuda" and (_is_pil(image) or (isinstance(image, (list, tuple)) and image and all(_is_pil(i) for i in image))):
+            img = image_io.preprocess_pil(image, height, width, device)
+        else:
+            img = self.preprocess_image(image, height, width).to(device=device, dtype=torch.bfloat16)
         latents, condition = self.prepare_latents(img, B, self.vae.config.z_dim, height, width, num_frames, torch.bfloat16, device,
                                                   generator, latents)
         if offload_model and hasattr(self.vae, "clear_graphs"):
@@ -1190,7 +1206,10 @@ class ChronoEditPipeline:
                 video = self.video_guardrail_runner(video)
                 if video is None:
                     raise Exception("Guardrail blocked video2world generation.")
-            video = self.postprocess_video(video, output_type=output_type)
+            if self.device_image_io and output_type == "pil" and video.is_cuda and video.dtype in (torch.bfloat16, torch.float32):
+                video = image_io.frames_to_pil(video)
+            else:
+                video = self.postprocess_video(video, output_type=output_type)
         else:
             video = latents
         if offload_model and hasattr(self.vae, "clear_graphs"):

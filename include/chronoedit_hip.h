@@ -495,6 +495,25 @@ int ce_tea_apply_bf16(void* x, const void* r, long long count, hipStream_t strea
 int ce_tea_store_dist_bf16(const void* x, void* r, const void* prev, float* sums, float* scratch, long long scratch_bytes, long long count,
                            hipStream_t stream);
 
+/* ---- image pre- and post-processing (csrc/ce_image.hip; chronoedit_amd/image_io.py): the byte passes of VideoProcessor.preprocess,
+ * CLIPImageProcessor and VideoProcessor.postprocess_video (pipeline_chronoedit.py:247-256,673,801), bit-equal to PIL / numpy ----
+ * ce_image_resample_u8: ONE 1-D pass of PIL's 8-bit resampler over interleaved RGB bytes.  src = uint8 [src_h][src_w][3];
+ *   axis 0 (horizontal): dst = uint8 [src_h][out_len][3];  axis 1 (vertical): dst = uint8 [out_len][src_w][3].
+ *   coeff = int32 [out_len][ksize] (22-bit fixed point), bounds = int32 [out_len][2] = (first, count) along the resampled axis, both in
+ *   device memory, 4-byte aligned.  Per output index o and channel: ss = 2^21 + sum_{k < count} coeff[o][k] * src[first + k] (int32),
+ *   out = clip(ss >> 22, 0, 255) with an arithmetic shift.  count is clipped to ksize and to the source extent.  src != dst.
+ * ce_image_u8_lut_planar: dst[c][y][x] = lut[c][src[top + y][left + x][c]] for c < 3, y < out_h, x < out_w.  src = uint8 [src_h][src_w][3];
+ *   lut = [3][256] and dst = [3][out_h][out_w] (contiguous) of bf16 (dst_f32 == 0) or fp32 (dst_f32 != 0), copied as bits.  The crop
+ *   must lie inside the source (otherwise -1).
+ * ce_video_to_u8: src = [B][3][F][H][W] of bf16 (src_f32 == 0) or fp32, contiguous; dst = uint8 [B][F][H][W][3].  Per element, in fp32 with
+ *   every operation rounded on its own: f = v * 0.5 + 0.5, clamped to [0, 1], u = rint(f * 255) (half to even).  NaN gives 0.
+ * No state, no scratch, nothing allocated: every call is capturable.  An image of 2^31 bytes or more returns -2. */
+int ce_image_resample_u8(const void* src, void* dst, int axis, int src_h, int src_w, int out_len, const int* coeff, const int* bounds,
+                         int ksize, hipStream_t stream);
+int ce_image_u8_lut_planar(const void* src, int src_h, int src_w, int top, int left, int out_h, int out_w, const void* lut, void* dst,
+                           int dst_f32, hipStream_t stream);
+int ce_video_to_u8(const void* src, void* dst, int B, int F, int H, int W, int src_f32, hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
