@@ -834,6 +834,67 @@ def video_to_u8(video: torch.Tensor, out: Optional[torch.Tensor] = None):
     return out
 
 
+# ---- region-limited edits (csrc/ce_region.hip) -------------------------------------------------------------------------
+def region_weights_u8(mask: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """uint8 mask [H, W] (H, W multiples of 8) -> fp32 [H / 8, W / 8]: float(sum of the 64 bytes of a tile) / 16320, the 8x8 box mean."""
+    _dev(mask, torch.uint8, "mask")
+    if mask.dim() != 2 or not mask.is_contiguous():
+        raise ValueError(f"mask: need a contiguous [H, W] tensor, got shape {tuple(mask.shape)} stride {mask.stride()}")
+    H, W = mask.shape
+    if out is None:
+        out = torch.empty((H // 8, W // 8), dtype=torch.float32, device=mask.device)
+    _dev(out, torch.float32, "out")
+    assert out.is_contiguous() and out.numel() == (H // 8) * (W // 8)
+    st = _prof_begin()
+    _check(lib().ce_region_weights_u8(_ptr(mask), _ptr(out), H, W, _stream()), "ce_region_weights_u8")
+    _prof_end(st, f"region_weights_{H}x{W}", float(mask.numel() + 4 * out.numel()))
+    return out
+
+
+def region_blend_(x: torch.Tensor, z_src: torch.Tensor, eps: torch.Tensor, w: torch.Tensor, sigma_next: torch.Tensor, bf16_state: bool = False):
+    """In place on x (fp32, [..., h, w]): k = (1 - s) * z_src + s * eps, x = w * x + (1 - w) * k, every operation rounded in fp32; s is the
+    ONE fp32 element of the device tensor sigma_next, read by the kernel; w = fp32 [h, w], broadcast over the leading axes.
+    bf16_state: x is rounded to a bf16 value (fp32 storage), as cfg_unipc_step's."""
+    for name, t in (("x", x), ("z_src", z_src), ("eps", eps), ("w", w), ("sigma_next", sigma_next)):
+        _dev(t, torch.float32, name)
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: need a contiguous tensor, got shape {tuple(t.shape)} stride {t.stride()}")
+    n, plane = x.numel(), w.numel()
+    if z_src.numel() != n or eps.numel() != n or sigma_next.numel() != 1:
+        raise ValueError(f"z_src / eps: need {n} elements each and ONE sigma, got {z_src.numel()}, {eps.numel()} and {sigma_next.numel()}")
+    if w.dim() != 2 or x.dim() < 2 or tuple(x.shape[-2:]) != tuple(w.shape):
+        raise ValueError(f"w: need [h, w] = the last two axes of x {tuple(x.shape)}, got {tuple(w.shape)}")
+    st = _prof_begin()
+    _check(lib().ce_region_blend_f32(_ptr(x), _ptr(z_src), _ptr(eps), _ptr(w), _ptr(sigma_next), n, plane, 2 if bf16_state else 0, _stream()),
+           "ce_region_blend_f32")
+    _prof_end(st, f"region_blend_{n}", 16.0 * n)
+    return x
+
+
+def region_composite(video: torch.Tensor, src: torch.Tensor, mask: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """video [B, 3, F, H, W] bf16 / fp32, src bf16 [B, 3, H, W], mask uint8 [H, W] -> a NEW fp32 video: m = float(mask) / 255,
+    out = m * video + (1 - m) * src, every operation rounded in fp32; mask and source broadcast over the frames."""
+    if video.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"video: expected bfloat16 or float32, got {video.dtype}")
+    _dev(video, video.dtype, "video"), _dev(src, torch.bfloat16, "src"), _dev(mask, torch.uint8, "mask")
+    if video.dim() != 5 or video.shape[1] != 3 or not video.is_contiguous():
+        raise ValueError(f"video: need a contiguous [B, 3, F, H, W] tensor, got shape {tuple(video.shape)} stride {video.stride()}")
+    B, _, F, H, W = video.shape
+    if tuple(src.shape) != (B, 3, H, W) or not src.is_contiguous():
+        raise ValueError(f"src: need a contiguous [{B}, 3, {H}, {W}] tensor, got shape {tuple(src.shape)} stride {src.stride()}")
+    if tuple(mask.shape) != (H, W) or not mask.is_contiguous():
+        raise ValueError(f"mask: need a contiguous [{H}, {W}] tensor, got shape {tuple(mask.shape)} stride {mask.stride()}")
+    if out is None:
+        out = torch.empty(video.shape, dtype=torch.float32, device=video.device)
+    _dev(out, torch.float32, "out")
+    assert out.is_contiguous() and out.shape == video.shape and out.data_ptr() != video.data_ptr()
+    st = _prof_begin()
+    _check(lib().ce_region_composite(_ptr(video), int(video.dtype == torch.bfloat16), _ptr(src), _ptr(mask), _ptr(out), B, F, H, W, _stream()),
+           "ce_region_composite")
+    _prof_end(st, f"region_composite_{B}x{F}x{H}x{W}", float(video.numel() * (video.element_size() + 4) + src.numel() * 2 + mask.numel()))
+    return out
+
+
 # ---- Wan VAE ------------------------------------------------------------------------------------------------------
 def conv3d_gemm(in_stack: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], out_stack: torch.Tensor,
                 res_stack: Optional[torch.Tensor], *, T_out: int, H: int, W: int, Cin: int, Cout: int, KT: int, n_tile: int = 0):

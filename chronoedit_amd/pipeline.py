@@ -217,14 +217,16 @@ class GraphedDenoiser:
 
     def __init__(self, transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
                  guidance_scale: float, batch_cfg: bool = True, warm: bool = False, keep_warmup_step: bool = True, tea_plan=None,
-                 guidance_plan=None, delta: Optional[torch.Tensor] = None):
+                 guidance_plan=None, delta: Optional[torch.Tensor] = None, region=None):
         """warm: this process has already run a step of exactly this shape / guidance form through `transformer` (packed weights,
         workspaces, kernel attributes exist), so no un-captured step is needed in front of the capture; only the step-invariant context
         projections are computed eagerly so that the graph holds the cache HIT (`cache_context`), not the projections.
         Not warm: the un-captured step that triggers the lazy initialisations IS the trajectory's current step (it runs eagerly on the
         live state, `step()` then skips the replay for that index) - a discarded warm-up cost a whole step per new shape: 2 s of a
         temporal-reasoning edit at 28 800 tokens, 12 % of an 8-step edit.  keep_warmup_step=False: run it on saved state and put the
-        state back (a caller that wants every `step()` to be a replay: bench.py)."""
+        state back (a caller that wants every `step()` to be a replay: bench.py).
+        region: the edit's region.RegionState, or None.  Every kind of step then ends with the region blend, inside its graph; the blend
+        reads its sigma from the state's staging float, which `_stage` fills next to the coefficient row."""
         assert latents.dtype == torch.float32 and latents.is_contiguous()
         if not _capturable(transformer):
             # Measured on this stack (ROCm 7.0 / RCCL 2.26 / torch 2.10: tools/rccl_graph_probe.py, profiles/r03_rccl_graph_probe.txt): ONE
@@ -237,6 +239,7 @@ class GraphedDenoiser:
             raise NotImplementedError("hipGraph capture of a step with torch.distributed exchanges is not usable on this torch / RCCL build: "
                                       "enable_sequence_parallel(owned_comm=True) or run the sharded loop eagerly")
         self.tr, self.sch, self.latents, self.condition = transformer, scheduler, latents, condition
+        self.region = region
         self._ran_eagerly = set()  # sample counts (1: the single sample, 2: the stacked pair) this object has run an eager step of
         self.prompt, self.negative, self.image, self.g, self.batch_cfg = prompt_embeds, negative_prompt_embeds, image_embeds, guidance_scale, batch_cfg
         dev = latents.device
@@ -363,6 +366,8 @@ class GraphedDenoiser:
     def _stage(self, i):
         self.t_buf.copy_(self.sch.timesteps[i])
         self.coef_buf.copy_(self.sch.coef_row(i, self.g, self.latents.device))
+        if self.region is not None:
+            self.region.stage(i)
 
     def _body(self, kind: str = "compute"):
         if self.tea_plan is None:
@@ -374,6 +379,13 @@ class GraphedDenoiser:
             self.tr._tea_mode = None  # a forward outside the loop runs the whole model
 
     def _step_body(self, kind: str = "compute"):
+        """One step of any kind - pair, reuse, off, TeaCache compute or skip, captured or eager: the model and the scheduler update,
+        then, with a region, the blend (chronoedit_amd/region.py)."""
+        self._model_step(kind)
+        if self.region is not None:
+            self.region.blend(self.latents)
+
+    def _model_step(self, kind: str = "compute"):
         inp = torch.cat([self.latents.to(torch.bfloat16), self.condition], dim=1)
         B = inp.shape[0]
         ts = self.t_buf.expand(B)
@@ -434,7 +446,7 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
             num_inference_steps: int, guidance_scale: float = 5.0, enable_temporal_reasoning: bool = False,
             num_temporal_reasoning_steps: int = 0, use_graph: bool = False, on_step_end=None, interrupted=None, graph_warm=None,
             teacache=None, teacache_measure: bool = False, guidance_reuse=None, guidance_measure: Optional[int] = None,
-            keep_deltas: bool = False):
+            keep_deltas: bool = False, region=None):
     """The whole loop, including the temporal-reasoning truncation 8 -> 2 latent frames (pipeline_chronoedit.py:700-709).
     on_step_end(i, t, latents) -> replacement latents, a dict with any of latents / prompt_embeds / negative_prompt_embeds, or None
     (the reference's callback_on_step_end hook, :741-749); graph_warm: a set the caller keeps across edits - shapes already run once in
@@ -462,9 +474,23 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     guidance_measure = A (1..4): every step a "pair" whose store pass also measures, on the device, how far the direction is from those
     of the 1..A steps before; one read-back after the last step.  The latents are the plain loop's; runs eagerly.  Afterwards
     `transformer.guidance_measurement` holds {"timesteps", "rel_l2": [steps][A] (NaN where no direction of that age and shape exists)} and,
-    with keep_deltas, "deltas": the per-step directions (bf16, on the CPU)."""
+    with keep_deltas, "deltas": the per-step directions (bf16, on the CPU).
+    region: a region.RegionConfig (w = fp32 [h, w] box-mean weights of the mask, z_src = fp32 static-source latents of the latents' shape)
+    for a region-limited edit; None = the plain loop, launch for launch.  The loop takes eps = a copy of the latents it starts from and the
+    schedule's sigma_next table itself (region.RegionState.begin).  After every step's scheduler update, before `on_step_end`, the sample
+    is blended in place: x = w * x + (1 - w) * ((1 - s) * z_src + s * eps), s = sigmas[i + 1] - inside the captured graph when `use_graph`
+    (one graph per kind of step, as without).  At the truncation z_src and eps are sliced like the latents.  Works with TeaCache, guidance
+    reuse and trajectory_dtype = bfloat16.  A callback that replaces the latents is taken at its word; the next step blends again.  With
+    sharded tokens or CFG parallelism a NotImplementedError."""
     scheduler.set_timesteps(num_inference_steps, device=latents.device)
     latents = latents.to(torch.float32).contiguous()
+    region_state = None
+    if region is not None:
+        if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
+            raise NotImplementedError("an edit region with the tokens sharded over ranks or with CFG parallelism is not implemented "
+                                      "(the blend runs on replicated latents; nothing sharded has been tested with it)")
+        from . import region as _rg
+        region_state = _rg.RegionState.begin(region, latents, scheduler)
     sharded = getattr(transformer, "_cfgp", None) is not None or (_token_sharded(transformer) and not _sharded_batchable(transformer))
     cfg_inputs = None
     if guidance_scale > 1.0 and negative_prompt_embeds is not None and not sharded:
@@ -540,6 +566,8 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                     scheduler.model_outputs[j] = mo[:, :, [0, -1]].contiguous()
             if scheduler.last_sample is not None and scheduler.last_sample.shape[-3] != latents.shape[-3]:
                 scheduler.last_sample = scheduler.last_sample[:, :, [0, -1]].contiguous()
+            if region_state is not None and region_state.eps.shape[-3] != latents.shape[-3]:
+                region_state.truncate()
         kind = None if g_plan is None else g_plan[i]
         if g_plan is not None:
             if g_table is not None:  # measuring: a ring of the last A directions of this latent shape
@@ -563,10 +591,11 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                     # (with guidance reuse: which forms - the stacked pair, the single sample - the rest of the plan runs; GraphedDenoiser
                     # asks the engine per form on top of this)
                     forms = None if g_plan is None else tuple(sorted({1 if k in ("reuse", "off") else 2 for k in g_plan[i:]}))
-                    return (tuple(latents.shape), guidance_scale > 1.0 and negative_prompt_embeds is not None, gen, tea_plan is not None, forms)
+                    return (tuple(latents.shape), guidance_scale > 1.0 and negative_prompt_embeds is not None, gen, tea_plan is not None, forms,
+                            region_state is not None)
                 graphed = GraphedDenoiser(transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds,
                                           image_embeds, guidance_scale, batch_cfg=not sharded, warm=graph_warm is not None and warm_key() in graph_warm,
-                                          tea_plan=tea_plan, guidance_plan=g_plan, delta=delta)
+                                          tea_plan=tea_plan, guidance_plan=g_plan, delta=delta, region=region_state)
                 if graph_warm is not None:
                     graph_warm.add(warm_key())  # (taken AFTER the construction: the first step of a process creates the engine)
             latents = graphed.step(i)
@@ -594,6 +623,8 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                                        image_embeds, guidance_scale, batch_cfg=True, cfg_inputs=cfg_inputs)
             finally:
                 transformer._tea_mode = None  # a forward outside the loop runs the whole model
+        if region_state is not None and not use_graph:  # (every eager branch above; a graphed step blends inside its graph)
+            region_state.blend(latents, i)
         if kind == "pair":
             delta_valid = True
         elif kind == "off":
@@ -741,6 +772,7 @@ class ChronoEditPipeline:
         # PIL in, PIL out: the resize / normalise passes in front of the encoders and the uint8 packing behind the VAE run on the device
         # (image_io.py, bit-equal to the host path); arrays, tensors, "np" and "pt" keep the host code.  enable_device_image_io(False): A/B.
         self.device_image_io = True
+        self._edit_region = None  # (mask or list of masks, composite) while set_edit_region is in force
 
     # -- properties of the reference pipeline (:458-478) ---------------------------------------------------------------
     @property
@@ -1027,6 +1059,41 @@ class ChronoEditPipeline:
             self._guidance_measure = None
         return out
 
+    # Region-limited edits (chronoedit_amd/region.py): change what the mask marks, keep the source elsewhere.  Off by default; a switch on
+    # the pipeline, `__call__` keeps the reference's signature
+    def set_edit_region(self, mask, composite: bool = True):
+        """mask: ONE mask for every image of the next calls, or a list with one mask per image - a PIL image, a numpy / torch bool or uint8
+        array [height, width], or a float array in [0, 1] (region.normalize_mask; 255 = edit here, 0 = keep the source, greys are weights).
+        Stays set until `clear_edit_region()`.  composite: also paste the source back in pixel space behind the decode (the returned
+        frames then carry the source's bytes exactly where the mask is 0); False: the latent-space blend alone."""
+        if mask is None:
+            raise ValueError("set_edit_region needs a mask (clear_edit_region() switches the region off)")
+        self._edit_region = (list(mask) if isinstance(mask, (list, tuple)) else mask, bool(composite))
+        return self
+
+    def clear_edit_region(self):
+        self._edit_region = None
+        return self
+
+    def _region_setup(self, masks, img: torch.Tensor, num_frames: int):
+        """masks (one, or a list with one per image of img) -> per image (uint8 mask [H, W] on the device, region.RegionConfig)."""
+        from . import region as _rg
+        n_img, _, H, W = img.shape
+        if isinstance(masks, list):
+            if len(masks) != n_img:
+                raise ValueError(f"the edit region holds {len(masks)} masks, but the call has {n_img} image(s): pass one mask, or one per image")
+        else:
+            masks = [masks] * n_img
+        z_src = _rg.static_source_latents(self.vae, img, num_frames)
+        out, seen = [], {}
+        for j, m in enumerate(masks):
+            if id(m) not in seen:  # (one mask for all images: normalised, uploaded and reduced once)
+                mu8 = _rg.normalize_mask(m, H, W).to(img.device)
+                seen[id(m)] = (mu8, _rg.latent_weights(mu8))
+            mu8, w = seen[id(m)]
+            out.append((mu8, _rg.RegionConfig(w=w, z_src=z_src[j:j + 1])))
+        return out
+
     def _measure_kwargs(self) -> dict:
         """What `denoise` gets on top while measure_guidance_reuse runs."""
         if self._guidance_measure is None:
@@ -1157,6 +1224,11 @@ class ChronoEditPipeline:
             img = self.preprocess_image(image, height, width).to(device=device, dtype=torch.bfloat16)
         latents, condition = self.prepare_latents(img, B, self.vae.config.z_dim, height, width, num_frames, torch.bfloat16, device,
                                                   generator, latents)
+        regions = None  # per image: (uint8 mask on the device, region.RegionConfig)
+        if self._edit_region is not None:
+            regions = self._region_setup(self._edit_region[0], img, num_frames)  # one more VAE encode, of the condition encode's shape
+        n_img = img.shape[0]
+        image_of = lambda b: b // num_videos_per_prompt if n_img > 1 else 0  # which image (and mask) sample b edits
         if offload_model and hasattr(self.vae, "clear_graphs"):
             self.vae.clear_graphs()  # a captured encode graph pins its activation pool next to the 14B DiT: the low-memory mode drops it
         if prompt_embeds.shape[0] != B or (negative_prompt_embeds is not None and negative_prompt_embeds.shape[0] != B):
@@ -1193,7 +1265,8 @@ class ChronoEditPipeline:
                                     embeds["negative_prompt_embeds"] if self.do_classifier_free_guidance else None, image_embeds[b:b + 1],
                                     num_inference_steps, guidance_scale, enable_temporal_reasoning, num_temporal_reasoning_steps,
                                     use_graph=self.use_graph, on_step_end=on_step_end, interrupted=lambda: self._interrupt,
-                                    graph_warm=self._graph_warm, **self._measure_kwargs()))
+                                    graph_warm=self._graph_warm, region=None if regions is None else regions[image_of(b)][1],
+                                    **self._measure_kwargs()))
         latents = done[0] if B == 1 else torch.cat(done, dim=0)
         if offload_model and self.transformer is not None:
             self.transformer.cpu()
@@ -1206,6 +1279,12 @@ class ChronoEditPipeline:
                 video = self.video_guardrail_runner(video)
                 if video is None:
                     raise Exception("Guardrail blocked video2world generation.")
+            if regions is not None and self._edit_region[1]:
+                # the paste-back: every returned frame (reasoning frames included) keeps the source where the mask says so - a new fp32 video
+                from . import region as _rg
+                video = video.to(device)
+                video = torch.cat([_rg.composite(video[b:b + 1], img[image_of(b):image_of(b) + 1], regions[image_of(b)][0])
+                                   for b in range(video.shape[0])], dim=0)
             if self.device_image_io and output_type == "pil" and video.is_cuda and video.dtype in (torch.bfloat16, torch.float32):
                 video = image_io.frames_to_pil(video)
             else:
@@ -1224,18 +1303,29 @@ class ChronoEditPipeline:
     def edit_tensors(self, image: torch.Tensor, prompt_embeds: torch.Tensor, negative_prompt_embeds: Optional[torch.Tensor],
                      image_embeds: Optional[torch.Tensor], num_frames: int = 5, num_inference_steps: int = 50, guidance_scale: float = 5.0,
                      enable_temporal_reasoning: bool = False, num_temporal_reasoning_steps: int = 0, generator=None,
-                     latents: Optional[torch.Tensor] = None, output_type: str = "pt"):
+                     latents: Optional[torch.Tensor] = None, output_type: str = "pt", region_mask: Optional[torch.Tensor] = None,
+                     composite: bool = True):
         """Tensor-level form of the same edit (no pre / post processing): image [1,3,H,W] in [-1,1] -> video [1,3,F,H,W] in
-        [-1,1] ("pt") or the final latents ("latent").  What the parity tests and tools/full_edit.py drive."""
+        [-1,1] ("pt") or the final latents ("latent").  What the parity tests and tools/full_edit.py drive.
+        region_mask: a uint8 / bool / float tensor [H, W] for a region-limited edit (region.normalize_mask); `set_edit_region` is not
+        looked at here.  composite: paste the source back behind the decode - the video is then a new fp32 tensor."""
         H, W = image.shape[-2:]
         if H % 16 != 0 or W % 16 != 0:
             raise ValueError(f"`height` and `width` have to be divisible by 16 but are {H} and {W}.")  # pipeline_chronoedit.py:361-362
         if num_frames % 4 != 1:
             num_frames = max(num_frames // 4 * 4 + 1, 1)  # :606-611
         latents, condition = prepare_latents(self.vae, image, num_frames, latents, generator)
+        region = mask_u8 = None
+        if region_mask is not None:
+            from . import region as _rg
+            mask_u8 = _rg.normalize_mask(region_mask, H, W).to(image.device)
+            region = _rg.RegionConfig(w=_rg.latent_weights(mask_u8), z_src=_rg.static_source_latents(self.vae, image, num_frames))
         latents = denoise(self.transformer, self.scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
                           num_inference_steps, guidance_scale, enable_temporal_reasoning, num_temporal_reasoning_steps,
-                          use_graph=self.use_graph, graph_warm=self._graph_warm, **self._measure_kwargs())
+                          use_graph=self.use_graph, graph_warm=self._graph_warm, region=region, **self._measure_kwargs())
         if output_type == "latent":
             return latents
-        return decode_latents(self.vae, latents, enable_temporal_reasoning, num_temporal_reasoning_steps)
+        video = decode_latents(self.vae, latents, enable_temporal_reasoning, num_temporal_reasoning_steps)
+        if region is not None and composite:
+            video = _rg.composite(video, image.to(torch.bfloat16), mask_u8)
+        return video

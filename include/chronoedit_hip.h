@@ -514,6 +514,27 @@ int ce_image_u8_lut_planar(const void* src, int src_h, int src_w, int top, int l
                            int dst_f32, hipStream_t stream);
 int ce_video_to_u8(const void* src, void* dst, int B, int F, int H, int W, int src_f32, hipStream_t stream);
 
+/* ---- region-limited edits (csrc/ce_region.hip; chronoedit_amd/region.py): keep the source outside a caller-given mask - the flow-matching
+ * form of the loop of diffusers' inpaint pipelines, latents = (1 - mask) * scale_noise(image_latents, t_next, noise) + mask * latents.
+ * Every *, + and - below is an fp32 operation rounded on its own (no contraction): each pass is bit-equal to the eager torch expression.
+ * ce_region_weights_u8: mask = uint8 [H][W] (255 = edit, 0 = keep, greys are weights), H and W multiples of 8 (otherwise -1);
+ *   w = fp32 [H/8][W/8], w[i][j] = float(sum of the 64 bytes of tile (i, j)) / 16320.0f: the 8x8 box mean.  All-255 gives exactly 1.0f.
+ * ce_region_blend_f32: in place on x (fp32 [n]), after a scheduler step:
+ *     k = (1.0f - s) * z_src[i] + s * eps[i],   x[i] = w[i % plane] * x[i] + (1.0f - w[i % plane]) * k,   s = *sigma_next
+ *   z_src, eps = fp32 [n]; w = fp32 [plane] (plane = h * w of the latents: broadcast over batch, channel and frame); n % plane == 0.
+ *   sigma_next points to ONE float in device memory, read by the kernel: the loop stages the step's value there and one captured graph
+ *   serves every step.  w == 1 leaves x bit-unchanged, w == 0 gives exactly k, s == 0 gives k == z_src.
+ *   flags bit1: round the stored x to a bf16 value (ce_cfg_unipc_step's "reference-precision trajectory").  All pointers 4-byte aligned.
+ * ce_region_composite: v = [B][3][F][H][W] of bf16 (v_is_bf16 != 0) or fp32, src = bf16 [B][3][H][W], mask = uint8 [H][W],
+ *   out = fp32 [B][3][F][H][W] (not v):  m = float(mask[y][x]) / 255.0f,  out = m * v + (1.0f - m) * src[b][c][y][x]  - mask and source
+ *   broadcast over the frames, the mask over samples and channels.  Where the mask is 0, out == float(src) for every finite v.
+ * No state, no scratch, nothing allocated, no host read: every call is capturable. */
+int ce_region_weights_u8(const void* mask, float* w, int H, int W, hipStream_t stream);
+int ce_region_blend_f32(float* x, const float* z_src, const float* eps, const float* w, const float* sigma_next, long long n,
+                        long long plane, int flags, hipStream_t stream);
+int ce_region_composite(const void* v, int v_is_bf16, const void* src, const void* mask, float* out, int B, int F, int H, int W,
+                        hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
