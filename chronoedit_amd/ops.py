@@ -896,6 +896,80 @@ def region_composite(video: torch.Tensor, src: torch.Tensor, mask: torch.Tensor,
 
 
 # ---- Wan VAE ------------------------------------------------------------------------------------------------------
+# ---- sparse region edits (csrc/ce_sparse.hip) ----------------------------------------------------------------------------
+def _sparse_ids(ids: torch.Tensor):
+    """ids on the device -> (Na, ids_i64).  Sorted / unique / in range is the caller's once-per-edit check (sparse_region.validate_ids)."""
+    if not ids.is_cuda:
+        raise HipKernelError("ids: tensor must live on the GPU (the HIP path has no CPU fallback)")
+    if ids.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"ids: expected int32 or int64, got {ids.dtype}")
+    if ids.dim() != 1 or not ids.is_contiguous() or ids.numel() == 0:
+        raise ValueError(f"ids: need a non-empty contiguous 1-D tensor, got shape {tuple(ids.shape)} stride {ids.stride()}")
+    return ids.numel(), int(ids.dtype == torch.int64)
+
+
+def sparse_patchify(x: torch.Tensor, ids: torch.Tensor, kpad: int, out: Optional[torch.Tensor] = None):
+    """x [C,T,H,W] bf16, ids [Na] -> [Na, kpad]: the rows `patchify` gives for the listed tokens."""
+    _dev(x, torch.bfloat16, "x")
+    assert x.is_contiguous() and x.dim() == 4
+    C, T, H, W = x.shape
+    na, i64 = _sparse_ids(ids)
+    if out is None:
+        out = torch.empty((na, kpad), dtype=torch.bfloat16, device=x.device)
+    _dev(out, torch.bfloat16, "out")
+    assert out.is_contiguous() and out.shape == (na, kpad)
+    st = _prof_begin()
+    _check(lib().ce_sparse_patchify_bf16(_ptr(x), _ptr(ids), i64, _ptr(out), C, T, H, W, kpad, na, _stream()), "ce_sparse_patchify_bf16")
+    _prof_end(st, f"sparse_patchify_{na}x{kpad}", 4.0 * na * kpad)
+    return out
+
+
+def sparse_scatter_rows_(dst: torch.Tensor, src: torch.Tensor, ids: torch.Tensor, batch: int = 1):
+    """dst [batch*N, D], src [batch*Na, D] (row strides free), ids [Na]: dst[b*N + ids[a]] = src[b*Na + a]; other rows are not written."""
+    _dev(dst, torch.bfloat16, "dst"), _dev(src, torch.bfloat16, "src")
+    Md, D, ldd = _rows(dst, "dst")
+    Ms, Ds, lds = _rows(src, "src")
+    na, i64 = _sparse_ids(ids)
+    if batch < 1 or Ds != D or Ms != batch * na or Md % batch or na > Md // batch:
+        raise ValueError(f"sparse_scatter_rows_: src {tuple(src.shape)} / dst {tuple(dst.shape)} do not fit {na} ids and batch={batch}")
+    st = _prof_begin()
+    _check(lib().ce_sparse_scatter_rows_bf16(_ptr(src), lds, _ptr(dst), ldd, _ptr(ids), i64, na, Md // batch, batch, D, _stream()),
+           "ce_sparse_scatter_rows_bf16")
+    _prof_end(st, f"sparse_scatter_rows_{Ms}x{D}", 4.0 * Ms * D)
+    return dst
+
+
+def sparse_scatter_vt_(vt: torch.Tensor, src: torch.Tensor, ids: torch.Tensor, n_tokens: int, batch: int = 1, src_rows: bool = False):
+    """vt [D, >= batch*n_tokens] (the cached V^T, row stride free), ids [Na]: vt[:, b*n_tokens + ids[a]] = V of sample b's active token a.
+    src: V^T [D, batch*Na] as the transposed-store GEMM leaves it (row stride free), or - src_rows - row-major V [batch*Na, D]."""
+    _dev(vt, torch.bfloat16, "vt"), _dev(src, torch.bfloat16, "src")
+    D, cols, ldvt = _rows(vt, "vt")
+    Ms, Ns, lds = _rows(src, "src")
+    na, i64 = _sparse_ids(ids)
+    want = (batch * na, D) if src_rows else (D, batch * na)
+    if batch < 1 or (Ms, Ns) != want or na > n_tokens or cols < batch * n_tokens:
+        raise ValueError(f"sparse_scatter_vt_: src {tuple(src.shape)} (expected {want}) / vt {tuple(vt.shape)} do not fit {na} ids of "
+                         f"{n_tokens} tokens and batch={batch}")
+    st = _prof_begin()
+    _check(lib().ce_sparse_scatter_vt_bf16(_ptr(src), lds, int(bool(src_rows)), _ptr(vt), ldvt, _ptr(ids), i64, na, int(n_tokens), batch, D,
+                                           _stream()), "ce_sparse_scatter_vt_bf16")
+    _prof_end(st, f"sparse_scatter_vt_{batch * na}x{D}" + ("_rows" if src_rows else ""), 4.0 * batch * na * D)
+    return vt
+
+
+def sparse_unpatchify_(out: torch.Tensor, y: torch.Tensor, ids: torch.Tensor):
+    """y [Na, >= 4*Cout] (head rows of the listed tokens), out [Cout,T,H,W]: the 2 x 2 cells of those tokens; nothing else is written."""
+    _dev(y, torch.bfloat16, "y"), _dev(out, torch.bfloat16, "out")
+    Ms, _, ldy = _rows(y, "y")
+    na, i64 = _sparse_ids(ids)
+    assert out.is_contiguous() and out.dim() == 4 and Ms == na, (out.shape, y.shape, na)
+    cout, T, H, W = out.shape
+    st = _prof_begin()
+    _check(lib().ce_sparse_unpatchify_bf16(_ptr(y), ldy, _ptr(ids), i64, _ptr(out), cout, T, H, W, na, _stream()), "ce_sparse_unpatchify_bf16")
+    _prof_end(st, f"sparse_unpatchify_{na}x{4 * cout}", 16.0 * na * cout)
+    return out
+
+
 def conv3d_gemm(in_stack: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], out_stack: torch.Tensor,
                 res_stack: Optional[torch.Tensor], *, T_out: int, H: int, W: int, Cin: int, Cout: int, KT: int, n_tile: int = 0):
     """Stride-1 3x3 / 3x3x3 conv of a wide layer as ONE large-tile GEMM over a contiguous stack of bordered frames (see

@@ -213,11 +213,14 @@ class GraphedDenoiser:
     With a guidance-reuse plan (`guidance_plan`, chronoedit_amd/guidance.py: "pair" / "reuse" / "off" per step, and the loop's `delta` buffer)
     there is one graph per kind of step the plan contains, each captured lazily at the first step of its kind that is replayed; all of them
     address the same latents, scheduler history, staging buffers and delta buffer.  "reuse" and "off" run ONE sample where "pair" runs two: the
-    first step of either form on an engine that has not run it yet (`is_warm`) runs eagerly, for real, before that form is captured."""
+    first step of either form on an engine that has not run it yet (`is_warm`) runs eagerly, for real, before that form is captured.
+    With a sparse-region plan (`sparse_plan`, chronoedit_amd/sparse_region.py: "compute" / "refresh" / "sparse" per step; the engine's
+    `sparse_begin` has been called for this edit) there is likewise one graph per kind, captured lazily; all address the engine's one K / V^T
+    cache.  The first sparse step on an engine that has not run a sparse step of this geometry (`sparse_is_warm`) runs eagerly."""
 
     def __init__(self, transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
                  guidance_scale: float, batch_cfg: bool = True, warm: bool = False, keep_warmup_step: bool = True, tea_plan=None,
-                 guidance_plan=None, delta: Optional[torch.Tensor] = None, region=None):
+                 guidance_plan=None, delta: Optional[torch.Tensor] = None, region=None, sparse_plan=None):
         """warm: this process has already run a step of exactly this shape / guidance form through `transformer` (packed weights,
         workspaces, kernel attributes exist), so no un-captured step is needed in front of the capture; only the step-invariant context
         projections are computed eagerly so that the graph holds the cache HIT (`cache_context`), not the projections.
@@ -259,6 +262,12 @@ class GraphedDenoiser:
             if any(k != "pair" for k in self.guidance_plan):
                 compact_text_context(prompt_embeds)  # the single-sample steps' context, examined once, outside any capture
         self.tea_plan = None if tea_plan is None else [bool(c) for c in tea_plan]
+        self.sparse_plan = None if sparse_plan is None else [str(k) for k in sparse_plan]
+        if self.sparse_plan is not None:
+            if tea_plan is not None or self.guidance_plan is not None:
+                raise ValueError("a sparse region plan excludes TeaCache and guidance reuse")
+            if region is None:
+                raise ValueError("a sparse region plan needs the edit's region")
         if self.tea_plan is not None and self.guided and self.cfg_inputs is None:
             raise NotImplementedError("TeaCache needs the guidance pair as ONE batched forward (one residual buffer covers both samples)")
         self.t_buf = torch.zeros((), dtype=torch.int64, device=dev)
@@ -281,7 +290,7 @@ class GraphedDenoiser:
             with torch.cuda.stream(side):
                 self._body(kind0)
             torch.cuda.current_stream().wait_stream(side)
-            self._ran_eagerly.add(self._n_samples(kind0))
+            self._ran_eagerly.add(self._form(kind0))
             if keep_warmup_step:
                 self._done_index = idx0 or 0
             else:
@@ -316,13 +325,20 @@ class GraphedDenoiser:
     def _n_samples(self, kind: str) -> int:
         return self.latents.shape[0] * (2 if self.cfg_inputs is not None and not self._single(kind) else 1)
 
+    def _form(self, kind: str):
+        """What an eager step of this kind warms: the sample count of a dense forward, or the sparse forward."""
+        return "sparse" if kind == "sparse" else self._n_samples(kind)
+
     def _form_warm(self, kind: str) -> bool:
         """May a step of this kind be captured without an eager step of its form in front?  Yes when this object already ran one, or when the
-        caller vouches for the edit's shape (`warm`) and the engine holds the workspace of exactly this sample count."""
-        n = self._n_samples(kind)
+        caller vouches for the edit's shape (`warm`) and the engine holds the workspace of exactly this sample count.  A sparse step: when
+        the engine has run one of this edit's geometry."""
+        n = self._form(kind)
         if n in self._ran_eagerly:
             return True
         eng = getattr(self.tr, "_engine", None)
+        if kind == "sparse":
+            return bool(eng is not None and eng.sparse_is_warm())
         return bool(self._caller_warm and eng is not None and hasattr(eng, "is_warm") and eng.is_warm(n, *self.latents.shape[2:]))
 
     def _prime_context(self, kind: str = "compute"):
@@ -341,6 +357,8 @@ class GraphedDenoiser:
         """The kind of step i: which graph replays it."""
         if self.guidance_plan is not None:
             return self.guidance_plan[i]
+        if self.sparse_plan is not None:
+            return self.sparse_plan[i]
         return "skip" if self.tea_plan is not None and not self.tea_plan[i] else "compute"
 
     def _capture(self, kind: str = "compute"):
@@ -370,6 +388,12 @@ class GraphedDenoiser:
             self.region.stage(i)
 
     def _body(self, kind: str = "compute"):
+        if self.sparse_plan is not None:
+            self.tr._sparse_mode = kind if kind in ("refresh", "sparse") else None
+            try:
+                return self._step_body(kind)
+            finally:
+                self.tr._sparse_mode = None  # a forward outside the loop runs the whole model
         if self.tea_plan is None:
             return self._step_body(kind)
         self.tr._tea_mode = "skip" if kind == "skip" else "compute"
@@ -379,7 +403,7 @@ class GraphedDenoiser:
             self.tr._tea_mode = None  # a forward outside the loop runs the whole model
 
     def _step_body(self, kind: str = "compute"):
-        """One step of any kind - pair, reuse, off, TeaCache compute or skip, captured or eager: the model and the scheduler update,
+        """One step of any kind - pair, reuse, off, TeaCache compute or skip, sparse-region refresh or sparse, captured or eager: the model and the scheduler update,
         then, with a region, the blend (chronoedit_amd/region.py)."""
         self._model_step(kind)
         if self.region is not None:
@@ -431,7 +455,7 @@ class GraphedDenoiser:
                 with torch.cuda.stream(side):
                     self._body(kind)
                 torch.cuda.current_stream().wait_stream(side)
-                self._ran_eagerly.add(self._n_samples(kind))
+                self._ran_eagerly.add(self._form(kind))
                 self.sch._step_index = i + 1
                 return self.latents
             self._capture(kind)
@@ -446,7 +470,7 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
             num_inference_steps: int, guidance_scale: float = 5.0, enable_temporal_reasoning: bool = False,
             num_temporal_reasoning_steps: int = 0, use_graph: bool = False, on_step_end=None, interrupted=None, graph_warm=None,
             teacache=None, teacache_measure: bool = False, guidance_reuse=None, guidance_measure: Optional[int] = None,
-            keep_deltas: bool = False, region=None):
+            keep_deltas: bool = False, region=None, sparse_region=None):
     """The whole loop, including the temporal-reasoning truncation 8 -> 2 latent frames (pipeline_chronoedit.py:700-709).
     on_step_end(i, t, latents) -> replacement latents, a dict with any of latents / prompt_embeds / negative_prompt_embeds, or None
     (the reference's callback_on_step_end hook, :741-749); graph_warm: a set the caller keeps across edits - shapes already run once in
@@ -481,7 +505,16 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     is blended in place: x = w * x + (1 - w) * ((1 - s) * z_src + s * eps), s = sigmas[i + 1] - inside the captured graph when `use_graph`
     (one graph per kind of step, as without).  At the truncation z_src and eps are sliced like the latents.  Works with TeaCache, guidance
     reuse and trajectory_dtype = bfloat16.  A callback that replaces the latents is taken at its word; the next step blends again.  With
-    sharded tokens or CFG parallelism a NotImplementedError."""
+    sharded tokens or CFG parallelism a NotImplementedError.
+    sparse_region: a sparse_region.SparseRegionConfig for this call (needs `region=`: a ValueError without); None = whatever
+    `transformer.enable_sparse_region()` set, which an edit without a region ignores.  The "compute" / "refresh" / "sparse" plan of the whole
+    edit is made here, before the first step, from the schedule and the mask alone (every step up to and including the truncation step is a
+    "compute"; the active tokens are those of the shape behind it); afterwards `transformer.sparse_report` holds {"plan", "compute", "refresh",
+    "sparse", "active", "tokens"}, None for an edit without a plan.  A sparse step runs the model on the active token rows only, against the
+    K / V^T the last refresh step stored (DiTEngine.sparse_begin has the sizes); the blend keeps the source where w == 0 exactly, as ever.  A
+    callback that replaces the latents or an embedding makes the next step dense, and the plan is remade from there.  With TeaCache or guidance
+    reuse (enabled or measuring) it is a ValueError; with fp8 GEMMs or attention, without the transposed-V self-attention, with sharded
+    tokens or CFG parallelism a NotImplementedError."""
     scheduler.set_timesteps(num_inference_steps, device=latents.device)
     latents = latents.to(torch.float32).contiguous()
     region_state = None
@@ -499,6 +532,14 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
         transformer.clear_context_cache()  # a new edit: nothing of the previous edit's conditioning may be reused
     tea = teacache if teacache is not None else getattr(transformer, "_teacache", None)
     measure = bool(teacache_measure or getattr(transformer, "_tea_measure", False))
+    # sparse region: what it needs and what it excludes, before anything of the edit is set up (the plan itself is made further down)
+    sr = sparse_region if sparse_region is not None else getattr(transformer, "_sparse_region", None)
+    if sparse_region is not None and region is None:
+        raise ValueError("sparse_region needs the edit's region (region=): without a mask there are no inactive tokens to leave out")
+    if sr is not None and region is not None and (tea is not None or measure or guidance_reuse is not None or guidance_measure is not None
+                                                  or getattr(transformer, "_guidance_reuse", None) is not None):
+        raise ValueError("a sparse region plan and TeaCache or guidance reuse (enabled or measuring) exclude each other: their cached "
+                         "residual / direction covers all token rows of a step, a sparse step computes the active ones only")
     if measure and tea is not None:
         raise ValueError("TeaCache: measuring (teacache_measure / calibrate_teacache) and a skip plan (teacache= / enable_teacache) "
                          "exclude each other: disable_teacache() first")
@@ -550,6 +591,26 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
         use_graph = False
         tea_ratios = transformer.teacache_ratios(scheduler.timesteps)
         transformer.engine().tea_measure_begin(len(scheduler.timesteps))
+    # -- sparse region: the plan of the edit, the active ids and the engine's cache (reserved here: before any capture)
+    s_plan, s_forced = None, set()
+    if hasattr(transformer, "sparse_report"):
+        transformer.sparse_report = None
+    if sr is not None and region is not None:
+        from . import sparse_region as _sr
+        eng = transformer.engine()
+        eng.sparse_check()
+        n_steps = len(scheduler.timesteps)
+        truncates = enable_temporal_reasoning and 0 <= int(num_temporal_reasoning_steps) < n_steps
+        if enable_temporal_reasoning:  # every step up to and including the truncation step: the cache is never built at the 8-frame shape
+            s_forced = set(range(min(int(num_temporal_reasoning_steps), n_steps - 1) + 1))
+        T_s = 2 if truncates else latents.shape[2]
+        s_ids, _ = _sr.active_tokens(region_state.w, T_s, sr.margin)  # (the one device-to-host read: the latent weights)
+        s_tokens = T_s * (latents.shape[3] // 2) * (latents.shape[4] // 2)
+        s_full = s_ids.numel() >= s_tokens or s_ids.numel() % _sr.PAD != 0  # the whole grid: nothing to leave out
+        s_plan = _sr.plan(n_steps, sr, s_forced, full=s_full)
+        transformer.sparse_report = _sr.report(s_plan, s_ids.numel(), s_tokens)
+        if "sparse" in s_plan:
+            eng.sparse_begin(s_ids, latents.shape[0] * (2 if cfg_inputs is not None else 1), T_s, latents.shape[3], latents.shape[4])
     graphed = None
     if use_graph and not _capturable(transformer):
         use_graph = False  # a step with torch.distributed exchanges runs eagerly (GraphedDenoiser says why); the pipeline default stays use_graph=True
@@ -595,7 +656,7 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                             region_state is not None)
                 graphed = GraphedDenoiser(transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds,
                                           image_embeds, guidance_scale, batch_cfg=not sharded, warm=graph_warm is not None and warm_key() in graph_warm,
-                                          tea_plan=tea_plan, guidance_plan=g_plan, delta=delta, region=region_state)
+                                          tea_plan=tea_plan, guidance_plan=g_plan, delta=delta, region=region_state, sparse_plan=s_plan)
                 if graph_warm is not None:
                     graph_warm.add(warm_key())  # (taken AFTER the construction: the first step of a process creates the engine)
             latents = graphed.step(i)
@@ -611,6 +672,13 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                 if keep_deltas:
                     g_kept.append(g_ring[g_seen % A].clone())
                 g_seen += 1
+        elif s_plan is not None:
+            transformer._sparse_mode = s_plan[i] if s_plan[i] in ("refresh", "sparse") else None
+            try:
+                latents = denoise_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds,
+                                       image_embeds, guidance_scale, batch_cfg=True, cfg_inputs=cfg_inputs)
+            finally:
+                transformer._sparse_mode = None  # a forward outside the loop runs the whole model
         elif tea_plan is None and not measure:
             latents = denoise_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds,
                                    image_embeds, guidance_scale, batch_cfg=not sharded, cfg_inputs=cfg_inputs)
@@ -631,6 +699,15 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
             delta_valid = False
         if on_step_end is not None:
             new = on_step_end(i, t, latents)
+            replaced = (isinstance(new, dict) and any(k in new for k in ("latents", "prompt_embeds", "negative_prompt_embeds"))) or \
+                (new is not None and not isinstance(new, dict) and new is not latents)
+            if s_plan is not None and replaced and i + 1 < len(s_plan):
+                # the cached K / V^T of the inactive tokens belong to the old latents / conditioning: the next step is dense and the count
+                # restarts behind it
+                s_forced = s_forced | {i + 1}
+                s_plan = s_plan[: i + 1] + _sr.plan(len(s_plan), sr, s_forced, full=s_full)[i + 1:]
+                transformer.sparse_report = _sr.report(s_plan, s_ids.numel(), s_tokens)
+                graphed = None  # (the graphed loop holds the plan it was built with)
             if isinstance(new, dict):  # the reference's callback may also replace the conditioning (pipeline_chronoedit.py:747-749)
                 if "prompt_embeds" in new or "negative_prompt_embeds" in new:
                     prompt_embeds = new.get("prompt_embeds", prompt_embeds)
@@ -1032,6 +1109,17 @@ class ChronoEditPipeline:
 
     def disable_guidance_reuse(self):
         self.transformer.disable_guidance_reuse()
+        return self
+
+    def enable_sparse_region(self, refresh_every: int, start: float = 0.0, margin: int = 1):
+        """Sparse region edits (chronoedit_amd/sparse_region.py): while an edit region is set (`set_edit_region`), one step in `refresh_every`
+        runs the whole model and the others only the tokens under the mask (dilated by `margin` patches), against the keys and values the
+        dense step stored; the first `start` of the schedule runs dense.  Off by default; no effect without an edit region."""
+        self.transformer.enable_sparse_region(refresh_every, start, margin)
+        return self
+
+    def disable_sparse_region(self):
+        self.transformer.disable_sparse_region()
         return self
 
     def measure_guidance_reuse(self, edits, num_inference_steps: int, max_age: int = 3, guidance_scale: float = 5.0, keep_deltas: bool = False,

@@ -219,6 +219,9 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         self._guidance_reuse = None  # guidance reuse (chronoedit_amd.guidance): a GuidanceReuseConfig once enable_guidance_reuse() was called
         self.guidance_report = None  # {"plan", "pair", "reuse", "off"} of the last guided edit that ran with guidance reuse; None otherwise
         self.guidance_measurement = None  # {"timesteps", "rel_l2"[, "deltas"]} of the last edit measured with denoise(guidance_measure=)
+        self._sparse_region = None  # sparse region edits (chronoedit_amd/sparse_region.py): a SparseRegionConfig once enable_sparse_region() was called
+        self._sparse_mode = None    # per forward, set by the denoising loop: None = off (the plain forward), "refresh" or "sparse"
+        self.sparse_report = None   # {"plan", "compute", "refresh", "sparse", "active", "tokens"} of the last edit that ran with a sparse region plan
 
     # -- reference-compatible helpers --------------------------------------------------
     @property
@@ -436,6 +439,23 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
 
     def disable_guidance_reuse(self):
         self._guidance_reuse = None
+        return self
+
+    def enable_sparse_region(self, refresh_every: int, start: float = 0.0, margin: int = 1):
+        """Sparse region edits in `pipeline.denoise` (chronoedit_amd/sparse_region.py): in a region-limited edit (`region=`) one step in
+        `refresh_every` runs the whole model and stores every layer's K / V^T of all tokens; the others run the model on the token rows under
+        the mask (dilated by `margin` patches) only, their self-attention reading the stored K / V^T.  The first `start` of the schedule runs
+        dense.  An edit without a region ignores it.  Not together with TeaCache or guidance reuse; only the default bf16 path with the
+        transposed-V self-attention, not with the tokens sharded or with CFG parallelism."""
+        from .sparse_region import SparseRegionConfig
+        self._sparse_region = SparseRegionConfig(refresh_every, start, margin)
+        return self
+
+    def disable_sparse_region(self):
+        self._sparse_region = None
+        self._sparse_mode = None
+        if self._engine is not None:
+            self._engine.sparse_drop()
         return self
 
     def disable_teacache(self):
@@ -744,6 +764,8 @@ class DiTEngine:
         self._tea_prev = None     # measuring only: the second residual buffer (the step before's residual; the two alternate)
         self._tea_sums = None     # measuring only: fp32 [steps, 2], row i = the two distance sums of step i (NaN: nothing measured)
         self._tea_row = 0         # ... and the row the next measured forward writes (set by the loop)
+        self._sparse = None       # sparse region edits: the active ids, the sparse workspace and the K / V^T cache of one edit (sparse_begin)
+        self._sparse_ran = set()  # ... and the geometries (B, Na, N) a sparse step has run eagerly at on this engine (sparse_is_warm)
         self._tap = None          # tests: a dict here receives copies of intermediates of eager (not captured) forwards ("x_pre_cross0": block 0's stream in front of its cross-attention)
 
     def _fuse(self, linears) -> torch.Tensor:
@@ -1120,6 +1142,157 @@ class DiTEngine:
             ops.gemv(self.tp_w, temb, self.tp_b, flags=1 | 4, out=rows[i])
         return rows.to(torch.bfloat16)  # (exact: flag 4 left bf16 values in the fp32 rows)
 
+    # -- sparse region edits (chronoedit_amd/sparse_region.py) -------------------------------
+    def sparse_check(self, B: int = 1, N: int = 0):
+        """The launch sequences a sparse region edit exists for: the default bf16 path with the transposed-V self-attention, unsharded."""
+        m = self.model
+        if self.fp8 or self.fp8_attn:
+            raise NotImplementedError("sparse region edits with fp8 GEMMs or fp8 attention are not implemented: the cached K / V^T are the "
+                                      "bf16 attention kernel's operands")
+        if not self.v_transposed:
+            raise NotImplementedError("sparse region edits need the transposed-V self-attention (enable_transposed_v): the cache holds V^T")
+        if (m._sp is not None and m._sp.sharded) or getattr(m, "_cfgp", None) is not None:
+            raise NotImplementedError("sparse region edits with the tokens sharded over ranks or with CFG parallelism are not implemented "
+                                      "(the cache is row-local; nothing sharded has been tested with it)")
+        if N and ((B * N) % 8 or (B > 1 and N % 2)):
+            raise NotImplementedError(f"sparse region edits need the V^T form of the dense step: {B} x {N} token rows are not a multiple of 8 "
+                                      "(or an odd count per sample)")
+
+    def sparse_begin(self, ids: torch.Tensor, B: int, T: int, Hh: int, Ww: int):
+        """A sparse region edit starts: `ids` (sparse_region.active_tokens: sorted, unique, a multiple of 8 of them, validated HERE, once) are
+        the active token rows of every one of the B samples of a forward on latents [.., T, Hh, Ww].  Reserves, outside any capture,
+          * the K / V^T cache, [L][B*N, D] and [L][D][vt_columns(B*N)] bf16 - at 720p with a guidance pair 40 x 2 x 14 400 x 5 120 x 2 B =
+            11.8 GB; never at the 8-frame shape of a temporal-reasoning edit, whose steps are all "compute";
+          * the workspace of the sparse steps (B*Na rows) - here, not in `_ws`, which holds the two most recent dense shapes only;
+          * the RoPE table of the active rows, gathered once.
+        A second call with the same geometry keeps the buffers (and drops what the cache holds); `sparse_drop` gives everything back."""
+        from .sparse_region import validate_ids
+        B, T, Hh, Ww = int(B), int(T), int(Hh), int(Ww)
+        Hp, Wp = Hh // 2, Ww // 2
+        N = T * Hp * Wp
+        self.sparse_check(B, N)
+        host = validate_ids(ids, N)
+        Na = host.numel()
+        if Na % 8:
+            raise ValueError(f"sparse region: the active rows per sample must be a multiple of 8 (sparse_region.active_tokens pads), got {Na}")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("sparse region: sparse_begin allocates; it cannot run under a hipGraph capture")
+        D, F, L, dev = self.D, self.F, self.L, self.dev
+        st = self._sparse
+        if st is None or (st.B, st.N) != (B, N):
+            self._sparse = st = None  # (the old cache goes before the new one comes)
+            st = SimpleNamespace(B=B, N=N, k=torch.empty((L, B * N, D), dtype=torch.bfloat16, device=dev),
+                                 vt=torch.zeros((L, D, ops.vt_columns(B * N)), dtype=torch.bfloat16, device=dev), Na=0, ws=None)
+        if st.Na != Na:
+            M = B * Na
+            e = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=dev)
+            st.ws = SimpleNamespace(x=e(M, D), h=e(M, D), qkv=e(M, 3 * D), att=e(M, D), q2=e(M, D), ffn=e(M, F),
+                                    cols=e(M, self.kpatch), head=e(M, self.w_out.shape[0]))
+        st.T, st.Hh, st.Ww, st.Na = T, Hh, Ww, Na
+        st.ids = host.to(device=dev, dtype=torch.int32)
+        st.cs = self._rope_table(T, Hp, Wp)[host.to(dev)].contiguous()
+        st.valid = False  # no refresh step of THIS edit has filled the cache yet
+        self._sparse = st
+        return st
+
+    def sparse_drop(self):
+        """Forget the active ids and give the cache and the sparse workspace back."""
+        self._sparse = None
+
+    def sparse_is_warm(self) -> bool:
+        """Has a sparse step of the begun edit's geometry already run eagerly through this engine?  What a hipGraph capture of a sparse step
+        without an eager one in front requires (pipeline.GraphedDenoiser), as `is_warm` for the dense forms."""
+        st = self._sparse
+        return st is not None and (st.B, st.Na, st.N) in self._sparse_ran
+
+    def _sparse_state(self, B: int, T: int, Hh: int, Ww: int):
+        st = self._sparse
+        if st is None or (st.B, st.T, st.Hh, st.Ww) != (B, T, Hh, Ww):
+            raise RuntimeError(f"sparse region: no sparse_begin for {B} samples of latents [.., {T}, {Hh}, {Ww}]"
+                               + ("" if st is None else f" (the edit was begun for {(st.B, st.T, st.Hh, st.Ww)})"))
+        return st
+
+    def _forward_sparse(self, st, hidden: torch.Tensor, timestep: torch.Tensor, text: torch.Tensor, image: Optional[torch.Tensor]):
+        """A "sparse" step: the plain forward's arithmetic on the Na active token rows of every sample.  Per block the fresh K (after norm +
+        RoPE) and V^T of the active rows replace their entries in the layer's cache, and the self-attention runs Na queries against all N
+        cached keys; everything else is row-local and runs on B*Na rows.  The prediction is written at the active tokens' cells of an output
+        that is zero elsewhere (the region blend discards it there).  The guidance pair's shared prefix is not used."""
+        cfg, D, H = self.cfg, self.D, self.H
+        B, C, T, Hh, Ww = hidden.shape
+        hd, eps = cfg.attention_head_dim, cfg.eps
+        if not st.valid:
+            raise RuntimeError("sparse region: a sparse step needs the K / V^T a refresh step of this edit stored")
+        self.sparse_check(B, st.N)
+        Na, N, ids, cs, ws = st.Na, st.N, st.ids, st.cs, st.ws
+        hidden = hidden.to(torch.bfloat16).contiguous()
+        timestep = timestep.to(device=self.dev, dtype=torch.float32 if timestep.is_floating_point() else torch.int64).contiguous()
+        rows = [slice(b * Na, (b + 1) * Na) for b in range(B)]
+        for b in range(B):
+            ops.sparse_patchify(hidden[b], ids, self.kpatch, out=ws.cols[rows[b]])
+        x = ops.gemm(ws.cols, self.w_patch, self.b_patch, out=ws.x)
+        mods, mods_out = [], []
+        for b in range(B):  # K2, as the plain forward
+            sin = ops.timestep_sinusoid(timestep[b : b + 1], cfg.freq_dim)
+            h1 = ops.gemv(self.te_w1, sin, self.te_b1, flags=2)
+            temb = ops.gemv(self.te_w2, h1, self.te_b2, flags=4)
+            tproj = ops.gemv(self.tp_w, temb, self.tp_b, flags=1 | 4)
+            mods.append(ops.modulation(self.tables, tproj.view(6, D), one_mask=0b010010))
+            mods_out.append(ops.modulation(self.table_out, temb.view(1, D), one_mask=0b10))
+        mod = torch.stack(mods, dim=1).contiguous()          # [L, B, 6, D]; ab_rows / gate_rows = Na
+        mod_out = torch.stack(mods_out, dim=0).contiguous()  # [B, 1, 2, D]
+        if B > 1:
+            gate_msa, gate_ffn = mod[:, :, 2].contiguous(), mod[:, :, 5].contiguous()
+        grow = Na if B > 1 else 0
+        # the context in the form the dense steps of this edit use: the same cache entry serves both kinds
+        ctx = self._context(text, image, share_image=B == 2 and self._share_image(text, image))
+        if ctx.f8:
+            raise NotImplementedError("sparse region edits with fp8 cross-attention are not implemented")
+        Tt, Ti = ctx.Tt, ctx.Ti
+        for li, p in enumerate(self.blk):
+            # 1. self-attention: q | k | v of the active rows as ONE product; k and v are scattered into the layer's cache, v transposed on
+            # the way (measured at 720p, profiles/notes_region_sparse.md: the scatter from row-major V is 1.0 - 1.7 x faster than from the
+            # transposed store's V^T, and the fused product replaces two); Nq = Na queries, len = N keys
+            ops.ln_affine(x, mod[li, 0, 1], mod[li, 0, 0], eps, out=ws.h, ab_rows=Na, ab_stride=6 * D)
+            ops.gemm(ws.h, p.w_qkv, p.b_qkv, out=ws.qkv)
+            ops.rmsnorm_rope_(ws.qkv[:, :D], p.nq1, cs, hd, eps, x2=ws.qkv[:, D : 2 * D], w2=p.nk1)
+            ops.sparse_scatter_rows_(st.k[li], ws.qkv[:, D : 2 * D], ids, batch=B)
+            ops.sparse_scatter_vt_(st.vt[li], ws.qkv[:, 2 * D :], ids, N, batch=B, src_rows=True)
+            ops.attention_vt(ws.qkv[:, :D], st.k[li], st.vt[li], H, out=ws.att, batch=B)
+            ops.gemm(ws.att, p.w_o1, p.b_o1, out=x, epilogue=ops.EPI_GATE_RES, gate=gate_msa[li] if B > 1 else mods[0][li, 2], res=x, gate_rows=grow)
+            # 2. cross-attention: row-local, the launch the dense step makes with Na query rows per sample
+            if p.n2w is not None:
+                ops.ln_affine(x, p.n2w, p.n2b, eps, out=ws.h)
+                ops.gemm(ws.h, p.w_q2, p.b_q2, out=ws.q2)
+            else:
+                ops.gemm(x, p.w_q2, p.b_q2, out=ws.q2)
+            ops.rmsnorm_rope_(ws.q2, p.nq2, None, hd, eps)
+            k_t, v_t, k_i, v_i = ctx.kv[li]
+            if ctx.valid is not None:
+                ops.attention_2seg_vt_weighted(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, valid1=ctx.valid, w1=ctx.w,
+                                               share2=ctx.img_shared, cols1=ctx.c1, cols2=None if ctx.img_shared else ctx.c2)
+            elif ctx.img_shared:
+                ops.attention_2seg_vt_shared(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, share2=True, cols1=ctx.c1)
+            elif ctx.vt:
+                ops.attention_2seg_vt(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, cols1=ctx.c1, cols2=ctx.c2)
+            elif k_i is not None:
+                ops.attention(ws.q2, k_t, v_t, H, out=ws.att, k2=k_i, v2=v_i, batch=B)
+            else:
+                ops.attention(ws.q2, k_t, v_t, H, out=ws.att, batch=B)
+            ops.gemm(ws.att, p.w_o2, p.b_o2, out=x, epilogue=ops.EPI_GATE_RES, gate=None, res=x)
+            # 3. feed-forward
+            ops.ln_affine(x, mod[li, 0, 4], mod[li, 0, 3], eps, out=ws.h, ab_rows=Na, ab_stride=6 * D)
+            ops.gemm(ws.h, p.w_f1, p.b_f1, out=ws.ffn, epilogue=ops.EPI_BIAS_GELU)
+            ops.gemm(ws.ffn, p.w_f2, p.b_f2, out=x, epilogue=ops.EPI_GATE_RES, gate=gate_ffn[li] if B > 1 else mods[0][li, 5], res=x, gate_rows=grow)
+        # K18 on the active rows, then their cells of an output that is zero elsewhere
+        ops.ln_affine(x, mod_out[0, 0, 1], mod_out[0, 0, 0], eps, out=ws.h, ab_rows=Na, ab_stride=2 * D)
+        ops.gemm(ws.h, self.w_out, self.b_out, out=ws.head)
+        out = torch.zeros((B, cfg.out_channels, T, Hh, Ww), dtype=torch.bfloat16, device=self.dev)
+        for b in range(B):
+            ops.sparse_unpatchify_(out[b], ws.head[rows[b]], ids)
+        if not torch.cuda.is_current_stream_capturing():
+            self._sparse_ran.add((st.B, Na, N))
+        return out
+
     # -- the forward (transformer_chronoedit.py:397-476) ---------------------------------
     def forward(self, hidden: torch.Tensor, timestep: torch.Tensor, text: torch.Tensor, image: Optional[torch.Tensor]):
         """hidden [B,C,T,H,W], timestep [B], text [B,Tt,text_dim], image [B,Ti,image_dim] -> [B,Cout,T,H,W] (bf16).
@@ -1136,6 +1309,22 @@ class DiTEngine:
         hd = cfg.attention_head_dim
         eps = cfg.eps
         cs = self._rope_table(T, Hp, Wp)  # raises AssertionError for unsupported frame counts (:205)
+        # Sparse region edits (per-call mode, set by the denoising loop; None = off: the launch sequence below is exactly the plain forward's).
+        # sparse: the forward on the active rows (_forward_sparse).  refresh: the plain forward, which also copies every layer's K (after norm +
+        # RoPE) and V^T into the edit's cache - copies only, so its output is the plain forward's bit for bit.
+        sparse = self.model._sparse_mode
+        sparse_st = None
+        if sparse is not None:
+            if sparse not in ("refresh", "sparse"):
+                raise ValueError(f"unknown sparse region mode {sparse!r}")
+            if self.model._tea_mode is not None:
+                raise ValueError("sparse region edits and TeaCache exclude each other")
+            self.sparse_check(B, N)
+            sparse_st = self._sparse_state(B, T, Hh, Ww)
+            if text.shape[0] != B or (image is not None and image.shape[0] != B):
+                raise ValueError("encoder_hidden_states / encoder_hidden_states_image batch size must match hidden_states")
+            if sparse == "sparse":
+                return self._forward_sparse(sparse_st, hidden, timestep, text, image)
         sp = self.model._sp
         if sp is not None and sp.sharded:
             if B != 1 and not self.v_transposed:
@@ -1256,6 +1445,10 @@ class DiTEngine:
                 # block 0 up to its cross-attention on the one shared sample (the B = 1 launches on N rows), then the fan-out: queries shared,
                 # text keys per sample, image keys shared, output per sample; the out-projection adds the shared residual to both
                 self._block0_shared_prefix(ws, xs, p, mods[0], cs, N)
+                if sparse_st is not None:  # refresh: the one shared sample's K / V^T are both samples'
+                    for b in range(B):
+                        sparse_st.k[0][rows[b]].copy_(ws.qkv[:N, D : 2 * D])
+                        sparse_st.vt[0][:, b * N : (b + 1) * N].copy_(ws.vt[:, :N])
                 k_t, v_t, k_i, v_i = ctx.kv[0]
                 if ctx.valid is not None:
                     ops.attention_2seg_vt_weighted(ws.q2[:N], k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, valid1=ctx.valid, w1=ctx.w,
@@ -1293,6 +1486,9 @@ class DiTEngine:
                 else:
                     ops.gemm(ws.h, p.w_qkv[2 * D :], p.b_qkv[2 * D :], out=ws.vt[:, : B * Nl], epilogue=ops.EPI_BIAS_T)  # (stores the transpose: V^T)
                 ops.rmsnorm_rope_(ws.qkv[:, :D], p.nq1, cs, hd, eps, x2=ws.qkv[:, D : 2 * D], w2=p.nk1)
+                if sparse_st is not None:  # refresh
+                    sparse_st.k[li].copy_(ws.qkv[:, D : 2 * D])
+                    sparse_st.vt[li][:, : B * Nl].copy_(ws.vt[:, : B * Nl])
                 ops.attention_vt(ws.qkv[:, :D], ws.qkv[:, D : 2 * D], ws.vt, H, out=ws.att, batch=B)
                 att = ws.att
             elif sp is None:  # all samples in one launch (stacked rows)
@@ -1354,6 +1550,8 @@ class DiTEngine:
             else:
                 ops.tea_store_(x, self._tea_res)
             self._tea_valid = True
+        if sparse_st is not None:
+            sparse_st.valid = True
         return self._head(ws, x, mod_out, sp, B, T, Hh, Ww, N, Nl, rows)
 
     def _block0_shared_prefix(self, ws, xs, p, mods0, cs, N: int):

@@ -535,6 +535,28 @@ int ce_region_blend_f32(float* x, const float* z_src, const float* eps, const fl
 int ce_region_composite(const void* v, int v_is_bf16, const void* src, const void* mask, float* out, int B, int F, int H, int W,
                         hipStream_t stream);
 
+/* ---- sparse region edits (csrc/ce_sparse.hip; chronoedit_amd/sparse_region.py): the gather / scatter layer of a step that runs the DiT on
+ * the Na ACTIVE token rows per sample only.  ids = Na sorted, unique token indices in [0, N) - int32, or int64 when ids_i64 != 0 - in device
+ * memory, the same for every sample; the host validates them once per edit, and an id outside [0, N) is skipped by every pass.
+ * Pure data movement: bit-equal to the indexing expression, nothing outside the listed rows / columns / cells is written.
+ * ce_sparse_patchify_bf16: x [C][T][H][W] -> cols [Na][Kpad]: row a = row ids[a] of ce_patchify_bf16's result.
+ * ce_sparse_scatter_rows_bf16: src [B*Na][lds] -> dst [B*N][ldd] (D columns, D % 8 == 0; lds, ldd multiples of 8, both pointers 16-byte
+ *   aligned): row b*Na + a goes to row b*N + ids[a] - K after norm + RoPE into the cached K.
+ * ce_sparse_scatter_vt_bf16: the fresh V of the active tokens -> columns b*N + ids[a] of vt [D][ldvt] (ldvt >= B*N).  src_rows == 0: src is
+ *   V^T [D][lds], sample b's active token a in column b*Na + a (what the transposed-store GEMM, CE_EPI_BIAS_T, leaves); src_rows != 0: src is
+ *   row-major V [B*Na][lds], transposed on the way.  Columns not listed, the padding columns among them, are not written.
+ * ce_sparse_unpatchify_bf16: y [Na][ldy] (col = (dh*2+dw)*Cout + c, as ce_unpatchify_bf16) -> the 2 x 2 cells of token ids[a] in
+ *   out [Cout][T][H][W].
+ * No state, no scratch, nothing allocated, no host read: every call is capturable. */
+int ce_sparse_patchify_bf16(const void* x, const void* ids, int ids_i64, void* cols, int C, int T, int H, int W, int Kpad, int Na,
+                            hipStream_t stream);
+int ce_sparse_scatter_rows_bf16(const void* src, int lds, void* dst, int ldd, const void* ids, int ids_i64, int Na, int N, int B, int D,
+                                hipStream_t stream);
+int ce_sparse_scatter_vt_bf16(const void* src, int lds, int src_rows, void* vt, int ldvt, const void* ids, int ids_i64, int Na, int N, int B,
+                              int D, hipStream_t stream);
+int ce_sparse_unpatchify_bf16(const void* y, int ldy, const void* ids, int ids_i64, void* out, int Cout, int T, int H, int W, int Na,
+                              hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
