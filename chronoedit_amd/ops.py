@@ -895,6 +895,84 @@ def region_composite(video: torch.Tensor, src: torch.Tensor, mask: torch.Tensor,
     return out
 
 
+# ---- automatic edit regions (csrc/ce_region_auto.hip) ------------------------------------------------------------------
+def _f32c(t: torch.Tensor, name: str):
+    _dev(t, torch.float32, name)
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: need a contiguous tensor, got shape {tuple(t.shape)} stride {t.stride()}")
+
+
+def auto_region_change(x0: torch.Tensor, z_src: torch.Tensor, frame: int = -1, out: Optional[torch.Tensor] = None):
+    """x0, z_src fp32 [B, C, T, h, w] -> d fp32 [h, w] on latent frame `frame` (negative: from the end):
+    d = max over b of ((sum over c, in order, of (x0 - z_src)^2) / C), every operation rounded in fp32."""
+    _f32c(x0, "x0"), _f32c(z_src, "z_src")
+    if x0.dim() != 5 or tuple(z_src.shape) != tuple(x0.shape):
+        raise ValueError(f"x0 / z_src: need two [B, C, T, h, w] tensors of one shape, got {tuple(x0.shape)} and {tuple(z_src.shape)}")
+    B, C, T, h, w = x0.shape
+    f = int(frame) + T if frame < 0 else int(frame)
+    if not 0 <= f < T:
+        raise ValueError(f"frame: {frame} is outside the {T} latent frames")
+    if out is None:
+        out = torch.empty((h, w), dtype=torch.float32, device=x0.device)
+    _f32c(out, "out")
+    assert out.numel() == h * w
+    st = _prof_begin()
+    _check(lib().ce_auto_region_change_f32(_ptr(x0), _ptr(z_src), _ptr(out), B, C, T, h, w, f, _stream()), "ce_auto_region_change_f32")
+    _prof_end(st, f"auto_region_change_{B}x{C}x{h}x{w}", float(8 * B * C * h * w + 4 * h * w))
+    return out
+
+
+def auto_region_otsu(d: torch.Tensor, floor: float = 0.0, thr: Optional[torch.Tensor] = None, dmax: Optional[torch.Tensor] = None):
+    """d fp32 (any shape, >= 0 or NaN) -> (thr, dmax), one device float each: Otsu's threshold over 256 bins of [0, dmax], at least floor^2;
+    +inf when dmax == 0.  One workgroup, nothing read back."""
+    _f32c(d, "d")
+    if thr is None:
+        thr = torch.empty(1, dtype=torch.float32, device=d.device)
+    if dmax is None:
+        dmax = torch.empty(1, dtype=torch.float32, device=d.device)
+    _f32c(thr, "thr"), _f32c(dmax, "dmax")
+    assert thr.numel() == 1 and dmax.numel() == 1
+    st = _prof_begin()
+    _check(lib().ce_auto_region_otsu_f32(_ptr(d), d.numel(), float(floor), _ptr(thr), _ptr(dmax), _stream()), "ce_auto_region_otsu_f32")
+    _prof_end(st, f"auto_region_otsu_{d.numel()}", float(8 * d.numel()))
+    return thr, dmax
+
+
+def auto_region_ramp(d: torch.Tensor, thr: torch.Tensor, dilate: int, feather: int, out: Optional[torch.Tensor] = None):
+    """d fp32 [h, w], thr = ONE device float -> w fp32 [h, w]: 1 within `dilate` cells (Chebyshev) of a cell with d > thr, a linear ramp
+    over the next `feather` cells, 0 beyond.  dilate + feather <= 8."""
+    _f32c(d, "d"), _f32c(thr, "thr")
+    if d.dim() != 2 or thr.numel() != 1:
+        raise ValueError(f"d / thr: need an [h, w] map and ONE threshold, got {tuple(d.shape)} and {thr.numel()} elements")
+    if dilate < 0 or feather < 0 or dilate + feather > 8:
+        raise ValueError(f"dilate + feather must lie in 0..8, got {dilate} + {feather}")
+    if out is None:
+        out = torch.empty_like(d)
+    _f32c(out, "out")
+    assert out.numel() == d.numel() and out.data_ptr() != d.data_ptr()
+    st = _prof_begin()
+    _check(lib().ce_auto_region_ramp_f32(_ptr(d), _ptr(thr), _ptr(out), d.shape[0], d.shape[1], int(dilate), int(feather), _stream()),
+           "ce_auto_region_ramp_f32")
+    _prof_end(st, f"auto_region_ramp_{d.shape[0]}x{d.shape[1]}_r{dilate + feather}", float(8 * d.numel()))
+    return out
+
+
+def auto_region_mask_u8(w: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """w fp32 [h, w] -> uint8 [8 h, 8 w]: byte = rint(255 * w) of the pixel's cell."""
+    _f32c(w, "w")
+    if w.dim() != 2:
+        raise ValueError(f"w: need an [h, w] map, got {tuple(w.shape)}")
+    h, wl = w.shape
+    if out is None:
+        out = torch.empty((8 * h, 8 * wl), dtype=torch.uint8, device=w.device)
+    _dev(out, torch.uint8, "out")
+    assert out.is_contiguous() and out.numel() == 64 * h * wl
+    st = _prof_begin()
+    _check(lib().ce_auto_region_mask_u8(_ptr(w), _ptr(out), h, wl, _stream()), "ce_auto_region_mask_u8")
+    _prof_end(st, f"auto_region_mask_{h}x{wl}", float(4 * w.numel() + out.numel()))
+    return out
+
+
 # ---- Wan VAE ------------------------------------------------------------------------------------------------------
 # ---- sparse region edits (csrc/ce_sparse.hip) ----------------------------------------------------------------------------
 def _sparse_ids(ids: torch.Tensor):

@@ -470,7 +470,7 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
             num_inference_steps: int, guidance_scale: float = 5.0, enable_temporal_reasoning: bool = False,
             num_temporal_reasoning_steps: int = 0, use_graph: bool = False, on_step_end=None, interrupted=None, graph_warm=None,
             teacache=None, teacache_measure: bool = False, guidance_reuse=None, guidance_measure: Optional[int] = None,
-            keep_deltas: bool = False, region=None, sparse_region=None):
+            keep_deltas: bool = False, region=None, sparse_region=None, auto_region=None):
     """The whole loop, including the temporal-reasoning truncation 8 -> 2 latent frames (pipeline_chronoedit.py:700-709).
     on_step_end(i, t, latents) -> replacement latents, a dict with any of latents / prompt_embeds / negative_prompt_embeds, or None
     (the reference's callback_on_step_end hook, :741-749); graph_warm: a set the caller keeps across edits - shapes already run once in
@@ -506,7 +506,7 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     (one graph per kind of step, as without).  At the truncation z_src and eps are sliced like the latents.  Works with TeaCache, guidance
     reuse and trajectory_dtype = bfloat16.  A callback that replaces the latents is taken at its word; the next step blends again.  With
     sharded tokens or CFG parallelism a NotImplementedError.
-    sparse_region: a sparse_region.SparseRegionConfig for this call (needs `region=`: a ValueError without); None = whatever
+    sparse_region: a sparse_region.SparseRegionConfig for this call (needs `region=` or a detecting `auto_region=`: a ValueError without); None = whatever
     `transformer.enable_sparse_region()` set, which an edit without a region ignores.  The "compute" / "refresh" / "sparse" plan of the whole
     edit is made here, before the first step, from the schedule and the mask alone (every step up to and including the truncation step is a
     "compute"; the active tokens are those of the shape behind it); afterwards `transformer.sparse_report` holds {"plan", "compute", "refresh",
@@ -514,9 +514,48 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     K / V^T the last refresh step stored (DiTEngine.sparse_begin has the sizes); the blend keeps the source where w == 0 exactly, as ever.  A
     callback that replaces the latents or an embedding makes the next step dense, and the plan is remade from there.  With TeaCache or guidance
     reuse (enabled or measuring) it is a ValueError; with fp8 GEMMs or attention, without the transposed-V self-attention, with sharded
-    tokens or CFG parallelism a NotImplementedError."""
+    tokens or CFG parallelism a NotImplementedError.
+    auto_region: an auto_region.AutoRegion (the config - None: whatever `transformer.enable_auto_region()` set - and z_src = fp32
+    static-source latents of the latents' shape) for an edit that finds its own region; None = the plain loop, launch for launch.  An explicit `region=` wins: the detector is not run and the report is None.
+    The loop keeps a clone of the latents it starts from (the blend's eps); steps 0 .. k run as the plain loop (k = detect_step, or with
+    temporal reasoning the first step at or behind it that runs at the truncated shape; past the last step nothing is detected).  After
+    step k's scheduler update, before `on_step_end`, four device passes (csrc/ce_region_auto.hip) turn x0 = scheduler.model_outputs[-1]
+    and z_src into the weights w and the pixel mask, and ONE read brings w to the host.  Declined (no active cell, or more active patches
+    than max_area of the grid - with the sparse margin when a sparse region is enabled): the edit stays the plain loop, bit for bit.
+    Accepted: a RegionState is built from (w, z_src, eps, sigma_next), the blend runs after step k itself and after every later step,
+    the graphed loop is rebuilt (a region is another warm shape), and with a sparse region config the plan is made now, every step <= k
+    forced dense, so that step k + 1 is the first refresh.  Composition and refusals are those of an explicit region.  Afterwards
+    `transformer.auto_region_report` and `auto_region.report` hold {"step", "threshold", "dmax", "active_fraction", "accepted", "reason",
+    "w", "mask"} and `auto_region.mask_u8` the device mask of an accepted region.  auto_region.measure: every step runs the plain loop and
+    writes its change map into a [steps, h, w] device table, read back once after the last step: `transformer.auto_region_measurement`
+    then holds one row per step (auto_region.measurement)."""
     scheduler.set_timesteps(num_inference_steps, device=latents.device)
     latents = latents.to(torch.float32).contiguous()
+    auto = auto_region if region is None else None  # an explicit mask wins
+    a_cfg = None
+    if auto is not None:  # (no config of its own: whatever `transformer.enable_auto_region()` set - nothing: the plain loop)
+        a_cfg = auto.config if auto.config is not None else getattr(transformer, "_auto_region", None)
+        if a_cfg is None:
+            auto = None
+    if hasattr(transformer, "auto_region_report"):
+        transformer.auto_region_report = None
+    if auto_region is not None:
+        auto_region.report = auto_region.mask_u8 = None
+    auto_k = auto_z = auto_eps = auto_table = None
+    if auto is not None:
+        if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
+            raise NotImplementedError("an edit region with the tokens sharded over ranks or with CFG parallelism is not implemented "
+                                      "(the blend runs on replicated latents; nothing sharded has been tested with it)")
+        from . import auto_region as _ar
+        if tuple(auto.z_src.shape) != tuple(latents.shape):
+            raise ValueError(f"auto region: z_src {tuple(auto.z_src.shape)} does not have the latents' shape {tuple(latents.shape)}")
+        auto_z = auto.z_src.to(device=latents.device, dtype=torch.float32).contiguous()
+        if auto.measure:
+            auto_table = torch.zeros((len(scheduler.timesteps),) + tuple(latents.shape[-2:]), dtype=torch.float32, device=latents.device)
+        else:
+            auto_k = _ar.detect_index(a_cfg, len(scheduler.timesteps), enable_temporal_reasoning, num_temporal_reasoning_steps)
+            auto_eps = latents.clone()  # the blend's eps, should a region be found
+    detecting = auto is not None and not auto.measure
     region_state = None
     if region is not None:
         if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
@@ -534,9 +573,9 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     measure = bool(teacache_measure or getattr(transformer, "_tea_measure", False))
     # sparse region: what it needs and what it excludes, before anything of the edit is set up (the plan itself is made further down)
     sr = sparse_region if sparse_region is not None else getattr(transformer, "_sparse_region", None)
-    if sparse_region is not None and region is None:
+    if sparse_region is not None and region is None and not detecting:
         raise ValueError("sparse_region needs the edit's region (region=): without a mask there are no inactive tokens to leave out")
-    if sr is not None and region is not None and (tea is not None or measure or guidance_reuse is not None or guidance_measure is not None
+    if sr is not None and (region is not None or detecting) and (tea is not None or measure or guidance_reuse is not None or guidance_measure is not None
                                                   or getattr(transformer, "_guidance_reuse", None) is not None):
         raise ValueError("a sparse region plan and TeaCache or guidance reuse (enabled or measuring) exclude each other: their cached "
                          "residual / direction covers all token rows of a step, a sparse step computes the active ones only")
@@ -595,22 +634,28 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     s_plan, s_forced = None, set()
     if hasattr(transformer, "sparse_report"):
         transformer.sparse_report = None
-    if sr is not None and region is not None:
+    s_ids = s_tokens = s_full = None
+    if sr is not None and (region is not None or detecting):
         from . import sparse_region as _sr
-        eng = transformer.engine()
-        eng.sparse_check()
+        transformer.engine().sparse_check()
+
+    def sparse_setup(w, forced, T_s):
+        """The plan, the active ids and the engine's cache for the weights w, at T_s latent frames (outside any capture)."""
+        ids, _ = _sr.active_tokens(w, T_s, sr.margin)  # (the one device-to-host read: the latent weights)
+        tokens = T_s * (latents.shape[3] // 2) * (latents.shape[4] // 2)
+        full = ids.numel() >= tokens or ids.numel() % _sr.PAD != 0  # the whole grid: nothing to leave out
+        plan_ = _sr.plan(len(scheduler.timesteps), sr, forced, full=full)
+        transformer.sparse_report = _sr.report(plan_, ids.numel(), tokens)
+        if "sparse" in plan_:
+            transformer.engine().sparse_begin(ids, latents.shape[0] * (2 if cfg_inputs is not None else 1), T_s, latents.shape[3], latents.shape[4])
+        return plan_, ids, tokens, full
+
+    if sr is not None and region is not None:
         n_steps = len(scheduler.timesteps)
         truncates = enable_temporal_reasoning and 0 <= int(num_temporal_reasoning_steps) < n_steps
         if enable_temporal_reasoning:  # every step up to and including the truncation step: the cache is never built at the 8-frame shape
             s_forced = set(range(min(int(num_temporal_reasoning_steps), n_steps - 1) + 1))
-        T_s = 2 if truncates else latents.shape[2]
-        s_ids, _ = _sr.active_tokens(region_state.w, T_s, sr.margin)  # (the one device-to-host read: the latent weights)
-        s_tokens = T_s * (latents.shape[3] // 2) * (latents.shape[4] // 2)
-        s_full = s_ids.numel() >= s_tokens or s_ids.numel() % _sr.PAD != 0  # the whole grid: nothing to leave out
-        s_plan = _sr.plan(n_steps, sr, s_forced, full=s_full)
-        transformer.sparse_report = _sr.report(s_plan, s_ids.numel(), s_tokens)
-        if "sparse" in s_plan:
-            eng.sparse_begin(s_ids, latents.shape[0] * (2 if cfg_inputs is not None else 1), T_s, latents.shape[3], latents.shape[4])
+        s_plan, s_ids, s_tokens, s_full = sparse_setup(region_state.w, s_forced, 2 if truncates else latents.shape[2])
     graphed = None
     if use_graph and not _capturable(transformer):
         use_graph = False  # a step with torch.distributed exchanges runs eagerly (GraphedDenoiser says why); the pipeline default stays use_graph=True
@@ -629,6 +674,9 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                 scheduler.last_sample = scheduler.last_sample[:, :, [0, -1]].contiguous()
             if region_state is not None and region_state.eps.shape[-3] != latents.shape[-3]:
                 region_state.truncate()
+            if auto_z is not None and auto_z.shape[-3] != latents.shape[-3]:  # sliced exactly as the latents are
+                auto_z = auto_z[:, :, [0, -1]].contiguous()
+                auto_eps = None if auto_eps is None else auto_eps[:, :, [0, -1]].contiguous()
         kind = None if g_plan is None else g_plan[i]
         if g_plan is not None:
             if g_table is not None:  # measuring: a ring of the last A directions of this latent shape
@@ -693,6 +741,25 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                 transformer._tea_mode = None  # a forward outside the loop runs the whole model
         if region_state is not None and not use_graph:  # (every eager branch above; a graphed step blends inside its graph)
             region_state.blend(latents, i)
+        if auto_table is not None:  # measuring: this step's change map into its row of the table
+            from . import ops as _ops
+            _ops.auto_region_change(scheduler.model_outputs[-1], auto_z, -1, out=auto_table[i])
+        elif detecting and i == auto_k:
+            # the detection: four passes on the estimate of the final image the step kernel just wrote, one read, the decision
+            from . import region as _rg
+            a_w, a_mask, a_w_cpu, a_thr, a_dmax = _ar.detect(scheduler.model_outputs[-1], auto_z, a_cfg)
+            ok, why, frac = _ar.decide(a_w_cpu, a_cfg, sr.margin if sr is not None else 0)
+            auto.report = transformer.auto_region_report = _ar.report(i, a_thr, a_dmax, frac, ok, why, a_w_cpu)
+            if ok:
+                region_state = _rg.RegionState(a_w, auto_z, auto_eps, _rg.sigma_next_table(scheduler, latents.device),
+                                               bf16_state=scheduler.trajectory_dtype == torch.bfloat16)
+                auto.mask_u8 = a_mask
+                region_state.blend(latents, i)  # the blend after step k itself
+                graphed = None  # a region is a different warm shape, and every later step ends with the blend
+                if sr is not None:
+                    s_forced = set(range(i + 1))  # every step up to here ran dense: step k + 1 is the first refresh
+                    s_plan, s_ids, s_tokens, s_full = sparse_setup(a_w_cpu, s_forced, latents.shape[2])
+            auto_z = auto_eps = None
         if kind == "pair":
             delta_valid = True
         elif kind == "off":
@@ -738,6 +805,9 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
         if keep_deltas:
             m["deltas"] = [d.cpu() for d in g_kept]
         transformer.guidance_measurement = m
+    if auto_table is not None:
+        transformer.auto_region_measurement = {"timesteps": [int(v) for v in scheduler.timesteps.tolist()],
+                                               "steps": _ar.measurement(auto_table.cpu(), a_cfg)}  # the one read of the table
     return latents
 
 
@@ -850,6 +920,8 @@ class ChronoEditPipeline:
         # (image_io.py, bit-equal to the host path); arrays, tensors, "np" and "pt" keep the host code.  enable_device_image_io(False): A/B.
         self.device_image_io = True
         self._edit_region = None  # (mask or list of masks, composite) while set_edit_region is in force
+        self._auto_region_measure = None  # the detector options while measure_auto_region runs
+        self.auto_region_report = None  # the last call's auto-region report (a list of them for a call with several samples); None without a detection
 
     # -- properties of the reference pipeline (:458-478) ---------------------------------------------------------------
     @property
@@ -1122,6 +1194,56 @@ class ChronoEditPipeline:
         self.transformer.disable_sparse_region()
         return self
 
+    # Automatic edit regions (chronoedit_amd/auto_region.py): an edit without a mask finds its own region.  Off by default; an explicit
+    # `set_edit_region` mask wins
+    def enable_auto_region(self, detect_step: int, threshold="otsu", floor: float = 0.0, dilate: int = 1, feather: int = 1,
+                           max_area: float = 0.5, composite: bool = True):
+        """Behind step `detect_step` the model's estimate of the final image is compared with the source latents (one more VAE encode per
+        call, as for an explicit region), the difference thresholded ("otsu", or a number in RMS units of the normalised latents; `floor`
+        bounds Otsu's from below), dilated by `dilate` cells and feathered over `feather`; when the region covers at most `max_area` of
+        the grid the edit continues as a region-limited one - with `enable_sparse_region`, as a sparse one - and with `composite` the
+        source is pasted back behind the decode.  Otherwise it stays the plain edit.  `auto_region_report` tells what happened; its
+        "mask" can be repainted and handed to `set_edit_region`."""
+        self.transformer.enable_auto_region(detect_step, threshold, floor, dilate, feather, max_area, composite)
+        return self
+
+    def disable_auto_region(self):
+        self.transformer.disable_auto_region()
+        return self
+
+    def _auto_region_config(self):
+        """(config, measuring) of the next edit without an explicit region; (None, False): the detector is off."""
+        if self._auto_region_measure is not None:
+            return self._auto_region_measure, True
+        return getattr(self.transformer, "_auto_region", None), False
+
+    def measure_auto_region(self, edits, num_inference_steps: int, guidance_scale: float = 5.0, **options):
+        """How early the region of an edit shows on the loaded checkpoint: what tells which `detect_step`, threshold and `max_area` suit
+        it.  edits: a list of keyword dicts as `calibrate_teacache` takes them; options: the detector's (threshold, floor, dilate, feather,
+        max_area), anything else is added to every edit.  Each edit runs the plain loop - the latents are the plain loop's - and every
+        step also writes its change map into a [steps, h, w] device table, read back once after the last step.  Returns per edit
+        {"timesteps", "steps": per step {"step", "threshold", "active_fraction", "iou" (of that step's seed set with the last step's)},
+        "latents"}.  The detector itself is NOT switched on, an enabled one and an edit region are ignored here."""
+        import inspect
+        from . import auto_region as _ar
+        det = {k: options.pop(k) for k in ("threshold", "floor", "dilate", "feather", "max_area") if k in options}
+        cfg = _ar.AutoRegionConfig(detect_step=0, **det)
+        tensor_args = set(inspect.signature(self.edit_tensors).parameters)
+        embeds = {"prompt_embeds", "negative_prompt_embeds", "image_embeds"}
+        out, saved = [], self._edit_region
+        self._auto_region_measure, self._edit_region = cfg, None
+        try:
+            for kw in edits:
+                kw = dict(options, **kw, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, output_type="latent")
+                self.transformer.auto_region_measurement = None
+                res = (self.edit_tensors if embeds <= set(kw) <= tensor_args else self.__call__)(**kw)
+                if self.transformer.auto_region_measurement is None:
+                    raise RuntimeError("measure_auto_region: the edit was not measured")
+                out.append(dict(self.transformer.auto_region_measurement, latents=res if isinstance(res, torch.Tensor) else res.frames))
+        finally:
+            self._auto_region_measure, self._edit_region = None, saved
+        return out
+
     def measure_guidance_reuse(self, edits, num_inference_steps: int, max_age: int = 3, guidance_scale: float = 5.0, keep_deltas: bool = False,
                                **call_kwargs):
         """How fast the guidance direction bf16(c - u) moves on the loaded checkpoint: what tells how large `pair_every` may be.  edits: a
@@ -1316,6 +1438,15 @@ class ChronoEditPipeline:
         if self._edit_region is not None:
             regions = self._region_setup(self._edit_region[0], img, num_frames)  # one more VAE encode, of the condition encode's shape
         n_img = img.shape[0]
+        self.auto_region_report = None
+        autos = None  # per sample: the auto_region.AutoRegion the loop fills in
+        a_cfg, a_measure = self._auto_region_config()
+        if regions is None and a_cfg is not None:
+            from . import auto_region as _ar
+            from . import region as _rg
+            z_all = _rg.static_source_latents(self.vae, img, num_frames)  # one more VAE encode, as for an explicit region
+            src_of = lambda b: b // num_videos_per_prompt if n_img > 1 else 0
+            autos = [_ar.AutoRegion(a_cfg, z_all[src_of(b):src_of(b) + 1], measure=a_measure) for b in range(B)]
         image_of = lambda b: b // num_videos_per_prompt if n_img > 1 else 0  # which image (and mask) sample b edits
         if offload_model and hasattr(self.vae, "clear_graphs"):
             self.vae.clear_graphs()  # a captured encode graph pins its activation pool next to the 14B DiT: the low-memory mode drops it
@@ -1354,7 +1485,9 @@ class ChronoEditPipeline:
                                     num_inference_steps, guidance_scale, enable_temporal_reasoning, num_temporal_reasoning_steps,
                                     use_graph=self.use_graph, on_step_end=on_step_end, interrupted=lambda: self._interrupt,
                                     graph_warm=self._graph_warm, region=None if regions is None else regions[image_of(b)][1],
-                                    **self._measure_kwargs()))
+                                    auto_region=None if autos is None else autos[b], **self._measure_kwargs()))
+        if autos is not None and not autos[0].measure:
+            self.auto_region_report = autos[0].report if B == 1 else [a.report for a in autos]
         latents = done[0] if B == 1 else torch.cat(done, dim=0)
         if offload_model and self.transformer is not None:
             self.transformer.cpu()
@@ -1372,6 +1505,13 @@ class ChronoEditPipeline:
                 from . import region as _rg
                 video = video.to(device)
                 video = torch.cat([_rg.composite(video[b:b + 1], img[image_of(b):image_of(b) + 1], regions[image_of(b)][0])
+                                   for b in range(video.shape[0])], dim=0)
+            elif autos is not None and autos[0].config.composite and any(a.mask_u8 is not None for a in autos):
+                # the same paste-back with the detected masks; a sample whose detection was declined keeps its decoded frames
+                from . import region as _rg
+                video = video.to(device)
+                video = torch.cat([video[b:b + 1].float() if autos[b].mask_u8 is None else
+                                   _rg.composite(video[b:b + 1], img[image_of(b):image_of(b) + 1], autos[b].mask_u8)
                                    for b in range(video.shape[0])], dim=0)
             if self.device_image_io and output_type == "pil" and video.is_cuda and video.dtype in (torch.bfloat16, torch.float32):
                 video = image_io.frames_to_pil(video)
@@ -1408,12 +1548,23 @@ class ChronoEditPipeline:
             from . import region as _rg
             mask_u8 = _rg.normalize_mask(region_mask, H, W).to(image.device)
             region = _rg.RegionConfig(w=_rg.latent_weights(mask_u8), z_src=_rg.static_source_latents(self.vae, image, num_frames))
+        auto = None
+        self.auto_region_report = None
+        a_cfg, a_measure = self._auto_region_config()
+        if region is None and a_cfg is not None:
+            from . import auto_region as _ar
+            from . import region as _rg
+            auto = _ar.AutoRegion(a_cfg, _rg.static_source_latents(self.vae, image, num_frames), measure=a_measure)
         latents = denoise(self.transformer, self.scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
                           num_inference_steps, guidance_scale, enable_temporal_reasoning, num_temporal_reasoning_steps,
-                          use_graph=self.use_graph, graph_warm=self._graph_warm, region=region, **self._measure_kwargs())
+                          use_graph=self.use_graph, graph_warm=self._graph_warm, region=region, auto_region=auto, **self._measure_kwargs())
+        if auto is not None and not auto.measure:
+            self.auto_region_report = auto.report
         if output_type == "latent":
             return latents
         video = decode_latents(self.vae, latents, enable_temporal_reasoning, num_temporal_reasoning_steps)
         if region is not None and composite:
             video = _rg.composite(video, image.to(torch.bfloat16), mask_u8)
+        elif auto is not None and auto.mask_u8 is not None and auto.config.composite and composite:
+            video = _rg.composite(video, image.to(torch.bfloat16), auto.mask_u8)
         return video

@@ -222,6 +222,9 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         self._sparse_region = None  # sparse region edits (chronoedit_amd/sparse_region.py): a SparseRegionConfig once enable_sparse_region() was called
         self._sparse_mode = None    # per forward, set by the denoising loop: None = off (the plain forward), "refresh" or "sparse"
         self.sparse_report = None   # {"plan", "compute", "refresh", "sparse", "active", "tokens"} of the last edit that ran with a sparse region plan
+        self._auto_region = None    # automatic edit regions (chronoedit_amd/auto_region.py): an AutoRegionConfig once enable_auto_region() was called
+        self.auto_region_report = None  # {"step", "threshold", "dmax", "active_fraction", "accepted", "reason", "w", "mask"} of the last edit that looked for its region
+        self.auto_region_measurement = None  # {"timesteps", "steps"} of the last edit measured with denoise(auto_region=AutoRegion(measure=True))
 
     # -- reference-compatible helpers --------------------------------------------------
     @property
@@ -456,6 +459,19 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         self._sparse_mode = None
         if self._engine is not None:
             self._engine.sparse_drop()
+        return self
+
+    def enable_auto_region(self, detect_step: int, threshold="otsu", floor: float = 0.0, dilate: int = 1, feather: int = 1,
+                           max_area: float = 0.5, composite: bool = True):
+        """Automatic edit regions (chronoedit_amd/auto_region.py): an edit without an explicit region looks for its own behind step
+        `detect_step` and, when it finds one, continues as a region-limited edit (`pipeline.denoise(auto_region=)`; the pipeline supplies
+        the source latents).  Off by default; an explicit region wins."""
+        from .auto_region import AutoRegionConfig
+        self._auto_region = AutoRegionConfig(detect_step, threshold, floor, dilate, feather, max_area, composite)
+        return self
+
+    def disable_auto_region(self):
+        self._auto_region = None
         return self
 
     def disable_teacache(self):

@@ -535,6 +535,28 @@ int ce_region_blend_f32(float* x, const float* z_src, const float* eps, const fl
 int ce_region_composite(const void* v, int v_is_bf16, const void* src, const void* mask, float* out, int B, int F, int H, int W,
                         hipStream_t stream);
 
+/* ---- automatic edit regions (csrc/ce_region_auto.hip; chronoedit_amd/auto_region.py): the region of an instruction-only edit, found from the
+ * model's estimate of the final image after a few dense steps.  Every fp32 operation below is rounded on its own (no contraction); each pass
+ * is bit-equal to the torch expression of auto_region.py.
+ * ce_auto_region_change_f32: x0, z_src = fp32 [B][C][T][h][w] (contiguous), d = fp32 [h][w], on latent frame `frame` alone:
+ *     d[y][x] = max over b of ((sum over c = 0..C-1, in that order, of (x0 - z_src)^2) / float(C));  a NaN stays a NaN.
+ * ce_auto_region_otsu_f32: d = fp32 [n] (>= 0 or NaN) -> *thr, and *dmax when dmax is not NULL.  dmax = max(d) (NaNs ignored);
+ *   scale = 256.0f / dmax;  bin = min(255, int(d * scale)), a NaN in bin 0;  t = the lowest arg-max over the t in 0..255 with 0 < w0 < n of
+ *   (s0 n - S w0)^2 / (w0 (n - w0)) - w0, s0 = the cumulative count and sum of i n_i through bin t, S = s0 of bin 255; integers, the
+ *   expression in float64 - or 0 when no t qualifies;  *thr = max(float(t + 1) * (dmax / 256.0f), floor * floor).  dmax == 0: *thr = +inf.
+ *   One workgroup; n < 2^24, floor >= 0.
+ * ce_auto_region_ramp_f32: seed = d > *thr (thr in device memory);  w[y][x] = ramp(r), r = the smallest Chebyshev distance to a seed within
+ *   R = dilate + feather <= 8 cells (0 when there is none; cells outside the grid are no seeds): ramp(r) = 1.0f for r <= dilate, else
+ *   float(feather + 1 - (r - dilate)) / float(feather + 1).  d and w = fp32 [h][wl], not the same buffer.
+ * ce_auto_region_mask_u8: w = fp32 [h][wl] -> mask = uint8 [8 h][8 wl], byte = rint(255.0f * w[Y / 8][X / 8]) (half to even, clamped to
+ *   0..255): what ce_region_composite and ce_region_weights_u8 take; w in {0, 1} comes back from the latter unchanged.
+ * No state, no scratch, nothing allocated, no host read: every call is capturable.  fp32 pointers 4-byte aligned. */
+int ce_auto_region_change_f32(const float* x0, const float* z_src, float* d, int B, int C, int T, int h, int w, int frame,
+                              hipStream_t stream);
+int ce_auto_region_otsu_f32(const float* d, int n, float floor_v, float* thr, float* dmax, hipStream_t stream);
+int ce_auto_region_ramp_f32(const float* d, const float* thr, float* w, int h, int wl, int dilate, int feather, hipStream_t stream);
+int ce_auto_region_mask_u8(const float* w, void* mask, int h, int wl, hipStream_t stream);
+
 /* ---- sparse region edits (csrc/ce_sparse.hip; chronoedit_amd/sparse_region.py): the gather / scatter layer of a step that runs the DiT on
  * the Na ACTIVE token rows per sample only.  ids = Na sorted, unique token indices in [0, N) - int32, or int64 when ids_i64 != 0 - in device
  * memory, the same for every sample; the host validates them once per edit, and an id outside [0, N) is skipped by every pass.
