@@ -103,6 +103,17 @@ __device__ __forceinline__ float mul_then_add(float y, float g, float r) {
   return r + t;
 }
 
+// ---- PIL's 8-bit resampler (ce_image.hip, ce_focus.hip): coefficients are fixed point with 22 fractional bits
+#define CE_RESAMPLE_BITS 22
+
+// clip(ss >> 22, 0, 255) with an arithmetic shift, written as a clamp of ss followed by a logical shift (the same value: the shift is
+// monotonic).  The shift-then-clamp form of two neighbouring bytes is matched by hipcc to v_ashr_pk_u8_i32, whose result it then ORs with
+// the upper two bytes as if bits 16-31 were zero; on the MI355X they were not (bytes 2 and 3 of every packed dword came out OR-ed with
+// stale register bits).  This form keeps the instruction out of the files that use it.
+__device__ __forceinline__ uint32_t resample_clip8(int ss) {
+  return (uint32_t)min(max(ss, 0), (256 << CE_RESAMPLE_BITS) - 1) >> CE_RESAMPLE_BITS;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -14,16 +14,6 @@
 // row geometry keeps them aligned (a launch-uniform flag) and every other launch runs the byte-wise body.
 #include "ce_common.h"
 
-#define CE_RESAMPLE_BITS 22
-
-// clip(ss >> 22, 0, 255) with an arithmetic shift, written as a clamp of ss followed by a logical shift (the same value: the shift is
-// monotonic).  The shift-then-clamp form of two neighbouring bytes is matched by hipcc to v_ashr_pk_u8_i32, whose result it then ORs with
-// the upper two bytes as if bits 16-31 were zero; on the MI355X they were not (bytes 2 and 3 of every packed dword came out OR-ed with
-// stale register bits).  This form keeps the instruction out of the file.
-__device__ __forceinline__ uint32_t resample_clip8(int ss) {
-  return (uint32_t)min(max(ss, 0), (256 << CE_RESAMPLE_BITS) - 1) >> CE_RESAMPLE_BITS;
-}
-
 // Horizontal pass: src [H][in_w][3] -> dst [H][out_w][3].  One lane per output pixel (three consecutive output bytes, lanes of a wave
 // cover one contiguous run of an output row); its taps are count consecutive source pixels: overlapping windows that the L1 / L2 serve.
 __global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int in_w, int out_w,

@@ -24,7 +24,7 @@ import torch
 
 from . import ops
 
-LANCZOS, BICUBIC = "lanczos", "bicubic"
+LANCZOS, BICUBIC, BILINEAR = "lanczos", "bicubic", "bilinear"
 PRECISION_BITS = 32 - 8 - 2  # PIL's Resample.c: coefficients of the 8-bit passes are fixed point with 22 fractional bits
 
 
@@ -52,7 +52,15 @@ def _bicubic(x: float) -> float:
     return 0.0
 
 
-_FILTERS = {LANCZOS: (_lanczos, 3.0), BICUBIC: (_bicubic, 2.0)}
+def _bilinear(x: float) -> float:
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return 1.0 - x
+    return 0.0
+
+
+_FILTERS = {LANCZOS: (_lanczos, 3.0), BICUBIC: (_bicubic, 2.0), BILINEAR: (_bilinear, 1.0)}
 
 
 def resize_tables(in_len: int, out_len: int, filter: str) -> Tuple[List[List[int]], List[Tuple[int, int]], int]:
@@ -146,15 +154,21 @@ def vae_table(device=None) -> torch.Tensor:
     return lut if device is None else lut.to(device)
 
 
+def vae_lut(device) -> torch.Tensor:
+    """vae_table on the device, made once per device."""
+    lut = _VAE_LUT.get(str(device))
+    if lut is None:
+        lut = _VAE_LUT[str(device)] = vae_table(device)
+    return lut
+
+
 def preprocess_pil(images, height: int, width: int, device) -> torch.Tensor:
     """pipeline.preprocess_image(images, height, width).to(device, bfloat16) for a PIL image or a list of them: bf16 [B, 3, height, width]."""
     imgs = _pil_list(images)
     if imgs is None:
         raise ValueError("preprocess_pil takes a PIL image or a list of PIL images")
     device = torch.device(device)
-    lut = _VAE_LUT.get(str(device))
-    if lut is None:
-        lut = _VAE_LUT[str(device)] = vae_table(device)
+    lut = vae_lut(device)
     out = torch.empty((len(imgs), 3, height, width), dtype=torch.bfloat16, device=device)
     for b, im in enumerate(imgs):
         ops.image_u8_lut_planar(resize_u8(upload_rgb(im, device), (width, height), LANCZOS), lut, out[b])

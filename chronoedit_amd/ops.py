@@ -895,6 +895,58 @@ def region_composite(video: torch.Tensor, src: torch.Tensor, mask: torch.Tensor,
     return out
 
 
+# ---- focused region edits (csrc/ce_focus.hip) ---------------------------------------------------------------------------
+def focus_resample_l8(src: torch.Tensor, axis: int, coeff: torch.Tensor, bounds: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """One 1-D pass of PIL's 8-bit resampler over single-channel bytes: src uint8 [H, W] with unit inner stride and ANY row stride >= W (a
+    crop of a larger mask is a view, not a copy) -> a contiguous [H, out] (axis 0, horizontal) or [out, W] (axis 1, vertical); coeff and
+    bounds as image_resample_u8 takes them."""
+    _dev(src, torch.uint8, "src"), _dev(coeff, torch.int32, "coeff"), _dev(bounds, torch.int32, "bounds")
+    if src.dim() != 2 or src.stride(1) != 1 or src.stride(0) < src.shape[1]:
+        raise ValueError(f"src: need an [H, W] tensor with unit inner stride and a row stride >= W, got shape {tuple(src.shape)} stride {src.stride()}")
+    if axis not in (0, 1):
+        raise ValueError(f"axis: 0 (horizontal) or 1 (vertical), got {axis}")
+    H, W = src.shape
+    n, ksize = coeff.shape
+    if not (coeff.is_contiguous() and bounds.is_contiguous()) or bounds.shape != (n, 2):
+        raise ValueError(f"coeff / bounds: need contiguous [out, ksize] and [out, 2], got {tuple(coeff.shape)} and {tuple(bounds.shape)}")
+    shape = (H, n) if axis == 0 else (n, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+    _dev(out, torch.uint8, "out")
+    assert out.is_contiguous() and tuple(out.shape) == shape and out.data_ptr() != src.data_ptr()
+    st = _prof_begin()
+    _check(lib().ce_focus_resample_l8(_ptr(src), src.stride(0), _ptr(out), axis, H, W, n, _ptr(coeff), _ptr(bounds), ksize, _stream()),
+           "ce_focus_resample_l8")
+    _prof_end(st, f"focus_resample_{'hv'[axis]}_{H}x{W}_{n}", float(src.numel() + out.numel()))
+    return out
+
+
+def focus_paste_u8(edit: torch.Tensor, src: torch.Tensor, mask: Optional[torch.Tensor], left: int, top: int, out: Optional[torch.Tensor] = None):
+    """Image.paste(edit[f], (left, top), mask) into a copy of src, for every frame: edit uint8 [F, bh, bw, 3], src uint8 [SH, SW, 3], mask
+    uint8 [SH, SW] at the SOURCE's size or None (the whole box is replaced) -> a new uint8 [F, SH, SW, 3]."""
+    _dev(edit, torch.uint8, "edit"), _dev(src, torch.uint8, "src")
+    if edit.dim() != 4 or edit.shape[3] != 3 or not edit.is_contiguous():
+        raise ValueError(f"edit: need a contiguous [F, bh, bw, 3] tensor, got shape {tuple(edit.shape)} stride {edit.stride()}")
+    if src.dim() != 3 or src.shape[2] != 3 or not src.is_contiguous():
+        raise ValueError(f"src: need a contiguous [SH, SW, 3] tensor, got shape {tuple(src.shape)} stride {src.stride()}")
+    F, bh, bw, _ = edit.shape
+    SH, SW, _ = src.shape
+    if mask is not None:
+        _dev(mask, torch.uint8, "mask")
+        if tuple(mask.shape) != (SH, SW) or not mask.is_contiguous():
+            raise ValueError(f"mask: need a contiguous [{SH}, {SW}] tensor, got shape {tuple(mask.shape)} stride {mask.stride()}")
+    if left < 0 or top < 0 or left + bw > SW or top + bh > SH:
+        raise ValueError(f"the {bw}x{bh} box at ({left}, {top}) does not lie inside the {SW}x{SH} source")
+    if out is None:
+        out = torch.empty((F, SH, SW, 3), dtype=torch.uint8, device=src.device)
+    _dev(out, torch.uint8, "out")
+    assert out.is_contiguous() and tuple(out.shape) == (F, SH, SW, 3) and out.data_ptr() not in (edit.data_ptr(), src.data_ptr())
+    st = _prof_begin()
+    _check(lib().ce_focus_paste_u8(_ptr(edit), _ptr(src), _ptr(mask), _ptr(out), F, SH, SW, int(left), int(top), bw, bh, _stream()), "ce_focus_paste_u8")
+    _prof_end(st, f"focus_paste_{F}x{SH}x{SW}", float(out.numel() + src.numel() + edit.numel()))
+    return out
+
+
 # ---- automatic edit regions (csrc/ce_region_auto.hip) ------------------------------------------------------------------
 def _f32c(t: torch.Tensor, name: str):
     _dev(t, torch.float32, name)

@@ -922,6 +922,8 @@ class ChronoEditPipeline:
         self._edit_region = None  # (mask or list of masks, composite) while set_edit_region is in force
         self._auto_region_measure = None  # the detector options while measure_auto_region runs
         self.auto_region_report = None  # the last call's auto-region report (a list of them for a call with several samples); None without a detection
+        self._region_focus = None  # the context fraction while enable_region_focus is in force
+        self.focus_report = None  # the last call's focus plans, one dict per image (focus.plan); None when focus did not run
 
     # -- properties of the reference pipeline (:458-478) ---------------------------------------------------------------
     @property
@@ -1087,10 +1089,12 @@ class ChronoEditPipeline:
                      image_embeds=None, callback_on_step_end_tensor_inputs=None):
         """:332-390, message for message - with ONE rule relaxed: the reference rejects `image` together with `image_embeds`
         although its own `__call__` needs `image` for `prepare_latents`, which makes `image_embeds` unusable there; here
-        both may be given (the embeds then skip the CLIP encoder)."""
+        both may be given (the embeds then skip the CLIP encoder).  A non-empty list of PIL images is taken as well (one image per
+        prompt, as a batched tensor is: what preprocessing and the CLIP path already handle, and a focused region edit of several photos
+        needs - their sizes may differ)."""
         if image is None and image_embeds is None:
             raise ValueError("Provide either `image` or `prompt_embeds`. Cannot leave both `image` and `image_embeds` undefined.")
-        if image is not None and not isinstance(image, torch.Tensor) and not _is_pil(image):
+        if image is not None and not isinstance(image, torch.Tensor) and not _is_pil(image) and image_io._pil_list(image) is None:
             raise ValueError(f"`image` has to be of type `torch.Tensor` or `PIL.Image.Image` but is {type(image)}")
         if height % 16 != 0 or width % 16 != 0:
             raise ValueError(f"`height` and `width` have to be divisible by 16 but are {height} and {width}.")
@@ -1275,7 +1279,8 @@ class ChronoEditPipeline:
         """mask: ONE mask for every image of the next calls, or a list with one mask per image - a PIL image, a numpy / torch bool or uint8
         array [height, width], or a float array in [0, 1] (region.normalize_mask; 255 = edit here, 0 = keep the source, greys are weights).
         Stays set until `clear_edit_region()`.  composite: also paste the source back in pixel space behind the decode (the returned
-        frames then carry the source's bytes exactly where the mask is 0); False: the latent-space blend alone."""
+        frames then carry the source's bytes exactly where the mask is 0); False: the latent-space blend alone.
+        With `enable_region_focus()` the mask is taken at the SOURCE image's size and the edit runs on a crop around it."""
         if mask is None:
             raise ValueError("set_edit_region needs a mask (clear_edit_region() switches the region off)")
         self._edit_region = (list(mask) if isinstance(mask, (list, tuple)) else mask, bool(composite))
@@ -1284,6 +1289,91 @@ class ChronoEditPipeline:
     def clear_edit_region(self):
         self._edit_region = None
         return self
+
+    # Focused region edits (chronoedit_amd/focus.py): crop to the mask, edit the crop, paste back at the source's size.  Off by default
+    def enable_region_focus(self, context: float = 0.25):
+        """While an edit region is set (`set_edit_region`, its mask now at the SOURCE image's size - a PIL mask of another size is resized
+        to it, an array or tensor must be [source height, source width]), every call crops a box of the edit's aspect ratio around the
+        mask's bounding box, padded by `context` times its longer side (focus.focus_box), edits the crop at width x height as an ordinary
+        region edit - sparse steps, TeaCache, guidance reuse, temporal reasoning and graph replay compose and refuse as they do there -
+        and pastes every returned frame, scaled back to the box, into the untouched source: "pil" frames have the SOURCE's size, "np" /
+        "pt" carry the same bytes / 255 (the sources of one call must then share a size), "latent" returns the crop's latents.
+        composite=True pastes through the source-size mask (the source's bytes exactly where it is 0), composite=False replaces the whole
+        box.  `image` must be PIL, one or a list (a ValueError otherwise: an array has no full-resolution bytes to paste into).
+        `focus_report` holds one dict per image afterwards (focus.plan shows the same before an edit is spent).
+        No effect without an explicit mask: with only `enable_auto_region` the call is the plain call - a detected mask arrives mid-edit,
+        which is too late to re-crop."""
+        from . import focus as _fc
+        _fc.focus_box(None, (1, 1), (1, 1), context)  # (validates the context)
+        self._region_focus = float(context)
+        return self
+
+    def disable_region_focus(self):
+        self._region_focus = None
+        return self
+
+    def _focus_setup(self, image, height: int, width: int, device, output_type):
+        """Per image of a focused call: {"image", "box", "mask_u8" (host, source size), "report"} and, on the device path, "src_u8" (the
+        photo's bytes) and "mask_dev" - both uploaded once."""
+        from . import focus as _fc
+        imgs = image_io._pil_list(image) if image is not None else None
+        if imgs is None:
+            raise ValueError("region focus needs PIL input (one image or a list): an array or tensor `image` has no full-resolution bytes to "
+                             "paste the edit back into - pass PIL images, or disable_region_focus()")
+        if output_type in ("np", "pt") and len({im.size for im in imgs}) > 1:
+            raise ValueError(f"region focus returns frames of the sources' sizes {[im.size for im in imgs]}: output_type={output_type!r} "
+                             'needs sources of one size, use "pil"')
+        on_device = self.device_image_io and torch.device(device).type == "cuda"
+        plans = []
+        for im, m in zip(imgs, _fc.masks_for(self._edit_region[0], len(imgs))):
+            report, mask_u8 = _fc._plan(im.size, m, height, width, self._region_focus)
+            p = {"image": im, "box": report["box"], "mask_u8": mask_u8, "report": report}
+            if on_device:
+                p["src_u8"], p["mask_dev"] = image_io.upload_rgb(im, device), mask_u8.to(device)
+            plans.append(p)
+        return plans
+
+    def _focus_inputs(self, plans, height: int, width: int, device):
+        """(img bf16 [n, 3, height, width] as preprocessing leaves it, the edit-size region masks uint8 [height, width] on the device) of
+        the crops: the device passes, or PIL itself (focus.host_inputs)."""
+        from . import focus as _fc
+        from . import ops
+        if "src_u8" in plans[0]:
+            img = torch.empty((len(plans), 3, height, width), dtype=torch.bfloat16, device=device)
+            masks = []
+            for j, p in enumerate(plans):
+                crop, m = _fc.device_inputs(p["src_u8"], p["mask_dev"], p["box"], width, height)
+                ops.image_u8_lut_planar(crop, image_io.vae_lut(torch.device(device)), img[j])
+                masks.append(m)
+            return img, masks
+        host = [_fc.host_inputs(p["image"], p["mask_u8"], p["box"], width, height) for p in plans]
+        img = self.preprocess_image([c for c, _ in host], height, width).to(device=device, dtype=torch.bfloat16)
+        return img, [m.to(device) for _, m in host]
+
+    def _focus_output(self, video: torch.Tensor, plans, image_of, output_type: str):
+        """The source-size paste-back of every sample's frames (reasoning frames included), in postprocess_video's layouts."""
+        import numpy as np
+        from . import focus as _fc
+        from . import ops
+        if output_type not in ("np", "pt", "pil"):
+            raise ValueError(f"{output_type} does not exist. Please choose one of ['np', 'pt', 'pil']")
+        composite = self._edit_region[1]
+        on_device = "src_u8" in plans[0] and video.is_cuda and video.dtype in (torch.bfloat16, torch.float32)
+        u8 = ops.video_to_u8(video.contiguous()) if on_device else None
+        out = []
+        for b in range(video.shape[0]):
+            p = plans[image_of(b)]
+            if on_device:
+                out.append(_fc.device_paste(u8[b], p["src_u8"], p["mask_dev"] if composite else None, p["box"]).cpu().numpy())
+            else:
+                frames = self.postprocess_video(video[b:b + 1], "pil")[0]
+                pasted = _fc.host_paste(p["image"], frames, p["mask_u8"] if composite else None, p["box"])
+                out.append(np.stack([np.asarray(f, dtype=np.uint8) for f in pasted]))
+        if output_type == "pil":
+            from PIL import Image
+            return [[Image.fromarray(f) for f in sample] for sample in out]
+        arr = np.stack(out).astype(np.float32) / 255.0  # [B, F, SH, SW, 3]
+        return arr if output_type == "np" else torch.from_numpy(arr).permute(0, 1, 4, 2, 3)
 
     def _region_setup(self, masks, img: torch.Tensor, num_frames: int):
         """masks (one, or a list with one per image of img) -> per image (uint8 mask [H, W] on the device, region.RegionConfig)."""
@@ -1417,8 +1507,17 @@ class ChronoEditPipeline:
         prompt_embeds = prompt_embeds.to(device=device, dtype=tdtype)
         if negative_prompt_embeds is not None:
             negative_prompt_embeds = negative_prompt_embeds.to(device=device, dtype=tdtype)
+        self.focus_report = None
+        focus = None  # per image: the plan of a focused region edit (chronoedit_amd/focus.py); the encoders then see the crops
+        if self._region_focus is not None and self._edit_region is not None:
+            focus = self._focus_setup(image, height, width, device, output_type)
+            self.focus_report = [p["report"] for p in focus]
         if image_embeds is None:
-            image_embeds = self.encode_image(image, device)
+            if focus is None:
+                image_embeds = self.encode_image(image, device)
+            else:  # the conditioning shows what the model edits
+                crops = [p["image"].crop(p["box"]) for p in focus]
+                image_embeds = self.encode_image(crops if isinstance(image, (list, tuple)) else crops[0], device)
         image_embeds = image_embeds.to(device=device, dtype=tdtype)
         if image_embeds.shape[0] != batch_size:
             image_embeds = image_embeds.repeat(batch_size, 1, 1)
@@ -1428,14 +1527,21 @@ class ChronoEditPipeline:
         B = batch_size * num_videos_per_prompt
         if hasattr(self.vae, "use_graph"):  # the VAE replays captured graphs from the second edit of a shape on (vae.py)
             self.vae.use_graph = bool(self.use_graph)
-        if self.device_image_io and device.type == "cuda" and (_is_pil(image) or (isinstance(image, (list, tuple)) and image and all(_is_pil(i) for i in image))):
+        focus_masks = None
+        if focus is not None:
+            img, focus_masks = self._focus_inputs(focus, height, width, device)
+        elif self.device_image_io and device.type == "cuda" and (_is_pil(image) or (isinstance(image, (list, tuple)) and image and all(_is_pil(i) for i in image))):
             img = image_io.preprocess_pil(image, height, width, device)
         else:
             img = self.preprocess_image(image, height, width).to(device=device, dtype=torch.bfloat16)
         latents, condition = self.prepare_latents(img, B, self.vae.config.z_dim, height, width, num_frames, torch.bfloat16, device,
                                                   generator, latents)
         regions = None  # per image: (uint8 mask on the device, region.RegionConfig)
-        if self._edit_region is not None:
+        if focus is not None:  # the crops' masks are made already: the same VAE encode, weights per mask
+            from . import region as _rg
+            z_src = _rg.static_source_latents(self.vae, img, num_frames)
+            regions = [(m, _rg.RegionConfig(w=_rg.latent_weights(m), z_src=z_src[j:j + 1])) for j, m in enumerate(focus_masks)]
+        elif self._edit_region is not None:
             regions = self._region_setup(self._edit_region[0], img, num_frames)  # one more VAE encode, of the condition encode's shape
         n_img = img.shape[0]
         self.auto_region_report = None
@@ -1500,7 +1606,7 @@ class ChronoEditPipeline:
                 video = self.video_guardrail_runner(video)
                 if video is None:
                     raise Exception("Guardrail blocked video2world generation.")
-            if regions is not None and self._edit_region[1]:
+            if focus is None and regions is not None and self._edit_region[1]:
                 # the paste-back: every returned frame (reasoning frames included) keeps the source where the mask says so - a new fp32 video
                 from . import region as _rg
                 video = video.to(device)
@@ -1513,7 +1619,9 @@ class ChronoEditPipeline:
                 video = torch.cat([video[b:b + 1].float() if autos[b].mask_u8 is None else
                                    _rg.composite(video[b:b + 1], img[image_of(b):image_of(b) + 1], autos[b].mask_u8)
                                    for b in range(video.shape[0])], dim=0)
-            if self.device_image_io and output_type == "pil" and video.is_cuda and video.dtype in (torch.bfloat16, torch.float32):
+            if focus is not None:  # the source-size paste replaces the edit-size composite
+                video = self._focus_output(video, focus, image_of, output_type)
+            elif self.device_image_io and output_type == "pil" and video.is_cuda and video.dtype in (torch.bfloat16, torch.float32):
                 video = image_io.frames_to_pil(video)
             else:
                 video = self.postprocess_video(video, output_type=output_type)

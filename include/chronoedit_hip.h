@@ -579,6 +579,24 @@ int ce_sparse_scatter_vt_bf16(const void* src, int lds, int src_rows, void* vt, 
 int ce_sparse_unpatchify_bf16(const void* y, int ldy, const void* ids, int ids_i64, void* out, int Cout, int T, int H, int W, int Na,
                               hipStream_t stream);
 
+/* ---- focused region edits (csrc/ce_focus.hip; chronoedit_amd/focus.py): the edit runs on a crop of the photo around the mask and is pasted
+ * back into the photo at the photo's own size.  Both passes are integer-exact, bit-equal to the installed PIL.
+ * ce_focus_resample_l8: ONE 1-D pass of PIL's 8-bit resampler over SINGLE-channel bytes: ce_image_resample_u8's tables and arithmetic
+ *   (ss = 2^21 + sum_k coeff[o][k] * src[first + k], out = clip(ss >> 22, 0, 255)).  src = src_h rows of src_w bytes, row y at
+ *   src + y * src_pitch (src_pitch >= src_w, otherwise -1): a crop of a larger image is read where it lies.  dst is contiguous:
+ *   axis 0 (horizontal) uint8 [src_h][out_len], axis 1 (vertical) uint8 [out_len][src_w].  src != dst.  With image_io.resize_tables(...,
+ *   "bilinear"), horizontal then vertical equals Image.resize(..., Image.BILINEAR) of an "L" image.
+ * ce_focus_paste_u8: edit = uint8 [F][bh][bw][3] (the frames, scaled to the box), src = uint8 [src_h][src_w][3] (the photo), mask = uint8
+ *   [src_h][src_w] at the photo's size or NULL (= 255 everywhere), out = uint8 [F][src_h][src_w][3], aliasing no input.  Outside the box
+ *   [top, top + bh) x [left, left + bw) out = src.  Inside, per byte, with m = mask[Y][X], s = src, e = edit[f][Y - top][X - left][c], in
+ *   32-bit integers:  t = s * (255 - m) + e * m + 128,  out = ((t >> 8) + t) >> 8  - Image.paste(edit, (left, top), mask).  m == 0 gives s
+ *   and m == 255 gives e exactly.  A box that leaves the image returns -1; F <= 65535.
+ * No state, no scratch, nothing allocated: every call is capturable.  An image of 2^31 bytes or more returns -2. */
+int ce_focus_resample_l8(const void* src, long long src_pitch, void* dst, int axis, int src_h, int src_w, int out_len, const int* coeff,
+                         const int* bounds, int ksize, hipStream_t stream);
+int ce_focus_paste_u8(const void* edit, const void* src, const void* mask, void* out, int F, int src_h, int src_w, int left, int top, int bw,
+                      int bh, hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
