@@ -69,12 +69,15 @@ class AutoRegion:
     """What `pipeline.denoise(auto_region=)` takes for ONE edit: the config (None: the transformer's switch decides) and z_src = fp32 source latents of the latents' shape
     (region.static_source_latents).  measure: run the plain loop and record every step's change map instead of detecting
     (`measure_auto_region`).  The loop leaves `report` (see `report`) and `mask_u8` (the device mask of an accepted region, else None)
-    here."""
+    here.  on_accept: a callable (the device mask of an accepted region) -> bool; True ends the loop behind the detecting step, with
+    `exited` set (the scout of an auto-focused edit, chronoedit_amd/autofocus.py)."""
 
-    def __init__(self, config: Optional[AutoRegionConfig], z_src: torch.Tensor, measure: bool = False):
+    def __init__(self, config: Optional[AutoRegionConfig], z_src: torch.Tensor, measure: bool = False, on_accept=None):
         self.config, self.z_src, self.measure = config, z_src, bool(measure)
         self.report: Optional[dict] = None
         self.mask_u8: Optional[torch.Tensor] = None
+        self.on_accept = on_accept
+        self.exited = False
 
 
 def detect_index(cfg: AutoRegionConfig, n_steps: int, enable_temporal_reasoning: bool = False, num_temporal_reasoning_steps: int = 0) -> Optional[int]:

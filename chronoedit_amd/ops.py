@@ -947,6 +947,50 @@ def focus_paste_u8(edit: torch.Tensor, src: torch.Tensor, mask: Optional[torch.T
     return out
 
 
+# ---- auto-focused edits (csrc/ce_autofocus.hip) -------------------------------------------------------------------------
+def autofocus_bbox_u8(mask: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """mask uint8 [H, W] with unit inner stride and ANY row stride >= W (a box's view of a larger mask is reduced where it lies) -> int32
+    [5] on the device: left, top, right, bottom (half open) of mask > 0 and the count of non-zero bytes; W, H, 0, 0, 0 for an empty mask.
+    `out` needs no initialisation.  Nothing is read back here."""
+    _dev(mask, torch.uint8, "mask")
+    if mask.dim() != 2 or mask.stride(1) != 1 or mask.stride(0) < mask.shape[1] or mask.numel() == 0:
+        raise ValueError(f"mask: need a non-empty [H, W] tensor with unit inner stride and a row stride >= W, got shape {tuple(mask.shape)} stride {mask.stride()}")
+    if out is None:
+        out = torch.empty(5, dtype=torch.int32, device=mask.device)
+    _dev(out, torch.int32, "out")
+    assert out.is_contiguous() and out.numel() == 5
+    H, W = mask.shape
+    st = _prof_begin()
+    _check(lib().ce_autofocus_bbox_u8(_ptr(mask), mask.stride(0), H, W, _ptr(out), _stream()), "ce_autofocus_bbox_u8")
+    _prof_end(st, f"autofocus_bbox_{H}x{W}", float(mask.numel()))
+    return out
+
+
+def autofocus_restart(x0: torch.Tensor, eps: torch.Tensor, tables, s: float, bf16_state: bool = False, out: Optional[torch.Tensor] = None):
+    """x0, eps fp32 [..., h, w] of one shape, tables = (ix0, ix1, fx, iy0, iy1, fy) on the device (int32 [w], int32 [w], fp32 [w], int32 [h],
+    int32 [h], fp32 [h]: autofocus.restart_tables) -> a new fp32 tensor (1 - s) * R(x0) + s * eps, R the bilinear sample through the
+    tables, every operation rounded in fp32; bf16_state: rounded to a bf16 value (fp32 storage).  One launch, no host read."""
+    _f32c(x0, "x0"), _f32c(eps, "eps")
+    if x0.dim() < 2 or tuple(eps.shape) != tuple(x0.shape) or x0.numel() == 0:
+        raise ValueError(f"x0 / eps: need two non-empty [..., h, w] tensors of one shape, got {tuple(x0.shape)} and {tuple(eps.shape)}")
+    h, w = x0.shape[-2:]
+    ix0, ix1, fx, iy0, iy1, fy = tables
+    for name, t, dt, n in (("ix0", ix0, torch.int32, w), ("ix1", ix1, torch.int32, w), ("fx", fx, torch.float32, w),
+                           ("iy0", iy0, torch.int32, h), ("iy1", iy1, torch.int32, h), ("fy", fy, torch.float32, h)):
+        _dev(t, dt, name)
+        if t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{name}: need a contiguous [{n}] table, got shape {tuple(t.shape)} stride {t.stride()}")
+    if out is None:
+        out = torch.empty_like(x0)
+    _f32c(out, "out")
+    assert out.shape == x0.shape and out.data_ptr() != x0.data_ptr()
+    st = _prof_begin()
+    _check(lib().ce_autofocus_restart_f32(_ptr(x0), _ptr(eps), _ptr(out), _ptr(ix0), _ptr(ix1), _ptr(fx), _ptr(iy0), _ptr(iy1), _ptr(fy), float(s),
+                                          x0.numel() // (h * w), h, w, int(bool(bf16_state)), _stream()), "ce_autofocus_restart_f32")
+    _prof_end(st, f"autofocus_restart_{x0.numel()}", 12.0 * x0.numel())
+    return out
+
+
 # ---- automatic edit regions (csrc/ce_region_auto.hip) ------------------------------------------------------------------
 def _f32c(t: torch.Tensor, name: str):
     _dev(t, torch.float32, name)

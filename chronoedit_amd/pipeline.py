@@ -470,7 +470,7 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
             num_inference_steps: int, guidance_scale: float = 5.0, enable_temporal_reasoning: bool = False,
             num_temporal_reasoning_steps: int = 0, use_graph: bool = False, on_step_end=None, interrupted=None, graph_warm=None,
             teacache=None, teacache_measure: bool = False, guidance_reuse=None, guidance_measure: Optional[int] = None,
-            keep_deltas: bool = False, region=None, sparse_region=None, auto_region=None):
+            keep_deltas: bool = False, region=None, sparse_region=None, auto_region=None, start_step: int = 0, start_eps=None):
     """The whole loop, including the temporal-reasoning truncation 8 -> 2 latent frames (pipeline_chronoedit.py:700-709).
     on_step_end(i, t, latents) -> replacement latents, a dict with any of latents / prompt_embeds / negative_prompt_embeds, or None
     (the reference's callback_on_step_end hook, :741-749); graph_warm: a set the caller keeps across edits - shapes already run once in
@@ -528,8 +528,21 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     `transformer.auto_region_report` and `auto_region.report` hold {"step", "threshold", "dmax", "active_fraction", "accepted", "reason",
     "w", "mask"} and `auto_region.mask_u8` the device mask of an accepted region.  auto_region.measure: every step runs the plain loop and
     writes its change map into a [steps, h, w] device table, read back once after the last step: `transformer.auto_region_measurement`
-    then holds one row per step (auto_region.measurement)."""
-    scheduler.set_timesteps(num_inference_steps, device=latents.device)
+    then holds one row per step (auto_region.measurement).  auto_region.on_accept: a callable (the device pixel mask of an accepted
+    region) -> bool, asked before anything of the region is set up; True ends the loop behind step k (its `on_step_end` still runs) with
+    `auto_region.exited` set - the scout of an auto-focused edit (chronoedit_amd/autofocus.py); False, or none: as above.
+    start_step = b > 0: the loop runs the TAIL of the schedule, steps b .. n - 1, on latents the caller has brought to sigma[b]
+    (`scheduler.set_timesteps(n, begin=b)`: the history starts empty); every plan above is made from the tail's arrays, `on_step_end` is
+    told i + b.  start_eps: the region blend's eps instead of a copy of the incoming latents - which, behind a warm start, are no longer
+    the noise.  start_step=0 is the loop as ever, launch for launch.  With temporal reasoning or a detecting auto_region a ValueError."""
+    start_step = int(start_step)
+    if start_step:
+        if enable_temporal_reasoning or (auto_region is not None and region is None):
+            raise ValueError("denoise: start_step > 0 goes with neither temporal reasoning nor a detecting auto_region (their step indices "
+                             "count from the head of the schedule)")
+        scheduler.set_timesteps(num_inference_steps, device=latents.device, begin=start_step)
+    else:
+        scheduler.set_timesteps(num_inference_steps, device=latents.device)
     latents = latents.to(torch.float32).contiguous()
     auto = auto_region if region is None else None  # an explicit mask wins
     a_cfg = None
@@ -562,7 +575,7 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
             raise NotImplementedError("an edit region with the tokens sharded over ranks or with CFG parallelism is not implemented "
                                       "(the blend runs on replicated latents; nothing sharded has been tested with it)")
         from . import region as _rg
-        region_state = _rg.RegionState.begin(region, latents, scheduler)
+        region_state = _rg.RegionState.begin(region, latents if start_eps is None else start_eps.to(latents.device), scheduler)
     sharded = getattr(transformer, "_cfgp", None) is not None or (_token_sharded(transformer) and not _sharded_batchable(transformer))
     cfg_inputs = None
     if guidance_scale > 1.0 and negative_prompt_embeds is not None and not sharded:
@@ -659,7 +672,10 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     graphed = None
     if use_graph and not _capturable(transformer):
         use_graph = False  # a step with torch.distributed exchanges runs eagerly (GraphedDenoiser says why); the pipeline default stays use_graph=True
+    exiting = False
     for i, t in enumerate(scheduler.timesteps):
+        if exiting:
+            break
         if interrupted is not None and interrupted():
             continue
         if enable_temporal_reasoning and i == num_temporal_reasoning_steps:
@@ -750,7 +766,9 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
             a_w, a_mask, a_w_cpu, a_thr, a_dmax = _ar.detect(scheduler.model_outputs[-1], auto_z, a_cfg)
             ok, why, frac = _ar.decide(a_w_cpu, a_cfg, sr.margin if sr is not None else 0)
             auto.report = transformer.auto_region_report = _ar.report(i, a_thr, a_dmax, frac, ok, why, a_w_cpu)
-            if ok:
+            if ok and auto.on_accept is not None and auto.on_accept(a_mask):
+                auto.mask_u8, auto.exited, exiting = a_mask, True, True  # the caller goes on from here (the history is as step k left it)
+            elif ok:
                 region_state = _rg.RegionState(a_w, auto_z, auto_eps, _rg.sigma_next_table(scheduler, latents.device),
                                                bf16_state=scheduler.trajectory_dtype == torch.bfloat16)
                 auto.mask_u8 = a_mask
@@ -765,7 +783,7 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
         elif kind == "off":
             delta_valid = False
         if on_step_end is not None:
-            new = on_step_end(i, t, latents)
+            new = on_step_end(i + start_step, t, latents)
             replaced = (isinstance(new, dict) and any(k in new for k in ("latents", "prompt_embeds", "negative_prompt_embeds"))) or \
                 (new is not None and not isinstance(new, dict) and new is not latents)
             if s_plan is not None and replaced and i + 1 < len(s_plan):
@@ -924,6 +942,8 @@ class ChronoEditPipeline:
         self.auto_region_report = None  # the last call's auto-region report (a list of them for a call with several samples); None without a detection
         self._region_focus = None  # the context fraction while enable_region_focus is in force
         self.focus_report = None  # the last call's focus plans, one dict per image (focus.plan); None when focus did not run
+        self._auto_focus = None  # the autofocus.AutoFocusConfig while enable_auto_focus is in force
+        self._focus_pass = None  # one shot: what the scout of an auto-focused call hands to the focused pass it starts (`_auto_focus_pass`)
 
     # -- properties of the reference pipeline (:458-478) ---------------------------------------------------------------
     @property
@@ -1302,7 +1322,7 @@ class ChronoEditPipeline:
         box.  `image` must be PIL, one or a list (a ValueError otherwise: an array has no full-resolution bytes to paste into).
         `focus_report` holds one dict per image afterwards (focus.plan shows the same before an edit is spent).
         No effect without an explicit mask: with only `enable_auto_region` the call is the plain call - a detected mask arrives mid-edit,
-        which is too late to re-crop."""
+        which is too late to re-crop; `enable_auto_focus` is the switch that starts over on the crop."""
         from . import focus as _fc
         _fc.focus_box(None, (1, 1), (1, 1), context)  # (validates the context)
         self._region_focus = float(context)
@@ -1311,6 +1331,41 @@ class ChronoEditPipeline:
     def disable_region_focus(self):
         self._region_focus = None
         return self
+
+    # Auto-focused edits (chronoedit_amd/autofocus.py): find the region on the whole photo, then edit its crop at the photo's size.  Off by default
+    def enable_auto_focus(self, context: float = 0.25, warm_start: bool = False):
+        """While `enable_auto_region` is on and no `set_edit_region` mask is set (an explicit mask wins, as ever), a call with ONE PIL
+        image first runs the auto-region call on the whole photo up to and including the detection behind step k (the scout).  Declined,
+        or a box that is the whole photo: the scout runs on to its end and the call returns exactly what the auto-region call returns,
+        `focus_report[0]["reason"]` = "declined" / "whole".  Accepted: the detected mask is lifted to the photo's size on the device, and the
+        call starts over as the focused region edit (`enable_region_focus`) of the crop around it, padded by `context`, from the SAME noise
+        (the call's one draw, or `latents=`), composite as `enable_auto_region` says: the frames have the photo's size and carry its
+        bytes wherever the mask is 0.  warm_start=False: all steps - bit for bit the call that `set_edit_region(focus_report[0]["mask"])`
+        + `enable_region_focus(context)` would make with the same `latents`.  warm_start=True: from step k + 1, on the scout's estimate of
+        the final image cropped and resampled to the crop's latent grid and noised to that step's level (autofocus.restart).
+        `focus_report[0]` holds the focus plan plus "mask" (the photo-size mask, a PIL "L" image), "detect" (the scout's auto-region
+        report) and "start_step"; `callback_on_step_end` sees the scout's steps 0..k, then the focused pass's.  An array or tensor image
+        is a ValueError; more than one sample per call, temporal reasoning and `offload_model` a NotImplementedError."""
+        from . import autofocus as _af
+        self._auto_focus = _af.AutoFocusConfig(float(context), warm_start)
+        return self
+
+    def disable_auto_focus(self):
+        self._auto_focus = None
+        return self
+
+    def _auto_focus_plan(self, image, mask_edit: torch.Tensor, height: int, width: int, device) -> dict:
+        """The scout's decision: the detected edit-size mask (on the device) -> {"go", "plan"}: the lifted mask, the box (two reductions,
+        five integers read each) and, when the box is worth cropping to, a plan as `_focus_setup` makes them."""
+        from . import autofocus as _af
+        on_device = self.device_image_io and torch.device(device).type == "cuda"
+        mask_src = _af.lift_mask(mask_edit if on_device else mask_edit.cpu(), image.size)
+        report = _af.plan(mask_src, (width, height), self._auto_focus.context)
+        p = {"image": image, "box": report["box"], "report": report, "mask_u8": None if on_device else mask_src}
+        go = _af.worth_focusing(report)
+        if go and on_device:
+            p["src_u8"], p["mask_dev"] = image_io.upload_rgb(image, device), mask_src
+        return {"go": go, "plan": p}
 
     def _focus_setup(self, image, height: int, width: int, device, output_type):
         """Per image of a focused call: {"image", "box", "mask_u8" (host, source size), "report"} and, on the device path, "src_u8" (the
@@ -1367,6 +1422,8 @@ class ChronoEditPipeline:
                 out.append(_fc.device_paste(u8[b], p["src_u8"], p["mask_dev"] if composite else None, p["box"]).cpu().numpy())
             else:
                 frames = self.postprocess_video(video[b:b + 1], "pil")[0]
+                if composite and p["mask_u8"] is None:  # (an auto-focused call keeps its lifted mask on the device)
+                    p["mask_u8"] = p["mask_dev"].cpu()
                 pasted = _fc.host_paste(p["image"], frames, p["mask_u8"] if composite else None, p["box"])
                 out.append(np.stack([np.asarray(f, dtype=np.uint8) for f in pasted]))
         if output_type == "pil":
@@ -1479,6 +1536,7 @@ class ChronoEditPipeline:
         """Same arguments, defaults, checks and return value as the reference's `__call__`.  What differs is underneath: the two
         guidance passes run as ONE batched forward, CFG + flow-UniPC are one fused launch, the latents stay fp32 on the device
         (`scheduler.trajectory_dtype = torch.bfloat16` restores the reference's bf16 rounding of latents and history)."""
+        fpass, self._focus_pass = self._focus_pass, None  # set: this is the focused pass of an auto-focused call (`_auto_focus_pass`)
         if hasattr(callback_on_step_end, "tensor_inputs"):
             callback_on_step_end_tensor_inputs = callback_on_step_end.tensor_inputs
         self.check_inputs(prompt, negative_prompt, image, height, width, prompt_embeds, negative_prompt_embeds, image_embeds,
@@ -1488,7 +1546,7 @@ class ChronoEditPipeline:
         num_frames = max(num_frames, 1)
         self._guidance_scale, self._attention_kwargs, self._current_timestep, self._interrupt = guidance_scale, attention_kwargs, None, False
         device = self._execution_device
-        if self.text_guardrail_runner is not None and not self.text_guardrail_runner(prompt):  # :621-629
+        if fpass is None and self.text_guardrail_runner is not None and not self.text_guardrail_runner(prompt):  # :621-629
             raise Exception(f"Guardrail blocked text2world generation. Prompt: {prompt}")
 
         if prompt is not None and isinstance(prompt, str):
@@ -1509,9 +1567,29 @@ class ChronoEditPipeline:
             negative_prompt_embeds = negative_prompt_embeds.to(device=device, dtype=tdtype)
         self.focus_report = None
         focus = None  # per image: the plan of a focused region edit (chronoedit_amd/focus.py); the encoders then see the crops
-        if self._region_focus is not None and self._edit_region is not None:
+        if fpass is not None:
+            focus = fpass["plans"]  # (made by the scout, the mask already on the device)
+        elif self._region_focus is not None and self._edit_region is not None:
             focus = self._focus_setup(image, height, width, device, output_type)
+        if focus is not None:
             self.focus_report = [p["report"] for p in focus]
+        # auto focus (chronoedit_amd/autofocus.py): this call is the scout, and starts the focused pass when the detection says so
+        a_focus = None
+        if fpass is None and self._auto_focus is not None and self._edit_region is None and self._auto_region_config()[0] is not None \
+                and not self._auto_region_config()[1]:
+            a_focus = self._auto_focus
+            if image is None or image_io._pil_list(image) is None:
+                raise ValueError("auto focus needs PIL input: an array or tensor `image` has no full-resolution bytes to paste the edit back "
+                                 "into - pass a PIL image, or disable_auto_focus()")
+            if batch_size * num_videos_per_prompt != 1 or len(image_io._pil_list(image)) != 1:
+                raise NotImplementedError("auto focus edits one photo per call: a list of images or prompts, or num_videos_per_prompt > 1, is not implemented")
+            if enable_temporal_reasoning:
+                raise NotImplementedError("auto focus with temporal reasoning is not implemented (the scout would run the reasoning steps "
+                                          "twice, or the focused pass would start at the truncated shape)")
+            if offload_model:
+                raise NotImplementedError("auto focus with offload_model is not implemented (the encoders leave the device before the "
+                                          "focused pass needs them)")
+        user_image_embeds = image_embeds
         if image_embeds is None:
             if focus is None:
                 image_embeds = self.encode_image(image, device)
@@ -1536,6 +1614,15 @@ class ChronoEditPipeline:
             img = self.preprocess_image(image, height, width).to(device=device, dtype=torch.bfloat16)
         latents, condition = self.prepare_latents(img, B, self.vae.config.z_dim, height, width, num_frames, torch.bfloat16, device,
                                                   generator, latents)
+        noise = latents  # (what the focused pass of an auto-focused call starts from as well)
+        start_step, start_eps = 0, None
+        if fpass is not None and fpass["start"] is not None:
+            # the warm start: the scout's estimate of the final image on the crop's latent grid, noised to the level of step k + 1
+            from . import autofocus as _af
+            st = fpass["start"]
+            start_step, start_eps = st["step"], latents.to(torch.float32)
+            tables = _af.restart_tables(focus[0]["box"], focus[0]["image"].size, tuple(latents.shape[-2:]), device)
+            latents = _af.restart(st["x0"], start_eps, tables, st["sigma"], bf16_state=self.scheduler.trajectory_dtype == torch.bfloat16)
         regions = None  # per image: (uint8 mask on the device, region.RegionConfig)
         if focus is not None:  # the crops' masks are made already: the same VAE encode, weights per mask
             from . import region as _rg
@@ -1553,6 +1640,9 @@ class ChronoEditPipeline:
             z_all = _rg.static_source_latents(self.vae, img, num_frames)  # one more VAE encode, as for an explicit region
             src_of = lambda b: b // num_videos_per_prompt if n_img > 1 else 0
             autos = [_ar.AutoRegion(a_cfg, z_all[src_of(b):src_of(b) + 1], measure=a_measure) for b in range(B)]
+            if a_focus is not None:
+                decision = {}
+                autos[0].on_accept = lambda m: decision.update(self._auto_focus_plan(image_io._pil_list(image)[0], m, height, width, device)) or decision["go"]
         image_of = lambda b: b // num_videos_per_prompt if n_img > 1 else 0  # which image (and mask) sample b edits
         if offload_model and hasattr(self.vae, "clear_graphs"):
             self.vae.clear_graphs()  # a captured encode graph pins its activation pool next to the 14B DiT: the low-memory mode drops it
@@ -1591,9 +1681,26 @@ class ChronoEditPipeline:
                                     num_inference_steps, guidance_scale, enable_temporal_reasoning, num_temporal_reasoning_steps,
                                     use_graph=self.use_graph, on_step_end=on_step_end, interrupted=lambda: self._interrupt,
                                     graph_warm=self._graph_warm, region=None if regions is None else regions[image_of(b)][1],
-                                    auto_region=None if autos is None else autos[b], **self._measure_kwargs()))
+                                    auto_region=None if autos is None else autos[b], start_step=start_step,
+                                    start_eps=None if start_eps is None else start_eps[b:b + 1], **self._measure_kwargs()))
         if autos is not None and not autos[0].measure:
             self.auto_region_report = autos[0].report if B == 1 else [a.report for a in autos]
+        if a_focus is not None:
+            if autos[0].exited:
+                k = autos[0].report["step"]
+                start = None
+                if a_focus.warm_start and k + 1 < num_inference_steps:  # (a detection behind the last step leaves no tail: cold)
+                    start = {"step": k + 1, "x0": self.scheduler.model_outputs[-1], "sigma": float(self.scheduler.sigmas[k + 1])}
+                return self._auto_focus_pass(
+                    decision["plan"], start, autos[0], a_focus, image=image, negative_prompt=None, height=height, width=width, num_frames=num_frames,
+                    num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, num_videos_per_prompt=1, generator=generator,
+                    latents=noise, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, image_embeds=user_image_embeds,
+                    output_type=output_type, return_dict=return_dict, attention_kwargs=attention_kwargs, callback_on_step_end=callback_on_step_end,
+                    callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, max_sequence_length=max_sequence_length)
+            # the scout ran to its end: the auto-region call, bit for bit
+            declined = autos[0].report is None or not autos[0].report["accepted"]
+            self.focus_report = [{"reason": "declined", "detect": autos[0].report} if declined else
+                                 dict(decision["plan"]["report"], box_reason=decision["plan"]["report"]["reason"], reason="whole", detect=autos[0].report)]
         latents = done[0] if B == 1 else torch.cat(done, dim=0)
         if offload_model and self.transformer is not None:
             self.transformer.cpu()
@@ -1634,6 +1741,26 @@ class ChronoEditPipeline:
         if not return_dict:
             return (video,)
         return WanPipelineOutput(frames=video)
+
+    def _auto_focus_pass(self, plan: dict, start: Optional[dict], auto, cfg, **call):
+        """The focused pass of an auto-focused call: the explicit-mask focused region edit of the crop (`__call__` itself, with the scout's plan
+        in place of `_focus_setup`'s), then the report's new entries."""
+        from PIL import Image
+        saved = (self._edit_region, self._region_focus)
+        mask = plan["mask_dev"] if "mask_dev" in plan else plan["mask_u8"]
+        self._edit_region, self._region_focus = (mask, bool(auto.config.composite)), cfg.context
+        self._focus_pass = {"plans": [plan], "start": start}
+        try:
+            out = self(**call)
+        finally:
+            self._focus_pass = None
+            self._edit_region, self._region_focus = saved
+        if plan["mask_u8"] is None:
+            plan["mask_u8"] = plan["mask_dev"].cpu()
+        self.auto_region_report = auto.report
+        self.focus_report = [dict(plan["report"], mask=Image.fromarray(plan["mask_u8"].numpy(), mode="L"), detect=auto.report,
+                                  start_step=0 if start is None else start["step"])]
+        return out
 
     @torch.no_grad()
     def edit_tensors(self, image: torch.Tensor, prompt_embeds: torch.Tensor, negative_prompt_embeds: Optional[torch.Tensor],

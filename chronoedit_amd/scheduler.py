@@ -157,11 +157,18 @@ class FlowUniPCMultistepScheduler:
     def step_index(self):
         return self._step_index
 
-    def set_timesteps(self, num_inference_steps: int, device=None, shift: Optional[float] = None):
+    def set_timesteps(self, num_inference_steps: int, device=None, shift: Optional[float] = None, begin: int = 0):
+        """begin > 0: the TAIL of the num_inference_steps schedule - entries begin .. n - 1 of its timesteps and sigmas - for a loop that
+        starts from a sample already at sigma[begin] (an auto-focused edit's warm start).  The coefficient table is that of the sliced
+        sigma array: the history starts empty, so the multistep order ramps up again from 1.  `num_inference_steps` then counts the tail."""
         c = self.config
         if shift is None:
             shift = c.shift
-        sig = flow_sigmas(num_inference_steps, shift, c.num_train_timesteps, c.sigma_grid)
+        begin = int(begin)
+        if not 0 <= begin < num_inference_steps:
+            raise ValueError(f"set_timesteps: begin must lie in 0..{num_inference_steps - 1}, got {begin}")
+        sig = flow_sigmas(num_inference_steps, shift, c.num_train_timesteps, c.sigma_grid)[begin:]
+        num_inference_steps -= begin
         self.timesteps = torch.from_numpy(sig * c.num_train_timesteps).to(device=device, dtype=torch.int64)
         sig_full = np.concatenate([sig, [0.0]]).astype(np.float32)
         self.sigmas = torch.from_numpy(sig_full)  # stays on the host like the reference (:240)

@@ -597,6 +597,22 @@ int ce_focus_resample_l8(const void* src, long long src_pitch, void* dst, int ax
 int ce_focus_paste_u8(const void* edit, const void* src, const void* mask, void* out, int F, int src_h, int src_w, int left, int top, int bw,
                       int bh, hipStream_t stream);
 
+/* ---- auto-focused edits (csrc/ce_autofocus.hip; chronoedit_amd/autofocus.py): an instruction-only edit finds its region on the whole photo,
+ * lifts the detected mask to the photo's size on the device and goes on as a focused region edit of the crop.
+ * ce_autofocus_bbox_u8: mask = H rows of W bytes, row y at mask + y * pitch (pitch >= W, otherwise -1: a box's view of a larger mask is
+ *   reduced where it lies) -> out = int32 [5]: left, top, right, bottom (half open) of mask > 0, then the count of non-zero bytes.  An empty
+ *   mask gives W, H, 0, 0, 0.  `out` is initialised by a leading launch of the call itself; integers only, so the result is exact and does
+ *   not depend on the launch order.  H * W < 2^31 (otherwise -2).
+ * ce_autofocus_restart_f32: x0, eps, out = fp32 [planes][h][w] (contiguous; out != x0), ix0, ix1 = int32 [w], fx = fp32 [w], iy0, iy1 =
+ *   int32 [h], fy = fp32 [h] in device memory (an index outside the grid is clamped into it).  With a00 = x0[p][iy0[y]][ix0[x]], a01 =
+ *   x0[p][iy0[y]][ix1[x]], a10 = x0[p][iy1[y]][ix0[x]], a11 = x0[p][iy1[y]][ix1[x]]:
+ *     top = a00 + fx * (a01 - a00),  bot = a10 + fx * (a11 - a10),  v = top + fy * (bot - top),  out = (1 - s) * v + s * eps[p][y][x]
+ *   every operation an fp32 operation rounded on its own (no contraction); bf16_state != 0: out is rounded to a bf16 value (fp32 storage).
+ * No state, no scratch, nothing allocated, no host read: every call is capturable.  int32 / fp32 pointers 4-byte aligned (otherwise -3). */
+int ce_autofocus_bbox_u8(const void* mask, long long pitch, int H, int W, int* out, hipStream_t stream);
+int ce_autofocus_restart_f32(const float* x0, const float* eps, float* out, const int* ix0, const int* ix1, const float* fx, const int* iy0,
+                             const int* iy1, const float* fy, float s, int planes, int h, int w, int bf16_state, hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
