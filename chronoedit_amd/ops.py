@@ -1069,6 +1069,73 @@ def auto_region_mask_u8(w: torch.Tensor, out: Optional[torch.Tensor] = None):
     return out
 
 
+# ---- live previews (csrc/ce_preview.hip) ---------------------------------------------------------------------------------
+PREVIEW_SCALES = (1, 2, 4, 8)
+PREVIEW_GRAM_SCRATCH = 1024 * 210 * 8  # the most ce_preview_gram_f64 uses: 1024 workgroups x 210 float64 partials
+
+
+def preview_rgb_u8(x0: torch.Tensor, factors: torch.Tensor, scale: int = 2, frame: int = -1, w: Optional[torch.Tensor] = None,
+                   z_src: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """x0 fp32 [B, 16, T, h, w] on latent frame `frame` (negative: from the end), factors fp32 [17, 3] -> uint8 [B, h scale, w scale, 3]:
+    the projection per cell, a bilinear upsample, ce_video_to_u8's byte (preview.rgb_u8_reference, bit for bit).  w fp32 [h, w] and z_src
+    (x0's shape), both or neither: cells show w * x0 + (1 - w) * z_src."""
+    _f32c(x0, "x0"), _f32c(factors, "factors")
+    if x0.dim() != 5 or x0.shape[1] != 16:
+        raise ValueError(f"x0: need a [B, 16, T, h, w] tensor, got {tuple(x0.shape)}")
+    if tuple(factors.shape) != (17, 3):
+        raise ValueError(f"factors: need [17, 3] (16 channel rows and the bias), got {tuple(factors.shape)}")
+    if int(scale) not in PREVIEW_SCALES:
+        raise ValueError(f"scale: must be one of {PREVIEW_SCALES}, got {scale}")
+    if (w is None) != (z_src is None):
+        raise ValueError("w and z_src: the composite takes both or neither")
+    B, C, T, h, wl = x0.shape
+    f = int(frame) + T if frame < 0 else int(frame)
+    if not 0 <= f < T:
+        raise ValueError(f"frame: {frame} is outside the {T} latent frames")
+    if w is not None:
+        _f32c(w, "w"), _f32c(z_src, "z_src")
+        if tuple(w.shape) != (h, wl) or tuple(z_src.shape) != tuple(x0.shape):
+            raise ValueError(f"w / z_src: need [{h}, {wl}] and x0's shape, got {tuple(w.shape)} and {tuple(z_src.shape)}")
+    s = int(scale)
+    if out is None:
+        out = torch.empty((B, h * s, wl * s, 3), dtype=torch.uint8, device=x0.device)
+    _dev(out, torch.uint8, "out")
+    assert out.is_contiguous() and out.numel() == B * h * s * wl * s * 3
+    st = _prof_begin()
+    _check(lib().ce_preview_rgb_u8(_ptr(x0), _ptr(z_src), _ptr(w), _ptr(factors), _ptr(out), B, C, T, f, h, wl, s, _stream()), "ce_preview_rgb_u8")
+    _prof_end(st, f"preview_rgb_{B}x{h}x{wl}_s{s}", float((1 if w is None else 2) * 64 * B * h * wl + out.numel()))
+    return out
+
+
+def preview_gram(z: torch.Tensor, y: torch.Tensor, frame: int = -1, out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
+    """z fp32 [B, 16, T, h, w] on latent frame `frame`, y [B, 3, 8h, 8w] fp32 / bf16 -> float64 [20, 20] = sum over cells of v v^T,
+    v = (z_0..z_15, 1, r, g, b) with r, g, b the fp32 8x8 box mean (preview.gram_reference).  Fixed summation order: the same bits every run."""
+    _f32c(z, "z")
+    if y.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"y: expected bfloat16 or float32, got {y.dtype}")
+    _dev(y, y.dtype, "y")
+    if z.dim() != 5 or z.shape[1] != 16:
+        raise ValueError(f"z: need a [B, 16, T, h, w] tensor, got {tuple(z.shape)}")
+    B, _, T, h, wl = z.shape
+    if not y.is_contiguous() or tuple(y.shape) != (B, 3, 8 * h, 8 * wl):
+        raise ValueError(f"y: need a contiguous [{B}, 3, {8 * h}, {8 * wl}] tensor, got shape {tuple(y.shape)} stride {y.stride()}")
+    f = int(frame) + T if frame < 0 else int(frame)
+    if not 0 <= f < T:
+        raise ValueError(f"frame: {frame} is outside the {T} latent frames")
+    if out is None:
+        out = torch.empty((20, 20), dtype=torch.float64, device=z.device)
+    _dev(out, torch.float64, "out")
+    assert out.is_contiguous() and out.numel() == 400
+    if scratch is None:
+        scratch = torch.empty(PREVIEW_GRAM_SCRATCH, dtype=torch.uint8, device=z.device)
+    _dev(scratch, torch.uint8, "scratch")
+    st = _prof_begin()
+    _check(lib().ce_preview_gram_f64(_ptr(z), f, _ptr(y), int(y.dtype == torch.bfloat16), _ptr(out), _ptr(scratch), scratch.numel(), B, T, h, wl,
+                                     _stream()), "ce_preview_gram_f64")
+    _prof_end(st, f"preview_gram_{B}x{h}x{wl}", float(64 * B * h * wl + y.numel() * y.element_size()))
+    return out
+
+
 # ---- Wan VAE ------------------------------------------------------------------------------------------------------
 # ---- sparse region edits (csrc/ce_sparse.hip) ----------------------------------------------------------------------------
 def _sparse_ids(ids: torch.Tensor):

@@ -470,7 +470,8 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
             num_inference_steps: int, guidance_scale: float = 5.0, enable_temporal_reasoning: bool = False,
             num_temporal_reasoning_steps: int = 0, use_graph: bool = False, on_step_end=None, interrupted=None, graph_warm=None,
             teacache=None, teacache_measure: bool = False, guidance_reuse=None, guidance_measure: Optional[int] = None,
-            keep_deltas: bool = False, region=None, sparse_region=None, auto_region=None, start_step: int = 0, start_eps=None):
+            keep_deltas: bool = False, region=None, sparse_region=None, auto_region=None, start_step: int = 0, start_eps=None,
+            preview=None):
     """The whole loop, including the temporal-reasoning truncation 8 -> 2 latent frames (pipeline_chronoedit.py:700-709).
     on_step_end(i, t, latents) -> replacement latents, a dict with any of latents / prompt_embeds / negative_prompt_embeds, or None
     (the reference's callback_on_step_end hook, :741-749); graph_warm: a set the caller keeps across edits - shapes already run once in
@@ -534,7 +535,15 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     start_step = b > 0: the loop runs the TAIL of the schedule, steps b .. n - 1, on latents the caller has brought to sigma[b]
     (`scheduler.set_timesteps(n, begin=b)`: the history starts empty); every plan above is made from the tail's arrays, `on_step_end` is
     told i + b.  start_eps: the region blend's eps instead of a copy of the incoming latents - which, behind a warm start, are no longer
-    the noise.  start_step=0 is the loop as ever, launch for launch.  With temporal reasoning or a detecting auto_region a ValueError."""
+    the noise.  start_step=0 is the loop as ever, launch for launch.  With temporal reasoning or a detecting auto_region a ValueError.
+    preview: a preview.PreviewConfig for live previews; None = the loop as it is, launch for launch.  A step is previewed when
+    (i + 1) % every == 0, or when it is the last: behind the scheduler update and the region blend, before `on_step_end`, ONE launch
+    (csrc/ce_preview.hip, outside the captured graph) turns latent frame `frame` of scheduler.model_outputs[-1] - the estimate of the final
+    image, a stable buffer under replay - into bytes, an asynchronous copy brings them into a pinned buffer, an event marks it.  With a
+    region (explicit, or accepted: from step k on) and `composite` the kept cells show z_src; under a sparse plan always.  The preview of
+    step i is handed to `on_preview` - {"step": i + start_step, "timestep", "image": PIL RGB} - once step i + lag has been enqueued, in
+    ascending order, once each; everything outstanding before the loop returns (an interrupt and a scout's exit included).  The loop only
+    reads its state for this: the latents are the plain loop's.  With sharded tokens or CFG parallelism a NotImplementedError."""
     start_step = int(start_step)
     if start_step:
         if enable_temporal_reasoning or (auto_region is not None and region is None):
@@ -544,6 +553,13 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     else:
         scheduler.set_timesteps(num_inference_steps, device=latents.device)
     latents = latents.to(torch.float32).contiguous()
+    pv = None
+    if preview is not None:
+        if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
+            raise NotImplementedError("live previews with the tokens sharded over ranks or with CFG parallelism are not implemented "
+                                      "(nothing sharded has been tested with them)")
+        from . import preview as _pv
+        pv = _pv.PreviewDelivery(preview, latents.device, [int(v) for v in scheduler.timesteps.tolist()])  # (one read, before the first step)
     auto = auto_region if region is None else None  # an explicit mask wins
     a_cfg = None
     if auto is not None:  # (no config of its own: whatever `transformer.enable_auto_region()` set - nothing: the plain loop)
@@ -755,6 +771,8 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                                        image_embeds, guidance_scale, batch_cfg=True, cfg_inputs=cfg_inputs)
             finally:
                 transformer._tea_mode = None  # a forward outside the loop runs the whole model
+        if pv is not None and preview.lag > 0:
+            pv.deliver(i - preview.lag)  # step i is enqueued: the previews of the steps up to i - lag have had that long
         if region_state is not None and not use_graph:  # (every eager branch above; a graphed step blends inside its graph)
             region_state.blend(latents, i)
         if auto_table is not None:  # measuring: this step's change map into its row of the table
@@ -778,6 +796,12 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                     s_forced = set(range(i + 1))  # every step up to here ran dense: step k + 1 is the first refresh
                     s_plan, s_ids, s_tokens, s_full = sparse_setup(a_w_cpu, s_forced, latents.shape[2])
             auto_z = auto_eps = None
+        if pv is not None and _pv.due(i, len(scheduler.timesteps), preview.every):
+            # kept cells show the source when asked to - and always under a sparse plan, whose steps predict 0 outside the active tokens
+            comp = region_state is not None and (preview.composite or s_plan is not None)
+            pv.submit(i, i + start_step, scheduler.model_outputs[-1], region_state.w if comp else None, region_state.z_src if comp else None)
+            if preview.lag == 0:
+                pv.deliver(i)
         if kind == "pair":
             delta_valid = True
         elif kind == "off":
@@ -813,6 +837,8 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
             if new is not None and new is not latents:
                 graphed = None  # the graph is tied to the latents' storage
                 latents = new.to(torch.float32).contiguous()
+    if pv is not None:
+        pv.flush()  # everything outstanding, before the loop returns
     if measure:
         from .teacache import distances_from_sums
         sums = transformer.engine().tea_measure_end()  # the one read of the table, after the last step
@@ -944,6 +970,10 @@ class ChronoEditPipeline:
         self.focus_report = None  # the last call's focus plans, one dict per image (focus.plan); None when focus did not run
         self._auto_focus = None  # the autofocus.AutoFocusConfig while enable_auto_focus is in force
         self._focus_pass = None  # one shot: what the scout of an auto-focused call hands to the focused pass it starts (`_auto_focus_pass`)
+        self._preview = None  # the options of `enable_preview` while it is in force
+        self.preview_factors = None  # fp32 [17, 3]: the latent -> RGB map of the previews (`fit_preview_factors`, or set by hand)
+        self.preview_fit_report = None  # {"rms", "r2"} per colour of the last fit
+        self.preview_fit_gram = None  # float64 [20, 20] on the CPU: the Gram matrix the last fit solved
 
     # -- properties of the reference pipeline (:458-478) ---------------------------------------------------------------
     @property
@@ -1234,6 +1264,82 @@ class ChronoEditPipeline:
     def disable_auto_region(self):
         self.transformer.disable_auto_region()
         return self
+
+    # -- live previews (chronoedit_amd/preview.py): off by default
+    def enable_preview(self, on_preview, every: int = 1, scale: int = 2, frame: int = -1, composite: bool = True, lag: int = 1, factors=None):
+        """While the steps run, `on_preview` gets {"step", "timestep", "image": PIL RGB, "sample", "pass"} for every `every`-th step and the
+        last: latent frame `frame` of the model's current estimate of the result through a linear map (`factors`, default
+        `preview_factors` as `fit_preview_factors` left it) at `scale` pixels per latent cell.  Step i's picture arrives once step
+        i + lag is enqueued, so the loop never waits for it; `pipe._interrupt = True` from the callback stops the edit early.  With an edit
+        region and `composite` the kept area shows the source; under region focus the picture is the crop's.  "pass" is "scout" / "focus"
+        in an auto-focused call, else None.  The returned frames are those of the call without previews, bit for bit."""
+        from . import preview as _pv
+        if factors is None and self.preview_factors is None:
+            raise ValueError("enable_preview: no factors - pass factors=, or fit them on the loaded VAE with fit_preview_factors(images)")
+        _pv.PreviewConfig(on_preview, every, scale, frame, composite, lag, factors if factors is not None else self.preview_factors)  # validates
+        self._preview = dict(on_preview=on_preview, every=every, scale=scale, frame=frame, composite=composite, lag=lag,
+                             factors=None if factors is None else _pv.as_factors(factors))
+        return self
+
+    def disable_preview(self):
+        self._preview = None
+        return self
+
+    def _preview_config(self, sample: int = 0, tag=None):
+        """The preview.PreviewConfig of sample `sample` of this call (None: previews are off): the user's callback gets the loop's dict
+        with "sample" and "pass" added."""
+        if self._preview is None:
+            return None
+        from . import preview as _pv
+        o = dict(self._preview)
+        user = o["on_preview"]
+        o["on_preview"] = lambda d: user({**d, "sample": sample, "pass": tag})
+        if o["factors"] is None:
+            if self.preview_factors is None:
+                raise ValueError("previews are enabled but preview_factors is None: fit_preview_factors(images), or enable_preview(factors=)")
+            o["factors"] = self.preview_factors
+        return _pv.PreviewConfig(**o)
+
+    @torch.no_grad()
+    def preview_fit_tensors(self, images, height: Optional[int] = None, width: Optional[int] = None):
+        """What the fit is made from: (z fp32 [N, 16, 1, h, w], y [N, 3, H, W]) on the device.  Every image goes through the ordinary
+        pre-processing and ONE single-frame VAE encode; z is the posterior mode normalised with latents_mean / latents_std as in
+        `prepare_latents`; y is z decoded again."""
+        height, width = 480 if height is None else int(height), 832 if width is None else int(width)
+        if height % 16 != 0 or width % 16 != 0:
+            raise ValueError(f"`height` and `width` have to be divisible by 16 but are {height} and {width}.")
+        images = list(images) if isinstance(images, (list, tuple)) else [images]
+        if not images:
+            raise ValueError("fit_preview_factors: no images")
+        device, zd = self._execution_device, self.vae.config.z_dim
+        mean = torch.tensor(self.vae.config.latents_mean, device=device, dtype=torch.bfloat16).view(1, zd, 1, 1, 1)
+        inv_std = (1.0 / torch.tensor(self.vae.config.latents_std)).to(device=device, dtype=torch.bfloat16).view(1, zd, 1, 1, 1)
+        zs, ys = [], []
+        for im in images:
+            if self.device_image_io and device.type == "cuda" and _is_pil(im):
+                img = image_io.preprocess_pil(im, height, width, device)
+            else:
+                img = self.preprocess_image(im, height, width).to(device=device, dtype=torch.bfloat16)
+            lat = self.vae.encode(img.unsqueeze(2).to(torch.bfloat16)).latent_dist.mode()
+            z = (lat - mean) * inv_std
+            y = self.vae.decode(z / inv_std + mean, return_dict=False)[0]
+            zs.append(z.float())
+            ys.append(y[:, :, 0])
+        return torch.cat(zs, dim=0).contiguous(), torch.cat(ys, dim=0).contiguous()
+
+    @torch.no_grad()
+    def fit_preview_factors(self, images, height: Optional[int] = None, width: Optional[int] = None):
+        """Fit the previews' latent -> RGB map on the loaded VAE: `preview_fit_tensors`, ONE ce_preview_gram_f64 over all images, then
+        preview.solve_factors.  Sets `preview_factors`, `preview_fit_report` ({"rms", "r2"} per colour: how well a linear map fits THIS
+        checkpoint) and `preview_fit_gram`; returns the factors (fp32 [17, 3])."""
+        from . import ops
+        from . import preview as _pv
+        z, y = self.preview_fit_tensors(images, height, width)
+        if y.dtype not in (torch.bfloat16, torch.float32):
+            y = y.float()
+        self.preview_fit_gram = ops.preview_gram(z, y.contiguous(), 0).cpu()
+        self.preview_factors, self.preview_fit_report = _pv.solve_factors(self.preview_fit_gram)
+        return self.preview_factors
 
     def _auto_region_config(self):
         """(config, measuring) of the next edit without an explicit region; (None, False): the detector is off."""
@@ -1682,7 +1788,9 @@ class ChronoEditPipeline:
                                     use_graph=self.use_graph, on_step_end=on_step_end, interrupted=lambda: self._interrupt,
                                     graph_warm=self._graph_warm, region=None if regions is None else regions[image_of(b)][1],
                                     auto_region=None if autos is None else autos[b], start_step=start_step,
-                                    start_eps=None if start_eps is None else start_eps[b:b + 1], **self._measure_kwargs()))
+                                    start_eps=None if start_eps is None else start_eps[b:b + 1],
+                                    preview=self._preview_config(b, "focus" if fpass is not None else "scout" if a_focus is not None else None),
+                                    **self._measure_kwargs()))
         if autos is not None and not autos[0].measure:
             self.auto_region_report = autos[0].report if B == 1 else [a.report for a in autos]
         if a_focus is not None:
@@ -1792,7 +1900,8 @@ class ChronoEditPipeline:
             auto = _ar.AutoRegion(a_cfg, _rg.static_source_latents(self.vae, image, num_frames), measure=a_measure)
         latents = denoise(self.transformer, self.scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
                           num_inference_steps, guidance_scale, enable_temporal_reasoning, num_temporal_reasoning_steps,
-                          use_graph=self.use_graph, graph_warm=self._graph_warm, region=region, auto_region=auto, **self._measure_kwargs())
+                          use_graph=self.use_graph, graph_warm=self._graph_warm, region=region, auto_region=auto,
+                          preview=self._preview_config(), **self._measure_kwargs())
         if auto is not None and not auto.measure:
             self.auto_region_report = auto.report
         if output_type == "latent":

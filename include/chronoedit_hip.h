@@ -613,6 +613,25 @@ int ce_autofocus_bbox_u8(const void* mask, long long pitch, int H, int W, int* o
 int ce_autofocus_restart_f32(const float* x0, const float* eps, float* out, const int* ix0, const int* ix1, const float* fx, const int* iy0,
                              const int* iy1, const float* fy, float s, int planes, int h, int w, int bf16_state, hipStream_t stream);
 
+/* ---- live previews (csrc/ce_preview.hip; chronoedit_amd/preview.py): an RGB estimate of the running edit from the scheduler's predict-x0
+ * slot through a fitted linear map, and the Gram matrix that map is fitted from.  Every fp32 operation is rounded on its own.
+ * ce_preview_rgb_u8: x0 (and z_src) = fp32 [B][C = 16][T][h][w] (contiguous), on latent frame `frame`; w = fp32 [h][w]; z_src and w are both
+ *   given or both NULL; factors = fp32 [17][3] (rows 0..15 channel weights, row 16 the bias); out = uint8 [B][h scale][w scale][3], scale in
+ *   {1, 2, 4, 8}.  Per cell: u_k = (w * x0_k) + ((1 - w) * z_k), or x0_k without w;  p_c = factors[16][c], then for k = 0..15 in order
+ *   p_c = p_c + factors[k][c] * u_k.  Per pixel, half-pixel centres: fy = (Y + 0.5) / scale - 0.5 clamped to [0, h - 1], y0 = floor(fy),
+ *   y1 = min(y0 + 1, h - 1), ty = fy - y0, the same along X;  top = p(y0, x0) * (1 - tx) + p(y0, x1) * tx, bot likewise on y1,
+ *   v = top * (1 - ty) + bot * ty;  the byte is ce_video_to_u8's: rint(clamp(v * 0.5 + 0.5, 0, 1) * 255), NaN -> 0.  Every byte of out is written.
+ * ce_preview_gram_f64: z = fp32 [B][16][T][h][w] on latent frame `frame`; y = [B][3][8 h][8 w] of fp32 (y_bf16 == 0) or bf16;
+ *   out = float64 [20][20] = sum over samples and cells of v v^T, v = (z_0..z_15, 1, r, g, b), r / g / b = (the fp32 sum of the cell's 8 x 8
+ *   pixels in row-major order) * 0.015625f.  Products and sums are float64 in a fixed order: per-workgroup partials in `scratch` (8-byte
+ *   aligned, at least 1680 bytes - otherwise -1; more lets more workgroups run, up to 1024 x 1680), added in workgroup order by a second
+ *   launch.  The same arguments give the same bits.
+ * No state, nothing allocated, no host read: every call is capturable.  fp32 pointers 4-byte aligned (otherwise -3). */
+int ce_preview_rgb_u8(const float* x0, const float* z_src, const float* w, const float* factors, void* out, int B, int C, int T, int frame,
+                      int h, int wl, int scale, hipStream_t stream);
+int ce_preview_gram_f64(const float* z, int frame, const void* y, int y_bf16, double* out, void* scratch, size_t scratch_bytes, int B, int T,
+                        int h, int wl, hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
