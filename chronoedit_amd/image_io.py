@@ -162,8 +162,10 @@ def vae_lut(device) -> torch.Tensor:
     return lut
 
 
-def preprocess_pil(images, height: int, width: int, device) -> torch.Tensor:
-    """pipeline.preprocess_image(images, height, width).to(device, bfloat16) for a PIL image or a list of them: bf16 [B, 3, height, width]."""
+def preprocess_pil(images, height: int, width: int, device, keep: Optional[list] = None) -> torch.Tensor:
+    """pipeline.preprocess_image(images, height, width).to(device, bfloat16) for a PIL image or a list of them: bf16 [B, 3, height, width].
+    keep: a list that receives, per image, (the photo's bytes uint8 [SH, SW, 3], their Lanczos resize uint8 [height, width, 3]) as they lie
+    on the device - what the detail lift (lift.py) works from, with no second upload."""
     imgs = _pil_list(images)
     if imgs is None:
         raise ValueError("preprocess_pil takes a PIL image or a list of PIL images")
@@ -171,7 +173,11 @@ def preprocess_pil(images, height: int, width: int, device) -> torch.Tensor:
     lut = vae_lut(device)
     out = torch.empty((len(imgs), 3, height, width), dtype=torch.bfloat16, device=device)
     for b, im in enumerate(imgs):
-        ops.image_u8_lut_planar(resize_u8(upload_rgb(im, device), (width, height), LANCZOS), lut, out[b])
+        src = upload_rgb(im, device)
+        small = resize_u8(src, (width, height), LANCZOS)
+        ops.image_u8_lut_planar(small, lut, out[b])
+        if keep is not None:
+            keep.append((src, small))
     return out
 
 

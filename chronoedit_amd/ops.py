@@ -1136,6 +1136,94 @@ def preview_gram(z: torch.Tensor, y: torch.Tensor, frame: int = -1, out: Optiona
     return out
 
 
+# ---- guided detail lift (csrc/ce_lift.hip) --------------------------------------------------------------------------------
+LIFT_CELL = 8  # floats per coefficient cell: abar_rgb, bbar_rgb, g, 0
+
+
+def _lift_planes(L: torch.Tensor, E: torch.Tensor):
+    _dev(L, torch.uint8, "L"), _dev(E, torch.uint8, "E")
+    if L.dim() != 3 or L.shape[2] != 3 or not L.is_contiguous():
+        raise ValueError(f"L: need a contiguous [H, W, 3] tensor, got shape {tuple(L.shape)} stride {L.stride()}")
+    if E.dim() != 4 or tuple(E.shape[1:]) != tuple(L.shape) or not E.is_contiguous():
+        raise ValueError(f"E: need a contiguous [F, {L.shape[0]}, {L.shape[1]}, 3] tensor, got shape {tuple(E.shape)} stride {E.stride()}")
+    return E.shape[0], L.shape[0], L.shape[1]
+
+
+def lift_fit_q16(L: torch.Tensor, E: torch.Tensor, radius: int, eps_q: int, max_gain: float, out: Optional[torch.Tensor] = None):
+    """Stage 1 of lift.reference: L uint8 [H, W, 3], E uint8 [F, H, W, 3] -> int32 [F, H, W, 6] = rint(65536 a_rgb), rint(65536 b_rgb)."""
+    F, H, W = _lift_planes(L, E)
+    if out is None:
+        out = torch.empty((F, H, W, 6), dtype=torch.int32, device=L.device)
+    _dev(out, torch.int32, "out")
+    assert out.is_contiguous() and tuple(out.shape) == (F, H, W, 6)
+    st = _prof_begin()
+    _check(lib().ce_lift_fit_q16(_ptr(L), _ptr(E), _ptr(out), F, H, W, int(radius), int(eps_q), float(max_gain), _stream()), "ce_lift_fit_q16")
+    _prof_end(st, f"lift_fit_{F}x{H}x{W}_r{radius}", float(L.numel() + E.numel() + 4 * out.numel()))
+    return out
+
+
+def lift_smooth(L: torch.Tensor, E: torch.Tensor, AB: torch.Tensor, radius: int, coef: Optional[torch.Tensor] = None,
+                R: Optional[torch.Tensor] = None):
+    """Stage 2: -> (the cells fp32 [F, H, W, 8]: the box means of a and b, slots 6 and 7 zeroed; R int32 [F, H, W] = rint(256 min(res, 255)))."""
+    F, H, W = _lift_planes(L, E)
+    _dev(AB, torch.int32, "AB")
+    if not AB.is_contiguous() or tuple(AB.shape) != (F, H, W, 6):
+        raise ValueError(f"AB: need a contiguous [{F}, {H}, {W}, 6] tensor, got shape {tuple(AB.shape)} stride {AB.stride()}")
+    if coef is None:
+        coef = torch.empty((F, H, W, LIFT_CELL), dtype=torch.float32, device=L.device)
+    if R is None:
+        R = torch.empty((F, H, W), dtype=torch.int32, device=L.device)
+    _dev(coef, torch.float32, "coef"), _dev(R, torch.int32, "R")
+    assert coef.is_contiguous() and tuple(coef.shape) == (F, H, W, LIFT_CELL) and R.is_contiguous() and tuple(R.shape) == (F, H, W)
+    st = _prof_begin()
+    _check(lib().ce_lift_smooth_f32(_ptr(L), _ptr(E), _ptr(AB), _ptr(coef), _ptr(R), F, H, W, int(radius), _stream()), "ce_lift_smooth_f32")
+    _prof_end(st, f"lift_smooth_{F}x{H}x{W}_r{radius}", float(4 * (AB.numel() + coef.numel() + R.numel())))
+    return coef, R
+
+
+def lift_gate(R: torch.Tensor, coef: torch.Tensor, radius: int, t0: float, t1: float):
+    """Stage 3: g = clamp((box mean of R / 256 - t0) / (t1 - t0), 0, 1) into slot 6 of the cells, in place."""
+    _dev(R, torch.int32, "R"), _dev(coef, torch.float32, "coef")
+    if R.dim() != 3 or not R.is_contiguous() or not coef.is_contiguous() or tuple(coef.shape) != tuple(R.shape) + (LIFT_CELL,):
+        raise ValueError(f"R / coef: need contiguous [F, H, W] and [F, H, W, 8], got {tuple(R.shape)} and {tuple(coef.shape)}")
+    F, H, W = R.shape
+    st = _prof_begin()
+    _check(lib().ce_lift_gate_f32(_ptr(R), _ptr(coef), F, H, W, int(radius), float(t0), float(t1), _stream()), "ce_lift_gate_f32")
+    _prof_end(st, f"lift_gate_{F}x{H}x{W}_r{radius}", float(8 * R.numel()))
+    return coef
+
+
+def lift_apply_u8(P: torch.Tensor, coef: torch.Tensor, tables, U: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """Stage 4: P uint8 [SH, SW, 3], the cells fp32 [F, H, W, 8], tables = (ix0, ix1 int32 [SW], tx fp32 [SW], iy0, iy1 int32 [SH], ty fp32 [SH])
+    on the device, U uint8 [F, SH, SW, 3] or None -> a new uint8 [F, SH, SW, 3]."""
+    _dev(P, torch.uint8, "P"), _dev(coef, torch.float32, "coef")
+    if P.dim() != 3 or P.shape[2] != 3 or not P.is_contiguous():
+        raise ValueError(f"P: need a contiguous [SH, SW, 3] tensor, got shape {tuple(P.shape)} stride {P.stride()}")
+    if coef.dim() != 4 or coef.shape[3] != LIFT_CELL or not coef.is_contiguous():
+        raise ValueError(f"coef: need a contiguous [F, H, W, 8] tensor, got shape {tuple(coef.shape)} stride {coef.stride()}")
+    SH, SW, _ = P.shape
+    F, H, W, _ = coef.shape
+    ix0, ix1, tx, iy0, iy1, ty = tables
+    for t, dt, n, name in ((ix0, torch.int32, SW, "ix0"), (ix1, torch.int32, SW, "ix1"), (tx, torch.float32, SW, "tx"),
+                           (iy0, torch.int32, SH, "iy0"), (iy1, torch.int32, SH, "iy1"), (ty, torch.float32, SH, "ty")):
+        _dev(t, dt, name)
+        if tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name}: need a contiguous [{n}] tensor, got shape {tuple(t.shape)}")
+    if U is not None:
+        _dev(U, torch.uint8, "U")
+        if tuple(U.shape) != (F, SH, SW, 3) or not U.is_contiguous():
+            raise ValueError(f"U: need a contiguous [{F}, {SH}, {SW}, 3] tensor, got shape {tuple(U.shape)} stride {U.stride()}")
+    if out is None:
+        out = torch.empty((F, SH, SW, 3), dtype=torch.uint8, device=P.device)
+    _dev(out, torch.uint8, "out")
+    assert out.is_contiguous() and tuple(out.shape) == (F, SH, SW, 3) and not _overlap(out, P) and (U is None or not _overlap(out, U))
+    st = _prof_begin()
+    _check(lib().ce_lift_apply_u8(_ptr(P), _ptr(U), _ptr(coef), _ptr(ix0), _ptr(ix1), _ptr(tx), _ptr(iy0), _ptr(iy1), _ptr(ty), _ptr(out),
+                                  F, SH, SW, H, W, _stream()), "ce_lift_apply_u8")
+    _prof_end(st, f"lift_apply_{F}x{SH}x{SW}", float(out.numel() + P.numel() + (0 if U is None else U.numel())))
+    return out
+
+
 # ---- Wan VAE ------------------------------------------------------------------------------------------------------
 # ---- sparse region edits (csrc/ce_sparse.hip) ----------------------------------------------------------------------------
 def _sparse_ids(ids: torch.Tensor):

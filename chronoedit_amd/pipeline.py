@@ -974,6 +974,8 @@ class ChronoEditPipeline:
         self.preview_factors = None  # fp32 [17, 3]: the latent -> RGB map of the previews (`fit_preview_factors`, or set by hand)
         self.preview_fit_report = None  # {"rms", "r2"} per colour of the last fit
         self.preview_fit_gram = None  # float64 [20, 20] on the CPU: the Gram matrix the last fit solved
+        self._detail_lift = None  # the lift.LiftConfig while enable_detail_lift is in force
+        self.lift_report = None  # the last call's detail-lift report, one dict per sample; None when the switch is off (or "latent" was asked for)
 
     # -- properties of the reference pipeline (:458-478) ---------------------------------------------------------------
     @property
@@ -1460,6 +1462,80 @@ class ChronoEditPipeline:
         self._auto_focus = None
         return self
 
+    # Guided detail lift (chronoedit_amd/lift.py): whole-image edits returned at the photo's size.  Off by default
+    def enable_detail_lift(self, radius: int = 4, eps: float = 26.0, gate=(4.0, 12.0), max_gain: float = 8.0):
+        """While on, a call with PIL input (one image, or a list with one per prompt) and output_type "pil" / "np" / "pt" returns every frame
+        - reasoning frames included, behind the edit-size region composite if there is one - at the IMAGE's own size: per edit-size
+        neighbourhood and colour an affine map from the resized photo to the edit's change is fitted (window radius `radius` cells,
+        regulariser `eps` in squared bytes, |slope| <= `max_gain`), the maps are smoothed, sampled at the photo's pixel centres and applied to
+        the photo's own bytes; where the smoothed map leaves a mean residual between gate[0] and gate[1] bytes the plain Lanczos upsample
+        of the edited frame is blended in, and beyond gate[1] it replaces the lift (gate=None: no fallback, and no Lanczos pass).  "np" /
+        "pt" carry the "pil" bytes / 255 (the images of one call must then share a size), "latent" is untouched.  A focused call (an explicit
+        mask under `enable_region_focus`, or an accepted auto focus) returns what focus returns: `lift_report` says "reason": "focus"; a
+        declined auto focus is lifted.  An image already of the edit's size returns the plain frames ("reason": "same").  An array or tensor
+        `image` is a ValueError.  The lift runs behind the decode (csrc/ce_lift.hip; lift.reference on the host with
+        `enable_device_image_io(False)`, the same bytes), never inside a captured graph.  `lift_report` holds per sample {"size",
+        "edit_size", "applied", "reason", "fallback_fraction"}: the last is the mean of the gate - how much of the picture was plain
+        upsampling."""
+        from . import lift as _lf
+        self._detail_lift = _lf.LiftConfig(radius, eps, None if gate is None else tuple(gate) if isinstance(gate, (tuple, list)) else gate, max_gain)
+        return self
+
+    def disable_detail_lift(self):
+        self._detail_lift = None
+        return self
+
+    def _lift_output(self, video: torch.Tensor, cfg, kept, imgs, image_of, height: int, width: int, output_type: str):
+        """Every sample's frames lifted to its image's size, in postprocess_video's layouts - or None when every image already has the
+        edit's size (the caller then returns the plain frames).  kept: per image (P, L) on the device (`image_io.preprocess_pil`), or None:
+        the host form.  Fills `lift_report`; the gate means of all samples are read back once."""
+        import numpy as np
+        from PIL import Image
+        from . import lift as _lf
+        from . import ops
+        if output_type not in ("np", "pt", "pil"):
+            raise ValueError(f"{output_type} does not exist. Please choose one of ['np', 'pt', 'pil']")
+        B = video.shape[0]
+        same = [imgs[image_of(b)].size == (width, height) for b in range(B)]
+        entry = lambda b: {"size": imgs[image_of(b)].size, "edit_size": (int(width), int(height)), "applied": not same[b],
+                           "reason": "same" if same[b] else "ok", "fallback_fraction": None}
+        self.lift_report = [entry(b) for b in range(B)]
+        if all(same):
+            return None
+        on_device = kept is not None and video.is_cuda and video.dtype in (torch.bfloat16, torch.float32)
+        u8 = ops.video_to_u8(video.contiguous()) if on_device else None
+        out, fractions = [], []
+        for b in range(B):
+            im = imgs[image_of(b)]
+            if on_device:
+                E = u8[b]
+                if same[b]:
+                    out.append(E)
+                    continue
+                P, L = kept[image_of(b)]
+                U = None if cfg.gate is None else torch.stack([image_io.resize_u8(f, im.size, image_io.LANCZOS) for f in E])
+            else:
+                frames = self.postprocess_video(video[b:b + 1], "pil")[0]
+                E = torch.from_numpy(np.stack([np.asarray(f, dtype=np.uint8) for f in frames]))
+                if same[b]:
+                    out.append(E)
+                    continue
+                rgb = im.convert("RGB")
+                P = torch.from_numpy(np.array(rgb, dtype=np.uint8))
+                L = torch.from_numpy(np.array(rgb.resize((width, height), Image.LANCZOS), dtype=np.uint8))
+                U = None if cfg.gate is None else torch.from_numpy(np.stack([np.asarray(f.resize(im.size, Image.LANCZOS), dtype=np.uint8) for f in frames]))
+            o, frac = _lf.lift(P, L, E, U, cfg)
+            out.append(o)
+            fractions.append((b, frac))
+        if fractions:
+            for (b, _), v in zip(fractions, torch.stack([f for _, f in fractions]).cpu().tolist()):
+                self.lift_report[b]["fallback_fraction"] = float(v)
+        out = [o.cpu().numpy() for o in out]
+        if output_type == "pil":
+            return [[Image.fromarray(f) for f in sample] for sample in out]
+        arr = np.stack(out).astype(np.float32) / 255.0  # [B, F, SH, SW, 3]
+        return arr if output_type == "np" else torch.from_numpy(arr).permute(0, 1, 4, 2, 3)
+
     def _auto_focus_plan(self, image, mask_edit: torch.Tensor, height: int, width: int, device) -> dict:
         """The scout's decision: the detected edit-size mask (on the device) -> {"go", "plan"}: the lifted mask, the box (two reductions,
         five integers read each) and, when the box is worth cropping to, a plan as `_focus_setup` makes them."""
@@ -1695,6 +1771,19 @@ class ChronoEditPipeline:
             if offload_model:
                 raise NotImplementedError("auto focus with offload_model is not implemented (the encoders leave the device before the "
                                           "focused pass needs them)")
+        # detail lift (chronoedit_amd/lift.py): the frames of an unfocused call go back at the images' own sizes
+        self.lift_report = None
+        lift, lift_kept = None, None
+        if self._detail_lift is not None and output_type != "latent":
+            lift_imgs = image_io._pil_list(image) if image is not None else None
+            if lift_imgs is None:
+                raise ValueError("detail lift needs PIL input (one image or a list): an array or tensor `image` has no full-resolution bytes to "
+                                 "lift the edit onto - pass PIL images, or disable_detail_lift()")
+            if focus is None:
+                lift = self._detail_lift
+                if output_type in ("np", "pt") and len({im.size for im in lift_imgs}) > 1:
+                    raise ValueError(f"detail lift returns frames of the images' sizes {[im.size for im in lift_imgs]}: output_type={output_type!r} "
+                                     'needs images of one size, use "pil"')
         user_image_embeds = image_embeds
         if image_embeds is None:
             if focus is None:
@@ -1715,7 +1804,8 @@ class ChronoEditPipeline:
         if focus is not None:
             img, focus_masks = self._focus_inputs(focus, height, width, device)
         elif self.device_image_io and device.type == "cuda" and (_is_pil(image) or (isinstance(image, (list, tuple)) and image and all(_is_pil(i) for i in image))):
-            img = image_io.preprocess_pil(image, height, width, device)
+            lift_kept = [] if lift is not None else None  # (the photo's bytes stay on the device: one upload)
+            img = image_io.preprocess_pil(image, height, width, device, keep=lift_kept)
         else:
             img = self.preprocess_image(image, height, width).to(device=device, dtype=torch.bfloat16)
         latents, condition = self.prepare_latents(img, B, self.vae.config.z_dim, height, width, num_frames, torch.bfloat16, device,
@@ -1834,8 +1924,14 @@ class ChronoEditPipeline:
                 video = torch.cat([video[b:b + 1].float() if autos[b].mask_u8 is None else
                                    _rg.composite(video[b:b + 1], img[image_of(b):image_of(b) + 1], autos[b].mask_u8)
                                    for b in range(video.shape[0])], dim=0)
+            lifted = None if lift is None else self._lift_output(video, lift, lift_kept, lift_imgs, image_of, height, width, output_type)
             if focus is not None:  # the source-size paste replaces the edit-size composite
                 video = self._focus_output(video, focus, image_of, output_type)
+                if self._detail_lift is not None:
+                    self.lift_report = [{"size": focus[image_of(b)]["image"].size, "edit_size": (int(width), int(height)), "applied": False,
+                                         "reason": "focus", "fallback_fraction": None} for b in range(B)]
+            elif lifted is not None:
+                video = lifted
             elif self.device_image_io and output_type == "pil" and video.is_cuda and video.dtype in (torch.bfloat16, torch.float32):
                 video = image_io.frames_to_pil(video)
             else:

@@ -632,6 +632,36 @@ int ce_preview_rgb_u8(const float* x0, const float* z_src, const float* w, const
 int ce_preview_gram_f64(const float* z, int frame, const void* y, int y_bf16, double* out, void* scratch, size_t scratch_bytes, int B, int T,
                         int h, int wl, hipStream_t stream);
 
+/* ---- guided detail lift (csrc/ce_lift.hip; chronoedit_amd/lift.py): a whole-image edit made at the edit's size is carried up to the photo's
+ * pixel grid.  lift.reference (CPU torch) is the definition; every pass is bit-equal to its stage.  L = uint8 [H][W][3] (the photo resized to
+ * the edit's size), E = uint8 [F][H][W][3] (the frames), P = uint8 [SH][SW][3] (the photo), U = uint8 [F][SH][SW][3] (the frames' Lanczos
+ * upsample) or NULL.  Box sums run over the window [y - r, y + r] x [x - r, x + r] clipped to the image, n = its cell count, r = radius in
+ * 1..16 (otherwise -1).  Every fp32 / fp64 operation is rounded on its own.
+ * ce_lift_fit_q16: per frame, cell and colour, I = L_c, d = E_c - I; the integer box sums S_I, S_d, S_II, S_Id; in int64
+ *   num = n S_Id - S_I S_d, den = n S_II - S_I^2 + eps_q n^2 (eps_q in 1..2^30: squared bytes; both below 2^53);
+ *   a = fp32(clamp(double(num) / double(den), -max_gain, max_gain)), 1 <= max_gain <= 8;  b = fp32((double(S_d) - double(a) * double(S_I)) /
+ *   double(n));  AB = int32 [F][H][W][6] = rint(65536 a_rgb), rint(65536 b_rgb).
+ * ce_lift_smooth_f32: the int64 box sums of A and B -> abar = fp32(double(sum A) / double(65536 n)), bbar likewise;  res = max over colours
+ *   of |float(d) - (abar * float(I) + bbar)|;  coef = fp32 [F][H][W][8] = abar_rgb, bbar_rgb, 0, 0 (16-byte aligned);  R = int32 [F][H][W] =
+ *   rint(256 min(res, 255)).
+ * ce_lift_gate_f32: coef[..][6] = clamp((fp32(double(box sum R) / double(256 n)) - t0) / (t1 - t0), 0, 1), 0 <= t0 < t1 (otherwise -1).
+ *   Without this call g = 0: no fallback.
+ * ce_lift_apply_u8: ix0, ix1 = int32 [SW], tx = fp32 [SW], iy0, iy1 = int32 [SH], ty = fp32 [SH] in device memory: the corner cells and
+ *   weight of every photo column and row (lift.axis_table; an index outside the grid is clamped into it).  Per output byte, p = float(P),
+ *   c00 .. c11 the four corner cells:  top = c00 * (1 - tx) + c01 * tx, bot likewise, v = top * (1 - ty) + bot * ty, for abar_c, bbar_c and g;
+ *   q = p + (a_up * p + b_up);  with U: q = q + g_up * (float(U) - q);  out = rint(clamp(q, 0, 255)), NaN -> 0.  out = uint8 [F][SH][SW][3],
+ *   aliasing no input; every byte is written.  U is not read where g_up == 0.  16-byte accesses when SH * SW % 16 == 0 and P, U, out are
+ *   16-byte aligned, byte by byte otherwise - the same bytes.
+ * What follows from the arithmetic: E == L gives out == P byte for byte (a = b = g = 0, p + (0 p + 0) = p); wherever E == L over the
+ * +-(3 r + 1)-cell neighbourhood of a pixel's four corners, the pixel is P's; wherever g_up == 1 the pixel is U's.
+ * No state, nothing allocated, no host read: every call is capturable.  F <= 65535.  A plane of 2^31 bytes or more (H * W * 3, SH * SW * 3,
+ * H * W * 32) returns -2; AB, R and the tables 4-byte, coef 16-byte aligned (otherwise -3). */
+int ce_lift_fit_q16(const void* L, const void* E, int* AB, int F, int H, int W, int radius, int eps_q, float max_gain, hipStream_t stream);
+int ce_lift_smooth_f32(const void* L, const void* E, const int* AB, float* coef, int* R, int F, int H, int W, int radius, hipStream_t stream);
+int ce_lift_gate_f32(const int* R, float* coef, int F, int H, int W, int radius, float t0, float t1, hipStream_t stream);
+int ce_lift_apply_u8(const void* P, const void* U, const float* coef, const int* ix0, const int* ix1, const float* tx, const int* iy0,
+                     const int* iy1, const float* ty, void* out, int F, int SH, int SW, int H, int W, hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
