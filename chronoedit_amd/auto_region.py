@@ -66,7 +66,7 @@ class AutoRegionConfig:
 
 
 class AutoRegion:
-    """What `pipeline.denoise(auto_region=)` takes for ONE edit: the config (None: the transformer's switch decides) and z_src = fp32 source latents of the latents' shape
+    """What `loop.denoise(auto_region=)` takes for ONE edit: the config (None: the transformer's switch decides) and z_src = fp32 source latents of the latents' shape
     (region.static_source_latents).  measure: run the plain loop and record every step's change map instead of detecting
     (`measure_auto_region`).  The loop leaves `report` (see `report`) and `mask_u8` (the device mask of an accepted region, else None)
     here.  on_accept: a callable (the device mask of an accepted region) -> bool; True ends the loop behind the detecting step, with
@@ -78,6 +78,95 @@ class AutoRegion:
         self.mask_u8: Optional[torch.Tensor] = None
         self.on_accept = on_accept
         self.exited = False
+
+
+class AutoRegionState:
+    """The automatic region of one running edit (`loop.denoise(auto_region=)`: an AutoRegion - the config, None: whatever
+    `transformer.enable_auto_region()` set - and z_src = fp32 static-source latents of the latents' shape).  An explicit `region=` wins: the
+    detector is not run and the report is None.
+    Detecting: the state keeps a clone of the latents the loop starts from (the blend's eps); steps 0 .. k run as the plain loop (k =
+    detect_step, or with temporal reasoning the first step at or behind it that runs at the truncated shape; past the last step nothing
+    is detected).  After step k's scheduler update, before `on_step_end`, four device passes (csrc/ce_region_auto.hip) turn x0 =
+    scheduler.model_outputs[-1] and z_src into the weights w and the pixel mask, and ONE read brings w to the host (`after_step`).
+    Declined (no active cell, or more active patches than max_area of the grid - with the sparse margin when a sparse region is enabled):
+    the edit stays the plain loop, bit for bit.  Accepted: a RegionState is built from (w, z_src, eps, sigma_next), the blend runs after
+    step k itself and after every later step, the loop rebuilds its graphed form (a region is another warm shape), and with a sparse
+    region config makes the plan now, every step <= k forced dense, so that step k + 1 is the first refresh.  Composition and refusals
+    are those of an explicit region.  Afterwards `transformer.auto_region_report` and `auto_region.report` hold {"step", "threshold",
+    "dmax", "active_fraction", "accepted", "reason", "w", "mask"} and `auto_region.mask_u8` the device mask of an accepted region.
+    auto_region.measure: every step runs the plain loop and writes its change map into a [steps, h, w] device table, read back once after
+    the last step (`finish`): `transformer.auto_region_measurement` then holds one row per step (`measurement`).
+    auto_region.on_accept: a callable (the device pixel mask of an accepted region) -> bool, asked before anything of the region is set
+    up; True ends the loop behind step k (its `on_step_end` still runs) with `auto_region.exited` and this state's `exiting` set - the
+    scout of an auto-focused edit (chronoedit_amd/autofocus.py); False, or none: as above."""
+
+    def __init__(self, transformer, auto: AutoRegion, config: AutoRegionConfig, latents: torch.Tensor, n_steps: int, k: Optional[int]):
+        self.transformer, self.auto, self.config, self.k = transformer, auto, config, k  # k: the step the detection follows
+        self.detecting, self.exiting = not auto.measure, False
+        self.z = auto.z_src.to(device=latents.device, dtype=torch.float32).contiguous()
+        self.eps = latents.clone() if self.detecting else None  # the blend's eps, should a region be found
+        self.table = None if self.detecting else torch.zeros((n_steps,) + tuple(latents.shape[-2:]), dtype=torch.float32, device=latents.device)
+
+    @classmethod
+    def begin(cls, transformer, auto_region: Optional[AutoRegion], region, latents: torch.Tensor, n_steps: int,
+              enable_temporal_reasoning: bool = False, num_temporal_reasoning_steps: int = 0) -> Optional["AutoRegionState"]:
+        """Resets the reports; None when nothing is to be detected or measured (no AutoRegion, an explicit region, or no config anywhere).
+        With sharded tokens or CFG parallelism a NotImplementedError, then a z_src of another shape than the latents a ValueError."""
+        auto = auto_region if region is None else None  # an explicit mask wins
+        cfg = None
+        if auto is not None:  # (no config of its own: whatever `transformer.enable_auto_region()` set - nothing: the plain loop)
+            cfg = auto.config if auto.config is not None else getattr(transformer, "_auto_region", None)
+        if hasattr(transformer, "auto_region_report"):
+            transformer.auto_region_report = None
+        if auto_region is not None:
+            auto_region.report = auto_region.mask_u8 = None
+        if cfg is None:
+            return None
+        from .loop import refuse_sharded
+        from .region import SHARDED
+        refuse_sharded(transformer, SHARDED)
+        if tuple(auto.z_src.shape) != tuple(latents.shape):
+            raise ValueError(f"auto region: z_src {tuple(auto.z_src.shape)} does not have the latents' shape {tuple(latents.shape)}")
+        k = None if auto.measure else detect_index(cfg, n_steps, enable_temporal_reasoning, num_temporal_reasoning_steps)
+        return cls(transformer, auto, cfg, latents, n_steps, k)
+
+    def truncated(self, latents: torch.Tensor):
+        """The temporal-reasoning truncation: z_src and eps are sliced exactly as the latents are."""
+        if self.z is not None and self.z.shape[-3] != latents.shape[-3]:
+            self.z = self.z[:, :, [0, -1]].contiguous()
+            self.eps = None if self.eps is None else self.eps[:, :, [0, -1]].contiguous()
+
+    def after_step(self, i: int, scheduler, latents: torch.Tensor, margin: int = 0):
+        """Measuring: this step's change map into its row of the table.  Detecting, behind step k: the four passes on the estimate of the
+        final image the step kernel just wrote, one read, the decision.  -> (the RegionState of an accepted region, already blended into
+        step k's latents; w on the CPU), else None."""
+        if self.table is not None:
+            from . import ops
+            ops.auto_region_change(scheduler.model_outputs[-1], self.z, -1, out=self.table[i])
+            return None
+        if i != self.k or self.z is None:
+            return None
+        from . import region as _rg
+        auto, found = self.auto, None
+        w, mask, w_cpu, thr, dmax = detect(scheduler.model_outputs[-1], self.z, self.config)
+        ok, why, frac = decide(w_cpu, self.config, margin)
+        auto.report = self.transformer.auto_region_report = report(i, thr, dmax, frac, ok, why, w_cpu)
+        if ok and auto.on_accept is not None and auto.on_accept(mask):
+            auto.mask_u8, auto.exited, self.exiting = mask, True, True  # the caller goes on from here (the history is as step k left it)
+        elif ok:
+            state = _rg.RegionState(w, self.z, self.eps, _rg.sigma_next_table(scheduler, latents.device),
+                                    bf16_state=scheduler.trajectory_dtype == torch.bfloat16)
+            auto.mask_u8 = mask
+            state.blend(latents, i)  # the blend after step k itself
+            found = (state, w_cpu)
+        self.z = self.eps = None
+        return found
+
+    def finish(self, timesteps: torch.Tensor):
+        """Measuring: the one read of the table, after the last step."""
+        if self.table is not None:
+            self.transformer.auto_region_measurement = {"timesteps": [int(v) for v in timesteps.tolist()],
+                                                        "steps": measurement(self.table.cpu(), self.config)}
 
 
 def detect_index(cfg: AutoRegionConfig, n_steps: int, enable_temporal_reasoning: bool = False, num_temporal_reasoning_steps: int = 0) -> Optional[int]:

@@ -1,23 +1,22 @@
-"""Denoising loop of ChronoEditPipeline.__call__ on the HIP engine
-(/root/reference/chronoedit_diffusers/pipeline_chronoedit.py:694-756).
+"""ChronoEditPipeline on the HIP engine: the drop-in for the reference pipeline of the same name
+(chronoedit_diffusers/pipeline_chronoedit.py), with `prepare_latents` and `decode_latents` around the denoising loop.
 
-`denoise_step` is one loop iteration — the unit BASELINE.json's "denoising-steps/sec" counts:
-cat(latents, condition) -> 1 or 2 DiT forwards -> CFG -> scheduler update.  The latents stay fp32
-on the device for the whole trajectory; the CFG combine and the UniPC update are one fused launch.
+The loop itself - `denoise`, `denoise_step`, `GraphedDenoiser`, the text-compaction helpers, `make_cfg_inputs` - lives in
+chronoedit_amd/loop.py; every name of it that callers, tests and tools import from here is re-exported below (the same objects).
 """
 from __future__ import annotations
 
 import contextlib
 import html
-import math
 import re
 from dataclasses import dataclass
-from types import SimpleNamespace
-from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
+from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
 from . import image_io
+from .loop import (GraphedDenoiser, _capturable, _sharded_batchable, _shared_inputs, _token_sharded, _warmup_stream,  # noqa: F401
+                   compact_text_context, denoise, denoise_step, make_cfg_inputs, text_compaction_plan, text_real_lengths)
 from .scheduler import FlowUniPCMultistepScheduler
 from .transformer import ChronoEditTransformer3DModel
 
@@ -40,819 +39,6 @@ def prompt_clean(text: str) -> str:
         pass
     text = html.unescape(html.unescape(text)).strip()
     return re.sub(r"\s+", " ", text).strip()
-
-
-_INT_OF_SIZE = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
-
-
-def text_real_lengths(text: torch.Tensor) -> torch.Tensor:
-    """text [B, Tt, C] -> int64 [B] (on text's device): per sample, the rows in front of its padding = Tt minus the length of the trailing run
-    of rows that equal the LAST row bit for bit (compared as integers: no tolerance, -0 != +0, a NaN equals itself).  The reference
-    re-pads every prompt with zero rows (pipeline_chronoedit.py:230-237); any constant padding row is found the same way.  A last row that is
-    unlike its predecessor is a run of one: the sample has no padding to speak of."""
-    B, Tt = text.shape[0], text.shape[1]
-    bits = text.contiguous().view(_INT_OF_SIZE[text.element_size()]).reshape(B, Tt, -1)
-    differs = (bits != bits[:, -1:, :]).any(-1)  # [B, Tt]; False at the last row
-    idx = torch.arange(1, Tt + 1, device=text.device).expand(B, Tt)
-    return torch.where(differs, idx, torch.zeros_like(idx)).amax(1)  # one past the last row that differs from the last row
-
-
-def text_compaction_plan(real: Sequence[int], Tt: int):
-    """real = rows in front of the padding per sample -> (Lc, valid, log2 weights) or None when nothing is saved.  Sample b keeps its real
-    rows and ONE padding row that stands for all Tt - real[b] of them (valid = real + 1, weight log2(Tt - real)); a sample whose trailing
-    run is a single row keeps everything (valid = Tt, weight 0).  Lc = the largest valid count rounded up to 8 (the transposed-V projection
-    wants its columns in multiples of 8 with even per-sample strides).  None unless every sample walks at least one 64-key tile less."""
-    valid = [min(int(n) + 1, Tt) for n in real]
-    Lc = (max(valid) + 7) // 8 * 8
-    if Lc > Tt or (max(valid) + 63) // 64 >= (Tt + 63) // 64:
-        return None
-    return Lc, valid, [math.log2(Tt - v + 1) for v in valid]
-
-
-def compact_text_context(text: torch.Tensor):
-    """Find the padding of a text context [B, Tt, C] (one device-to-host read) and hang the compacted form on the tensor as
-    `text._ce_compact`: rows [0, Lc) of every sample (its real rows, the representative padding row, then rows the kernel masks), the valid
-    counts (int32) and log2 weights (fp32) on the device, and the tensor version they were taken at.  The engine picks it up when the SAME
-    tensor object reaches a forward (chronoedit_amd/transformer.py `_context`); a tensor without the attribute is never compacted.  Returns text."""
-    if getattr(text, "_ce_compact", None) is not None and text._ce_compact.version == text._version:
-        return text
-    info = SimpleNamespace(version=text._version, shape=tuple(text.shape), text=None, valid=None, w=None, Lc=0, real=None)
-    if text.dim() == 3 and text.shape[1] > 1 and text.is_floating_point():
-        Tt = text.shape[1]
-        info.real = [int(n) for n in text_real_lengths(text).tolist()]
-        plan = text_compaction_plan(info.real, Tt)
-        if plan is not None:
-            info.Lc, valid, w = plan
-            info.text = text[:, : info.Lc].contiguous()
-            info.valid = torch.tensor(valid, dtype=torch.int32, device=text.device)
-            info.w = torch.tensor(w, dtype=torch.float32, device=text.device)
-    text._ce_compact = info
-    return text
-
-
-def make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds):
-    """[cond | uncond] conditioning stacked along the batch axis; build it ONCE per edit so that the transformer's
-    context cache (step-invariant text/image K/V) can recognise the tensors across steps.  The text padding is found here, once
-    (`compact_text_context`): the stacked text tensor carries its compacted form to the engine."""
-    text2 = compact_text_context(torch.cat([prompt_embeds, negative_prompt_embeds], 0))
-    image2 = None if image_embeds is None else torch.cat([image_embeds, image_embeds], 0)
-    return text2, image2
-
-
-@contextlib.contextmanager
-def _shared_inputs(transformer):
-    """Declare, for the forwards inside, that the two halves of the batch carry the same latents, timestep and image embedding and differ in the
-    text context only - what `make_cfg_inputs` and the loops below build.  The engine then runs the pair's common work once
-    (ChronoEditTransformer3DModel.enable_shared_guidance); a transformer without the attribute is left alone.  Cleared on the way out: a
-    forward from anywhere else never shares."""
-    if not hasattr(transformer, "_shared_inputs"):
-        yield
-        return
-    transformer._shared_inputs = True
-    try:
-        yield
-    finally:
-        transformer._shared_inputs = None
-
-
-def _token_sharded(transformer) -> bool:
-    sp = getattr(transformer, "_sp", None)
-    return sp is not None and sp.sharded
-
-
-def _capturable(transformer) -> bool:
-    """Can a step of this transformer be captured into a hipGraph?  Unsharded: yes.  Token-sharded: only when the exchanges run on the
-    library-owned RCCL communicator (`enable_sequence_parallel(owned_comm=True)`, parallel.OwnedComm); CFG parallelism (its pairwise
-    exchange is a torch.distributed collective) runs eagerly."""
-    if getattr(transformer, "_cfgp", None) is not None:
-        return False
-    if not _token_sharded(transformer):
-        return True
-    return bool(getattr(transformer._sp, "capturable", False))
-
-
-def _sharded_batchable(transformer) -> bool:
-    """Can a token-sharded (Ulysses) forward take the guidance pair as ONE batch of two?  Yes on the V^T attention path (the
-    blocked-layout kernels, chronoedit_amd/parallel.py) - with bf16 or fp8 GEMMs; the sharded self-attention itself is always the
-    bf16 kernel (transformer.attention_path()).  The register-staged attention kernel runs the passes in sequence."""
-    return bool(getattr(transformer, "v_transposed", False) and getattr(transformer, "sp_batch_cfg", True))
-
-
-@torch.no_grad()
-def denoise_step(transformer: ChronoEditTransformer3DModel, scheduler: FlowUniPCMultistepScheduler, latents: torch.Tensor,
-                 condition: torch.Tensor, t: torch.Tensor, prompt_embeds: torch.Tensor,
-                 negative_prompt_embeds: Optional[torch.Tensor], image_embeds: Optional[torch.Tensor],
-                 guidance_scale: float, batch_cfg: bool = True, cfg_inputs=None, guidance_kind: Optional[str] = None,
-                 delta: Optional[torch.Tensor] = None, delta_measure=None) -> torch.Tensor:
-    """latents fp32 [B,16,T,h,w] (updated in place), condition bf16 [B,20,T,h,w]  (pipeline_chronoedit.py:711-739).
-    guidance_kind (guidance reuse, chronoedit_amd/guidance.py; needs the bf16 `delta` buffer of the latents' shape): "pair" = the guided
-    step as ever, which also stores the guidance direction in `delta` (delta_measure = (slot, table, row): into that slot of a ring, with
-    the distance sums); "reuse" = the conditional sample alone, guided by the stored direction; "off" = the conditional sample alone,
-    unguided.  None: the plain step."""
-    if guidance_kind not in (None, "pair", "reuse", "off"):
-        raise ValueError(f"denoise_step: guidance_kind {guidance_kind!r} is none of 'pair', 'reuse', 'off'")
-    if guidance_kind in ("pair", "reuse") and (delta is None or not (guidance_scale > 1.0 and negative_prompt_embeds is not None)):
-        raise ValueError(f"denoise_step: a {guidance_kind!r} step needs a guided edit and its delta buffer")
-    latent_model_input = torch.cat([latents.to(torch.bfloat16), condition], dim=1)
-    B = latents.shape[0]
-    timestep = t.expand(B)
-    batch_cfg = batch_cfg and (not _token_sharded(transformer) or _sharded_batchable(transformer))
-    cfgp = getattr(transformer, "_cfgp", None)
-    if guidance_scale > 1.0 and negative_prompt_embeds is not None and guidance_kind not in ("reuse", "off"):  # do_classifier_free_guidance
-        if cfgp is not None:
-            # CFG parallelism: this rank's Ulysses group runs ONE of the two passes, the predictions are exchanged pairwise
-            text = prompt_embeds if cfgp.branch == 0 else negative_prompt_embeds
-            mine = transformer(latent_model_input, timestep, text, image_embeds, return_dict=False)[0]
-            noise_pred, noise_uncond = cfgp.exchange(mine)
-        elif batch_cfg:
-            # the conditional and unconditional passes (pipeline_chronoedit.py:715-735) as ONE forward over 2B samples:
-            # identical per-sample arithmetic, but every weight streams from HBM once and the GEMM grids fill the chip
-            text2, image2 = cfg_inputs if cfg_inputs is not None else make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds)
-            with _shared_inputs(transformer):  # both halves of the batch: the same latents, timestep and image embedding (built right here)
-                out = transformer(torch.cat([latent_model_input, latent_model_input], 0), torch.cat([timestep, timestep], 0),
-                                  text2, image2, return_dict=False)[0]
-            noise_pred, noise_uncond = out[:B].contiguous(), out[B:].contiguous()
-        else:
-            noise_pred = transformer(latent_model_input, timestep, prompt_embeds, image_embeds, return_dict=False)[0]
-            noise_uncond = transformer(latent_model_input, timestep, negative_prompt_embeds, image_embeds, return_dict=False)[0]
-    else:
-        compact_text_context(prompt_embeds)  # (examined once per tensor version: later steps find the attribute)
-        noise_pred = transformer(latent_model_input, timestep, prompt_embeds, image_embeds, return_dict=False)[0]
-        noise_uncond = None
-    if guidance_kind in ("pair", "reuse"):
-        mode = "reuse" if guidance_kind == "reuse" else "store" if delta_measure is None else "measure"
-        return scheduler.step_cfg(noise_pred, noise_uncond, guidance_scale, latents, delta=delta, delta_mode=mode, delta_measure=delta_measure)
-    return scheduler.step_cfg(noise_pred, noise_uncond, guidance_scale, latents)
-
-
-_WARMUP_STREAMS = {}
-
-
-def _warmup_stream(dev: torch.device) -> "torch.cuda.Stream":
-    """The side stream the un-captured step in front of a capture runs on - one per device for the life of the process (a fresh stream per
-    GraphedDenoiser left a 64 MiB split-K scratch registered for each of them: ADVICE r4)."""
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    st = _WARMUP_STREAMS.get(key)
-    if st is None:
-        st = _WARMUP_STREAMS[key] = torch.cuda.Stream(device=dev)
-    return st
-
-
-class GraphedDenoiser:
-    """One denoising step captured as a hipGraph and replayed per step (north star: "the 50-step / 8-step sampling loops
-    are hipGraph-captured").  Everything a step reads lives at fixed device addresses: the fp32 latents (updated in place),
-    the condition, the stacked CFG conditioning, the scheduler history, and two small staging buffers that receive the
-    step's timestep and UniPC coefficient row (device-to-device copies enqueued in front of the replay - no host sync).
-    A new graph is needed when the latent shape changes (temporal-reasoning truncation 8 -> 2 frames).
-    `step(i)` raises RuntimeError when the object was built at one step index with keep_warmup_step=True (that step ran eagerly in the
-    constructor) and the first `step()` asks for another index: build it at the index it starts from.  Between construction and the last
-    `step()` the transformer's modes (fp8, sequence parallelism, cache_context) must not change; other forwards of the same transformer
-    are allowed (the lazy capture re-primes its context entry).
-    With a TeaCache plan (`tea_plan`, chronoedit_amd/teacache.py: one bool per step of the schedule, True = compute) the computed steps replay
-    one graph and the skipped steps a second one, captured lazily at the first skipped step; both address the engine's one residual buffer.
-    With a guidance-reuse plan (`guidance_plan`, chronoedit_amd/guidance.py: "pair" / "reuse" / "off" per step, and the loop's `delta` buffer)
-    there is one graph per kind of step the plan contains, each captured lazily at the first step of its kind that is replayed; all of them
-    address the same latents, scheduler history, staging buffers and delta buffer.  "reuse" and "off" run ONE sample where "pair" runs two: the
-    first step of either form on an engine that has not run it yet (`is_warm`) runs eagerly, for real, before that form is captured.
-    With a sparse-region plan (`sparse_plan`, chronoedit_amd/sparse_region.py: "compute" / "refresh" / "sparse" per step; the engine's
-    `sparse_begin` has been called for this edit) there is likewise one graph per kind, captured lazily; all address the engine's one K / V^T
-    cache.  The first sparse step on an engine that has not run a sparse step of this geometry (`sparse_is_warm`) runs eagerly."""
-
-    def __init__(self, transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
-                 guidance_scale: float, batch_cfg: bool = True, warm: bool = False, keep_warmup_step: bool = True, tea_plan=None,
-                 guidance_plan=None, delta: Optional[torch.Tensor] = None, region=None, sparse_plan=None):
-        """warm: this process has already run a step of exactly this shape / guidance form through `transformer` (packed weights,
-        workspaces, kernel attributes exist), so no un-captured step is needed in front of the capture; only the step-invariant context
-        projections are computed eagerly so that the graph holds the cache HIT (`cache_context`), not the projections.
-        Not warm: the un-captured step that triggers the lazy initialisations IS the trajectory's current step (it runs eagerly on the
-        live state, `step()` then skips the replay for that index) - a discarded warm-up cost a whole step per new shape: 2 s of a
-        temporal-reasoning edit at 28 800 tokens, 12 % of an 8-step edit.  keep_warmup_step=False: run it on saved state and put the
-        state back (a caller that wants every `step()` to be a replay: bench.py).
-        region: the edit's region.RegionState, or None.  Every kind of step then ends with the region blend, inside its graph; the blend
-        reads its sigma from the state's staging float, which `_stage` fills next to the coefficient row."""
-        assert latents.dtype == torch.float32 and latents.is_contiguous()
-        if not _capturable(transformer):
-            # Measured on this stack (ROCm 7.0 / RCCL 2.26 / torch 2.10: tools/rccl_graph_probe.py, profiles/r03_rccl_graph_probe.txt): ONE
-            # collective of torch.distributed's "nccl" backend can be captured and replayed, but the process-group watchdog thread keeps
-            # polling the event of every Work created under capture - the next capture (or any later poll) kills the process
-            # (hipErrorStreamCaptureUnsupported in "global" capture mode, a segmentation fault in "thread_local" / "relaxed"), with
-            # synchronous collectives, async_op=True and side-stream fork / join alike.  A sharded loop needs two graphs (8 -> 2 frames), so it
-            # runs eagerly on torch's communicator; DESIGN.md section 6 has the measurement of why that costs nothing at the per-rank kernel
-            # times of 4 / 8 GPUs.  The way to capture it: the library-owned communicator (`enable_sequence_parallel(owned_comm=True)`).
-            raise NotImplementedError("hipGraph capture of a step with torch.distributed exchanges is not usable on this torch / RCCL build: "
-                                      "enable_sequence_parallel(owned_comm=True) or run the sharded loop eagerly")
-        self.tr, self.sch, self.latents, self.condition = transformer, scheduler, latents, condition
-        self.region = region
-        self._ran_eagerly = set()  # sample counts (1: the single sample, 2: the stacked pair) this object has run an eager step of
-        self.prompt, self.negative, self.image, self.g, self.batch_cfg = prompt_embeds, negative_prompt_embeds, image_embeds, guidance_scale, batch_cfg
-        dev = latents.device
-        self.cfg_inputs = None
-        self.guided = guidance_scale > 1.0 and negative_prompt_embeds is not None
-        if self.guided and batch_cfg:
-            self.cfg_inputs = make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds)
-        elif not self.guided:
-            compact_text_context(prompt_embeds)  # (here, not under the capture: it reads the lengths back)
-        self.guidance_plan = None if guidance_plan is None or not self.guided else [str(k) for k in guidance_plan]
-        self.delta = delta
-        if self.guidance_plan is not None:
-            if tea_plan is not None:
-                raise ValueError("guidance reuse and TeaCache exclude each other")
-            if delta is None or delta.shape != latents.shape or delta.dtype != torch.bfloat16 or not delta.is_contiguous():
-                raise ValueError("guidance reuse: the delta buffer must be a contiguous bf16 tensor of the latents' shape")
-            if any(k != "pair" for k in self.guidance_plan):
-                compact_text_context(prompt_embeds)  # the single-sample steps' context, examined once, outside any capture
-        self.tea_plan = None if tea_plan is None else [bool(c) for c in tea_plan]
-        self.sparse_plan = None if sparse_plan is None else [str(k) for k in sparse_plan]
-        if self.sparse_plan is not None:
-            if tea_plan is not None or self.guidance_plan is not None:
-                raise ValueError("a sparse region plan excludes TeaCache and guidance reuse")
-            if region is None:
-                raise ValueError("a sparse region plan needs the edit's region")
-        if self.tea_plan is not None and self.guided and self.cfg_inputs is None:
-            raise NotImplementedError("TeaCache needs the guidance pair as ONE batched forward (one residual buffer covers both samples)")
-        self.t_buf = torch.zeros((), dtype=torch.int64, device=dev)
-        self.coef_buf = torch.zeros(10, dtype=torch.float32, device=dev)
-        scheduler._ensure_state(latents)
-        if scheduler.last_sample is None:
-            scheduler.last_sample = torch.zeros_like(latents)
-        idx0 = scheduler._step_index
-        self._stage(idx0 or 0)
-        kind0 = self._kind(idx0 or 0)
-        self._caller_warm = bool(warm)
-        warm = self._form_warm(kind0)
-        self._done_index = None  # the step that already ran eagerly (below); step() does not replay it
-        if not warm:
-            # lazy initialisations (packed weights, workspaces, function attributes) must not happen under capture: run the CURRENT step
-            # eagerly, for real, on a side stream as torch asks of anything that precedes a capture
-            saved = None if keep_warmup_step else (latents.clone(), [m.clone() for m in scheduler.model_outputs], scheduler.last_sample.clone())
-            side = _warmup_stream(dev)  # ONE long-lived side stream per device: every stream GEMMs run on gets a split-K scratch of its own (ops._gemm_scratch)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._body(kind0)
-            torch.cuda.current_stream().wait_stream(side)
-            self._ran_eagerly.add(self._form(kind0))
-            if keep_warmup_step:
-                self._done_index = idx0 or 0
-            else:
-                self.latents.copy_(saved[0])
-                for m, sv in zip(scheduler.model_outputs, saved[1]):
-                    m.copy_(sv)
-                scheduler.last_sample.copy_(saved[2])
-        else:
-            self._prime_context(kind0)
-        # The capture: at once when every step() must be a replay (warm shape, or keep_warmup_step=False); LAZILY - at the first step() that needs a
-        # replay - when the constructor already ran the trajectory's current step eagerly: if that was the last step of this shape (truncation lands
-        # there, or a callback replaces the latents every step) nothing is ever replayed and a whole capture would be thrown away (ADVICE r4)
-        self.graphs = {}  # kind of step -> captured graph
-        if self._done_index is None:
-            self._capture(kind0)
-        scheduler._step_index = idx0  # step_cfg counts on the host, also while being captured
-
-    @property
-    def graph(self):
-        """The step that runs the whole model on the edit's usual form (with TeaCache: the computed steps; with guidance reuse: "pair")."""
-        return self.graphs.get("compute", self.graphs.get("pair"))
-
-    @property
-    def skip_graph(self):
-        """TeaCache: the skipped steps."""
-        return self.graphs.get("skip")
-
-    def _single(self, kind: str) -> bool:
-        """Does a step of this kind run the conditional sample alone?"""
-        return not self.guided or kind in ("reuse", "off")
-
-    def _n_samples(self, kind: str) -> int:
-        return self.latents.shape[0] * (2 if self.cfg_inputs is not None and not self._single(kind) else 1)
-
-    def _form(self, kind: str):
-        """What an eager step of this kind warms: the sample count of a dense forward, or the sparse forward."""
-        return "sparse" if kind == "sparse" else self._n_samples(kind)
-
-    def _form_warm(self, kind: str) -> bool:
-        """May a step of this kind be captured without an eager step of its form in front?  Yes when this object already ran one, or when the
-        caller vouches for the edit's shape (`warm`) and the engine holds the workspace of exactly this sample count.  A sparse step: when
-        the engine has run one of this edit's geometry."""
-        n = self._form(kind)
-        if n in self._ran_eagerly:
-            return True
-        eng = getattr(self.tr, "_engine", None)
-        if kind == "sparse":
-            return bool(eng is not None and eng.sparse_is_warm())
-        return bool(self._caller_warm and eng is not None and hasattr(eng, "is_warm") and eng.is_warm(n, *self.latents.shape[2:]))
-
-    def _prime_context(self, kind: str = "compute"):
-        """With `cache_context`: the step-invariant context projections of THIS conditioning, in the form a step of this kind looks up,
-        computed eagerly now, so that the capture records the cache hit and not the projections."""
-        tr = self.tr
-        if hasattr(tr, "prime_context"):  # (without `cache_context` it only reserves the buffers of a compacted text context)
-            if self._single(kind):
-                if not self.guided or self.guidance_plan is not None:
-                    tr.prime_context(self.prompt, self.image)
-            elif self.cfg_inputs is not None:
-                with _shared_inputs(tr):  # (the entry the captured forward will look up)
-                    tr.prime_context(self.cfg_inputs[0], self.cfg_inputs[1])
-
-    def _kind(self, i: int) -> str:
-        """The kind of step i: which graph replays it."""
-        if self.guidance_plan is not None:
-            return self.guidance_plan[i]
-        if self.sparse_plan is not None:
-            return self.sparse_plan[i]
-        return "skip" if self.tea_plan is not None and not self.tea_plan[i] else "compute"
-
-    def _capture(self, kind: str = "compute"):
-        # The LAZY capture (first replayed step()) runs at an arbitrary later point of the caller's program: another forward of the same
-        # transformer in between (another conditioning of the same shape) may have replaced the context-cache entry and the engine-owned
-        # context buffers the eager step left, so the entry is re-primed here (a hit costs nothing) - ADVICE r5.  torch.cuda.graph() itself
-        # synchronises the device and runs a gc pass: callers that cannot afford that inside their loop build with keep_warmup_step=False
-        # (capture in the constructor).
-        self._prime_context(kind)
-        if self.tea_plan is not None:  # the residual buffer both graphs address exists before either is captured
-            self.tr.engine().tea_reserve(self.latents.shape[0] * (2 if self.cfg_inputs is not None else 1) * self._tokens())
-        idx = self.sch._step_index
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):  # (a capture executes nothing: the device state stays what the eager step left)
-            self._body(kind)
-        self.sch._step_index = idx
-        self.graphs[kind] = graph
-
-    def _tokens(self) -> int:
-        _, _, T, h, w = self.latents.shape
-        return T * (h // 2) * (w // 2)
-
-    def _stage(self, i):
-        self.t_buf.copy_(self.sch.timesteps[i])
-        self.coef_buf.copy_(self.sch.coef_row(i, self.g, self.latents.device))
-        if self.region is not None:
-            self.region.stage(i)
-
-    def _body(self, kind: str = "compute"):
-        if self.sparse_plan is not None:
-            self.tr._sparse_mode = kind if kind in ("refresh", "sparse") else None
-            try:
-                return self._step_body(kind)
-            finally:
-                self.tr._sparse_mode = None  # a forward outside the loop runs the whole model
-        if self.tea_plan is None:
-            return self._step_body(kind)
-        self.tr._tea_mode = "skip" if kind == "skip" else "compute"
-        try:
-            return self._step_body(kind)
-        finally:
-            self.tr._tea_mode = None  # a forward outside the loop runs the whole model
-
-    def _step_body(self, kind: str = "compute"):
-        """One step of any kind - pair, reuse, off, TeaCache compute or skip, sparse-region refresh or sparse, captured or eager: the model and the scheduler update,
-        then, with a region, the blend (chronoedit_amd/region.py)."""
-        self._model_step(kind)
-        if self.region is not None:
-            self.region.blend(self.latents)
-
-    def _model_step(self, kind: str = "compute"):
-        inp = torch.cat([self.latents.to(torch.bfloat16), self.condition], dim=1)
-        B = inp.shape[0]
-        ts = self.t_buf.expand(B)
-        if self.guided and self._single(kind):  # guidance reuse: the conditional sample alone
-            c = self.tr(inp, ts, self.prompt, self.image, return_dict=False)[0]
-            if kind == "reuse":
-                self.sch.step_cfg(c, None, self.g, self.latents, coef=self.coef_buf, delta=self.delta, delta_mode="reuse")
-            else:
-                self.sch.step_cfg(c, None, self.g, self.latents, coef=self.coef_buf)
-            return
-        if self.cfg_inputs is not None:
-            with _shared_inputs(self.tr):
-                out = self.tr(torch.cat([inp, inp], 0), torch.cat([ts, ts], 0), self.cfg_inputs[0], self.cfg_inputs[1], return_dict=False)[0]
-            c, u = out[:B].contiguous(), out[B:].contiguous()
-        elif self.guided:
-            c = self.tr(inp, ts, self.prompt, self.image, return_dict=False)[0]
-            u = self.tr(inp, ts, self.negative, self.image, return_dict=False)[0]
-        else:
-            c, u = self.tr(inp, ts, self.prompt, self.image, return_dict=False)[0], None
-        if kind == "pair":
-            self.sch.step_cfg(c, u, self.g, self.latents, coef=self.coef_buf, delta=self.delta, delta_mode="store")
-        else:
-            self.sch.step_cfg(c, u, self.g, self.latents, coef=self.coef_buf)
-
-    def step(self, i: int) -> torch.Tensor:
-        if self._done_index is not None:  # the constructor already ran ONE real step (index _done_index) eagerly on the live state
-            if i != self._done_index:
-                # a caller that re-seeded the latents or starts elsewhere would silently get a trajectory with one extra step (ADVICE r4)
-                raise RuntimeError(f"GraphedDenoiser was built at step {self._done_index} (which it ran eagerly, keep_warmup_step=True) but step({i}) "
-                                   "was asked first: build it at the step it starts from, or with keep_warmup_step=False")
-            self._done_index = None
-            self.sch._step_index = i + 1
-            return self.latents
-        kind = self._kind(i)
-        if kind not in self.graphs:
-            if not self._form_warm(kind):
-                # this form (the single sample after pairs, or the other way round) has not run on this engine yet: its lazy initialisations
-                # must not happen under capture, so THIS step runs eagerly, on the live state, as the constructor's first step does
-                self._stage(i)
-                self.sch._step_index = i
-                side = _warmup_stream(self.latents.device)
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    self._body(kind)
-                torch.cuda.current_stream().wait_stream(side)
-                self._ran_eagerly.add(self._form(kind))
-                self.sch._step_index = i + 1
-                return self.latents
-            self._capture(kind)
-        self._stage(i)
-        self.graphs[kind].replay()
-        self.sch._step_index = i + 1
-        return self.latents
-
-
-@torch.no_grad()
-def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
-            num_inference_steps: int, guidance_scale: float = 5.0, enable_temporal_reasoning: bool = False,
-            num_temporal_reasoning_steps: int = 0, use_graph: bool = False, on_step_end=None, interrupted=None, graph_warm=None,
-            teacache=None, teacache_measure: bool = False, guidance_reuse=None, guidance_measure: Optional[int] = None,
-            keep_deltas: bool = False, region=None, sparse_region=None, auto_region=None, start_step: int = 0, start_eps=None,
-            preview=None):
-    """The whole loop, including the temporal-reasoning truncation 8 -> 2 latent frames (pipeline_chronoedit.py:700-709).
-    on_step_end(i, t, latents) -> replacement latents, a dict with any of latents / prompt_embeds / negative_prompt_embeds, or None
-    (the reference's callback_on_step_end hook, :741-749); graph_warm: a set the caller keeps across edits - shapes already run once in
-    this process skip GraphedDenoiser's warm-up step;
-    interrupted() -> True skips the remaining steps (`self.interrupt`, :697-698).  With the tokens sharded over ranks
-    (Ulysses) every rank holds the replicated latents and scheduler history, so the truncation is a local slice on every
-    rank (the reference all-gathers and re-shards: chronoedit_14b_edit_model.py:168-186) and the next forward simply shards
-    the shorter sequence.
-    teacache: a teacache.TeaCacheConfig for this call; None = whatever `transformer.enable_teacache()` set (nothing: no step is skipped).
-    The compute / skip plan of the whole edit is made here, before the first step (the truncation step always computes: the 8-frame
-    residual does not fit 2-frame tokens); afterwards `transformer.teacache_report` holds {"plan", "computed", "skipped", "ratios"}.
-    teacache_measure (or `transformer.calibrate_teacache` around the call): calibration instead of skipping.  Every step computes - the
-    latents are the plain loop's - and the pass that stores the block stack's residual also measures its relative L1 distance to the previous
-    step's residual, on the device, into a table read back once after the last step: afterwards `transformer.teacache_measurement` holds
-    {"ratios": teacache_ratios(timesteps), "distances": per step, NaN for step 0 and for the first step after the truncation} - the points
-    teacache.fit_calibration fits.  A measured edit always runs eagerly (`use_graph` is ignored: the table row changes per step, and
-    calibration is offline).  Together with a skip plan (`teacache=` or an enabled TeaCache) it is a ValueError.
-    guidance_reuse: a guidance.GuidanceReuseConfig for this call; None = whatever `transformer.enable_guidance_reuse()` set (nothing: every
-    guided step runs the pair).  The "pair" / "reuse" / "off" plan of the whole edit is made here, before the first step, from the schedule
-    alone (the truncation step is always a "pair": an 8-frame direction does not fit 2-frame latents); afterwards
-    `transformer.guidance_report` holds {"plan", "pair", "reuse", "off"}.  An edit without guidance ignores the config and its report is
-    None.  The stored direction is one bf16 tensor of the latents' shape that this loop owns: a second edit never sees the first one's.  A
-    callback that replaces the latents keeps it; one that replaces an embedding makes the next guided step a "pair".  With TeaCache (enabled
-    or measuring) it is a ValueError, with sharded tokens or CFG parallelism a NotImplementedError.
-    guidance_measure = A (1..4): every step a "pair" whose store pass also measures, on the device, how far the direction is from those
-    of the 1..A steps before; one read-back after the last step.  The latents are the plain loop's; runs eagerly.  Afterwards
-    `transformer.guidance_measurement` holds {"timesteps", "rel_l2": [steps][A] (NaN where no direction of that age and shape exists)} and,
-    with keep_deltas, "deltas": the per-step directions (bf16, on the CPU).
-    region: a region.RegionConfig (w = fp32 [h, w] box-mean weights of the mask, z_src = fp32 static-source latents of the latents' shape)
-    for a region-limited edit; None = the plain loop, launch for launch.  The loop takes eps = a copy of the latents it starts from and the
-    schedule's sigma_next table itself (region.RegionState.begin).  After every step's scheduler update, before `on_step_end`, the sample
-    is blended in place: x = w * x + (1 - w) * ((1 - s) * z_src + s * eps), s = sigmas[i + 1] - inside the captured graph when `use_graph`
-    (one graph per kind of step, as without).  At the truncation z_src and eps are sliced like the latents.  Works with TeaCache, guidance
-    reuse and trajectory_dtype = bfloat16.  A callback that replaces the latents is taken at its word; the next step blends again.  With
-    sharded tokens or CFG parallelism a NotImplementedError.
-    sparse_region: a sparse_region.SparseRegionConfig for this call (needs `region=` or a detecting `auto_region=`: a ValueError without); None = whatever
-    `transformer.enable_sparse_region()` set, which an edit without a region ignores.  The "compute" / "refresh" / "sparse" plan of the whole
-    edit is made here, before the first step, from the schedule and the mask alone (every step up to and including the truncation step is a
-    "compute"; the active tokens are those of the shape behind it); afterwards `transformer.sparse_report` holds {"plan", "compute", "refresh",
-    "sparse", "active", "tokens"}, None for an edit without a plan.  A sparse step runs the model on the active token rows only, against the
-    K / V^T the last refresh step stored (DiTEngine.sparse_begin has the sizes); the blend keeps the source where w == 0 exactly, as ever.  A
-    callback that replaces the latents or an embedding makes the next step dense, and the plan is remade from there.  With TeaCache or guidance
-    reuse (enabled or measuring) it is a ValueError; with fp8 GEMMs or attention, without the transposed-V self-attention, with sharded
-    tokens or CFG parallelism a NotImplementedError.
-    auto_region: an auto_region.AutoRegion (the config - None: whatever `transformer.enable_auto_region()` set - and z_src = fp32
-    static-source latents of the latents' shape) for an edit that finds its own region; None = the plain loop, launch for launch.  An explicit `region=` wins: the detector is not run and the report is None.
-    The loop keeps a clone of the latents it starts from (the blend's eps); steps 0 .. k run as the plain loop (k = detect_step, or with
-    temporal reasoning the first step at or behind it that runs at the truncated shape; past the last step nothing is detected).  After
-    step k's scheduler update, before `on_step_end`, four device passes (csrc/ce_region_auto.hip) turn x0 = scheduler.model_outputs[-1]
-    and z_src into the weights w and the pixel mask, and ONE read brings w to the host.  Declined (no active cell, or more active patches
-    than max_area of the grid - with the sparse margin when a sparse region is enabled): the edit stays the plain loop, bit for bit.
-    Accepted: a RegionState is built from (w, z_src, eps, sigma_next), the blend runs after step k itself and after every later step,
-    the graphed loop is rebuilt (a region is another warm shape), and with a sparse region config the plan is made now, every step <= k
-    forced dense, so that step k + 1 is the first refresh.  Composition and refusals are those of an explicit region.  Afterwards
-    `transformer.auto_region_report` and `auto_region.report` hold {"step", "threshold", "dmax", "active_fraction", "accepted", "reason",
-    "w", "mask"} and `auto_region.mask_u8` the device mask of an accepted region.  auto_region.measure: every step runs the plain loop and
-    writes its change map into a [steps, h, w] device table, read back once after the last step: `transformer.auto_region_measurement`
-    then holds one row per step (auto_region.measurement).  auto_region.on_accept: a callable (the device pixel mask of an accepted
-    region) -> bool, asked before anything of the region is set up; True ends the loop behind step k (its `on_step_end` still runs) with
-    `auto_region.exited` set - the scout of an auto-focused edit (chronoedit_amd/autofocus.py); False, or none: as above.
-    start_step = b > 0: the loop runs the TAIL of the schedule, steps b .. n - 1, on latents the caller has brought to sigma[b]
-    (`scheduler.set_timesteps(n, begin=b)`: the history starts empty); every plan above is made from the tail's arrays, `on_step_end` is
-    told i + b.  start_eps: the region blend's eps instead of a copy of the incoming latents - which, behind a warm start, are no longer
-    the noise.  start_step=0 is the loop as ever, launch for launch.  With temporal reasoning or a detecting auto_region a ValueError.
-    preview: a preview.PreviewConfig for live previews; None = the loop as it is, launch for launch.  A step is previewed when
-    (i + 1) % every == 0, or when it is the last: behind the scheduler update and the region blend, before `on_step_end`, ONE launch
-    (csrc/ce_preview.hip, outside the captured graph) turns latent frame `frame` of scheduler.model_outputs[-1] - the estimate of the final
-    image, a stable buffer under replay - into bytes, an asynchronous copy brings them into a pinned buffer, an event marks it.  With a
-    region (explicit, or accepted: from step k on) and `composite` the kept cells show z_src; under a sparse plan always.  The preview of
-    step i is handed to `on_preview` - {"step": i + start_step, "timestep", "image": PIL RGB} - once step i + lag has been enqueued, in
-    ascending order, once each; everything outstanding before the loop returns (an interrupt and a scout's exit included).  The loop only
-    reads its state for this: the latents are the plain loop's.  With sharded tokens or CFG parallelism a NotImplementedError."""
-    start_step = int(start_step)
-    if start_step:
-        if enable_temporal_reasoning or (auto_region is not None and region is None):
-            raise ValueError("denoise: start_step > 0 goes with neither temporal reasoning nor a detecting auto_region (their step indices "
-                             "count from the head of the schedule)")
-        scheduler.set_timesteps(num_inference_steps, device=latents.device, begin=start_step)
-    else:
-        scheduler.set_timesteps(num_inference_steps, device=latents.device)
-    latents = latents.to(torch.float32).contiguous()
-    pv = None
-    if preview is not None:
-        if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
-            raise NotImplementedError("live previews with the tokens sharded over ranks or with CFG parallelism are not implemented "
-                                      "(nothing sharded has been tested with them)")
-        from . import preview as _pv
-        pv = _pv.PreviewDelivery(preview, latents.device, [int(v) for v in scheduler.timesteps.tolist()])  # (one read, before the first step)
-    auto = auto_region if region is None else None  # an explicit mask wins
-    a_cfg = None
-    if auto is not None:  # (no config of its own: whatever `transformer.enable_auto_region()` set - nothing: the plain loop)
-        a_cfg = auto.config if auto.config is not None else getattr(transformer, "_auto_region", None)
-        if a_cfg is None:
-            auto = None
-    if hasattr(transformer, "auto_region_report"):
-        transformer.auto_region_report = None
-    if auto_region is not None:
-        auto_region.report = auto_region.mask_u8 = None
-    auto_k = auto_z = auto_eps = auto_table = None
-    if auto is not None:
-        if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
-            raise NotImplementedError("an edit region with the tokens sharded over ranks or with CFG parallelism is not implemented "
-                                      "(the blend runs on replicated latents; nothing sharded has been tested with it)")
-        from . import auto_region as _ar
-        if tuple(auto.z_src.shape) != tuple(latents.shape):
-            raise ValueError(f"auto region: z_src {tuple(auto.z_src.shape)} does not have the latents' shape {tuple(latents.shape)}")
-        auto_z = auto.z_src.to(device=latents.device, dtype=torch.float32).contiguous()
-        if auto.measure:
-            auto_table = torch.zeros((len(scheduler.timesteps),) + tuple(latents.shape[-2:]), dtype=torch.float32, device=latents.device)
-        else:
-            auto_k = _ar.detect_index(a_cfg, len(scheduler.timesteps), enable_temporal_reasoning, num_temporal_reasoning_steps)
-            auto_eps = latents.clone()  # the blend's eps, should a region be found
-    detecting = auto is not None and not auto.measure
-    region_state = None
-    if region is not None:
-        if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
-            raise NotImplementedError("an edit region with the tokens sharded over ranks or with CFG parallelism is not implemented "
-                                      "(the blend runs on replicated latents; nothing sharded has been tested with it)")
-        from . import region as _rg
-        region_state = _rg.RegionState.begin(region, latents if start_eps is None else start_eps.to(latents.device), scheduler)
-    sharded = getattr(transformer, "_cfgp", None) is not None or (_token_sharded(transformer) and not _sharded_batchable(transformer))
-    cfg_inputs = None
-    if guidance_scale > 1.0 and negative_prompt_embeds is not None and not sharded:
-        cfg_inputs = make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds)
-    if hasattr(transformer, "clear_context_cache"):
-        transformer.clear_context_cache()  # a new edit: nothing of the previous edit's conditioning may be reused
-    tea = teacache if teacache is not None else getattr(transformer, "_teacache", None)
-    measure = bool(teacache_measure or getattr(transformer, "_tea_measure", False))
-    # sparse region: what it needs and what it excludes, before anything of the edit is set up (the plan itself is made further down)
-    sr = sparse_region if sparse_region is not None else getattr(transformer, "_sparse_region", None)
-    if sparse_region is not None and region is None and not detecting:
-        raise ValueError("sparse_region needs the edit's region (region=): without a mask there are no inactive tokens to leave out")
-    if sr is not None and (region is not None or detecting) and (tea is not None or measure or guidance_reuse is not None or guidance_measure is not None
-                                                  or getattr(transformer, "_guidance_reuse", None) is not None):
-        raise ValueError("a sparse region plan and TeaCache or guidance reuse (enabled or measuring) exclude each other: their cached "
-                         "residual / direction covers all token rows of a step, a sparse step computes the active ones only")
-    if measure and tea is not None:
-        raise ValueError("TeaCache: measuring (teacache_measure / calibrate_teacache) and a skip plan (teacache= / enable_teacache) "
-                         "exclude each other: disable_teacache() first")
-    # -- guidance reuse: the plan of the edit, and the one buffer that holds the stored direction (loop-owned: dropped with the edit)
-    guided = guidance_scale > 1.0 and negative_prompt_embeds is not None
-    gr = guidance_reuse if guidance_reuse is not None else getattr(transformer, "_guidance_reuse", None)
-    g_plan = delta = g_ring = g_table = None
-    g_forced = {int(num_temporal_reasoning_steps)} if enable_temporal_reasoning else set()
-    g_seen, g_history, g_kept = 0, [0] * len(scheduler.timesteps), []  # measuring: directions of this shape stored so far; per step, how many the ring held
-    if hasattr(transformer, "guidance_report"):
-        transformer.guidance_report = None
-    if guidance_measure is not None and not guided:
-        raise ValueError("guidance_measure needs a guided edit (guidance_scale > 1 and negative_prompt_embeds)")
-    if guided and (gr is not None or guidance_measure is not None):
-        from . import guidance as _gd
-        if tea is not None or measure:
-            raise ValueError("guidance reuse and TeaCache (enabled or measuring) exclude each other: the cached residual has the guidance "
-                             "pair's row count, which a single-sample step does not match")
-        if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
-            raise NotImplementedError("guidance reuse with the tokens sharded over ranks or with CFG parallelism is not implemented "
-                                      "(the stored direction is latent-local; nothing sharded has been tested with it)")
-        if guidance_measure is not None:
-            from . import ops as _ops
-            if guidance_reuse is not None:
-                raise ValueError("guidance_measure measures the plain loop (every step a pair): it takes no guidance_reuse plan")
-            if not 1 <= int(guidance_measure) <= _ops.CFG_MAX_AGE:
-                raise ValueError(f"guidance_measure: max_age must be in 1..{_ops.CFG_MAX_AGE}, got {guidance_measure}")
-            gr = _gd.GuidanceReuseConfig(pair_every=1)
-            use_graph = False  # the table row and the ring slot change per step, and measuring is offline
-            g_table = torch.full((len(scheduler.timesteps), int(guidance_measure) + 1), float("nan"), dtype=torch.float32, device=latents.device)
-        g_plan = _gd.plan(len(scheduler.timesteps), gr, g_forced)
-        transformer.guidance_report = _gd.report(g_plan)
-    delta_valid = False  # has a "pair" step of this edit, at this latent shape and conditioning, written the direction?
-    tea_plan = None
-    if tea is not None:
-        from . import teacache as _tea
-        if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
-            raise NotImplementedError("TeaCache with the tokens sharded over ranks or with CFG parallelism is not implemented "
-                                      "(the cached residual is row-local; nothing sharded has been tested with it)")
-        forced = {int(num_temporal_reasoning_steps)} if enable_temporal_reasoning else ()
-        ratios = transformer.teacache_ratios(scheduler.timesteps)  # the one device-to-host read of the edit
-        tea_plan = _tea.plan_from_ratios(ratios, len(scheduler.timesteps), tea.rel_l1_thresh, tea.coefficients, forced)
-        transformer.teacache_report = _tea.report(tea_plan, ratios)
-        transformer.engine().tea_drop()  # nothing of the previous edit's residual may be reused
-    if measure:
-        if getattr(transformer, "_cfgp", None) is not None or _token_sharded(transformer):
-            raise NotImplementedError("TeaCache with the tokens sharded over ranks or with CFG parallelism is not implemented "
-                                      "(the cached residual is row-local; nothing sharded has been tested with it)")
-        use_graph = False
-        tea_ratios = transformer.teacache_ratios(scheduler.timesteps)
-        transformer.engine().tea_measure_begin(len(scheduler.timesteps))
-    # -- sparse region: the plan of the edit, the active ids and the engine's cache (reserved here: before any capture)
-    s_plan, s_forced = None, set()
-    if hasattr(transformer, "sparse_report"):
-        transformer.sparse_report = None
-    s_ids = s_tokens = s_full = None
-    if sr is not None and (region is not None or detecting):
-        from . import sparse_region as _sr
-        transformer.engine().sparse_check()
-
-    def sparse_setup(w, forced, T_s):
-        """The plan, the active ids and the engine's cache for the weights w, at T_s latent frames (outside any capture)."""
-        ids, _ = _sr.active_tokens(w, T_s, sr.margin)  # (the one device-to-host read: the latent weights)
-        tokens = T_s * (latents.shape[3] // 2) * (latents.shape[4] // 2)
-        full = ids.numel() >= tokens or ids.numel() % _sr.PAD != 0  # the whole grid: nothing to leave out
-        plan_ = _sr.plan(len(scheduler.timesteps), sr, forced, full=full)
-        transformer.sparse_report = _sr.report(plan_, ids.numel(), tokens)
-        if "sparse" in plan_:
-            transformer.engine().sparse_begin(ids, latents.shape[0] * (2 if cfg_inputs is not None else 1), T_s, latents.shape[3], latents.shape[4])
-        return plan_, ids, tokens, full
-
-    if sr is not None and region is not None:
-        n_steps = len(scheduler.timesteps)
-        truncates = enable_temporal_reasoning and 0 <= int(num_temporal_reasoning_steps) < n_steps
-        if enable_temporal_reasoning:  # every step up to and including the truncation step: the cache is never built at the 8-frame shape
-            s_forced = set(range(min(int(num_temporal_reasoning_steps), n_steps - 1) + 1))
-        s_plan, s_ids, s_tokens, s_full = sparse_setup(region_state.w, s_forced, 2 if truncates else latents.shape[2])
-    graphed = None
-    if use_graph and not _capturable(transformer):
-        use_graph = False  # a step with torch.distributed exchanges runs eagerly (GraphedDenoiser says why); the pipeline default stays use_graph=True
-    exiting = False
-    for i, t in enumerate(scheduler.timesteps):
-        if exiting:
-            break
-        if interrupted is not None and interrupted():
-            continue
-        if enable_temporal_reasoning and i == num_temporal_reasoning_steps:
-            graphed = None  # new latent shape -> new graph
-            latents = latents[:, :, [0, -1]].contiguous()
-            condition = condition[:, :, [0, -1]].contiguous()
-            for j in range(len(scheduler.model_outputs)):
-                mo = scheduler.model_outputs[j]
-                if mo is not None and mo.shape[-3] != latents.shape[-3]:
-                    scheduler.model_outputs[j] = mo[:, :, [0, -1]].contiguous()
-            if scheduler.last_sample is not None and scheduler.last_sample.shape[-3] != latents.shape[-3]:
-                scheduler.last_sample = scheduler.last_sample[:, :, [0, -1]].contiguous()
-            if region_state is not None and region_state.eps.shape[-3] != latents.shape[-3]:
-                region_state.truncate()
-            if auto_z is not None and auto_z.shape[-3] != latents.shape[-3]:  # sliced exactly as the latents are
-                auto_z = auto_z[:, :, [0, -1]].contiguous()
-                auto_eps = None if auto_eps is None else auto_eps[:, :, [0, -1]].contiguous()
-        kind = None if g_plan is None else g_plan[i]
-        if g_plan is not None:
-            if g_table is not None:  # measuring: a ring of the last A directions of this latent shape
-                A = g_table.shape[1] - 1
-                if g_ring is None or g_ring.shape[1:] != latents.shape:
-                    g_ring, g_seen = torch.zeros((A,) + tuple(latents.shape), dtype=torch.bfloat16, device=latents.device), 0
-            elif delta is None or delta.shape != latents.shape:  # (re-made at the truncation; never under a capture)
-                delta, delta_valid = torch.zeros(latents.shape, dtype=torch.bfloat16, device=latents.device), False
-            if kind == "reuse" and not delta_valid:
-                raise RuntimeError(f"guidance reuse: step {i} is planned to reuse a direction no step has stored")
-        if use_graph:
-            if graphed is None:
-                if scheduler._step_index is None:
-                    scheduler._step_index = i
-                # engine_generation(): bumped whenever the transformer's engine, its workspaces or a mode that changes the launch sequence
-                # is replaced - a recycled id() or a mode switch that keeps the workspace key must not skip the eager warm-up step
-                def warm_key():
-                    gen = transformer.engine_generation() if hasattr(transformer, "engine_generation") else id(transformer)
-                    # (the scheduler object is not part of the key: everything a step reads from it is created eagerly by GraphedDenoiser
-                    # before the capture - _ensure_state, the staged timestep / coefficient row - so a fresh scheduler per edit stays warm)
-                    # (with guidance reuse: which forms - the stacked pair, the single sample - the rest of the plan runs; GraphedDenoiser
-                    # asks the engine per form on top of this)
-                    forms = None if g_plan is None else tuple(sorted({1 if k in ("reuse", "off") else 2 for k in g_plan[i:]}))
-                    return (tuple(latents.shape), guidance_scale > 1.0 and negative_prompt_embeds is not None, gen, tea_plan is not None, forms,
-                            region_state is not None)
-                graphed = GraphedDenoiser(transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds,
-                                          image_embeds, guidance_scale, batch_cfg=not sharded, warm=graph_warm is not None and warm_key() in graph_warm,
-                                          tea_plan=tea_plan, guidance_plan=g_plan, delta=delta, region=region_state, sparse_plan=s_plan)
-                if graph_warm is not None:
-                    graph_warm.add(warm_key())  # (taken AFTER the construction: the first step of a process creates the engine)
-            latents = graphed.step(i)
-        elif g_plan is not None:
-            dm = None
-            if g_table is not None:
-                dm = (g_seen % A, g_table, i)
-                g_history[i] = min(g_seen, A)
-            latents = denoise_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds,
-                                   image_embeds, guidance_scale, batch_cfg=not sharded, cfg_inputs=cfg_inputs, guidance_kind=kind,
-                                   delta=delta if g_table is None else g_ring, delta_measure=dm)
-            if g_table is not None:
-                if keep_deltas:
-                    g_kept.append(g_ring[g_seen % A].clone())
-                g_seen += 1
-        elif s_plan is not None:
-            transformer._sparse_mode = s_plan[i] if s_plan[i] in ("refresh", "sparse") else None
-            try:
-                latents = denoise_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds,
-                                       image_embeds, guidance_scale, batch_cfg=True, cfg_inputs=cfg_inputs)
-            finally:
-                transformer._sparse_mode = None  # a forward outside the loop runs the whole model
-        elif tea_plan is None and not measure:
-            latents = denoise_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds,
-                                   image_embeds, guidance_scale, batch_cfg=not sharded, cfg_inputs=cfg_inputs)
-        else:
-            if measure:
-                transformer.engine()._tea_row = i  # the row of the sums table this step's forward writes
-            transformer._tea_mode = "measure" if measure else "compute" if tea_plan[i] else "skip"
-            try:
-                latents = denoise_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds,
-                                       image_embeds, guidance_scale, batch_cfg=True, cfg_inputs=cfg_inputs)
-            finally:
-                transformer._tea_mode = None  # a forward outside the loop runs the whole model
-        if pv is not None and preview.lag > 0:
-            pv.deliver(i - preview.lag)  # step i is enqueued: the previews of the steps up to i - lag have had that long
-        if region_state is not None and not use_graph:  # (every eager branch above; a graphed step blends inside its graph)
-            region_state.blend(latents, i)
-        if auto_table is not None:  # measuring: this step's change map into its row of the table
-            from . import ops as _ops
-            _ops.auto_region_change(scheduler.model_outputs[-1], auto_z, -1, out=auto_table[i])
-        elif detecting and i == auto_k:
-            # the detection: four passes on the estimate of the final image the step kernel just wrote, one read, the decision
-            from . import region as _rg
-            a_w, a_mask, a_w_cpu, a_thr, a_dmax = _ar.detect(scheduler.model_outputs[-1], auto_z, a_cfg)
-            ok, why, frac = _ar.decide(a_w_cpu, a_cfg, sr.margin if sr is not None else 0)
-            auto.report = transformer.auto_region_report = _ar.report(i, a_thr, a_dmax, frac, ok, why, a_w_cpu)
-            if ok and auto.on_accept is not None and auto.on_accept(a_mask):
-                auto.mask_u8, auto.exited, exiting = a_mask, True, True  # the caller goes on from here (the history is as step k left it)
-            elif ok:
-                region_state = _rg.RegionState(a_w, auto_z, auto_eps, _rg.sigma_next_table(scheduler, latents.device),
-                                               bf16_state=scheduler.trajectory_dtype == torch.bfloat16)
-                auto.mask_u8 = a_mask
-                region_state.blend(latents, i)  # the blend after step k itself
-                graphed = None  # a region is a different warm shape, and every later step ends with the blend
-                if sr is not None:
-                    s_forced = set(range(i + 1))  # every step up to here ran dense: step k + 1 is the first refresh
-                    s_plan, s_ids, s_tokens, s_full = sparse_setup(a_w_cpu, s_forced, latents.shape[2])
-            auto_z = auto_eps = None
-        if pv is not None and _pv.due(i, len(scheduler.timesteps), preview.every):
-            # kept cells show the source when asked to - and always under a sparse plan, whose steps predict 0 outside the active tokens
-            comp = region_state is not None and (preview.composite or s_plan is not None)
-            pv.submit(i, i + start_step, scheduler.model_outputs[-1], region_state.w if comp else None, region_state.z_src if comp else None)
-            if preview.lag == 0:
-                pv.deliver(i)
-        if kind == "pair":
-            delta_valid = True
-        elif kind == "off":
-            delta_valid = False
-        if on_step_end is not None:
-            new = on_step_end(i + start_step, t, latents)
-            replaced = (isinstance(new, dict) and any(k in new for k in ("latents", "prompt_embeds", "negative_prompt_embeds"))) or \
-                (new is not None and not isinstance(new, dict) and new is not latents)
-            if s_plan is not None and replaced and i + 1 < len(s_plan):
-                # the cached K / V^T of the inactive tokens belong to the old latents / conditioning: the next step is dense and the count
-                # restarts behind it
-                s_forced = s_forced | {i + 1}
-                s_plan = s_plan[: i + 1] + _sr.plan(len(s_plan), sr, s_forced, full=s_full)[i + 1:]
-                transformer.sparse_report = _sr.report(s_plan, s_ids.numel(), s_tokens)
-                graphed = None  # (the graphed loop holds the plan it was built with)
-            if isinstance(new, dict):  # the reference's callback may also replace the conditioning (pipeline_chronoedit.py:747-749)
-                if "prompt_embeds" in new or "negative_prompt_embeds" in new:
-                    prompt_embeds = new.get("prompt_embeds", prompt_embeds)
-                    if negative_prompt_embeds is not None:
-                        negative_prompt_embeds = new.get("negative_prompt_embeds", negative_prompt_embeds)
-                    if cfg_inputs is not None:
-                        cfg_inputs = make_cfg_inputs(prompt_embeds, negative_prompt_embeds, image_embeds)
-                    graphed = None  # the graph holds the stacked conditioning it was captured with
-                    if g_plan is not None and g_table is None and i + 1 < len(g_plan):
-                        # the stored direction belongs to the old conditioning: the next guided step runs the pair, the count restarts there
-                        g_forced = g_forced | {i + 1}
-                        g_plan = g_plan[: i + 1] + _gd.plan(len(g_plan), gr, g_forced)[i + 1:]
-                        if g_plan[i + 1] == "reuse":  # (an inside step: forced)
-                            raise RuntimeError("guidance reuse: the re-planned step is not a pair")
-                        transformer.guidance_report = _gd.report(g_plan)
-                        delta_valid = False
-                new = new.get("latents")
-            if new is not None and new is not latents:
-                graphed = None  # the graph is tied to the latents' storage
-                latents = new.to(torch.float32).contiguous()
-    if pv is not None:
-        pv.flush()  # everything outstanding, before the loop returns
-    if measure:
-        from .teacache import distances_from_sums
-        sums = transformer.engine().tea_measure_end()  # the one read of the table, after the last step
-        transformer.teacache_measurement = {"ratios": [float(r) for r in tea_ratios], "distances": distances_from_sums(sums.numpy())}
-    if g_table is not None:
-        m = {"timesteps": [int(v) for v in scheduler.timesteps.tolist()],
-             "rel_l2": _gd.rel_l2_from_sums(g_table.cpu().numpy(), g_table.shape[1] - 1, g_history)}  # the one read of the table
-        if keep_deltas:
-            m["deltas"] = [d.cpu() for d in g_kept]
-        transformer.guidance_measurement = m
-    if auto_table is not None:
-        transformer.auto_region_measurement = {"timesteps": [int(v) for v in scheduler.timesteps.tolist()],
-                                               "steps": _ar.measurement(auto_table.cpu(), a_cfg)}  # the one read of the table
-    return latents
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -26,6 +26,8 @@ from typing import Optional
 
 import torch
 
+SHARDED = "an edit region with {} is not implemented (the blend runs on replicated latents; nothing sharded has been tested with it)"
+
 
 def normalize_mask(mask, height: int, width: int) -> torch.Tensor:
     """Whatever a caller may pass as a mask -> uint8 [height, width] on the CPU.
@@ -98,7 +100,7 @@ def sigma_next_table(scheduler, device=None) -> torch.Tensor:
 
 @dataclass
 class RegionConfig:
-    """What `pipeline.denoise(region=)` takes for ONE edit: w = fp32 [h, w] on the device (`latent_weights`), z_src = fp32 of the latents'
+    """What `loop.denoise(region=)` takes for ONE edit: w = fp32 [h, w] on the device (`latent_weights`), z_src = fp32 of the latents'
     shape (`static_source_latents`).  The loop itself adds what only it knows - the noise it starts from and the schedule's sigmas - and
     builds the `RegionState`."""
     w: torch.Tensor

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Iterable, List, Sequence, Tuple
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -117,3 +117,55 @@ def report(plan_: Sequence[str], n_active: int, n_tokens: int) -> dict:
     (padding included) and the tokens per sample of the shape the sparse steps run at."""
     plan_ = [str(k) for k in plan_]
     return {"plan": plan_, **{k: plan_.count(k) for k in KINDS}, "active": int(n_active), "tokens": int(n_tokens)}
+
+
+class SparseRegionState:
+    """The sparse region of one running edit (`loop.denoise(sparse_region=)`; needs `region=` or a detecting `auto_region=`: a ValueError
+    without).  config: a SparseRegionConfig for this call; None = whatever `transformer.enable_sparse_region()` set, which an edit without a
+    region ignores.  The "compute" / "refresh" / "sparse" plan of the whole edit is made in `setup` - before the first step for an explicit
+    region, behind the detecting step for an automatic one - from the schedule and the mask alone (every step in `forced` is dense: with
+    temporal reasoning every step up to and including the truncation step, with an automatic region every step up to the detecting one;
+    the active tokens are those of the shape the sparse steps run at); `transformer.sparse_report` then holds {"plan", "compute",
+    "refresh", "sparse", "active", "tokens"}, None for an edit without a plan.  A sparse step runs the model on the active token rows only,
+    against the K / V^T the last refresh step stored (DiTEngine.sparse_begin has the sizes); the blend keeps the source where w == 0
+    exactly, as ever.  A callback that replaces the latents or an embedding makes the next step dense, and the plan is remade from there
+    (`replaced`).  With TeaCache or guidance reuse (enabled or measuring) it is a ValueError (raised by the loop, in front of every
+    feature's setup); with fp8 GEMMs or attention, without the transposed-V self-attention, with sharded tokens or CFG parallelism a
+    NotImplementedError (the engine's `sparse_check`, and the region's own refusal)."""
+
+    def __init__(self, transformer, config: SparseRegionConfig, n_steps: int):
+        self.transformer, self.config, self.n_steps = transformer, config, int(n_steps)
+        self.plan = self.ids = self.tokens = self.full = None
+        self.forced = set()
+
+    @classmethod
+    def begin(cls, transformer, config: Optional[SparseRegionConfig], n_steps: int) -> Optional["SparseRegionState"]:
+        """Resets the report; None without a config (the caller passes none for an edit without a region)."""
+        if hasattr(transformer, "sparse_report"):
+            transformer.sparse_report = None
+        if config is None:
+            return None
+        transformer.engine().sparse_check()
+        return cls(transformer, config, n_steps)
+
+    def setup(self, w: torch.Tensor, forced: Iterable[int], n_samples: int, T: int, h: int, wl: int):
+        """The plan, the active ids and the engine's cache (reserved here: outside any capture) for the weights w, for forwards of n_samples
+        samples at T latent frames of h x wl cells."""
+        self.forced = set(forced)
+        self.ids, _ = active_tokens(w, T, self.config.margin)  # (the one device-to-host read: the latent weights)
+        self.tokens = T * (h // 2) * (wl // 2)
+        self.full = self.ids.numel() >= self.tokens or self.ids.numel() % PAD != 0  # the whole grid: nothing to leave out
+        self.plan = plan(self.n_steps, self.config, self.forced, full=self.full)
+        self.transformer.sparse_report = report(self.plan, self.ids.numel(), self.tokens)
+        if "sparse" in self.plan:
+            self.transformer.engine().sparse_begin(self.ids, n_samples, T, h, wl)
+
+    def replaced(self, i: int) -> bool:
+        """A callback replaced the latents or an embedding behind step i: the cached K / V^T of the inactive tokens belong to the old ones, so
+        the next step is dense and the count restarts behind it.  True when the plan changed."""
+        if self.plan is None or i + 1 >= len(self.plan):
+            return False
+        self.forced = self.forced | {i + 1}
+        self.plan = self.plan[: i + 1] + plan(len(self.plan), self.config, self.forced, full=self.full)[i + 1:]
+        self.transformer.sparse_report = report(self.plan, self.ids.numel(), self.tokens)
+        return True

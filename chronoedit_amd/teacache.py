@@ -6,16 +6,19 @@ last computed step (tokens behind the stack minus tokens in front of it) is adde
 The quantity the rule watches is the time-projection output of the step - a function of the timestep and the weights alone, not of
 the latents, the prompt or the guidance branch.  So the whole compute / skip plan of an edit is a function of the schedule: it is
 computed here BEFORE the loop (one device-to-host read per edit, none per step), the conditional and unconditional passes share it,
-and a hipGraph-replayed loop needs just a second captured graph for the skipped steps (pipeline.GraphedDenoiser).
+and a hipGraph-replayed loop needs just a second captured graph for the skipped steps (loop.GraphedDenoiser).  `TeaCacheState` is
+what one edit keeps.
 
 Host side only: `plan_from_ratios`, the bf16 arithmetic of the ratios and the fit of the rescaling polynomial (`fit_calibration`, from the
 points a measured edit yields) need no device; the device passes are csrc/ce_tea.hip."""
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Iterable, List, Sequence, Tuple
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
+
+SHARDED = "TeaCache with {} is not implemented (the cached residual is row-local; nothing sharded has been tested with it)"
 
 
 @dataclass(frozen=True)
@@ -84,7 +87,7 @@ def report(plan: Sequence[bool], ratios: Sequence[float]) -> dict:
 # ---- calibration: the rescaling polynomial fitted on the loaded checkpoint ---------------------------------------------------------
 # The polynomial maps what the rule watches (ratios: the relative L1 change of the time projection, a function of the schedule) to what
 # a skipped step gets wrong (distances: the relative L1 change of the block stack's residual, which a skipped step reuses unchanged).
-# A measured edit (pipeline.denoise(teacache_measure=True)) yields one (ratio, distance) point per step; the fit is least squares.
+# A measured edit (loop.denoise(teacache_measure=True)) yields one (ratio, distance) point per step; the fit is least squares.
 @dataclass(frozen=True)
 class TeaCacheCalibration:
     """coefficients: highest power first, what `enable_teacache(thresh, coefficients)` and TeaCacheConfig take.  degree: the degree
@@ -143,3 +146,42 @@ def distances_from_sums(sums) -> List[float]:
     with np.errstate(divide="ignore", invalid="ignore"):
         d = sums[:, 0] / sums[:, 1]
     return [float(v) if np.isfinite(v) else float("nan") for v in d]
+
+
+class TeaCacheState:
+    """TeaCache in one running edit (`loop.denoise(teacache=, teacache_measure=)`).
+    config: a TeaCacheConfig for this call; None = whatever `transformer.enable_teacache()` set (nothing: no step is skipped).  The compute /
+    skip plan of the whole edit is made in `begin`, before the first step (`forced`, the truncation step, always computes: the 8-frame
+    residual does not fit 2-frame tokens); `transformer.teacache_report` then holds {"plan", "computed", "skipped", "ratios"}, and the
+    engine has dropped the previous edit's residual.
+    measure (`teacache_measure`, or `transformer.calibrate_teacache` around the call): calibration instead of skipping - `plan` is None.
+    Every step computes - the latents are the plain loop's - and the pass that stores the block stack's residual also measures its relative
+    L1 distance to the previous step's residual, on the device, into a table read back once after the last step (`finish`): afterwards
+    `transformer.teacache_measurement` holds {"ratios": teacache_ratios(timesteps), "distances": per step, NaN for step 0 and for the first
+    step after the truncation} - the points fit_calibration fits.  A measured edit always runs eagerly (the table row changes per step,
+    and calibration is offline).  Together with a skip plan it is a ValueError (raised by the loop, in front of every feature's setup)."""
+
+    def __init__(self, transformer, plan: Optional[List[bool]], ratios: Sequence[float]):
+        self.transformer, self.plan, self.ratios = transformer, plan, ratios
+
+    @classmethod
+    def begin(cls, transformer, timesteps, config: Optional[TeaCacheConfig], measure: bool, forced: Iterable[int] = ()) -> Optional["TeaCacheState"]:
+        """None when the edit neither skips nor measures.  With sharded tokens or CFG parallelism a NotImplementedError."""
+        if config is None and not measure:
+            return None
+        from .loop import refuse_sharded
+        refuse_sharded(transformer, SHARDED)
+        ratios = transformer.teacache_ratios(timesteps)  # the one device-to-host read of the edit
+        if config is None:
+            transformer.engine().tea_measure_begin(len(timesteps))
+            return cls(transformer, None, ratios)
+        plan = plan_from_ratios(ratios, len(timesteps), config.rel_l1_thresh, config.coefficients, forced)
+        transformer.teacache_report = report(plan, ratios)
+        transformer.engine().tea_drop()  # nothing of the previous edit's residual may be reused
+        return cls(transformer, plan, ratios)
+
+    def finish(self):
+        """Measuring: the one read of the table, after the last step."""
+        if self.plan is None:
+            sums = self.transformer.engine().tea_measure_end()
+            self.transformer.teacache_measurement = {"ratios": [float(r) for r in self.ratios], "distances": distances_from_sums(sums.numpy())}
