@@ -991,6 +991,76 @@ def autofocus_restart(x0: torch.Tensor, eps: torch.Tensor, tables, s: float, bf1
     return out
 
 
+# ---- sketch edits (csrc/ce_sketch.hip) -----------------------------------------------------------------------------------
+def _plane(t: torch.Tensor, name: str):
+    _dev(t, torch.uint8, name)
+    if t.dim() != 2 or not t.is_contiguous() or t.numel() == 0:
+        raise ValueError(f"{name}: need a non-empty contiguous [H, W] tensor, got shape {tuple(t.shape)} stride {t.stride()}")
+
+
+def sketch_changed_u8(background: torch.Tensor, composite: torch.Tensor, threshold: int = 0, out: Optional[torch.Tensor] = None):
+    """background, composite uint8 [SH, SW, 3] -> a new uint8 [SH, SW]: 255 where max over the channels of |composite - background| >
+    threshold (0..254), else 0."""
+    _dev(background, torch.uint8, "background"), _dev(composite, torch.uint8, "composite")
+    for name, t in (("background", background), ("composite", composite)):
+        if t.dim() != 3 or t.shape[2] != 3 or not t.is_contiguous() or t.numel() == 0:
+            raise ValueError(f"{name}: need a non-empty contiguous [SH, SW, 3] tensor, got shape {tuple(t.shape)} stride {t.stride()}")
+    if background.shape != composite.shape:
+        raise ValueError(f"background {tuple(background.shape)} and composite {tuple(composite.shape)} differ in shape")
+    if isinstance(threshold, bool) or not 0 <= int(threshold) <= 254:
+        raise ValueError(f"threshold: an int in 0..254, got {threshold!r}")
+    SH, SW, _ = background.shape
+    if out is None:
+        out = torch.empty((SH, SW), dtype=torch.uint8, device=background.device)
+    _plane(out, "out")
+    assert tuple(out.shape) == (SH, SW) and out.data_ptr() not in (background.data_ptr(), composite.data_ptr())
+    st = _prof_begin()
+    _check(lib().ce_sketch_changed_u8(_ptr(background), _ptr(composite), _ptr(out), SH * SW, int(threshold), _stream()), "ce_sketch_changed_u8")
+    _prof_end(st, f"sketch_changed_{SH}x{SW}", 7.0 * SH * SW)
+    return out
+
+
+def sketch_scratch_bytes(H: int, W: int, axis: int, radius: int) -> int:
+    """The scratch a `sketch_dilate_u8` / `sketch_box_u8` call needs: the per-segment sums uint16 [ceil(H / 32), W] of a vertical pass whose
+    window holds more than 128 rows; 0 otherwise."""
+    return (H + 31) // 32 * W * 2 if axis == 1 and int(radius) >= 64 else 0
+
+
+def _sketch_filter(fn_name: str, src: torch.Tensor, axis: int, radius: int, out: Optional[torch.Tensor], scratch: Optional[torch.Tensor]):
+    _plane(src, "src")
+    if axis not in (0, 1):
+        raise ValueError(f"axis: 0 (horizontal) or 1 (vertical), got {axis}")
+    if out is None:
+        out = torch.empty_like(src)
+    _plane(out, "out")
+    assert out.shape == src.shape and out.data_ptr() != src.data_ptr()
+    H, W = src.shape
+    need = sketch_scratch_bytes(H, W, axis, radius)
+    if scratch is None and need:
+        scratch = torch.empty(need, dtype=torch.uint8, device=src.device)
+    if scratch is not None:
+        _dev(scratch, torch.uint8, "scratch")
+        assert scratch.is_contiguous()
+    st = _prof_begin()
+    _check(getattr(lib(), fn_name)(_ptr(src), _ptr(out), H, W, int(axis), int(radius), _ptr(scratch), 0 if scratch is None else scratch.numel(),
+                                   _stream()), fn_name)
+    _prof_end(st, f"{fn_name[3:-3]}_{'hv'[axis]}_{H}x{W}_r{int(radius)}", 2.0 * src.numel())
+    return out
+
+
+def sketch_dilate_u8(src: torch.Tensor, axis: int, radius: int, out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
+    """One axis (0: horizontal, 1: vertical) of the maximum filter of a 0 / 255 plane uint8 [H, W], window [i - radius, i + radius] clipped to
+    the image, radius 0..4096 -> a new plane: 255 where the window holds a non-zero byte, else 0.  scratch: uint8, at least
+    `sketch_scratch_bytes` (made here when not given)."""
+    return _sketch_filter("ce_sketch_dilate_u8", src, axis, radius, out, scratch)
+
+
+def sketch_box_u8(src: torch.Tensor, axis: int, radius: int, out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
+    """One axis of PIL's BoxBlur(radius) for an integer radius 0..1024 over uint8 [H, W], edges replicated -> a new plane:
+    (window sum * (2^24 // (2 radius + 1)) + 2^23) >> 24."""
+    return _sketch_filter("ce_sketch_box_u8", src, axis, radius, out, scratch)
+
+
 # ---- automatic edit regions (csrc/ce_region_auto.hip) ------------------------------------------------------------------
 def _f32c(t: torch.Tensor, name: str):
     _dev(t, torch.float32, name)

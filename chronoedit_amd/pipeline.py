@@ -162,6 +162,8 @@ class ChronoEditPipeline:
         self.preview_fit_gram = None  # float64 [20, 20] on the CPU: the Gram matrix the last fit solved
         self._detail_lift = None  # the lift.LiftConfig while enable_detail_lift is in force
         self.lift_report = None  # the last call's detail-lift report, one dict per sample; None when the switch is off (or "latent" was asked for)
+        self._sketch_region = None  # the sketch.SketchConfig while enable_sketch_region is in force
+        self.sketch_report = None  # the last call's sketch plans, one dict per editor value; None when the call got no editor value
 
     # -- properties of the reference pipeline (:458-478) ---------------------------------------------------------------
     @property
@@ -648,6 +650,133 @@ class ChronoEditPipeline:
         self._auto_focus = None
         return self
 
+    # Sketch edits (chronoedit_amd/sketch.py): the region is where the editor's composite differs from its background.  Off by default
+    def enable_sketch_region(self, grow=0.02, feather=0.01, threshold: int = 0, context: float = 0.25, composite: bool = True):
+        """While on and no `set_edit_region` mask is set, `__call__(image=...)` also takes an image editor's value: a dict with PIL images
+        under "background" (the photo) and "composite" (the photo with the strokes on it) - other keys, such as "layers", are ignored -, or
+        a list of such dicts, one per prompt.  Per value the mask is built at the PHOTO's size before the first step (sketch.reference:
+        changed by more than `threshold` in a channel -> grown by grow + feather -> box mean of radius feather; on the device with
+        `device_image_io`, csrc/ce_sketch.hip, the same bytes; one read of ten integers per image before the edit - the report's copy of
+        the mask is made behind it), and the call goes on as the focused
+        region edit (`enable_region_focus(context)`, `set_edit_region(mask, composite)`: what that call composes with or refuses, this one
+        does) with ONE difference: the crop that the VAE, CLIP and the kept latents see is the COMPOSITE's, the frames are pasted into the
+        BACKGROUND - the photo untouched wherever the mask is 0, the model's pixels where the user drew.  grow, feather: an int is pixels
+        of the photo, a float in [0, 1) that fraction of its longer side, rounded up (grow + feather <= 4096, feather <= 1024 pixels, a
+        ValueError otherwise - for fractions, at the call).  The defaults are choices, not measurements.
+        No strokes in any value: the plain call on the composite(s), bit for bit, `sketch_report[i]["reason"]` = "empty".  A plain PIL
+        image, array or tensor is the call it is without the switch (`sketch_report` None).  With a `set_edit_region` mask the explicit mask
+        wins: an editor value then stands for its composite.  A value whose two images differ in size, or that lacks one, is a ValueError.
+        `sketch_report` holds per value the focus plan's entries (`focus_report`'s) plus "mask" (PIL "L", the photo's size), "grow_px",
+        "feather_px", "threshold" and "changed_pixels"."""
+        from . import sketch as _sk
+        self._sketch_region = _sk.SketchConfig(grow, feather, threshold, context, composite)
+        return self
+
+    def disable_sketch_region(self):
+        self._sketch_region = None
+        return self
+
+    def sketch_mask(self, background, composite):
+        """The mask a sketch call would build for this pair of PIL images with the enabled parameters, as a PIL "L" image of their size - for
+        a front end to show before an edit is spent."""
+        from PIL import Image
+        from . import sketch as _sk
+        if self._sketch_region is None:
+            raise ValueError("sketch_mask needs the parameters of enable_sketch_region(): the switch is off")
+        bgs, cps = _sk.editor_images({"background": background, "composite": composite})
+        e = self._sketch_masks(bgs, cps, self._execution_device)[0]
+        return Image.fromarray(self._sketch_host_mask(e).numpy(), mode="L")  # (no edit follows: the copy of the mask may be made here)
+
+    def _sketch_masks(self, bgs, cps, device):
+        """Per editor value {"background", "composite", "mask_u8" (host; None on the device path: `_sketch_host_mask` copies it when the edit
+        is done), "grow_px", "feather_px", "bbox" (None: no strokes), "mask_pixels", "changed_pixels"} and, on the device path, "bg_u8",
+        "cp_u8", "mask_dev": each image uploaded once, two reductions and ONE read of their ten integers per value - nothing else comes back."""
+        from . import autofocus as _af
+        from . import sketch as _sk
+        cfg = self._sketch_region
+        on_device = self.device_image_io and torch.device(device).type == "cuda"
+        out = []
+        for bg, cp in zip(bgs, cps):
+            g, f = cfg.pixels(bg.size)
+            e = {"background": bg, "composite": cp, "grow_px": g, "feather_px": f}
+            if on_device:
+                e["bg_u8"], e["cp_u8"] = image_io.upload_rgb(bg, device), image_io.upload_rgb(cp, device)
+                ch, _, m = _sk.stages(e["bg_u8"], e["cp_u8"], g, f, cfg.threshold)
+                counts = torch.cat([_af.bbox_counts(m), _af.bbox_counts(ch)]).tolist()
+                e["mask_dev"], e["mask_u8"] = m, None
+            else:
+                ch, _, m = _sk.stages(bg, cp, g, f, cfg.threshold)
+                counts = _af.bbox_counts(m).tolist() + _af.bbox_counts(ch).tolist()
+                e["mask_u8"] = m
+            e["bbox"] = tuple(int(v) for v in counts[:4]) if counts[4] else None
+            e["mask_pixels"], e["changed_pixels"] = int(counts[4]), int(counts[9])
+            out.append(e)
+        return out
+
+    @staticmethod
+    def _sketch_host_mask(e) -> torch.Tensor:
+        """The mask of one `_sketch_masks` entry on the host: the device path's 12 MB copy, made once and behind the edit (an empty mask needs
+        no copy)."""
+        if e["mask_u8"] is None:
+            e["mask_u8"] = e["mask_dev"].cpu() if e["bbox"] is not None else torch.zeros(tuple(e["mask_dev"].shape), dtype=torch.uint8)
+        return e["mask_u8"]
+
+    def _sketch_call(self, value, call: dict):
+        """`__call__` with an editor's value (or a list of them) as `image`: see `enable_sketch_region`."""
+        from PIL import Image
+        from . import focus as _fc
+        from . import sketch as _sk
+        if self._sketch_region is None:
+            raise ValueError("`image` is an image editor's value (a dict with \"background\" and \"composite\"): switch sketch edits on with "
+                             "enable_sketch_region() first, or pass the composite itself")
+        cfg = self._sketch_region
+        bgs, cps = _sk.editor_images(value)
+        image = cps if isinstance(value, (list, tuple)) else cps[0]
+        if self._edit_region is not None:  # an explicit mask wins: the editor value stands for its composite
+            return self(image=image, **call)
+        height, width = call["height"], call["width"]
+        if call["output_type"] in ("np", "pt") and len({im.size for im in bgs}) > 1:
+            raise ValueError(f"a sketch edit returns frames of the photos' sizes {[im.size for im in bgs]}: output_type={call['output_type']!r} "
+                             'needs photos of one size, use "pil"')
+        device = self._execution_device
+        entries = self._sketch_masks(bgs, cps, device)
+        plans, plan_reports = [], []
+        for e in entries:
+            SW, SH = e["background"].size
+            box, reason = _fc.focus_box(e["bbox"], (SW, SH), (width, height), cfg.context)
+            l, t, r, b = box
+            # (the box holds the mask's bounding box, so the mask's share of the box is its count over the box's area)
+            plan = {"box": box, "reason": reason, "source_size": (SW, SH), "edit_size": (int(width), int(height)), "scale": (r - l) / int(width),
+                    "mask_fraction_of_box": float(e["mask_pixels"]) / ((r - l) * (b - t))}
+            p = {"image": e["composite"], "paste_image": e["background"], "box": box, "mask_u8": e["mask_u8"], "report": plan}
+            if "mask_dev" in e:
+                p["src_u8"], p["paste_u8"], p["mask_dev"] = e["cp_u8"], e["bg_u8"], e["mask_dev"]
+            plans.append(p)
+            plan_reports.append(plan)
+
+        def report():  # behind the edit: the device path copies its masks to the host here, not in front of the first step
+            return [dict(plan, mask=Image.fromarray(self._sketch_host_mask(e).numpy(), mode="L"), grow_px=e["grow_px"], feather_px=e["feather_px"],
+                         threshold=cfg.threshold, changed_pixels=e["changed_pixels"]) for plan, e in zip(plan_reports, entries)]
+
+        if all(e["bbox"] is None for e in entries):  # no strokes anywhere: the plain call on the composite(s)
+            out = self(image=image, **call)
+            self.sketch_report = report()
+            return out
+        saved = (self._edit_region, self._region_focus)
+        # (with the plans handed over, `__call__` reads the composite flag only; the masks named here are the plans' own, where they lie)
+        self._edit_region, self._region_focus = ([p.get("mask_dev", p["mask_u8"]) for p in plans], cfg.composite), cfg.context
+        self._focus_pass = {"plans": plans, "start": None, "explicit": True}
+        try:
+            out = self(image=image, **call)
+        finally:
+            self._focus_pass = None
+            self._edit_region, self._region_focus = saved
+        for p, e in zip(plans, entries):  # (a host paste-back has copied the mask already: keep that copy)
+            if e["mask_u8"] is None and p["mask_u8"] is not None:
+                e["mask_u8"] = p["mask_u8"]
+        self.sketch_report = report()
+        return out
+
     # Guided detail lift (chronoedit_amd/lift.py): whole-image edits returned at the photo's size.  Off by default
     def enable_detail_lift(self, radius: int = 4, eps: float = 26.0, gate=(4.0, 12.0), max_gain: float = 8.0):
         """While on, a call with PIL input (one image, or a list with one per prompt) and output_type "pil" / "np" / "pt" returns every frame
@@ -774,7 +903,8 @@ class ChronoEditPipeline:
         return img, [m.to(device) for _, m in host]
 
     def _focus_output(self, video: torch.Tensor, plans, image_of, output_type: str):
-        """The source-size paste-back of every sample's frames (reasoning frames included), in postprocess_video's layouts."""
+        """The source-size paste-back of every sample's frames (reasoning frames included), in postprocess_video's layouts.  A plan with a
+        second source ("paste_image" / "paste_u8": a sketch edit's background) is pasted into that one."""
         import numpy as np
         from . import focus as _fc
         from . import ops
@@ -787,12 +917,12 @@ class ChronoEditPipeline:
         for b in range(video.shape[0]):
             p = plans[image_of(b)]
             if on_device:
-                out.append(_fc.device_paste(u8[b], p["src_u8"], p["mask_dev"] if composite else None, p["box"]).cpu().numpy())
+                out.append(_fc.device_paste(u8[b], p.get("paste_u8", p["src_u8"]), p["mask_dev"] if composite else None, p["box"]).cpu().numpy())
             else:
                 frames = self.postprocess_video(video[b:b + 1], "pil")[0]
                 if composite and p["mask_u8"] is None:  # (an auto-focused call keeps its lifted mask on the device)
                     p["mask_u8"] = p["mask_dev"].cpu()
-                pasted = _fc.host_paste(p["image"], frames, p["mask_u8"] if composite else None, p["box"])
+                pasted = _fc.host_paste(p.get("paste_image", p["image"]), frames, p["mask_u8"] if composite else None, p["box"])
                 out.append(np.stack([np.asarray(f, dtype=np.uint8) for f in pasted]))
         if output_type == "pil":
             from PIL import Image
@@ -904,7 +1034,20 @@ class ChronoEditPipeline:
         """Same arguments, defaults, checks and return value as the reference's `__call__`.  What differs is underneath: the two
         guidance passes run as ONE batched forward, CFG + flow-UniPC are one fused launch, the latents stay fp32 on the device
         (`scheduler.trajectory_dtype = torch.bfloat16` restores the reference's bf16 rounding of latents and history)."""
-        fpass, self._focus_pass = self._focus_pass, None  # set: this is the focused pass of an auto-focused call (`_auto_focus_pass`)
+        fpass, self._focus_pass = self._focus_pass, None  # set: this is the focused pass of an auto-focused call (`_auto_focus_pass`) or of a sketch edit
+        if fpass is None:
+            from . import sketch as _sk
+            self.sketch_report = None
+            if _sk.is_editor_value(image):  # an image editor's value: the sketch edit (chronoedit_amd/sketch.py) - or its refusal
+                return self._sketch_call(image, dict(
+                    prompt=prompt, negative_prompt=negative_prompt, height=height, width=width, num_frames=num_frames,
+                    num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, num_videos_per_prompt=num_videos_per_prompt,
+                    generator=generator, latents=latents, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
+                    image_embeds=image_embeds, output_type=output_type, return_dict=return_dict, attention_kwargs=attention_kwargs,
+                    callback_on_step_end=callback_on_step_end, callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs,
+                    max_sequence_length=max_sequence_length, enable_temporal_reasoning=enable_temporal_reasoning,
+                    num_temporal_reasoning_steps=num_temporal_reasoning_steps, offload_model=offload_model))
+        scouted = fpass is not None and not fpass.get("explicit")  # the pass an auto-focus scout started: its guardrail ran, its previews are tagged
         if hasattr(callback_on_step_end, "tensor_inputs"):
             callback_on_step_end_tensor_inputs = callback_on_step_end.tensor_inputs
         self.check_inputs(prompt, negative_prompt, image, height, width, prompt_embeds, negative_prompt_embeds, image_embeds,
@@ -914,7 +1057,7 @@ class ChronoEditPipeline:
         num_frames = max(num_frames, 1)
         self._guidance_scale, self._attention_kwargs, self._current_timestep, self._interrupt = guidance_scale, attention_kwargs, None, False
         device = self._execution_device
-        if fpass is None and self.text_guardrail_runner is not None and not self.text_guardrail_runner(prompt):  # :621-629
+        if not scouted and self.text_guardrail_runner is not None and not self.text_guardrail_runner(prompt):  # :621-629
             raise Exception(f"Guardrail blocked text2world generation. Prompt: {prompt}")
 
         if prompt is not None and isinstance(prompt, str):
@@ -1065,7 +1208,7 @@ class ChronoEditPipeline:
                                     graph_warm=self._graph_warm, region=None if regions is None else regions[image_of(b)][1],
                                     auto_region=None if autos is None else autos[b], start_step=start_step,
                                     start_eps=None if start_eps is None else start_eps[b:b + 1],
-                                    preview=self._preview_config(b, "focus" if fpass is not None else "scout" if a_focus is not None else None),
+                                    preview=self._preview_config(b, "focus" if scouted else "scout" if a_focus is not None else None),
                                     **self._measure_kwargs()))
         if autos is not None and not autos[0].measure:
             self.auto_region_report = autos[0].report if B == 1 else [a.report for a in autos]

@@ -1,0 +1,206 @@
+"""Sketch edits: the user draws on the photo, the region of the edit is where the drawing is.
+
+An image editor (gradio's `ImageEditor`, the reference's scripts/gradio_paintbrush.py) hands over {"background", "layers", "composite"}:
+the photo, and the photo with the strokes on it.  With `ChronoEditPipeline.enable_sketch_region` one call is
+
+    mask      at the PHOTO's size, before the first step: changed -> grown -> feathered (`reference` below is the definition)
+                changed  255 where max over the channels of |composite - background| > threshold, else 0
+                grown    the square maximum filter of radius R = grow + feather, the window clipped to the image
+                mask     the box mean of radius feather, horizontal then vertical over the rounded bytes, edges replicated; per axis, with
+                         n = 2 feather + 1 and ww = 2^24 // n:  out = (window sum * ww + 2^23) >> 24
+              which is ImageChops.difference -> the bands' maximum -> point(v > threshold) -> MaxFilter(2 R + 1) -> BoxBlur(feather) of PIL,
+              byte for byte (tests/test_sketch_cpu.py) - without MaxFilter's cost, which is quadratic in the window
+    focused   the explicit-mask focused region edit (chronoedit_amd/focus.py) with that mask: the crop the model sees is the COMPOSITE's (it
+              must see the sketch), the frames are pasted into the BACKGROUND (the strokes do not come back where the mask keeps the photo)
+
+What follows from the arithmetic: every pixel within `grow` (Chebyshev distance) of a changed pixel is 255 exactly, every pixel farther
+than grow + 2 feather from all of them is 0, and with threshold = 0 composite and background carry the same bytes wherever the mask is below
+255.  All integers: the device passes (csrc/ce_sketch.hip) give `reference`'s bits.  What the paint-brush LoRA makes of a sketch inside a
+crop is the checkpoint's business."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from fractions import Fraction
+from typing import Tuple, Union
+
+import numpy as np
+import torch
+
+from .focus import _ceil, focus_box
+
+ENTRY_POINTS = ("ce_sketch_changed_u8", "ce_sketch_dilate_u8", "ce_sketch_box_u8")
+MAX_GROWN, MAX_FEATHER = 4096, 1024  # the largest grow + feather and feather, in pixels (the passes' LDS and their 32-bit sums are sized for them)
+
+
+def _length(v, name: str):
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise ValueError(f"sketch region: {name} must be an int (pixels) or a float in [0, 1) (a fraction of the photo's longer side), got {v!r}")
+    if isinstance(v, int):
+        if v < 0:
+            raise ValueError(f"sketch region: {name} must be >= 0, got {v}")
+        return v
+    if not (0.0 <= v < 1.0):  # (a NaN fails the comparison)
+        raise ValueError(f"sketch region: {name} as a float must lie in [0, 1), got {v!r}")
+    return float(v)
+
+
+@dataclass(frozen=True)
+class SketchConfig:
+    """grow, feather: an int is pixels of the photo, a float in [0, 1) that fraction of the photo's longer side (`pixels`).  threshold: a
+    pixel counts as drawn on when a channel differs by MORE than this (0..254).  context, composite: `enable_region_focus`'s and
+    `set_edit_region`'s.  The defaults are choices, not measurements: a margin of 2 % of the photo around the strokes belongs to the
+    model, a further 1 % (twice: the box mean spreads over 2 feather) fades into the photo, and a lossless editor changes no byte it was
+    not asked to (a front end that re-encodes its composite needs a threshold above its codec's error)."""
+    grow: Union[int, float] = 0.02
+    feather: Union[int, float] = 0.01
+    threshold: int = 0
+    context: float = 0.25
+    composite: bool = True
+
+    def __post_init__(self):
+        object.__setattr__(self, "grow", _length(self.grow, "grow"))
+        object.__setattr__(self, "feather", _length(self.feather, "feather"))
+        if isinstance(self.threshold, bool) or not isinstance(self.threshold, int) or not 0 <= self.threshold <= 254:
+            raise ValueError(f"sketch region: threshold must be an int in 0..254, got {self.threshold!r}")
+        focus_box(None, (1, 1), (1, 1), self.context)  # (validates the context)
+        if not isinstance(self.composite, bool):
+            raise ValueError(f"sketch region: composite must be a bool, got {self.composite!r}")
+        _check_pixels(self.grow if isinstance(self.grow, int) else 0, self.feather if isinstance(self.feather, int) else 0)  # (fractions: at the call)
+
+    def pixels(self, src_size: Tuple[int, int]) -> Tuple[int, int]:
+        """(grow, feather) in pixels for a photo of src_size = (SW, SH)."""
+        g, f = pixels(self.grow, src_size), pixels(self.feather, src_size)
+        _check_pixels(g, f)
+        return g, f
+
+
+def _check_pixels(grow: int, feather: int):
+    if grow < 0 or feather < 0 or grow + feather > MAX_GROWN or feather > MAX_FEATHER:
+        raise ValueError(f"sketch region: need 0 <= grow, 0 <= feather <= {MAX_FEATHER} and grow + feather <= {MAX_GROWN} pixels, got grow "
+                         f"{grow} and feather {feather}")
+
+
+def pixels(v, src_size: Tuple[int, int]) -> int:
+    """An int is pixels; a float in [0, 1) is ceil(that fraction * the photo's longer side), the fraction read as the nearest one with a
+    denominator <= 65536 (0.02 is 1 / 50: 0.02 of 4032 is 81), the idiom of `focus.focus_box`."""
+    v = _length(v, "a length")
+    if isinstance(v, int):
+        return v
+    return _ceil(Fraction(v).limit_denominator(1 << 16) * max(int(src_size[0]), int(src_size[1])))
+
+
+# ---- the editor's value -------------------------------------------------------------------------------------------------------------
+def is_editor_value(image) -> bool:
+    """A dict, or a non-empty list / tuple of dicts: what `__call__(image=...)` takes as an image editor's value(s)."""
+    if isinstance(image, dict):
+        return True
+    return isinstance(image, (list, tuple)) and len(image) > 0 and all(isinstance(v, dict) for v in image)
+
+
+def editor_images(value) -> Tuple[list, list]:
+    """One editor value or a list of them -> (backgrounds, composites), PIL images; keys other than "background" and "composite" (such as
+    "layers") are ignored.  A missing or None entry, an entry that is no PIL image, or two sizes in one value are a ValueError."""
+    from .image_io import _is_pil
+    values = [value] if isinstance(value, dict) else list(value)
+    bgs, cps = [], []
+    for i, v in enumerate(values):
+        for key in ("background", "composite"):
+            if v.get(key) is None:
+                raise ValueError(f'sketch region: the editor value {i} has no "{key}" (got the keys {sorted(map(str, v))}): it needs PIL images '
+                                 'under "background" and "composite"')
+            if not _is_pil(v[key]):
+                raise ValueError(f'sketch region: "{key}" of the editor value {i} must be a PIL image, got {type(v[key])}')
+        if v["background"].size != v["composite"].size:
+            raise ValueError(f'sketch region: "background" {v["background"].size} and "composite" {v["composite"].size} of the editor value {i} '
+                             "differ in size")
+        bgs.append(v["background"]), cps.append(v["composite"])
+    return bgs, cps
+
+
+def rgb_bytes(image) -> torch.Tensor:
+    """A PIL image (`convert("RGB")`), or a uint8 [SH, SW, 3] array / tensor -> a uint8 [SH, SW, 3] tensor where it lies."""
+    if isinstance(image, torch.Tensor):
+        t = image
+    elif isinstance(image, np.ndarray):
+        t = torch.from_numpy(image)
+    else:
+        t = torch.from_numpy(np.array(image.convert("RGB"), dtype=np.uint8))
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.numel() == 0:
+        raise ValueError(f"sketch: need RGB bytes uint8 [SH, SW, 3], got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+# ---- the stages: the device pass for a tensor on the GPU, the torch expression for one on the CPU - the same bits ---------------------
+def changed(background: torch.Tensor, composite: torch.Tensor, threshold: int = 0) -> torch.Tensor:
+    """Two uint8 [SH, SW, 3] -> uint8 [SH, SW]: 255 where max over the channels of |composite - background| > threshold, else 0."""
+    if background.shape != composite.shape:
+        raise ValueError(f"sketch: background {tuple(background.shape[:2])} and composite {tuple(composite.shape[:2])} differ in size")
+    if background.is_cuda:
+        from . import ops
+        return ops.sketch_changed_u8(background, composite, threshold)
+    d = (composite.to(torch.int16) - background.to(torch.int16)).abs().amax(dim=2)
+    return (d > int(threshold)).to(torch.uint8) * 255
+
+
+def _window_sums(x: torch.Tensor, r: int, axis: int, replicate: bool) -> torch.Tensor:
+    """int32 [H, W] -> the sums over [i - r, i + r] along `axis` (0: horizontal), the line continued by its edge values (replicate) or by
+    zeros: one running sum, whatever the radius."""
+    x = x if axis == 0 else x.t().contiguous()
+    n = x.shape[1]
+    if replicate:
+        idx = torch.arange(-r, n + r).clamp_(0, n - 1)
+        line = x.index_select(1, idx)
+    else:
+        line = torch.nn.functional.pad(x, (r, r))
+    c = torch.nn.functional.pad(line.cumsum(1, dtype=torch.int64), (1, 0))
+    s = c[:, 2 * r + 1:] - c[:, :n]
+    return s if axis == 0 else s.t().contiguous()
+
+
+def dilate(plane: torch.Tensor, radius: int, axis: int) -> torch.Tensor:
+    """One axis (0: horizontal, 1: vertical) of the maximum filter of a 0 / 255 plane uint8 [SH, SW], window [i - radius, i + radius]
+    clipped to the image: 255 where the window holds a non-zero byte, else 0 - a new tensor."""
+    _check_pixels(int(radius), 0)
+    if plane.is_cuda:
+        from . import ops
+        return ops.sketch_dilate_u8(plane, axis, int(radius))
+    return (_window_sums((plane != 0).to(torch.int32), int(radius), axis, False) > 0).to(torch.uint8) * 255
+
+
+def box(plane: torch.Tensor, radius: int, axis: int) -> torch.Tensor:
+    """One axis of the box mean of uint8 [SH, SW], window [i - radius, i + radius] over the edge-replicated line:
+    out = (sum * (2^24 // (2 radius + 1)) + 2^23) >> 24 - a new tensor."""
+    _check_pixels(0, int(radius))
+    if plane.is_cuda:
+        from . import ops
+        return ops.sketch_box_u8(plane, axis, int(radius))
+    ww = (1 << 24) // (2 * int(radius) + 1)
+    return ((_window_sums(plane.to(torch.int32), int(radius), axis, True) * ww + (1 << 23)) >> 24).to(torch.uint8)
+
+
+def stages(background, composite, grow: int, feather: int, threshold: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(changed, grown, mask), uint8 [SH, SW] each, where the images lie (two PIL images: on the host).  grow, feather in pixels.  A radius
+    of 0 runs no pass: with grow = feather = 0 the three are one tensor."""
+    grow, feather = int(grow), int(feather)
+    _check_pixels(grow, feather)
+    if isinstance(threshold, bool) or not 0 <= int(threshold) <= 254:
+        raise ValueError(f"sketch: threshold must be an int in 0..254, got {threshold!r}")
+    ch = changed(rgb_bytes(background), rgb_bytes(composite), int(threshold))
+    grown = ch
+    if grow + feather:
+        grown = dilate(dilate(ch, grow + feather, 0), grow + feather, 1)
+    mask = grown
+    if feather:
+        mask = box(box(grown, feather, 0), feather, 1)
+    return ch, grown, mask
+
+
+def reference(background, composite, grow: int, feather: int, threshold: int = 0) -> torch.Tensor:
+    """THE definition, and the host path: two images (PIL, or uint8 [SH, SW, 3]) -> the mask uint8 [SH, SW] on the host.  grow, feather in
+    pixels of the photo."""
+    return stages(rgb_bytes(background).cpu(), rgb_bytes(composite).cpu(), grow, feather, threshold)[2]
+
+
+def mask(background: torch.Tensor, composite: torch.Tensor, grow: int, feather: int, threshold: int = 0) -> torch.Tensor:
+    """`reference` where the bytes lie: uint8 [SH, SW, 3] twice, on the GPU (five launches at most, no host read) or on the host."""
+    return stages(background, composite, grow, feather, threshold)[2]

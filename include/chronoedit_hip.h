@@ -662,6 +662,36 @@ int ce_lift_gate_f32(const int* R, float* coef, int F, int H, int W, int radius,
 int ce_lift_apply_u8(const void* P, const void* U, const float* coef, const int* ix0, const int* ix1, const float* tx, const int* iy0,
                      const int* iy1, const float* ty, void* out, int F, int SH, int SW, int H, int W, hipStream_t stream);
 
+/* ---- sketch edits (csrc/ce_sketch.hip; chronoedit_amd/sketch.py): the region of an edit drawn on the photo is where the editor's composite
+ * differs from its background, grown and feathered at the photo's size.  sketch.reference (CPU torch) is the definition; every pass is
+ * bit-equal to its stage.  Planes are uint8 [H][W], contiguous.
+ * ce_sketch_changed_u8: background, composite = uint8 [pixels][3] -> out = uint8 [pixels]: 255 where max over the three channels of
+ *   |composite - background| > threshold, else 0.  threshold in 0..254 (otherwise -1).  16-byte accesses when all three pointers are
+ *   16-byte aligned, byte by byte otherwise - the same bytes.
+ * ce_sketch_dilate_u8: one axis (0: along a row, 1: along a column) of the maximum filter of a 0 / 255 plane, the window [i - radius,
+ *   i + radius] clipped to the image: dst = 255 where the window holds a non-zero byte of src, else 0 (the input is binary by construction,
+ *   so the pass counts).  radius in 0..4096 (otherwise -1).
+ * ce_sketch_box_u8: one axis of the box mean, the window [i - radius, i + radius] over the line continued by its edge bytes: acc = the
+ *   integer sum of the 2 radius + 1 bytes, ww = 2^24 / (2 radius + 1) in integers, dst = (acc * ww + 2^23) >> 24 - PIL's BoxBlur for an
+ *   integer radius.  radius in 0..1024 (otherwise -1).
+ * What a pass costs per byte: along a row a window sum is the difference of two entries of a prefix sum built in the LDS (up to 52 KiB of it
+ *   at the largest radius) - the run of 4096 outputs reads 2 radius more input bytes, nothing else follows the radius.  Along a column it is
+ *   a running sum (two loads per output) over segments of 32 rows, four adjacent columns per lane; the first window of a segment is summed
+ *   row by row while it holds at most 128 rows (radius <= 63: 2 to 6 loads per output), and from per-segment sums otherwise: a first launch
+ *   writes uint16 [ceil(H / 32)][W] to `scratch`, and a segment then gathers fewer than 64 rows and (2 radius + 1) / 32 eight-byte entries -
+ *   the one term that still follows the radius, at most 8 such loads per output at radius 4096.  The grid does not depend on the radius.
+ *   W % 4 != 0, or a base that is not 4-byte aligned: the column passes keep four columns per lane but move single bytes (the same
+ *   bytes come out; measured 2 - 4 times slower, profiles/notes_sketch.md).
+ * scratch: needed when axis == 1 and radius >= 64: at least ceil(H / 32) * W * 2 bytes, 8-byte aligned (otherwise -1 / -3), aliasing neither
+ *   plane; ignored (may be NULL) otherwise.
+ * out / dst alias no input (otherwise -1); every byte of it is written.  No state, nothing allocated, no host read: every call is
+ * capturable.  Integers only: the result is exact and does not depend on the launch order.  An image of 2^31 bytes or more (pixels * 3,
+ * H * W) returns -2. */
+int ce_sketch_changed_u8(const void* background, const void* composite, void* out, long long pixels, int threshold, hipStream_t stream);
+int ce_sketch_dilate_u8(const void* src, void* dst, int H, int W, int axis, int radius, void* scratch, size_t scratch_bytes,
+                        hipStream_t stream);
+int ce_sketch_box_u8(const void* src, void* dst, int H, int W, int axis, int radius, void* scratch, size_t scratch_bytes, hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
