@@ -15,8 +15,9 @@ seam, is the checkpoint's business."""
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from fractions import Fraction
-from typing import List, Optional, Tuple
+from typing import Any, List, Optional, Tuple
 
 import torch
 
@@ -164,3 +165,92 @@ def masks_for(masks, n_img: int) -> List:
             raise ValueError(f"the edit region holds {len(masks)} masks, but the call has {n_img} image(s): pass one mask, or one per image")
         return masks
     return [masks] * n_img
+
+
+# ---- one image of a focused call --------------------------------------------------------------------------------------------------
+@dataclass
+class FocusPlan:
+    """What a focused edit knows about one image; the mask lies on the host, on the device, or both."""
+    image: Any  # the PIL photo the crop is cut from: the VAE and CLIP see its crop
+    report: dict  # `plan`'s entries; report["box"] is the crop
+    mask_u8: Optional[torch.Tensor] = None  # the source-size mask on the host
+    mask_dev: Optional[torch.Tensor] = None  # ... on the device
+    src_u8: Optional[torch.Tensor] = None  # the photo's bytes on the device: set when the device passes run
+    paste_image: Any = None  # a second source the frames are pasted into (a sketch edit's background); None: `image`
+    paste_u8: Optional[torch.Tensor] = None  # its bytes on the device
+
+    @classmethod
+    def make(cls, image, report: dict, mask: torch.Tensor, device=None, paste_image=None, uploaded=None) -> "FocusPlan":
+        """mask: uint8 [SH, SW] where it lies.  device: set for the device passes - the photo is uploaded once (uploaded = (the photo's
+        bytes, the paste source's) when they are up there already) and a host mask goes with it; None: PIL on the host."""
+        from . import image_io
+        p = cls(image, report, paste_image=paste_image)
+        if mask.is_cuda:
+            p.mask_dev = mask
+        else:
+            p.mask_u8 = mask
+        if device is not None:
+            p.src_u8, p.paste_u8 = uploaded if uploaded is not None else (image_io.upload_rgb(image, device), None)
+            if p.mask_dev is None:
+                p.mask_dev = mask.to(device)
+        return p
+
+    @property
+    def box(self) -> Box:
+        return self.report["box"]
+
+    def host_mask(self) -> torch.Tensor:
+        """The mask on the host: a mask that was made on the device is copied once, when somebody asks."""
+        if self.mask_u8 is None:
+            self.mask_u8 = self.mask_dev.cpu()
+        return self.mask_u8
+
+
+def setup(image, masks, height: int, width: int, context: float, output_type, device=None) -> List[FocusPlan]:
+    """Per image of a focused call its FocusPlan (device as in `FocusPlan.make`), or the refusals of `enable_region_focus`."""
+    from . import image_io
+    imgs = image_io._pil_list(image) if image is not None else None
+    if imgs is None:
+        raise ValueError("region focus needs PIL input (one image or a list): an array or tensor `image` has no full-resolution bytes to "
+                         "paste the edit back into - pass PIL images, or disable_region_focus()")
+    if output_type in ("np", "pt") and len({im.size for im in imgs}) > 1:
+        raise ValueError(f"region focus returns frames of the sources' sizes {[im.size for im in imgs]}: output_type={output_type!r} "
+                         'needs sources of one size, use "pil"')
+    return [FocusPlan.make(im, *_plan(im.size, m, height, width, context), device) for im, m in zip(imgs, masks_for(masks, len(imgs)))]
+
+
+def inputs(plans: List[FocusPlan], height: int, width: int, device):
+    """(img bf16 [n, 3, height, width] as preprocessing leaves it, the edit-size region masks uint8 [height, width] on the device) of
+    the crops: the device passes, or PIL itself (`host_inputs`)."""
+    from . import image_io, ops
+    if plans[0].src_u8 is not None:
+        img = torch.empty((len(plans), 3, height, width), dtype=torch.bfloat16, device=device)
+        masks = []
+        for j, p in enumerate(plans):
+            crop, m = device_inputs(p.src_u8, p.mask_dev, p.box, width, height)
+            ops.image_u8_lut_planar(crop, image_io.vae_lut(torch.device(device)), img[j])
+            masks.append(m)
+        return img, masks
+    host = [host_inputs(p.image, p.host_mask(), p.box, width, height) for p in plans]
+    img = image_io.preprocess_image([c for c, _ in host], height, width).to(device=device, dtype=torch.bfloat16)
+    return img, [m.to(device) for _, m in host]
+
+
+def paste(video: torch.Tensor, plans: List[FocusPlan], image_of, output_type: str, composite: bool):
+    """The source-size paste-back of every sample's frames (reasoning frames included), in postprocess_video's layouts: through the mask
+    (composite), or the whole box.  A plan with a second source is pasted into that one."""
+    import numpy as np
+    from . import image_io, ops
+    image_io.check_output_type(output_type)
+    on_device = plans[0].src_u8 is not None and image_io.device_video(video)
+    u8 = ops.video_to_u8(video.contiguous()) if on_device else None
+    out = []
+    for b in range(video.shape[0]):
+        p = plans[image_of(b)]
+        if on_device:
+            out.append(device_paste(u8[b], p.src_u8 if p.paste_u8 is None else p.paste_u8, p.mask_dev if composite else None, p.box).cpu().numpy())
+        else:
+            frames = image_io.postprocess_video(video[b:b + 1], "pil")[0]
+            pasted = host_paste(p.image if p.paste_image is None else p.paste_image, frames, p.host_mask() if composite else None, p.box)
+            out.append(np.stack([np.asarray(f, dtype=np.uint8) for f in pasted]))
+    return image_io.frames_from_u8(out, output_type)

@@ -136,6 +136,16 @@ def _pil_list(images) -> Optional[list]:
     return imgs if imgs and all(_is_pil(i) for i in imgs) else None
 
 
+def on_device(enabled: bool, device) -> bool:
+    """Do the image passes of this call run on the device?  `enable_device_image_io` is on and the pipeline lies on a GPU."""
+    return bool(enabled) and torch.device(device).type == "cuda"
+
+
+def device_video(video: torch.Tensor) -> bool:
+    """A decoded video that `ops.video_to_u8` takes where it lies."""
+    return video.is_cuda and video.dtype in (torch.bfloat16, torch.float32)
+
+
 def upload_rgb(image, device) -> torch.Tensor:
     """A PIL image as uint8 [H, W, 3] on the device (`convert("RGB")` on the host, then the raw bytes)."""
     import numpy as np
@@ -273,9 +283,64 @@ def clip_pixel_values(processor, images, device) -> Optional[torch.Tensor]:
     return out
 
 
+def preprocess_image(image, height: int, width: int) -> torch.Tensor:
+    """VideoProcessor.preprocess(image, height=, width=): PIL / array / tensor -> [B,3,height,width] in [-1, 1] (fp32, CPU or
+    the tensor's device).  PIL images are resized with Lanczos, arrays / tensors with F.interpolate's default mode (nearest) - both as
+    diffusers' VaeImageProcessor.resize does; arrays / tensors are taken as [0, 1] unless they already carry negative values
+    (diffusers' own rule)."""
+    import numpy as np
+    if _is_pil(image) or (isinstance(image, (list, tuple)) and all(_is_pil(i) for i in image)):
+        from PIL import Image
+        imgs = list(image) if isinstance(image, (list, tuple)) else [image]
+        arr = np.stack([np.asarray(i.convert("RGB").resize((width, height), Image.LANCZOS), dtype=np.float32) / 255.0 for i in imgs])
+        x = torch.from_numpy(arr).permute(0, 3, 1, 2)
+    elif isinstance(image, np.ndarray):
+        x = torch.from_numpy(image.astype(np.float32))
+        x = x[None] if x.dim() == 3 else x
+        x = x.permute(0, 3, 1, 2)
+    elif isinstance(image, torch.Tensor):
+        x = image.float()
+        x = x[None] if x.dim() == 3 else x
+    else:
+        raise ValueError(f"`image` has to be of type `torch.Tensor` or `PIL.Image.Image` but is {type(image)}")
+    if x.shape[-2:] != (height, width):
+        x = torch.nn.functional.interpolate(x, size=(height, width))  # arrays / tensors: F.interpolate's default (nearest), as diffusers' VaeImageProcessor.resize
+    if x.min() >= 0:
+        x = 2.0 * x - 1.0
+    return x.contiguous()
+
+
+def check_output_type(output_type):
+    if output_type not in ("np", "pt", "pil"):
+        raise ValueError(f"{output_type} does not exist. Please choose one of ['np', 'pt', 'pil']")
+
+
+def postprocess_video(video: torch.Tensor, output_type: str = "np"):
+    """VideoProcessor.postprocess_video: [B,3,F,H,W] in [-1,1] -> per sample F frames in [0,1]: "np" [B,F,H,W,3] float32,
+    "pt" [B,F,3,H,W], "pil" list of lists of PIL images."""
+    v = (video.float() / 2 + 0.5).clamp(0, 1).permute(0, 2, 1, 3, 4)  # [B,F,3,H,W]
+    if output_type == "pt":
+        return v
+    arr = v.permute(0, 1, 3, 4, 2).cpu().numpy()
+    if output_type == "np":
+        return arr
+    check_output_type(output_type)
+    from PIL import Image
+    return [[Image.fromarray((f * 255).round().astype("uint8")) for f in sample] for sample in arr]
+
+
+def frames_from_u8(samples, output_type: str):
+    """Per sample the bytes uint8 [F, H, W, 3] (numpy, on the host) in postprocess_video's layouts: "pil" the frames themselves, "np" /
+    "pt" the bytes / 255 (the samples must then share a size)."""
+    import numpy as np
+    if output_type == "pil":
+        from PIL import Image
+        return [[Image.fromarray(f) for f in sample] for sample in samples]
+    arr = np.stack(samples).astype(np.float32) / 255.0  # [B, F, H, W, 3]
+    return arr if output_type == "np" else torch.from_numpy(arr).permute(0, 1, 4, 2, 3)
+
+
 def frames_to_pil(video: torch.Tensor):
     """pipeline.postprocess_video(video, "pil") for a bf16 / fp32 video [B, 3, F, H, W] on the device: one pass to uint8 [B, F, H, W, 3], one
     device-to-host copy of the bytes, Image.fromarray per frame."""
-    from PIL import Image
-    arr = ops.video_to_u8(video.contiguous()).cpu().numpy()
-    return [[Image.fromarray(f) for f in sample] for sample in arr]
+    return frames_from_u8(ops.video_to_u8(video.contiguous()).cpu().numpy(), "pil")

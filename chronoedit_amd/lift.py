@@ -258,3 +258,51 @@ def lift(P: torch.Tensor, L: torch.Tensor, E: torch.Tensor, U: Optional[torch.Te
     tabs = tables((P.shape[1], P.shape[0]), tuple(L.shape[:2]), P.device)
     out = ops.lift_apply_u8(P, coef, tabs, U.contiguous() if cfg.gate is not None else None)
     return out, coef[..., 6].double().mean()
+
+
+# ---- the output stage of a lifted call ---------------------------------------------------------------------------------------------------
+def report_entry(size, edit_size, reason: str) -> dict:
+    """One sample's `lift_report` entry: "ok" is the lift, "same" (the image has the edit's size already) and "focus" are not."""
+    return {"size": size, "edit_size": (int(edit_size[0]), int(edit_size[1])), "applied": reason == "ok", "reason": reason, "fallback_fraction": None}
+
+
+def output(video: torch.Tensor, cfg: LiftConfig, kept, imgs, image_of, height: int, width: int, output_type: str):
+    """(every sample's frames lifted to its image's size, in postprocess_video's layouts - None when every image already has the edit's
+    size: the caller then returns the plain frames -, the `lift_report`).  kept: per image (P, L) on the device
+    (`image_io.preprocess_pil`), or None: the host form.  The gate means of all samples are read back once."""
+    from PIL import Image
+    from . import image_io, ops
+    image_io.check_output_type(output_type)
+    B = video.shape[0]
+    same = [imgs[image_of(b)].size == (width, height) for b in range(B)]
+    report = [report_entry(imgs[image_of(b)].size, (width, height), "same" if same[b] else "ok") for b in range(B)]
+    if all(same):
+        return None, report
+    on_device = kept is not None and image_io.device_video(video)
+    u8 = ops.video_to_u8(video.contiguous()) if on_device else None
+    out, fractions = [], []
+    for b in range(B):
+        im = imgs[image_of(b)]
+        if on_device:
+            E = u8[b]
+        else:
+            frames = image_io.postprocess_video(video[b:b + 1], "pil")[0]
+            E = torch.from_numpy(np.stack([np.asarray(f, dtype=np.uint8) for f in frames]))
+        if same[b]:
+            out.append(E)
+            continue
+        if on_device:
+            P, L = kept[image_of(b)]
+            U = None if cfg.gate is None else torch.stack([image_io.resize_u8(f, im.size, image_io.LANCZOS) for f in E])
+        else:
+            rgb = im.convert("RGB")
+            P = torch.from_numpy(np.array(rgb, dtype=np.uint8))
+            L = torch.from_numpy(np.array(rgb.resize((width, height), Image.LANCZOS), dtype=np.uint8))
+            U = None if cfg.gate is None else torch.from_numpy(np.stack([np.asarray(f.resize(im.size, Image.LANCZOS), dtype=np.uint8) for f in frames]))
+        o, frac = lift(P, L, E, U, cfg)
+        out.append(o)
+        fractions.append((b, frac))
+    if fractions:
+        for (b, _), v in zip(fractions, torch.stack([f for _, f in fractions]).cpu().tolist()):
+            report[b]["fallback_fraction"] = float(v)
+    return image_io.frames_from_u8([o.cpu().numpy() for o in out], output_type), report

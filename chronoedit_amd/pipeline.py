@@ -8,25 +8,18 @@ from __future__ import annotations
 
 import contextlib
 import html
+import inspect
 import re
-from dataclasses import dataclass
+from dataclasses import dataclass, make_dataclass, replace
 from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
-from . import image_io
+from . import auto_region as _ar, autofocus as _af, focus as _fc, image_io, lift as _lf, preview as _pv, region as _rg, sketch as _sk
 from .loop import (GraphedDenoiser, _capturable, _sharded_batchable, _shared_inputs, _token_sharded, _warmup_stream,  # noqa: F401
                    compact_text_context, denoise, denoise_step, make_cfg_inputs, text_compaction_plan, text_real_lengths)
 from .scheduler import FlowUniPCMultistepScheduler
 from .transformer import ChronoEditTransformer3DModel
-
-
-def _is_pil(x) -> bool:
-    try:
-        from PIL import Image
-    except ImportError:  # pragma: no cover
-        return False
-    return isinstance(x, Image.Image)
 
 
 def prompt_clean(text: str) -> str:
@@ -60,8 +53,7 @@ def prepare_latents(vae, image: torch.Tensor, num_frames: int, latents: Optional
     else:
         latents = latents.to(device=dev, dtype=torch.float32)
     video = torch.cat([image.unsqueeze(2), image.new_zeros(B, 3, num_frames - 1, H, W)], dim=2).to(torch.bfloat16)
-    mean = torch.tensor(vae.config.latents_mean, device=dev, dtype=torch.bfloat16).view(1, z, 1, 1, 1)
-    inv_std = (1.0 / torch.tensor(vae.config.latents_std)).to(device=dev, dtype=torch.bfloat16).view(1, z, 1, 1, 1)
+    mean, inv_std = _rg.latent_stats(vae, dev)
     cond = vae.encode(video).latent_dist.mode()
     cond = (cond - mean) * inv_std
     mask = torch.ones(B, 1, num_frames, h, w, device=dev)
@@ -75,10 +67,8 @@ def prepare_latents(vae, image: torch.Tensor, num_frames: int, latents: Optional
 def decode_latents(vae, latents: torch.Tensor, enable_temporal_reasoning: bool = False, num_temporal_reasoning_steps: int = 0):
     """pipeline_chronoedit.py:765-781: de-normalise, decode; in reasoning mode the edit frames and the reasoning frames are
     decoded separately and concatenated."""
-    z = vae.config.z_dim
     latents = latents.to(torch.bfloat16)
-    mean = torch.tensor(vae.config.latents_mean, device=latents.device, dtype=latents.dtype).view(1, z, 1, 1, 1)
-    inv_std = (1.0 / torch.tensor(vae.config.latents_std)).to(device=latents.device, dtype=latents.dtype).view(1, z, 1, 1, 1)
+    mean, inv_std = _rg.latent_stats(vae, latents.device)
     latents = latents / inv_std + mean
     if enable_temporal_reasoning and num_temporal_reasoning_steps > 0 and latents.shape[2] > 2:
         edit = vae.decode(latents[:, :, [0, -1]], return_dict=False)[0]
@@ -92,6 +82,27 @@ class WanPipelineOutput:
     """diffusers.pipelines.wan.pipeline_output.WanPipelineOutput: `.frames` is what callers index
     (run_inference_diffusers.py:441 `.frames[0]`)."""
     frames: Any
+
+
+@dataclass
+class FocusPass:
+    """A focused pass that its caller planned - a sketch edit, or the scout of an auto-focused call - in place of the user's switches."""
+    plans: list  # one focus.FocusPlan per image
+    composite: bool  # paste the frames through the masks (else: the whole box)
+    start: Optional[dict] = None  # the warm start {"step", "x0", "sigma"}: begin at that step on the scout's resampled estimate
+    preview_tag: Optional[str] = None  # the "pass" entry of this pass's previews
+    guarded: bool = False  # the text guardrail has seen the call's prompt already
+
+
+@dataclass
+class EditSources:
+    """What one pass edits, resolved once at its top (`ChronoEditPipeline._resolve`)."""
+    pil: Optional[list] = None  # the call's PIL images; None: arrays or tensors
+    focus: Optional[list] = None  # a focused region edit: per image its focus.FocusPlan (the encoders then see the crops)
+    masks: Any = None  # an unfocused region edit: the explicit edit-size mask(s)
+    composite: bool = False  # paste the source back through the masks behind the decode
+    auto_focus: Any = None  # the autofocus.AutoFocusConfig when this pass is a scout
+    lift: Any = None  # the lift.LiftConfig while the detail lift is on (a focused pass only reports it)
 
 
 def _randn_tensor(shape, generator, device, dtype):
@@ -155,7 +166,6 @@ class ChronoEditPipeline:
         self._region_focus = None  # the context fraction while enable_region_focus is in force
         self.focus_report = None  # the last call's focus plans, one dict per image (focus.plan); None when focus did not run
         self._auto_focus = None  # the autofocus.AutoFocusConfig while enable_auto_focus is in force
-        self._focus_pass = None  # one shot: what the scout of an auto-focused call hands to the focused pass it starts (`_auto_focus_pass`)
         self._preview = None  # the options of `enable_preview` while it is in force
         self.preview_factors = None  # fp32 [17, 3]: the latent -> RGB map of the previews (`fit_preview_factors`, or set by hand)
         self.preview_fit_report = None  # {"rms", "r2"} per colour of the last fit
@@ -315,7 +325,7 @@ class ChronoEditPipeline:
         if self.image_processor is not None and not (isinstance(image, torch.Tensor) and image.dim() == 4 and image.is_floating_point()
                                                      and image.shape[1] == 3 and image.min() < 0):
             pixel_values = None
-            if self.device_image_io and torch.device(device).type == "cuda":
+            if image_io.on_device(self.device_image_io, device):
                 pixel_values = image_io.clip_pixel_values(self.image_processor, image, device)  # None: not the plain CLIP recipe on PIL input
             if pixel_values is None:
                 pixel_values = self.image_processor(images=image, return_tensors="pt")["pixel_values"]
@@ -334,7 +344,7 @@ class ChronoEditPipeline:
         needs - their sizes may differ)."""
         if image is None and image_embeds is None:
             raise ValueError("Provide either `image` or `prompt_embeds`. Cannot leave both `image` and `image_embeds` undefined.")
-        if image is not None and not isinstance(image, torch.Tensor) and not _is_pil(image) and image_io._pil_list(image) is None:
+        if image is not None and not isinstance(image, torch.Tensor) and not image_io._is_pil(image) and image_io._pil_list(image) is None:
             raise ValueError(f"`image` has to be of type `torch.Tensor` or `PIL.Image.Image` but is {type(image)}")
         if height % 16 != 0 or width % 16 != 0:
             raise ValueError(f"`height` and `width` have to be divisible by 16 but are {height} and {width}.")
@@ -392,6 +402,29 @@ class ChronoEditPipeline:
         self.transformer.disable_lora()
         return self
 
+    def enable_lora(self):
+        self.transformer.enable_lora()
+        return self
+
+    def unfuse_lora(self):
+        self.transformer.unfuse_lora()
+        return self
+
+    def delete_adapters(self, adapter_names):
+        self.transformer.delete_adapters(adapter_names)
+        return self
+
+    def get_active_adapters(self) -> List[str]:
+        return self.transformer.get_active_adapters()
+
+    def get_list_adapters(self) -> Dict[str, List[str]]:
+        """{component: loaded adapter names}, as diffusers returns it; the adapters target the transformer only."""
+        return {"transformer": self.transformer.get_list_adapters()}
+
+    def unload_lora_weights(self):
+        self.transformer.unload_lora_weights()
+        return self
+
     # TeaCache step skipping (chronoedit_amd/teacache.py): a switch on the pipeline, `__call__` keeps the reference's signature
     def enable_teacache(self, rel_l1_thresh: float, coefficients=(1.0, 0.0)):
         self.transformer.enable_teacache(rel_l1_thresh, coefficients)
@@ -407,15 +440,16 @@ class ChronoEditPipeline:
         and nothing `edit_tensors` does not take, of `__call__` otherwise; call_kwargs are added to every edit.  Each edit runs measured (`denoise`: every step computes, eagerly; no frames are
         decoded), the (ratio, distance) points of all of them are pooled and fitted.  Returns the teacache.TeaCacheCalibration, whose
         `.coefficients` `enable_teacache(thresh, coefficients)` takes as they are; TeaCache itself is NOT switched on."""
-        import inspect
+        runs = [lambda kw=kw: self._run_edit(kw, call_kwargs, num_inference_steps, guidance_scale) for kw in edits]
+        return self.transformer.calibrate_teacache(runs, degree=degree)
+
+    def _run_edit(self, kw: dict, common: dict, num_inference_steps: int, guidance_scale: float) -> torch.Tensor:
+        """One edit dict of `calibrate_teacache` and the measuring methods, `common` added: through `edit_tensors` when it carries the three
+        embeds and nothing `edit_tensors` does not take, through `__call__` otherwise -> the edit's final latents."""
+        kw = dict(common, **kw, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, output_type="latent")
         tensor_args = set(inspect.signature(self.edit_tensors).parameters)
-        embeds = {"prompt_embeds", "negative_prompt_embeds", "image_embeds"}
-
-        def runner(kw):
-            kw = dict(call_kwargs, **kw, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, output_type="latent")
-            return lambda: (self.edit_tensors if embeds <= set(kw) <= tensor_args else self.__call__)(**kw)
-
-        return self.transformer.calibrate_teacache([runner(kw) for kw in edits], degree=degree)
+        res = (self.edit_tensors if {"prompt_embeds", "negative_prompt_embeds", "image_embeds"} <= set(kw) <= tensor_args else self.__call__)(**kw)
+        return res if isinstance(res, torch.Tensor) else res.frames
 
     # Guidance reuse (chronoedit_amd/guidance.py): the unconditional sample only on planned steps.  Off by default; a switch on the
     # pipeline, `__call__` keeps the reference's signature and `edit_tensors` honours it too
@@ -463,7 +497,6 @@ class ChronoEditPipeline:
         i + lag is enqueued, so the loop never waits for it; `pipe._interrupt = True` from the callback stops the edit early.  With an edit
         region and `composite` the kept area shows the source; under region focus the picture is the crop's.  "pass" is "scout" / "focus"
         in an auto-focused call, else None.  The returned frames are those of the call without previews, bit for bit."""
-        from . import preview as _pv
         if factors is None and self.preview_factors is None:
             raise ValueError("enable_preview: no factors - pass factors=, or fit them on the loaded VAE with fit_preview_factors(images)")
         _pv.PreviewConfig(on_preview, every, scale, frame, composite, lag, factors if factors is not None else self.preview_factors)  # validates
@@ -480,7 +513,6 @@ class ChronoEditPipeline:
         with "sample" and "pass" added."""
         if self._preview is None:
             return None
-        from . import preview as _pv
         o = dict(self._preview)
         user = o["on_preview"]
         o["on_preview"] = lambda d: user({**d, "sample": sample, "pass": tag})
@@ -501,12 +533,11 @@ class ChronoEditPipeline:
         images = list(images) if isinstance(images, (list, tuple)) else [images]
         if not images:
             raise ValueError("fit_preview_factors: no images")
-        device, zd = self._execution_device, self.vae.config.z_dim
-        mean = torch.tensor(self.vae.config.latents_mean, device=device, dtype=torch.bfloat16).view(1, zd, 1, 1, 1)
-        inv_std = (1.0 / torch.tensor(self.vae.config.latents_std)).to(device=device, dtype=torch.bfloat16).view(1, zd, 1, 1, 1)
+        device = self._execution_device
+        mean, inv_std = _rg.latent_stats(self.vae, device)
         zs, ys = [], []
         for im in images:
-            if self.device_image_io and device.type == "cuda" and _is_pil(im):
+            if image_io.on_device(self.device_image_io, device) and image_io._is_pil(im):
                 img = image_io.preprocess_pil(im, height, width, device)
             else:
                 img = self.preprocess_image(im, height, width).to(device=device, dtype=torch.bfloat16)
@@ -523,7 +554,6 @@ class ChronoEditPipeline:
         preview.solve_factors.  Sets `preview_factors`, `preview_fit_report` ({"rms", "r2"} per colour: how well a linear map fits THIS
         checkpoint) and `preview_fit_gram`; returns the factors (fp32 [17, 3])."""
         from . import ops
-        from . import preview as _pv
         z, y = self.preview_fit_tensors(images, height, width)
         if y.dtype not in (torch.bfloat16, torch.float32):
             y = y.float()
@@ -544,22 +574,17 @@ class ChronoEditPipeline:
         step also writes its change map into a [steps, h, w] device table, read back once after the last step.  Returns per edit
         {"timesteps", "steps": per step {"step", "threshold", "active_fraction", "iou" (of that step's seed set with the last step's)},
         "latents"}.  The detector itself is NOT switched on, an enabled one and an edit region are ignored here."""
-        import inspect
-        from . import auto_region as _ar
         det = {k: options.pop(k) for k in ("threshold", "floor", "dilate", "feather", "max_area") if k in options}
         cfg = _ar.AutoRegionConfig(detect_step=0, **det)
-        tensor_args = set(inspect.signature(self.edit_tensors).parameters)
-        embeds = {"prompt_embeds", "negative_prompt_embeds", "image_embeds"}
         out, saved = [], self._edit_region
         self._auto_region_measure, self._edit_region = cfg, None
         try:
             for kw in edits:
-                kw = dict(options, **kw, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, output_type="latent")
                 self.transformer.auto_region_measurement = None
-                res = (self.edit_tensors if embeds <= set(kw) <= tensor_args else self.__call__)(**kw)
+                latents = self._run_edit(kw, options, num_inference_steps, guidance_scale)
                 if self.transformer.auto_region_measurement is None:
                     raise RuntimeError("measure_auto_region: the edit was not measured")
-                out.append(dict(self.transformer.auto_region_measurement, latents=res if isinstance(res, torch.Tensor) else res.frames))
+                out.append(dict(self.transformer.auto_region_measurement, latents=latents))
         finally:
             self._auto_region_measure, self._edit_region = None, saved
         return out
@@ -572,19 +597,15 @@ class ChronoEditPipeline:
         are decoded).  Returns per edit {"timesteps", "rel_l2": [steps][max_age]} - rel_l2[i][a - 1] = ||d_i - d_(i-a)|| / ||d_i||, NaN
         where no direction of that age and latent shape exists - plus, with keep_deltas, "deltas" (the per-step directions, on the CPU)
         and always "latents" (the edit's final latents).  Guidance reuse itself is NOT switched on, and an enabled one is ignored here."""
-        import inspect
-        tensor_args = set(inspect.signature(self.edit_tensors).parameters)
-        embeds = {"prompt_embeds", "negative_prompt_embeds", "image_embeds"}
         out = []
         self._guidance_measure = (int(max_age), bool(keep_deltas))
         try:
             for kw in edits:
-                kw = dict(call_kwargs, **kw, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, output_type="latent")
                 self.transformer.guidance_measurement = None
-                res = (self.edit_tensors if embeds <= set(kw) <= tensor_args else self.__call__)(**kw)
+                latents = self._run_edit(kw, call_kwargs, num_inference_steps, guidance_scale)
                 if self.transformer.guidance_measurement is None:
                     raise RuntimeError("measure_guidance_reuse: the edit was not measured (more than one sample per call, or no guidance)")
-                out.append(dict(self.transformer.guidance_measurement, latents=res if isinstance(res, torch.Tensor) else res.frames))
+                out.append(dict(self.transformer.guidance_measurement, latents=latents))
         finally:
             self._guidance_measure = None
         return out
@@ -619,7 +640,6 @@ class ChronoEditPipeline:
         `focus_report` holds one dict per image afterwards (focus.plan shows the same before an edit is spent).
         No effect without an explicit mask: with only `enable_auto_region` the call is the plain call - a detected mask arrives mid-edit,
         which is too late to re-crop; `enable_auto_focus` is the switch that starts over on the crop."""
-        from . import focus as _fc
         _fc.focus_box(None, (1, 1), (1, 1), context)  # (validates the context)
         self._region_focus = float(context)
         return self
@@ -642,7 +662,6 @@ class ChronoEditPipeline:
         `focus_report[0]` holds the focus plan plus "mask" (the photo-size mask, a PIL "L" image), "detect" (the scout's auto-region
         report) and "start_step"; `callback_on_step_end` sees the scout's steps 0..k, then the focused pass's.  An array or tensor image
         is a ValueError; more than one sample per call, temporal reasoning and `offload_model` a NotImplementedError."""
-        from . import autofocus as _af
         self._auto_focus = _af.AutoFocusConfig(float(context), warm_start)
         return self
 
@@ -668,7 +687,6 @@ class ChronoEditPipeline:
         wins: an editor value then stands for its composite.  A value whose two images differ in size, or that lacks one, is a ValueError.
         `sketch_report` holds per value the focus plan's entries (`focus_report`'s) plus "mask" (PIL "L", the photo's size), "grow_px",
         "feather_px", "threshold" and "changed_pixels"."""
-        from . import sketch as _sk
         self._sketch_region = _sk.SketchConfig(grow, feather, threshold, context, composite)
         return self
 
@@ -680,102 +698,12 @@ class ChronoEditPipeline:
         """The mask a sketch call would build for this pair of PIL images with the enabled parameters, as a PIL "L" image of their size - for
         a front end to show before an edit is spent."""
         from PIL import Image
-        from . import sketch as _sk
         if self._sketch_region is None:
             raise ValueError("sketch_mask needs the parameters of enable_sketch_region(): the switch is off")
         bgs, cps = _sk.editor_images({"background": background, "composite": composite})
-        e = self._sketch_masks(bgs, cps, self._execution_device)[0]
-        return Image.fromarray(self._sketch_host_mask(e).numpy(), mode="L")  # (no edit follows: the copy of the mask may be made here)
-
-    def _sketch_masks(self, bgs, cps, device):
-        """Per editor value {"background", "composite", "mask_u8" (host; None on the device path: `_sketch_host_mask` copies it when the edit
-        is done), "grow_px", "feather_px", "bbox" (None: no strokes), "mask_pixels", "changed_pixels"} and, on the device path, "bg_u8",
-        "cp_u8", "mask_dev": each image uploaded once, two reductions and ONE read of their ten integers per value - nothing else comes back."""
-        from . import autofocus as _af
-        from . import sketch as _sk
-        cfg = self._sketch_region
-        on_device = self.device_image_io and torch.device(device).type == "cuda"
-        out = []
-        for bg, cp in zip(bgs, cps):
-            g, f = cfg.pixels(bg.size)
-            e = {"background": bg, "composite": cp, "grow_px": g, "feather_px": f}
-            if on_device:
-                e["bg_u8"], e["cp_u8"] = image_io.upload_rgb(bg, device), image_io.upload_rgb(cp, device)
-                ch, _, m = _sk.stages(e["bg_u8"], e["cp_u8"], g, f, cfg.threshold)
-                counts = torch.cat([_af.bbox_counts(m), _af.bbox_counts(ch)]).tolist()
-                e["mask_dev"], e["mask_u8"] = m, None
-            else:
-                ch, _, m = _sk.stages(bg, cp, g, f, cfg.threshold)
-                counts = _af.bbox_counts(m).tolist() + _af.bbox_counts(ch).tolist()
-                e["mask_u8"] = m
-            e["bbox"] = tuple(int(v) for v in counts[:4]) if counts[4] else None
-            e["mask_pixels"], e["changed_pixels"] = int(counts[4]), int(counts[9])
-            out.append(e)
-        return out
-
-    @staticmethod
-    def _sketch_host_mask(e) -> torch.Tensor:
-        """The mask of one `_sketch_masks` entry on the host: the device path's 12 MB copy, made once and behind the edit (an empty mask needs
-        no copy)."""
-        if e["mask_u8"] is None:
-            e["mask_u8"] = e["mask_dev"].cpu() if e["bbox"] is not None else torch.zeros(tuple(e["mask_dev"].shape), dtype=torch.uint8)
-        return e["mask_u8"]
-
-    def _sketch_call(self, value, call: dict):
-        """`__call__` with an editor's value (or a list of them) as `image`: see `enable_sketch_region`."""
-        from PIL import Image
-        from . import focus as _fc
-        from . import sketch as _sk
-        if self._sketch_region is None:
-            raise ValueError("`image` is an image editor's value (a dict with \"background\" and \"composite\"): switch sketch edits on with "
-                             "enable_sketch_region() first, or pass the composite itself")
-        cfg = self._sketch_region
-        bgs, cps = _sk.editor_images(value)
-        image = cps if isinstance(value, (list, tuple)) else cps[0]
-        if self._edit_region is not None:  # an explicit mask wins: the editor value stands for its composite
-            return self(image=image, **call)
-        height, width = call["height"], call["width"]
-        if call["output_type"] in ("np", "pt") and len({im.size for im in bgs}) > 1:
-            raise ValueError(f"a sketch edit returns frames of the photos' sizes {[im.size for im in bgs]}: output_type={call['output_type']!r} "
-                             'needs photos of one size, use "pil"')
         device = self._execution_device
-        entries = self._sketch_masks(bgs, cps, device)
-        plans, plan_reports = [], []
-        for e in entries:
-            SW, SH = e["background"].size
-            box, reason = _fc.focus_box(e["bbox"], (SW, SH), (width, height), cfg.context)
-            l, t, r, b = box
-            # (the box holds the mask's bounding box, so the mask's share of the box is its count over the box's area)
-            plan = {"box": box, "reason": reason, "source_size": (SW, SH), "edit_size": (int(width), int(height)), "scale": (r - l) / int(width),
-                    "mask_fraction_of_box": float(e["mask_pixels"]) / ((r - l) * (b - t))}
-            p = {"image": e["composite"], "paste_image": e["background"], "box": box, "mask_u8": e["mask_u8"], "report": plan}
-            if "mask_dev" in e:
-                p["src_u8"], p["paste_u8"], p["mask_dev"] = e["cp_u8"], e["bg_u8"], e["mask_dev"]
-            plans.append(p)
-            plan_reports.append(plan)
-
-        def report():  # behind the edit: the device path copies its masks to the host here, not in front of the first step
-            return [dict(plan, mask=Image.fromarray(self._sketch_host_mask(e).numpy(), mode="L"), grow_px=e["grow_px"], feather_px=e["feather_px"],
-                         threshold=cfg.threshold, changed_pixels=e["changed_pixels"]) for plan, e in zip(plan_reports, entries)]
-
-        if all(e["bbox"] is None for e in entries):  # no strokes anywhere: the plain call on the composite(s)
-            out = self(image=image, **call)
-            self.sketch_report = report()
-            return out
-        saved = (self._edit_region, self._region_focus)
-        # (with the plans handed over, `__call__` reads the composite flag only; the masks named here are the plans' own, where they lie)
-        self._edit_region, self._region_focus = ([p.get("mask_dev", p["mask_u8"]) for p in plans], cfg.composite), cfg.context
-        self._focus_pass = {"plans": plans, "start": None, "explicit": True}
-        try:
-            out = self(image=image, **call)
-        finally:
-            self._focus_pass = None
-            self._edit_region, self._region_focus = saved
-        for p, e in zip(plans, entries):  # (a host paste-back has copied the mask already: keep that copy)
-            if e["mask_u8"] is None and p["mask_u8"] is not None:
-                e["mask_u8"] = p["mask_u8"]
-        self.sketch_report = report()
-        return out
+        e = _sk.masks(self._sketch_region, bgs, cps, device if image_io.on_device(self.device_image_io, device) else None)[0]
+        return Image.fromarray(_sk.host_mask(e).numpy(), mode="L")  # (no edit follows: the copy of the mask may be made here)
 
     # Guided detail lift (chronoedit_amd/lift.py): whole-image edits returned at the photo's size.  Off by default
     def enable_detail_lift(self, radius: int = 4, eps: float = 26.0, gate=(4.0, 12.0), max_gain: float = 8.0):
@@ -792,7 +720,6 @@ class ChronoEditPipeline:
         `enable_device_image_io(False)`, the same bytes), never inside a captured graph.  `lift_report` holds per sample {"size",
         "edit_size", "applied", "reason", "fallback_fraction"}: the last is the mean of the gate - how much of the picture was plain
         upsampling."""
-        from . import lift as _lf
         self._detail_lift = _lf.LiftConfig(radius, eps, None if gate is None else tuple(gate) if isinstance(gate, (tuple, list)) else gate, max_gain)
         return self
 
@@ -800,226 +727,15 @@ class ChronoEditPipeline:
         self._detail_lift = None
         return self
 
-    def _lift_output(self, video: torch.Tensor, cfg, kept, imgs, image_of, height: int, width: int, output_type: str):
-        """Every sample's frames lifted to its image's size, in postprocess_video's layouts - or None when every image already has the
-        edit's size (the caller then returns the plain frames).  kept: per image (P, L) on the device (`image_io.preprocess_pil`), or None:
-        the host form.  Fills `lift_report`; the gate means of all samples are read back once."""
-        import numpy as np
-        from PIL import Image
-        from . import lift as _lf
-        from . import ops
-        if output_type not in ("np", "pt", "pil"):
-            raise ValueError(f"{output_type} does not exist. Please choose one of ['np', 'pt', 'pil']")
-        B = video.shape[0]
-        same = [imgs[image_of(b)].size == (width, height) for b in range(B)]
-        entry = lambda b: {"size": imgs[image_of(b)].size, "edit_size": (int(width), int(height)), "applied": not same[b],
-                           "reason": "same" if same[b] else "ok", "fallback_fraction": None}
-        self.lift_report = [entry(b) for b in range(B)]
-        if all(same):
-            return None
-        on_device = kept is not None and video.is_cuda and video.dtype in (torch.bfloat16, torch.float32)
-        u8 = ops.video_to_u8(video.contiguous()) if on_device else None
-        out, fractions = [], []
-        for b in range(B):
-            im = imgs[image_of(b)]
-            if on_device:
-                E = u8[b]
-                if same[b]:
-                    out.append(E)
-                    continue
-                P, L = kept[image_of(b)]
-                U = None if cfg.gate is None else torch.stack([image_io.resize_u8(f, im.size, image_io.LANCZOS) for f in E])
-            else:
-                frames = self.postprocess_video(video[b:b + 1], "pil")[0]
-                E = torch.from_numpy(np.stack([np.asarray(f, dtype=np.uint8) for f in frames]))
-                if same[b]:
-                    out.append(E)
-                    continue
-                rgb = im.convert("RGB")
-                P = torch.from_numpy(np.array(rgb, dtype=np.uint8))
-                L = torch.from_numpy(np.array(rgb.resize((width, height), Image.LANCZOS), dtype=np.uint8))
-                U = None if cfg.gate is None else torch.from_numpy(np.stack([np.asarray(f.resize(im.size, Image.LANCZOS), dtype=np.uint8) for f in frames]))
-            o, frac = _lf.lift(P, L, E, U, cfg)
-            out.append(o)
-            fractions.append((b, frac))
-        if fractions:
-            for (b, _), v in zip(fractions, torch.stack([f for _, f in fractions]).cpu().tolist()):
-                self.lift_report[b]["fallback_fraction"] = float(v)
-        out = [o.cpu().numpy() for o in out]
-        if output_type == "pil":
-            return [[Image.fromarray(f) for f in sample] for sample in out]
-        arr = np.stack(out).astype(np.float32) / 255.0  # [B, F, SH, SW, 3]
-        return arr if output_type == "np" else torch.from_numpy(arr).permute(0, 1, 4, 2, 3)
-
-    def _auto_focus_plan(self, image, mask_edit: torch.Tensor, height: int, width: int, device) -> dict:
-        """The scout's decision: the detected edit-size mask (on the device) -> {"go", "plan"}: the lifted mask, the box (two reductions,
-        five integers read each) and, when the box is worth cropping to, a plan as `_focus_setup` makes them."""
-        from . import autofocus as _af
-        on_device = self.device_image_io and torch.device(device).type == "cuda"
-        mask_src = _af.lift_mask(mask_edit if on_device else mask_edit.cpu(), image.size)
-        report = _af.plan(mask_src, (width, height), self._auto_focus.context)
-        p = {"image": image, "box": report["box"], "report": report, "mask_u8": None if on_device else mask_src}
-        go = _af.worth_focusing(report)
-        if go and on_device:
-            p["src_u8"], p["mask_dev"] = image_io.upload_rgb(image, device), mask_src
-        return {"go": go, "plan": p}
-
-    def _focus_setup(self, image, height: int, width: int, device, output_type):
-        """Per image of a focused call: {"image", "box", "mask_u8" (host, source size), "report"} and, on the device path, "src_u8" (the
-        photo's bytes) and "mask_dev" - both uploaded once."""
-        from . import focus as _fc
-        imgs = image_io._pil_list(image) if image is not None else None
-        if imgs is None:
-            raise ValueError("region focus needs PIL input (one image or a list): an array or tensor `image` has no full-resolution bytes to "
-                             "paste the edit back into - pass PIL images, or disable_region_focus()")
-        if output_type in ("np", "pt") and len({im.size for im in imgs}) > 1:
-            raise ValueError(f"region focus returns frames of the sources' sizes {[im.size for im in imgs]}: output_type={output_type!r} "
-                             'needs sources of one size, use "pil"')
-        on_device = self.device_image_io and torch.device(device).type == "cuda"
-        plans = []
-        for im, m in zip(imgs, _fc.masks_for(self._edit_region[0], len(imgs))):
-            report, mask_u8 = _fc._plan(im.size, m, height, width, self._region_focus)
-            p = {"image": im, "box": report["box"], "mask_u8": mask_u8, "report": report}
-            if on_device:
-                p["src_u8"], p["mask_dev"] = image_io.upload_rgb(im, device), mask_u8.to(device)
-            plans.append(p)
-        return plans
-
-    def _focus_inputs(self, plans, height: int, width: int, device):
-        """(img bf16 [n, 3, height, width] as preprocessing leaves it, the edit-size region masks uint8 [height, width] on the device) of
-        the crops: the device passes, or PIL itself (focus.host_inputs)."""
-        from . import focus as _fc
-        from . import ops
-        if "src_u8" in plans[0]:
-            img = torch.empty((len(plans), 3, height, width), dtype=torch.bfloat16, device=device)
-            masks = []
-            for j, p in enumerate(plans):
-                crop, m = _fc.device_inputs(p["src_u8"], p["mask_dev"], p["box"], width, height)
-                ops.image_u8_lut_planar(crop, image_io.vae_lut(torch.device(device)), img[j])
-                masks.append(m)
-            return img, masks
-        host = [_fc.host_inputs(p["image"], p["mask_u8"], p["box"], width, height) for p in plans]
-        img = self.preprocess_image([c for c, _ in host], height, width).to(device=device, dtype=torch.bfloat16)
-        return img, [m.to(device) for _, m in host]
-
-    def _focus_output(self, video: torch.Tensor, plans, image_of, output_type: str):
-        """The source-size paste-back of every sample's frames (reasoning frames included), in postprocess_video's layouts.  A plan with a
-        second source ("paste_image" / "paste_u8": a sketch edit's background) is pasted into that one."""
-        import numpy as np
-        from . import focus as _fc
-        from . import ops
-        if output_type not in ("np", "pt", "pil"):
-            raise ValueError(f"{output_type} does not exist. Please choose one of ['np', 'pt', 'pil']")
-        composite = self._edit_region[1]
-        on_device = "src_u8" in plans[0] and video.is_cuda and video.dtype in (torch.bfloat16, torch.float32)
-        u8 = ops.video_to_u8(video.contiguous()) if on_device else None
-        out = []
-        for b in range(video.shape[0]):
-            p = plans[image_of(b)]
-            if on_device:
-                out.append(_fc.device_paste(u8[b], p.get("paste_u8", p["src_u8"]), p["mask_dev"] if composite else None, p["box"]).cpu().numpy())
-            else:
-                frames = self.postprocess_video(video[b:b + 1], "pil")[0]
-                if composite and p["mask_u8"] is None:  # (an auto-focused call keeps its lifted mask on the device)
-                    p["mask_u8"] = p["mask_dev"].cpu()
-                pasted = _fc.host_paste(p.get("paste_image", p["image"]), frames, p["mask_u8"] if composite else None, p["box"])
-                out.append(np.stack([np.asarray(f, dtype=np.uint8) for f in pasted]))
-        if output_type == "pil":
-            from PIL import Image
-            return [[Image.fromarray(f) for f in sample] for sample in out]
-        arr = np.stack(out).astype(np.float32) / 255.0  # [B, F, SH, SW, 3]
-        return arr if output_type == "np" else torch.from_numpy(arr).permute(0, 1, 4, 2, 3)
-
-    def _region_setup(self, masks, img: torch.Tensor, num_frames: int):
-        """masks (one, or a list with one per image of img) -> per image (uint8 mask [H, W] on the device, region.RegionConfig)."""
-        from . import region as _rg
-        n_img, _, H, W = img.shape
-        if isinstance(masks, list):
-            if len(masks) != n_img:
-                raise ValueError(f"the edit region holds {len(masks)} masks, but the call has {n_img} image(s): pass one mask, or one per image")
-        else:
-            masks = [masks] * n_img
-        z_src = _rg.static_source_latents(self.vae, img, num_frames)
-        out, seen = [], {}
-        for j, m in enumerate(masks):
-            if id(m) not in seen:  # (one mask for all images: normalised, uploaded and reduced once)
-                mu8 = _rg.normalize_mask(m, H, W).to(img.device)
-                seen[id(m)] = (mu8, _rg.latent_weights(mu8))
-            mu8, w = seen[id(m)]
-            out.append((mu8, _rg.RegionConfig(w=w, z_src=z_src[j:j + 1])))
-        return out
-
     def _measure_kwargs(self) -> dict:
         """What `denoise` gets on top while measure_guidance_reuse runs."""
         if self._guidance_measure is None:
             return {}
         return {"guidance_measure": self._guidance_measure[0], "keep_deltas": self._guidance_measure[1]}
 
-    def enable_lora(self):
-        self.transformer.enable_lora()
-        return self
-
-    def unfuse_lora(self):
-        self.transformer.unfuse_lora()
-        return self
-
-    def delete_adapters(self, adapter_names):
-        self.transformer.delete_adapters(adapter_names)
-        return self
-
-    def get_active_adapters(self) -> List[str]:
-        return self.transformer.get_active_adapters()
-
-    def get_list_adapters(self) -> Dict[str, List[str]]:
-        """{component: loaded adapter names}, as diffusers returns it; the adapters target the transformer only."""
-        return {"transformer": self.transformer.get_list_adapters()}
-
-    def unload_lora_weights(self):
-        self.transformer.unload_lora_weights()
-        return self
-
-    # -- image pre / post processing (diffusers VideoProcessor, pipeline_chronoedit.py:673,801) ---------------------------
-    @staticmethod
-    def preprocess_image(image, height: int, width: int) -> torch.Tensor:
-        """VideoProcessor.preprocess(image, height=, width=): PIL / array / tensor -> [B,3,height,width] in [-1, 1] (fp32, CPU or
-        the tensor's device).  PIL images are resized with Lanczos, arrays / tensors with F.interpolate's default mode (nearest) - both as
-        diffusers' VaeImageProcessor.resize does; arrays / tensors are taken as [0, 1] unless they already carry negative values
-        (diffusers' own rule)."""
-        import numpy as np
-        if _is_pil(image) or (isinstance(image, (list, tuple)) and all(_is_pil(i) for i in image)):
-            from PIL import Image
-            imgs = list(image) if isinstance(image, (list, tuple)) else [image]
-            arr = np.stack([np.asarray(i.convert("RGB").resize((width, height), Image.LANCZOS), dtype=np.float32) / 255.0 for i in imgs])
-            x = torch.from_numpy(arr).permute(0, 3, 1, 2)
-        elif isinstance(image, np.ndarray):
-            x = torch.from_numpy(image.astype(np.float32))
-            x = x[None] if x.dim() == 3 else x
-            x = x.permute(0, 3, 1, 2)
-        elif isinstance(image, torch.Tensor):
-            x = image.float()
-            x = x[None] if x.dim() == 3 else x
-        else:
-            raise ValueError(f"`image` has to be of type `torch.Tensor` or `PIL.Image.Image` but is {type(image)}")
-        if x.shape[-2:] != (height, width):
-            x = torch.nn.functional.interpolate(x, size=(height, width))  # arrays / tensors: F.interpolate's default (nearest), as diffusers' VaeImageProcessor.resize
-        if x.min() >= 0:
-            x = 2.0 * x - 1.0
-        return x.contiguous()
-
-    @staticmethod
-    def postprocess_video(video: torch.Tensor, output_type: str = "np"):
-        """VideoProcessor.postprocess_video: [B,3,F,H,W] in [-1,1] -> per sample F frames in [0,1]: "np" [B,F,H,W,3] float32,
-        "pt" [B,F,3,H,W], "pil" list of lists of PIL images."""
-        v = (video.float() / 2 + 0.5).clamp(0, 1).permute(0, 2, 1, 3, 4)  # [B,F,3,H,W]
-        if output_type == "pt":
-            return v
-        arr = v.permute(0, 1, 3, 4, 2).cpu().numpy()
-        if output_type == "np":
-            return arr
-        if output_type == "pil":
-            from PIL import Image
-            return [[Image.fromarray((f * 255).round().astype("uint8")) for f in sample] for sample in arr]
-        raise ValueError(f"{output_type} does not exist. Please choose one of ['np', 'pt', 'pil']")
+    # -- image pre / post processing (diffusers VideoProcessor, pipeline_chronoedit.py:673,801; the bodies are image_io's) ---
+    preprocess_image = staticmethod(image_io.preprocess_image)
+    postprocess_video = staticmethod(image_io.postprocess_video)
 
     # -- the call (pipeline_chronoedit.py:484-812) -----------------------------------------------------------------------
     @torch.no_grad()
@@ -1034,167 +750,242 @@ class ChronoEditPipeline:
         """Same arguments, defaults, checks and return value as the reference's `__call__`.  What differs is underneath: the two
         guidance passes run as ONE batched forward, CFG + flow-UniPC are one fused launch, the latents stay fp32 on the device
         (`scheduler.trajectory_dtype = torch.bfloat16` restores the reference's bf16 rounding of latents and history)."""
-        fpass, self._focus_pass = self._focus_pass, None  # set: this is the focused pass of an auto-focused call (`_auto_focus_pass`) or of a sketch edit
-        if fpass is None:
-            from . import sketch as _sk
-            self.sketch_report = None
-            if _sk.is_editor_value(image):  # an image editor's value: the sketch edit (chronoedit_amd/sketch.py) - or its refusal
-                return self._sketch_call(image, dict(
-                    prompt=prompt, negative_prompt=negative_prompt, height=height, width=width, num_frames=num_frames,
-                    num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, num_videos_per_prompt=num_videos_per_prompt,
-                    generator=generator, latents=latents, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
-                    image_embeds=image_embeds, output_type=output_type, return_dict=return_dict, attention_kwargs=attention_kwargs,
-                    callback_on_step_end=callback_on_step_end, callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs,
-                    max_sequence_length=max_sequence_length, enable_temporal_reasoning=enable_temporal_reasoning,
-                    num_temporal_reasoning_steps=num_temporal_reasoning_steps, offload_model=offload_model))
-        scouted = fpass is not None and not fpass.get("explicit")  # the pass an auto-focus scout started: its guardrail ran, its previews are tagged
-        if hasattr(callback_on_step_end, "tensor_inputs"):
-            callback_on_step_end_tensor_inputs = callback_on_step_end.tensor_inputs
-        self.check_inputs(prompt, negative_prompt, image, height, width, prompt_embeds, negative_prompt_embeds, image_embeds,
-                          callback_on_step_end_tensor_inputs)
-        if num_frames % self.vae_scale_factor_temporal != 1:  # :606-611
-            num_frames = num_frames // self.vae_scale_factor_temporal * self.vae_scale_factor_temporal + 1
-        num_frames = max(num_frames, 1)
-        self._guidance_scale, self._attention_kwargs, self._current_timestep, self._interrupt = guidance_scale, attention_kwargs, None, False
+        args = CallArgs(**{k: v for k, v in locals().items() if k != "self"})  # (the first statement: the locals are the arguments)
+        self.sketch_report = None
+        if _sk.is_editor_value(image):  # an image editor's value: the sketch edit (chronoedit_amd/sketch.py) - or its refusal
+            return self._sketch_edit(args)
+        return self._edit(args)
+
+    def _sketch_edit(self, a: CallArgs):
+        """`__call__` with an editor's value (or a list of them) as `image`: see `enable_sketch_region`."""
+        from PIL import Image
+        if self._sketch_region is None:
+            raise ValueError("`image` is an image editor's value (a dict with \"background\" and \"composite\"): switch sketch edits on with "
+                             "enable_sketch_region() first, or pass the composite itself")
+        cfg = self._sketch_region
+        bgs, cps = _sk.editor_images(a.image)
+        a = replace(a, image=cps if isinstance(a.image, (list, tuple)) else cps[0])
+        if self._edit_region is not None:  # an explicit mask wins: the editor value stands for its composite
+            return self._edit(a)
+        if a.output_type in ("np", "pt") and len({im.size for im in bgs}) > 1:
+            raise ValueError(f"a sketch edit returns frames of the photos' sizes {[im.size for im in bgs]}: output_type={a.output_type!r} "
+                             'needs photos of one size, use "pil"')
         device = self._execution_device
-        if not scouted and self.text_guardrail_runner is not None and not self.text_guardrail_runner(prompt):  # :621-629
-            raise Exception(f"Guardrail blocked text2world generation. Prompt: {prompt}")
-
-        if prompt is not None and isinstance(prompt, str):
-            batch_size = 1
-        elif prompt is not None and isinstance(prompt, list):
-            batch_size = len(prompt)
+        entries = _sk.masks(cfg, bgs, cps, device if image_io.on_device(self.device_image_io, device) else None)
+        plans = [_sk.focus_plan(e, a.width, a.height, cfg.context) for e in entries]
+        if all(e["bbox"] is None for e in entries):  # no strokes anywhere: the plain call on the composite(s)
+            out = self._edit(a)
         else:
-            batch_size = prompt_embeds.shape[0]
-        prompt_embeds, negative_prompt_embeds = self.encode_prompt(
-            prompt=prompt, negative_prompt=negative_prompt, do_classifier_free_guidance=self.do_classifier_free_guidance,
-            num_videos_per_prompt=num_videos_per_prompt, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
-            max_sequence_length=max_sequence_length, device=device)
-        if offload_model and self.text_encoder is not None:
-            self.text_encoder.cpu()
-        tdtype = self.transformer.dtype
-        prompt_embeds = prompt_embeds.to(device=device, dtype=tdtype)
-        if negative_prompt_embeds is not None:
-            negative_prompt_embeds = negative_prompt_embeds.to(device=device, dtype=tdtype)
-        self.focus_report = None
-        focus = None  # per image: the plan of a focused region edit (chronoedit_amd/focus.py); the encoders then see the crops
-        if fpass is not None:
-            focus = fpass["plans"]  # (made by the scout, the mask already on the device)
-        elif self._region_focus is not None and self._edit_region is not None:
-            focus = self._focus_setup(image, height, width, device, output_type)
-        if focus is not None:
-            self.focus_report = [p["report"] for p in focus]
-        # auto focus (chronoedit_amd/autofocus.py): this call is the scout, and starts the focused pass when the detection says so
-        a_focus = None
-        if fpass is None and self._auto_focus is not None and self._edit_region is None and self._auto_region_config()[0] is not None \
-                and not self._auto_region_config()[1]:
-            a_focus = self._auto_focus
-            if image is None or image_io._pil_list(image) is None:
-                raise ValueError("auto focus needs PIL input: an array or tensor `image` has no full-resolution bytes to paste the edit back "
-                                 "into - pass a PIL image, or disable_auto_focus()")
-            if batch_size * num_videos_per_prompt != 1 or len(image_io._pil_list(image)) != 1:
-                raise NotImplementedError("auto focus edits one photo per call: a list of images or prompts, or num_videos_per_prompt > 1, is not implemented")
-            if enable_temporal_reasoning:
-                raise NotImplementedError("auto focus with temporal reasoning is not implemented (the scout would run the reasoning steps "
-                                          "twice, or the focused pass would start at the truncated shape)")
-            if offload_model:
-                raise NotImplementedError("auto focus with offload_model is not implemented (the encoders leave the device before the "
-                                          "focused pass needs them)")
-        # detail lift (chronoedit_amd/lift.py): the frames of an unfocused call go back at the images' own sizes
-        self.lift_report = None
-        lift, lift_kept = None, None
-        if self._detail_lift is not None and output_type != "latent":
-            lift_imgs = image_io._pil_list(image) if image is not None else None
-            if lift_imgs is None:
-                raise ValueError("detail lift needs PIL input (one image or a list): an array or tensor `image` has no full-resolution bytes to "
-                                 "lift the edit onto - pass PIL images, or disable_detail_lift()")
-            if focus is None:
-                lift = self._detail_lift
-                if output_type in ("np", "pt") and len({im.size for im in lift_imgs}) > 1:
-                    raise ValueError(f"detail lift returns frames of the images' sizes {[im.size for im in lift_imgs]}: output_type={output_type!r} "
-                                     'needs images of one size, use "pil"')
-        user_image_embeds = image_embeds
-        if image_embeds is None:
-            if focus is None:
-                image_embeds = self.encode_image(image, device)
-            else:  # the conditioning shows what the model edits
-                crops = [p["image"].crop(p["box"]) for p in focus]
-                image_embeds = self.encode_image(crops if isinstance(image, (list, tuple)) else crops[0], device)
-        image_embeds = image_embeds.to(device=device, dtype=tdtype)
-        if image_embeds.shape[0] != batch_size:
-            image_embeds = image_embeds.repeat(batch_size, 1, 1)
-        if offload_model and self.image_encoder is not None:
-            self.image_encoder.cpu()
+            out = self._edit(a, FocusPass(plans, cfg.composite))
+        # behind the edit: the device path copies its masks to the host here, not in front of the first step
+        self.sketch_report = [dict(p.report, mask=Image.fromarray(p.host_mask().numpy(), mode="L"), grow_px=e["grow_px"], feather_px=e["feather_px"],
+                                   threshold=cfg.threshold, changed_pixels=e["changed_pixels"]) for p, e in zip(plans, entries)]
+        return out
 
-        B = batch_size * num_videos_per_prompt
-        if hasattr(self.vae, "use_graph"):  # the VAE replays captured graphs from the second edit of a shape on (vae.py)
-            self.vae.use_graph = bool(self.use_graph)
-        focus_masks = None
-        if focus is not None:
-            img, focus_masks = self._focus_inputs(focus, height, width, device)
-        elif self.device_image_io and device.type == "cuda" and (_is_pil(image) or (isinstance(image, (list, tuple)) and image and all(_is_pil(i) for i in image))):
-            lift_kept = [] if lift is not None else None  # (the photo's bytes stay on the device: one upload)
-            img = image_io.preprocess_pil(image, height, width, device, keep=lift_kept)
-        else:
-            img = self.preprocess_image(image, height, width).to(device=device, dtype=torch.bfloat16)
-        latents, condition = self.prepare_latents(img, B, self.vae.config.z_dim, height, width, num_frames, torch.bfloat16, device,
-                                                  generator, latents)
-        noise = latents  # (what the focused pass of an auto-focused call starts from as well)
-        start_step, start_eps = 0, None
-        if fpass is not None and fpass["start"] is not None:
+    def _edit(self, a: CallArgs, fpass: Optional[FocusPass] = None):
+        """The body of every call.  fpass: this is a focused pass somebody planned (a sketch edit, or the scout of an auto-focused call);
+        None: what is edited follows from the user's switches (`_resolve`).  Nothing below `_resolve` reads them."""
+        a, device = self._begin(a, guarded=fpass is not None and fpass.guarded)
+        batch_size, prompt_embeds, negative_prompt_embeds = self._encode_text(a, device)
+        what = self._resolve(a, fpass, batch_size, device)
+        image_embeds = self._image_embeds(a, what.focus, batch_size, device)
+        B = batch_size * a.num_videos_per_prompt
+        img, focus_masks, lift_kept = self._preprocess(a, what, device)
+        noise, condition = self.prepare_latents(img, B, self.vae.config.z_dim, a.height, a.width, a.num_frames, torch.bfloat16, device,
+                                                a.generator, a.latents)
+        latents, start_step, start_eps = noise, 0, None
+        if fpass is not None and fpass.start is not None:
             # the warm start: the scout's estimate of the final image on the crop's latent grid, noised to the level of step k + 1
-            from . import autofocus as _af
-            st = fpass["start"]
-            start_step, start_eps = st["step"], latents.to(torch.float32)
-            tables = _af.restart_tables(focus[0]["box"], focus[0]["image"].size, tuple(latents.shape[-2:]), device)
+            st = fpass.start
+            start_step, start_eps = st["step"], noise.to(torch.float32)
+            tables = _af.restart_tables(what.focus[0].box, what.focus[0].image.size, tuple(noise.shape[-2:]), device)
             latents = _af.restart(st["x0"], start_eps, tables, st["sigma"], bf16_state=self.scheduler.trajectory_dtype == torch.bfloat16)
-        regions = None  # per image: (uint8 mask on the device, region.RegionConfig)
-        if focus is not None:  # the crops' masks are made already: the same VAE encode, weights per mask
-            from . import region as _rg
-            z_src = _rg.static_source_latents(self.vae, img, num_frames)
-            regions = [(m, _rg.RegionConfig(w=_rg.latent_weights(m), z_src=z_src[j:j + 1])) for j, m in enumerate(focus_masks)]
-        elif self._edit_region is not None:
-            regions = self._region_setup(self._edit_region[0], img, num_frames)  # one more VAE encode, of the condition encode's shape
         n_img = img.shape[0]
-        self.auto_region_report = None
-        autos = None  # per sample: the auto_region.AutoRegion the loop fills in
-        a_cfg, a_measure = self._auto_region_config()
-        if regions is None and a_cfg is not None:
-            from . import auto_region as _ar
-            from . import region as _rg
-            z_all = _rg.static_source_latents(self.vae, img, num_frames)  # one more VAE encode, as for an explicit region
-            src_of = lambda b: b // num_videos_per_prompt if n_img > 1 else 0
-            autos = [_ar.AutoRegion(a_cfg, z_all[src_of(b):src_of(b) + 1], measure=a_measure) for b in range(B)]
-            if a_focus is not None:
-                decision = {}
-                autos[0].on_accept = lambda m: decision.update(self._auto_focus_plan(image_io._pil_list(image)[0], m, height, width, device)) or decision["go"]
-        image_of = lambda b: b // num_videos_per_prompt if n_img > 1 else 0  # which image (and mask) sample b edits
-        if offload_model and hasattr(self.vae, "clear_graphs"):
+        image_of = lambda b: b // a.num_videos_per_prompt if n_img > 1 else 0  # which image (and mask) sample b edits
+        if what.masks is not None:
+            focus_masks = _rg.device_masks(_fc.masks_for(what.masks, n_img), a.height, a.width, device)
+        regions, autos = self._region_setup(img, a.num_frames, focus_masks, B, image_of)
+        decision = {}
+        if what.auto_focus is not None:  # this call is the scout: the detection decides whether a focused pass follows
+            autos[0].on_accept = lambda m: decision.update(self._auto_focus_plan(what.pil[0], m, a.height, a.width, what.auto_focus, device)) or decision["go"]
+        if a.offload_model and hasattr(self.vae, "clear_graphs"):
             self.vae.clear_graphs()  # a captured encode graph pins its activation pool next to the 14B DiT: the low-memory mode drops it
         if prompt_embeds.shape[0] != B or (negative_prompt_embeds is not None and negative_prompt_embeds.shape[0] != B):
             raise ValueError(f"prompt_embeds carry {prompt_embeds.shape[0]} samples, expected batch_size * num_videos_per_prompt = {B}")
         if image_embeds.shape[0] != B:
             image_embeds = image_embeds.repeat(B // image_embeds.shape[0], 1, 1)
+        latents = self._denoise_samples(a, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
+                                        None if regions is None else [regions[image_of(b)][1] for b in range(B)], autos, start_step, start_eps,
+                                        fpass.preview_tag if fpass is not None else "scout" if what.auto_focus is not None else None)
+        if autos is not None and not autos[0].measure:
+            self.auto_region_report = autos[0].report if B == 1 else [x.report for x in autos]
+        if what.auto_focus is not None:
+            if autos[0].exited:
+                return self._focused_pass(a, decision["plan"], autos[0], what.auto_focus, noise, prompt_embeds, negative_prompt_embeds)
+            # the scout ran to its end: the auto-region call, bit for bit
+            declined = autos[0].report is None or not autos[0].report["accepted"]
+            self.focus_report = [{"reason": "declined", "detect": autos[0].report} if declined else
+                                 dict(decision["report"], box_reason=decision["report"]["reason"], reason="whole", detect=autos[0].report)]
+        if a.offload_model and self.transformer is not None:
+            self.transformer.cpu()
+            torch.cuda.empty_cache()
+        self._current_timestep = None
+        video = latents if a.output_type == "latent" else self._output(a, what, latents, img, regions, autos, image_of, lift_kept, device)
+        if a.offload_model and hasattr(self.vae, "clear_graphs"):
+            self.vae.clear_graphs()
+            torch.cuda.empty_cache()
+        self.maybe_free_model_hooks()
+        if not a.return_dict:
+            return (video,)
+        return WanPipelineOutput(frames=video)
 
+    def _begin(self, a: CallArgs, guarded: bool):
+        """The checks and resets every pass starts with -> (the arguments as the reference adjusts them, the device).  guarded: the text
+        guardrail has seen this call's prompt already."""
+        if hasattr(a.callback_on_step_end, "tensor_inputs"):
+            a = replace(a, callback_on_step_end_tensor_inputs=a.callback_on_step_end.tensor_inputs)
+        self.check_inputs(a.prompt, a.negative_prompt, a.image, a.height, a.width, a.prompt_embeds, a.negative_prompt_embeds, a.image_embeds,
+                          a.callback_on_step_end_tensor_inputs)
+        num_frames = a.num_frames
+        if num_frames % self.vae_scale_factor_temporal != 1:  # :606-611
+            num_frames = num_frames // self.vae_scale_factor_temporal * self.vae_scale_factor_temporal + 1
+        a = replace(a, num_frames=max(num_frames, 1))
+        self._guidance_scale, self._attention_kwargs, self._current_timestep, self._interrupt = a.guidance_scale, a.attention_kwargs, None, False
+        device = self._execution_device
+        if not guarded and self.text_guardrail_runner is not None and not self.text_guardrail_runner(a.prompt):  # :621-629
+            raise Exception(f"Guardrail blocked text2world generation. Prompt: {a.prompt}")
+        return a, device
+
+    def _encode_text(self, a: CallArgs, device):
+        """-> (batch_size, prompt_embeds, negative_prompt_embeds) on the device in the transformer's dtype (:631-660)."""
+        if a.prompt is not None and isinstance(a.prompt, str):
+            batch_size = 1
+        elif a.prompt is not None and isinstance(a.prompt, list):
+            batch_size = len(a.prompt)
+        else:
+            batch_size = a.prompt_embeds.shape[0]
+        prompt_embeds, negative_prompt_embeds = self.encode_prompt(
+            prompt=a.prompt, negative_prompt=a.negative_prompt, do_classifier_free_guidance=self.do_classifier_free_guidance,
+            num_videos_per_prompt=a.num_videos_per_prompt, prompt_embeds=a.prompt_embeds, negative_prompt_embeds=a.negative_prompt_embeds,
+            max_sequence_length=a.max_sequence_length, device=device)
+        if a.offload_model and self.text_encoder is not None:
+            self.text_encoder.cpu()
+        tdtype = self.transformer.dtype
+        prompt_embeds = prompt_embeds.to(device=device, dtype=tdtype)
+        if negative_prompt_embeds is not None:
+            negative_prompt_embeds = negative_prompt_embeds.to(device=device, dtype=tdtype)
+        return batch_size, prompt_embeds, negative_prompt_embeds
+
+    def _resolve(self, a: CallArgs, fpass: Optional[FocusPass], batch_size: int, device) -> EditSources:
+        """What this pass edits and how its frames go back - from the focus pass, else from the user's switches - and what must be refused."""
+        pil = image_io._pil_list(a.image) if a.image is not None else None
+        what = EditSources(pil=pil)
+        self.focus_report = None
+        if fpass is not None:  # (planned by the caller, the masks where they lie)
+            what.focus, what.composite = fpass.plans, fpass.composite
+        elif self._edit_region is not None:
+            masks, what.composite = self._edit_region
+            if self._region_focus is not None:
+                what.focus = _fc.setup(a.image, masks, a.height, a.width, self._region_focus, a.output_type,
+                                       device if image_io.on_device(self.device_image_io, device) else None)
+            else:
+                what.masks = masks
+        if what.focus is not None:
+            self.focus_report = [p.report for p in what.focus]
+        # auto focus (chronoedit_amd/autofocus.py): this call is the scout, and starts the focused pass when the detection says so
+        a_cfg, a_measure = self._auto_region_config()
+        if fpass is None and self._auto_focus is not None and self._edit_region is None and a_cfg is not None and not a_measure:
+            what.auto_focus = self._auto_focus
+            if pil is None:
+                raise ValueError("auto focus needs PIL input: an array or tensor `image` has no full-resolution bytes to paste the edit back "
+                                 "into - pass a PIL image, or disable_auto_focus()")
+            if batch_size * a.num_videos_per_prompt != 1 or len(pil) != 1:
+                raise NotImplementedError("auto focus edits one photo per call: a list of images or prompts, or num_videos_per_prompt > 1, is not implemented")
+            if a.enable_temporal_reasoning:
+                raise NotImplementedError("auto focus with temporal reasoning is not implemented (the scout would run the reasoning steps "
+                                          "twice, or the focused pass would start at the truncated shape)")
+            if a.offload_model:
+                raise NotImplementedError("auto focus with offload_model is not implemented (the encoders leave the device before the "
+                                          "focused pass needs them)")
+        # detail lift (chronoedit_amd/lift.py): the frames of an unfocused call go back at the images' own sizes
+        self.lift_report = None
+        if self._detail_lift is not None and a.output_type != "latent":
+            if pil is None:
+                raise ValueError("detail lift needs PIL input (one image or a list): an array or tensor `image` has no full-resolution bytes to "
+                                 "lift the edit onto - pass PIL images, or disable_detail_lift()")
+            what.lift = self._detail_lift
+            if what.focus is None and a.output_type in ("np", "pt") and len({im.size for im in pil}) > 1:
+                raise ValueError(f"detail lift returns frames of the images' sizes {[im.size for im in pil]}: output_type={a.output_type!r} "
+                                 'needs images of one size, use "pil"')
+        return what
+
+    def _image_embeds(self, a: CallArgs, focus, batch_size: int, device) -> torch.Tensor:
+        """The user's `image_embeds`, or CLIP on what the model edits: the image, or the crops of a focused pass."""
+        image_embeds = a.image_embeds
+        if image_embeds is None:
+            if focus is None:
+                image_embeds = self.encode_image(a.image, device)
+            else:  # the conditioning shows what the model edits
+                crops = [p.image.crop(p.box) for p in focus]
+                image_embeds = self.encode_image(crops if isinstance(a.image, (list, tuple)) else crops[0], device)
+        image_embeds = image_embeds.to(device=device, dtype=self.transformer.dtype)
+        if image_embeds.shape[0] != batch_size:
+            image_embeds = image_embeds.repeat(batch_size, 1, 1)
+        if a.offload_model and self.image_encoder is not None:
+            self.image_encoder.cpu()
+        return image_embeds
+
+    def _preprocess(self, a: CallArgs, what: EditSources, device):
+        """-> (img bf16 [n, 3, height, width] on the device, the crops' edit-size masks of a focused pass or None, what the lift keeps on
+        the device or None)."""
+        if hasattr(self.vae, "use_graph"):  # the VAE replays captured graphs from the second edit of a shape on (vae.py)
+            self.vae.use_graph = bool(self.use_graph)
+        if what.focus is not None:
+            return _fc.inputs(what.focus, a.height, a.width, device) + (None,)
+        if image_io.on_device(self.device_image_io, device) and what.pil is not None:
+            lift_kept = [] if what.lift is not None else None  # (the photo's bytes stay on the device: one upload)
+            return image_io.preprocess_pil(a.image, a.height, a.width, device, keep=lift_kept), None, lift_kept
+        return self.preprocess_image(a.image, a.height, a.width).to(device=device, dtype=torch.bfloat16), None, None
+
+    def _region_setup(self, img: torch.Tensor, num_frames: int, masks=None, n_samples: int = 1, image_of=lambda b: 0):
+        """masks: per image of img its edit-size uint8 mask on the device, or None -> (per image (mask, region.RegionConfig), None), or
+        without masks (None, per sample the auto_region.AutoRegion the loop fills in) when a detector is configured, else (None, None).
+        Either costs one more VAE encode, of the condition encode's shape."""
+        self.auto_region_report = None
+        a_cfg, a_measure = self._auto_region_config()
+        if masks is None and a_cfg is None:
+            return None, None
+        z_src = _rg.static_source_latents(self.vae, img, num_frames)
+        if masks is None:
+            return None, [_ar.AutoRegion(a_cfg, z_src[image_of(b):image_of(b) + 1], measure=a_measure) for b in range(n_samples)]
+        weights = {}
+        for m in masks:  # (one mask for all images: reduced once)
+            if id(m) not in weights:
+                weights[id(m)] = _rg.latent_weights(m)
+        return [(m, _rg.RegionConfig(w=weights[id(m)], z_src=z_src[j:j + 1])) for j, m in enumerate(masks)], None
+
+    def _denoise_samples(self, a: CallArgs, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds, regions, autos,
+                         start_step: int, start_eps, preview_tag) -> torch.Tensor:
+        """The loop, sample by sample (regions, autos: per sample, or None) -> the final latents of all of them."""
         # The engine denoises ONE edit at a time (its batch axis carries the guidance pair); B = batch_size * num_videos_per_prompt
         # edits (pipeline_chronoedit.py:493,631-637,676-691) run one after the other on the same weights - the reference's batched
         # loop computes the same per-sample arithmetic.  `callback_on_step_end` is then called per sample and step with that
         # sample's tensors; returned `latents`, `prompt_embeds`, `negative_prompt_embeds` are honoured (:741-749).
-        self._num_timesteps = num_inference_steps
+        self._num_timesteps = a.num_inference_steps
         done = []
         # attention_kwargs={"scale": s} (diffusers' per-call LoRA scale): the active adapters times s for this call's denoising only
         lora_scale = getattr(self.transformer, "lora_scale", None)
-        scaled = lora_scale((attention_kwargs or {}).get("scale")) if lora_scale is not None else contextlib.nullcontext()
+        scaled = lora_scale((a.attention_kwargs or {}).get("scale")) if lora_scale is not None else contextlib.nullcontext()
         with scaled:
-            for b in range(B):
+            for b in range(prompt_embeds.shape[0]):
                 embeds = {"prompt_embeds": prompt_embeds[b:b + 1], "negative_prompt_embeds": None if negative_prompt_embeds is None else negative_prompt_embeds[b:b + 1]}
 
                 def on_step_end(i, t, lat, embeds=embeds):
                     self._current_timestep = t
-                    if callback_on_step_end is None:
+                    if a.callback_on_step_end is None:
                         return None
                     pool = {"latents": lat, **embeds}
-                    outs = callback_on_step_end(self, i, t, {k: pool[k] for k in callback_on_step_end_tensor_inputs})
+                    outs = a.callback_on_step_end(self, i, t, {k: pool[k] for k in a.callback_on_step_end_tensor_inputs})
                     if not outs:
                         return None
                     new = {k: outs[k] for k in ("latents", "prompt_embeds", "negative_prompt_embeds") if k in outs and outs[k] is not pool[k]}
@@ -1203,95 +994,70 @@ class ChronoEditPipeline:
 
                 done.append(denoise(self.transformer, self.scheduler, latents[b:b + 1], condition[b:b + 1], embeds["prompt_embeds"],
                                     embeds["negative_prompt_embeds"] if self.do_classifier_free_guidance else None, image_embeds[b:b + 1],
-                                    num_inference_steps, guidance_scale, enable_temporal_reasoning, num_temporal_reasoning_steps,
+                                    a.num_inference_steps, a.guidance_scale, a.enable_temporal_reasoning, a.num_temporal_reasoning_steps,
                                     use_graph=self.use_graph, on_step_end=on_step_end, interrupted=lambda: self._interrupt,
-                                    graph_warm=self._graph_warm, region=None if regions is None else regions[image_of(b)][1],
+                                    graph_warm=self._graph_warm, region=None if regions is None else regions[b],
                                     auto_region=None if autos is None else autos[b], start_step=start_step,
                                     start_eps=None if start_eps is None else start_eps[b:b + 1],
-                                    preview=self._preview_config(b, "focus" if scouted else "scout" if a_focus is not None else None),
-                                    **self._measure_kwargs()))
-        if autos is not None and not autos[0].measure:
-            self.auto_region_report = autos[0].report if B == 1 else [a.report for a in autos]
-        if a_focus is not None:
-            if autos[0].exited:
-                k = autos[0].report["step"]
-                start = None
-                if a_focus.warm_start and k + 1 < num_inference_steps:  # (a detection behind the last step leaves no tail: cold)
-                    start = {"step": k + 1, "x0": self.scheduler.model_outputs[-1], "sigma": float(self.scheduler.sigmas[k + 1])}
-                return self._auto_focus_pass(
-                    decision["plan"], start, autos[0], a_focus, image=image, negative_prompt=None, height=height, width=width, num_frames=num_frames,
-                    num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, num_videos_per_prompt=1, generator=generator,
-                    latents=noise, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, image_embeds=user_image_embeds,
-                    output_type=output_type, return_dict=return_dict, attention_kwargs=attention_kwargs, callback_on_step_end=callback_on_step_end,
-                    callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, max_sequence_length=max_sequence_length)
-            # the scout ran to its end: the auto-region call, bit for bit
-            declined = autos[0].report is None or not autos[0].report["accepted"]
-            self.focus_report = [{"reason": "declined", "detect": autos[0].report} if declined else
-                                 dict(decision["plan"]["report"], box_reason=decision["plan"]["report"]["reason"], reason="whole", detect=autos[0].report)]
-        latents = done[0] if B == 1 else torch.cat(done, dim=0)
-        if offload_model and self.transformer is not None:
-            self.transformer.cpu()
-            torch.cuda.empty_cache()
-        self._current_timestep = None
+                                    preview=self._preview_config(b, preview_tag), **self._measure_kwargs()))
+        return done[0] if len(done) == 1 else torch.cat(done, dim=0)
 
-        if output_type != "latent":
-            video = decode_latents(self.vae, latents, enable_temporal_reasoning, num_temporal_reasoning_steps)
-            if self.video_guardrail_runner is not None:  # :784-799
-                video = self.video_guardrail_runner(video)
-                if video is None:
-                    raise Exception("Guardrail blocked video2world generation.")
-            if focus is None and regions is not None and self._edit_region[1]:
-                # the paste-back: every returned frame (reasoning frames included) keeps the source where the mask says so - a new fp32 video
-                from . import region as _rg
-                video = video.to(device)
-                video = torch.cat([_rg.composite(video[b:b + 1], img[image_of(b):image_of(b) + 1], regions[image_of(b)][0])
-                                   for b in range(video.shape[0])], dim=0)
-            elif autos is not None and autos[0].config.composite and any(a.mask_u8 is not None for a in autos):
-                # the same paste-back with the detected masks; a sample whose detection was declined keeps its decoded frames
-                from . import region as _rg
-                video = video.to(device)
-                video = torch.cat([video[b:b + 1].float() if autos[b].mask_u8 is None else
-                                   _rg.composite(video[b:b + 1], img[image_of(b):image_of(b) + 1], autos[b].mask_u8)
-                                   for b in range(video.shape[0])], dim=0)
-            lifted = None if lift is None else self._lift_output(video, lift, lift_kept, lift_imgs, image_of, height, width, output_type)
-            if focus is not None:  # the source-size paste replaces the edit-size composite
-                video = self._focus_output(video, focus, image_of, output_type)
-                if self._detail_lift is not None:
-                    self.lift_report = [{"size": focus[image_of(b)]["image"].size, "edit_size": (int(width), int(height)), "applied": False,
-                                         "reason": "focus", "fallback_fraction": None} for b in range(B)]
-            elif lifted is not None:
-                video = lifted
-            elif self.device_image_io and output_type == "pil" and video.is_cuda and video.dtype in (torch.bfloat16, torch.float32):
-                video = image_io.frames_to_pil(video)
-            else:
-                video = self.postprocess_video(video, output_type=output_type)
-        else:
-            video = latents
-        if offload_model and hasattr(self.vae, "clear_graphs"):
-            self.vae.clear_graphs()
-            torch.cuda.empty_cache()
-        self.maybe_free_model_hooks()
-        if not return_dict:
-            return (video,)
-        return WanPipelineOutput(frames=video)
+    def _composited(self, video: torch.Tensor, img: torch.Tensor, masks, image_of=lambda b: 0) -> List[torch.Tensor]:
+        """The edit-size paste-back behind the decode: per sample its frames (reasoning frames included) with the source kept where that
+        sample's mask says so - a new fp32 video; a sample without a mask (a declined detection) keeps its decoded frames."""
+        return [video[b:b + 1].float() if m is None else _rg.composite(video[b:b + 1], img[image_of(b):image_of(b) + 1], m)
+                for b, m in enumerate(masks)]
 
-    def _auto_focus_pass(self, plan: dict, start: Optional[dict], auto, cfg, **call):
-        """The focused pass of an auto-focused call: the explicit-mask focused region edit of the crop (`__call__` itself, with the scout's plan
-        in place of `_focus_setup`'s), then the report's new entries."""
+    def _output(self, a: CallArgs, what: EditSources, latents, img, regions, autos, image_of, lift_kept, device):
+        """Decode, the video guardrail, the edit-size composite, then the focus paste, the lift or the plain frames."""
+        video = decode_latents(self.vae, latents, a.enable_temporal_reasoning, a.num_temporal_reasoning_steps)
+        if self.video_guardrail_runner is not None:  # :784-799
+            video = self.video_guardrail_runner(video)
+            if video is None:
+                raise Exception("Guardrail blocked video2world generation.")
+        B = video.shape[0]
+        masks = None
+        if what.focus is None and regions is not None and what.composite:
+            masks = [regions[image_of(b)][0] for b in range(B)]
+        elif autos is not None and autos[0].config.composite and any(x.mask_u8 is not None for x in autos):
+            masks = [x.mask_u8 for x in autos]  # the detected ones
+        if masks is not None:
+            video = torch.cat(self._composited(video.to(device), img, masks, image_of), dim=0)
+        if what.lift is not None and what.focus is None:
+            lifted, self.lift_report = _lf.output(video, what.lift, lift_kept, what.pil, image_of, a.height, a.width, a.output_type)
+            if lifted is not None:
+                return lifted
+        if what.focus is not None:  # the source-size paste replaces the edit-size composite
+            video = _fc.paste(video, what.focus, image_of, a.output_type, what.composite)
+            if what.lift is not None:
+                self.lift_report = [_lf.report_entry(what.focus[image_of(b)].image.size, (a.width, a.height), "focus") for b in range(B)]
+            return video
+        if self.device_image_io and a.output_type == "pil" and image_io.device_video(video):
+            return image_io.frames_to_pil(video)
+        return self.postprocess_video(video, output_type=a.output_type)
+
+    def _auto_focus_plan(self, image, mask_edit: torch.Tensor, height: int, width: int, cfg, device) -> dict:
+        """The scout's decision: the detected edit-size mask (on the device) -> {"go", "report", "plan"}: the lifted mask, the box (two
+        reductions, five integers read each) and, when the box is worth cropping to, the focus.FocusPlan."""
+        on_device = image_io.on_device(self.device_image_io, device)
+        mask_src = _af.lift_mask(mask_edit if on_device else mask_edit.cpu(), image.size)
+        report = _af.plan(mask_src, (width, height), cfg.context)
+        go = _af.worth_focusing(report)
+        return {"go": go, "report": report, "plan": _fc.FocusPlan.make(image, report, mask_src, device if on_device else None) if go else None}
+
+    def _focused_pass(self, a: CallArgs, plan, auto, cfg, noise, prompt_embeds, negative_prompt_embeds):
+        """The focused pass of an auto-focused call: the explicit-mask focused region edit of the crop around the detected region, from the
+        scout's noise and its encoded prompts (CLIP sees the crop unless the user gave `image_embeds`), then the report's new entries."""
         from PIL import Image
-        saved = (self._edit_region, self._region_focus)
-        mask = plan["mask_dev"] if "mask_dev" in plan else plan["mask_u8"]
-        self._edit_region, self._region_focus = (mask, bool(auto.config.composite)), cfg.context
-        self._focus_pass = {"plans": [plan], "start": start}
-        try:
-            out = self(**call)
-        finally:
-            self._focus_pass = None
-            self._edit_region, self._region_focus = saved
-        if plan["mask_u8"] is None:
-            plan["mask_u8"] = plan["mask_dev"].cpu()
+        k = auto.report["step"]
+        start = None
+        if cfg.warm_start and k + 1 < a.num_inference_steps:  # (a detection behind the last step leaves no tail: cold)
+            start = {"step": k + 1, "x0": self.scheduler.model_outputs[-1], "sigma": float(self.scheduler.sigmas[k + 1])}
+        a = replace(a, prompt=None, negative_prompt=None, num_videos_per_prompt=1, latents=noise, prompt_embeds=prompt_embeds,
+                    negative_prompt_embeds=negative_prompt_embeds, num_temporal_reasoning_steps=0)
+        out = self._edit(a, FocusPass([plan], bool(auto.config.composite), start=start, preview_tag="focus", guarded=True))
         self.auto_region_report = auto.report
-        self.focus_report = [dict(plan["report"], mask=Image.fromarray(plan["mask_u8"].numpy(), mode="L"), detect=auto.report,
+        self.focus_report = [dict(plan.report, mask=Image.fromarray(plan.host_mask().numpy(), mode="L"), detect=auto.report,
                                   start_step=0 if start is None else start["step"])]
         return out
 
@@ -1311,18 +1077,9 @@ class ChronoEditPipeline:
         if num_frames % 4 != 1:
             num_frames = max(num_frames // 4 * 4 + 1, 1)  # :606-611
         latents, condition = prepare_latents(self.vae, image, num_frames, latents, generator)
-        region = mask_u8 = None
-        if region_mask is not None:
-            from . import region as _rg
-            mask_u8 = _rg.normalize_mask(region_mask, H, W).to(image.device)
-            region = _rg.RegionConfig(w=_rg.latent_weights(mask_u8), z_src=_rg.static_source_latents(self.vae, image, num_frames))
-        auto = None
-        self.auto_region_report = None
-        a_cfg, a_measure = self._auto_region_config()
-        if region is None and a_cfg is not None:
-            from . import auto_region as _ar
-            from . import region as _rg
-            auto = _ar.AutoRegion(a_cfg, _rg.static_source_latents(self.vae, image, num_frames), measure=a_measure)
+        masks = None if region_mask is None else _rg.device_masks([region_mask], H, W, image.device)
+        regions, autos = self._region_setup(image, num_frames, masks)
+        region, auto = None if regions is None else regions[0][1], None if autos is None else autos[0]
         latents = denoise(self.transformer, self.scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
                           num_inference_steps, guidance_scale, enable_temporal_reasoning, num_temporal_reasoning_steps,
                           use_graph=self.use_graph, graph_warm=self._graph_warm, region=region, auto_region=auto,
@@ -1332,8 +1089,12 @@ class ChronoEditPipeline:
         if output_type == "latent":
             return latents
         video = decode_latents(self.vae, latents, enable_temporal_reasoning, num_temporal_reasoning_steps)
-        if region is not None and composite:
-            video = _rg.composite(video, image.to(torch.bfloat16), mask_u8)
-        elif auto is not None and auto.mask_u8 is not None and auto.config.composite and composite:
-            video = _rg.composite(video, image.to(torch.bfloat16), auto.mask_u8)
+        mask = masks[0] if masks is not None else auto.mask_u8 if auto is not None and auto.config.composite else None
+        if mask is not None and composite:
+            video = self._composited(video, image.to(torch.bfloat16), [mask])[0]
         return video
+
+
+# The arguments of `__call__` - the reference's (pipeline_chronoedit.py:484-512) -, captured once per call; a pass that differs from the user's
+# call (`dataclasses.replace`) says in what
+CallArgs = make_dataclass("CallArgs", list(inspect.signature(ChronoEditPipeline.__call__).parameters)[1:])

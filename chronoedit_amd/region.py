@@ -64,6 +64,16 @@ def normalize_mask(mask, height: int, width: int) -> torch.Tensor:
     raise TypeError(f"mask: expected bool, uint8 or a floating-point dtype, got {t.dtype}")
 
 
+def device_masks(masks: list, height: int, width: int, device) -> list:
+    """Per image its mask (whatever `normalize_mask` takes) -> uint8 [height, width] on the device; a mask that several images share is
+    normalised and uploaded once (and is ONE tensor afterwards too)."""
+    seen = {}
+    for m in masks:
+        if id(m) not in seen:
+            seen[id(m)] = normalize_mask(m, height, width).to(device)
+    return [seen[id(m)] for m in masks]
+
+
 def latent_weights(mask_u8: torch.Tensor) -> torch.Tensor:
     """uint8 [H, W] -> fp32 [H/8, W/8], the 8x8 box mean: ce_region_weights_u8 for a tensor on the device, the torch expression for one on
     the CPU (the same bits: the sum is an integer, the division one fp32 operation)."""
@@ -78,16 +88,23 @@ def latent_weights(mask_u8: torch.Tensor) -> torch.Tensor:
     return mask_u8.contiguous().view(H // 8, 8, W // 8, 8).sum((1, 3)).to(torch.float32) / 16320.0
 
 
+def latent_stats(vae, device, dtype=torch.bfloat16):
+    """(latents_mean, 1 / latents_std) of the VAE's config as [1, z, 1, 1, 1] tensors: what normalises a posterior mode,
+    (z - mean) * inv_std, and takes latents back in front of the decode, z / inv_std + mean."""
+    z = vae.config.z_dim
+    mean = torch.tensor(vae.config.latents_mean, device=device, dtype=dtype).view(1, z, 1, 1, 1)
+    inv_std = (1.0 / torch.tensor(vae.config.latents_std)).to(device=device, dtype=dtype).view(1, z, 1, 1, 1)
+    return mean, inv_std
+
+
 @torch.no_grad()
 def static_source_latents(vae, image: torch.Tensor, num_frames: int) -> torch.Tensor:
     """image [B, 3, H, W] in [-1, 1] -> fp32 [B, z, T, h, w]: the VAE posterior mode of the video that shows the image in EVERY frame,
     normalised with the latent mean / inverse std in the bf16 expressions `pipeline.prepare_latents` uses for the condition.  (The
     condition's video is [image, 0, 0, ...]: its later latent frames encode the black frames, not the source.)  One VAE encode of the
     condition encode's shape."""
-    dev, z = image.device, vae.config.z_dim
     video = image.unsqueeze(2).repeat(1, 1, num_frames, 1, 1).to(torch.bfloat16)
-    mean = torch.tensor(vae.config.latents_mean, device=dev, dtype=torch.bfloat16).view(1, z, 1, 1, 1)
-    inv_std = (1.0 / torch.tensor(vae.config.latents_std)).to(device=dev, dtype=torch.bfloat16).view(1, z, 1, 1, 1)
+    mean, inv_std = latent_stats(vae, image.device)
     lat = vae.encode(video).latent_dist.mode()
     lat = (lat - mean) * inv_std
     return lat.float().contiguous()

@@ -204,3 +204,54 @@ def reference(background, composite, grow: int, feather: int, threshold: int = 0
 def mask(background: torch.Tensor, composite: torch.Tensor, grow: int, feather: int, threshold: int = 0) -> torch.Tensor:
     """`reference` where the bytes lie: uint8 [SH, SW, 3] twice, on the GPU (five launches at most, no host read) or on the host."""
     return stages(background, composite, grow, feather, threshold)[2]
+
+
+# ---- the masks of one call ---------------------------------------------------------------------------------------------------------
+def masks(cfg: SketchConfig, bgs, cps, device=None) -> list:
+    """Per editor value {"background", "composite", "mask_u8" (host; None on the device path: `host_mask` copies it when the edit is done),
+    "grow_px", "feather_px", "bbox" (None: no strokes), "mask_pixels", "changed_pixels"} and, on the device path (device set), "bg_u8",
+    "cp_u8", "mask_dev": each image uploaded once, two reductions and ONE read of their ten integers per value - nothing else comes back."""
+    from . import autofocus as _af
+    from . import image_io
+    out = []
+    for bg, cp in zip(bgs, cps):
+        g, f = cfg.pixels(bg.size)
+        e = {"background": bg, "composite": cp, "grow_px": g, "feather_px": f}
+        if device is not None:
+            e["bg_u8"], e["cp_u8"] = image_io.upload_rgb(bg, device), image_io.upload_rgb(cp, device)
+            ch, _, m = stages(e["bg_u8"], e["cp_u8"], g, f, cfg.threshold)
+            counts = torch.cat([_af.bbox_counts(m), _af.bbox_counts(ch)]).tolist()
+            e["mask_dev"], e["mask_u8"] = m, None
+        else:
+            ch, _, m = stages(bg, cp, g, f, cfg.threshold)
+            counts = _af.bbox_counts(m).tolist() + _af.bbox_counts(ch).tolist()
+            e["mask_u8"] = m
+        e["bbox"] = tuple(int(v) for v in counts[:4]) if counts[4] else None
+        e["mask_pixels"], e["changed_pixels"] = int(counts[4]), int(counts[9])
+        out.append(e)
+    return out
+
+
+def host_mask(e: dict) -> torch.Tensor:
+    """The mask of one `masks` entry on the host: the device path's 12 MB copy, made once and behind the edit (an empty mask needs no
+    copy)."""
+    if e["mask_u8"] is None:
+        e["mask_u8"] = e["mask_dev"].cpu() if e["bbox"] is not None else torch.zeros(tuple(e["mask_dev"].shape), dtype=torch.uint8)
+    return e["mask_u8"]
+
+
+def focus_plan(e: dict, width: int, height: int, context: float):
+    """The focus.FocusPlan of one `masks` entry: the crop is the COMPOSITE's, the frames are pasted into the BACKGROUND."""
+    from .focus import FocusPlan
+    SW, SH = e["background"].size
+    box, reason = focus_box(e["bbox"], (SW, SH), (width, height), context)
+    l, t, r, b = box
+    # (the box holds the mask's bounding box, so the mask's share of the box is its count over the box's area)
+    report = {"box": box, "reason": reason, "source_size": (SW, SH), "edit_size": (int(width), int(height)), "scale": (r - l) / int(width),
+              "mask_fraction_of_box": float(e["mask_pixels"]) / ((r - l) * (b - t))}
+    if "mask_dev" not in e:
+        return FocusPlan.make(e["composite"], report, e["mask_u8"], paste_image=e["background"])
+    p = FocusPlan.make(e["composite"], report, e["mask_dev"], e["mask_dev"].device, e["background"], uploaded=(e["cp_u8"], e["bg_u8"]))
+    if e["bbox"] is None:
+        p.mask_u8 = host_mask(e)  # (no copy)
+    return p

@@ -207,7 +207,7 @@ def test_the_c_abi_declares_the_two_entry_points():
 def test_the_pipeline_switches():
     from chronoedit_amd.pipeline import ChronoEditPipeline
     pipe = ChronoEditPipeline()
-    assert pipe._auto_focus is None and pipe._focus_pass is None
+    assert pipe._auto_focus is None and not hasattr(pipe, "_focus_pass")  # a focused pass is handed over explicitly, not through a slot
     assert pipe.enable_auto_focus() is pipe and pipe._auto_focus == autofocus.AutoFocusConfig(0.25, False)
     assert pipe.enable_auto_focus(context=1, warm_start=True) is pipe and pipe._auto_focus == autofocus.AutoFocusConfig(1.0, True)
     assert pipe._region_focus is None  # `enable_region_focus` keeps its own switch

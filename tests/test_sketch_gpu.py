@@ -324,7 +324,7 @@ def test_one_read_of_ten_integers_per_image_before_the_edit(pipe, monkeypatch):
     pipe.enable_sketch_region(grow=GROW, feather=FEATHER)
     try:
         del reads.log[:]
-        entries = pipe._sketch_masks([v["background"] for v in values], [v["composite"] for v in values], torch.device(DEV))
+        entries = sketch.masks(pipe._sketch_region, [v["background"] for v in values], [v["composite"] for v in values], torch.device(DEV))
         assert reads.log == [10, 10] and all(e["mask_u8"] is None and e["mask_dev"].is_cuda for e in entries)
         del reads.log[:]
         call(pipe, values, kw, callback_on_step_end=first_step("sketch"))

@@ -4,7 +4,7 @@ edit at 1280x720, radius 4, 2 and 29 frames, the 14B architecture with seeded ra
     passes     ce_lift_fit_q16, ce_lift_smooth_f32, ce_lift_gate_f32 and ce_lift_apply_u8 (g = 0 / mixed / 1 everywhere, and without a fallback
                plane): device time per launch; the apply's rate over P + U + out next to ce_focus_paste_u8's on the same photo (a whole-photo
                box, no mask: the same bytes written, the same bytes read)
-    out        the whole output stage behind the decode (`_lift_output`: uint8, the Lanczos upsample of every frame, the four passes, one copy
+    out        the whole output stage behind the decode (`lift.output`: uint8, the Lanczos upsample of every frame, the four passes, one copy
                to the host, PIL frames) for 2 and 29 frames, with and without the gate, next to the focused call's paste-back
     __call__   a whole 8-step edit, PIL in, PIL out: plain (edit-size frames), lifted, lifted with gate=None, and the focused call
 
@@ -25,7 +25,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from region_focus_bench import H, W, SH, SW, G, alternate, commit, device_ms, fmt, photo_and_mask, wall  # noqa: E402
 
-from chronoedit_amd import image_io, lift, ops  # noqa: E402
+from chronoedit_amd import focus, image_io, lift, ops  # noqa: E402
 from chronoedit_amd.pipeline import ChronoEditPipeline  # noqa: E402
 
 
@@ -105,26 +105,23 @@ def main():
               + ", ".join(f"**{ratio[F]:.2f}** at {F} frames" for F in ratio) + "."]
 
     # ---- the output stage behind the decode ------------------------------------------------------------------------------------------
-    pipe = ChronoEditPipeline()
     kept = [(P, L)]
-    pipe.enable_region_focus(0.25).set_edit_region(mask)
-    plans = pipe._focus_setup(im, H, W, dev, "pil")
+    plans = focus.setup(im, mask, H, W, 0.25, "pil", dev)
     lines += ["", "## The output stage behind the decode", "",
               "`ce_video_to_u8` -> (with a gate) per frame the Lanczos upsample to the photo's size -> the four passes -> one device-to-host copy ->",
               "`Image.fromarray` per frame, ending with PIL frames of the photo's size; next to it the focused call's paste-back of the same frames",
-              "(`_focus_output`: Lanczos to the box, paste).  The host form (`lift.reference`) is not measured at this size.", "",
+              "(`focus.paste`: Lanczos to the box, paste).  The host form (`lift.reference`) is not measured at this size.", "",
               "| frames | lifted, ms | per frame | lifted, gate=None, ms | per frame | focused paste-back, ms | per frame |", "|---|---|---|---|---|---|---|"]
     for F in (2, 29):
         video = (torch.rand((1, 3, F, H, W), generator=g, device=dev) * 2.2 - 1.1).to(torch.bfloat16)
-        post = lambda c: pipe._lift_output(video, c, kept, [im], lambda b_: 0, H, W, "pil")
+        post = lambda c: lift.output(video, c, kept, [im], lambda b_: 0, H, W, "pil")[0]
         forms = {"lift": lambda: post(cfg), "nogate": lambda: post(lift.LiftConfig(radius=a.radius, gate=None)),
-                 "focus": lambda: pipe._focus_output(video, plans, lambda b_: 0, "pil")}
+                 "focus": lambda: focus.paste(video, plans, lambda b_: 0, "pil", True)}
         ts = alternate(forms, max(3, a.reps // 2), wall)
         m = {k: statistics.median(v) for k, v in ts.items()}
         print(f"output stage {F} frames: lifted {fmt(ts['lift'])} ms, gate=None {fmt(ts['nogate'])} ms, focused paste-back {fmt(ts['focus'])} ms", flush=True)
         lines.append(f"| {F} | {fmt(ts['lift'])} | {m['lift'] / F:.1f} | {fmt(ts['nogate'])} | {m['nogate'] / F:.1f} | {fmt(ts['focus'])} | {m['focus'] / F:.1f} |")
         del video
-    pipe.disable_region_focus().clear_edit_region()
     del plans
 
     # ---- the whole edit ----------------------------------------------------------------------------------------------------------

@@ -140,13 +140,9 @@ def main():
     del passes, edit, out
 
     # ---- the pre-processing and the paste-back: device passes against PIL on the host ---------------------------------------------
-    pipe = ChronoEditPipeline()
-    pipe.enable_region_focus(a.context).set_edit_region(mask)
-
     def pre(flag):
-        pipe.enable_device_image_io(flag)
-        plans = pipe._focus_setup(im, H, W, dev, "pil")
-        return plans, pipe._focus_inputs(plans, H, W, dev)
+        plans = focus.setup(im, mask, H, W, a.context, "pil", dev if flag else None)
+        return plans, focus.inputs(plans, H, W, dev)
 
     (plans_d, (img_d, m_d)), (plans_h, (img_h, m_h)) = pre(True), pre(False)
     same_in = bool(torch.equal(img_d, img_h)) and bool(torch.equal(m_d[0], m_h[0]))
@@ -162,7 +158,7 @@ def main():
               "| frames | device passes, ms | per frame | host (PIL), ms | per frame | same bytes |", "|---|---|---|---|---|---|"]
     for F in (2, 29):
         video = (torch.rand((1, 3, F, H, W), generator=g, device=dev) * 2.2 - 1.1).to(torch.bfloat16)
-        post = lambda plans: pipe._focus_output(video, plans, lambda b_: 0, "pil")
+        post = lambda plans: focus.paste(video, plans, lambda b_: 0, "pil", True)
         fd, fh = post(plans_d), post(plans_h)
         same = all(np.array_equal(np.asarray(x), np.asarray(y)) for x, y in zip(fd[0], fh[0]))
         del fd, fh

@@ -261,16 +261,16 @@ def main():
         # what the difference is made of: one more upload, and the build with its reductions and its one read
         up = [wall(lambda: image_io.upload_rgb(im, dev)) for _ in range(5)]
         pipe.enable_sketch_region(grow=grow, feather=feather)
-        masks = [wall(lambda: pipe._sketch_masks([im], [cp], dev)) for _ in range(5)]
-        entry = pipe._sketch_masks([im], [cp], dev)[0]
+        masks = [wall(lambda: sketch.masks(pipe._sketch_region, [im], [cp], dev)) for _ in range(5)]
+        entry = sketch.masks(pipe._sketch_region, [im], [cp], dev)[0]
         copies = [wall(lambda: entry["mask_dev"].cpu()) for _ in range(5)]
         pipe.disable_sketch_region()
         rep = reports["sketch"]
         lines += [f"One upload of the photo ({3 * plane / 1e6:.1f} MB from pageable memory, `convert(\"RGB\")` and the copy included): {fmt(up)} ms.  Both uploads, the build, the two "
-                  f"reductions and the read of ten integers (`_sketch_masks`: all that runs in front of the edit): {fmt(masks)} ms.  The report's copy of the "
+                  f"reductions and the read of ten integers (`sketch.masks`: all that runs in front of the edit): {fmt(masks)} ms.  The report's copy of the "
                   f"mask to the host, behind the edit: {fmt(copies)} ms.",
                   f"The plan: box {rep['box']}, scale {rep['scale']:.3f}, the mask covers {rep['mask_fraction_of_box']:.3f} of the box; {rep['changed_pixels']} changed pixels."]
-        print(f"upload {fmt(up)} ms, _sketch_masks {fmt(masks)} ms, mask copy {fmt(copies)} ms", flush=True)
+        print(f"upload {fmt(up)} ms, sketch.masks {fmt(masks)} ms, mask copy {fmt(copies)} ms", flush=True)
     lines += ["", "## What these numbers do not say", "",
               "The weights are random: nothing here judges what the paint-brush LoRA makes of a sketch inside a crop.  What the feature guarantees is",
               "arithmetic - the mask equal to PIL's recipe (tests/test_sketch_cpu.py), the three passes bit-equal to it (tests/test_exact_sketch_gpu.py), a",
