@@ -7,7 +7,11 @@ go on as chronoedit_amd/region.py would with a caller-given mask - blend, sparse
     d      fp32 [h, w]    on the LAST latent frame: max over samples of ((sum over channels, in order, of (x0 - z_src)^2) / C)
     thr    one float      a number t (RMS units of the normalised latents): fp32(t) * fp32(t); "otsu": Otsu's threshold of a 256-bin
                           histogram of d over [0, dmax], at least floor^2 - on the device, nothing is read back for it
-    w      fp32 [h, w]    seed = d > thr, dilated by `dilate` cells (Chebyshev) at weight 1, then a linear ramp over `feather` cells to 0
+    w      fp32 [h, w]    seed = d > thr, dilated by `dilate` cells (Chebyshev) at weight 1, then a linear ramp over `feather` cells to 0.
+                          With `min_area` the seed set first loses its speckle (chronoedit_amd/components.py): its 8-connected components
+                          of fewer cells than min_area (an int), or than that fraction of the largest one (a float), are taken out:
+                          d' = where(kept, d, -1), w = the ramp of d'.  d is a mean of squares and no threshold is below 0, so a cell at
+                          -1 is no seed and the ramp pass itself is untouched
     mask   uint8 [8h, 8w] rint(255 * w) of the pixel's cell: the mask of the paste-back, and what `set_edit_region` takes back
 
 Then ONE device-to-host read (w, thr, dmax) and the decision: no active cell, or more active patches than `max_area` of the grid, and the
@@ -32,7 +36,8 @@ class AutoRegionConfig:
     it that runs at the truncated shape; past the last step: nothing is detected).  threshold: "otsu", or a number in RMS units of the
     normalised latents.  floor: the least RMS change Otsu's threshold may call an edit.  dilate / feather: cells of weight 1 around the
     seed, and cells of the ramp to 0 behind them.  max_area: the largest fraction of the patch grid an accepted region may cover.
-    composite: paste the source back in pixel space behind the decode."""
+    composite: paste the source back in pixel space behind the decode.  min_area: 0 is off; an int >= 1 is the least number of cells a
+    component of the seed set must hold, a float in (0, 1) that fraction of the largest component's."""
     detect_step: int
     threshold: Union[str, float] = "otsu"
     floor: float = 0.0
@@ -40,6 +45,7 @@ class AutoRegionConfig:
     feather: int = 1
     max_area: float = 0.5
     composite: bool = True
+    min_area: Union[int, float] = 0
 
     def __post_init__(self):
         ds = self.detect_step
@@ -63,6 +69,11 @@ class AutoRegionConfig:
         ma = self.max_area
         if isinstance(ma, bool) or not isinstance(ma, (int, float)) or not 0.0 < ma <= 1.0:  # (a NaN fails the comparison)
             raise ValueError(f"auto region: max_area must lie in (0, 1], got {ma!r}")
+        from .components import check_min_weight
+        object.__setattr__(self, "min_area", check_min_weight(self.min_area, "auto region: min_area", zero_is_off=True))
+        # (a dropped seed is marked by d' = -1: that is below every threshold, because none is negative - a number and the floor are checked
+        # above, and Otsu's is a bin edge of [0, dmax] or the floor's square)
+        assert isinstance(th, str) or th >= 0
 
 
 class AutoRegion:
@@ -148,9 +159,11 @@ class AutoRegionState:
             return None
         from . import region as _rg
         auto, found = self.auto, None
-        w, mask, w_cpu, thr, dmax = detect(scheduler.model_outputs[-1], self.z, self.config)
+        w, mask, w_cpu, thr, dmax, *counters = detect(scheduler.model_outputs[-1], self.z, self.config)
         ok, why, frac = decide(w_cpu, self.config, margin)
         auto.report = self.transformer.auto_region_report = report(i, thr, dmax, frac, ok, why, w_cpu)
+        if counters:  # (min_area is on)
+            auto.report.update(min_area=self.config.min_area, components=counters[0][0], dropped_components=counters[0][1], dropped_cells=counters[0][2])
         if ok and auto.on_accept is not None and auto.on_accept(mask):
             auto.mask_u8, auto.exited, self.exiting = mask, True, True  # the caller goes on from here (the history is as step k left it)
         elif ok:
@@ -256,6 +269,30 @@ def ramp_weights(d: torch.Tensor, thr: torch.Tensor, dilate: int = 1, feather: i
     return w
 
 
+def seed_plane(d: torch.Tensor, thr: torch.Tensor) -> torch.Tensor:
+    """d fp32 [h, w], thr one float -> uint8 [h, w]: 255 where d > thr (a seed), else 0."""
+    if d.is_cuda:
+        from . import ops
+        return ops.components_seeds(d.contiguous(), thr.to(d.device).reshape(1).contiguous())
+    return (d.to(torch.float32) > thr.reshape(()).to(torch.float32)).to(torch.uint8) * 255
+
+
+def masked_map(d: torch.Tensor, kept: torch.Tensor) -> torch.Tensor:
+    """d' = where(kept, d, -1): the change map without the seeds that were dropped."""
+    if d.is_cuda:
+        from . import ops
+        return ops.components_masked(d.contiguous(), kept.contiguous())
+    return torch.where(kept != 0, d.to(torch.float32), torch.tensor(-1.0, dtype=torch.float32))
+
+
+def kept_map(d: torch.Tensor, thr: torch.Tensor, min_area) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (d', stats): the seed set d > thr without its components below `min_area` (components.filter, weight = cells), as the change map
+    the ramp pass takes, and int32 [4] = (components kept, components dropped, cells dropped, the largest component's cells) where d lies."""
+    from . import components
+    kept, stats = components.filter(seed_plane(d, thr), min_area)
+    return masked_map(d, kept), stats
+
+
 def pixel_mask(w: torch.Tensor) -> torch.Tensor:
     """w fp32 [h, w] -> uint8 [8h, 8w]."""
     if w.is_cuda:
@@ -271,6 +308,8 @@ def weights(x0: torch.Tensor, z_src: torch.Tensor, cfg: AutoRegionConfig):
     thr, dmax = otsu_threshold(d, cfg.floor)
     if cfg.threshold != "otsu":
         thr = number_threshold(cfg.threshold).to(d.device)
+    if cfg.min_area:
+        return d, thr, dmax, ramp_weights(kept_map(d, thr, cfg.min_area)[0], thr, cfg.dilate, cfg.feather)
     return d, thr, dmax, ramp_weights(d, thr, cfg.dilate, cfg.feather)
 
 
@@ -279,19 +318,25 @@ def weights(x0: torch.Tensor, z_src: torch.Tensor, cfg: AutoRegionConfig):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 def detect(x0: torch.Tensor, z_src: torch.Tensor, cfg: AutoRegionConfig):
     """The four device passes and the ONE read behind them -> (w on the device, mask_u8 on the device, w on the CPU, thr, dmax).  w, thr and
-    dmax share one buffer, so one copy brings all three."""
+    dmax share one buffer, so one copy brings all three.  With cfg.min_area the speckle filter runs in front of the ramp pass, its four
+    counters ride in the same buffer (their int32 bits in four more fp32 slots) and a sixth element, a tuple of the four, is returned."""
     from . import ops
     h, wl = x0.shape[-2:]
     d = ops.auto_region_change(x0, z_src, -1)
-    buf = torch.empty(h * wl + 2, dtype=torch.float32, device=x0.device)
-    w, thr, dmax = buf[:h * wl].view(h, wl), buf[h * wl:h * wl + 1], buf[h * wl + 1:]
+    extra = 4 if cfg.min_area else 0
+    buf = torch.empty(h * wl + 2 + extra, dtype=torch.float32, device=x0.device)
+    w, thr, dmax = buf[:h * wl].view(h, wl), buf[h * wl:h * wl + 1], buf[h * wl + 1:h * wl + 2]
     ops.auto_region_otsu(d, cfg.floor, thr, dmax)  # (with a number for a threshold: for dmax, which the report carries)
     if cfg.threshold != "otsu":
         thr.copy_(number_threshold(cfg.threshold), non_blocking=True)  # staged from the host
+    if extra:
+        d, stats = kept_map(d, thr, cfg.min_area)
+        buf[h * wl + 2:].view(torch.int32).copy_(stats)
     ops.auto_region_ramp(d, thr, cfg.dilate, cfg.feather, out=w)
     mask = ops.auto_region_mask_u8(w)
     host = buf.cpu()  # the one device-to-host read: what sparse_region.active_tokens reads anyway
-    return w, mask, host[:h * wl].view(h, wl).clone(), float(host[h * wl]), float(host[h * wl + 1])
+    out = (w, mask, host[:h * wl].view(h, wl).clone(), float(host[h * wl]), float(host[h * wl + 1]))
+    return out + (tuple(host[h * wl + 2:].view(torch.int32).tolist()),) if extra else out
 
 
 def decide(w_cpu: torch.Tensor, cfg: AutoRegionConfig, margin: int = 0) -> Tuple[bool, str, float]:
@@ -319,14 +364,20 @@ def report(step: Optional[int], thr: float, dmax: float, frac: float, accepted: 
 
 
 def measurement(table: torch.Tensor, cfg: AutoRegionConfig) -> list:
-    """table = fp32 [steps, h, w] change maps on the CPU -> per step {"step", "threshold", "active_fraction", "iou"}: the threshold of that
-    step's map, the fraction of cells above it, and the IoU of that seed set with the last step's (1 for two empty sets)."""
+    """table = fp32 [steps, h, w] change maps on the CPU -> per step {"step", "threshold", "active_fraction", "iou", "components",
+    "largest_fraction"}: the threshold of that step's map, the fraction of cells above it, the IoU of that seed set with the last step's
+    (1 for two empty sets), the number of 8-connected components of the seed set and the largest one's share of the seeds (0 without
+    seeds) - what `min_area` is chosen from."""
+    from . import components
     seeds, rows = [], []
     for i in range(table.shape[0]):
         d = table[i]
         thr = otsu_threshold(d, cfg.floor)[0] if cfg.threshold == "otsu" else number_threshold(cfg.threshold)
         seeds.append(d > thr.reshape(()))
-        rows.append({"step": i, "threshold": float(thr), "active_fraction": float(seeds[-1].float().mean())})
+        stats = components.filter(seeds[-1].to(torch.uint8), 1)[1].tolist()
+        n_seeds = int(seeds[-1].sum())
+        rows.append({"step": i, "threshold": float(thr), "active_fraction": float(seeds[-1].float().mean()), "components": stats[0],
+                     "largest_fraction": stats[3] / n_seeds if n_seeds else 0.0})
     last = seeds[-1]
     for row, s in zip(rows, seeds):
         union = int((s | last).sum())

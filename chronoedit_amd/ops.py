@@ -1061,6 +1061,104 @@ def sketch_box_u8(src: torch.Tensor, axis: int, radius: int, out: Optional[torch
     return _sketch_filter("ce_sketch_box_u8", src, axis, radius, out, scratch)
 
 
+# ---- connected components (csrc/ce_components.hip) ------------------------------------------------------------------------
+def _iplane(t: torch.Tensor, name: str, shape):
+    _dev(t, torch.int32, name)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name}: need a contiguous int32 {list(shape)} tensor, got shape {tuple(t.shape)} stride {t.stride()}")
+
+
+def components_scratch_bytes(H: int, W: int) -> int:
+    """The scratch of one `components.filter` on the device: the label plane and the sums plane int32 [H, W], and 16 bytes of counters."""
+    return 8 * int(H) * int(W) + 16
+
+
+def components_roots_i32(plane: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """plane uint8 [H, W] -> int32 [H, W]: the smallest index y * W + x of the pixel's 8-connected component of non-zero bytes, -1 for a
+    zero byte.  `out` needs no initialisation."""
+    _plane(plane, "plane")
+    H, W = plane.shape
+    if H * W >= 1 << 31:
+        raise ValueError(f"plane: need H * W < 2^31, got {H} x {W}")
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.int32, device=plane.device)
+    _iplane(out, "out", (H, W))
+    st = _prof_begin()
+    _check(lib().ce_components_roots_i32(_ptr(plane), _ptr(out), H, W, _stream()), "ce_components_roots_i32")
+    _prof_end(st, f"components_roots_{H}x{W}", 13.0 * H * W)
+    return out
+
+
+def components_sums_i32(roots: torch.Tensor, weight: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """roots int32 [H, W] (+ weight uint8 [H, W]; None: every pixel counts) -> int32 [H, W]: at a root's own position the number of its
+    component's pixels with a non-zero weight byte, 0 elsewhere."""
+    if roots.dim() != 2 or roots.numel() == 0:
+        raise ValueError(f"roots: need a non-empty [H, W] tensor, got shape {tuple(roots.shape)}")
+    H, W = roots.shape
+    _iplane(roots, "roots", (H, W))
+    if weight is not None:
+        _plane(weight, "weight")
+        if tuple(weight.shape) != (H, W):
+            raise ValueError(f"weight: need shape {(H, W)}, got {tuple(weight.shape)}")
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.int32, device=roots.device)
+    _iplane(out, "out", (H, W))
+    assert out.data_ptr() != roots.data_ptr()
+    st = _prof_begin()
+    _check(lib().ce_components_sums_i32(_ptr(roots), _ptr(weight), _ptr(out), H, W, _stream()), "ce_components_sums_i32")
+    _prof_end(st, f"components_sums_{H}x{W}", 9.0 * H * W)
+    return out
+
+
+def components_keep_u8(plane: torch.Tensor, roots: torch.Tensor, sums: torch.Tensor, min_weight: int, num: int = 0, den: int = 0,
+                       out: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None):
+    """-> (out uint8 [H, W], counters int32 [4]): plane where the component's weight is >= the least weight kept - min_weight (den == 0), or
+    ceil(num * the largest weight / den), taken on the device -, else 0; counters = components kept, dropped, weight dropped, largest."""
+    _plane(plane, "plane")
+    H, W = plane.shape
+    _iplane(roots, "roots", (H, W)), _iplane(sums, "sums", (H, W))
+    if out is None:
+        out = torch.empty_like(plane)
+    _plane(out, "out")
+    assert out.shape == plane.shape and out.data_ptr() != plane.data_ptr()
+    if counters is None:
+        counters = torch.empty(4, dtype=torch.int32, device=plane.device)
+    _iplane(counters, "counters", (4,))
+    if not ((den == 0 and min_weight >= 1) or (0 < num < den <= 65536)):
+        raise ValueError(f"need min_weight >= 1, or a fraction 0 < num / den < 1 with den <= 65536, got {min_weight}, {num} / {den}")
+    st = _prof_begin()
+    _check(lib().ce_components_keep_u8(_ptr(plane), _ptr(roots), _ptr(sums), _ptr(out), _ptr(counters), int(min_weight), int(num), int(den), H, W,
+                                       _stream()), "ce_components_keep_u8")
+    _prof_end(st, f"components_keep_{H}x{W}", 14.0 * H * W)
+    return out, counters
+
+
+def components_seeds(d: torch.Tensor, thr: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """d fp32 [h, w], thr one fp32 element on the device -> uint8 [h, w]: 255 where d > thr, else 0."""
+    _f32c(d, "d"), _f32c(thr, "thr")
+    if d.dim() != 2 or d.numel() == 0 or thr.numel() != 1:
+        raise ValueError(f"need d [h, w] and one threshold, got {tuple(d.shape)} and {tuple(thr.shape)}")
+    if out is None:
+        out = torch.empty(tuple(d.shape), dtype=torch.uint8, device=d.device)
+    _plane(out, "out")
+    assert out.shape == d.shape
+    _check(lib().ce_components_seeds_f32(_ptr(d), _ptr(thr), _ptr(out), d.numel(), _stream()), "ce_components_seeds_f32")
+    return out
+
+
+def components_masked(d: torch.Tensor, kept: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """d fp32 [h, w], kept uint8 [h, w] -> a new fp32 [h, w]: d where kept is non-zero, else -1."""
+    _f32c(d, "d"), _plane(kept, "kept")
+    if d.shape != kept.shape:
+        raise ValueError(f"d {tuple(d.shape)} and kept {tuple(kept.shape)} differ in shape")
+    if out is None:
+        out = torch.empty_like(d)
+    _f32c(out, "out")
+    assert out.shape == d.shape and out.data_ptr() != d.data_ptr()
+    _check(lib().ce_components_masked_f32(_ptr(d), _ptr(kept), _ptr(out), d.numel(), _stream()), "ce_components_masked_f32")
+    return out
+
+
 # ---- automatic edit regions (csrc/ce_region_auto.hip) ------------------------------------------------------------------
 def _f32c(t: torch.Tensor, name: str):
     _dev(t, torch.float32, name)

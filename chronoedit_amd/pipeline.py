@@ -475,14 +475,20 @@ class ChronoEditPipeline:
     # Automatic edit regions (chronoedit_amd/auto_region.py): an edit without a mask finds its own region.  Off by default; an explicit
     # `set_edit_region` mask wins
     def enable_auto_region(self, detect_step: int, threshold="otsu", floor: float = 0.0, dilate: int = 1, feather: int = 1,
-                           max_area: float = 0.5, composite: bool = True):
+                           max_area: float = 0.5, composite: bool = True, min_area=0):
         """Behind step `detect_step` the model's estimate of the final image is compared with the source latents (one more VAE encode per
         call, as for an explicit region), the difference thresholded ("otsu", or a number in RMS units of the normalised latents; `floor`
         bounds Otsu's from below), dilated by `dilate` cells and feathered over `feather`; when the region covers at most `max_area` of
         the grid the edit continues as a region-limited one - with `enable_sparse_region`, as a sparse one - and with `composite` the
         source is pasted back behind the decode.  Otherwise it stays the plain edit.  `auto_region_report` tells what happened; its
-        "mask" can be repainted and handed to `set_edit_region`."""
-        self.transformer.enable_auto_region(detect_step, threshold, floor, dilate, feather, max_area, composite)
+        "mask" can be repainted and handed to `set_edit_region`.
+        min_area (0: off, today's call bit for bit): the seed set - the cells above the threshold - first loses its speckle: its 8-connected
+        components of fewer cells than `min_area` (an int >= 1), or than that fraction of the largest one (a float in (0, 1)), are dropped
+        on the device (chronoedit_amd/components.py) before it is dilated and feathered; the decision, the sparse plan, the paste-back mask
+        and `enable_auto_focus` see the filtered region, the detection step still reads the device once, and `auto_region_report` also
+        holds "min_area", "components" (kept), "dropped_components" and "dropped_cells".  `measure_auto_region`'s rows carry "components"
+        and "largest_fraction" per step to choose it from."""
+        self.transformer.enable_auto_region(detect_step, threshold, floor, dilate, feather, max_area, composite, min_area)
         return self
 
     def disable_auto_region(self):
@@ -572,9 +578,10 @@ class ChronoEditPipeline:
         it.  edits: a list of keyword dicts as `calibrate_teacache` takes them; options: the detector's (threshold, floor, dilate, feather,
         max_area), anything else is added to every edit.  Each edit runs the plain loop - the latents are the plain loop's - and every
         step also writes its change map into a [steps, h, w] device table, read back once after the last step.  Returns per edit
-        {"timesteps", "steps": per step {"step", "threshold", "active_fraction", "iou" (of that step's seed set with the last step's)},
-        "latents"}.  The detector itself is NOT switched on, an enabled one and an edit region are ignored here."""
-        det = {k: options.pop(k) for k in ("threshold", "floor", "dilate", "feather", "max_area") if k in options}
+        {"timesteps", "steps": per step {"step", "threshold", "active_fraction", "iou" (of that step's seed set with the last step's),
+        "components" (8-connected, of the seed set), "largest_fraction" (the largest one's share of the seeds): what `min_area` is chosen
+        from}, "latents"}.  The detector itself is NOT switched on, an enabled one and an edit region are ignored here."""
+        det = {k: options.pop(k) for k in ("threshold", "floor", "dilate", "feather", "max_area", "min_area") if k in options}
         cfg = _ar.AutoRegionConfig(detect_step=0, **det)
         out, saved = [], self._edit_region
         self._auto_region_measure, self._edit_region = cfg, None
@@ -670,7 +677,7 @@ class ChronoEditPipeline:
         return self
 
     # Sketch edits (chronoedit_amd/sketch.py): the region is where the editor's composite differs from its background.  Off by default
-    def enable_sketch_region(self, grow=0.02, feather=0.01, threshold: int = 0, context: float = 0.25, composite: bool = True):
+    def enable_sketch_region(self, grow=0.02, feather=0.01, threshold: int = 0, context: float = 0.25, composite: bool = True, min_stroke=0):
         """While on and no `set_edit_region` mask is set, `__call__(image=...)` also takes an image editor's value: a dict with PIL images
         under "background" (the photo) and "composite" (the photo with the strokes on it) - other keys, such as "layers", are ignored -, or
         a list of such dicts, one per prompt.  Per value the mask is built at the PHOTO's size before the first step (sketch.reference:
@@ -686,8 +693,17 @@ class ChronoEditPipeline:
         image, array or tensor is the call it is without the switch (`sketch_report` None).  With a `set_edit_region` mask the explicit mask
         wins: an editor value then stands for its composite.  A value whose two images differ in size, or that lacks one, is a ValueError.
         `sketch_report` holds per value the focus plan's entries (`focus_report`'s) plus "mask" (PIL "L", the photo's size), "grow_px",
-        "feather_px", "threshold" and "changed_pixels"."""
-        self._sketch_region = _sk.SketchConfig(grow, feather, threshold, context, composite)
+        "feather_px", "threshold" and "changed_pixels".
+        min_stroke (0: off, today's call bit for bit, no launch): drop speckle.  The grown strokes fall into clusters - the 8-connected
+        components of the grown plane, i.e. strokes within 2 (grow + feather) of each other -, each weighted by the changed pixels it holds;
+        clusters below `min_stroke` changed pixels (an int >= 1), or below that fraction of the heaviest cluster (a float in (0, 1)), leave
+        the mask before it is feathered (chronoedit_amd/components.py; csrc/ce_components.hip on the device, the same bits, and the
+        one read grows to fourteen integers).  One stray pixel far from the sketch then no longer stretches the box to the whole photo.
+        A dropped cluster's strokes are not pasted: there the frames carry the background, and "composite and background agree wherever
+        the mask is below 255" holds outside the dropped clusters.  All clusters dropped (an int only): "empty", the plain call on the
+        composite.  `sketch_report[i]` then also holds "min_stroke", "clusters" (kept), "dropped_clusters" and "dropped_pixels" (changed
+        pixels of the dropped clusters); `sketch_mask` applies the filter too."""
+        self._sketch_region = _sk.SketchConfig(grow, feather, threshold, context, composite, min_stroke)
         return self
 
     def disable_sketch_region(self):
@@ -780,6 +796,9 @@ class ChronoEditPipeline:
         # behind the edit: the device path copies its masks to the host here, not in front of the first step
         self.sketch_report = [dict(p.report, mask=Image.fromarray(p.host_mask().numpy(), mode="L"), grow_px=e["grow_px"], feather_px=e["feather_px"],
                                    threshold=cfg.threshold, changed_pixels=e["changed_pixels"]) for p, e in zip(plans, entries)]
+        if cfg.min_stroke:
+            for rep, e in zip(self.sketch_report, entries):
+                rep.update(min_stroke=cfg.min_stroke, clusters=e["clusters"], dropped_clusters=e["dropped_clusters"], dropped_pixels=e["dropped_pixels"])
         return out
 
     def _edit(self, a: CallArgs, fpass: Optional[FocusPass] = None):

@@ -16,7 +16,18 @@ the photo, and the photo with the strokes on it.  With `ChronoEditPipeline.enabl
 What follows from the arithmetic: every pixel within `grow` (Chebyshev distance) of a changed pixel is 255 exactly, every pixel farther
 than grow + 2 feather from all of them is 0, and with threshold = 0 composite and background carry the same bytes wherever the mask is below
 255.  All integers: the device passes (csrc/ce_sketch.hip) give `reference`'s bits.  What the paint-brush LoRA makes of a sketch inside a
-crop is the checkpoint's business."""
+crop is the checkpoint's business.
+
+With `min_stroke` the chain drops speckle (chronoedit_amd/components.py) between the two filters:
+
+    changed -> grown -> the 8-connected components of GROWN, each weighted by its CHANGED pixels -> kept -> box mean
+
+A component of the grown plane is a CLUSTER of strokes that lie within 2 R of each other; clusters with fewer changed pixels than
+`min_stroke` (an int), or than that fraction of the heaviest cluster (a float), leave the grown plane before the box mean.  Dotted or
+hatched strokes are many tiny components of `changed` but one cluster; a speck beside a stroke lies inside the region anyway; a speck far
+from every stroke is a cluster of its own with next to no weight, and goes.  The guarantees above then speak of the changed pixels of KEPT
+clusters, and "composite and background agree wherever the mask is below 255" holds outside the dropped clusters: the frames are pasted
+into the background, so a dropped speck does not come back."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -26,6 +37,7 @@ from typing import Tuple, Union
 import numpy as np
 import torch
 
+from . import components as _cc
 from .focus import _ceil, focus_box
 
 ENTRY_POINTS = ("ce_sketch_changed_u8", "ce_sketch_dilate_u8", "ce_sketch_box_u8")
@@ -50,12 +62,14 @@ class SketchConfig:
     pixel counts as drawn on when a channel differs by MORE than this (0..254).  context, composite: `enable_region_focus`'s and
     `set_edit_region`'s.  The defaults are choices, not measurements: a margin of 2 % of the photo around the strokes belongs to the
     model, a further 1 % (twice: the box mean spreads over 2 feather) fades into the photo, and a lossless editor changes no byte it was
-    not asked to (a front end that re-encodes its composite needs a threshold above its codec's error)."""
+    not asked to (a front end that re-encodes its composite needs a threshold above its codec's error).  min_stroke: 0 is off; an int >= 1
+    is the least number of changed pixels a cluster of strokes must hold, a float in (0, 1) that fraction of the heaviest cluster's."""
     grow: Union[int, float] = 0.02
     feather: Union[int, float] = 0.01
     threshold: int = 0
     context: float = 0.25
     composite: bool = True
+    min_stroke: Union[int, float] = 0
 
     def __post_init__(self):
         object.__setattr__(self, "grow", _length(self.grow, "grow"))
@@ -65,6 +79,7 @@ class SketchConfig:
         focus_box(None, (1, 1), (1, 1), self.context)  # (validates the context)
         if not isinstance(self.composite, bool):
             raise ValueError(f"sketch region: composite must be a bool, got {self.composite!r}")
+        object.__setattr__(self, "min_stroke", _cc.check_min_weight(self.min_stroke, "sketch region: min_stroke", zero_is_off=True))
         _check_pixels(self.grow if isinstance(self.grow, int) else 0, self.feather if isinstance(self.feather, int) else 0)  # (fractions: at the call)
 
     def pixels(self, src_size: Tuple[int, int]) -> Tuple[int, int]:
@@ -195,14 +210,40 @@ def stages(background, composite, grow: int, feather: int, threshold: int = 0) -
     return ch, grown, mask
 
 
-def reference(background, composite, grow: int, feather: int, threshold: int = 0) -> torch.Tensor:
+def filtered_stages(background, composite, grow: int, feather: int, threshold: int = 0, min_stroke=1, scratch=None):
+    """`stages` with the speckle filter between the two filters -> (changed, grown, kept, mask, stats): kept = the grown plane without the
+    clusters that hold fewer changed pixels than min_stroke (components.filter of grown, weighted by changed), mask its box mean, stats
+    int32 [4] = (clusters kept, clusters dropped, changed pixels dropped, the heaviest cluster's changed pixels) where the images lie -
+    nothing is read back.  scratch: components.filter's, on the device."""
+    grow, feather = int(grow), int(feather)
+    _check_pixels(grow, feather)
+    if isinstance(threshold, bool) or not 0 <= int(threshold) <= 254:
+        raise ValueError(f"sketch: threshold must be an int in 0..254, got {threshold!r}")
+    ch = changed(rgb_bytes(background), rgb_bytes(composite), int(threshold))
+    grown = ch
+    if grow + feather:
+        grown = dilate(dilate(ch, grow + feather, 0), grow + feather, 1)
+    kept, stats = _cc.filter(grown, min_stroke, ch, scratch)
+    m = kept
+    if feather:
+        m = box(box(kept, feather, 0), feather, 1)
+    return ch, grown, kept, m, stats
+
+
+def reference(background, composite, grow: int, feather: int, threshold: int = 0, min_stroke=0) -> torch.Tensor:
     """THE definition, and the host path: two images (PIL, or uint8 [SH, SW, 3]) -> the mask uint8 [SH, SW] on the host.  grow, feather in
     pixels of the photo."""
-    return stages(rgb_bytes(background).cpu(), rgb_bytes(composite).cpu(), grow, feather, threshold)[2]
+    bg, cp = rgb_bytes(background).cpu(), rgb_bytes(composite).cpu()
+    if min_stroke:
+        return filtered_stages(bg, cp, grow, feather, threshold, min_stroke)[3]
+    return stages(bg, cp, grow, feather, threshold)[2]
 
 
-def mask(background: torch.Tensor, composite: torch.Tensor, grow: int, feather: int, threshold: int = 0) -> torch.Tensor:
-    """`reference` where the bytes lie: uint8 [SH, SW, 3] twice, on the GPU (five launches at most, no host read) or on the host."""
+def mask(background: torch.Tensor, composite: torch.Tensor, grow: int, feather: int, threshold: int = 0, min_stroke=0) -> torch.Tensor:
+    """`reference` where the bytes lie: uint8 [SH, SW, 3] twice, on the GPU (five launches at most - eleven and two memsets with min_stroke -, no host
+    read) or on the host."""
+    if min_stroke:
+        return filtered_stages(background, composite, grow, feather, threshold, min_stroke)[3]
     return stages(background, composite, grow, feather, threshold)[2]
 
 
@@ -210,7 +251,9 @@ def mask(background: torch.Tensor, composite: torch.Tensor, grow: int, feather: 
 def masks(cfg: SketchConfig, bgs, cps, device=None) -> list:
     """Per editor value {"background", "composite", "mask_u8" (host; None on the device path: `host_mask` copies it when the edit is done),
     "grow_px", "feather_px", "bbox" (None: no strokes), "mask_pixels", "changed_pixels"} and, on the device path (device set), "bg_u8",
-    "cp_u8", "mask_dev": each image uploaded once, two reductions and ONE read of their ten integers per value - nothing else comes back."""
+    "cp_u8", "mask_dev": each image uploaded once, two reductions and ONE read of their ten integers per value - nothing else comes back.
+    With cfg.min_stroke the mask is the filtered chain's, the entry also holds "clusters", "dropped_clusters" and "dropped_pixels", and the
+    filter's four counters come back in the same read: fourteen integers ("changed_pixels" still counts every changed pixel)."""
     from . import autofocus as _af
     from . import image_io
     out = []
@@ -219,15 +262,25 @@ def masks(cfg: SketchConfig, bgs, cps, device=None) -> list:
         e = {"background": bg, "composite": cp, "grow_px": g, "feather_px": f}
         if device is not None:
             e["bg_u8"], e["cp_u8"] = image_io.upload_rgb(bg, device), image_io.upload_rgb(cp, device)
-            ch, _, m = stages(e["bg_u8"], e["cp_u8"], g, f, cfg.threshold)
-            counts = torch.cat([_af.bbox_counts(m), _af.bbox_counts(ch)]).tolist()
+            if cfg.min_stroke:
+                ch, _, _, m, stats = filtered_stages(e["bg_u8"], e["cp_u8"], g, f, cfg.threshold, cfg.min_stroke)
+                counts = torch.cat([_af.bbox_counts(m), _af.bbox_counts(ch), stats]).tolist()
+            else:
+                ch, _, m = stages(e["bg_u8"], e["cp_u8"], g, f, cfg.threshold)
+                counts = torch.cat([_af.bbox_counts(m), _af.bbox_counts(ch)]).tolist()
             e["mask_dev"], e["mask_u8"] = m, None
         else:
-            ch, _, m = stages(bg, cp, g, f, cfg.threshold)
-            counts = _af.bbox_counts(m).tolist() + _af.bbox_counts(ch).tolist()
+            if cfg.min_stroke:
+                ch, _, _, m, stats = filtered_stages(bg, cp, g, f, cfg.threshold, cfg.min_stroke)
+                counts = _af.bbox_counts(m).tolist() + _af.bbox_counts(ch).tolist() + stats.tolist()
+            else:
+                ch, _, m = stages(bg, cp, g, f, cfg.threshold)
+                counts = _af.bbox_counts(m).tolist() + _af.bbox_counts(ch).tolist()
             e["mask_u8"] = m
         e["bbox"] = tuple(int(v) for v in counts[:4]) if counts[4] else None
         e["mask_pixels"], e["changed_pixels"] = int(counts[4]), int(counts[9])
+        if cfg.min_stroke:
+            e["clusters"], e["dropped_clusters"], e["dropped_pixels"] = int(counts[10]), int(counts[11]), int(counts[12])
         out.append(e)
     return out
 

@@ -462,12 +462,12 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         return self
 
     def enable_auto_region(self, detect_step: int, threshold="otsu", floor: float = 0.0, dilate: int = 1, feather: int = 1,
-                           max_area: float = 0.5, composite: bool = True):
+                           max_area: float = 0.5, composite: bool = True, min_area=0):
         """Automatic edit regions (chronoedit_amd/auto_region.py): an edit without an explicit region looks for its own behind step
         `detect_step` and, when it finds one, continues as a region-limited edit (`pipeline.denoise(auto_region=)`; the pipeline supplies
         the source latents).  Off by default; an explicit region wins."""
         from .auto_region import AutoRegionConfig
-        self._auto_region = AutoRegionConfig(detect_step, threshold, floor, dilate, feather, max_area, composite)
+        self._auto_region = AutoRegionConfig(detect_step, threshold, floor, dilate, feather, max_area, composite, min_area)
         return self
 
     def disable_auto_region(self):

@@ -692,6 +692,31 @@ int ce_sketch_dilate_u8(const void* src, void* dst, int H, int W, int axis, int 
                         hipStream_t stream);
 int ce_sketch_box_u8(const void* src, void* dst, int H, int W, int axis, int radius, void* scratch, size_t scratch_bytes, hipStream_t stream);
 
+/* ---- connected components of a byte plane (csrc/ce_components.hip; chronoedit_amd/components.py): speckle removal for sketched and
+ * detected regions.  Foreground is a non-zero byte, the neighbourhood is 8-connected; components.reference (numpy, on row runs) is the
+ * definition and every pass gives its bits.  Planes are [H][W], contiguous, H * W < 2^31 (otherwise -2); int32 planes 4-byte aligned
+ * (otherwise -3); byte planes at any address.
+ * ce_components_roots_i32: plane uint8 -> labels int32: for a foreground pixel the smallest index y * W + x of its component, -1 for
+ *   background.  Three launches: 32 x 64 tiles labelled in the LDS (row runs, then a union-find over touching runs), unions across the tile
+ *   borders by device-scope atomicMin whose returned value decides, and a pass that replaces every label by its root.  Every byte of
+ *   `labels` is written; it needs no initialisation.
+ * ce_components_sums_i32: labels (+ weight uint8, or NULL: every pixel counts) -> sums int32: at a root's own position the number of its
+ *   component's pixels whose weight byte is non-zero, 0 everywhere else.  One integer atomic per wave and distinct root, a root that goes
+ *   on along a workgroup's run of pixels added once.
+ * ce_components_keep_u8: out = plane where the component's weight is >= the least weight kept, else 0; counters int32 [4] = components
+ *   kept, components dropped, weight dropped, largest weight (zeroed by the call).  den == 0: the least weight is min_weight >= 1;
+ *   0 < num < den <= 65536: it is ceil(num * largest / den), computed on the device in 64-bit integers - nothing is read back.
+ * ce_components_seeds_f32: seeds[i] = d[i] > thr[0] ? 255 : 0 (thr in device memory; a NaN is no seed).
+ * ce_components_masked_f32: out[i] = kept[i] != 0 ? d[i] : -1 - the change map of an automatic region without its dropped seeds.
+ * Outputs alias no input (otherwise -1).  No state, nothing allocated, no host read, no wait between workgroups: every call is capturable.
+ * Integers and integer atomics only: the results are exact and do not depend on the launch order. */
+int ce_components_roots_i32(const void* plane, int* labels, int H, int W, hipStream_t stream);
+int ce_components_sums_i32(const int* labels, const void* weight, int* sums, int H, int W, hipStream_t stream);
+int ce_components_keep_u8(const void* plane, const int* labels, const int* sums, void* out, int* counters, int min_weight, int num, int den,
+                          int H, int W, hipStream_t stream);
+int ce_components_seeds_f32(const float* d, const float* thr, void* seeds, int n, hipStream_t stream);
+int ce_components_masked_f32(const float* d, const void* kept, float* out, int n, hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
