@@ -305,11 +305,18 @@ def attention_mxfp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, lazy_offs
       lazy_offset=False  (plain loop, variant 0) running row maximum - 3 after every tile; l is the fp32 sum of the un-rounded P.
     e4m3 is a floating-point format, so the two schedules differ in individual roundings of P, not in their distribution.
     The reference has no fp8 path (transformer_chronoedit.py:91-104 is plain SDPA): this IS the definition."""
-    B, H, N, hd = q.shape
-    Nk = k.shape[2]
+    hd = q.shape[-1]
     c = hd ** -0.5 * 1.4426950408889634
     qq, kq = mx_quant(q.float() * c, -1), mx_quant(k, -1)
     vq = mx_quant(v, 2)
+    return attention_mxfp8_quantised(qq, kq, vq, lazy_offset).to(q.dtype)
+
+
+def attention_mxfp8_quantised(qq: torch.Tensor, kq: torch.Tensor, vq: torch.Tensor, lazy_offset: bool = True) -> torch.Tensor:
+    """The online softmax of `attention_mxfp8` on operands that are ALREADY MXFP8 values (fp32 [B, H, N, 128], de-quantised; qq with
+    softmax_scale * log2 e multiplied in): what the kernel computes from the bytes it is handed.  Returns O / l in fp32, unrounded."""
+    B, H, N, hd = qq.shape
+    Nk = kq.shape[2]
     off = torch.full((B, H, N, 1), -1.0e30)
     l = torch.zeros((B, H, N, 1))
     o = torch.zeros((B, H, N, hd))
@@ -332,7 +339,7 @@ def attention_mxfp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, lazy_offs
         o = o * alpha + p8 @ vq[:, :, t0:t0 + 64]
         l = l * alpha + (p8 if lazy_offset else pr).sum(-1, keepdim=True)
         off = new_off
-    return (o / l).to(q.dtype)
+    return o / l
 
 
 # --------------------------------------------------------------------------------------

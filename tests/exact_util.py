@@ -9,6 +9,9 @@ Attention needles (`needle_q`, `needle_k`): every query row has one winning key 
 away from zero).  Keys a kernel must not read
 (rows past the valid length, padding, the neighbouring samples) win outright if they are read at all.
 
+MXFP8 attention (`mx_case`, `mxfp8_attention_f64`, `MX_MISTAKES`): the same idea on operands handed over as e4m3 bytes with E8M0 block
+scales - integer scores in the exp2 domain, every P a power of two or 0, needle rows and tie rows, scales that a wrong scale byte betrays.
+
 An ordinary module (not a conftest): the test files import it by name."""
 import math
 
@@ -772,3 +775,370 @@ def unequal_share(got: torch.Tensor, want: torch.Tensor) -> float:
 def gemv_bias(N: int, gen: torch.Generator) -> torch.Tensor:
     """fp32 [N] bias: distinct multiples of 8 (bias[0] for every row shows, also after a rounding to bf16 of a result below 2048)."""
     return (torch.randperm(N, generator=gen) - N // 2).float() * 8
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# MXFP8 attention (ce_attention_mxfp8 / _quant / _add): operands handed over as BYTES - e4m3 elements with E8M0 block scales - that the
+# test writes itself, so every value is exact in MXFP8 and the producers (pinned elsewhere) stay out of the comparison.
+#
+# Per head (128 channels = four 32-channel MX blocks), all values integers of at most 4 significant bits times a power of two:
+#   dims 3p .. 3p+2, p < 7   K = (d_p, d_p^2, 1), Q = (2 C a_p, -C, -C a_p^2): score = -C sum_p (a_p - d_p)^2, base-4 digits, C = 64 - the winner
+#                            scores exactly 0 and every other key <= -64 in the exp2 domain (the kernel applies no further factor): 44 nats,
+#                            and exp2(-64 + 3) rounds to 0 in e4m3, so every P is a power of two or 0 and l is exact under both schedules
+#   dims 21, 22, 23          tie flags: K = 0 on the 2 / 4 / 8 keys of the head's tie set (the last valid key among them), else 1; a tie row's
+#                            query is -128 on one of them and 0 on the digits: the set scores 0, everyone else -128
+#   dims (30, 40), (72, 110) balance pairs in blocks (0, 1) and (2, 3): Q = (+G, -G), K = (u, u), u in 1..14 per key - they cancel exactly
+#                            under the right block scales and leave G u (2^a - 2^b) under a scale byte taken from elsewhere: the key with
+#                            the largest (or smallest) u then wins.  A needle alone survives any positive reweighting of a block.
+#   dims 100..102, 103       neighbour-sample bonus and invalid flag as in `needle_k` / `needle_q`, weight 2^13 > 64 * 7 * 9
+# Every block is stored under a scale chosen at random among those that hold it exactly (the canonical 2^(floor(log2 amax) - 8) times 1, 2, 4).
+# ------------------------------------------------------------------------------------------------------------------------------------
+MX_C = 64.0
+MX_DIGITS = 7            # base-4 digits: up to 16384 keys per sample
+MX_TIE_DIM = 21          # dims 21, 22, 23: tie sets of 2, 4, 8 keys
+MX_TIE_C = 128.0
+MX_BAL = ((30, 40), (72, 110))
+MX_G = 2.0 ** 13
+MX_BIG = 2.0 ** 13       # beats the largest in-sample lead, 64 * 7 * 9 = 4032, by 4160 octaves
+MX_OCTAVES = MIN_MARGIN_NATS * LOG2E  # the margin in the exp2 domain
+E4M3_LUT = torch.arange(256, dtype=torch.int16).to(torch.uint8).view(torch.float8_e4m3fn).double()
+MX_KEY_OF_POS = torch.tensor([32 * ((p % 32) >> 4) + (p % 32 & 3) + 8 * (((p % 32) & 15) >> 2) + 4 * (p // 32) for p in range(64)])
+MX_POS_OF_KEY = torch.argsort(MX_KEY_OF_POS)  # position inside a 64-key tile of V^T that holds key k (test_mxfp8_v_transpose_matches_contract)
+MX_GAP_BYTE = 0x7E       # e4m3 448: what the gap columns and the spare V^T blocks hold
+
+
+def mx_key_digits(j: torch.Tensor) -> torch.Tensor:
+    """[n] labels -> [n, 7] base-4 digits (least significant first)."""
+    return torch.stack([(j >> (2 * p)) & 3 for p in range(MX_DIGITS)], -1).double()
+
+
+def mx_pack(x: torch.Tensor, gen: torch.Generator, vary: bool = True):
+    """fp64 [..., 32 n] -> (e4m3 bytes of the same shape, E8M0 bytes [..., n]): every 32-element block under the scale 2^(floor(log2 amax) - 8 + s),
+    s random in 0..2 (0 when not `vary`); an all-zero block gets the contract's 2^-126.  Asserts that the bytes hold x exactly."""
+    xb = x.reshape(x.shape[:-1] + (x.shape[-1] // 32, 32))
+    amax = xb.abs().amax(-1)
+    e = torch.floor(torch.log2(amax.clamp(min=2.0 ** -100))) - 8.0
+    if vary:
+        e = e + torch.randint(0, 3, e.shape, generator=gen).double()
+    e = torch.where(amax > 0, e, torch.full_like(e, -126.0))
+    el = (xb / torch.exp2(e)[..., None]).float().to(torch.float8_e4m3fn)
+    assert torch.equal(el.double() * torch.exp2(e)[..., None], xb), "mx_pack: a block is not exact in MXFP8 under its scale"
+    return el.view(torch.uint8).reshape(x.shape), (e + 127.0).to(torch.uint8)
+
+
+def mx_unpack(b8: torch.Tensor, s8: torch.Tensor) -> torch.Tensor:
+    """bytes [..., 32 n] and scale bytes [..., n] -> fp64 values."""
+    return E4M3_LUT[b8.long()] * torch.exp2(s8.double() - 127.0).repeat_interleave(32, dim=-1)
+
+
+class MxCase:
+    """The operands of one ce_attention_mxfp8* launch (CPU) and its expected outputs."""
+
+
+def _mx_tie_sizes(n_kv: int):
+    return [min(1 << k, 1 << (n_kv.bit_length() - 1)) for k in (1, 2, 3)]
+
+
+def mx_case(n_q: int, n_kv: int, heads: int, batch: int, seed: int, mode: str = "perm", n_tie=None, gap_q: int = 16, gap_k: int = 32) -> MxCase:
+    """Needle and tie operands of one launch, as bytes in roomy buffers.
+    mode "perm":  every sample's keys carry their labels in a random order of its own (a neighbour's rows read in place of the sample's own pick
+                  another row); winners from `winners_for` with `edge_keys` on the first and last needle rows
+         "tile0": the same with every winner among keys 0..63 (no offset raise after the first tile; use with n_tie = 0)
+         "mixed": even rows win in tile 0, odd rows at a key >= 64: in every 32-row wave group some rows raise the offset late, the others never
+         "far":   the MX form of `far_first_tile`: rows 0..63 carry labels with four digits at 3, the winners' are 0 there: all of tile 0 lies
+                  >= 64 * 4 * 9 = 2304 octaves below every winner
+    The last n_tie rows of every sample (default 12, a quarter of the rows of a short sample; they share the partial last query block with needle
+    rows) are tie rows: 2^k keys (k = 1 + i % 3, as many as fit) of a set per (sample, head) score 0, the last valid key among them, all others
+    -128; the expected row is the mean of V over the set, exact in fp32.
+    V = +-n 2^e, n in 8..14, e in -1..2 per (channel, 32-key block): exact in MXFP8, never near zero, another scale in most neighbouring blocks;
+    the keys of a tie set share one sign per column, so that no mean cancels: a mean of exactly 0 would expose the 2^-128 weights of the losers.
+    Buffers: q8 [B n_q + 256 B, D + gap_q] (the spare rows hold other queries), k8 [B n_kv + 64 B + 64, D + gap_k] (the spare rows win if read),
+    their scale rows alike; v8t / sv with one spare sample block behind the last; gap columns and spare V^T blocks hold 448.  Fields: q, k
+    (fp64, de-quantised, [rows, D]), v (fp64 [B, n_kv, D]), win (int64 [B, n_needle, H]: winning ROW), tie_sets[b][h][k - 1], want /
+    add / want_add (bf16 [B n_q, D])."""
+    g = torch.Generator().manual_seed(seed)
+    c = MxCase()
+    H, B, D = heads, batch, heads * 128
+    if n_tie is None:
+        n_tie = 12 if n_q >= 36 else n_q // 4
+    nn = n_q - n_tie
+    c.n_q, c.n_kv, c.H, c.B, c.D, c.mode, c.n_tie, c.n_needle = n_q, n_kv, H, B, D, mode, n_tie, nn
+    c.npad = pad64(n_kv)
+    c.ldq8, c.ldk8 = D + gap_q, D + gap_k
+    nt = c.npad // 64
+    extra_q, extra_k = 256 * B, 64 * B + 64
+    sizes = _mx_tie_sizes(n_kv)
+
+    qv = torch.zeros(B, n_q, H, 128, dtype=torch.float64)
+    kv = torch.zeros(B * n_kv + extra_k, H, 128, dtype=torch.float64)
+    c.win = torch.empty(B, nn, H, dtype=torch.int64)
+    c.labels, c.tie_sets = [], []
+    for b in range(B):
+        if mode == "far":
+            assert 128 <= n_kv <= 64 + 255 * 64
+            labels = torch.cat([255 * 64 + torch.arange(64), torch.arange(n_kv - 64)])
+            win = 64 + torch.randint(0, 64, (nn, H), generator=g)
+        else:
+            labels = torch.randperm(n_kv, generator=g)
+            if mode == "tile0":
+                win = winners_for(nn, min(n_kv, 64), H, g, must=(0, 63))
+            else:
+                win = winners_for(nn, n_kv, H, g, must=edge_keys(n_kv))
+                if mode == "mixed":
+                    assert n_kv > 64
+                    even = (torch.arange(nn) % 2 == 0)[:, None]
+                    win = torch.where(even, win % 64, 64 + win % (n_kv - 64))
+        c.labels.append(labels)
+        c.win[b] = win
+        kb = kv[b * n_kv:(b + 1) * n_kv]
+        dg = mx_key_digits(labels)                                     # [n_kv, 7]
+        kb[:, :, 0:3 * MX_DIGITS:3] = dg[:, None, :]
+        kb[:, :, 1:3 * MX_DIGITS:3] = (dg * dg)[:, None, :]
+        kb[:, :, 2:3 * MX_DIGITS:3] = 1.0
+        kb[:, :, LEAK_DIM + b % 3] = 1.0
+        for (d0, d1) in MX_BAL:
+            u = torch.randint(1, 15, (n_kv, H), generator=g).double()
+            kb[:, :, d0] = u
+            kb[:, :, d1] = u
+        sets = []
+        for h in range(H):
+            per_k = []
+            for ki, m in enumerate(sizes):
+                t = torch.cat([torch.randperm(n_kv - 1, generator=g)[:m - 1], torch.tensor([n_kv - 1])])
+                kb[:, h, MX_TIE_DIM + ki] = 1.0
+                kb[t, h, MX_TIE_DIM + ki] = 0.0
+                per_k.append(t)
+            sets.append(per_k)
+        c.tie_sets.append(sets)
+        a = mx_key_digits(labels[win.reshape(-1)]).view(nn, H, MX_DIGITS)
+        qb = qv[b]
+        qb[:nn, :, 0:3 * MX_DIGITS:3] = 2.0 * MX_C * a
+        qb[:nn, :, 1:3 * MX_DIGITS:3] = -MX_C
+        qb[:nn, :, 2:3 * MX_DIGITS:3] = -MX_C * a * a
+        for i in range(n_tie):
+            qb[nn + i, :, MX_TIE_DIM + i % 3] = -MX_TIE_C
+        for (d0, d1) in MX_BAL:
+            qb[:, :, d0] = MX_G
+            qb[:, :, d1] = -MX_G
+        if B > 1:
+            for nb in {(b + 1) % 3, (b - 1) % 3} - {b % 3}:
+                qb[:, :, LEAK_DIM + nb] = MX_BIG
+        qb[:, :, INVALID_DIM] = MX_BIG
+    tail = kv[B * n_kv:]                                               # rows nobody may read: flagged, otherwise ordinary keys
+    dg = mx_key_digits(torch.arange(extra_k))
+    tail[:, :, 0:3 * MX_DIGITS:3] = dg[:, None, :]
+    tail[:, :, 1:3 * MX_DIGITS:3] = (dg * dg)[:, None, :]
+    tail[:, :, 2:3 * MX_DIGITS:3] = 1.0
+    for (d0, d1) in MX_BAL:
+        tail[:, :, d0] = 1.0
+        tail[:, :, d1] = 1.0
+    tail[:, :, INVALID_DIM] = 1.0
+    qall = qv.view(B * n_q, D)
+    behind = qall.roll(B * n_q // 2 + 1, 0)
+    qall = torch.cat([qall] + [behind] * ((extra_q + B * n_q - 1) // (B * n_q)))[:B * n_q + extra_q]
+    c.q, c.k = qall, kv.view(-1, D)
+    qb8, c.sq = mx_pack(c.q, g)
+    kb8, c.sk = mx_pack(c.k, g)
+    c.q8 = torch.full((c.q.shape[0], c.ldq8), MX_GAP_BYTE, dtype=torch.uint8)
+    c.q8[:, :D] = qb8
+    c.k8 = torch.full((c.k.shape[0], c.ldk8), MX_GAP_BYTE, dtype=torch.uint8)
+    c.k8[:, :D] = kb8
+
+    nblk = c.npad // 32
+    sign = torch.randint(0, 2, (B, n_kv, D), generator=g).double() * 2 - 1
+    colsign = torch.randint(0, 2, (D,), generator=g).double() * 2 - 1
+    for b in range(B):                                                 # one sign per column on the keys of a tie set: no mean cancels to (near) zero
+        for h in range(H):
+            for t in c.tie_sets[b][h]:
+                sign[b, t, h * 128:(h + 1) * 128] = colsign[h * 128:(h + 1) * 128]
+    n = torch.randint(8, 15, (B, n_kv, D), generator=g).double() * sign
+    e = torch.randint(-1, 3, (B, nblk, D), generator=g).double()
+    c.v = n * torch.exp2(e).repeat_interleave(32, dim=1)[:, :n_kv]
+    vt = torch.zeros(B, H, 128, c.npad, dtype=torch.float64)           # key order, zero padding
+    vt[..., :n_kv] = c.v.view(B, n_kv, H, 128).permute(0, 2, 3, 1)
+    vb8, vs8 = mx_pack(vt, g)                                          # [B, H, 128, npad], [B, H, 128, npad / 32]
+    pos = torch.arange(c.npad)
+    key_at = pos // 64 * 64 + MX_KEY_OF_POS[pos % 64]
+    c.v8t = torch.full((B + 1, H, 128, c.npad), MX_GAP_BYTE, dtype=torch.uint8)
+    c.v8t[:B] = vb8[..., key_at]
+    c.sv = torch.full((B + 1, H, nt, 128, 2), 130, dtype=torch.uint8)
+    c.sv[:B] = vs8.view(B, H, 128, nt, 2).permute(0, 1, 3, 2, 4)
+
+    want = torch.empty(B, n_q, D, dtype=torch.float64)
+    for b in range(B):
+        want[b, :nn] = _gather_rows(c.v[b], c.win[b], H)
+        for i in range(n_tie):
+            for h in range(H):
+                t = c.tie_sets[b][h][i % 3]
+                want[b, nn + i, h * 128:(h + 1) * 128] = c.v[b][t, h * 128:(h + 1) * 128].sum(0) / len(t)
+    c.want = bf16_rne(want.view(B * n_q, D))
+    mag = 100.0 + torch.randint(0, 56, (B * n_q, D), generator=g).double() / 2
+    c.add = (mag * (torch.randint(0, 2, (B * n_q, D), generator=g).double() * 2 - 1)).to(BF)
+    c.want_add = (c.want.float() + c.add.float()).to(BF)
+    return c
+
+
+def mx_margins(c: MxCase):
+    """(lead, forbidden lead, tie gap) in octaves (the exp2 domain of the kernel), from the de-quantised buffers: needle rows - the winner's
+    score (asserted to be exactly 0) minus the best other key's of the sample, and the worst forbidden row's score minus the winner's; tie rows
+    - the set scores exactly 0 (asserted), and the gap to the best other key of the sample.  Forbidden: every other row of the K buffer, except
+    the samples b +- 3, +- 6 ... that the bonus dims cannot tell from b (their row order and V differ)."""
+    lead, forb, gap = math.inf, math.inf, math.inf
+    kh = c.k.view(-1, c.H, 128).transpose(0, 1)
+    for b in range(c.B):
+        qh = c.q[b * c.n_q:(b + 1) * c.n_q].view(c.n_q, c.H, 128).transpose(0, 1)
+        s = qh @ kh.transpose(1, 2)                                     # [H, n_q, rows]
+        own = s[:, :, b * c.n_kv:(b + 1) * c.n_kv]
+        keep = torch.ones(s.shape[-1], dtype=torch.bool)
+        for o in range(c.B):
+            if o == b or (o - b) % 3 == 0:
+                keep[o * c.n_kv:(o + 1) * c.n_kv] = False
+        if keep.any():
+            forb = min(forb, s[:, :, keep].amin().item())
+        wi = c.win[b].t().unsqueeze(-1)
+        sw = own[:, :c.n_needle].gather(-1, wi)
+        assert not sw.any(), "a winner's score is not exactly 0"
+        if c.n_kv > 1 and c.n_needle:
+            lead = min(lead, -own[:, :c.n_needle].scatter(-1, wi, -math.inf).amax().item())
+        for i in range(c.n_tie):
+            for h in range(c.H):
+                t = c.tie_sets[b][h][i % 3]
+                row = own[h, c.n_needle + i].clone()
+                assert not row[t].any(), "a tie key does not score exactly 0"
+                row[t] = -math.inf
+                if len(t) < c.n_kv:
+                    gap = min(gap, -row.max().item())
+    return lead, forb, gap
+
+
+MX_MISTAKES = ("neighbour sample's K rows", "neighbour sample's V^T", "neighbour head's sq dword", "neighbour head's sk dword",
+               "sv of the other 32-key half", "sv of the neighbouring tile", "key order inside a tile unpermuted", "no tail mask",
+               "tail mask at Nkv-1", "Nkv rounded up to npad", "row stride D", "head and query block swapped", "remainder block of the wrong sample",
+               "neighbour sample's add rows")
+_MX_ORDER_MISTAKES = ("head and query block swapped", "remainder block of the wrong sample", "neighbour sample's add rows")
+
+
+def mx_mistake_applies(mistake: str, n_q: int, n_kv: int, heads: int, batch: int, mode: str = "perm", gap_q: int = 16, gap_k: int = 32) -> bool:
+    """Whether a launch of this shape can tell `mistake` from the right index at all (one key: the softmax is 1 whatever the score; mode "tile0":
+    no row wins or ties at the last key, so only a key past it that is READ shows)."""
+    nqb_full, hx = n_q // 256, heads // 8
+    last = mode != "tile0"
+    return {"neighbour sample's K rows": batch > 1, "neighbour sample's V^T": batch > 1, "neighbour sample's add rows": batch > 1,
+            "neighbour head's sq dword": heads > 1 and n_kv > 1, "neighbour head's sk dword": heads > 1 and n_kv > 1, "sv of the other 32-key half": True,
+            "sv of the neighbouring tile": n_kv > 64, "key order inside a tile unpermuted": n_kv > 4, "no tail mask": n_kv % 64 != 0 and last,
+            "tail mask at Nkv-1": n_kv > 1 and last, "Nkv rounded up to npad": n_kv % 64 != 0, "row stride D": (gap_q > 0 or gap_k > 0) and n_kv > 1,
+            "head and query block swapped": heads % 8 == 0 and nqb_full >= 1 and nqb_full != hx,
+            "remainder block of the wrong sample": heads % 8 == 0 and batch > 1 and n_q % 256 != 0}[mistake]
+
+
+def mx_work_items(n_q: int, heads: int, batch: int, mistake=None):
+    """(sample, head, query block) of every work item in the order of the persistent kernel: with H % 8 == 0 item -> (xcd, local), every xcd takes
+    its heads' full 256-row blocks first, sample by sample, and the remainder blocks last; otherwise sample-major, head, block.
+    "head and query block swapped": quotient and remainder of the full-block index used for one another; "remainder block of the wrong sample":
+    the remainder index divided by H in place of H / 8."""
+    nqb, nqb_full = (n_q + 255) // 256, n_q // 256
+    out = []
+    for item in range(nqb * heads * batch):
+        if heads % 8 == 0:
+            xcd, local, hx = item & 7, item >> 3, heads >> 3
+            full = batch * hx * nqb_full
+            if local < full:
+                bz, r = local // (hx * nqb_full), local % (hx * nqb_full)
+                hq, qb = r // nqb_full, r % nqb_full
+                if mistake == "head and query block swapped":
+                    hq, qb = qb, hq
+                head = xcd + 8 * hq
+            else:
+                l2 = local - full
+                bz = l2 // heads if mistake == "remainder block of the wrong sample" else l2 // hx
+                head, qb = xcd + 8 * (l2 % hx), nqb_full
+        else:
+            bz, r = item // (nqb * heads), item % (nqb * heads)
+            head, qb = r // nqb, r % nqb
+        out.append((bz, head, qb))
+    return out
+
+
+def _mx_head_f64(c: MxCase, bz: int, head: int, m) -> torch.Tensor:
+    """fp64 [n_q, 128]: the attention of one (sample, head) from the flat byte buffers, every address written out as the kernel derives it."""
+    H, B, nq, nkv, npad, D = c.H, c.B, c.n_q, c.n_kv, c.npad, c.D
+    D32, nt = D // 32, npad // 64
+    ldq, ldk = (D, D) if m == "row stride D" else (c.ldq8, c.ldk8)
+    d = torch.arange(128)
+    rq = (bz * nq + torch.arange(nq))[:, None]
+    hq = (head + 1) % H if m == "neighbour head's sq dword" else head
+    q = E4M3_LUT[c.q8.reshape(-1)[rq * ldq + head * 128 + d].long()] * torch.exp2(c.sq.reshape(-1)[rq * D32 + hq * 4 + d // 32].double() - 127.0)
+    bk = (bz + 1) % B if m == "neighbour sample's K rows" else bz
+    if m == "no tail mask":           # the ragged tile's clamped rows counted: the last key once more for every padding position
+        j = torch.arange(npad)
+        rk = bk * nkv + j.clamp(max=nkv - 1)
+    elif m == "Nkv rounded up to npad":
+        j = torch.arange(npad)
+        rk = bk * nkv + j
+    else:
+        j = torch.arange(nkv - 1 if m == "tail mask at Nkv-1" else nkv)
+        rk = bk * nkv + j
+    rk = rk[:, None]
+    hk = (head + 1) % H if m == "neighbour head's sk dword" else head
+    k = E4M3_LUT[c.k8.reshape(-1)[rk * ldk + head * 128 + d].long()] * torch.exp2(c.sk.reshape(-1)[rk * D32 + hk * 4 + d // 32].double() - 127.0)
+    bv = (bz + 1) % B if m == "neighbour sample's V^T" else bz
+    t, kk = j // 64, j % 64
+    pos = kk if m == "key order inside a tile unpermuted" else MX_POS_OF_KEY[kk]
+    beta = 1 - kk // 32 if m == "sv of the other 32-key half" else kk // 32
+    ts = (t + 1) % nt if m == "sv of the neighbouring tile" else t
+    v = E4M3_LUT[c.v8t.reshape(-1)[((bv * H + head) * 128 + d[None, :]) * npad + (t * 64 + pos)[:, None]].long()]
+    v = v * torch.exp2(c.sv.reshape(-1)[(((bv * H + head) * nt + ts[:, None]) * 128 + d[None, :]) * 2 + beta[:, None]].double() - 127.0)
+    s = q @ k.t()
+    p = torch.exp2(s - s.amax(-1, keepdim=True))
+    return (p @ v) / p.sum(-1, keepdim=True)
+
+
+def mxfp8_attention_f64(c: MxCase, mistake=None, add: bool = False, cache=None) -> torch.Tensor:
+    """The attention of the entry points' contract on the PACKED buffers of `c`, plain fp64 (the scores are already in the exp2 domain), walked
+    item by item in the kernel's work order, with the single rounding to bf16 at the end (add: bf16(bf16(o) + add row) after it).  Rows that no
+    item writes stay NaN.  `mistake` (one of MX_MISTAKES): the same with one deliberately wrong index.  cache: a dict shared between calls on
+    one case (the per-head results of the unmistaken loads serve every work-order mistake)."""
+    assert mistake is None or mistake in MX_MISTAKES
+    load_m = None if mistake in _MX_ORDER_MISTAKES else mistake
+    cache = {} if cache is None else cache
+    out = torch.full((c.B, c.n_q, c.D), math.nan, dtype=torch.float64)
+    for bz, head, qb in mx_work_items(c.n_q, c.H, c.B, mistake):
+        if not (0 <= bz < c.B and 0 <= head < c.H and qb * 256 < c.n_q):
+            continue  # (a kernel with this mistake reads and writes past its operands here; the rows it should have written stay NaN)
+        key = (load_m, bz, head)
+        if key not in cache:
+            cache[key] = _mx_head_f64(c, bz, head, load_m)
+        out[bz, qb * 256:(qb + 1) * 256, head * 128:(head + 1) * 128] = cache[key][qb * 256:(qb + 1) * 256]
+    o = out.view(c.B * c.n_q, c.D).float().to(BF)
+    if add:
+        a = c.add.view(c.B, c.n_q, c.D).roll(-1, 0).reshape(c.B * c.n_q, c.D) if mistake == "neighbour sample's add rows" else c.add
+        o = (o.float() + a.float()).to(BF)
+    return o
+
+
+# The launches of tests/test_exact_attention_mxfp8_gpu.py, proven on the CPU in tests/test_exact_constructions.py: (n_q, n_kv, H, B, mode, n_tie).
+# n_q: no full 256-row block, exactly one, one or two plus a remainder; n_kv: 1, 2, 3, 5 and 11 tiles, ragged and full, one key; H: both work
+# orders, one and two heads per xcd; the last one has more work items than the persistent form has workgroups by default (2 * 16 * 17 = 544).
+MX_CASES = {
+    "q31-k1-h2-b1": (31, 1, 2, 1, "perm", None),
+    "q31-k31-h3-b3": (31, 31, 3, 3, "perm", None),
+    "q256-k64-h5-b2": (256, 64, 5, 2, "perm", None),
+    "q300-k65-h8-b2": (300, 65, 8, 2, "perm", None),
+    "q300-k130-h16-b3": (300, 130, 16, 3, "perm", None),
+    "q556-k257-h8-b2": (556, 257, 8, 2, "perm", None),
+    "q556-k700-h2-b1": (556, 700, 2, 1, "perm", None),
+    "q300-k700-h3-b3": (300, 700, 3, 3, "perm", None),
+    "q300-k257-h5-b3-mixed": (300, 257, 5, 3, "mixed", None),
+    "q300-k130-h2-b1-far": (300, 130, 2, 1, "far", None),
+    "q256-k130-h16-b1-tile0": (256, 130, 16, 1, "tile0", 0),
+    "q257-k70-h16-b17": (257, 70, 16, 17, "perm", None),
+}
+_mx_cases = {}
+
+
+def mx_named_case(name: str) -> MxCase:
+    """The case MX_CASES[name], built once per process and never modified."""
+    if name not in _mx_cases:
+        n_q, n_kv, H, B, mode, n_tie = MX_CASES[name]
+        _mx_cases[name] = mx_case(n_q, n_kv, H, B, seed=1000 + len(name) + n_q + n_kv, mode=mode, n_tie=n_tie)
+    return _mx_cases[name]

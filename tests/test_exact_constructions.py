@@ -5,7 +5,11 @@ changed element wherever it sits.
 
 The row / scheduler / softmax recipes (`unit_rows`, `rope_table`, `unipc_state`, `tie_targets`, ...): fp32 evaluation in a scrambled order
 equals the fp64 answer bit for bit (exactness), the asserted share of results needs a real bf16 rounding, and the reference evaluated with
-one deliberately wrong index differs from the right one in every affected row (sensitivity: the data can see that bug)."""
+one deliberately wrong index differs from the right one in every affected row (sensitivity: the data can see that bug).
+
+The MXFP8 attention cases (`mx_case`, every launch of tests/test_exact_attention_mxfp8_gpu.py): the bytes hold the intended values and the
+quantisation contract keeps them, the margins hold, the contract oracle returns the closed form under both offset schedules, and every entry
+of `MX_MISTAKES` is seen by the cases it applies to - and by one case at least."""
 import math
 
 import pytest
@@ -394,3 +398,148 @@ def test_far_first_tile_recipe_overflows_the_first_rescale_factor():
     assert lead.min() >= MIN_MARGIN_NATS and int(rows.min()) >= 64 and len(rows.unique()) > 20
     first = X.needle_scores(q, k[:64], 3).amax(-1) * X.LOG2E
     assert first.max().item() < -128 and torch.isinf(torch.exp2(-first.float())).all()
+
+
+# ---- MXFP8 attention: the cases of tests/test_exact_attention_mxfp8_gpu.py, every one of them ---------------------------------------------
+MX_NAMES = list(X.MX_CASES)
+LN2 = math.log(2.0)
+
+
+def _mx_heads(t, B, n, H):
+    """[>= B n, H 128] fp64 rows -> fp32 [B, H, n, 128], exactly."""
+    return X.exact_f64(t[:B * n]).view(B, n, H, 128).permute(0, 2, 1, 3)
+
+
+@pytest.mark.parametrize("name", MX_NAMES)
+def test_mx_case_bytes_hold_the_intended_values_and_the_contract_keeps_them(name):
+    """The bytes and scale bytes of q, k and V^T de-quantise to the recipe's values (V^T through the key order and the sv layout that
+    test_mxfp8_v_transpose_matches_contract states); `mx_quant` of those values returns them unchanged; block scales take all three
+    offsets from the canonical one; gap columns, spare blocks and the zero padding of V^T are in place."""
+    from oracle import dit_oracle as O
+    c = X.mx_named_case(name)
+    B, H, D, nkv, npad = c.B, c.H, c.D, c.n_kv, c.npad
+    for b8, s8, val, ld in ((c.q8, c.sq, c.q, c.ldq8), (c.k8, c.sk, c.k, c.ldk8)):
+        assert b8.shape[1] == ld > D and ld % 16 == 0 and bool((b8[:, D:] == X.MX_GAP_BYTE).all())
+        assert torch.equal(X.mx_unpack(b8[:, :D], s8), val)
+        assert torch.equal(O.mx_quant(X.exact_f64(val), -1).double(), val)
+        canon = torch.floor(torch.log2(val.view(val.shape[0], -1, 32).abs().amax(-1))) - 8 + 127
+        assert set((s8.double() - canon).unique().tolist()) == {0.0, 1.0, 2.0}
+    pos = torch.arange(npad)
+    key = pos // 64 * 64 + 32 * ((pos % 32) >> 4) + (pos % 32 & 3) + 8 * (((pos % 32) & 15) >> 2) + 4 * (pos % 64 // 32)  # key stored at position pos
+    vt = torch.zeros(B, H, 128, npad, dtype=torch.float64)
+    vt[..., key] = X.E4M3_LUT[c.v8t[:B].long()]
+    svk = c.sv[:B].permute(0, 1, 3, 2, 4).reshape(B, H, 128, npad // 32)
+    vt = vt * torch.exp2(svk.double() - 127.0).repeat_interleave(32, dim=-1)
+    vp = torch.zeros(B, H, npad, 128, dtype=torch.float64)
+    vp[:, :, :nkv] = c.v.view(B, nkv, H, 128).permute(0, 2, 1, 3)
+    assert torch.equal(vt, vp.permute(0, 1, 3, 2))
+    assert torch.equal(O.mx_quant(X.exact_f64(vp), 2).double(), vp)
+    assert not X.E4M3_LUT[c.v8t[:B].long()][..., key >= nkv].any(), "V^T padding columns are not zero"
+    assert bool((c.v8t[B:] == X.MX_GAP_BYTE).all()) and c.v.abs().min() >= 4.0
+    assert c.q8.shape[0] >= B * c.n_q + 256 * B and c.k8.shape[0] >= B * nkv + 64 * B + 64  # roomy: a stride of 256 nqb or npad stays inside
+    assert len(torch.unique(c.v.view(B * nkv, D), dim=0)) == B * nkv                       # no two keys share a V row
+    if nkv > 32:
+        e = svk.double()
+        assert (e[..., 0] != e[..., 1]).double().mean() > 0.5 and (e[:, 0] != e[:, 1]).double().mean() > 0.5  # beta / head neighbours differ
+
+
+@pytest.mark.parametrize("name", MX_NAMES)
+def test_mx_case_margins_winners_and_ties(name):
+    """Every winner scores exactly 0 and leads by >= 22 nats; every row nobody may read would win by as much; every tie set scores exactly 0 with
+    the rest of the sample 128 octaves behind; winners cover the edge keys and differ per head; the modes are what they say."""
+    c = X.mx_named_case(name)
+    lead, forb, gap = X.mx_margins(c)
+    assert min(lead, forb, gap) * LN2 >= MIN_MARGIN_NATS, (lead, forb, gap)
+    assert min(lead, gap) >= 64.0  # exp2(-64 + 3) rounds to 0 in e4m3 (half the smallest subnormal is 2^-10) and is far below an fp32 ulp of l
+    w = c.win
+    if c.mode == "perm":
+        must = [k for k in edge_keys(c.n_kv) if k < c.n_kv]
+        for b in range(c.B):
+            for h in range(c.H):
+                if len(must) <= c.n_needle:
+                    assert set(must) <= set(w[b, :, h].tolist()), (b, h)
+                tail = set(w[b, -min(len(must), c.n_needle):, h].tolist())
+                assert tail <= set(must)
+        if c.n_kv > 8:
+            assert not torch.equal(w[:, :, 0], w[:, :, 1])
+        assert c.n_tie > 0 and all(c.n_kv - 1 in t.tolist() for s in c.tie_sets for hs in s for t in hs)
+        assert [len(t) for t in c.tie_sets[0][0]] == [min(2 ** k, 2 ** (c.n_kv.bit_length() - 1)) for k in (1, 2, 3)]
+        if c.n_q % 256 > c.n_tie:  # the partial last query block holds needle rows and tie rows
+            assert c.n_q // 256 * 256 < c.n_needle < c.n_q
+    elif c.mode == "tile0":
+        assert int(w.max()) < 64 and c.n_tie == 0 and c.n_kv > 64
+    elif c.mode == "mixed":
+        grp = w[:, :c.n_needle // 32 * 32].reshape(c.B, -1, 32, c.H)
+        assert bool(((grp < 64).any(2) & (grp >= 64).any(2)).all())
+    elif c.mode == "far":
+        assert int(w.min()) >= 64
+        s0 = torch.einsum("qhd,khd->hqk", c.q[:c.n_q].view(c.n_q, c.H, 128), c.k[:64].view(64, c.H, 128))
+        assert s0[:, :c.n_needle].max().item() <= -2304.0
+
+
+@pytest.mark.parametrize("name", MX_NAMES)
+def test_mx_contract_oracle_returns_the_closed_form_under_both_offset_schedules(name):
+    """oracle.dit_oracle.attention_mxfp8's loop on the de-quantised operands (`attention_mxfp8_quantised`: no constant multiplied into q) gives
+    exactly the expected rows, with the lazy integer offset of the default kernel and with the running maximum of the plain loop."""
+    from oracle import dit_oracle as O
+    c = X.mx_named_case(name)
+    B, H = c.B, c.H
+    qq, kq, vq = _mx_heads(c.q, B, c.n_q, H), _mx_heads(c.k, B, c.n_kv, H), _mx_heads(c.v.view(B * c.n_kv, c.D), B, c.n_kv, H)
+    for lazy in (True, False):
+        o = O.attention_mxfp8_quantised(qq, kq, vq, lazy_offset=lazy).permute(0, 2, 1, 3).reshape(B * c.n_q, c.D)
+        assert_exact(o.to(BF), c.want, f"{name}: contract oracle, lazy_offset={lazy}")
+
+
+def test_mx_oracle_factoring_keeps_what_its_callers_get():
+    """`attention_mxfp8` is its quantisation front plus `attention_mxfp8_quantised`, in the input's dtype."""
+    from oracle import dit_oracle as O
+    g = torch.Generator().manual_seed(5)
+    q, k, v = (torch.randn(1, 2, 70, 128, generator=g).to(BF) for _ in range(3))
+    for lazy in (True, False):
+        got = O.attention_mxfp8(q, k, v, lazy_offset=lazy)
+        want = O.attention_mxfp8_quantised(O.mx_quant(q.float() * (128 ** -0.5 * 1.4426950408889634), -1), O.mx_quant(k, -1), O.mx_quant(v, 2), lazy)
+        assert got.dtype == BF and torch.equal(got, want.to(BF)) and want.dtype == torch.float32
+
+
+@pytest.mark.parametrize("name", MX_NAMES)
+def test_mx_f64_reference_equals_the_closed_form_and_sees_every_mistake_that_applies(name):
+    """`mxfp8_attention_f64` on the packed buffers, item by item in the kernel's work order, equals the expectation (plain and with `add`); with
+    any one entry of MX_MISTAKES that the shape can show, it does not."""
+    c = X.mx_named_case(name)
+    n_q, n_kv, H, B, mode = X.MX_CASES[name][:5]
+    cache = {}
+    assert_exact(X.mxfp8_attention_f64(c, cache=cache), c.want, name)
+    assert_exact(X.mxfp8_attention_f64(c, add=True, cache=cache), c.want_add, name + " add")
+    for m in X.MX_MISTAKES:
+        if X.mx_mistake_applies(m, n_q, n_kv, H, B, mode, c.ldq8 - c.D, c.ldk8 - c.D):
+            is_add = m == "neighbour sample's add rows"
+            wrong = X.mxfp8_attention_f64(c, mistake=m, add=is_add, cache=cache)
+            bad = X.mismatches(wrong, c.want_add if is_add else c.want)
+            assert bad.any(), f"{name}: the data cannot see '{m}'"
+            if m in ("neighbour head's sq dword", "neighbour head's sk dword"):
+                assert bad.any(1).double().mean() > 0.5, (m, bad.any(1).double().mean())  # most rows, not a lucky one
+
+
+def test_every_mx_mistake_is_seen_by_some_case():
+    seen = {m for m in X.MX_MISTAKES for (n_q, n_kv, H, B, mode, _) in X.MX_CASES.values() if X.mx_mistake_applies(m, n_q, n_kv, H, B, mode)}
+    assert seen == set(X.MX_MISTAKES), set(X.MX_MISTAKES) - seen
+    nq, nkv, H, B = X.MX_CASES["q257-k70-h16-b17"][:4]
+    assert len(X.mx_work_items(nq, H, B)) == (nq + 255) // 256 * H * B > 512
+    for (n_q, n_kv, H, B, _, _) in X.MX_CASES.values():  # the work order itself: every (sample, head, block) exactly once
+        items = X.mx_work_items(n_q, H, B)
+        assert sorted(items) == sorted((b, h, q) for b in range(B) for h in range(H) for q in range((n_q + 255) // 256))
+
+
+@pytest.mark.parametrize("name", MX_NAMES)
+def test_mx_add_and_quant_expectations(name):
+    """_add: bf16(bf16(o) + add) needs a real rounding on part of the elements and never comes near zero; _quant: the contract's bytes of the
+    expected bf16 rows hold the needle rows exactly (four significant bits, one block of 32 channels spans 2^-1 .. 2^2)."""
+    c = X.mx_named_case(name)
+    exact = c.want.double() + c.add.double()
+    rounded = (c.want_add.double() != exact).double().mean().item()
+    assert 0.02 < rounded < 0.9 and c.want_add.float().abs().min() >= 32.0, (rounded, c.want_add.float().abs().min())
+    s, q = _contract(c.want)
+    needle = torch.arange(c.B * c.n_q) % c.n_q < c.n_needle
+    assert torch.equal(_deq(q, s)[needle], c.want.float()[needle])
+    s2, q2 = _contract(c.want_add)
+    assert (_deq(q2, s2) - c.want_add.float()).abs().max() <= 8.0 and not torch.equal(q, q2)
