@@ -1159,6 +1159,82 @@ def components_masked(d: torch.Tensor, kept: torch.Tensor, out: Optional[torch.T
     return out
 
 
+# ---- one crop per group of stroke clusters (csrc/ce_clusters.hip) ---------------------------------------------------------
+CLUSTERS_ROWS = 256  # rows of the cluster table (CL_ROWS of csrc/ce_clusters.hip)
+
+
+def clusters_table_i32(roots: torch.Tensor, sums: torch.Tensor, kept: torch.Tensor, table: Optional[torch.Tensor] = None,
+                       counters: Optional[torch.Tensor] = None):
+    """roots, sums int32 [H, W], kept uint8 [H, W] -> (table int32 [256, 8], counters int32 [257]): one row per kept cluster in ascending
+    label order (label, left, top, right, bottom, pixels, weight, 0), rows at and after the count 0; counters[0] = the exact number of kept
+    clusters (the rest is scratch).  Neither needs initialisation; nothing is read back here."""
+    if roots.dim() != 2 or roots.numel() == 0:
+        raise ValueError(f"roots: need a non-empty [H, W] tensor, got shape {tuple(roots.shape)}")
+    H, W = roots.shape
+    _iplane(roots, "roots", (H, W)), _iplane(sums, "sums", (H, W)), _plane(kept, "kept")
+    if tuple(kept.shape) != (H, W):
+        raise ValueError(f"kept: need shape {(H, W)}, got {tuple(kept.shape)}")
+    if H * W >= 1 << 31:
+        raise ValueError(f"roots: need H * W < 2^31, got {H} x {W}")
+    if table is None:
+        table = torch.empty((CLUSTERS_ROWS, 8), dtype=torch.int32, device=roots.device)
+    if counters is None:
+        counters = torch.empty(1 + CLUSTERS_ROWS, dtype=torch.int32, device=roots.device)
+    _iplane(table, "table", (CLUSTERS_ROWS, 8)), _iplane(counters, "counters", (1 + CLUSTERS_ROWS,))
+    st = _prof_begin()
+    _check(lib().ce_clusters_table_i32(_ptr(roots), _ptr(sums), _ptr(kept), _ptr(table), _ptr(counters), CLUSTERS_ROWS, H, W, _stream()),
+           "ce_clusters_table_i32")
+    _prof_end(st, f"clusters_table_{H}x{W}", 10.0 * H * W)
+    return table, counters
+
+
+def clusters_select_u8(roots: torch.Tensor, kept: torch.Tensor, table: torch.Tensor, group_of_row: torch.Tensor, g: int,
+                       out: Optional[torch.Tensor] = None):
+    """-> a new uint8 [H, W]: 255 where kept is non-zero and the pixel's root is the label of a row i of `table` with group_of_row[i] == g
+    (int32 [256] on the device), else 0."""
+    if roots.dim() != 2 or roots.numel() == 0:
+        raise ValueError(f"roots: need a non-empty [H, W] tensor, got shape {tuple(roots.shape)}")
+    H, W = roots.shape
+    _iplane(roots, "roots", (H, W)), _plane(kept, "kept")
+    _iplane(table, "table", (CLUSTERS_ROWS, 8)), _iplane(group_of_row, "group_of_row", (CLUSTERS_ROWS,))
+    if tuple(kept.shape) != (H, W):
+        raise ValueError(f"kept: need shape {(H, W)}, got {tuple(kept.shape)}")
+    if isinstance(g, bool) or int(g) < 0:
+        raise ValueError(f"g: a group index >= 0, got {g!r}")
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.uint8, device=roots.device)
+    _plane(out, "out")
+    assert tuple(out.shape) == (H, W) and out.data_ptr() != kept.data_ptr()
+    st = _prof_begin()
+    _check(lib().ce_clusters_select_u8(_ptr(roots), _ptr(kept), _ptr(table), _ptr(group_of_row), int(g), _ptr(out), H, W, _stream()),
+           "ce_clusters_select_u8")
+    _prof_end(st, f"clusters_select_{H}x{W}", 6.0 * H * W)
+    return out
+
+
+def clusters_paste_u8(edit: torch.Tensor, mask: Optional[torch.Tensor], canvas: torch.Tensor, left: int, top: int):
+    """Image.paste(edit[f], (left, top), mask) into canvas[f] IN PLACE, for every frame: edit uint8 [F, bh, bw, 3], canvas uint8 [F, SH, SW, 3],
+    mask uint8 [SH, SW] at the photo's size or None (the whole box is replaced) -> canvas.  Only the box's bytes are touched."""
+    _dev(edit, torch.uint8, "edit"), _dev(canvas, torch.uint8, "canvas")
+    if edit.dim() != 4 or edit.shape[3] != 3 or not edit.is_contiguous() or edit.numel() == 0:
+        raise ValueError(f"edit: need a non-empty contiguous [F, bh, bw, 3] tensor, got shape {tuple(edit.shape)} stride {edit.stride()}")
+    if canvas.dim() != 4 or canvas.shape[3] != 3 or not canvas.is_contiguous() or canvas.shape[0] != edit.shape[0]:
+        raise ValueError(f"canvas: need a contiguous [{edit.shape[0]}, SH, SW, 3] tensor, got shape {tuple(canvas.shape)} stride {canvas.stride()}")
+    F, bh, bw, _ = edit.shape
+    _, SH, SW, _ = canvas.shape
+    if mask is not None:
+        _dev(mask, torch.uint8, "mask")
+        if tuple(mask.shape) != (SH, SW) or not mask.is_contiguous():
+            raise ValueError(f"mask: need a contiguous [{SH}, {SW}] tensor, got shape {tuple(mask.shape)} stride {mask.stride()}")
+    if left < 0 or top < 0 or left + bw > SW or top + bh > SH:
+        raise ValueError(f"the {bw}x{bh} box at ({left}, {top}) does not lie inside the {SW}x{SH} canvas")
+    assert canvas.data_ptr() != edit.data_ptr()
+    st = _prof_begin()
+    _check(lib().ce_clusters_paste_u8(_ptr(edit), _ptr(mask), _ptr(canvas), F, SH, SW, int(left), int(top), bw, bh, _stream()), "ce_clusters_paste_u8")
+    _prof_end(st, f"clusters_paste_{F}x{bh}x{bw}", 7.0 * F * bh * bw)
+    return canvas
+
+
 # ---- automatic edit regions (csrc/ce_region_auto.hip) ------------------------------------------------------------------
 def _f32c(t: torch.Tensor, name: str):
     _dev(t, torch.float32, name)

@@ -15,7 +15,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
-from . import auto_region as _ar, autofocus as _af, focus as _fc, image_io, lift as _lf, preview as _pv, region as _rg, sketch as _sk
+from . import auto_region as _ar, autofocus as _af, clusters as _cl, focus as _fc, image_io, lift as _lf, preview as _pv, region as _rg, sketch as _sk
 from .loop import (GraphedDenoiser, _capturable, _sharded_batchable, _shared_inputs, _token_sharded, _warmup_stream,  # noqa: F401
                    compact_text_context, denoise, denoise_step, make_cfg_inputs, text_compaction_plan, text_real_lengths)
 from .scheduler import FlowUniPCMultistepScheduler
@@ -92,6 +92,7 @@ class FocusPass:
     start: Optional[dict] = None  # the warm start {"step", "x0", "sigma"}: begin at that step on the scout's resampled estimate
     preview_tag: Optional[str] = None  # the "pass" entry of this pass's previews
     guarded: bool = False  # the text guardrail has seen the call's prompt already
+    crop_of: Optional[list] = None  # a sketch edit with several crops per photo: per plan (editor value, crop), chained into one video per value
 
 
 @dataclass
@@ -103,6 +104,7 @@ class EditSources:
     composite: bool = False  # paste the source back through the masks behind the decode
     auto_focus: Any = None  # the autofocus.AutoFocusConfig when this pass is a scout
     lift: Any = None  # the lift.LiftConfig while the detail lift is on (a focused pass only reports it)
+    crop_of: Optional[list] = None  # per focus plan (editor value, crop) when the crops of a value are chained into one video (clusters.paste)
 
 
 def _randn_tensor(shape, generator, device, dtype):
@@ -514,14 +516,14 @@ class ChronoEditPipeline:
         self._preview = None
         return self
 
-    def _preview_config(self, sample: int = 0, tag=None):
+    def _preview_config(self, sample: int = 0, tag=None, crop=None):
         """The preview.PreviewConfig of sample `sample` of this call (None: previews are off): the user's callback gets the loop's dict
-        with "sample" and "pass" added."""
+        with "sample" and "pass" added - and "crop" = (editor value, crop) when the sample is one crop of a sketch edit with several."""
         if self._preview is None:
             return None
         o = dict(self._preview)
         user = o["on_preview"]
-        o["on_preview"] = lambda d: user({**d, "sample": sample, "pass": tag})
+        o["on_preview"] = lambda d: user({**d, "sample": sample, "pass": tag, **({} if crop is None else {"crop": tuple(crop)})})
         if o["factors"] is None:
             if self.preview_factors is None:
                 raise ValueError("previews are enabled but preview_factors is None: fit_preview_factors(images), or enable_preview(factors=)")
@@ -677,7 +679,8 @@ class ChronoEditPipeline:
         return self
 
     # Sketch edits (chronoedit_amd/sketch.py): the region is where the editor's composite differs from its background.  Off by default
-    def enable_sketch_region(self, grow=0.02, feather=0.01, threshold: int = 0, context: float = 0.25, composite: bool = True, min_stroke=0):
+    def enable_sketch_region(self, grow=0.02, feather=0.01, threshold: int = 0, context: float = 0.25, composite: bool = True, min_stroke=0,
+                             max_crops: int = 1):
         """While on and no `set_edit_region` mask is set, `__call__(image=...)` also takes an image editor's value: a dict with PIL images
         under "background" (the photo) and "composite" (the photo with the strokes on it) - other keys, such as "layers", are ignored -, or
         a list of such dicts, one per prompt.  Per value the mask is built at the PHOTO's size before the first step (sketch.reference:
@@ -702,8 +705,25 @@ class ChronoEditPipeline:
         A dropped cluster's strokes are not pasted: there the frames carry the background, and "composite and background agree wherever
         the mask is below 255" holds outside the dropped clusters.  All clusters dropped (an int only): "empty", the plain call on the
         composite.  `sketch_report[i]` then also holds "min_stroke", "clusters" (kept), "dropped_clusters" and "dropped_pixels" (changed
-        pixels of the dropped clusters); `sketch_mask` applies the filter too."""
-        self._sketch_region = _sk.SketchConfig(grow, feather, threshold, context, composite, min_stroke)
+        pixels of the dropped clusters); `sketch_mask` applies the filter too.
+        max_crops (1: one box around every kept stroke, today's call bit for bit - same launches, same reads; an int in 1..16): with 2 or
+        more, every editor value is edited as up to `max_crops` focused crops, one per GROUP of stroke clusters, and still returns ONE video
+        at the photo's size (chronoedit_amd/clusters.py; csrc/ce_clusters.hip on the device, the same bytes).  The clusters' table - label,
+        bounding box, pixels, weight per kept cluster - rides on the one read; clusters whose crops would intersect are grouped, then the
+        groups whose union is smallest until at most `max_crops` are left (clusters.group: integers only); each group gets its own
+        feathered mask and its own box through the single-box call's route, at the price of ONE more read of five integers per group.  The
+        crops run as the samples of one focused call, one after the other - whatever composes with a focused region edit composes per
+        crop -, each from ITS VALUE's prompt, noise row (drawn as the single-box call draws it, then repeated) and `image_embeds` row; the
+        text encoder runs once per prompt, CLIP sees each crop.  Behind the decode the crops are pasted into the background in order
+        (PIL's paste, chained: clusters.host_paste).  `sketch_report[i]` keeps its keys, computed from the union mask - its "box" is what
+        the single-box call would have used - and gains "max_crops", "crops" (per crop that ran, in paste order: "box", "reason", "scale",
+        "mask_fraction_of_box", "clusters" (labels), "mask") and "crops_reason": "crops" (two or more crops ran), or the single-box call,
+        bit for bit, because of "single" (one group), "many" (more than 256 clusters) or "unfit" (some group's box is not "ok").
+        `focus_report` is the flat list of the plans that ran; previews carry "sample" = the flat crop index and "crop" = (value, crop).
+        output_type "latent" returns the crops' latents, flat.  `num_videos_per_prompt > 1` with a value of two or more crops is a
+        NotImplementedError.  How a checkpoint edits two crops of one photo consistently is the checkpoint's business; the default of 1
+        is a choice, not a measurement."""
+        self._sketch_region = _sk.SketchConfig(grow, feather, threshold, context, composite, min_stroke, max_crops)
         return self
 
     def disable_sketch_region(self):
@@ -720,6 +740,20 @@ class ChronoEditPipeline:
         device = self._execution_device
         e = _sk.masks(self._sketch_region, bgs, cps, device if image_io.on_device(self.device_image_io, device) else None)[0]
         return Image.fromarray(_sk.host_mask(e).numpy(), mode="L")  # (no edit follows: the copy of the mask may be made here)
+
+    def sketch_crops(self, background, composite, height: int, width: int) -> list:
+        """The crops a sketch call at width x height would run for this pair of PIL images with the enabled parameters, without running an
+        edit: a list of {"box", "reason", "scale", "mask_fraction_of_box", "clusters" (labels), "mask" (PIL "L", the photo's size)} in paste
+        order - `sketch_report[i]["crops"]`.  One entry (the single-box plan) with max_crops == 1 or when the call would fall back to it."""
+        if self._sketch_region is None:
+            raise ValueError("sketch_crops needs the parameters of enable_sketch_region(): the switch is off")
+        cfg = self._sketch_region
+        bgs, cps = _sk.editor_images({"background": background, "composite": composite})
+        device = self._execution_device
+        e = _sk.masks(cfg, bgs, cps, device if image_io.on_device(self.device_image_io, device) else None)[0]
+        single = _sk.focus_plan(e, width, height, cfg.context)
+        crops = _cl.plan(e, cfg.max_crops, width, height, cfg.context) if cfg.max_crops >= 2 else _cl.Crops("single")
+        return _cl.crop_reports(crops, single)
 
     # Guided detail lift (chronoedit_amd/lift.py): whole-image edits returned at the photo's size.  Off by default
     def enable_detail_lift(self, radius: int = 4, eps: float = 26.0, gate=(4.0, 12.0), max_gain: float = 8.0):
@@ -789,8 +823,11 @@ class ChronoEditPipeline:
         device = self._execution_device
         entries = _sk.masks(cfg, bgs, cps, device if image_io.on_device(self.device_image_io, device) else None)
         plans = [_sk.focus_plan(e, a.width, a.height, cfg.context) for e in entries]
+        crops = [_cl.plan(e, cfg.max_crops, a.width, a.height, cfg.context) for e in entries] if cfg.max_crops >= 2 else None
         if all(e["bbox"] is None for e in entries):  # no strokes anywhere: the plain call on the composite(s)
             out = self._edit(a)
+        elif crops is not None and any(c.reason == "crops" for c in crops):
+            out = self._sketch_crops_edit(a, cfg, plans, crops)
         else:
             out = self._edit(a, FocusPass(plans, cfg.composite))
         # behind the edit: the device path copies its masks to the host here, not in front of the first step
@@ -799,7 +836,47 @@ class ChronoEditPipeline:
         if cfg.min_stroke:
             for rep, e in zip(self.sketch_report, entries):
                 rep.update(min_stroke=cfg.min_stroke, clusters=e["clusters"], dropped_clusters=e["dropped_clusters"], dropped_pixels=e["dropped_pixels"])
+        if crops is not None:
+            for rep, p, c in zip(self.sketch_report, plans, crops):
+                rep.update(max_crops=cfg.max_crops, crops=_cl.crop_reports(c, p), crops_reason=c.reason)
         return out
+
+    def _sketch_crops_edit(self, a: CallArgs, cfg, plans: list, crops: list):
+        """The sketch edit in which some value has two or more crops: the flat list of crops - a value without them contributes its single-box
+        plan - runs as the samples of ONE focused pass, each from its value's rows of the embeds and of the noise; `_output` chains the
+        crops of a value into one video (clusters.paste)."""
+        if a.num_videos_per_prompt != 1:
+            raise NotImplementedError("a sketch edit with two or more crops per photo and num_videos_per_prompt > 1 is not implemented: "
+                                      "run the videos one call each, or enable_sketch_region(max_crops=1)")
+        a, device = self._begin(a, guarded=False)
+        n, prompt_embeds, negative_prompt_embeds = self._encode_text(a, device)  # the text encoder: once per prompt
+        if n != len(plans):
+            raise ValueError(f"a sketch edit with several crops per photo needs one prompt per editor value: got {n} prompt(s) for {len(plans)} value(s)")
+        flat, crop_of = [], []
+        for v, (p, c) in enumerate(zip(plans, crops)):
+            for g, q in enumerate(c.plans if c.reason == "crops" else [p]):
+                flat.append(q), crop_of.append((v, g))
+        rows = torch.tensor([v for v, _ in crop_of], dtype=torch.long)
+        repeat = lambda t: None if t is None else t.index_select(0, rows.to(t.device))
+        noise = a.latents
+        if noise is None:  # what the single-box call would draw: one row per value
+            if isinstance(a.generator, list) and len(a.generator) != n:
+                raise ValueError(f"You have passed a list of generators of length {len(a.generator)}, but requested an effective batch"
+                                 f" size of {n}. Make sure the batch size matches the length of the generators.")
+            T = (a.num_frames - 1) // self.vae_scale_factor_temporal + 1
+            shape = (n, self.vae.config.z_dim, T, a.height // self.vae_scale_factor_spatial, a.width // self.vae_scale_factor_spatial)
+            noise = _randn_tensor(shape, a.generator, device, torch.bfloat16)
+        elif noise.shape[0] != n:
+            raise ValueError(f"`latents` carry {noise.shape[0]} samples, expected one per editor value: {n}")
+        image_embeds = a.image_embeds
+        if image_embeds is not None:
+            if image_embeds.shape[0] not in (1, n, len(flat)):
+                raise ValueError(f"`image_embeds` carry {image_embeds.shape[0]} samples, expected 1, one per editor value ({n}) or one per crop ({len(flat)})")
+            if image_embeds.shape[0] == n:
+                image_embeds = repeat(image_embeds)
+        a = replace(a, image=[q.image for q in flat], prompt=None, negative_prompt=None, prompt_embeds=repeat(prompt_embeds),
+                    negative_prompt_embeds=repeat(negative_prompt_embeds), image_embeds=image_embeds, latents=repeat(noise), generator=None)
+        return self._edit(a, FocusPass(flat, cfg.composite, guarded=True, crop_of=crop_of))
 
     def _edit(self, a: CallArgs, fpass: Optional[FocusPass] = None):
         """The body of every call.  fpass: this is a focused pass somebody planned (a sketch edit, or the scout of an auto-focused call);
@@ -835,7 +912,7 @@ class ChronoEditPipeline:
             image_embeds = image_embeds.repeat(B // image_embeds.shape[0], 1, 1)
         latents = self._denoise_samples(a, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
                                         None if regions is None else [regions[image_of(b)][1] for b in range(B)], autos, start_step, start_eps,
-                                        fpass.preview_tag if fpass is not None else "scout" if what.auto_focus is not None else None)
+                                        fpass.preview_tag if fpass is not None else "scout" if what.auto_focus is not None else None, what.crop_of)
         if autos is not None and not autos[0].measure:
             self.auto_region_report = autos[0].report if B == 1 else [x.report for x in autos]
         if what.auto_focus is not None:
@@ -901,7 +978,7 @@ class ChronoEditPipeline:
         what = EditSources(pil=pil)
         self.focus_report = None
         if fpass is not None:  # (planned by the caller, the masks where they lie)
-            what.focus, what.composite = fpass.plans, fpass.composite
+            what.focus, what.composite, what.crop_of = fpass.plans, fpass.composite, fpass.crop_of
         elif self._edit_region is not None:
             masks, what.composite = self._edit_region
             if self._region_focus is not None:
@@ -984,8 +1061,9 @@ class ChronoEditPipeline:
         return [(m, _rg.RegionConfig(w=weights[id(m)], z_src=z_src[j:j + 1])) for j, m in enumerate(masks)], None
 
     def _denoise_samples(self, a: CallArgs, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds, regions, autos,
-                         start_step: int, start_eps, preview_tag) -> torch.Tensor:
-        """The loop, sample by sample (regions, autos: per sample, or None) -> the final latents of all of them."""
+                         start_step: int, start_eps, preview_tag, crop_of=None) -> torch.Tensor:
+        """The loop, sample by sample (regions, autos: per sample, or None; crop_of: per sample its (editor value, crop), or None) -> the
+        final latents of all of them."""
         # The engine denoises ONE edit at a time (its batch axis carries the guidance pair); B = batch_size * num_videos_per_prompt
         # edits (pipeline_chronoedit.py:493,631-637,676-691) run one after the other on the same weights - the reference's batched
         # loop computes the same per-sample arithmetic.  `callback_on_step_end` is then called per sample and step with that
@@ -1018,7 +1096,7 @@ class ChronoEditPipeline:
                                     graph_warm=self._graph_warm, region=None if regions is None else regions[b],
                                     auto_region=None if autos is None else autos[b], start_step=start_step,
                                     start_eps=None if start_eps is None else start_eps[b:b + 1],
-                                    preview=self._preview_config(b, preview_tag), **self._measure_kwargs()))
+                                    preview=self._preview_config(b, preview_tag, None if crop_of is None else crop_of[b]), **self._measure_kwargs()))
         return done[0] if len(done) == 1 else torch.cat(done, dim=0)
 
     def _composited(self, video: torch.Tensor, img: torch.Tensor, masks, image_of=lambda b: 0) -> List[torch.Tensor]:
@@ -1047,7 +1125,10 @@ class ChronoEditPipeline:
             if lifted is not None:
                 return lifted
         if what.focus is not None:  # the source-size paste replaces the edit-size composite
-            video = _fc.paste(video, what.focus, image_of, a.output_type, what.composite)
+            if what.crop_of is not None:  # the crops of an editor value, chained into one video
+                video = _cl.paste(video, what.focus, what.crop_of, a.output_type, what.composite)
+            else:
+                video = _fc.paste(video, what.focus, image_of, a.output_type, what.composite)
             if what.lift is not None:
                 self.lift_report = [_lf.report_entry(what.focus[image_of(b)].image.size, (a.width, a.height), "focus") for b in range(B)]
             return video

@@ -63,13 +63,15 @@ class SketchConfig:
     `set_edit_region`'s.  The defaults are choices, not measurements: a margin of 2 % of the photo around the strokes belongs to the
     model, a further 1 % (twice: the box mean spreads over 2 feather) fades into the photo, and a lossless editor changes no byte it was
     not asked to (a front end that re-encodes its composite needs a threshold above its codec's error).  min_stroke: 0 is off; an int >= 1
-    is the least number of changed pixels a cluster of strokes must hold, a float in (0, 1) that fraction of the heaviest cluster's."""
+    is the least number of changed pixels a cluster of strokes must hold, a float in (0, 1) that fraction of the heaviest cluster's.
+    max_crops: 1 is one box around every kept stroke; 2..16: up to that many crops, one per group of clusters (chronoedit_amd/clusters.py)."""
     grow: Union[int, float] = 0.02
     feather: Union[int, float] = 0.01
     threshold: int = 0
     context: float = 0.25
     composite: bool = True
     min_stroke: Union[int, float] = 0
+    max_crops: int = 1
 
     def __post_init__(self):
         object.__setattr__(self, "grow", _length(self.grow, "grow"))
@@ -80,6 +82,8 @@ class SketchConfig:
         if not isinstance(self.composite, bool):
             raise ValueError(f"sketch region: composite must be a bool, got {self.composite!r}")
         object.__setattr__(self, "min_stroke", _cc.check_min_weight(self.min_stroke, "sketch region: min_stroke", zero_is_off=True))
+        from .clusters import check_max_crops
+        check_max_crops(self.max_crops)
         _check_pixels(self.grow if isinstance(self.grow, int) else 0, self.feather if isinstance(self.feather, int) else 0)  # (fractions: at the call)
 
     def pixels(self, src_size: Tuple[int, int]) -> Tuple[int, int]:
@@ -193,21 +197,27 @@ def box(plane: torch.Tensor, radius: int, axis: int) -> torch.Tensor:
     return ((_window_sums(plane.to(torch.int32), int(radius), axis, True) * ww + (1 << 23)) >> 24).to(torch.uint8)
 
 
-def stages(background, composite, grow: int, feather: int, threshold: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """(changed, grown, mask), uint8 [SH, SW] each, where the images lie (two PIL images: on the host).  grow, feather in pixels.  A radius
-    of 0 runs no pass: with grow = feather = 0 the three are one tensor."""
-    grow, feather = int(grow), int(feather)
+def _grown(background, composite, grow: int, feather: int, threshold):
+    """The checks, then (changed, grown) where the images lie: what every chain below starts with."""
     _check_pixels(grow, feather)
     if isinstance(threshold, bool) or not 0 <= int(threshold) <= 254:
         raise ValueError(f"sketch: threshold must be an int in 0..254, got {threshold!r}")
     ch = changed(rgb_bytes(background), rgb_bytes(composite), int(threshold))
-    grown = ch
     if grow + feather:
-        grown = dilate(dilate(ch, grow + feather, 0), grow + feather, 1)
-    mask = grown
-    if feather:
-        mask = box(box(grown, feather, 0), feather, 1)
-    return ch, grown, mask
+        return ch, dilate(dilate(ch, grow + feather, 0), grow + feather, 1)
+    return ch, ch
+
+
+def _feathered(plane: torch.Tensor, feather: int) -> torch.Tensor:
+    return box(box(plane, feather, 0), feather, 1) if feather else plane
+
+
+def stages(background, composite, grow: int, feather: int, threshold: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(changed, grown, mask), uint8 [SH, SW] each, where the images lie (two PIL images: on the host).  grow, feather in pixels.  A radius
+    of 0 runs no pass: with grow = feather = 0 the three are one tensor."""
+    grow, feather = int(grow), int(feather)
+    ch, grown = _grown(background, composite, grow, feather, threshold)
+    return ch, grown, _feathered(grown, feather)
 
 
 def filtered_stages(background, composite, grow: int, feather: int, threshold: int = 0, min_stroke=1, scratch=None):
@@ -216,18 +226,20 @@ def filtered_stages(background, composite, grow: int, feather: int, threshold: i
     int32 [4] = (clusters kept, clusters dropped, changed pixels dropped, the heaviest cluster's changed pixels) where the images lie -
     nothing is read back.  scratch: components.filter's, on the device."""
     grow, feather = int(grow), int(feather)
-    _check_pixels(grow, feather)
-    if isinstance(threshold, bool) or not 0 <= int(threshold) <= 254:
-        raise ValueError(f"sketch: threshold must be an int in 0..254, got {threshold!r}")
-    ch = changed(rgb_bytes(background), rgb_bytes(composite), int(threshold))
-    grown = ch
-    if grow + feather:
-        grown = dilate(dilate(ch, grow + feather, 0), grow + feather, 1)
+    ch, grown = _grown(background, composite, grow, feather, threshold)
     kept, stats = _cc.filter(grown, min_stroke, ch, scratch)
-    m = kept
-    if feather:
-        m = box(box(kept, feather, 0), feather, 1)
-    return ch, grown, kept, m, stats
+    return ch, grown, kept, _feathered(kept, feather), stats
+
+
+def labelled_stages(background, composite, grow: int, feather: int, threshold: int = 0, min_stroke=0):
+    """`filtered_stages` that keeps its label planes, and labels with min_stroke == 0 too (kept = grown then, stats None) -> (changed, grown,
+    roots, sums, kept, mask, stats): what chronoedit_amd/clusters.py builds its table from.  The mask is `mask`'s, bit for bit."""
+    grow, feather = int(grow), int(feather)
+    ch, grown = _grown(background, composite, grow, feather, threshold)
+    roots = _cc.roots(grown)
+    sums = _cc.sums(roots, ch)
+    kept, stats = _cc.keep(grown, roots, sums, min_stroke) if min_stroke else (grown, None)
+    return ch, grown, roots, sums, kept, _feathered(kept, feather), stats
 
 
 def reference(background, composite, grow: int, feather: int, threshold: int = 0, min_stroke=0) -> torch.Tensor:
@@ -253,30 +265,37 @@ def masks(cfg: SketchConfig, bgs, cps, device=None) -> list:
     "grow_px", "feather_px", "bbox" (None: no strokes), "mask_pixels", "changed_pixels"} and, on the device path (device set), "bg_u8",
     "cp_u8", "mask_dev": each image uploaded once, two reductions and ONE read of their ten integers per value - nothing else comes back.
     With cfg.min_stroke the mask is the filtered chain's, the entry also holds "clusters", "dropped_clusters" and "dropped_pixels", and the
-    filter's four counters come back in the same read: fourteen integers ("changed_pixels" still counts every changed pixel)."""
+    filter's four counters come back in the same read: fourteen integers ("changed_pixels" still counts every changed pixel).
+    With cfg.max_crops >= 2 the labelling runs whatever min_stroke is (`labelled_stages`: the same mask), and the cluster table rides on that
+    read: the entry also holds "count" (kept clusters, exact), "rows" (the table on the host, a list of clusters.ROWS rows) and the planes
+    "roots", "kept" and "table" where they lie, for clusters.plan."""
     from . import autofocus as _af
+    from . import clusters as _cl
     from . import image_io
     out = []
     for bg, cp in zip(bgs, cps):
         g, f = cfg.pixels(bg.size)
         e = {"background": bg, "composite": cp, "grow_px": g, "feather_px": f}
+        planes = bg, cp
         if device is not None:
-            e["bg_u8"], e["cp_u8"] = image_io.upload_rgb(bg, device), image_io.upload_rgb(cp, device)
-            if cfg.min_stroke:
-                ch, _, _, m, stats = filtered_stages(e["bg_u8"], e["cp_u8"], g, f, cfg.threshold, cfg.min_stroke)
-                counts = torch.cat([_af.bbox_counts(m), _af.bbox_counts(ch), stats]).tolist()
-            else:
-                ch, _, m = stages(e["bg_u8"], e["cp_u8"], g, f, cfg.threshold)
-                counts = torch.cat([_af.bbox_counts(m), _af.bbox_counts(ch)]).tolist()
+            planes = e["bg_u8"], e["cp_u8"] = image_io.upload_rgb(bg, device), image_io.upload_rgb(cp, device)
+        stats, table = None, []
+        if cfg.max_crops >= 2:
+            ch, _, e["roots"], sm, e["kept"], m, stats = labelled_stages(*planes, g, f, cfg.threshold, cfg.min_stroke)
+            count, e["table"] = _cl.table(e["roots"], sm, e["kept"])
+            table = [count, e["table"].reshape(-1)]
+        elif cfg.min_stroke:
+            ch, _, _, m, stats = filtered_stages(*planes, g, f, cfg.threshold, cfg.min_stroke)
+        else:
+            ch, _, m = stages(*planes, g, f, cfg.threshold)
+        counts = torch.cat([_af.bbox_counts(m), _af.bbox_counts(ch)] + ([] if stats is None else [stats]) + table).tolist()  # the one read
+        if device is not None:
             e["mask_dev"], e["mask_u8"] = m, None
         else:
-            if cfg.min_stroke:
-                ch, _, _, m, stats = filtered_stages(bg, cp, g, f, cfg.threshold, cfg.min_stroke)
-                counts = _af.bbox_counts(m).tolist() + _af.bbox_counts(ch).tolist() + stats.tolist()
-            else:
-                ch, _, m = stages(bg, cp, g, f, cfg.threshold)
-                counts = _af.bbox_counts(m).tolist() + _af.bbox_counts(ch).tolist()
             e["mask_u8"] = m
+        if table:
+            n = len(counts) - 1 - 8 * _cl.ROWS
+            e["count"], e["rows"] = int(counts[n]), [counts[n + 1 + 8 * i:n + 9 + 8 * i] for i in range(_cl.ROWS)]
         e["bbox"] = tuple(int(v) for v in counts[:4]) if counts[4] else None
         e["mask_pixels"], e["changed_pixels"] = int(counts[4]), int(counts[9])
         if cfg.min_stroke:

@@ -717,6 +717,35 @@ int ce_components_keep_u8(const void* plane, const int* labels, const int* sums,
 int ce_components_seeds_f32(const float* d, const float* thr, void* seeds, int n, hipStream_t stream);
 int ce_components_masked_f32(const float* d, const void* kept, float* out, int n, hipStream_t stream);
 
+/* ---- sketch edits with one crop per group of stroke clusters (csrc/ce_clusters.hip; chronoedit_amd/clusters.py is the definition and every
+ * pass gives its bits).  labels / sums are ce_components_roots_i32's / ce_components_sums_i32's planes of the grown plane, kept the plane
+ * ce_components_keep_u8 left of it (or the grown plane itself).  Planes are [H][W], contiguous, H * W < 2^31 (otherwise -2); int32 planes
+ * and arrays 4-byte aligned (otherwise -3); byte planes at any address.  The table is int32 [256][8].
+ * ce_clusters_table_i32: one row per KEPT cluster - a root position p (labels[p] == p) with kept[p] != 0 - in ascending label order:
+ *   label, left, top, right, bottom (the half-open bounding box of the pixels with that label and a non-zero kept byte), their number,
+ *   sums[label], 0.  counters = int32 [1 + rows]: counters[0] <- the number of kept clusters, exact whatever it is; the rest is the call's
+ *   scratch.  Rows at and after the count are 0; with a count above `rows` the rows are unspecified (the first `rows` labels to arrive).
+ *   rows must be 256 (otherwise -1: a caller with another table in mind is refused, not written past).  A 4-byte memset and three
+ *   launches: the roots append their labels through counters[0]; one workgroup ranks them (row = the number of smaller labels) and
+ *   initialises every row; a pixel pass finds its row by binary search, reduces min / max / count per workgroup in the LDS and flushes
+ *   the rows it touched with atomicMin / atomicMax / atomicAdd.  `table` and `counters` need no initialisation and alias nothing.
+ * ce_clusters_select_u8: out[p] = 255 where kept[p] != 0 and labels[p] is the label of a row i of `table` (as the call above left it) with
+ *   group_of_row[i] == g, else 0.  group_of_row = int32 [256] in device memory; g >= 0.  Labels 16-byte, kept and out 4-byte aligned: four
+ *   pixels per lane, one 16-byte label load; otherwise element by element - the same bytes.  out aliases no input (otherwise -1).
+ * ce_clusters_paste_u8: Image.paste(edit[f], (left, top), mask) into canvas[f] IN PLACE, for every frame: edit = uint8 [F][bh][bw][3],
+ *   mask = uint8 [src_h][src_w] at the photo's size or NULL (= 255 everywhere), canvas = uint8 [F][src_h][src_w][3].  Only bytes of the box
+ *   [top, top + bh) x [left, left + bw) are touched, each reading and writing its own address, with ce_focus_paste_u8's arithmetic:
+ *   t = c * (255 - m) + e * m + 128, c = ((t >> 8) + t) >> 8; under m == 0 nothing is written.  A box that leaves the image returns -1;
+ *   F <= 65535; canvas aliases neither edit nor mask.  The first crop of a photo goes through ce_focus_paste_u8, which builds the canvas.
+ * No state, nothing allocated, no host read, no wait between workgroups, every loop bounded: every call is capturable.  Integers and integer
+ * atomics only: the results are exact and do not depend on the launch order. */
+int ce_clusters_table_i32(const int* labels, const int* sums, const void* kept, int* table, int* counters, int rows, int H, int W,
+                          hipStream_t stream);
+int ce_clusters_select_u8(const int* labels, const void* kept, const int* table, const int* group_of_row, int g, void* out, int H, int W,
+                          hipStream_t stream);
+int ce_clusters_paste_u8(const void* edit, const void* mask, void* canvas, int F, int src_h, int src_w, int left, int top, int bw, int bh,
+                         hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
