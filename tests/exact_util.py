@@ -12,6 +12,10 @@ away from zero).  Keys a kernel must not read
 MXFP8 attention (`mx_case`, `mxfp8_attention_f64`, `MX_MISTAKES`): the same idea on operands handed over as e4m3 bytes with E8M0 block
 scales - integer scores in the exp2 domain, every P a power of two or 0, needle rows and tie rows, scales that a wrong scale byte betrays.
 
+The fp8 mode's operand producers and GEMM tails (`row_fp8_ref`, `mx_contract`, `ln_mx_case`, `rms_mx_case`, `sat_gemm_case`, `bend_gemm_case`,
+`fp8_tail_plan`, `FP8_MISTAKES`): the per-row quantiser restated operation by operation, MX producers on rows that are known exactly, GEMM
+operands whose GELU input is exact and saturated (the FFN-up form's bytes need no transcendental), and the split-K plan restated.
+
 An ordinary module (not a conftest): the test files import it by name."""
 import math
 
@@ -1142,3 +1146,339 @@ def mx_named_case(name: str) -> MxCase:
         n_q, n_kv, H, B, mode, n_tie = MX_CASES[name]
         _mx_cases[name] = mx_case(n_q, n_kv, H, B, seed=1000 + len(name) + n_q + n_kv, mode=mode, n_tie=n_tie)
     return _mx_cases[name]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The fp8 mode's operand producers and GEMM tails (tests/test_exact_fp8_producers_gpu.py; CPU proofs in tests/test_exact_constructions.py)
+#
+# Row quantiser with one scale per row (quant_rows_fp8, ln_affine_fp8): `row_fp8_ref` is the kernel's documented arithmetic, one fp32 operation
+# per line - bits of the scale and every byte must agree.  Tier A (`fp8_pow2_rows`): rows of e4m3 values times 2^e with amax = 448 2^e, whose
+# scale is 2^e exactly and whose bytes dequantise to the input; tier B (`fp8_random_rows`): ordinary rows.
+# MX producers (ln_affine_mxfp8, rmsnorm_rope_mxfp8, the FFN-up epilogue): `mx_contract` on a row that is known exactly - `unit_rows` through
+# an affine whose 32-column blocks differ by octaves (`mx_affine_vectors`), or a GEMM whose GELU input is exact and lies where the
+# activation is x, -0 or 0 (`sat_gemm_case`).  `FP8_MISTAKES`: what each reference must be able to see on the data that is launched.
+# ------------------------------------------------------------------------------------------------------------------------------------
+F32_INV_448 = torch.ones((), dtype=torch.float32) / 448.0   # the constant 1.0f / 448.0f of the kernels (0x3b124925)
+SCALE_SENTINEL = 0xEE   # E8M0 byte no test data produces (2^111): what every scale byte a kernel must not write holds before the call
+BYTE_SENTINEL = 0x7F    # e4m3 NaN: what every element byte a kernel must not write holds before the call
+FP8_MISTAKES = ("scale byte of the neighbouring block", "W-order scale layout", "affine row of the wrong sample", "bias of column n+4",
+                "one slab fewer in the tail sum", "tail raster group 1", "post_scale ignored", "RoPE table row m")
+
+
+def row_fp8_ref(x: torch.Tensor):
+    """(s fp32 [M], e4m3 bytes [M, K]) of a bf16 / fp32 matrix under one scale per row, as ce_quant_rows_fp8 documents it, in fp32:
+    s = amax * float32(1 / 448) (1 for a zero row), inv = 1 / s (a correctly rounded division), bytes = RNE_e4m3(x * inv)."""
+    xf = x.float()
+    amax = xf.abs().amax(1)
+    s = torch.where(amax > 0, torch.mul(amax, F32_INV_448), torch.ones_like(amax))
+    inv = torch.div(torch.ones_like(s), s)
+    return s, torch.mul(xf, inv[:, None]).to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def fp8_pow2_rows(M: int, K: int, gen: torch.Generator):
+    """Tier A: (x bf16 [M, K], bytes uint8 [M, K], e int [M]): x = e4m3(bytes) * 2^e, e in -6..6 per row, every finite byte value allowed
+    (-0 and the subnormals among them) and one element per row at +-448 2^e, so that amax * float32(1 / 448) = 2^e exactly."""
+    b = torch.randint(0, 256, (M, K), generator=gen, dtype=torch.int64)
+    b[(b & 0x7F) == 0x7F] = 0x38                                    # (no NaN bytes: 1.0 in their place)
+    b[:, 0], b[:, 1] = 0x80, 0x01                                    # (-0 and the smallest subnormal in every row)
+    top = torch.where(torch.randint(0, 2, (M,), generator=gen) == 1, 0xFE, 0x7E)
+    b[torch.arange(M), torch.randint(2, K, (M,), generator=gen)] = top
+    e = torch.randint(-6, 7, (M,), generator=gen)
+    x64 = E4M3_LUT[b] * torch.exp2(e.double())[:, None]
+    x = x64.to(BF)
+    assert torch.equal(x.double(), x64)
+    return x, b.to(torch.uint8), e
+
+
+def fp8_random_rows(M: int, K: int, gen: torch.Generator) -> torch.Tensor:
+    """Tier B: ordinary rows (normal values, another magnitude per row); row 0 holds its maximum in the last 8-element chunk only, and the
+    last row (of two or more) is all zeros."""
+    x = torch.randn(M, K, generator=gen) * (0.05 + 3 * torch.rand(M, 1, generator=gen))
+    x[0, :K - 8] *= 2.0 ** -5
+    x[0, K - 8:] = torch.tensor([3.0, -40.0, 7.0, 0.5, -1.0, 33.0, 2.0, -9.0])
+    if M > 1:
+        x[M - 1] = 0
+    return x.to(BF)
+
+
+def mx_contract(x: torch.Tensor, saturating: bool = False):
+    """(E8M0 bytes [rows, K / 32], e4m3 bytes [rows, K]) of the MX contract for a bf16 / fp32 matrix: scale = 2^(floor(log2 amax) - 8), one step
+    up when amax / scale would exceed 448 unless `saturating` (the attention operands keep the floor rule and clip at 448: ce_common.h
+    mx_scale_byte / mx_scale_byte_nosat, oracle.dit_oracle.mx_quant), byte 1 (2^-126) for an all-zero block; elements RNE(x / scale) clamped
+    to +-448.  The exponent comes from frexp, not from a rounded log2."""
+    xf = x.float()
+    xb = xf.view(xf.shape[0], -1, 32)
+    amax = xb.abs().amax(-1)
+    e = torch.frexp(amax)[1].float() - 1.0 - 8.0
+    if not saturating:
+        e = e + (amax > 448.0 * torch.exp2(e)).float()
+    e = torch.where(amax > 0, torch.clamp(e, min=-126.0), torch.full_like(e, -126.0))
+    q = torch.clamp(xb / torch.exp2(e)[..., None], -448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8).reshape(xf.shape)
+    return (e + 127.0).to(torch.uint8), q
+
+
+def mx_scales_tiled(rows8: torch.Tensor, w_order: bool = False, fill: int = SCALE_SENTINEL) -> torch.Tensor:
+    """Scale bytes [R, K / 32] -> the flat tiled buffer of the MX GEMM operands (ce_common.h mx_gemm_scale_offset / mx_gemm_wscale_offset),
+    128 ceil(R / 128) rows long; the bytes of the rows past R hold `fill`."""
+    R, nb = rows8.shape
+    assert nb % 4 == 0
+    r, blk = torch.arange(R)[:, None], torch.arange(nb)[None, :]
+    inner = (r & 127) if w_order else (r & 15) * 8 + ((r >> 4) & 7)
+    off = ((r >> 7) * (nb // 4) + (blk >> 2)) * 512 + (blk & 3) * 128 + inner
+    out = torch.full(((R + 127) // 128 * (nb // 4) * 512,), fill, dtype=torch.uint8)
+    out[off.reshape(-1)] = rows8.reshape(-1)
+    return out
+
+
+def neighbour_block(rows8: torch.Tensor) -> torch.Tensor:
+    """Every scale byte replaced by the one of the next 32-column block of its row (the last by the first)."""
+    return rows8.roll(-1, 1)
+
+
+def scale_diversity(rows8: torch.Tensor) -> float:
+    """Share of (row, block) pairs whose scale byte differs from the next block's."""
+    return (rows8 != neighbour_block(rows8)).double().mean().item()
+
+
+def mx_affine_vectors(rows: int, D: int, gen: torch.Generator):
+    """`affine_vectors` with a and b of every 32-column block scaled by 2^e, e in -6..6 per (sample, block), and about one block in eight
+    at a = b = 0: neighbouring blocks of the output differ by octaves, and zero blocks (scale byte 1, zero bytes) occur."""
+    a, b = affine_vectors(rows, D, gen)
+    f = torch.exp2(torch.randint(-6, 7, (rows, D // 32), generator=gen).float())
+    keep = (torch.randint(0, 8, (rows, D // 32), generator=gen) != 0).repeat_interleave(32, dim=1)
+    f = f.repeat_interleave(32, dim=1)
+    return torch.where(keep, a * f, torch.zeros(())), torch.where(keep, b * f, torch.zeros(()))  # (+0 in the zero blocks)
+
+
+class Case:
+    """The operands of one launch (CPU) and what it must return."""
+
+
+_fp8_cases = {}
+
+
+def _cached(key, build):
+    if key not in _fp8_cases:
+        _fp8_cases[key] = build()
+    return _fp8_cases[key]
+
+
+LN_FP8_DS = (5120, 520)
+LN_MX_DS = (5120, 640)
+
+
+def ln_fp8_case(D: int, mistake=None) -> Case:
+    """ln_affine_fp8: 11 rows, one (a, b) per 3 rows (a sample boundary inside every block of four rows), ab_stride = D + 4.  want_s / want_q:
+    `row_fp8_ref` of the exactly known bf16 row."""
+    assert mistake in (None, "affine row of the wrong sample")
+    if mistake is None and ("ln_fp8", D) in _fp8_cases:
+        return _fp8_cases[("ln_fp8", D)]
+    g = torch.Generator().manual_seed(4100 + D)
+    c = Case()
+    c.M, c.D, c.ab_rows, c.S = 11, D, 3, 4
+    c.x, c.v = unit_rows(c.M, D, g)
+    c.a, c.b = affine_vectors(c.S, D, g)
+    sample = None if mistake is None else (torch.arange(c.M) + 1) // c.ab_rows
+    c.y = bf16_rne(ln_affine_exact(c.v, c.a, c.b, c.ab_rows, sample=sample))
+    c.want_s, c.want_q = row_fp8_ref(c.y)
+    if mistake is None:
+        _fp8_cases[("ln_fp8", D)] = c
+    return c
+
+
+def ln_mx_case(D: int, mistake=None) -> Case:
+    """ln_affine_mxfp8: 130 rows (two 128-row scale blocks, the second holding two rows), one `mx_affine_vectors` pair per 43 rows.  want_rows
+    (scale bytes [M, D / 32]), want_q, and want_s: the flat tiled scale buffer with SCALE_SENTINEL in the rows 130 .. 255."""
+    assert mistake in (None, "affine row of the wrong sample", "scale byte of the neighbouring block", "W-order scale layout")
+    if mistake is None and ("ln_mx", D) in _fp8_cases:
+        return _fp8_cases[("ln_mx", D)]
+    g = torch.Generator().manual_seed(4200 + D)
+    c = Case()
+    c.M, c.D, c.ab_rows, c.S = 130, D, 43, 4
+    c.x, c.v = unit_rows(c.M, D, g)
+    c.a, c.b = mx_affine_vectors(c.S, D, g)
+    sample = (torch.arange(c.M) + 1) // c.ab_rows if mistake == "affine row of the wrong sample" else None
+    c.y = bf16_rne(ln_affine_exact(c.v, c.a, c.b, c.ab_rows, sample=sample))
+    c.want_rows, c.want_q = mx_contract(c.y)
+    if mistake == "scale byte of the neighbouring block":
+        c.want_rows = neighbour_block(c.want_rows)
+    c.want_s = mx_scales_tiled(c.want_rows, w_order=mistake == "W-order scale layout")
+    if mistake is None:
+        _fp8_cases[("ln_mx", D)] = c
+    return c
+
+
+# (D, head_dim): the full-width form (one cos / sin entry per lane), and a narrow width whose heads do not divide 512 (an entry per chunk) and
+# whose last 16 lanes hold no chunk.  (D stays a multiple of 128: the kernel stores four scale bytes as one dword at row * D / 32.)
+RMS_MX_SHAPES = ((5120, 128), (384, 96))
+RMS_MX_M = 9
+
+
+def rms_mx_case(D: int, head_dim: int, R, post_scale: float, mistake=None) -> Case:
+    """rmsnorm_rope_mxfp8 on 9 rows: R = 9 (a table row per token), 3 (row m uses entry m % 3) or None (no RoPE).  want_rows / want_q: the
+    floor-rule contract (the attention operands') of float32(bf16 value) * float32(post_scale)."""
+    assert mistake in (None, "post_scale ignored", "RoPE table row m")
+    g = torch.Generator().manual_seed(4300 + D + (R or 0))
+    c = Case()
+    c.M, c.D, c.hd, c.R, c.post_scale = RMS_MX_M, D, head_dim, R, post_scale
+    c.x, c.v = unit_rows(c.M, D, g, centred=True)
+    c.w = rms_weights(D, g)
+    c.cs = rope_table(R, head_dim, g) if R else None
+    cs, table_row = c.cs, None
+    if mistake == "RoPE table row m" and R:
+        cs, table_row = torch.cat([c.cs, rope_table(c.M, head_dim, g)])[:max(c.M, R)], torch.arange(c.M)
+    c.t = rms_rope_exact(c.v, c.w, cs, head_dim, table_row=table_row)
+    ps = torch.tensor(1.0 if mistake == "post_scale ignored" else post_scale, dtype=torch.float32)
+    c.want_rows, c.want_q = mx_contract(torch.mul(c.t.float(), ps), saturating=True)
+    return c
+
+
+# ---- the split-K plan of the fp8 GEMMs, restated (ce_common.h ce_split_k, ce_gemm_fp8w4.hip fp8_split_k) ---------------------------------
+FP8_BM = FP8_BN = 256
+FP8_BK = 128
+FP8_GROUP = 4
+
+
+def ce_split_k(tail: int, kt: int, cus: int, slab_bytes: int, ws_bytes: int) -> int:
+    if tail <= 0:
+        return 1
+    for s in range(min(cus // tail, 8), 1, -1):
+        if kt % (2 * s) == 0 and tail * s * slab_bytes <= ws_bytes:
+            return s
+    return 1
+
+
+def fp8_split_k(tail: int, kt: int, cus: int, ws_bytes: int) -> int:
+    split = ce_split_k(tail, kt, cus, FP8_BM * FP8_BN * 4, ws_bytes)
+    if split == 1:
+        return 1
+    saving_us, slabs_us = (1.0 - 1.0 / split) * kt * 1.7, tail * split * 0.128 + 8.0
+    return 1 if saving_us < 1.5 * slabs_us else split
+
+
+def fp8_tail_plan(M: int, N: int, K: int, cus: int, ws_bytes: int):
+    """(tiles_m, tiles_n, t_full, tail, split) of a one-wave-per-SIMD fp8 launch: the `tail` tiles of the partially filled last round are cut
+    in `split` along K (tail = 0, split = 1: nothing is cut)."""
+    tiles_m, tiles_n = -(-M // FP8_BM), -(-N // FP8_BN)
+    nwg = tiles_m * tiles_n
+    tail = nwg % cus
+    split = fp8_split_k(tail, K // FP8_BK, cus, ws_bytes)
+    if split == 1:
+        tail = 0
+    return tiles_m, tiles_n, nwg - tail, tail, split
+
+
+def fp8_tile_origin(wg: int, tiles_m: int, tiles_n: int, group: int = FP8_GROUP):
+    """(m0, n0) of workgroup wg under the grouped raster of gemm_fp8_w4."""
+    group_sz = group * tiles_n
+    first_m = wg // group_sz * group
+    gm = min(tiles_m - first_m, group)
+    return (first_m + (wg % group_sz) % gm) * FP8_BM, (wg % group_sz) // gm * FP8_BN
+
+
+def fp8_tail_launch_f64(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, plan, mistake=None) -> torch.Tensor:
+    """fp64 acc + bias [M, N] of a launch, tile by tile as the plan lays it out: a full tile sums all of K; a tail tile is the sum of its `split`
+    K slabs, which the reduce kernel places at the origin it recomputes and completes with the bias of its own columns.  Elements that nothing
+    writes stay NaN.  `mistake`: "one slab fewer in the tail sum", "tail raster group 1" (the reduce kernel's origin under a raster group of 1)
+    or "bias of column n+4" (in the reduce kernel)."""
+    assert mistake in (None, "one slab fewer in the tail sum", "tail raster group 1", "bias of column n+4")
+    tiles_m, tiles_n, t_full, tail, split = plan
+    M, K = a.shape
+    N = w.shape[0]
+    ad, wd, bd = a.double(), w.double(), bias.double()
+    out = torch.full((tiles_m * FP8_BM, tiles_n * FP8_BN), math.nan, dtype=torch.float64)
+    ap = torch.zeros(tiles_m * FP8_BM, K, dtype=torch.float64)
+    wp = torch.zeros(tiles_n * FP8_BN, K, dtype=torch.float64)
+    bp = torch.zeros(tiles_n * FP8_BN, dtype=torch.float64)
+    ap[:M], wp[:N], bp[:N] = ad, wd, bd
+    for wg in range(tiles_m * tiles_n):
+        m0, n0 = fp8_tile_origin(wg, tiles_m, tiles_n)
+        md, nd, kk, b = m0, n0, K, bp
+        if wg >= t_full:
+            if mistake == "one slab fewer in the tail sum":
+                kk = K - K // split
+            elif mistake == "tail raster group 1":
+                md, nd = fp8_tile_origin(wg, tiles_m, tiles_n, group=1)
+            elif mistake == "bias of column n+4":
+                b = bp.roll(-4)
+        out[md:md + FP8_BM, nd:nd + FP8_BN] = ap[m0:m0 + FP8_BM, :kk] @ wp[n0:n0 + FP8_BN, :kk].t() + b[nd:nd + FP8_BN]
+    return out[:M, :N]
+
+
+# ---- GEMM data whose GELU input is exact and lies where the activation is x, -0 or 0 ------------------------------------------------------
+SAT_POS, SAT_NEG = 6.0, -12.0   # gelu_tanh in fp32 with the kernel's constants: x at x >= 6 after the bf16 rounding, -0 at x <= -12
+# (M, N, K): four tiles, all tail, cut in six, a ragged second row of tiles; one tile, no cut; 256 full tiles and 16 tail tiles cut in five
+SAT_SHAPES = ((300, 512, 13824), (129, 256, 256), (4352, 4096, 5120))
+SAT_CUT = {(300, 512, 13824): True, (129, 256, 256): False, (4352, 4096, 5120): True}
+
+
+def sat_gemm_case(M: int, N: int, K: int) -> Case:
+    """a bf16 [M, K]: integers 0..7 times 2^e per 32-element block, e in {e_row - 1, e_row}, e_row in -2..2 (an all-zero row, an all-zero block);
+    w bf16 [N, K]: integers 0..7 times 2^(oct - 3 - {0, 1} per block), signed by the CLASS of the output column - positive, negative or zero (a
+    zero W row); oct in 0..5 per 32 output columns; bias fp32 [N]: class sign times (16..48) 2^oct.  Every partial sum of an output element is an
+    integer below 14 * 14 * 13824 < 2^22 units, so fp32 holds acc + bias exactly in any order; positive columns give x >= 16, negative ones
+    x <= -16, zero columns 0.  Most 32-column blocks mix the three classes; one in eight, and the second, hold no positive column (all -0 / 0: scale byte 1)."""
+    def build():
+        g = torch.Generator().manual_seed(4400 + M + N + K)
+        c = Case()
+        c.M, c.N, c.K = M, N, K
+        ia = torch.randint(0, 8, (M, K), generator=g).float()
+        er = torch.randint(-2, 3, (M, 1), generator=g).float()
+        ea = er - torch.randint(0, 2, (M, K // 32), generator=g).float()
+        ia[min(2, M - 1)] = 0
+        ia[0, 32:64] = 0
+        c.a = (ia * torch.exp2(ea).repeat_interleave(32, dim=1)).to(BF)
+        cls = torch.randint(-1, 2, (N,), generator=g)                                # -1 negative, 0 zero, +1 positive
+        nopos = torch.randint(0, 8, (N // 32,), generator=g) == 0
+        nopos[1] = True
+        nopos = nopos.repeat_interleave(32)
+        cls = torch.where(nopos & (cls > 0), -cls, cls)
+        c.cls = cls
+        octv = torch.randint(0, 6, (N // 32,), generator=g).float().repeat_interleave(32)
+        iw = torch.randint(0, 8, (N, K), generator=g).float() * cls[:, None].float()
+        ew = octv[:, None] - 3.0 - torch.randint(0, 2, (N, K // 32), generator=g).float()
+        c.w = (iw * torch.exp2(ew).repeat_interleave(32, dim=1)).to(BF)
+        c.bias = cls.float() * torch.randint(16, 49, (N,), generator=g).float() * torch.exp2(octv)
+        c.unit = torch.exp2(er.double() - 1.0) * torch.exp2(octv.double() - 4.0)[None, :]   # [M, N]: every term of acc + bias is a multiple
+        return c
+    return _cached(("sat", M, N, K), build)
+
+
+def sat_gelu(x: torch.Tensor) -> torch.Tensor:
+    """bf16 GELU of inputs in {0} u [6, inf) u (-inf, -12], without a transcendental: x, -0 or 0.  Asserts the premise."""
+    xf = x.float()
+    assert bool(((xf == 0) | (xf >= SAT_POS) | (xf <= SAT_NEG)).all()), "saturated GELU recipe: an input lies in the activation's bend"
+    return torch.where(xf >= SAT_POS, xf, torch.where(xf <= SAT_NEG, torch.full_like(xf, -0.0), torch.zeros_like(xf))).to(BF)
+
+
+def mixed_block_share(y: torch.Tensor) -> float:
+    """Share of 32-column blocks of a `sat_gelu` result that hold a positive value, a -0 and a +0."""
+    yb = y.float().view(y.shape[0], -1, 32)
+    neg0 = (yb == 0) & torch.signbit(yb)
+    pos0 = (yb == 0) & ~torch.signbit(yb)
+    return ((yb > 0).any(-1) & neg0.any(-1) & pos0.any(-1)).double().mean().item()
+
+
+# ---- GEMM data whose GELU input spans the activation's bend ---------------------------------------------------------------------------------
+BEND_SHAPES = ((300, 520, 256), (300, 520, 13824))   # no cut; six tiles, all tail, cut in six
+BEND_CUT = {(300, 520, 256): False, (300, 520, 13824): True}
+
+
+def bend_gemm_case(M: int, N: int, K: int) -> Case:
+    """Integers in -7..7 (exact in e4m3) under one power-of-two scale per row: ia, iw (fp32 integers), sa = 2^{-1, 0}, sw = 2^{E - 1, E} with E
+    chosen so that the largest standard deviation of a sum, 18.7 sqrt(K) 2^E, is about 1.1; bias in units of 1/16 up to 1.  a, w: the bf16 values
+    (what the MX quantiser is fed).  Partial sums stay below 49 * 13824 < 2^20 units."""
+    def build():
+        g = torch.Generator().manual_seed(4500 + M + N + K)
+        c = Case()
+        c.M, c.N, c.K = M, N, K
+        E = -round(math.log2(18.7 * math.sqrt(K)))
+        c.ia = torch.randint(-7, 8, (M, K), generator=g).float()
+        c.iw = torch.randint(-7, 8, (N, K), generator=g).float()
+        c.ia[min(2, M - 1)] = 0
+        c.sa = torch.exp2(torch.randint(-1, 1, (M,), generator=g).float())
+        c.sw = torch.exp2(E - torch.randint(0, 2, (N,), generator=g).float())
+        c.a, c.w = (c.ia * c.sa[:, None]).to(BF), (c.iw * c.sw[:, None]).to(BF)
+        c.bias = int_vector(N, g, lo=-16, hi=16, e=-4)
+        return c
+    return _cached(("bend", M, N, K), build)

@@ -9,7 +9,12 @@ one deliberately wrong index differs from the right one in every affected row (s
 
 The MXFP8 attention cases (`mx_case`, every launch of tests/test_exact_attention_mxfp8_gpu.py): the bytes hold the intended values and the
 quantisation contract keeps them, the margins hold, the contract oracle returns the closed form under both offset schedules, and every entry
-of `MX_MISTAKES` is seen by the cases it applies to - and by one case at least."""
+of `MX_MISTAKES` is seen by the cases it applies to - and by one case at least.
+
+The fp8 producers and GEMM tails (every launch of tests/test_exact_fp8_producers_gpu.py): the per-row restatement is exact on power-of-two rows,
+`mx_contract` equals the contracts in use, sums are exact in fp32, GELU inputs lie in the saturated set (or span the bend), scale bytes differ
+between neighbouring blocks, the split-K plan returns the expected cuts on 256 compute units, and every entry of `FP8_MISTAKES` changes the
+expected output of the launch it belongs to."""
 import math
 
 import pytest
@@ -543,3 +548,225 @@ def test_mx_add_and_quant_expectations(name):
     assert torch.equal(_deq(q, s)[needle], c.want.float()[needle])
     s2, q2 = _contract(c.want_add)
     assert (_deq(q2, s2) - c.want_add.float()).abs().max() <= 8.0 and not torch.equal(q, q2)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The fp8 mode's operand producers and GEMM tails (tests/test_exact_fp8_producers_gpu.py): the premise of every recipe, and every entry of
+# X.FP8_MISTAKES seen by the reference on the data that is launched.
+# ------------------------------------------------------------------------------------------------------------------------------------
+FP8_ROW_KS = (5120, 13824, 264, 8)
+FP8_ROW_MS = (1, 7, 129)
+
+
+def test_row_fp8_restatement_is_exact_on_power_of_two_rows():
+    """448 2^e * float32(1 / 448) == 2^e for e in -6..6; on tier A rows the restatement returns 2^e, the bytes the row was built from, and they
+    dequantise to the input.  On ordinary rows the division form amax / 448 is another function: most scales differ in the last bit."""
+    e = torch.arange(-6, 7).float()
+    assert torch.equal(torch.mul(448.0 * torch.exp2(e), X.F32_INV_448), torch.exp2(e))
+    assert X.F32_INV_448.view(torch.int32).item() == 0x3B124925
+    for K in FP8_ROW_KS:
+        for M in FP8_ROW_MS:
+            x, b, ex = X.fp8_pow2_rows(M, K, torch.Generator().manual_seed(5000 + K + M))
+            s, q = X.row_fp8_ref(x)
+            assert torch.equal(s, torch.exp2(ex.float())) and torch.equal(q, b)
+            assert torch.equal(X.E4M3_LUT[q.long()] * s.double()[:, None], x.double())
+            assert bool((b[:, 0] == 0x80).all()) and bool((x[:, 0].float() == 0).all()) and bool(torch.signbit(x[:, 0].float()).all())
+    x = X.fp8_random_rows(129, 5120, torch.Generator().manual_seed(5100 + 5120 + 129))
+    s, q = X.row_fp8_ref(x)
+    amax = x.float().abs().amax(1)
+    assert amax[128] == 0 and s[128] == 1 and not q[128].any()                         # the all-zero row
+    assert x[0, :-8].float().abs().max() < x[0, -8:].float().abs().max() == 40.0       # the maximum in the last chunk only
+    s_div = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+    assert (s_div != s).double().mean() > 0.25
+    q_div = (x.float() / s_div[:, None]).to(torch.float8_e4m3fn).view(torch.uint8)
+    assert (q_div != q).any()                                                            # ... and some bytes with them
+
+
+def test_mx_contract_restatement_equals_the_contracts_in_use_and_the_tiled_order_inverts():
+    """`mx_contract` == the tests' `_contract` (non-saturating) and dequantises to oracle.dit_oracle.mx_quant (both rules) on launched data;
+    `mx_scales_tiled` is the inverse of ops.mx_scales_to_rows in both scale orders, sentinel rows included."""
+    from chronoedit_amd import ops
+    from oracle import dit_oracle as O
+    c = X.ln_mx_case(640)
+    r = X.rms_mx_case(384, 96, 3, ops.MXFP8_Q_SCALE)
+    for x in (c.y, mx_operand(40, 512, torch.Generator().manual_seed(3))):
+        s, q = X.mx_contract(x)
+        s0, q0 = _contract(x)
+        assert torch.equal(s, s0) and torch.equal(q, q0)
+        assert torch.equal(_deq(q, s), O.mx_quant(x.float(), -1, saturating=False))
+    xr = torch.mul(r.t.float(), torch.tensor(ops.MXFP8_Q_SCALE, dtype=torch.float32))
+    s, q = X.mx_contract(xr, saturating=True)
+    assert torch.equal(_deq(q, s), O.mx_quant(xr, -1)) and torch.equal(s, r.want_rows)
+    assert not torch.equal(X.mx_contract(xr, saturating=False)[0], s)                    # (this data tells the two scale rules apart)
+    for w_order in (False, True):
+        t = X.mx_scales_tiled(c.want_rows, w_order=w_order)
+        assert t.numel() == ops.mx_scale_bytes(c.M, c.D)
+        rows = ops.mx_scales_to_rows(t, 256, c.D, w_order=w_order)
+        assert torch.equal(rows[:c.M], c.want_rows) and bool((rows[c.M:] == X.SCALE_SENTINEL).all())
+
+
+def _real_rounding_share(y_bf16, exact64):
+    return (y_bf16.double() != exact64).double().mean().item()
+
+
+@pytest.mark.parametrize("D", X.LN_FP8_DS)
+def test_ln_fp8_case_is_exact_rounds_and_sees_the_wrong_sample(D):
+    c = X.ln_fp8_case(D)
+    exact = X.ln_affine_exact(c.v, c.a, c.b, c.ab_rows)
+    f32 = c.v.float() * c.a[X.sample_of(c.M, c.ab_rows)] + c.b[X.sample_of(c.M, c.ab_rows)]
+    assert torch.equal(f32.double(), exact) and _real_rounding_share(c.y, exact) >= 0.25
+    assert c.ab_rows % 4 != 0 and c.M % 4 != 0
+    wrong = X.ln_fp8_case(D, "affine row of the wrong sample")
+    moved = torch.arange(c.M) % c.ab_rows == c.ab_rows - 1
+    assert _each_row_differs(wrong.want_q, c.want_q, moved) and not torch.equal(wrong.want_s[moved], c.want_s[moved])
+    assert torch.equal(wrong.want_q[~moved], c.want_q[~moved])
+
+
+@pytest.mark.parametrize("D", X.LN_MX_DS)
+def test_ln_mx_case_is_exact_has_diverse_scales_and_sees_every_mistake(D):
+    c = X.ln_mx_case(D)
+    exact = X.ln_affine_exact(c.v, c.a, c.b, c.ab_rows)
+    idx = X.sample_of(c.M, c.ab_rows)
+    assert torch.equal((c.v.float() * c.a[idx] + c.b[idx]).double(), exact) and _real_rounding_share(c.y, exact) >= 0.25
+    assert X.scale_diversity(c.want_rows) >= 0.5, X.scale_diversity(c.want_rows)
+    zero = c.want_rows == 1
+    assert zero.any() and not c.want_q.view(c.M, -1, 32)[zero].any()                    # zero blocks: scale byte 1, zero bytes
+    assert int(c.want_rows.max()) - int(c.want_rows[~zero].min()) >= 10                 # octaves apart along a row
+    assert c.M % 128 == 2 and c.ab_rows % 4 != 0 and not bool((c.want_rows == X.SCALE_SENTINEL).any())
+    wrong = X.ln_mx_case(D, "affine row of the wrong sample")
+    moved = torch.arange(c.M) % c.ab_rows == c.ab_rows - 1
+    assert _each_row_differs(wrong.want_rows, c.want_rows, moved) and _each_row_differs(wrong.want_q, c.want_q, moved)
+    wrong = X.ln_mx_case(D, "scale byte of the neighbouring block")
+    assert (wrong.want_rows != c.want_rows).double().mean() >= 0.5 and _each_row_differs(wrong.want_s.view(-1, 512), c.want_s.view(-1, 512))
+    wrong = X.ln_mx_case(D, "W-order scale layout")
+    assert torch.equal(wrong.want_rows, c.want_rows) and (wrong.want_s != c.want_s).double().mean() >= 0.25
+
+
+@pytest.mark.parametrize("R", [X.RMS_MX_M, 3, None])
+@pytest.mark.parametrize("D,hd", X.RMS_MX_SHAPES)
+def test_rms_mx_case_is_exact_and_sees_an_ignored_post_scale_or_a_wrong_table_row(D, hd, R):
+    from chronoedit_amd import ops
+    for ps in (ops.MXFP8_Q_SCALE, 1.0):
+        c = X.rms_mx_case(D, hd, R, ps)
+        assert torch.equal(c.x.double(), c.v * (c.x.double().abs().amax(1, keepdim=True) / c.v.abs().amax(1, keepdim=True)))  # x = s v, centred
+        assert c.M % 4 != 0 and (R is None or c.M % R == 0)
+        if ps != 1.0:
+            wrong = X.rms_mx_case(D, hd, R, ps, "post_scale ignored")
+            assert (wrong.want_rows != c.want_rows).double().mean() > 0.9 and _each_row_differs(wrong.want_q, c.want_q)
+            one = X.rms_mx_case(D, hd, R, 1.0)
+            assert torch.equal(wrong.want_rows, one.want_rows) and torch.equal(wrong.want_q, one.want_q)
+        if R == 3:
+            wrong = X.rms_mx_case(D, hd, R, ps, "RoPE table row m")
+            assert torch.equal(wrong.want_q[:R], c.want_q[:R]) and _each_row_differs(wrong.want_q, c.want_q, torch.arange(c.M) >= R)
+
+
+def _gelu_tanh_f32(x):
+    """ce_common.h gelu_tanh in torch fp32, operation by operation (the reciprocal as a correctly rounded division)."""
+    c1 = torch.tensor(-2.0 * 1.4426950408889634 * 0.7978845608028654, dtype=torch.float32)
+    c2 = torch.mul(c1, torch.tensor(0.044715, dtype=torch.float32))
+    e = torch.exp2(x * (c2 * (x * x) + c1))
+    return x * (1.0 / (1.0 + e))
+
+
+def test_saturated_gelu_margins():
+    """With the kernel's constants in fp32: 5.0 already returns 5.0 and -10.5 already -0, while -10.0 still returns a denormal-sized negative - the
+    set {0} u [6, inf) u (-inf, -12] keeps real margins."""
+    y = _gelu_tanh_f32(torch.tensor([5.0, 6.0, 16.0, 1.0e7, -10.5, -12.0, -16.0, -1.0e7, 0.0, -10.0]))
+    assert torch.equal(y[:4].to(BF), torch.tensor([5.0, 6.0, 16.0, 1.0e7]).to(BF))
+    assert bool((y[4:8] == 0).all()) and bool(torch.signbit(y[4:8]).all()) and y[8] == 0 and not torch.signbit(y[8])
+    assert -1e-36 < y[9].item() < 0
+
+
+def _sat_bytes(x64):
+    """(scale rows, bytes) of the FFN-up form for an fp64 acc + bias that a mistaken reference produced (NaN where nothing is written: 0 there;
+    torch's fp32 tanh GELU stands in where a mistake left the saturated set - on the set it returns x, -0 or 0 as well)."""
+    xb = torch.nan_to_num(x64).float().to(BF)
+    return X.mx_contract(torch.nn.functional.gelu(xb.float(), approximate="tanh").to(BF))
+
+
+@pytest.mark.parametrize("M,N,K", X.SAT_SHAPES)
+def test_sat_gemm_case_premises(M, N, K):
+    """fp32 holds acc + bias exactly, every GELU input lies in the saturated set, at least half the 32-column blocks are mixed, -0 bytes and the
+    scale byte 1 occur, neighbouring blocks differ in scale; the kernel's fp32 GELU returns the closed form on every input.  (The largest shape:
+    its first and last 300 rows - the last row of tiles, ragged, is the one the plan cuts.)"""
+    c = X.sat_gemm_case(M, N, K)
+    rows = torch.arange(M) if M <= 600 else torch.cat([torch.arange(300), torch.arange(M - 300, M)])
+    a = c.a[rows]
+    for t in (a, c.w):
+        s8, q8 = X.mx_contract(t)
+        assert torch.equal(X.mx_unpack(q8, s8), t.double())
+    f32 = a.float() @ c.w.float().t() + c.bias
+    exact = a.double() @ c.w.double().t() + c.bias.double()
+    assert torch.equal(f32.double(), exact)
+    units = exact / c.unit[rows]
+    assert torch.equal(units, units.round()) and units.abs().max().item() < 2 ** 22      # (non-negative terms: the full sum bounds every partial sum)
+    x = bf16_rne(exact)
+    assert _real_rounding_share(x, exact) > 0.25
+    y = X.sat_gelu(x)
+    assert torch.equal(_gelu_tanh_f32(x.float()).to(BF).view(torch.int16), y.view(torch.int16))
+    assert X.mixed_block_share(y) >= 0.5, X.mixed_block_share(y)
+    rows8, q = X.mx_contract(y)
+    assert bool((q == 0x80).any()) and bool((rows8 == 1).any()) and X.scale_diversity(rows8) >= 0.5
+    assert int(rows8.max()) - int(rows8[rows8 > 1].min()) >= 4 and not bool((rows8 == X.SCALE_SENTINEL).any())
+    assert torch.equal(_sat_bytes(exact)[1], q) and torch.equal(_sat_bytes(exact)[0], rows8)
+
+
+def test_fp8_split_k_plan_restated_on_256_compute_units():
+    ws = 256 * 384 * 256 * 4
+    want = {(300, 512, 13824): (2, 2, 0, 4, 6), (129, 256, 256): (1, 1, 1, 0, 1), (4352, 4096, 5120): (17, 16, 256, 16, 5),
+            (300, 520, 256): (2, 3, 6, 0, 1), (300, 520, 13824): (2, 3, 0, 6, 6), (1000, 1032, 5120): (4, 5, 0, 20, 5),
+            (7200, 13824, 5120): (29, 54, 1536, 30, 5)}
+    for shape, plan in want.items():
+        assert X.fp8_tail_plan(*shape, 256, ws) == plan, (shape, X.fp8_tail_plan(*shape, 256, ws))
+    assert X.fp8_tail_plan(300, 512, 13824, 256, 0)[4] == 1                              # no scratch: nothing is cut
+    for tm, tn in ((2, 2), (17, 16), (4, 5), (29, 54)):                                  # the raster visits every tile exactly once
+        seen = sorted(X.fp8_tile_origin(wg, tm, tn) for wg in range(tm * tn))
+        assert seen == sorted((m * 256, n * 256) for m in range(tm) for n in range(tn))
+
+
+@pytest.mark.parametrize("mistake", ["one slab fewer in the tail sum", "tail raster group 1", "bias of column n+4",
+                                     "scale byte of the neighbouring block", "W-order scale layout"])
+def test_ffn_up_reference_sees_every_tail_mistake(mistake):
+    """300 x 512 x 13824 (four tiles, all tail, cut in six): the tile-by-tile restatement of the launch equals the plain product, and with one slab
+    fewer, the reduce kernel's tiles under a raster group of 1, or the bias of column n + 4 it gives other bytes in every tile."""
+    M, N, K = X.SAT_SHAPES[0]
+    c = X.sat_gemm_case(M, N, K)
+    plan = X.fp8_tail_plan(M, N, K, 256, 256 * 384 * 256 * 4)
+    exact = c.a.double() @ c.w.double().t() + c.bias.double()
+    assert torch.equal(X.fp8_tail_launch_f64(c.a, c.w, c.bias, plan), exact)
+    rows8, q = _sat_bytes(exact)
+    if mistake == "scale byte of the neighbouring block":
+        assert (X.neighbour_block(rows8) != rows8).double().mean() >= 0.5
+    elif mistake == "W-order scale layout":
+        assert (X.mx_scales_tiled(rows8, w_order=True) != X.mx_scales_tiled(rows8)).double().mean() >= 0.25
+    else:
+        r2, q2 = _sat_bytes(X.fp8_tail_launch_f64(c.a, c.w, c.bias, plan, mistake))
+        moved = [X.fp8_tile_origin(wg, 2, 2) for wg in range(4) if mistake != "tail raster group 1" or X.fp8_tile_origin(wg, 2, 2, group=1) != X.fp8_tile_origin(wg, 2, 2)]
+        assert len(moved) >= 2
+        for m0, n0 in moved:
+            assert (q2[m0:m0 + 256, n0:n0 + 256] != q[m0:m0 + 256, n0:n0 + 256])[:M - m0].double().mean() > 0.05, (mistake, m0, n0)
+    if mistake == "tail raster group 1":                                                  # the largest shape cannot see this one: its tail is one row of tiles
+        assert all(X.fp8_tile_origin(wg, 17, 16) == X.fp8_tile_origin(wg, 17, 16, group=1) for wg in range(256, 272))
+        assert any(X.fp8_tile_origin(wg, 4, 5) != X.fp8_tile_origin(wg, 4, 5, group=1) for wg in range(20))
+
+
+def test_every_fp8_mistake_has_a_reference_that_sees_it():
+    covered = {"scale byte of the neighbouring block", "W-order scale layout", "affine row of the wrong sample"}      # ln_mx_case, ln_fp8_case
+    covered |= {"bias of column n+4", "one slab fewer in the tail sum", "tail raster group 1"}                      # fp8_tail_launch_f64
+    covered |= {"post_scale ignored", "RoPE table row m"}                                                            # rms_mx_case
+    assert covered == set(X.FP8_MISTAKES)
+
+
+@pytest.mark.parametrize("M,N,K", X.BEND_SHAPES)
+def test_bend_gemm_case_is_exact_and_spans_the_bend(M, N, K):
+    c = X.bend_gemm_case(M, N, K)
+    assert torch.equal(c.a.float(), c.ia * c.sa[:, None]) and torch.equal(c.w.float(), c.iw * c.sw[:, None])
+    assert torch.equal(c.ia.to(torch.float8_e4m3fn).float(), c.ia) and torch.equal(c.iw.to(torch.float8_e4m3fn).float(), c.iw)
+    for t in (c.a, c.w):
+        s8, q8 = X.mx_contract(t)
+        assert torch.equal(X.mx_unpack(q8, s8), t.double())
+    exact = c.a.double() @ c.w.double().t() + c.bias.double()
+    assert torch.equal((c.a.float() @ c.w.float().t() + c.bias).double(), exact)
+    x = bf16_rne(exact).float()
+    assert x.min().item() > -9.0 and (x.abs() < 4).double().mean().item() >= 0.5 and _real_rounding_share(bf16_rne(exact), exact) > 0.25
+    assert x.min().item() < -3.0 and x.max().item() > 3.0                                 # both sides of the bend
