@@ -114,6 +114,13 @@ __device__ __forceinline__ uint32_t resample_clip8(int ss) {
   return (uint32_t)min(max(ss, 0), (256 << CE_RESAMPLE_BITS) - 1) >> CE_RESAMPLE_BITS;
 }
 
+// PIL's MULDIV255-free blend of Paste.c / Image.composite / Image.alpha_composite over an opaque destination (ce_focus.hip, ce_layers.hip):
+// exact for m == 0 (s) and m == 255 (e)
+__device__ __forceinline__ uint32_t focus_blend8(uint32_t s, uint32_t e, uint32_t m) {
+  const uint32_t t = s * (255u - m) + e * m + 128u;
+  return ((t >> 8) + t) >> 8;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -102,12 +102,6 @@ CE_API int ce_focus_resample_l8(const void* src, long long src_pitch, void* dst,
   return (int)hipGetLastError();
 }
 
-// PIL's MULDIV255-free blend of Paste.c / Image.composite: exact for m == 0 (s) and m == 255 (e)
-__device__ __forceinline__ uint32_t focus_blend8(uint32_t s, uint32_t e, uint32_t m) {
-  const uint32_t t = s * (255u - m) + e * m + 128u;
-  return ((t >> 8) + t) >> 8;
-}
-
 // One lane per four consecutive bytes of one output frame (blockIdx.y = frame).  The group's first byte is split into (Y, X, channel) once
 // and the other three follow by counting.  A byte outside the box, or under a mask byte of 0, is the source's and reads nothing else.
 // WIDE (frame bytes % 4 == 0, src and out 4-byte aligned): the source group arrives and the result leaves as one dword.

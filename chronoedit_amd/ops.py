@@ -1235,6 +1235,45 @@ def clusters_paste_u8(edit: torch.Tensor, mask: Optional[torch.Tensor], canvas: 
     return canvas
 
 
+# ---- sketch edits from an editor's layers (csrc/ce_layers.hip) -----------------------------------------------------------
+def _layer_box(layer: torch.Tensor, left: int, top: int, SW: int, SH: int):
+    _dev(layer, torch.uint8, "layer")
+    if layer.dim() != 3 or layer.shape[2] != 4 or not layer.is_contiguous() or layer.numel() == 0:
+        raise ValueError(f"layer: need a non-empty contiguous [bh, bw, 4] tensor, got shape {tuple(layer.shape)} stride {layer.stride()}")
+    bh, bw, _ = layer.shape
+    if isinstance(left, bool) or isinstance(top, bool) or left < 0 or top < 0 or left + bw > SW or top + bh > SH:
+        raise ValueError(f"the {bw}x{bh} box at ({left}, {top}) does not lie inside the {SW}x{SH} photo")
+    return bw, bh
+
+
+def layers_strokes_u8(layer: torch.Tensor, left: int, top: int, plane: torch.Tensor, threshold: int = 0):
+    """layer uint8 [bh, bw, 4] (RGBA, a layer's alpha bounding box at (left, top) of the photo), plane uint8 [SH, SW] -> plane, IN PLACE: 255
+    where the layer's alpha > threshold (0..254), every other byte as it was.  Only the box's bytes are touched."""
+    _plane(plane, "plane")
+    SH, SW = plane.shape
+    bw, bh = _layer_box(layer, left, top, SW, SH)
+    if isinstance(threshold, bool) or not 0 <= int(threshold) <= 254:
+        raise ValueError(f"threshold: an int in 0..254, got {threshold!r}")
+    st = _prof_begin()
+    _check(lib().ce_layers_strokes_u8(_ptr(layer), bw, bh, int(left), int(top), _ptr(plane), SW, SH, int(threshold), _stream()), "ce_layers_strokes_u8")
+    _prof_end(st, f"layers_strokes_{bh}x{bw}", 5.0 * bh * bw)
+    return plane
+
+
+def layers_over_u8(layer: torch.Tensor, left: int, top: int, canvas: torch.Tensor):
+    """Image.alpha_composite(canvas, layer) over an opaque canvas, IN PLACE: layer uint8 [bh, bw, 4] at (left, top), canvas uint8 [SH, SW, 3]
+    -> canvas.  Only the box's bytes are touched."""
+    _dev(canvas, torch.uint8, "canvas")
+    if canvas.dim() != 3 or canvas.shape[2] != 3 or not canvas.is_contiguous() or canvas.numel() == 0:
+        raise ValueError(f"canvas: need a non-empty contiguous [SH, SW, 3] tensor, got shape {tuple(canvas.shape)} stride {canvas.stride()}")
+    SH, SW, _ = canvas.shape
+    bw, bh = _layer_box(layer, left, top, SW, SH)
+    st = _prof_begin()
+    _check(lib().ce_layers_over_u8(_ptr(layer), bw, bh, int(left), int(top), _ptr(canvas), SW, SH, _stream()), "ce_layers_over_u8")
+    _prof_end(st, f"layers_over_{bh}x{bw}", 10.0 * bh * bw)
+    return canvas
+
+
 # ---- automatic edit regions (csrc/ce_region_auto.hip) ------------------------------------------------------------------
 def _f32c(t: torch.Tensor, name: str):
     _dev(t, torch.float32, name)

@@ -15,7 +15,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
-from . import auto_region as _ar, autofocus as _af, clusters as _cl, focus as _fc, image_io, lift as _lf, preview as _pv, region as _rg, sketch as _sk
+from . import auto_region as _ar, autofocus as _af, clusters as _cl, focus as _fc, image_io, layers as _ly, lift as _lf, preview as _pv, region as _rg, sketch as _sk
 from .loop import (GraphedDenoiser, _capturable, _sharded_batchable, _shared_inputs, _token_sharded, _warmup_stream,  # noqa: F401
                    compact_text_context, denoise, denoise_step, make_cfg_inputs, text_compaction_plan, text_real_lengths)
 from .scheduler import FlowUniPCMultistepScheduler
@@ -680,7 +680,7 @@ class ChronoEditPipeline:
 
     # Sketch edits (chronoedit_amd/sketch.py): the region is where the editor's composite differs from its background.  Off by default
     def enable_sketch_region(self, grow=0.02, feather=0.01, threshold: int = 0, context: float = 0.25, composite: bool = True, min_stroke=0,
-                             max_crops: int = 1):
+                             max_crops: int = 1, strokes: str = "difference", alpha_threshold: int = 0, layer_prompts: bool = False):
         """While on and no `set_edit_region` mask is set, `__call__(image=...)` also takes an image editor's value: a dict with PIL images
         under "background" (the photo) and "composite" (the photo with the strokes on it) - other keys, such as "layers", are ignored -, or
         a list of such dicts, one per prompt.  Per value the mask is built at the PHOTO's size before the first step (sketch.reference:
@@ -722,35 +722,69 @@ class ChronoEditPipeline:
         `focus_report` is the flat list of the plans that ran; previews carry "sample" = the flat crop index and "crop" = (value, crop).
         output_type "latent" returns the crops' latents, flat.  `num_videos_per_prompt > 1` with a value of two or more crops is a
         NotImplementedError.  How a checkpoint edits two crops of one photo consistently is the checkpoint's business; the default of 1
-        is a choice, not a measurement."""
-        self._sketch_region = _sk.SketchConfig(grow, feather, threshold, context, composite, min_stroke, max_crops)
+        is a choice, not a measurement.
+        strokes ("difference": today's call bit for bit, no new launch; "layers" is ignored then and layer_prompts=True a ValueError):
+        with "layers" the strokes are where the editor's LAYERS say the user drew (chronoedit_amd/layers.py; csrc/ce_layers.hip on the
+        device, the same bytes): changed = 255 where some layer's alpha > `alpha_threshold` (an int in 0..254) - a black stroke on a dark
+        part of the photo is found, a lossy composite needs no threshold.  The value must hold "layers": a list (possibly empty) of PIL
+        images of the background's size whose mode has an alpha channel, used as `convert("RGBA")`; anything else is a ValueError before
+        anything runs.  Each layer is uploaded as its alpha bounding box only; the one read stays one read per value.  "composite" may be
+        missing or None: it is then built, `Image.alpha_composite` of the layers over the background in order, and
+        `sketch_report[i]["composite"]` holds it (PIL).  A given composite is what the model sees, as today.  `sketch_report[i]` gains
+        "strokes" and "alpha_threshold"; everything behind `changed` is the chain above.
+        layer_prompts (needs strokes="layers"): ONE editor value plus one prompt per layer (a list of L prompts, or L rows of
+        `prompt_embeds`; a layer without strokes consumes its prompt) is ONE edit.  Each layer with strokes is an entry of its own -
+        (background, the layer alone over the background, the layer's alpha) - through the chain above, with its own clusters, groups
+        and crops under max_crops >= 2; all plans run as the samples of one focused pass, each from its LAYER's prompt row (the text
+        encoder runs once per prompt, CLIP per crop, the noise drawn as the single-box call draws it for one value, then repeated), and
+        are pasted into the BACKGROUND in layer order, then crop order: where two layers' masks overlap the later layer wins.  At most two
+        host reads per layer with strokes in front of the edit (the layer's counts; its groups' boxes).  `sketch_report[0]` then holds
+        "reason": "layers", "source_size", "edit_size", "grow_px", "feather_px", "threshold", "strokes", "alpha_threshold",
+        "changed_pixels" (all layers'), "max_crops", "crops" (as above, each with "layer") and "layers": per layer {"bbox" (its mask's),
+        "stroke_pixels", "reason"} - "empty" for a layer without strokes.  Refused on the host, before anything is uploaded or launched: a
+        number of prompts other than L, no alpha above the threshold in any layer, more than 16 layers with strokes under max_crops == 1 and
+        min_stroke == 0 (ValueError); a list of editor values, num_videos_per_prompt > 1 (NotImplementedError).  What only the chain knows
+        is refused behind the layers' mask chains and before any encoder or the VAE runs: every stroke dropped by min_stroke, more than 16
+        plans in all under min_stroke or max_crops >= 2 (ValueError).  An explicit `set_edit_region` mask still wins: the value stands for its composite (built if absent) and
+        takes one prompt.  What a checkpoint makes of per-layer composites is the checkpoint's business."""
+        self._sketch_region = _sk.SketchConfig(grow, feather, threshold, context, composite, min_stroke, max_crops, strokes, alpha_threshold,
+                                               layer_prompts)
         return self
 
     def disable_sketch_region(self):
         self._sketch_region = None
         return self
 
-    def sketch_mask(self, background, composite):
+    def _sketch_entry(self, background, composite, layers) -> dict:
+        """The `sketch.masks` entry of one (background, composite, layers) with the enabled parameters: what sketch_mask / sketch_crops show."""
+        cfg = self._sketch_region
+        value = {"background": background, "composite": composite}
+        by_layers = cfg.strokes == "layers"
+        bgs, cps = _sk.editor_images(value, need_composite=not by_layers)
+        lys = [_ly.editor_layers(value, 0, layers)] if by_layers else None
+        device = self._execution_device
+        return _sk.masks(cfg, bgs, cps, device if image_io.on_device(self.device_image_io, device) else None, lys)[0]
+
+    def sketch_mask(self, background, composite, layers=None):
         """The mask a sketch call would build for this pair of PIL images with the enabled parameters, as a PIL "L" image of their size - for
-        a front end to show before an edit is spent."""
+        a front end to show before an edit is spent.  With strokes="layers": `layers` is the editor's list of layers (required; the
+        composite may be None), and the mask is the union over the layers, whatever `layer_prompts` says."""
         from PIL import Image
         if self._sketch_region is None:
             raise ValueError("sketch_mask needs the parameters of enable_sketch_region(): the switch is off")
-        bgs, cps = _sk.editor_images({"background": background, "composite": composite})
-        device = self._execution_device
-        e = _sk.masks(self._sketch_region, bgs, cps, device if image_io.on_device(self.device_image_io, device) else None)[0]
+        e = self._sketch_entry(background, composite, layers)
         return Image.fromarray(_sk.host_mask(e).numpy(), mode="L")  # (no edit follows: the copy of the mask may be made here)
 
-    def sketch_crops(self, background, composite, height: int, width: int) -> list:
+    def sketch_crops(self, background, composite, height: int, width: int, layers=None) -> list:
         """The crops a sketch call at width x height would run for this pair of PIL images with the enabled parameters, without running an
         edit: a list of {"box", "reason", "scale", "mask_fraction_of_box", "clusters" (labels), "mask" (PIL "L", the photo's size)} in paste
-        order - `sketch_report[i]["crops"]`.  One entry (the single-box plan) with max_crops == 1 or when the call would fall back to it."""
+        order - `sketch_report[i]["crops"]`.  One entry (the single-box plan) with max_crops == 1 or when the call would fall back to it.
+        With strokes="layers": `layers` as in `sketch_mask`; the crops are those of the union of the layers (a call with `layer_prompts`
+        plans every layer on its own)."""
         if self._sketch_region is None:
             raise ValueError("sketch_crops needs the parameters of enable_sketch_region(): the switch is off")
         cfg = self._sketch_region
-        bgs, cps = _sk.editor_images({"background": background, "composite": composite})
-        device = self._execution_device
-        e = _sk.masks(cfg, bgs, cps, device if image_io.on_device(self.device_image_io, device) else None)[0]
+        e = self._sketch_entry(background, composite, layers)
         single = _sk.focus_plan(e, width, height, cfg.context)
         crops = _cl.plan(e, cfg.max_crops, width, height, cfg.context) if cfg.max_crops >= 2 else _cl.Crops("single")
         return _cl.crop_reports(crops, single)
@@ -813,15 +847,23 @@ class ChronoEditPipeline:
             raise ValueError("`image` is an image editor's value (a dict with \"background\" and \"composite\"): switch sketch edits on with "
                              "enable_sketch_region() first, or pass the composite itself")
         cfg = self._sketch_region
-        bgs, cps = _sk.editor_images(a.image)
-        a = replace(a, image=cps if isinstance(a.image, (list, tuple)) else cps[0])
-        if self._edit_region is not None:  # an explicit mask wins: the editor value stands for its composite
-            return self._edit(a)
+        by_layers = cfg.strokes == "layers"
+        several = isinstance(a.image, (list, tuple))
+        bgs, cps = _sk.editor_images(a.image, need_composite=not by_layers)
+        lys = [_ly.editor_layers(v, i) for i, v in enumerate(a.image if several else [a.image])] if by_layers else None
+        if self._edit_region is not None:  # an explicit mask wins: the editor value stands for its composite (built if it has none)
+            if by_layers:
+                cps = [cp if cp is not None else _ly.composite(bg, _ly.boxes(ls)) for bg, cp, ls in zip(bgs, cps, lys)]
+            return self._edit(replace(a, image=cps if several else cps[0]))
+        if cfg.layer_prompts:
+            return self._sketch_layers_edit(a, cfg, several, bgs[0], lys[0])
         if a.output_type in ("np", "pt") and len({im.size for im in bgs}) > 1:
             raise ValueError(f"a sketch edit returns frames of the photos' sizes {[im.size for im in bgs]}: output_type={a.output_type!r} "
                              'needs photos of one size, use "pil"')
         device = self._execution_device
-        entries = _sk.masks(cfg, bgs, cps, device if image_io.on_device(self.device_image_io, device) else None)
+        entries = _sk.masks(cfg, bgs, cps, device if image_io.on_device(self.device_image_io, device) else None, lys)
+        cps = [e["composite"] for e in entries]  # (a value without one: built from its layers)
+        a = replace(a, image=cps if several else cps[0])
         plans = [_sk.focus_plan(e, a.width, a.height, cfg.context) for e in entries]
         crops = [_cl.plan(e, cfg.max_crops, a.width, a.height, cfg.context) for e in entries] if cfg.max_crops >= 2 else None
         if all(e["bbox"] is None for e in entries):  # no strokes anywhere: the plain call on the composite(s)
@@ -839,6 +881,79 @@ class ChronoEditPipeline:
         if crops is not None:
             for rep, p, c in zip(self.sketch_report, plans, crops):
                 rep.update(max_crops=cfg.max_crops, crops=_cl.crop_reports(c, p), crops_reason=c.reason)
+        if by_layers:
+            for rep, e in zip(self.sketch_report, entries):
+                rep.update(strokes=cfg.strokes, alpha_threshold=cfg.alpha_threshold, **({"composite": e["composite"]} if e.get("built") else {}))
+        return out
+
+    def _sketch_layers_edit(self, a: CallArgs, cfg, several: bool, bg, layers: list):
+        """The sketch edit with a prompt per layer (`enable_sketch_region(strokes="layers", layer_prompts=True)`): every layer with strokes
+        is planned on its own - the layer alone over the background, its alpha as `changed` - and all plans run as the samples of ONE focused
+        pass, each from its layer's prompt row; `_output` chains them into one video over the background (clusters.paste), in layer order,
+        then crop order.  In front of the edit at most two host reads per layer with strokes: the layer's counts, its groups' boxes."""
+        if several:
+            raise NotImplementedError("a sketch edit with a prompt per layer takes ONE editor value, not a list of them: run the values one call each")
+        if a.num_videos_per_prompt != 1:
+            raise NotImplementedError("a sketch edit with a prompt per layer and num_videos_per_prompt > 1 is not implemented: run the videos "
+                                      "one call each")
+        a, device = self._begin(replace(a, image=bg), guarded=False)  # (host checks only: nothing is launched)
+        L, n = len(layers), self._prompt_count(a)
+        if n != L:
+            raise ValueError(f"a sketch edit with a prompt per layer needs one prompt per layer, empty layers included: got {n} prompt(s) for {L} layer(s)")
+        # what the layers' bytes decide on the host, before anything is uploaded: no alpha above the threshold anywhere; and, where
+        # neither the speck filter nor the grouping can change the number of plans, too many of them
+        stroked = [lb for lb in _ly.boxes(layers) if bool((lb.rgba[:, :, 3] > cfg.alpha_threshold).any())]
+        none = (f"a sketch edit with a prompt per layer found no stroke in any of the {L} layer(s): there is no plain call to fall back to with "
+                "several prompts")
+        many = f"a sketch edit with a prompt per layer runs at most {_cl.MAX_CROPS} crops in all, the layers ask for {{}}: lower max_crops, or merge layers"
+        if not stroked:
+            raise ValueError(none)
+        if not cfg.min_stroke and cfg.max_crops == 1 and len(stroked) > _cl.MAX_CROPS:
+            raise ValueError(many.format(len(stroked)))
+        entries = _sk.layer_entries(cfg, bg, layers, device if image_io.on_device(self.device_image_io, device) else None, stroked)
+        flat, crop_of, row_of, singles, crops = [], [], [], {}, {}
+        for k, e in enumerate(entries):
+            if e is None:
+                continue
+            singles[k] = _sk.focus_plan(e, a.width, a.height, cfg.context)
+            crops[k] = _cl.plan(e, cfg.max_crops, a.width, a.height, cfg.context) if cfg.max_crops >= 2 else _cl.Crops("single")
+            for q in crops[k].plans if crops[k].reason == "crops" else [singles[k]]:
+                crop_of.append((0, len(flat))), flat.append(q), row_of.append(k)
+        if not flat:  # (the speck filter dropped every stroke)
+            raise ValueError(none)
+        if len(flat) > _cl.MAX_CROPS:  # (known only behind the chain: the filter and the grouping decide how many plans there are)
+            raise ValueError(many.format(len(flat)))
+        _, prompt_embeds, negative_prompt_embeds = self._encode_text(a, device)  # the text encoder: once per prompt
+        rows = torch.tensor(row_of, dtype=torch.long)
+        repeat = lambda t: None if t is None else t.index_select(0, rows.to(t.device))
+        noise = a.latents
+        if noise is None:  # what the single-box call would draw for one value
+            if isinstance(a.generator, list) and len(a.generator) != 1:
+                raise ValueError(f"You have passed a list of generators of length {len(a.generator)}, but requested an effective batch"
+                                 f" size of 1. Make sure the batch size matches the length of the generators.")
+            T = (a.num_frames - 1) // self.vae_scale_factor_temporal + 1
+            shape = (1, self.vae.config.z_dim, T, a.height // self.vae_scale_factor_spatial, a.width // self.vae_scale_factor_spatial)
+            noise = _randn_tensor(shape, a.generator, device, torch.bfloat16)
+        elif noise.shape[0] != 1:
+            raise ValueError(f"`latents` carry {noise.shape[0]} samples, expected one for the editor value")
+        image_embeds = a.image_embeds
+        if image_embeds is not None:
+            if image_embeds.shape[0] not in (1, len(flat)):
+                raise ValueError(f"`image_embeds` carry {image_embeds.shape[0]} samples, expected 1 or one per crop ({len(flat)})")
+        out = self._edit(replace(a, image=[q.image for q in flat], prompt=None, negative_prompt=None, prompt_embeds=repeat(prompt_embeds),
+                                 negative_prompt_embeds=repeat(negative_prompt_embeds), image_embeds=image_embeds,
+                                 latents=noise.repeat(len(flat), 1, 1, 1, 1), generator=None),
+                         FocusPass(flat, cfg.composite, guarded=True, crop_of=crop_of))
+        # behind the edit: the masks' copies for the report
+        stroked = [e for e in entries if e is not None]
+        per_crop = [dict(c, layer=k) for k in crops for c in _cl.crop_reports(crops[k], singles[k])]
+        self.sketch_report = [dict(reason="layers", source_size=bg.size, edit_size=(int(a.width), int(a.height)), grow_px=stroked[0]["grow_px"],
+                                   feather_px=stroked[0]["feather_px"], threshold=cfg.threshold, strokes=cfg.strokes,
+                                   alpha_threshold=cfg.alpha_threshold, changed_pixels=sum(e["changed_pixels"] for e in stroked),
+                                   max_crops=cfg.max_crops, crops=per_crop,
+                                   layers=[{"bbox": None, "stroke_pixels": 0, "reason": "empty"} if e is None else
+                                           {"bbox": e["bbox"], "stroke_pixels": e["changed_pixels"], "reason": singles[k].report["reason"]
+                                            if crops[k].reason != "crops" else "crops"} for k, e in enumerate(entries)])]
         return out
 
     def _sketch_crops_edit(self, a: CallArgs, cfg, plans: list, crops: list):
@@ -952,14 +1067,18 @@ class ChronoEditPipeline:
             raise Exception(f"Guardrail blocked text2world generation. Prompt: {a.prompt}")
         return a, device
 
+    @staticmethod
+    def _prompt_count(a: CallArgs) -> int:
+        """How many prompts the call carries (:631-637), behind `check_inputs`."""
+        if a.prompt is not None and isinstance(a.prompt, str):
+            return 1
+        if a.prompt is not None and isinstance(a.prompt, list):
+            return len(a.prompt)
+        return a.prompt_embeds.shape[0]
+
     def _encode_text(self, a: CallArgs, device):
         """-> (batch_size, prompt_embeds, negative_prompt_embeds) on the device in the transformer's dtype (:631-660)."""
-        if a.prompt is not None and isinstance(a.prompt, str):
-            batch_size = 1
-        elif a.prompt is not None and isinstance(a.prompt, list):
-            batch_size = len(a.prompt)
-        else:
-            batch_size = a.prompt_embeds.shape[0]
+        batch_size = self._prompt_count(a)
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(
             prompt=a.prompt, negative_prompt=a.negative_prompt, do_classifier_free_guidance=self.do_classifier_free_guidance,
             num_videos_per_prompt=a.num_videos_per_prompt, prompt_embeds=a.prompt_embeds, negative_prompt_embeds=a.negative_prompt_embeds,

@@ -746,6 +746,24 @@ int ce_clusters_select_u8(const int* labels, const void* kept, const int* table,
 int ce_clusters_paste_u8(const void* edit, const void* mask, void* canvas, int F, int src_h, int src_w, int left, int top, int bw, int bh,
                          hipStream_t stream);
 
+/* ---- sketch edits from an image editor's layers (csrc/ce_layers.hip; chronoedit_amd/layers.py is the definition and both passes give its
+ * bits).  layer = uint8 [bh][bw][4], RGBA: the layer's alpha bounding box, placed at (left, top) of the photo of SW x SH pixels.  Both calls
+ * work IN PLACE and touch only bytes of the box [top, top + bh) x [left, left + bw); a box that leaves the photo returns -1.
+ * ce_layers_strokes_u8: plane = uint8 [SH][SW]: plane[p] = 255 where the layer's alpha > threshold, every other byte is left as it is - on a
+ *   plane the caller zeroed, the layers of a value give "255 where max over the layers of alpha > threshold".  threshold in 0..254
+ *   (otherwise -1).
+ * ce_layers_over_u8: canvas = uint8 [SH][SW][3]: Image.alpha_composite(canvas, layer) over an opaque canvas, per channel
+ *   u = s * a + d * (255 - a) + 128, d = ((u >> 8) + u) >> 8 - ce_focus_paste_u8's arithmetic with the alpha as the mask; under a == 0
+ *   the byte stays.
+ * One lane per run of up to four pixels of a row.  Where the row address allows it a run moves as whole words - strokes: the layer's four
+ *   pixels as one 16-byte load; over: the canvas's twelve bytes as three aligned dwords, the layer's as one 16-byte load or four dwords -,
+ *   and the pixels in front of a row's first such address, its remainder, and everything at a base that is not 4-byte aligned move byte by
+ *   byte: the same bytes.  Any base address, any width.
+ * layer aliases neither plane nor canvas (otherwise -1).  No state, nothing allocated, no host read: every call is capturable.  Integers
+ * only: exact, and a pixel is read and written by one lane.  A photo or a box of 2^31 bytes or more returns -2. */
+int ce_layers_strokes_u8(const void* layer, int bw, int bh, int left, int top, void* plane, int SW, int SH, int threshold, hipStream_t stream);
+int ce_layers_over_u8(const void* layer, int bw, int bh, int left, int top, void* canvas, int SW, int SH, hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
