@@ -16,6 +16,10 @@ The fp8 mode's operand producers and GEMM tails (`row_fp8_ref`, `mx_contract`, `
 `fp8_tail_plan`, `FP8_MISTAKES`): the per-row quantiser restated operation by operation, MX producers on rows that are known exactly, GEMM
 operands whose GELU input is exact and saturated (the FFN-up form's bytes need no transcendental), and the split-K plan restated.
 
+The VAE's implicit-GEMM conv, RMS_norm (+ SiLU) and the conv with the norm in its epilogue (`conv_frames_f64`, `CONV_CASES`, `conv_case`,
+`CONV_MISTAKES`, `rms_case`, `rms_restate_f32`, `fused_case`, `RMS_MISTAKES`): the header's conv formula restated on the stored frames, border
+included, one case per configuration the engine sends, and rows of +-2^k whose norm is known bit for bit.
+
 An ordinary module (not a conftest): the test files import it by name."""
 import math
 
@@ -1482,3 +1486,392 @@ def bend_gemm_case(M: int, N: int, K: int) -> Case:
         c.bias = int_vector(N, g, lo=-16, hi=16, e=-4)
         return c
     return _cached(("bend", M, N, K), build)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the VAE's implicit-GEMM conv (ce_conv_igemm_bf16), RMS_norm (+ SiLU) (ce_rms_silu_bf16) and the conv with the norm in its epilogue
+# (ce_conv3d_gemm_rms_silu_bf16): tests/test_exact_vae_ops_gpu.py launches them, tests/test_exact_constructions.py proves the recipes.
+#
+# Conv: `int_rows` activations (one scale) and weights, `int_vector` bias - every sum exact in fp32, the expected output the fp64 value of
+# the header's formula rounded once (with a residual: bf16(res + that), an fp32 add of two bf16 values).  Every stored frame is written
+# everywhere, BORDER INCLUDED: only the positions the reference network calls padding are zero, and only where the engine's layout makes
+# them zero (the whole border under a stride-1 3 x 3, the bottom row and right column under the stride-2 3 x 3 = ZeroPad2d((0, 1, 0, 1)),
+# the shared zero frame of the temporal convs) - a read from the wrong side of the border changes the result.
+# ------------------------------------------------------------------------------------------------------------------------------------
+CONV_MISTAKES = ("in_off ignored", "in_off on rows only", "in_off on columns only", "stride multiplies the tap too", "kh and kw swapped",
+                 "frame t+kt instead of t*st+kt", "symmetric pad instead of bottom/right pad", "second slice uses weight rows 0..C",
+                 "second slice uses bias rows 0..C", "residual read without border offset")
+
+
+def _frame_at(frame: torch.Tensor, rows: torch.Tensor, cols: torch.Tensor) -> torch.Tensor:
+    """frame [Hs, Ws, C] at the stored positions (rows[i], cols[j]); a position outside the frame reads as zero (only a deliberately wrong
+    reference gets there)."""
+    Hs, Ws = frame.shape[:2]
+    ok = ((rows >= 0) & (rows < Hs))[:, None] & ((cols >= 0) & (cols < Ws))[None, :]
+    return frame[rows.clamp(0, Hs - 1)][:, cols.clamp(0, Ws - 1)] * ok[..., None]
+
+
+def conv_frames_f64(in_frames, w: torch.Tensor, bias, n_out: int, *, KT: int, KH: int, KW: int, st: int, ss: int, H_out: int, W_out: int,
+                    in_off: int, cout_slice=None, mistake=None) -> torch.Tensor:
+    """The formula of csrc/ce_conv.hip's header, literally, in fp64 - one matmul per (output frame, tap) on shifted views of the frame list:
+      out[t][h][w][co] = bias[co] + sum_{kt,kh,kw,ci} W[co][(kt,kh,kw)][ci] * in[t*st+kt][h*ss+kh+in_off][w*ss+kw+in_off][ci]
+    in_frames: list of [Hs, Ws, Cin] frames AS STORED (border included; the same frame may appear twice); w [Cout_all, KT*KH*KW, Cin] (the
+    pack's layout), bias [Cout_all] or None; cout_slice = (lo, hi): the output channels lo..hi-1 of the pack.  -> fp64 [n_out, H_out, W_out, hi-lo].
+    `mistake` (one of CONV_MISTAKES): the same with one deliberately wrong index ("residual ...": nothing changes here - `conv_want`)."""
+    assert mistake is None or mistake in CONV_MISTAKES, mistake
+    lo, hi = cout_slice if cout_slice is not None else (0, w.shape[0])
+    n = hi - lo
+    wlo = 0 if mistake == "second slice uses weight rows 0..C" else lo
+    blo = 0 if mistake == "second slice uses bias rows 0..C" else lo
+    off_h = off_w = in_off
+    if mistake == "in_off ignored":
+        off_h = off_w = 0
+    elif mistake == "in_off on rows only":
+        off_w = 0
+    elif mistake == "in_off on columns only":
+        off_h = 0
+    elif mistake == "symmetric pad instead of bottom/right pad":  # one zero row / column in FRONT of the image: every tap one position up and left
+        off_h = off_w = in_off - 1
+    tap_s, tap_t = (ss, st) if mistake == "stride multiplies the tap too" else (1, 1)
+    t_mul = 1 if mistake == "frame t+kt instead of t*st+kt" else st
+    swap = mistake == "kh and kw swapped"
+    assert not swap or KH == KW
+    wd = w.double()[wlo:wlo + n]
+    f64 = {}
+    h, wv = torch.arange(H_out, device=w.device), torch.arange(W_out, device=w.device)
+    out = torch.zeros(n_out, H_out, W_out, n, dtype=torch.float64, device=w.device)
+    for t in range(n_out):
+        for kt in range(KT):
+            fi = t * t_mul + kt * tap_t
+            if fi >= len(in_frames):
+                continue  # (a wrong reference only)
+            f = f64.setdefault(fi, in_frames[fi].double())
+            for kh in range(KH):
+                for kw in range(KW):
+                    x = _frame_at(f, h * ss + kh * tap_s + off_h, wv * ss + kw * tap_s + off_w)
+                    tap = (kt * KH + kw) * KW + kh if swap else (kt * KH + kh) * KW + kw
+                    out[t] += x @ wd[:, tap].t()
+    if bias is not None:
+        out += bias.double()[blo:blo + n]
+    return out
+
+
+def _conv_spec(Cin, Cout, k, T, H, W, **kw):
+    d = dict(Cin=Cin, Cout=Cout, k=k, T=T, H=H, W=W, st=1, ss=1, in_off=0, pad="none", in_rows=False, out_rows=False, res=False, cstride=None,
+             coff=0, cout_all=None, cout_lo=0, in_idx=None, zero_frames=(), out_idx=None, n_out_buf=None, seed_as=None)
+    d.update(kw)
+    return d
+
+
+def _conv_table():
+    t = {}
+    # 1 x 1 (x 1) reading the interior of bordered frames: .shortcut / conv1 / conv2 (one partial M tile; a ragged fourth one)
+    t["1x1 off1 M126"] = _conv_spec(96, 192, (1, 1, 1), 2, 9, 7, in_off=1)
+    t["1x1 off1 M429"] = _conv_spec(96, 192, (1, 1, 1), 3, 13, 11, in_off=1)
+    # .to_qkv: plain-row output, three N tiles; .proj: plain-row input, residual, bordered output
+    t["1x1 to rows"] = _conv_spec(128, 384, (1, 1, 1), 2, 9, 11, in_off=1, out_rows=True)
+    t["1x1 from rows + res"] = _conv_spec(96, 96, (1, 1, 1), 2, 7, 9, in_rows=True, res=True)
+    # .resample.1 down: 3 x 3, stride 2, padding from the bottom and right border only
+    for KT in (1, 3):
+        t[f"3x3 s2 even KT{KT}"] = _conv_spec(96, 96, (KT, 3, 3), 2, 10, 14, ss=2, in_off=1, pad="br")   # last taps on the border
+        t[f"3x3 s2 odd KT{KT}"] = _conv_spec(96, 96, (KT, 3, 3), 2, 11, 9, ss=2, in_off=1, pad="br")     # last taps on the interior
+    # .time_conv down: (3, 1, 1), temporal stride 2; the same zero frame twice in front
+    t["time down T2"] = _conv_spec(96, 96, (3, 1, 1), 2, 5, 6, st=2, in_off=1, in_idx=[0, 0, 1, 2, 3], zero_frames=(0,))
+    t["time down T7"] = _conv_spec(96, 96, (3, 1, 1), 7, 4, 5, st=2, in_off=1, in_idx=list(range(15)))
+    # .time_conv up: the two halves of a 2C-channel pack into the even and the odd frames of ONE buffer
+    up = dict(in_off=1, in_idx=[0, 0, 1, 2, 3], zero_frames=(0,), cout_all=192, n_out_buf=6, seed_as="time up")
+    t["time up lo"] = _conv_spec(96, 96, (3, 1, 1), 3, 5, 7, cout_lo=0, out_idx=[0, 2, 4], **up)
+    t["time up hi"] = _conv_spec(96, 96, (3, 1, 1), 3, 5, 7, cout_lo=96, out_idx=[1, 3, 5], **up)
+    # Cout <= 32: conv_igemm_kernel<32>; 40: five live chunks of a 128-wide tile; 136: a second N tile with one live chunk
+    for Cout in (8, 16, 24, 32, 40, 136):
+        for Cin in (32, 384):
+            t[f"k1 {Cin}->{Cout}"] = _conv_spec(Cin, Cout, (1, 1, 1), 2, 9, 8, in_off=1)
+            t[f"k3 {Cin}->{Cout}"] = _conv_spec(Cin, Cout, (3, 3, 3), 2, 9, 8, pad="all")
+    t["k1 32->16 in 32"] = _conv_spec(32, 16, (1, 1, 1), 2, 9, 8, in_off=1, cstride=32)
+    t["k3 32->16 in 32"] = _conv_spec(32, 16, (3, 3, 3), 2, 9, 8, pad="all", cstride=32)
+    t["coff 8 of 24+16"] = _conv_spec(32, 24, (3, 3, 3), 2, 9, 8, pad="all", cstride=40, coff=8)
+    t["coff 8 of 96+16"] = _conv_spec(96, 96, (1, 1, 1), 2, 9, 8, in_off=1, cstride=112, coff=8, res=True)
+    t["16 frames"] = _conv_spec(32, 32, (3, 1, 1), 14, 3, 3, in_off=1, in_idx=list(range(16)))
+    return t
+
+
+CONV_CASES = _conv_table()
+
+
+def conv_case(name: str) -> Case:
+    """The operands of one ce_conv_igemm_bf16 launch (CPU): in_stack [frames, Hs, Ws, Cin] as stored and in_idx (the frame list, as indices),
+    w [Cout_all, taps, Cin] / b [Cout_all] (the pack; the launch takes rows lo..hi), res (stored like the output) or None, and the output
+    buffer's geometry: out_shape [frames, Ho, Wo, out_cstride], out_idx (the frames the launch writes), out_border, out_Wp, out_coff."""
+    def build():
+        s = CONV_CASES[name]
+        g = torch.Generator().manual_seed(7000 + sum(ord(ch) * (i + 1) for i, ch in enumerate(s["seed_as"] or name)))
+        c = Case()
+        c.name, c.Cin, c.Cout, c.st, c.ss, c.in_off = name, s["Cin"], s["Cout"], s["st"], s["ss"], s["in_off"]
+        c.KT, c.KH, c.KW = s["k"]
+        c.n_out, H, W = s["T"], s["H"], s["W"]
+        c.H_out, c.W_out = (H, W) if c.ss == 1 else (H // 2, W // 2)
+        c.in_idx = s["in_idx"] if s["in_idx"] is not None else list(range((c.n_out - 1) * c.st + c.KT))
+        n_stack = max(c.in_idx) + 1
+        Hs, Ws = (H, W) if s["in_rows"] else (H + 2, W + 2)
+        c.in_Wp = Ws
+        x = int_rows(n_stack * Hs * Ws, c.Cin, g, emin=-1, emax=-1).view(n_stack, Hs, Ws, c.Cin).clone()
+        if s["pad"] == "all":
+            x[:, 0], x[:, -1], x[:, :, 0], x[:, :, -1] = 0, 0, 0, 0
+        elif s["pad"] == "br":
+            x[:, -1], x[:, :, -1] = 0, 0
+        for z in s["zero_frames"]:
+            x[z] = 0
+        c.in_stack = x
+        c.Cout_all = s["cout_all"] or c.Cout
+        c.cout_slice = (s["cout_lo"], s["cout_lo"] + c.Cout)
+        taps = c.KT * c.KH * c.KW
+        c.w = int_rows(c.Cout_all, taps * c.Cin, g, emin=-2, emax=2).view(c.Cout_all, taps, c.Cin).contiguous()
+        c.b = int_vector(c.Cout_all, g)
+        c.out_cstride, c.out_coff = s["cstride"] or c.Cout, s["coff"]
+        c.out_idx = s["out_idx"] if s["out_idx"] is not None else list(range(c.n_out))
+        n_buf = s["n_out_buf"] or c.n_out
+        if s["out_rows"]:  # plain rows [H_out * W_out (+ one spare image row), C]
+            c.out_border, c.out_Wp, c.out_shape = 0, c.W_out, (n_buf, c.H_out + 1, c.W_out, c.out_cstride)
+        else:
+            c.out_border, c.out_Wp, c.out_shape = 1, c.W_out + 2, (n_buf, c.H_out + 2, c.W_out + 2, c.out_cstride)
+        c.res = None
+        if s["res"]:  # written everywhere, border and the channels beside the slice included
+            c.res = (torch.randn((c.n_out,) + c.out_shape[1:], generator=g) * 64).to(BF)
+        return c
+    return _cached(("conv", name), build)
+
+
+def conv_want(c: Case, mistake=None) -> torch.Tensor:
+    """bf16 [n_out, H_out, W_out, Cout]: what the launch must leave in channels out_coff .. out_coff + Cout of the interior of its output frames."""
+    y = bf16_rne(conv_frames_f64([c.in_stack[i] for i in c.in_idx], c.w, c.b, c.n_out, KT=c.KT, KH=c.KH, KW=c.KW, st=c.st, ss=c.ss, H_out=c.H_out,
+                                 W_out=c.W_out, in_off=c.in_off, cout_slice=c.cout_slice, mistake=mistake))
+    if c.res is not None:
+        o = 0 if mistake == "residual read without border offset" else c.out_border
+        r = c.res[:, o:o + c.H_out, o:o + c.W_out, c.out_coff:c.out_coff + c.Cout]
+        y = torch.add(r.float(), y.float()).to(BF)  # (an fp32 add of two bf16 values, rounded once: the kernel's epilogue)
+    return y
+
+
+def conv_mistakes_for(c: Case):
+    """The entries of CONV_MISTAKES that name a different computation for this launch."""
+    m = []
+    if c.in_off:
+        m += ["in_off ignored", "in_off on rows only", "in_off on columns only"]
+    if (c.ss > 1 and max(c.KH, c.KW) > 1) or (c.st > 1 and c.KT > 1):
+        m.append("stride multiplies the tap too")
+    if c.KH == c.KW and c.KH > 1:
+        m.append("kh and kw swapped")
+    if c.st > 1 and c.KT > 1 and c.n_out > 1:
+        m.append("frame t+kt instead of t*st+kt")
+    if c.ss == 2 and c.in_off == 1 and c.KH == 3:
+        m.append("symmetric pad instead of bottom/right pad")
+    if c.cout_slice[0] > 0:
+        m += ["second slice uses weight rows 0..C", "second slice uses bias rows 0..C"]
+    if c.res is not None and c.out_border:
+        m.append("residual read without border offset")
+    return m
+
+
+def conv_place(c: Case, buf: torch.Tensor, want: torch.Tensor) -> torch.Tensor:
+    """`buf` (the output buffer as it was before the launch) with `want` where the launch writes: what the WHOLE buffer must hold afterwards."""
+    out = buf.clone()
+    o = c.out_border
+    idx = torch.tensor(c.out_idx, device=buf.device)
+    out[idx, o:o + c.H_out, o:o + c.W_out, c.out_coff:c.out_coff + c.Cout] = want.to(buf.device)
+    return out
+
+
+# ---- RMS_norm over channels (+ SiLU) --------------------------------------------------------------------------------------------------------
+# Rows of +-2^k, one k per pixel: the sum of squares is n 4^k in any order (n live channels), and for a full row sqrtf(C) / sqrtf(C 4^k) is
+# 2^-k exactly (a correctly rounded square root commutes with a factor 4^k): the result is bf16(+-gamma[c]).  Rows with n < C live
+# channels and all-zero pixels follow the fp32 restatement of the kernel's three operations (`rms_restate_f32`), evaluated on the CPU.
+RMS_CS = (32, 96, 128, 192, 384, 512)   # every (active lanes, chunks per lane) pair of the launcher: (4, 1) (12, 1) (16, 1) (12, 2) (16, 3) (16, 4)
+RMS_WS = (1, 17, 70, 129)               # a row that ends inside, at (64 + 6: the PER >= 3 bodies span 32) and one past a workgroup's pixels
+RMS_MISTAKES = ("norm of y", "norm before the bf16 rounding", "gamma of the neighbour chunk")
+SILU_LOG2E = -1.4426950408889634
+
+
+def ss_exact_in_any_order(x: torch.Tensor, quantum) -> bool:
+    """Is every partial sum of squares over the last axis exact in fp32 whatever the order?  x / quantum are integers and the total of their
+    squares stays below 2^24 (quantum: a power of two, a scalar or one per row)."""
+    q = x.double() / quantum
+    return bool((q == q.round()).all()) and bool(((q * q).sum(-1) < 2 ** 24).all())
+
+
+def _fl(x64: torch.Tensor) -> torch.Tensor:
+    """One rounding to fp32, the value kept in fp64."""
+    return x64.float().double()
+
+
+def rms_restate_f32(x: torch.Tensor, gamma: torch.Tensor, gshift: int = 0, check: bool = True) -> torch.Tensor:
+    """The kernel's operations in fp32, one rounding each: scale = fl(fl(sqrt(C)) / max(fl(sqrt(ss)), 1e-12)), pre = fl(fl(x * scale) * gamma)
+    -> fp32 [..., C], the value BEFORE the SiLU and the rounding to bf16.  Every operation is carried out in fp64 on fp32 operands and rounded
+    once to fp32: for *, / and sqrt that IS the correctly rounded fp32 operation (53 >= 2 * 24 + 2 bits: the second rounding is innocuous),
+    whatever the host's vector unit does with fp32.  ss is the exact sum of squares (asserted to be exact in fp32; `ss_exact_in_any_order` is
+    the recipes' business).  gshift: gamma[c + gshift] in place of gamma[c]."""
+    C = x.shape[-1]
+    xd = x.double()
+    ss64 = (xd ** 2).sum(-1, keepdim=True)
+    ss = exact_f64(ss64).double() if check else _fl(ss64)
+    floor = torch.tensor(1e-12, dtype=torch.float32).double()
+    scale = _fl(_fl(torch.sqrt(torch.tensor(float(C), dtype=torch.float64))) / torch.clamp(_fl(torch.sqrt(ss)), min=floor))
+    return _fl(_fl(xd * scale) * gamma.double().roll(-gshift)).float()
+
+
+def rms_f64(x: torch.Tensor, gamma: torch.Tensor) -> torch.Tensor:
+    """x / max(||x||, 1e-12) * sqrt(C) * gamma in fp64 (F.normalize semantics), before any rounding."""
+    xd = x.double()
+    nrm = xd.norm(dim=-1, keepdim=True).clamp(min=1e-12)
+    return xd / nrm * math.sqrt(x.shape[-1]) * gamma.double()
+
+
+def silu_f64(pre: torch.Tensor) -> torch.Tensor:
+    """bf16 of the fp64 SiLU of an exactly known fp32 pre-activation."""
+    p = pre.double()
+    return (p / (1.0 + torch.exp(-p))).float().to(BF)
+
+
+def silu_fast_f32(pre: torch.Tensor) -> torch.Tensor:
+    """csrc/ce_common.h's silu_fast with the CPU's fp32 operations in place of v_exp_f32 and v_rcp_f32: x * (1 / (1 + exp2(-log2(e) x)))."""
+    one = torch.ones((), dtype=torch.float32)
+    return torch.mul(pre, torch.div(one, torch.add(torch.exp2(torch.mul(pre, torch.tensor(SILU_LOG2E, dtype=torch.float32))), one)))
+
+
+def ulp_distance(a: torch.Tensor, b: torch.Tensor) -> int:
+    """The largest distance of two bf16 (fp32) tensors in units in the last place."""
+    return int((_ordered(a) - _ordered(b.to(a.device))).abs().max())
+
+
+# Tolerance of the comparisons that hold a SiLU: the largest distance, in bf16 ulps, between the CPU's fp32 evaluation of silu_fast and the fp64
+# SiLU on the pre-activations of every SiLU launch of the GPU file (measured by test_exact_constructions.py, which asserts the figure), plus
+# one ulp for the two hardware operations (v_exp_f32 and v_rcp_f32, one fp32 ulp each).
+SILU_F32_VS_F64_ULPS = 1
+SILU_ULPS = SILU_F32_VS_F64_ULPS + 1
+
+
+def silu_unequal_allowed(pre: torch.Tensor) -> int:
+    """How many SiLU results may differ from the fp64 answer at all (each of them within SILU_ULPS).  A result differs when a bf16 rounding
+    boundary lies between the true value and the computed one.  Relative error of silu_fast at x: the exponent -log2(e) x carries two fp32
+    roundings (the constant, the product) = 2 |x| 2^-24 relative in exp2's value; v_exp_f32 2 2^-24, the add 2^-24, v_rcp_f32 2 2^-24, the
+    product 2^-24: (2 |x| + 6) 2^-24 in all.  Rounding boundaries lie more than 2^-8 apart relative to the value, so an element differs with
+    probability <= (2 |x| + 6) 2^-16: the expected count lambda is the sum of that, and the allowance lambda + 4 sqrt(lambda) + 1 (four
+    standard deviations of a Poisson count, and one element for the small launches)."""
+    lam = float((2.0 * pre.double().abs() + 6.0).sum()) * 2.0 ** -16
+    return int(lam + 4.0 * math.sqrt(lam) + 1.0)
+
+
+def rms_case(C: int, T: int, H: int, W: int, diverse: bool = False) -> Case:
+    """One ce_rms_silu_bf16 launch: x [T, H+2, W+2, C] bordered input (the border holds other data), gamma, and per pixel a kind: 0 a full
+    row of +-2^k (k in -6..6 per pixel), 1 a row with n < C live channels (the others zero), 2 all zeros.  diverse (the SiLU launches): every
+    non-zero pixel is of kind 1 with C/4 <= n <= C, so that the pre-activations take many values, |pre| <= 2 max|gamma| = 8."""
+    def build():
+        g = torch.Generator().manual_seed(8000 + C * 7 + W * 3 + T + H + (1 if diverse else 0))
+        c = Case()
+        c.C, c.T, c.H, c.W = C, T, H, W
+        npix = T * H * W
+        k = torch.randint(-6, 7, (npix, 1), generator=g).double()
+        v = (torch.randint(0, 2, (npix, C), generator=g).double() * 2 - 1) * torch.exp2(k)
+        i = torch.arange(npix)
+        kind = torch.where(i % 7 == 5, 2, torch.where(i % 7 == 3, 1, 0))
+        if diverse:
+            kind = torch.where(kind == 2, 2, 1)
+        for p in (kind == 1).nonzero()[:, 0].tolist():
+            n = int(torch.randint(max(C // 4, 1), C + 1 if diverse else C, (1,), generator=g))
+            v[p, torch.randperm(C, generator=g)[n:]] = 0
+        v[kind == 2] = 0
+        c.kind = kind.view(T, H, W)
+        c.quantum = torch.exp2(k).view(T, H, W)
+        c.x = v.to(BF).view(T, H, W, C)
+        assert torch.equal(c.x.double().view(npix, C), v)
+        c.gamma = rms_weights(C, g)
+        c.x_stored = torch.full((T, H + 2, W + 2, C), 96.0, dtype=BF)  # (a border read in place of a pixel: another norm, another value)
+        c.x_stored[:, 1:-1, 1:-1] = c.x
+        return c
+    return _cached(("rms", C, T, H, W, diverse), build)
+
+
+def rms_ordinary(C: int, T: int, H: int, W: int):
+    """(x [T, H, W, C] bf16, gamma fp32 [C]): ordinary random data."""
+    g = torch.Generator().manual_seed(8500 + C + W)
+    return (torch.randn(T, H, W, C, generator=g) * 2).to(BF), 1.0 + 0.25 * torch.randn(C, generator=g)
+
+
+def rms_place(buf: torch.Tensor, want: torch.Tensor, border: int) -> torch.Tensor:
+    """The whole output buffer after the launch: `want` [T, H, W, C] in the interior of bordered frames [T, H+2, W+2, C] (border 1) or in the
+    first T H W rows of a plain row buffer [rows, C] (border 0); everything else as it was."""
+    out = buf.clone()
+    if border:
+        out[:, 1:-1, 1:-1] = want.to(buf.device)
+    else:
+        out[:want.numel() // want.shape[-1]] = want.reshape(-1, want.shape[-1]).to(buf.device)
+    return out
+
+
+# ---- the stride-1 3 x 3 (x 3) conv onto 96 channels with the next RMS_norm (+ SiLU) in its epilogue -----------------------------------------------
+# y = bf16(conv + bias) made exactly known AND norm-friendly: inputs +-2^k (one k per input pixel), every output channel ONE weight +-1 at
+# its own tap and input channel, bias 0 - y[p][co] is one input element or 0 (a tap on the border, on a zeroed pixel or on a causal front
+# frame).  All 27 taps and every 32-channel chunk of the input are addressed.  The norm of that y: `rms_restate_f32`.
+FUSED_CINS = (32, 96, 192)
+FUSED_FRAMES = ((1, 3, 5), (2, 5, 7), (2, 40, 64))   # the last one crosses position tiles (510 positions each) and ends in a ragged one
+
+
+def fused_case(Cin: int, KT: int, T: int, H: int, W: int, kind: str) -> Case:
+    """kind "single": k in -3..3 per input pixel, no residual (every pixel's squares are multiples of 2^-6 below 2^6: exact in any order).
+    kind "residual": k = 0 and a residual of the SAME sign as y, j 2^-10 with 0 < j < 256 (j 2^-7 with |j| < 128 where y = 0): res + y lies in
+    +-[1, 1.25), exact in fp32, and needs a real rounding to bf16's 2^-7 grid - bf16(res + y), y and the unrounded sum are three different
+    rows, and all squares are multiples of 2^-14 below 2^2.  kind "ordinary": `int_rows` data on every tap, data in the front frames, a
+    dyadic bias.  in_stack [KT-1 + T + 1, H+2, W+2, Cin] (front frames, chunk, zeroed slack frame); w5 [96, Cin, KT, 3, 3]; y bf16 [T, H, W, 96]."""
+    def build():
+        g = torch.Generator().manual_seed(9000 + Cin * 5 + KT * 3 + T + H + W + len(kind))
+        c = Case()
+        c.Cin, c.KT, c.T, c.H, c.W, c.kind, Cout = Cin, KT, T, H, W, kind, 96
+        n_in = T + KT - 1
+        taps = KT * 9
+        stack = torch.zeros(n_in + 1, H + 2, W + 2, Cin, dtype=torch.float64)
+        if kind == "ordinary":
+            stack[:n_in, 1:-1, 1:-1] = int_rows(n_in * H * W, Cin, g, emin=-1, emax=-1).double().view(n_in, H, W, Cin)
+            wp = int_rows(Cout, taps * Cin, g, emin=-2, emax=2).view(Cout, taps, Cin)
+            c.b = int_vector(Cout, g)
+        else:
+            k = torch.randint(-3, 4, (T, H, W, 1), generator=g).double() if kind == "single" else torch.zeros(T, H, W, 1, dtype=torch.float64)
+            x = (torch.randint(0, 2, (T, H, W, Cin), generator=g).double() * 2 - 1) * torch.exp2(k)
+            if H >= 5:
+                x[:, 0:3, 1:4] = 0  # a 3 x 3 block of zero pixels in every frame: the output pixel (1, 2) is all zeros
+            stack[KT - 1:n_in, 1:-1, 1:-1] = x
+            co = torch.arange(Cout)
+            c.tap_of, c.ci_of = co % taps, (co * 37 + 5) % Cin
+            wp = torch.zeros(Cout, taps, Cin, dtype=torch.float64)
+            wp[co, c.tap_of, c.ci_of] = torch.randint(0, 2, (Cout,), generator=g).double() * 2 - 1
+            wp = wp.to(BF)
+            c.b = torch.zeros(Cout)
+        c.in_stack = stack.to(BF)
+        c.wp = wp.contiguous()
+        c.w5 = wp.view(Cout, KT, 3, 3, Cin).permute(0, 4, 1, 2, 3).contiguous()
+        y64 = conv_frames_f64([c.in_stack[i] for i in range(n_in)], c.wp, c.b, T, KT=KT, KH=3, KW=3, st=1, ss=1, H_out=H, W_out=W, in_off=0)
+        c.y = bf16_rne(y64)
+        c.gamma = rms_weights(Cout, g)
+        c.res = None
+        if kind == "residual":
+            yd = c.y.double()
+            near = torch.randint(1, 256, yd.shape, generator=g).double() * 2.0 ** -10 * yd.sign()
+            far = torch.randint(-127, 128, yd.shape, generator=g).double() * 2.0 ** -7
+            r = torch.where(yd != 0, near, far).to(BF)
+            c.res = torch.full((T, H + 2, W + 2, Cout), 3.0, dtype=BF)  # (the border holds data: it must not reach either output)
+            c.res[:, 1:-1, 1:-1] = r
+            c.sum32 = torch.add(r.float(), c.y.float())
+            assert torch.equal(c.sum32.double(), r.double() + yd)
+            c.v = c.sum32.to(BF)
+        return c
+    return _cached(("fused", Cin, KT, T, H, W, kind), build)
+
+
+def fused_pre(c: Case, mistake=None) -> torch.Tensor:
+    """fp32 [T, H, W, 96]: the pre-activation of the normalised output (`rms_restate_f32` of bf16(res + y), or of y without a residual);
+    `mistake`: one of RMS_MISTAKES."""
+    assert mistake is None or mistake in RMS_MISTAKES
+    row = c.v if c.res is not None else c.y
+    if mistake == "norm of y":
+        row = c.y
+    elif mistake == "norm before the bf16 rounding":
+        return rms_restate_f32(c.sum32, c.gamma, check=False)
+    return rms_restate_f32(row, c.gamma, gshift=4 if mistake == "gamma of the neighbour chunk" else 0)  # (a lane owns 4 consecutive channels)

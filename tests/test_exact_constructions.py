@@ -770,3 +770,168 @@ def test_bend_gemm_case_is_exact_and_spans_the_bend(M, N, K):
     x = bf16_rne(exact).float()
     assert x.min().item() > -9.0 and (x.abs() < 4).double().mean().item() >= 0.5 and _real_rounding_share(bf16_rne(exact), exact) > 0.25
     assert x.min().item() < -3.0 and x.max().item() > 3.0                                 # both sides of the bend
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the VAE's implicit-GEMM conv, RMS_norm (+ SiLU) and the conv with the norm in its epilogue (every launch of tests/test_exact_vae_ops_gpu.py)
+# ------------------------------------------------------------------------------------------------------------------------------------
+CONV_NAMES = list(X.CONV_CASES)
+SEEN_SHARE = 0.01  # every mistake that applies to a launch changes at least this share of its expected output elements (after the bf16 rounding)
+
+
+def _differing_share(a, b):
+    return X.mismatches(a, b, 0).double().mean().item()
+
+
+@pytest.mark.parametrize("name", CONV_NAMES)
+def test_conv_case_is_exact_and_sees_every_mistake_that_applies(name):
+    """The sums are exact in fp32 (`bf16_rne` asserts it) and need a real rounding; positions the engine's layout does not zero hold data; each
+    applicable entry of CONV_MISTAKES moves >= 1 % of the expected elements."""
+    c = X.conv_case(name)
+    want = X.conv_want(c)
+    assert tuple(want.shape) == (c.n_out, c.H_out, c.W_out, c.Cout)
+    exact = X.conv_frames_f64([c.in_stack[i] for i in c.in_idx], c.w, c.b, c.n_out, KT=c.KT, KH=c.KH, KW=c.KW, st=c.st, ss=c.ss, H_out=c.H_out,
+                              W_out=c.W_out, in_off=c.in_off, cout_slice=c.cout_slice)
+    if c.KT * c.KH * c.KW * c.Cin >= 96:
+        assert _real_rounding_share(bf16_rne(exact), exact) > 0.05
+    rows = (torch.arange(c.H_out) * c.ss + c.in_off)[:, None]
+    assert int(rows.max()) + c.KH - 1 < c.in_stack.shape[1] and (c.W_out - 1) * c.ss + c.in_off + c.KW - 1 < c.in_stack.shape[2]  # every read in the frame
+    assert (c.n_out - 1) * c.st + c.KT <= len(c.in_idx) <= 16
+    live = [i for i in set(c.in_idx) if i not in X.CONV_CASES[name]["zero_frames"]]
+    pad = X.CONV_CASES[name]["pad"]
+    for i in live:  # what is not padding holds data: at most the share of zeros that integers in -4..4 bring
+        f = c.in_stack[i]
+        edges = {"top": f[0, 1:-1], "left": f[1:-1, 0], "bottom": f[-1], "right": f[:, -1]}
+        for side, e in edges.items():
+            zeroed = pad == "all" or (pad == "br" and side in ("bottom", "right"))
+            if X.CONV_CASES[name]["in_rows"]:
+                continue
+            assert bool((e == 0).all()) if zeroed else (e != 0).double().mean().item() > 0.8, (name, i, side)
+    mistakes = X.conv_mistakes_for(c)
+    for m in mistakes:
+        share = _differing_share(X.conv_want(c, m), want)
+        assert share >= SEEN_SHARE, (name, m, share)
+    for m in set(X.CONV_MISTAKES) - set(mistakes) - {"symmetric pad instead of bottom/right pad", "kh and kw swapped"}:
+        assert torch.equal(X.conv_want(c, m), want), (name, m)  # (what does not apply names the same computation)
+
+
+def test_every_conv_mistake_is_seen_by_some_case_and_the_halves_share_their_operands():
+    seen = set()
+    for name in CONV_NAMES:
+        seen |= set(X.conv_mistakes_for(X.conv_case(name)))
+    assert seen == set(X.CONV_MISTAKES)
+    lo, hi = X.conv_case("time up lo"), X.conv_case("time up hi")
+    assert torch.equal(lo.in_stack, hi.in_stack) and torch.equal(lo.w, hi.w) and torch.equal(lo.b, hi.b) and lo.cout_slice == (0, 96) and hi.cout_slice == (96, 192)
+    assert sorted(lo.out_idx + hi.out_idx) == list(range(6))
+
+
+@pytest.mark.parametrize("name", ["3x3 s2 even KT1", "3x3 s2 odd KT3", "time down T7", "k3 384->24", "1x1 off1 M126"])
+def test_conv_frames_f64_equals_the_library_convolution_in_fp64(name):
+    """The restated formula against torch's conv3d on the image the network sees: the interior of the stored frames under the reference's padding -
+    ZeroPad2d((0, 1, 0, 1)) before the stride-2 conv, one zero pixel all round a stride-1 3 x 3, none for a 1 x 1 or a (3, 1, 1)."""
+    c = X.conv_case(name)
+    x = torch.stack([c.in_stack[i] for i in c.in_idx]).double()[:, 1:-1, 1:-1]                  # [n_in, H, W, Cin]
+    w5 = c.w.double().view(c.Cout_all, c.KT, c.KH, c.KW, c.Cin).permute(0, 4, 1, 2, 3)
+    xi = x.permute(3, 0, 1, 2)[None]
+    if c.ss == 2:
+        xi = torch.nn.functional.pad(xi, (0, 1, 0, 1))
+    elif c.KH == 3:
+        xi = torch.nn.functional.pad(xi, (1, 1, 1, 1))
+    lib = torch.nn.functional.conv3d(xi, w5, c.b.double(), stride=(c.st, c.ss, c.ss))[0].permute(1, 2, 3, 0)
+    mine = X.conv_frames_f64([c.in_stack[i] for i in c.in_idx], c.w, c.b, c.n_out, KT=c.KT, KH=c.KH, KW=c.KW, st=c.st, ss=c.ss, H_out=c.H_out,
+                             W_out=c.W_out, in_off=c.in_off)
+    assert torch.equal(mine, lib[:c.n_out, :c.H_out, :c.W_out])
+
+
+def _scrambled_ss(x, gen):
+    """fp32 sum of squares over the last axis in a random order of the channels, accumulated one element at a time."""
+    xf = x.float().reshape(-1, x.shape[-1])[:, torch.randperm(x.shape[-1], generator=gen)]
+    acc = torch.zeros(xf.shape[0])
+    for j in range(xf.shape[1]):
+        acc = acc + xf[:, j] * xf[:, j]
+    return acc
+
+
+@pytest.mark.parametrize("diverse", [False, True])
+@pytest.mark.parametrize("C", X.RMS_CS)
+def test_rms_case_is_exact_in_any_order_and_full_rows_return_gamma(C, diverse):
+    g = torch.Generator().manual_seed(C)
+    worst = 0
+    for W in X.RMS_WS:
+        c = X.rms_case(C, 2, 3, W, diverse)
+        assert X.ss_exact_in_any_order(c.x, c.quantum[..., None])
+        assert torch.equal(_scrambled_ss(c.x, g).double(), (c.x.double() ** 2).sum(-1).reshape(-1))
+        pre = X.rms_restate_f32(c.x, c.gamma)
+        full, zero = c.kind == 0, c.kind == 2
+        if not diverse:  # a full row of +-2^k returns +-gamma exactly: sqrtf(C) / sqrtf(C 4^k) = 2^-k
+            assert torch.equal(pre[full], c.x[full].float().sign() * c.gamma)
+            if W > 1:
+                assert bool(full.any()) and bool((c.kind == 1).any()) and bool(zero.any())
+            assert _real_rounding_share(pre.to(BF), pre.double()) > 0.1
+        assert bool((pre[zero] == 0).all()) and bool(torch.isfinite(pre).all())
+        live = (c.x != 0).sum(-1)[c.kind == 1]
+        assert live.numel() == 0 or (int(live.min()) >= max(C // 4, 1) and (diverse or int(live.max()) < C))
+        # the neighbour chunk's gamma (16-byte chunk = 8 channels) and the fp64 formula's answer: seen, and within one ulp
+        assert _differing_share(X.rms_restate_f32(c.x, c.gamma, gshift=8).to(BF), pre.to(BF)) >= SEEN_SHARE
+        assert X.ulp_distance(pre.to(BF), X.rms_f64(c.x, c.gamma).float().to(BF)) <= 1
+        if diverse:
+            assert float(pre.abs().max()) <= 8.0
+            d = X.ulp_distance(X.silu_fast_f32(pre).to(BF), X.silu_f64(pre))
+            print(f"MEASURED rms C={C} W={W}: fp32 silu_fast vs fp64 SiLU {d} bf16 ulp, unequal {int(X.mismatches(X.silu_fast_f32(pre).to(BF), X.silu_f64(pre)).sum())}"
+                  f" of {pre.numel()} (allowed {X.silu_unequal_allowed(pre)})")
+            assert int(X.mismatches(X.silu_fast_f32(pre).to(BF), X.silu_f64(pre)).sum()) <= X.silu_unequal_allowed(pre)
+            worst = max(worst, d)
+    assert worst <= X.SILU_F32_VS_F64_ULPS
+
+
+FUSED_SHAPES = [(Cin, KT) + f for Cin in X.FUSED_CINS for KT in (1, 3) for f in X.FUSED_FRAMES]
+
+
+@pytest.mark.parametrize("Cin,KT,T,H,W", FUSED_SHAPES)
+def test_fused_case_y_is_one_input_element_and_every_tap_and_chunk_is_addressed(Cin, KT, T, H, W):
+    c = X.fused_case(Cin, KT, T, H, W, "single")
+    assert set(c.tap_of.tolist()) == set(range(KT * 9)) and set((c.ci_of // 32).tolist()) == set(range(Cin // 32))
+    assert len(set(zip(c.tap_of.tolist(), c.ci_of.tolist()))) == 96
+    yd = c.y.double()
+    mag = yd.abs()[yd != 0]
+    assert bool((torch.log2(mag) == torch.log2(mag).round()).all()) and 2.0 ** -3 <= float(mag.min()) and float(mag.max()) <= 8.0
+    assert X.ss_exact_in_any_order(c.y, 2.0 ** -3)
+    g = torch.Generator().manual_seed(Cin + KT)
+    assert torch.equal(_scrambled_ss(c.y, g).double(), (yd ** 2).sum(-1).reshape(-1))
+    if H >= 5:
+        assert bool((yd[:, 1, 2] == 0).all())                               # the all-zero pixel
+    assert (yd != 0).double().mean().item() > 0.15                          # (T = 1 under KT = 3: two of three taps fall on front frames)
+    if H * W >= 35:
+        assert len(set(mag.tolist())) == 7                                  # every k in -3..3
+    pre = X.fused_pre(c)
+    assert bool((pre[yd.abs().sum(-1) == 0] == 0).all()) and bool(torch.isfinite(pre).all())
+    assert X.ulp_distance(pre.to(BF), X.rms_f64(c.y, c.gamma).float().to(BF)) <= 1
+    assert _differing_share(X.fused_pre(c, "gamma of the neighbour chunk").to(BF), pre.to(BF)) >= SEEN_SHARE
+    d = X.ulp_distance(X.silu_fast_f32(pre).to(BF), X.silu_f64(pre))
+    assert d <= X.SILU_F32_VS_F64_ULPS, d
+    assert int(X.mismatches(X.silu_fast_f32(pre).to(BF), X.silu_f64(pre)).sum()) <= X.silu_unequal_allowed(pre)
+
+
+@pytest.mark.parametrize("Cin,KT,T,H,W", FUSED_SHAPES)
+def test_fused_residual_case_tells_the_three_candidate_rows_apart(Cin, KT, T, H, W):
+    """out_stack = bf16(res + y) needs a real rounding, its squares sum exactly in any order, and the norm of y, the norm of the unrounded sum and
+    the neighbour chunk's gamma each give other bits than the norm of bf16(res + y)."""
+    c = X.fused_case(Cin, KT, T, H, W, "residual")
+    live = c.y != 0
+    assert (c.v.double() != c.sum32.double())[live].double().mean().item() > 0.8  # a real rounding wherever the conv contributes
+    assert X.ss_exact_in_any_order(c.v, 2.0 ** -7)
+    g = torch.Generator().manual_seed(Cin + KT + 1)
+    assert torch.equal(_scrambled_ss(c.v, g).double(), (c.v.double() ** 2).sum(-1).reshape(-1))
+    want = X.fused_pre(c).to(BF)
+    for m in X.RMS_MISTAKES:
+        share = _differing_share(X.fused_pre(c, m).to(BF), want)
+        assert share >= (SEEN_SHARE if m == "norm before the bf16 rounding" else 0.5), (m, share)
+
+
+@pytest.mark.parametrize("Cin,KT", [(32, 3), (96, 1), (192, 3)])
+def test_fused_ordinary_case_is_exact_and_rounds(Cin, KT):
+    c = X.fused_case(Cin, KT, 2, 5, 7, "ordinary")
+    n_in = c.T + KT - 1
+    exact = X.conv_frames_f64([c.in_stack[i] for i in range(n_in)], c.wp, c.b, c.T, KT=KT, KH=3, KW=3, st=1, ss=1, H_out=c.H, W_out=c.W, in_off=0)
+    assert _real_rounding_share(c.y, exact) > 0.25
+    assert bool((c.in_stack[:KT - 1, 1:-1, 1:-1] != 0).any()) or KT == 1

@@ -5,25 +5,20 @@ upsample2x and zero_border must equal their torch counterparts bit for bit."""
 import pytest
 import torch
 
-from exact_util import BF, assert_exact, bf16_rne, int_rows, int_vector
+from exact_util import BF, assert_exact, bf16_rne, conv_frames_f64, int_rows, int_vector
 
 pytestmark = pytest.mark.gpu
 
 
 def _conv_f64(x, w):
-    """x [n_in, H, W, Cin] (bf16, the first KT - 1 frames are the causal front frames), w [Cout, Cin, KT, 3, 3] -> fp64 [T, H, W, Cout]
-    as 9 KT shifted fp64 GEMMs on the device (exact for this data; no library convolution algorithm in the way)."""
+    """x [n_in, H, W, Cin] (bf16, the first KT - 1 frames are the causal front frames), w [Cout, Cin, KT, 3, 3] -> fp64 [T, H, W, Cout]: the
+    general reference of exact_util.py on the zero-bordered frames (9 KT shifted fp64 GEMMs per output frame, on the device; exact for this
+    data; no library convolution algorithm in the way)."""
     n_in, H, W, Cin = x.shape
     Cout, _, KT = w.shape[:3]
-    T = n_in - KT + 1
-    xp = torch.nn.functional.pad(x.double(), (0, 0, 1, 1, 1, 1))  # zero spatial padding
-    wd = w.double()
-    acc = torch.zeros(T, H, W, Cout, dtype=torch.float64, device=x.device)
-    for kt in range(KT):
-        for kh in range(3):
-            for kw in range(3):
-                acc += xp[kt:kt + T, kh:kh + H, kw:kw + W] @ wd[:, :, kt, kh, kw].t()
-    return acc
+    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))  # zero spatial padding: the stored frame's border
+    wp = w.permute(0, 2, 3, 4, 1).reshape(Cout, KT * 9, Cin)
+    return conv_frames_f64([xp[i] for i in range(n_in)], wp, None, n_in - KT + 1, KT=KT, KH=3, KW=3, st=1, ss=1, H_out=H, W_out=W, in_off=0)
 
 
 def _operands(KT, Cin, Cout, T, H, W, seed):
