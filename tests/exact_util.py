@@ -9,6 +9,11 @@ Attention needles (`needle_q`, `needle_k`): every query row has one winning key 
 away from zero).  Keys a kernel must not read
 (rows past the valid length, padding, the neighbouring samples) win outright if they are read at all.
 
+Self-attention sums (`sums_case`, `SUM_CASES`, `sum_named_case`, `attention_sums_f64`, `SUM_MISTAKES`, `online_softmax_f32`, `sum_margins`,
+`sum_split_count`): tie rows (a set of keys scores exactly 0, the row is the mean of the set's V rows) and stair rows (keys j octaves below
+the top, one nonzero V entry per column, the row is +-r / 8) in the same 32-row groups as needle rows, silent all-zero keys behind the
+valid ones - they pin the row sum, the accumulation over tiles, the rescale and attention_1head's split merge.
+
 MXFP8 attention (`mx_case`, `mxfp8_attention_f64`, `MX_MISTAKES`): the same idea on operands handed over as e4m3 bytes with E8M0 block
 scales - integer scores in the exp2 domain, every P a power of two or 0, needle rows and tie rows, scales that a wrong scale byte betrays.
 
@@ -571,6 +576,358 @@ def cross_attention_f64(c: CrossCase, mistake=None) -> torch.Tensor:
         o2 = seg(qh, c.k2[b * k2_rows:][:c.len2], c.v2t[:, b * c2:b * c2 + c.len2], c.len2, -1, 0.0)
         out[b * nq:(b + 1) * nq] = (o1.float().to(BF).float() + o2.float().to(BF).float()).to(BF)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# self-attention sums (ce_attention_bf16 / _batched / _vt / _vt_blocked / _1head): tie rows and stair rows in one launch with needle rows
+#
+# A needle row pins addressing; it says nothing about the row sum l, the accumulation of P.V over keys and tiles, or a rescale by a factor
+# that is neither 1 nor 0.  Two more row kinds do, interleaved with the needle rows inside every 32-row wave group (`sum_row_kinds`; rows
+# 64..127 hold no needle row, so some waves never leave the speculative route on a needle's account).  Their queries are zero on the digit
+# dims and keep the neighbour bonus and NEEDLE_BIG on the invalid dim.
+# Tie rows: the keys of a tie set carry 0 on the set's dim (SUM_TIE_DIM + 0..3: sets of 2, 4, 8 and 32 or 64 keys), every other key 1, the
+# query -SUM_TIE_T: the set scores exactly 0 under any scale, every loser trails by >= TIE_GAP nats (its exp2 is 0 in fp32), V on the set is
+# small integers times one power of two with one sign per column, and the row is the set's mean - exactly.  The large set holds key 0, the
+# last valid key and a key in every key tile (64 keys; 32 for attention_1head: both sides of every key-split boundary).
+# Stair rows: the stair keys carry their level j on SUM_STEP_DIM and SUM_STEP_DIM + 1 (every other key SUM_OFF_LEVEL), the query -u: a key
+# at level j lies j octaves below the top.  Family "r" - the kernels that round Q * scale * log2(e) to bf16 before the first product
+# (attn_fwd_sp_kernel, attn_fwd_w4_kernel, ce_attn16.hip: `ops.attention` under waves 0 / 64, every attention_vt / attention_vt_blocked
+# selector): one component, 7.84375, whose rounded product is exactly 1.0 - integer scores, every P a power of two.  Family "f" - the
+# kernels that scale the fp32 score (the register-staged attn_fwd_kernel: `ops.attention` under waves 8 / 4, two-segment form included;
+# attn_1head_kernel): a coarse and a fine component whose sum times scale * log2(e) is within 2^-16 of 1.  sum 2^-j over the stair is a
+# power of two; V is sparse as in `flat_v1` - column c is nonzero at ONE stair key, +-r 2^level l / 8 - and the row is +-r / 8: every
+# column shows one key's weight, a wrong l or rescale shows in all of them.  Layouts of the levels over the 64-key tiles (`_stair_plan`):
+# falling (the offset never moves), rising by one octave per tile over five tiles (P runs above 1 in the speculative bodies, nothing
+# re-bases), jump (two keys ten octaves down, then 31 top keys in one tile: a lane's partial row sum passes 2^10 and the lazy bodies' +8).
+# Silent keys: in the `silent` cases the rows behind a sample's last valid key (past L, the blocked layout's padding tokens, past Nk) are
+# all-zero K rows over zero V: read by mistake they join every tie set and the stair's top, and change l and nothing else.  In the other
+# cases those rows win outright over POISON.
+# ------------------------------------------------------------------------------------------------------------------------------------
+SUM_TIE_DIM = 30        # dims 30..33: the tie sets of 2, 4, 8 and 32 / 64 keys
+SUM_TIE_T = 4096.0      # a tie row's losers trail by T * scale: 362 nats at head_dim 128, 209 at 384
+SUM_STEP_DIM = 40       # dims 40, 41: the level of a stair key
+SUM_OFF_LEVEL = 512.0   # ... and what every other key carries there: 512 octaves down
+SUM_STEP = {("r", 128): (7.84375, 0.0), ("f", 128): (7.84375, -0.00168609619140625), ("f", 384): (13.5625, 0.0203857421875)}
+SUM_PATTERN = (0, 5, 1, 5, 0, 2, 5, 0, 5, 3, 0, 5, 4, 0, 5, 5)  # 0 needle, 1..4 tie row of set 0..3, 5 stair
+# which family a selector of ce_set_attention_waves runs (the header comment above)
+SUM_FAMILY = {("attention", 0): "r", ("attention", 64): "r", ("attention", 8): "f", ("attention", 4): "f", ("attention_vt", 0): "r",
+              ("attention_vt", 128): "r", ("attention_vt", 129): "r", ("attention_vt", 16): "r", ("attention_vt_blocked", 0): "r",
+              ("attention_vt_blocked", 128): "r", ("attention_vt_blocked", 129): "r", ("attention_1head", 0): "f"}
+
+
+def sum_scale_log2e(C: int) -> float:
+    """The launchers' fp32 constant softmax_scale * 1.4426950408889634f at scale C^-1/2."""
+    return float(torch.tensor(C ** -0.5, dtype=torch.float32) * torch.tensor(LOG2E, dtype=torch.float32))
+
+
+def sum_row_kinds(n_q: int, pure: bool = False) -> torch.Tensor:
+    """int64 [n_q]: SUM_PATTERN repeated; rows 64..127 (all rows when `pure`) take a stair row in place of every needle row."""
+    i = torch.arange(n_q)
+    kind = torch.tensor(SUM_PATTERN)[i % len(SUM_PATTERN)]
+    no_needle = torch.ones(n_q, dtype=torch.bool) if pure else (i >= 64) & (i < 128)
+    return torch.where(no_needle & (kind == 0), torch.tensor(5), kind)
+
+
+def _stair_plan(layout: str, nt: int):
+    """([(64-key tile, level, keys)], sum of 2^-level over them) of a stair over nt key tiles."""
+    if layout == "falling":
+        top = 4 if nt >= 4 else 2
+        return [(0, 0, top)] + [(l * (nt - 1) // top, l, 2 ** l) for l in range(1, top + 1)], 2 * top
+    if layout == "rising":
+        assert nt >= 5
+        return [(4 - l, l, 2 ** l if l else 4) for l in range(4, -1, -1)], 8
+    assert layout == "jump" and nt >= 3, (layout, nt)
+    J = max(2, 2 * nt // 3)
+    return [(0, 10, 1), (1, 10, 1), (J, 0, 31)] + [(min(J + 1 + (l - 1) // 3, nt - 1), l, 1) for l in range(1, 10)], 32
+
+
+class SumsCase:
+    """The packed operands of one launch (CPU, bf16), its row kinds, tie sets and stairs, and its expected output."""
+
+
+def sums_case(n_q: int, n_k: int, heads: int, batch: int, seed: int, layout=("falling",), silent: bool = False, C: int = 128, stride=None,
+              extra: int = 64, tile: int = 64, nsplit: int = 1, families=("r", "f"), pure: bool = False) -> SumsCase:
+    """Needle, tie and stair rows of `batch` stacked samples.  Packed buffers: q[family] [batch n_q, D]; k, v [batch stride + extra, D] with
+    sample b's n_k valid keys from row b stride on (stride > n_k: the blocked layout's padding tokens, un-blocked) - the rows behind them
+    and the `extra` rows at the end are silent (zero K, zero V) or win if read (V = POISON); want [batch n_q, D].  layout: one per head,
+    cycling.  tile: the kernel's key tile (where the large tie set needs members), nsplit: the key split the launcher is expected to choose."""
+    assert (C == 128 or heads == 1) and all((f, C) in SUM_STEP for f in families)
+    gs, gt, gw, gv = (torch.Generator().manual_seed(seed * 4 + i) for i in range(4))  # tie sets, stairs, winners, V: one stream each
+    c = SumsCase()
+    H, B, D = heads, batch, heads * C
+    stride = n_k if stride is None else stride
+    nt, ntl = (n_k + 63) // 64, (n_k + tile - 1) // tile
+    big = 32 if ntl <= 32 else 64
+    assert ntl <= big and stride >= n_k
+    c.n_q, c.n_k, c.H, c.B, c.C, c.stride, c.extra, c.silent, c.tile, c.nsplit = n_q, n_k, H, B, C, stride, extra, silent, tile, nsplit
+    c.families, c.sizes, c.kind = tuple(families), (2, 4, 8, big), sum_row_kinds(n_q, pure)
+    c.layouts = [layout[h % len(layout)] for h in range(H)]
+    rows = B * stride + extra
+    k = torch.zeros(rows, H, C, dtype=torch.float64)
+    v = torch.zeros(rows, H, C, dtype=torch.float64)
+    q = {f: torch.zeros(B * n_q, H, C, dtype=torch.float64) for f in families}
+    want = torch.zeros(B * n_q, H, C, dtype=torch.float64)
+    c.sets, c.stair, c.win = [], [], torch.zeros(B, n_q, H, dtype=torch.int64)
+    needle, stair_rows = c.kind == 0, c.kind == 5
+    for b in range(B):
+        nb = stride + (extra if b == B - 1 else 0)
+        base = b * stride
+        behind = torch.arange(nb) >= n_k
+        k[base:base + nb, :, :128] = needle_k(nb, H, sample=b, invalid=None if silent else behind).view(nb, H, 128)
+        c.sets.append([])
+        c.stair.append([])
+        for h in range(H):
+            kh, vh = k[base:base + nb, h], v[base:base + nb, h]
+            # ---- tie sets: the large one first (key 0, the last valid key, one key per key tile), then random free keys
+            large = [0, n_k - 1]
+            for t in range(ntl):
+                lo, hi = t * tile, min((t + 1) * tile, n_k)
+                if not any(lo <= x < hi for x in large):
+                    large.append(lo + int(torch.randint(0, hi - lo, (1,), generator=gs)))
+            free = [x for x in torch.randperm(n_k, generator=gs).tolist() if x not in set(large)]
+            large += free[:big - len(large)]
+            free = [x for x in free if x not in set(large)]
+            sets = []
+            for s in (2, 4, 8):
+                sets.append(torch.tensor(sorted(free[:s])))
+                free = free[s:]
+            sets.append(torch.tensor(sorted(large)))
+            c.sets[b].append(sets)
+            # ---- the stair: `count` free keys of each planned tile at the planned level
+            plan, units = _stair_plan(c.layouts[h], nt)
+            skeys, slev = [], []
+            for (t, lev, count) in plan:
+                cand = [x for x in free if 64 * t <= x < 64 * (t + 1)]
+                assert len(cand) >= count, "stair recipe: a key tile has too few free keys"
+                pick = [cand[i] for i in torch.randperm(len(cand), generator=gt)[:count].tolist()]
+                free = [x for x in free if x not in set(pick)]
+                skeys += pick
+                slev += [lev] * count
+            skeys, slev = torch.tensor(skeys), torch.tensor(slev, dtype=torch.float64)
+            assert float(torch.exp2(-slev).sum()) == units
+            c.stair[b].append((skeys, slev, units))
+            # ---- K: tie dims, step dims; V: ordinary rows, the sets' integers, the stair's one entry per column
+            kh[:, SUM_TIE_DIM:SUM_TIE_DIM + 4] = 1.0
+            for s, members in enumerate(sets):
+                kh[members, SUM_TIE_DIM + s] = 0.0
+            kh[:, SUM_STEP_DIM:SUM_STEP_DIM + 2] = SUM_OFF_LEVEL
+            kh[skeys, SUM_STEP_DIM] = slev
+            kh[skeys, SUM_STEP_DIM + 1] = slev
+            vh[:] = needle_v(nb, C, gv).double()
+            means = []
+            for s, members in enumerate(sets):
+                ints = torch.randint(1, (3 if len(members) == 64 else 7) + 1, (len(members), C), generator=gv).double()
+                sign = torch.randint(0, 2, (C,), generator=gv).double() * 2 - 1
+                vh[members] = ints * sign * 2.0 ** int(torch.randint(-2, 3, (1,), generator=gv))
+                means.append(vh[members].mean(0))
+            col = torch.arange(C)
+            at = (col + int(torch.randint(0, len(skeys), (1,), generator=gv))) % len(skeys)  # column c's stair key: all of them, cycling
+            r = torch.randint(1, 8, (C,), generator=gv).double() * (torch.randint(0, 2, (C,), generator=gv).double() * 2 - 1)
+            vh[skeys] = 0.0
+            vh[skeys[at], col] = r * torch.exp2(slev[at]) * units / 8
+            if silent:
+                kh[behind] = 0.0
+            vh[behind] = 0.0 if silent else float(torch.tensor(POISON).to(BF))  # (as the buffers of the needle tests hold it)
+            # ---- winners of the needle rows: any key outside the stair (its V rows hold zeros)
+            avail = torch.tensor(sorted(set(range(n_k)) - set(skeys.tolist())))
+            c.win[b, :, h] = avail[winners_for(n_q, len(avail), 1, gw, must=(0, len(avail) - 1))[:, 0]]
+            wr = want[b * n_q:(b + 1) * n_q, h]
+            wr[needle] = vh[c.win[b, needle, h]]
+            for s in range(4):
+                wr[c.kind == 1 + s] = means[s]
+            wr[stair_rows] = r / 8
+        qn = needle_q(c.win[b], sample=b, batch=B).view(n_q, H, 128)
+        qn[~needle, :, 0:2 * NEEDLE_DIGITS] = 0.0
+        for s in range(4):
+            qn[c.kind == 1 + s, :, SUM_TIE_DIM + s] = -SUM_TIE_T
+        for f in families:
+            qf = qn.clone()
+            qf[stair_rows, :, SUM_STEP_DIM] = -SUM_STEP[(f, C)][0]
+            qf[stair_rows, :, SUM_STEP_DIM + 1] = -SUM_STEP[(f, C)][1]
+            q[f][b * n_q:(b + 1) * n_q, :, :128] = qf
+    for t in [k, v, want] + list(q.values()):
+        assert torch.equal(t.to(BF).double(), t), "sums recipe: a value is not exact in bf16"
+    c.q = {f: t.view(B * n_q, D).to(BF) for f, t in q.items()}
+    c.k, c.v, c.want = k.view(rows, D).to(BF), v.view(rows, D).to(BF), want.view(B * n_q, D).to(BF)
+    return c
+
+
+SUM_MISTAKES = ("a tied key dropped", "the last valid key dropped", "one silent key counted", "a tile's keys counted twice",
+                "rescale applied to O but not to l", "rescale applied one tile late", "split merge without the non-maximal splits' l",
+                "split merge with the splits' weights exchanged")
+
+
+def _sum_scores(c: SumsCase, family: str, b: int, h: int, n: int, f32: bool = False) -> torch.Tensor:
+    """Scores [n_q, n] in the exp2 domain of sample b, head h against the first n packed key rows of the sample, with the family's
+    rounding of the operands: "r" rounds fl32(q * scale * log2 e) to bf16 first, "f" scales the score.  fp64, or the kernels' fp32."""
+    sl2 = sum_scale_log2e(c.C)
+    qh = c.q[family][b * c.n_q:(b + 1) * c.n_q, h * c.C:(h + 1) * c.C]
+    kh = c.k[b * c.stride:b * c.stride + n, h * c.C:(h + 1) * c.C]
+    dt = torch.float32 if f32 else torch.float64
+    if family == "r":
+        return (qh.float() * sl2).to(BF).to(dt) @ kh.to(dt).t()
+    return (qh.to(dt) @ kh.to(dt).t()) * torch.tensor(sl2, dtype=dt)
+
+
+def attention_sums_f64(c: SumsCase, mistake=None, family=None) -> torch.Tensor:
+    """softmax(q k^T scale) v per sample and head on the PACKED buffers of `c`, plain fp64 (the exp2 domain, the family's operand rounding),
+    rounded to bf16 at the end (through fp32; no expected value lies near a rounding boundary of either).  `mistake` (one of SUM_MISTAKES): the same with one deliberate error; the two rescale mistakes walk the 64-key
+    tiles with a running maximum, the two merge mistakes the `c.nsplit` key splits of 32-key tiles (no change where nsplit == 1)."""
+    assert mistake is None or mistake in SUM_MISTAKES
+    family = family or c.families[0]
+    out = torch.empty(c.B * c.n_q, c.H * c.C, dtype=BF)
+    for b in range(c.B):
+        for h in range(c.H):
+            n = c.n_k + (1 if mistake == "one silent key counted" else 0)
+            s = _sum_scores(c, family, b, h, n)
+            vh = c.v[b * c.stride:b * c.stride + n, h * c.C:(h + 1) * c.C].double()
+            wgt = torch.ones(n, dtype=torch.float64)
+            if mistake == "a tied key dropped":
+                for members in c.sets[b][h]:
+                    wgt[members[1]] = 0.0
+            elif mistake == "the last valid key dropped":
+                wgt[c.n_k - 1] = 0.0
+            elif mistake == "a tile's keys counted twice":
+                t = 1 if c.n_k > 64 else 0
+                wgt[64 * t:64 * (t + 1)] = 2.0
+            if mistake in ("rescale applied to O but not to l", "rescale applied one tile late"):
+                m = s[:, :64].amax(1)
+                l = torch.zeros_like(m)
+                o = torch.zeros(c.n_q, c.C, dtype=torch.float64)
+                a_prev = torch.ones_like(m)
+                for t0 in range(0, n, 64):
+                    st = s[:, t0:t0 + 64]
+                    m_new = torch.maximum(m, st.amax(1))
+                    alpha = torch.exp2(m - m_new)
+                    m = m_new
+                    p = torch.exp2(st - m[:, None])
+                    a = a_prev if mistake == "rescale applied one tile late" else alpha
+                    a_prev = alpha
+                    o = o * a[:, None] + p @ vh[t0:t0 + 64]
+                    l = (l if mistake == "rescale applied to O but not to l" else l * a) + p.sum(1)
+                res = o / l[:, None]
+            elif mistake in ("split merge without the non-maximal splits' l", "split merge with the splits' weights exchanged") and c.nsplit > 1:
+                per = ((n + 31) // 32 + c.nsplit - 1) // c.nsplit * 32
+                ms, ls, os_ = [], [], []
+                for t0 in range(0, n, per):
+                    st = s[:, t0:t0 + per]
+                    ms.append(st.amax(1))
+                    p = torch.exp2(st - ms[-1][:, None])
+                    ls.append(p.sum(1))
+                    os_.append(p @ vh[t0:t0 + per])
+                ms, ls, os_ = torch.stack(ms), torch.stack(ls), torch.stack(os_)
+                w = torch.exp2(ms - ms.amax(0))
+                if mistake == "split merge with the splits' weights exchanged":
+                    w = w.flip(0)
+                    lw = ls * w
+                else:  # only the first split that holds the maximum brings its l
+                    first = torch.zeros_like(w).scatter_(0, ms.argmax(0, keepdim=True), 1.0)
+                    lw = ls * w * first
+                res = (os_ * w[:, :, None]).sum(0) / lw.sum(0)[:, None]
+            else:
+                p = torch.exp2(s - s[:, wgt > 0].amax(1, keepdim=True)) * wgt
+                res = (p @ vh) / p.sum(1, keepdim=True)
+            out[b * c.n_q:(b + 1) * c.n_q, h * c.C:(h + 1) * c.C] = res.float().to(BF)
+    return out
+
+
+def online_softmax_f32(c: SumsCase, family: str, schedule: str) -> torch.Tensor:
+    """An fp32 model of the kernels' online softmax over 64-key tiles: the offset of a row is tile 0's maximum and moves to a later tile's
+    maximum whenever that is larger (schedule "max") or only when it is more than 8 octaves larger ("lazy": P runs up to 2^8); P = exp2(score -
+    offset) in fp32, summed un-rounded into l, rounded to bf16 for P.V; O and l rescaled by exp2(old - new offset); O * (1 / l) rounded to bf16."""
+    assert schedule in ("max", "lazy")
+    out = torch.empty(c.B * c.n_q, c.H * c.C, dtype=BF)
+    for b in range(c.B):
+        for h in range(c.H):
+            s = _sum_scores(c, family, b, h, c.n_k, f32=True)
+            vh = c.v[b * c.stride:b * c.stride + c.n_k, h * c.C:(h + 1) * c.C].float()
+            m = s[:, :64].amax(1)
+            l = torch.zeros_like(m)
+            o = torch.zeros(c.n_q, c.C)
+            for t0 in range(0, c.n_k, 64):
+                st = s[:, t0:t0 + 64]
+                mt = st.amax(1)
+                m_new = torch.where(mt > (m if schedule == "max" else m + 8.0), mt, m)
+                alpha = torch.exp2(m - m_new)
+                m = m_new
+                p = torch.exp2(st - m[:, None])
+                l = l * alpha + p.sum(1)
+                o = o * alpha[:, None] + p.to(BF).float() @ vh[t0:t0 + 64]
+            out[b * c.n_q:(b + 1) * c.n_q, h * c.C:(h + 1) * c.C] = (o * (1.0 / l)[:, None]).to(BF)
+    return out
+
+
+def sum_margins(c: SumsCase, family: str):
+    """(needle lead, needle forbidden lead, tie gap) in nats, the minimum over samples, heads and rows; asserts that every member of a tie
+    row's set scores exactly 0.  Forbidden: every packed row but the sample's own valid keys - in a silent case only the other samples' keys
+    (a silent row carries no flag: it is told by the sums, not by a needle)."""
+    lead_min, forb_min, gap_min = math.inf, math.inf, math.inf
+    rows = c.k.shape[0]
+    ln2 = math.log(2.0)
+    for b in range(c.B):
+        forb = torch.ones(rows, dtype=torch.bool)
+        forb[b * c.stride:b * c.stride + c.n_k] = False
+        flagged = forb & (c.k.double().view(rows, c.H, c.C)[:, 0, :128].abs().sum(1) > 0)  # (silent rows are all-zero)
+        for h in range(c.H):
+            qh = c.q[family][b * c.n_q:(b + 1) * c.n_q, h * c.C:(h + 1) * c.C].double()
+            s = (qh @ c.k[:, h * c.C:(h + 1) * c.C].double().t()) * c.C ** -0.5   # nats, every packed row
+            nd = c.kind == 0
+            sw = s[nd].gather(1, (c.win[b, nd, h] + b * c.stride)[:, None])
+            own = s[nd].masked_fill(forb[None, :], -math.inf).scatter(1, (c.win[b, nd, h] + b * c.stride)[:, None], -math.inf)
+            if nd.any():
+                lead_min = min(lead_min, float((sw - own.amax(1, keepdim=True)).min()))
+            if nd.any() and flagged.any():
+                forb_min = min(forb_min, float((s[nd][:, flagged].amin(1, keepdim=True) - sw).min()))
+            valid = s[:, b * c.stride:b * c.stride + c.n_k]
+            for i, members in enumerate(c.sets[b][h]):
+                tr = valid[c.kind == 1 + i]
+                assert not tr[:, members].any(), "tie rows: a member of the set does not score exactly 0"
+                lose = torch.ones(c.n_k, dtype=torch.bool)
+                lose[members] = False
+                gap_min = min(gap_min, float(-tr[:, lose].amax()))
+                if flagged.any():
+                    forb_min = min(forb_min, float(s[c.kind == 1 + i][:, flagged].amin()))
+            if flagged.any():
+                forb_min = min(forb_min, float(s[c.kind == 5][:, flagged].amin()))
+    return lead_min, forb_min, gap_min
+
+
+def sum_split_count(n_q: int, n_k: int, C: int, cus: int, ws_floats: int) -> int:
+    """ce_attention_1head_bf16's key-split rule, restated: as many splits (<= 4, >= 16 32-key tiles each) as fill the chip."""
+    blocks, ntiles = (n_q + 127) // 128, (n_k + 31) // 32
+    if blocks * 4 < cus * 3:
+        for sp in (4, 3, 2):
+            if blocks * sp <= cus + cus // 8 and ntiles >= 16 * sp and sp * n_q * (C + 2) <= ws_floats:
+                return sp
+    return 1
+
+
+# every launch of tests/test_exact_attention_sums_gpu.py.  Row-major and V^T forms share the first group (696 = 8 x 87: the 16 x 16 x 32
+# body's column stride); 700 keys for the row-major forms alone; stride > n_k: the blocked layout (N valid of W x n tokens, queries on all).
+SUM_CASES = {
+    "mid-a": dict(n_q=300, n_k=696, heads=2, batch=2, layout=("falling", "rising"), silent=True),
+    "mid-b": dict(n_q=300, n_k=696, heads=2, batch=2, layout=("jump", "falling"), silent=False),
+    "rows-700": dict(n_q=300, n_k=700, heads=2, batch=2, layout=("rising", "jump"), silent=True),
+    "one-tile": dict(n_q=70, n_k=64, heads=2, batch=3, layout=("falling",), silent=True),
+    "long": dict(n_q=100, n_k=2104, heads=2, batch=1, layout=("jump", "rising"), silent=False),
+    "blk-300": dict(n_q=384, n_k=300, heads=2, batch=2, layout=("jump", "rising"), silent=True, stride=384, extra=0),
+    "blk-500": dict(n_q=512, n_k=500, heads=2, batch=2, layout=("falling", "jump"), silent=False, stride=512, extra=0),
+    "vae-1000-128": dict(n_q=1000, n_k=1000, heads=1, batch=1, layout=("jump",), silent=True, C=128, tile=32, nsplit=2, families=("f",)),
+    "vae-1000-384": dict(n_q=1000, n_k=1000, heads=1, batch=1, layout=("rising",), silent=False, C=384, tile=32, nsplit=2, families=("f",)),
+    "vae-2040-128": dict(n_q=2040, n_k=2040, heads=1, batch=1, layout=("falling",), silent=False, C=128, tile=32, nsplit=4, families=("f",)),
+    "vae-2040-384": dict(n_q=2040, n_k=2040, heads=1, batch=1, layout=("jump",), silent=True, C=384, tile=32, nsplit=4, families=("f",)),
+    # the route counters: no needle rows, one layout for every head, the same tie sets in both (one seed: the sets have a stream of their own)
+    "route-rising": dict(n_q=300, n_k=696, heads=2, batch=2, layout=("rising",), silent=True, pure=True, families=("r",), seed=77),
+    "route-jump": dict(n_q=300, n_k=696, heads=2, batch=2, layout=("jump",), silent=True, pure=True, families=("r",), seed=77),
+}
+_sum_cases = {}
+
+
+def sum_named_case(name: str) -> SumsCase:
+    """The case of that name, built once and shared (nobody writes to it)."""
+    if name not in _sum_cases:
+        _sum_cases[name] = sums_case(**dict({"seed": sorted(SUM_CASES).index(name) + 1}, **SUM_CASES[name]))
+    return _sum_cases[name]
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------

@@ -14,7 +14,11 @@ of `MX_MISTAKES` is seen by the cases it applies to - and by one case at least.
 The fp8 producers and GEMM tails (every launch of tests/test_exact_fp8_producers_gpu.py): the per-row restatement is exact on power-of-two rows,
 `mx_contract` equals the contracts in use, sums are exact in fp32, GELU inputs lie in the saturated set (or span the bend), scale bytes differ
 between neighbouring blocks, the split-K plan returns the expected cuts on 256 compute units, and every entry of `FP8_MISTAKES` changes the
-expected output of the launch it belongs to."""
+expected output of the launch it belongs to.
+
+The self-attention sums cases (`SUM_CASES`, every launch of tests/test_exact_attention_sums_gpu.py): the closed form equals the fp64 softmax on
+the packed buffers, tie sets score exactly 0 with the losers TIE_GAP below, the stair's step premise holds per kernel family, an fp32 online
+softmax returns the expected bits under both offset schedules, and every entry of `SUM_MISTAKES` is seen."""
 import math
 
 import pytest
@@ -935,3 +939,89 @@ def test_fused_ordinary_case_is_exact_and_rounds(Cin, KT):
     exact = X.conv_frames_f64([c.in_stack[i] for i in range(n_in)], c.wp, c.b, c.T, KT=KT, KH=3, KW=3, st=1, ss=1, H_out=c.H, W_out=c.W, in_off=0)
     assert _real_rounding_share(c.y, exact) > 0.25
     assert bool((c.in_stack[:KT - 1, 1:-1, 1:-1] != 0).any()) or KT == 1
+
+
+# ---- self-attention sums: tie rows and stair rows (every launch of tests/test_exact_attention_sums_gpu.py) -------------------------------
+SUM_NAMES = sorted(X.SUM_CASES)
+
+
+@pytest.mark.parametrize("name", SUM_NAMES)
+def test_sums_case_closed_form_is_the_fp64_softmax(name):
+    """The recipe's closed form (V[winner], the set's mean, +-r / 8) equals the plain fp64 softmax on the packed buffers for every family,
+    every expected element is exact in bf16 by construction (`sums_case` asserts it on the fp64 value), every row kind sits in every 32-row
+    group and in the partial last query block, and the large tie set holds what it must."""
+    c = X.sum_named_case(name)
+    for f in c.families:
+        assert_exact(X.attention_sums_f64(c, family=f), c.want, f"{name} family {f}: closed form vs fp64")
+    pure = X.SUM_CASES[name].get("pure", False)
+    for g0 in range(0, c.n_q - 31, 32):
+        kinds = set(c.kind[g0:g0 + 32].tolist())
+        assert kinds == ({1, 2, 3, 4, 5} if (pure or 64 <= g0 < 128) else {0, 1, 2, 3, 4, 5}), (g0, kinds)
+    if c.n_q % 256 >= 16:
+        assert len(set(c.kind[c.n_q // 256 * 256:].tolist())) >= (5 if pure else 6)
+    for b in range(c.B):
+        for h in range(c.H):
+            large = c.sets[b][h][3].tolist()
+            assert [len(s) for s in c.sets[b][h]] == list(c.sizes) and 0 in large and c.n_k - 1 in large
+            assert {x // c.tile for x in large} == set(range((c.n_k + c.tile - 1) // c.tile))
+            allk = torch.cat(list(c.sets[b][h]) + [c.stair[b][h][0]])
+            assert len(set(allk.tolist())) == len(allk)  # the sets and the stair share no key
+
+
+@pytest.mark.parametrize("name", SUM_NAMES)
+def test_sums_case_margins_and_step_premise(name):
+    c = X.sum_named_case(name)
+    sl2 = X.sum_scale_log2e(c.C)
+    for f in c.families:
+        lead, forb, gap = X.sum_margins(c, f)
+        assert gap >= X.TIE_GAP, gap
+        if not X.SUM_CASES[name].get("pure", False):
+            assert lead >= MIN_MARGIN_NATS, lead
+        assert forb >= MIN_MARGIN_NATS, forb
+        u1, u2 = X.SUM_STEP[(f, c.C)]
+        deepest = max(float(c.stair[b][h][1].max()) for b in range(c.B) for h in range(c.H))
+        if f == "r":  # one component: the rounded product is exactly 1.0
+            assert u2 == 0.0 and float((torch.tensor(u1, dtype=torch.float32) * sl2).to(BF)) == 1.0
+        else:         # two components: the deviation from one octave per level, at the deepest level, in nats
+            assert abs((u1 + u2) * sl2 - 1.0) < 2.0 ** -16 and abs((u1 + u2) * sl2 - 1.0) * deepest * math.log(2.0) < 2.0 ** -12
+
+
+@pytest.mark.parametrize("schedule", ["max", "lazy"])
+@pytest.mark.parametrize("name", SUM_NAMES)
+def test_sums_case_fp32_online_softmax_gives_the_expected_bits(name, schedule):
+    """An fp32 online softmax over 64-key tiles with P rounded to bf16 for P.V returns the expected bits whether the offset follows the
+    maximum or lags by up to 8 octaves: the recipe leaves the kernels no rounding to differ in."""
+    c = X.sum_named_case(name)
+    for f in c.families:
+        assert_exact(X.online_softmax_f32(c, f, schedule), c.want, f"{name} family {f} schedule {schedule}")
+
+
+def test_sum_mistakes_are_seen():
+    """Every entry of SUM_MISTAKES changes an expected element of some case, every case is changed by some mistake; a silent key changes
+    tie and stair rows only (it moves l and nothing else), and the merge mistakes are seen by every case with a key split."""
+    seen_by = {m: [] for m in X.SUM_MISTAKES}
+    for name in SUM_NAMES:
+        c = X.sum_named_case(name)
+        changed = False
+        for m in X.SUM_MISTAKES:
+            if m.startswith("split merge") and c.nsplit == 1:
+                continue
+            bad = X.mismatches(X.attention_sums_f64(c, mistake=m), c.want)
+            if bad.any():
+                seen_by[m].append(name)
+                changed = True
+            if m == "one silent key counted" and c.silent and c.B == 1:
+                assert bad[c.kind != 0].all(1).any(), name  # (a needle row whose winner is key 0 ties with it too)
+            if m.startswith("split merge"):
+                assert bad.any(), (name, m)
+        assert changed, name
+    for m, names in seen_by.items():
+        assert names, m
+    assert len(seen_by["a tied key dropped"]) == len(SUM_NAMES) and len(seen_by["the last valid key dropped"]) == len(SUM_NAMES)
+
+
+def test_sum_split_rule_on_256_compute_units():
+    for name, c in ((n, X.sum_named_case(n)) for n in SUM_NAMES if n.startswith("vae")):
+        assert X.sum_split_count(c.n_q, c.n_k, c.C, 256, 4 * c.n_q * (c.C + 2)) == c.nsplit, name
+        assert X.sum_split_count(c.n_q, c.n_k, c.C, 256, 0) == 1
+    assert {X.sum_named_case(n).nsplit for n in SUM_NAMES if n.startswith("vae")} == {2, 4}
