@@ -1,0 +1,154 @@
+"""Guided detail lift inside focus boxes: the crops of a focused edit come back at the photo's detail.
+
+A focused edit (chronoedit_amd/focus.py, clusters.py) edits a crop of a large photo at the model's resolution and pastes the frames back at
+the photo's size.  What it pastes is the Lanczos upsample of the edit-size frame: 1.3 to 3.15 photo pixels per edit pixel - a blurred patch
+in a sharp photo.  With `enable_detail_lift(focus=True)` every crop is lifted first (chronoedit_amd/lift.py): the edit-size CHANGE is
+carried onto the photo's own bytes inside the box, and the lifted box goes through the photo-size mask into the paste source.  For one
+sample and its `focus.FocusPlan` with box (l, t, r, b):
+
+    P    the crop [t:b, l:r] of the image the VAE saw (`plan.image`: a sketch edit's composite)
+    L    the bytes the pre-processing fed the VAE (`plan.lift_L`, kept by `focus.inputs`: image.crop(box).resize((width, height), LANCZOS))
+    E    the sample's frames (`ops.video_to_u8`)
+    U    the frames Lanczos-resized to the box, as the plain paste computes them; None under gate=None (no Lanczos pass runs)
+    Q    lift.reference(P, L, E, U, cfg)
+    out  Image.paste(Q[f], (l, t), mask.crop(box)) into the paste source (`plan.paste_image`, else `plan.image`); composite=False: no mask
+
+The crops of one editor value chain into one canvas in the plain paste's order.  A box of exactly the edit's size has nothing to lift: its
+frames are pasted as they are ("reason": "same").  `reference` (PIL and `lift.reference` on the CPU) is the definition and the host path;
+on the device the three grid passes of the lift run per crop, and csrc/ce_boxlift.hip fuses the apply with the paste, in place on the
+canvas - the same bytes.  The fit window knows nothing of the mask: along a feathered rim the residual rises and the gate hands the rim
+to the upsample, so the lift never does worse there than the plain paste."""
+from __future__ import annotations
+
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import lift as _lf
+
+ENTRY_POINTS = ("ce_boxlift_apply_paste_u8",)
+
+Box = Tuple[int, int, int, int]
+
+
+def report_entry(plan, edit_size, reason: str) -> dict:
+    """One crop's `lift_report` entry under focus=True: lift.report_entry's keys with the BOX's size, plus "box" and "scale"."""
+    l, t, r, b = plan.box
+    return dict(_lf.report_entry((r - l, b - t), edit_size, reason), box=plan.box, scale=plan.report["scale"])
+
+
+def gate_means(means: List[torch.Tensor]) -> List[float]:
+    """The gate means of all crops of a call (0-d float64 tensors where the cells lie) as floats: ONE read."""
+    return [float(v) for v in torch.stack(means).cpu().tolist()] if means else []
+
+
+# ---- the host form: PIL itself and lift.reference - the definition ----------------------------------------------------------------------
+def _t(image) -> torch.Tensor:
+    return torch.from_numpy(np.array(image, dtype=np.uint8))
+
+
+def lift_crop(image, L: torch.Tensor, frames: list, box: Box, cfg: _lf.LiftConfig):
+    """One crop: image = the PIL image the VAE saw, L uint8 [H, W, 3], frames = the sample's PIL frames (the edit's size) -> (Q uint8
+    [F, bh, bw, 3] on the host, the mean of g as a 0-d float64 tensor - or (the frames' bytes, None) for a box of the edit's size)."""
+    from PIL import Image
+    l, t, r, b = box
+    E = torch.stack([_t(f) for f in frames])
+    if (r - l, b - t) == (E.shape[2], E.shape[1]):
+        return E, None
+    P = _t(image.convert("RGB").crop(box))
+    U = None if cfg.gate is None else torch.stack([_t(f.resize((r - l, b - t), Image.LANCZOS)) for f in frames])
+    Q, coef = _lf.reference(P, L, E, U, cfg, return_coef=True)
+    return Q, coef[..., 6].double().mean()
+
+
+def host_paste(source, lifted: List[torch.Tensor], masks: Optional[list], boxes: List[Box]) -> list:
+    """source: the paste source (PIL); lifted[g]: crop g's Q uint8 [F, bh, bw, 3]; masks[g]: its photo-size mask uint8 [SH, SW] on the host
+    (masks None: whole boxes are replaced); boxes[g]: its box, in paste order -> per frame a PIL image of the photo's size."""
+    from PIL import Image
+    src = source.convert("RGB")
+    out = []
+    for f in range(lifted[0].shape[0]):
+        canvas = src.copy()
+        for g, (l, t, r, b) in enumerate(boxes):
+            m = None if masks is None else Image.fromarray(masks[g].numpy()).crop((l, t, r, b))
+            canvas.paste(Image.fromarray(lifted[g][f].numpy()), (l, t), m)
+        out.append(canvas)
+    return out
+
+
+def reference(source, crops: list, cfg: _lf.LiftConfig):
+    """THE definition for one canvas.  source: the paste source (PIL); crops: per crop, in paste order, (the image the VAE saw (PIL), L uint8
+    [H, W, 3], the sample's frames (PIL, the edit's size), its photo-size mask uint8 [SH, SW] on the host or None, its box) -> (per frame a
+    PIL image of the photo's size, per crop the mean of g or None for a box of the edit's size)."""
+    done = [lift_crop(im, L, frames, box, cfg) for im, L, frames, _, box in crops]
+    masks = [m for _, _, _, m, _ in crops]
+    return host_paste(source, [q for q, _ in done], None if all(m is None for m in masks) else masks, [c[4] for c in crops]), [v for _, v in done]
+
+
+# ---- the device form -----------------------------------------------------------------------------------------------------------------
+def device_lift_paste(canvas: torch.Tensor, plan, E: torch.Tensor, cfg: _lf.LiftConfig, composite: bool):
+    """One crop into canvas uint8 [F, SH, SW, 3] IN PLACE: the grid passes of the lift on (L, E), then ce_boxlift_apply_paste_u8; a box of
+    the edit's size through ce_clusters_paste_u8 -> the mean of g where it lies, or None.  Nothing is read back here."""
+    from . import image_io, ops
+    l, t, r, b = plan.box
+    bw, bh = r - l, b - t
+    mask = plan.mask_dev if composite else None
+    E = E.contiguous()
+    if (bw, bh) == (E.shape[2], E.shape[1]):
+        ops.clusters_paste_u8(E, mask, canvas, l, t)
+        return None
+    L = plan.lift_L.contiguous()
+    AB = ops.lift_fit_q16(L, E, cfg.radius, cfg.eps_q, cfg.max_gain)
+    coef, R = ops.lift_smooth(L, E, AB, cfg.radius)
+    U = None
+    if cfg.gate is not None:
+        ops.lift_gate(R, coef, cfg.radius, *cfg.gate)
+        U = torch.stack([image_io.resize_u8(f, (bw, bh), image_io.LANCZOS) for f in E]).contiguous()
+    tabs = _lf.tables((bw, bh), tuple(L.shape[:2]), L.device)
+    ops.boxlift_apply_paste_u8(plan.src_u8, coef, tabs, U, mask, canvas, l, t, bw, bh)
+    return coef[..., 6].double().mean()
+
+
+# ---- the output stage of a focused, lifted call ---------------------------------------------------------------------------------------
+def output(video: torch.Tensor, plans: list, image_of, crop_of, cfg: _lf.LiftConfig, output_type: str, composite: bool):
+    """What focus.paste / clusters.paste do under `lift=`: their paste with every crop lifted inside its box -> (the frames at the photos'
+    sizes in postprocess_video's layouts, the `lift_report`: one entry per sample).  video: [B, 3, F, height, width], the edit's size.
+    crop_of None: sample b edits plans[image_of(b)] and is a canvas of its own; else sample b is plans[b], crop crop_of[b] = (value, g) of
+    its editor value, and the crops of a value chain into one canvas in ascending g.  The gate means of all crops are read back once."""
+    from . import image_io, ops
+    image_io.check_output_type(output_type)
+    B, height, width = video.shape[0], int(video.shape[-2]), int(video.shape[-1])
+    plan_of = (lambda b: plans[image_of(b)]) if crop_of is None else (lambda b: plans[b])
+    if crop_of is None:
+        groups = [[b] for b in range(B)]
+    else:
+        groups = [[b for b, (vb, _) in enumerate(crop_of) if vb == v] for v in sorted({v for v, _ in crop_of})]  # (ascending b is ascending g)
+    missing = [b for b in range(B) if plan_of(b).lift_L is None]
+    if missing:
+        raise RuntimeError(f"detail lift inside focus boxes: the pre-processing kept no edit-size source for sample(s) {missing}")
+    on_device = plans[0].src_u8 is not None and image_io.device_video(video)
+    u8 = ops.video_to_u8(video.contiguous()) if on_device else None
+    out, means = [], {}
+    for members in groups:
+        first = plan_of(members[0])
+        if on_device:
+            src = first.src_u8 if first.paste_u8 is None else first.paste_u8
+            canvas = src.unsqueeze(0).repeat(u8.shape[1], 1, 1, 1)  # the paste source under every frame
+            for b in members:
+                means[b] = device_lift_paste(canvas, plan_of(b), u8[b], cfg, composite)
+            out.append(canvas.cpu().numpy())
+        else:
+            crops = []
+            for b in members:
+                p = plan_of(b)
+                frames = image_io.postprocess_video(video[b:b + 1], "pil")[0]
+                crops.append((p.image, p.lift_L.cpu(), frames, p.host_mask() if composite else None, p.box))
+            pasted, vals = reference(first.image if first.paste_image is None else first.paste_image, crops, cfg)
+            means.update(zip(members, vals))
+            out.append(np.stack([np.asarray(f, dtype=np.uint8) for f in pasted]))
+    report = [report_entry(plan_of(b), (width, height), "same" if means[b] is None else "ok") for b in range(B)]
+    lifted = [b for b in range(B) if means[b] is not None]
+    for b, v in zip(lifted, gate_means([means[b] for b in lifted])):
+        report[b]["fallback_fraction"] = v
+    return image_io.frames_from_u8(out, output_type), report

@@ -14,10 +14,10 @@
 // Every fp32 / fp64 multiply, add and subtract is rounded on its own (`#pragma clang fp contract(off)`, as in csrc/ce_preview.hip).
 // No state, nothing allocated, no host read: every call is capturable.
 #include "ce_common.h"
+#include "ce_lift_pixel.h"  // LF_CELL, the corner cells and the per-pixel arithmetic of the apply stage (shared with csrc/ce_boxlift.hip)
 
 #define LF_T 16         // a workgroup's tile: LF_T x LF_T cells, one lane per cell
 #define LF_RMAX 16      // the largest radius: the staged side is LF_T + 2 r <= 48 cells
-#define LF_CELL 8       // floats per coefficient cell: abar_rgb, bbar_rgb, g, 0
 
 // the window [i - r, i + r] clipped to [0, n): its cell count along one axis
 __device__ __forceinline__ int lf_span(int i, int r, int n) { return min(i + r, n - 1) - max(i - r, 0) + 1; }
@@ -243,18 +243,6 @@ CE_API int ce_lift_gate_f32(const int* R, float* coef, int F, int H, int W, int 
 #define LA_DW (LA_B / 4)
 #define LA_MAX_WG 2048      // a memory-bound pass: at most about eight workgroups per CU, the rest by the grid stride
 
-struct LaCell {
-  float v[7];  // abar_rgb, bbar_rgb, g
-};
-
-__device__ __forceinline__ LaCell la_load(const float* __restrict__ coef, int y, int x, int W) {
-  const float4* p = (const float4*)(coef + ((size_t)y * W + x) * LF_CELL);
-  const float4 lo = p[0], hi = p[1];
-  LaCell c;
-  c.v[0] = lo.x, c.v[1] = lo.y, c.v[2] = lo.z, c.v[3] = lo.w, c.v[4] = hi.x, c.v[5] = hi.y, c.v[6] = hi.z;
-  return c;
-}
-
 // LA_B bytes of a frame as LA_DW dwords: three 16-byte loads (WIDE), or nb single bytes
 template <bool WIDE>
 __device__ __forceinline__ void la_read(const uint8_t* __restrict__ p, int nb, uint32_t (&w)[LA_DW]) {
@@ -335,14 +323,7 @@ __global__ __launch_bounds__(256) void lift_apply_kernel(const uint8_t* __restri
           xa = nxa, xb = nxb;
         }
         const float sx = 1.0f - tx;
-#pragma unroll
-        for (int k = 0; k < 7; ++k) {
-          const float tl = c00.v[k] * sx, tr = c01.v[k] * tx;
-          const float bl = c10.v[k] * sx, br = c11.v[k] * tx;
-          const float top = tl + tr, bot = bl + br;
-          const float l = top * sy, r = bot * ty;
-          v[k] = l + r;
-        }
+        la_sample(c00, c01, c10, c11, tx, sx, ty, sy, v);
         any = any || v[6] != 0.0f;
         nxa = pxa, nxb = pxb, tx = ptx;
         if ((X = X1) == 0) ++Y;
@@ -352,26 +333,20 @@ __global__ __launch_bounds__(256) void lift_apply_kernel(const uint8_t* __restri
       for (int c = 0; c < 3; ++c) {
         const int j = 3 * i + c;
         const float p = (float)((pw[j >> 2] >> (8 * (j & 3))) & 255u);
-        const float m = v[c] * p;
-        const float e = m + v[3 + c];
-        q[j] = p + e;
+        q[j] = la_affine(v[c], v[3 + c], p);
       }
     }
     if (Uf && any) {
       uint32_t uw[LA_DW];
       la_read<WIDE>(Uf + b0, nb, uw);
 #pragma unroll
-      for (int j = 0; j < LA_B; ++j) {
-        const float d = (float)((uw[j >> 2] >> (8 * (j & 3))) & 255u) - q[j];
-        const float m = gq[j / 3] * d;
-        q[j] = q[j] + m;
-      }
+      for (int j = 0; j < LA_B; ++j) q[j] = la_fallback(q[j], gq[j / 3], (float)((uw[j >> 2] >> (8 * (j & 3))) & 255u));
     }
     uint32_t ow[LA_DW];
 #pragma unroll
     for (int k = 0; k < LA_DW; ++k) ow[k] = 0;
 #pragma unroll
-    for (int j = 0; j < LA_B; ++j) ow[j >> 2] |= (uint32_t)rintf(fminf(fmaxf(q[j], 0.0f), 255.0f)) << (8 * (j & 3));  // (fmaxf(NaN, 0) = 0)
+    for (int j = 0; j < LA_B; ++j) ow[j >> 2] |= la_byte(q[j]) << (8 * (j & 3));
     if (WIDE) {
 #pragma unroll
       for (int k = 0; k < LA_DW / 4; ++k) ((uint4*)(of + b0))[k] = make_uint4(ow[4 * k], ow[4 * k + 1], ow[4 * k + 2], ow[4 * k + 3]);

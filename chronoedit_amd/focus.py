@@ -178,6 +178,7 @@ class FocusPlan:
     src_u8: Optional[torch.Tensor] = None  # the photo's bytes on the device: set when the device passes run
     paste_image: Any = None  # a second source the frames are pasted into (a sketch edit's background); None: `image`
     paste_u8: Optional[torch.Tensor] = None  # its bytes on the device
+    lift_L: Optional[torch.Tensor] = None  # the crop at the edit's size uint8 [height, width, 3] as the VAE got it, where the passes run: kept for boxlift.py
 
     @classmethod
     def make(cls, image, report: dict, mask: torch.Tensor, device=None, paste_image=None, uploaded=None) -> "FocusPlan":
@@ -219,9 +220,10 @@ def setup(image, masks, height: int, width: int, context: float, output_type, de
     return [FocusPlan.make(im, *_plan(im.size, m, height, width, context), device) for im, m in zip(imgs, masks_for(masks, len(imgs)))]
 
 
-def inputs(plans: List[FocusPlan], height: int, width: int, device):
+def inputs(plans: List[FocusPlan], height: int, width: int, device, keep_L: bool = False):
     """(img bf16 [n, 3, height, width] as preprocessing leaves it, the edit-size region masks uint8 [height, width] on the device) of
-    the crops: the device passes, or PIL itself (`host_inputs`)."""
+    the crops: the device passes, or PIL itself (`host_inputs`).  keep_L: every plan keeps the resized crop's bytes (`lift_L`: the detail
+    lift inside the box works from them) - on the host the crop is then resized here, once, and preprocessing takes it as it is."""
     from . import image_io, ops
     if plans[0].src_u8 is not None:
         img = torch.empty((len(plans), 3, height, width), dtype=torch.bfloat16, device=device)
@@ -230,18 +232,33 @@ def inputs(plans: List[FocusPlan], height: int, width: int, device):
             crop, m = device_inputs(p.src_u8, p.mask_dev, p.box, width, height)
             ops.image_u8_lut_planar(crop, image_io.vae_lut(torch.device(device)), img[j])
             masks.append(m)
+            if keep_L:
+                p.lift_L = crop
         return img, masks
     host = [host_inputs(p.image, p.host_mask(), p.box, width, height) for p in plans]
+    if keep_L:
+        import numpy as np
+        from PIL import Image
+        host = [(c.resize((int(width), int(height)), Image.LANCZOS), m) for c, m in host]
+        for p, (c, _) in zip(plans, host):
+            p.lift_L = torch.from_numpy(np.array(c, dtype=np.uint8))
     img = image_io.preprocess_image([c for c, _ in host], height, width).to(device=device, dtype=torch.bfloat16)
     return img, [m.to(device) for _, m in host]
 
 
-def paste(video: torch.Tensor, plans: List[FocusPlan], image_of, output_type: str, composite: bool):
+def paste(video: torch.Tensor, plans: List[FocusPlan], image_of, output_type: str, composite: bool, lift=None, report: Optional[list] = None):
     """The source-size paste-back of every sample's frames (reasoning frames included), in postprocess_video's layouts: through the mask
-    (composite), or the whole box.  A plan with a second source is pasted into that one."""
+    (composite), or the whole box.  A plan with a second source is pasted into that one.  lift: a lift.LiftConfig - every sample is lifted
+    inside its box from its plan's `lift_L` before the paste (boxlift.output), and `report` receives one `lift_report` entry per sample."""
     import numpy as np
     from . import image_io, ops
     image_io.check_output_type(output_type)
+    if lift is not None:
+        from . import boxlift
+        frames, entries = boxlift.output(video, plans, image_of, None, lift, output_type, composite)
+        if report is not None:
+            report.extend(entries)
+        return frames
     on_device = plans[0].src_u8 is not None and image_io.device_video(video)
     u8 = ops.video_to_u8(video.contiguous()) if on_device else None
     out = []

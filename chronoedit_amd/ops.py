@@ -1507,6 +1507,46 @@ def lift_apply_u8(P: torch.Tensor, coef: torch.Tensor, tables, U: Optional[torch
     return out
 
 
+# ---- guided detail lift inside a focus box (csrc/ce_boxlift.hip) -----------------------------------------------------------
+def boxlift_apply_paste_u8(P: torch.Tensor, coef: torch.Tensor, tables, U: Optional[torch.Tensor], mask: Optional[torch.Tensor],
+                           canvas: torch.Tensor, left: int, top: int, bw: int, bh: int):
+    """Stage 4 of the lift fused with the paste, IN PLACE: P uint8 [SH, SW, 3] (the photo the crop was cut from), the cells fp32 [F, H, W, 8],
+    tables = lift.tables((bw, bh), (H, W)) on the device, U uint8 [F, bh, bw, 3] or None, mask uint8 [SH, SW] or None (the whole box),
+    canvas uint8 [F, SH, SW, 3] -> canvas.  Only the box's bytes are touched; under a mask byte of 0 nothing is computed or written."""
+    _dev(P, torch.uint8, "P"), _dev(coef, torch.float32, "coef"), _dev(canvas, torch.uint8, "canvas")
+    if P.dim() != 3 or P.shape[2] != 3 or not P.is_contiguous():
+        raise ValueError(f"P: need a contiguous [SH, SW, 3] tensor, got shape {tuple(P.shape)} stride {P.stride()}")
+    if coef.dim() != 4 or coef.shape[3] != LIFT_CELL or not coef.is_contiguous():
+        raise ValueError(f"coef: need a contiguous [F, H, W, 8] tensor, got shape {tuple(coef.shape)} stride {coef.stride()}")
+    SH, SW, _ = P.shape
+    F, H, W, _ = coef.shape
+    if tuple(canvas.shape) != (F, SH, SW, 3) or not canvas.is_contiguous():
+        raise ValueError(f"canvas: need a contiguous [{F}, {SH}, {SW}, 3] tensor, got shape {tuple(canvas.shape)} stride {canvas.stride()}")
+    left, top, bw, bh = int(left), int(top), int(bw), int(bh)
+    if bw < 1 or bh < 1 or left < 0 or top < 0 or left + bw > SW or top + bh > SH:
+        raise ValueError(f"the {bw}x{bh} box at ({left}, {top}) does not lie inside the {SW}x{SH} canvas")
+    ix0, ix1, tx, iy0, iy1, ty = tables
+    for t, dt, n, name in ((ix0, torch.int32, bw, "ix0"), (ix1, torch.int32, bw, "ix1"), (tx, torch.float32, bw, "tx"),
+                           (iy0, torch.int32, bh, "iy0"), (iy1, torch.int32, bh, "iy1"), (ty, torch.float32, bh, "ty")):
+        _dev(t, dt, name)
+        if tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name}: need a contiguous [{n}] tensor, got shape {tuple(t.shape)}")
+    if U is not None:
+        _dev(U, torch.uint8, "U")
+        if tuple(U.shape) != (F, bh, bw, 3) or not U.is_contiguous():
+            raise ValueError(f"U: need a contiguous [{F}, {bh}, {bw}, 3] tensor, got shape {tuple(U.shape)} stride {U.stride()}")
+    if mask is not None:
+        _dev(mask, torch.uint8, "mask")
+        if tuple(mask.shape) != (SH, SW) or not mask.is_contiguous():
+            raise ValueError(f"mask: need a contiguous [{SH}, {SW}] tensor, got shape {tuple(mask.shape)} stride {mask.stride()}")
+    assert not _overlap(canvas, P) and (U is None or not _overlap(canvas, U)) and (mask is None or not _overlap(canvas, mask))
+    st = _prof_begin()
+    _check(lib().ce_boxlift_apply_paste_u8(_ptr(P), _ptr(U), _ptr(coef), _ptr(ix0), _ptr(ix1), _ptr(tx), _ptr(iy0), _ptr(iy1), _ptr(ty), _ptr(mask),
+                                           _ptr(canvas), F, SH, SW, left, top, bw, bh, H, W, _stream()), "ce_boxlift_apply_paste_u8")
+    _prof_end(st, f"boxlift_apply_paste_{F}x{bh}x{bw}", float(F * bh * bw * (9 if U is not None else 6) + bh * bw * 4))
+    return canvas
+
+
 # ---- Wan VAE ------------------------------------------------------------------------------------------------------
 # ---- sparse region edits (csrc/ce_sparse.hip) ----------------------------------------------------------------------------
 def _sparse_ids(ids: torch.Tensor):

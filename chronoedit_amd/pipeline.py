@@ -103,7 +103,8 @@ class EditSources:
     masks: Any = None  # an unfocused region edit: the explicit edit-size mask(s)
     composite: bool = False  # paste the source back through the masks behind the decode
     auto_focus: Any = None  # the autofocus.AutoFocusConfig when this pass is a scout
-    lift: Any = None  # the lift.LiftConfig while the detail lift is on (a focused pass only reports it)
+    lift: Any = None  # the lift.LiftConfig while the detail lift is on (a focused pass only reports it, unless lift_focus)
+    lift_focus: bool = False  # enable_detail_lift(focus=True): a focused pass lifts every crop inside its box before the paste (boxlift.py)
     crop_of: Optional[list] = None  # per focus plan (editor value, crop) when the crops of a value are chained into one video (clusters.paste)
 
 
@@ -173,6 +174,7 @@ class ChronoEditPipeline:
         self.preview_fit_report = None  # {"rms", "r2"} per colour of the last fit
         self.preview_fit_gram = None  # float64 [20, 20] on the CPU: the Gram matrix the last fit solved
         self._detail_lift = None  # the lift.LiftConfig while enable_detail_lift is in force
+        self._detail_lift_focus = False  # enable_detail_lift(focus=True): focused passes lift inside their boxes
         self.lift_report = None  # the last call's detail-lift report, one dict per sample; None when the switch is off (or "latent" was asked for)
         self._sketch_region = None  # the sketch.SketchConfig while enable_sketch_region is in force
         self.sketch_report = None  # the last call's sketch plans, one dict per editor value; None when the call got no editor value
@@ -790,7 +792,7 @@ class ChronoEditPipeline:
         return _cl.crop_reports(crops, single)
 
     # Guided detail lift (chronoedit_amd/lift.py): whole-image edits returned at the photo's size.  Off by default
-    def enable_detail_lift(self, radius: int = 4, eps: float = 26.0, gate=(4.0, 12.0), max_gain: float = 8.0):
+    def enable_detail_lift(self, radius: int = 4, eps: float = 26.0, gate=(4.0, 12.0), max_gain: float = 8.0, focus: bool = False):
         """While on, a call with PIL input (one image, or a list with one per prompt) and output_type "pil" / "np" / "pt" returns every frame
         - reasoning frames included, behind the edit-size region composite if there is one - at the IMAGE's own size: per edit-size
         neighbourhood and colour an affine map from the resized photo to the edit's change is fitted (window radius `radius` cells,
@@ -803,12 +805,23 @@ class ChronoEditPipeline:
         `image` is a ValueError.  The lift runs behind the decode (csrc/ce_lift.hip; lift.reference on the host with
         `enable_device_image_io(False)`, the same bytes), never inside a captured graph.  `lift_report` holds per sample {"size",
         "edit_size", "applied", "reason", "fallback_fraction"}: the last is the mean of the gate - how much of the picture was plain
-        upsampling."""
+        upsampling.
+        focus=True: a focused pass - an explicit mask under `enable_region_focus`, an accepted auto focus (cold or warm start), a sketch
+        edit with one box, with one crop per stroke cluster, or with a prompt per layer - no longer stands back: every crop is lifted
+        INSIDE its box before the paste (chronoedit_amd/boxlift.py): P is the box of the image the VAE saw, L the resized crop the
+        pre-processing fed it, and the lifted box goes through the photo-size mask into the paste source (csrc/ce_boxlift.hip fuses the
+        apply with the paste; `boxlift.reference` on the host, the same bytes).  `lift_report` then holds one entry per sample - per
+        crop - with "size" = the box's size, "reason" "ok" or "same" (a box of exactly the edit's size: the plain paste), and "box" and
+        "scale" on top.  `focus_report` / `sketch_report`, and everything a focused edit composes with or refuses, stay as they are."""
+        if not isinstance(focus, bool):
+            raise ValueError(f"detail lift: focus must be True or False, got {focus!r}")
         self._detail_lift = _lf.LiftConfig(radius, eps, None if gate is None else tuple(gate) if isinstance(gate, (tuple, list)) else gate, max_gain)
+        self._detail_lift_focus = focus
         return self
 
     def disable_detail_lift(self):
         self._detail_lift = None
+        self._detail_lift_focus = False
         return self
 
     def _measure_kwargs(self) -> dict:
@@ -1128,7 +1141,7 @@ class ChronoEditPipeline:
             if pil is None:
                 raise ValueError("detail lift needs PIL input (one image or a list): an array or tensor `image` has no full-resolution bytes to "
                                  "lift the edit onto - pass PIL images, or disable_detail_lift()")
-            what.lift = self._detail_lift
+            what.lift, what.lift_focus = self._detail_lift, self._detail_lift_focus
             if what.focus is None and a.output_type in ("np", "pt") and len({im.size for im in pil}) > 1:
                 raise ValueError(f"detail lift returns frames of the images' sizes {[im.size for im in pil]}: output_type={a.output_type!r} "
                                  'needs images of one size, use "pil"')
@@ -1156,7 +1169,7 @@ class ChronoEditPipeline:
         if hasattr(self.vae, "use_graph"):  # the VAE replays captured graphs from the second edit of a shape on (vae.py)
             self.vae.use_graph = bool(self.use_graph)
         if what.focus is not None:
-            return _fc.inputs(what.focus, a.height, a.width, device) + (None,)
+            return _fc.inputs(what.focus, a.height, a.width, device, keep_L=what.lift is not None and what.lift_focus) + (None,)
         if image_io.on_device(self.device_image_io, device) and what.pil is not None:
             lift_kept = [] if what.lift is not None else None  # (the photo's bytes stay on the device: one upload)
             return image_io.preprocess_pil(a.image, a.height, a.width, device, keep=lift_kept), None, lift_kept
@@ -1244,11 +1257,14 @@ class ChronoEditPipeline:
             if lifted is not None:
                 return lifted
         if what.focus is not None:  # the source-size paste replaces the edit-size composite
+            boxed, lifted = (what.lift if what.lift_focus else None), []  # focus=True: every crop is lifted inside its box (boxlift.py)
             if what.crop_of is not None:  # the crops of an editor value, chained into one video
-                video = _cl.paste(video, what.focus, what.crop_of, a.output_type, what.composite)
+                video = _cl.paste(video, what.focus, what.crop_of, a.output_type, what.composite, lift=boxed, report=lifted)
             else:
-                video = _fc.paste(video, what.focus, image_of, a.output_type, what.composite)
-            if what.lift is not None:
+                video = _fc.paste(video, what.focus, image_of, a.output_type, what.composite, lift=boxed, report=lifted)
+            if boxed is not None:
+                self.lift_report = lifted
+            elif what.lift is not None:
                 self.lift_report = [_lf.report_entry(what.focus[image_of(b)].image.size, (a.width, a.height), "focus") for b in range(B)]
             return video
         if self.device_image_io and a.output_type == "pil" and image_io.device_video(video):

@@ -764,6 +764,30 @@ int ce_clusters_paste_u8(const void* edit, const void* mask, void* canvas, int F
 int ce_layers_strokes_u8(const void* layer, int bw, int bh, int left, int top, void* plane, int SW, int SH, int threshold, hipStream_t stream);
 int ce_layers_over_u8(const void* layer, int bw, int bh, int left, int top, void* canvas, int SW, int SH, hipStream_t stream);
 
+/* ---- guided detail lift inside a focus box (csrc/ce_boxlift.hip; chronoedit_amd/boxlift.py is the definition and the pass gives its bits):
+ * stage 4 of the lift fused with the paste of a focused edit.
+ * ce_boxlift_apply_paste_u8: works IN PLACE on canvas = uint8 [F][src_h][src_w][3], inside the box [top, top + bh) x [left, left + bw).
+ *   P = uint8 [src_h][src_w][3], the photo the crop was cut from, read at (top + y, left + x);  U = uint8 [F][bh][bw][3], the frames'
+ *   Lanczos upsample to the box, or NULL;  coef = fp32 [F][H][W][8], the cells ce_lift_smooth_f32 / ce_lift_gate_f32 left (16-byte aligned);
+ *   ix0, ix1 = int32 [bw], tx = fp32 [bw], iy0, iy1 = int32 [bh], ty = fp32 [bh] in device memory: lift.tables((bw, bh), (H, W)) - the box is
+ *   what the grid covers (an index outside the grid is clamped into it);  mask = uint8 [src_h][src_w] at the photo's size, or NULL (= 255
+ *   everywhere).  Per byte of the box, with m the mask byte of its pixel and c the canvas byte:
+ *     q = ce_lift_apply_u8's value, by the same fp32 operations in the same order, each rounded on its own (csrc/ce_lift_pixel.h holds them
+ *     for both): p = float(P), top = c00 * (1 - tx) + c01 * tx, bot likewise, v = top * (1 - ty) + bot * ty for abar_c, bbar_c and g;
+ *     q = p + (a_up * p + b_up);  with U: q = q + g_up * (float(U) - q);  e = rint(clamp(q, 0, 255)), NaN -> 0;
+ *     t = c * (255 - m) + e * m + 128, c = ((t >> 8) + t) >> 8 - ce_focus_paste_u8's arithmetic.
+ *   Under m == 0 nothing is computed, read from U or written; U is not read by a run of pixels whose g_up are all 0.  Only bytes of the box
+ *   are touched, each by one lane that reads and writes its own addresses.  One lane per run of up to eight pixels of a row: lane 0 of a
+ *   row takes the 0..3 pixels in front of the row's first pixel at which the canvas allows dword access, the others eight pixels each
+ *   from there; a whole run moves as dwords in every plane (canvas, P, U, mask) that is aligned at it, and byte by byte otherwise - the
+ *   same bytes.  A run whose mask bytes are all 0 leaves before a table entry or a cell is loaded.  Any base address, any width.
+ *   A box that leaves the image, or F > 65535, returns -1; so do P, U or a mask that share a byte with the canvas.  An image of 2^31 bytes
+ *   or more (src_h * src_w * 3, H * W * 32) returns -2; the tables 4-byte, coef 16-byte aligned (otherwise -3).
+ * No state, no scratch, nothing allocated, no host read: the call is capturable. */
+int ce_boxlift_apply_paste_u8(const void* P, const void* U, const float* coef, const int* ix0, const int* ix1, const float* tx, const int* iy0,
+                              const int* iy1, const float* ty, const void* mask, void* canvas, int F, int src_h, int src_w, int left, int top,
+                              int bw, int bh, int H, int W, hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
