@@ -27,9 +27,6 @@ from . import ops, weights
 from .weights import LoraMixin
 
 
-_VT_GEMM_SWAPPED = __import__("os").environ.get("CE_VT_GEMM") == "row"  # (tools: the rounds-2-5 form of the V^T product, see forward)
-
-
 @dataclass
 class Transformer2DModelOutput:
     sample: torch.Tensor
@@ -357,8 +354,8 @@ class ChronoEditTransformer3DModel(LoraMixin, nn.Module):
         return self
 
     def enable_transposed_v(self, on: bool = True):
-        """bf16 self-attention operand form (default on): the V third of the fused projection is taken as V^T = W_v.h^T (the GEMM
-        with its operand roles swapped and the bias along rows, CE_EPI_BIAS_ROW) so that K and V^T tiles both reach the attention
+        """bf16 self-attention operand form (default on): the V third of the fused projection is taken as V^T = (h.W_v^T)^T (a GEMM
+        whose epilogue stores the transpose, CE_EPI_BIAS_T) so that K and V^T tiles both reach the attention
         kernel's LDS by LDS-DMA (`ce_attention_vt_bf16`: +4.4 % on the kernel, no transpose pass).  Off = the fused q|k|v GEMM and
         the register-staged kernel; same arithmetic up to the summation order inside a key tile."""
         self.v_transposed = bool(on)
@@ -737,6 +734,8 @@ class DiTEngine:
         self.fp8_set = frozenset(getattr(model, "fp8_linears", model.FP8_LINEARS)) if self.fp8 else frozenset()  # which Linears (mixed precision)
         self.fuse_quant = bool(getattr(model, "fp8_fuse_quant", True)) and self.F % 128 == 0  # MX: quantisation fused into the FFN-up epilogue
         self.fuse_attn_quant = self.fuse_quant and bool(getattr(model, "fp8_fuse_attn_quant", True))
+        fuse_o = self.mx and self.fuse_attn_quant and self.D % 128 == 0  # MX: both attention kernels emit the out-projections' fp8 operands themselves
+        self.fuse_o1, self.fuse_o2 = fuse_o and "o1" in self.fp8_set, fuse_o and "o2" in self.fp8_set  # (only for an out-projection that runs in fp8)
         self.v_transposed = bool(getattr(model, "v_transposed", True))
         if self.fp8:
             if self.D % 256 or self.F % 256:
@@ -796,11 +795,13 @@ class DiTEngine:
 
     def _ln_linear(self, ws, x: torch.Tensor, a_row, b_row, p, name: str, out: torch.Tensor, ab_rows: int = 0, ab_stride: int = 0, **kw):
         """LayerNorm (+ affine / AdaLN rows) followed by one of the large projections.  fp8 mode: the LN kernel emits the fp8
-        operand and its row scales directly (no bf16 round trip through HBM, no separate quantisation pass)."""
+        operand and its row scales directly (no bf16 round trip through HBM, no separate quantisation pass).  bf16: x may be a row range of
+        the workspace (the normed rows go to the same range of ws.h)."""
         eps = self.cfg.eps
         if name not in self.fp8_set:
-            ops.ln_affine(x, a_row, b_row, eps, out=ws.h, ab_rows=ab_rows, ab_stride=ab_stride)
-            return ops.gemm(ws.h, getattr(p, "w_" + name), getattr(p, "b_" + name), out=out, **kw)
+            h = ws.h[: x.shape[0]]
+            ops.ln_affine(x, a_row, b_row, eps, out=h, ab_rows=ab_rows, ab_stride=ab_stride)
+            return ops.gemm(h, getattr(p, "w_" + name), getattr(p, "b_" + name), out=out, **kw)
         aq = ws.a8[:, : x.shape[1]]
         wq, sw = getattr(p, "q_" + name)
         if self.mx:
@@ -874,13 +875,19 @@ class DiTEngine:
         return y  # K-segmented A operand of the out-projection (a_seg_k of ce_gemm_bf16)
 
     # -- workspaces --------------------------------------------------------------------
+    def _row_buffers(self, M: int):
+        """The bf16 buffers every launch sequence over M token rows works in."""
+        D = self.D
+        e = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=self.dev)
+        return SimpleNamespace(x=e(M, D), h=e(M, D), qkv=e(M, 3 * D), att=e(M, D), q2=e(M, D), ffn=e(M, self.F),
+                               cols=e(M, self.kpatch), head=e(M, self.w_out.shape[0]))
+
     def _workspace(self, N: int):
         ws = self._ws.get(N)
         if ws is None:
             D, F, dev = self.D, self.F, self.dev
             e = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=dev)
-            ws = SimpleNamespace(x=e(N, D), h=e(N, D), qkv=e(N, 3 * D), att=e(N, D), q2=e(N, D), ffn=e(N, F),
-                                 cols=e(N, self.kpatch), head=e(N, self.w_out.shape[0]))
+            ws = self._row_buffers(N)
             if self.fp8:  # activation rows as fp8 + one scale per row (MX: one E8M0 byte per 32 elements, tiled: ops.mx_scale_bytes)
                 ws.a8 = torch.empty((N, max(D, F)), dtype=torch.uint8, device=dev)
                 ws.s8 = (torch.empty((ops.mx_scale_bytes(N, max(D, F)),), dtype=torch.uint8, device=dev) if self.mx else
@@ -935,25 +942,30 @@ class DiTEngine:
         builds the operands, and `_share_image`, which may only share a segment in this form."""
         return bool(self.cross_vt and image_given and self.has_image and self.all_img and Tt % 8 == 0 and not self._cross_fp8())
 
+    def _plain_vt_path(self, Tt: int) -> bool:
+        """Is this the one launch sequence that can express a shared image segment and a compacted text: plain bf16, unsharded, with the
+        transposed-V self- and cross-attention (an image context of this model given)?"""
+        m = self.model
+        return bool(self._cross_vt_form(Tt, True) and not self.fp8 and not self.fp8_attn and self.v_transposed
+                    and (m._sp is None or not m._sp.sharded) and getattr(m, "_cfgp", None) is None)
+
     def _share_image(self, text: torch.Tensor, image: Optional[torch.Tensor]) -> bool:
         """Does this forward project the image context ONCE for its two samples?  Only when the caller declared the pair's inputs shared
-        (model._shared_inputs; never inferred from the tensors) and the launch sequence is the one that can express it: two samples, bf16,
-        unsharded, the transposed-V cross-attention kernel.  Everything else keeps the stacked sequence, silently."""
+        (model._shared_inputs; never inferred from the tensors) and the launch sequence is the one that can express it: two samples on
+        `_plain_vt_path`.  Everything else keeps the stacked sequence, silently."""
         m = self.model
         return bool(m._shared_inputs and m.shared_guidance and image is not None and text.shape[0] == 2 and image.shape[0] == 2
-                    and self._cross_vt_form(text.shape[1], True) and not self.fp8 and not self.fp8_attn
-                    and self.v_transposed and (m._sp is None or not m._sp.sharded) and getattr(m, "_cfgp", None) is None)
+                    and self._plain_vt_path(text.shape[1]))
 
     def _text_compact(self, text: torch.Tensor, image: Optional[torch.Tensor]):
         """The compacted form of this text context (pipeline.compact_text_context hung it on the tensor where the edit's context was built),
         or None: switched off, a tensor nobody examined or that changed since, nothing to save, or a launch sequence that cannot express it
-        (as `_share_image`: bf16, unsharded, the transposed-V cross-attention kernel).  Never inferred from the tensor's content here."""
+        (as `_share_image`: `_plain_vt_path`).  Never inferred from the tensor's content here."""
         m = self.model
         info = getattr(text, "_ce_compact", None)
         if info is None or info.text is None or not m.text_compaction or info.version != text._version or info.shape != tuple(text.shape):
             return None
-        if not (image is not None and self._cross_vt_form(text.shape[1], True) and not self.fp8 and not self.fp8_attn and self.v_transposed
-                and (m._sp is None or not m._sp.sharded) and getattr(m, "_cfgp", None) is None):
+        if image is None or not self._plain_vt_path(text.shape[1]):
             return None
         return info
 
@@ -1193,17 +1205,14 @@ class DiTEngine:
             raise ValueError(f"sparse region: the active rows per sample must be a multiple of 8 (sparse_region.active_tokens pads), got {Na}")
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("sparse region: sparse_begin allocates; it cannot run under a hipGraph capture")
-        D, F, L, dev = self.D, self.F, self.L, self.dev
+        D, L, dev = self.D, self.L, self.dev
         st = self._sparse
         if st is None or (st.B, st.N) != (B, N):
             self._sparse = st = None  # (the old cache goes before the new one comes)
             st = SimpleNamespace(B=B, N=N, k=torch.empty((L, B * N, D), dtype=torch.bfloat16, device=dev),
                                  vt=torch.zeros((L, D, ops.vt_columns(B * N)), dtype=torch.bfloat16, device=dev), Na=0, ws=None)
         if st.Na != Na:
-            M = B * Na
-            e = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=dev)
-            st.ws = SimpleNamespace(x=e(M, D), h=e(M, D), qkv=e(M, 3 * D), att=e(M, D), q2=e(M, D), ffn=e(M, F),
-                                    cols=e(M, self.kpatch), head=e(M, self.w_out.shape[0]))
+            st.ws = self._row_buffers(B * Na)
         st.T, st.Hh, st.Ww, st.Na = T, Hh, Ww, Na
         st.ids = host.to(device=dev, dtype=torch.int32)
         st.cs = self._rope_table(T, Hp, Wp)[host.to(dev)].contiguous()
@@ -1241,29 +1250,16 @@ class DiTEngine:
         self.sparse_check(B, st.N)
         Na, N, ids, cs, ws = st.Na, st.N, st.ids, st.cs, st.ws
         hidden = hidden.to(torch.bfloat16).contiguous()
-        timestep = timestep.to(device=self.dev, dtype=torch.float32 if timestep.is_floating_point() else torch.int64).contiguous()
         rows = [slice(b * Na, (b + 1) * Na) for b in range(B)]
         for b in range(B):
             ops.sparse_patchify(hidden[b], ids, self.kpatch, out=ws.cols[rows[b]])
         x = ops.gemm(ws.cols, self.w_patch, self.b_patch, out=ws.x)
-        mods, mods_out = [], []
-        for b in range(B):  # K2, as the plain forward
-            sin = ops.timestep_sinusoid(timestep[b : b + 1], cfg.freq_dim)
-            h1 = ops.gemv(self.te_w1, sin, self.te_b1, flags=2)
-            temb = ops.gemv(self.te_w2, h1, self.te_b2, flags=4)
-            tproj = ops.gemv(self.tp_w, temb, self.tp_b, flags=1 | 4)
-            mods.append(ops.modulation(self.tables, tproj.view(6, D), one_mask=0b010010))
-            mods_out.append(ops.modulation(self.table_out, temb.view(1, D), one_mask=0b10))
-        mod = torch.stack(mods, dim=1).contiguous()          # [L, B, 6, D]; ab_rows / gate_rows = Na
-        mod_out = torch.stack(mods_out, dim=0).contiguous()  # [B, 1, 2, D]
-        if B > 1:
-            gate_msa, gate_ffn = mod[:, :, 2].contiguous(), mod[:, :, 5].contiguous()
+        _, mod, mod_out, gate_msa, gate_ffn = self._time_tables(timestep, B, B)  # ab_rows / gate_rows = Na
         grow = Na if B > 1 else 0
         # the context in the form the dense steps of this edit use: the same cache entry serves both kinds
         ctx = self._context(text, image, share_image=B == 2 and self._share_image(text, image))
         if ctx.f8:
             raise NotImplementedError("sparse region edits with fp8 cross-attention are not implemented")
-        Tt, Ti = ctx.Tt, ctx.Ti
         for li, p in enumerate(self.blk):
             # 1. self-attention: q | k | v of the active rows as ONE product; k and v are scattered into the layer's cache, v transposed on
             # the way (measured at 720p, profiles/notes_region_sparse.md: the scatter from row-major V is 1.0 - 1.7 x faster than from the
@@ -1274,34 +1270,14 @@ class DiTEngine:
             ops.sparse_scatter_rows_(st.k[li], ws.qkv[:, D : 2 * D], ids, batch=B)
             ops.sparse_scatter_vt_(st.vt[li], ws.qkv[:, 2 * D :], ids, N, batch=B, src_rows=True)
             ops.attention_vt(ws.qkv[:, :D], st.k[li], st.vt[li], H, out=ws.att, batch=B)
-            ops.gemm(ws.att, p.w_o1, p.b_o1, out=x, epilogue=ops.EPI_GATE_RES, gate=gate_msa[li] if B > 1 else mods[0][li, 2], res=x, gate_rows=grow)
-            # 2. cross-attention: row-local, the launch the dense step makes with Na query rows per sample
-            if p.n2w is not None:
-                ops.ln_affine(x, p.n2w, p.n2b, eps, out=ws.h)
-                ops.gemm(ws.h, p.w_q2, p.b_q2, out=ws.q2)
-            else:
-                ops.gemm(x, p.w_q2, p.b_q2, out=ws.q2)
-            ops.rmsnorm_rope_(ws.q2, p.nq2, None, hd, eps)
-            k_t, v_t, k_i, v_i = ctx.kv[li]
-            if ctx.valid is not None:
-                ops.attention_2seg_vt_weighted(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, valid1=ctx.valid, w1=ctx.w,
-                                               share2=ctx.img_shared, cols1=ctx.c1, cols2=None if ctx.img_shared else ctx.c2)
-            elif ctx.img_shared:
-                ops.attention_2seg_vt_shared(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, share2=True, cols1=ctx.c1)
-            elif ctx.vt:
-                ops.attention_2seg_vt(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, cols1=ctx.c1, cols2=ctx.c2)
-            elif k_i is not None:
-                ops.attention(ws.q2, k_t, v_t, H, out=ws.att, k2=k_i, v2=v_i, batch=B)
-            else:
-                ops.attention(ws.q2, k_t, v_t, H, out=ws.att, batch=B)
-            ops.gemm(ws.att, p.w_o2, p.b_o2, out=x, epilogue=ops.EPI_GATE_RES, gate=None, res=x)
-            # 3. feed-forward
-            ops.ln_affine(x, mod[li, 0, 4], mod[li, 0, 3], eps, out=ws.h, ab_rows=Na, ab_stride=6 * D)
-            ops.gemm(ws.h, p.w_f1, p.b_f1, out=ws.ffn, epilogue=ops.EPI_BIAS_GELU)
-            ops.gemm(ws.ffn, p.w_f2, p.b_f2, out=x, epilogue=ops.EPI_GATE_RES, gate=gate_ffn[li] if B > 1 else mods[0][li, 5], res=x, gate_rows=grow)
+            self._linear(ws, ws.att, p, "o1", x, epilogue=ops.EPI_GATE_RES, gate=gate_msa[li], res=x, gate_rows=grow)
+            # 2. cross-attention and 3. feed-forward: row-local, the launches the dense step makes with Na rows per sample
+            self._cross_queries(ws, x, ws.q2, p, ctx)
+            self._cross_attention(ws, ws.q2, ctx, li, B)
+            self._linear(ws, ws.att, p, "o2", x, epilogue=ops.EPI_GATE_RES, gate=None, res=x)
+            self._ffn(ws, x, p, mod[li, 0, 4], mod[li, 0, 3], gate_ffn[li], Na, grow)
         # K18 on the active rows, then their cells of an output that is zero elsewhere
-        ops.ln_affine(x, mod_out[0, 0, 1], mod_out[0, 0, 0], eps, out=ws.h, ab_rows=Na, ab_stride=2 * D)
-        ops.gemm(ws.h, self.w_out, self.b_out, out=ws.head)
+        self._head_rows(ws, x, mod_out, Na)
         out = torch.zeros((B, cfg.out_channels, T, Hh, Ww), dtype=torch.bfloat16, device=self.dev)
         for b in range(B):
             ops.sparse_unpatchify_(out[b], ws.head[rows[b]], ids)
@@ -1361,8 +1337,6 @@ class DiTEngine:
             Nl = N
         ws = self._workspace(B * Nl)
         hidden = hidden.to(torch.bfloat16).contiguous()
-        # integer timesteps as in the diffusers pipeline; floating-point ones (sibling stacks) keep their fraction
-        timestep = timestep.to(device=self.dev, dtype=torch.float32 if timestep.is_floating_point() else torch.int64).contiguous()
         rows = [slice(b * Nl, (b + 1) * Nl) for b in range(B)]
 
         # The guidance pair with shared inputs (model._shared_inputs, declared by the denoising loop): the image context is projected once
@@ -1413,66 +1387,27 @@ class DiTEngine:
                     tr.copy_(ws.x)
         skip = tea == "skip"
 
-        # K2 per sample: sinusoid -> time_embedder (fp32) -> temb (bf16-rounded) -> silu -> time_proj -> AdaLN tables
-        mods, gates1, gates2, mods_out = [], [], [], []
-        for b in range(1 if share else B):
-            sin = ops.timestep_sinusoid(timestep[b : b + 1], cfg.freq_dim)
-            h1 = ops.gemv(self.te_w1, sin, self.te_b1, flags=2)
-            temb = ops.gemv(self.te_w2, h1, self.te_b2, flags=4)
-            if not skip:
-                tproj = ops.gemv(self.tp_w, temb, self.tp_b, flags=1 | 4)  # [6*D]
-                mods.append(ops.modulation(self.tables, tproj.view(6, D), one_mask=0b010010))  # [L,6,D]: shift,1+scale,gate,...
-            mods_out.append(ops.modulation(self.table_out, temb.view(1, D), one_mask=0b10))  # [1,2,D]: shift, 1+scale
-        if share:  # one timestep: one set of tables, stacked twice for the per-sample row strides of the launches behind the fan-out
-            mods, mods_out = mods * B, mods_out * B
-        if not skip:
-            mod = torch.stack(mods, dim=1).contiguous()  # [L, B, 6, D]: per-sample AdaLN rows (ab_rows / gate_rows = tokens per sample)
-        mod_out = torch.stack(mods_out, dim=0).contiguous()  # [B, 1, 2, D]
+        # K2; the shared pair has one timestep: one set of tables, stacked twice for the per-sample row strides of the launches behind the fan-out
+        mods, mod, mod_out, gate_msa, gate_ffn = self._time_tables(timestep, 1 if share else B, B, blocks=not skip)
         x = ws.x
         if skip:
             return self._head(ws, x, mod_out, sp, B, T, Hh, Ww, N, Nl, rows)
-        if B > 1:  # per-sample gate vectors, stacked [L, B, D] for the GEMM epilogue
-            gate_msa = mod[:, :, 2].contiguous()
-            gate_ffn = mod[:, :, 5].contiguous()
 
         ctx = self._context(text, image, share_image=share_img)
-        Tt, Ti = ctx.Tt, ctx.Ti
         grow = Nl if B > 1 else 0
-
-        fuse_o = self.mx and self.fuse_attn_quant and D % 128 == 0  # MX: both attention kernels emit the out-projections' fp8 operands themselves
-        fuse_o1, fuse_o2 = fuse_o and "o1" in self.fp8_set, fuse_o and "o2" in self.fp8_set  # (only for an out-projection that runs in fp8)
-
-        def ffn(li, p):  # 3. feed-forward
-            if self.mx and self.fuse_quant and "f1" in self.fp8_set and "f2" in self.fp8_set:
-                # MX: the up-projection's bias + GELU epilogue emits the down-projection's fp8 operand and its block scales directly (a
-                # block = 32 consecutive output columns: no row-wide reduction) - no bf16 [N, F] matrix, no quantisation pass
-                aq = ws.a8[:, :D]
-                ops.ln_affine_mxfp8(x, mod[li, 0, 4], mod[li, 0, 3], eps, out=aq, scale=ws.s8, ab_rows=Nl, ab_stride=6 * D)
-                ops.gemm_mxfp8_gelu_quant(aq, ws.s8, *p.q_f1, p.b_f1, out=ws.a8b, scale=ws.s8b)
-                ops.gemm_mxfp8(ws.a8b, ws.s8b, *p.q_f2, p.b_f2, out=x, epilogue=ops.EPI_GATE_RES,
-                               gate=gate_ffn[li] if B > 1 else mods[0][li, 5], res=x, gate_rows=grow)
-            else:
-                self._ln_linear(ws, x, mod[li, 0, 4], mod[li, 0, 3], p, "f1", ws.ffn, ab_rows=Nl, ab_stride=6 * D, epilogue=ops.EPI_BIAS_GELU)
-                self._linear(ws, ws.ffn, p, "f2", x, epilogue=ops.EPI_GATE_RES, gate=gate_ffn[li] if B > 1 else mods[0][li, 5],
-                             res=x, gate_rows=grow)
 
         for li, p in enumerate(self.blk):
             if share and li == 0:
                 # block 0 up to its cross-attention on the one shared sample (the B = 1 launches on N rows), then the fan-out: queries shared,
                 # text keys per sample, image keys shared, output per sample; the out-projection adds the shared residual to both
-                self._block0_shared_prefix(ws, xs, p, mods[0], cs, N)
+                self._block0_shared_prefix(ws, xs, p, mods[0], cs, N, ctx)
                 if sparse_st is not None:  # refresh: the one shared sample's K / V^T are both samples'
                     for b in range(B):
                         sparse_st.k[0][rows[b]].copy_(ws.qkv[:N, D : 2 * D])
                         sparse_st.vt[0][:, b * N : (b + 1) * N].copy_(ws.vt[:, :N])
-                k_t, v_t, k_i, v_i = ctx.kv[0]
-                if ctx.valid is not None:
-                    ops.attention_2seg_vt_weighted(ws.q2[:N], k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, valid1=ctx.valid, w1=ctx.w,
-                                                   share_q=True, share2=True, cols1=ctx.c1)
-                else:
-                    ops.attention_2seg_vt_shared(ws.q2[:N], k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, share_q=True, share2=True, cols1=ctx.c1)
-                ops.gemm(ws.att, p.w_o2, p.b_o2, out=x, epilogue=ops.EPI_GATE_RES, gate=None, res=xs, res_rows=N)
-                ffn(li, p)
+                self._cross_attention(ws, ws.q2[:N], ctx, li, B, share_q=True)
+                self._linear(ws, ws.att, p, "o2", x, epilogue=ops.EPI_GATE_RES, gate=None, res=xs, res_rows=N)
+                self._ffn(ws, x, p, mod[li, 0, 4], mod[li, 0, 3], gate_ffn[li], Nl, grow)
                 continue
             q_o1 = False
             # 1. self-attention
@@ -1483,30 +1418,15 @@ class DiTEngine:
                 if ws.v8t is None or ws.v8t.shape[0] != B:
                     ws.v8t = ws.sv = None
                 ws.v8t, ws.sv = ops.v_mxfp8_transpose(ws.qkv[:, 2 * D :], Nl, B, H, out=ws.v8t, scale=ws.sv)
-                if fuse_o1:  # the out-projection's MX operand straight from the attention epilogue (no bf16 output, no quantisation pass)
+                if self.fuse_o1:  # the out-projection's MX operand straight from the attention epilogue (no bf16 output, no quantisation pass)
                     ops.attention_mxfp8(ws.q8, ws.sq, ws.k8, ws.sk, ws.v8t, ws.sv, H, batch=B, out8=ws.a8[:, :D], scale8=ws.s8)
                     q_o1 = True
                 else:
                     ops.attention_mxfp8(ws.q8, ws.sq, ws.k8, ws.sk, ws.v8t, ws.sv, H, out=ws.att, batch=B)
                 att = ws.att
             elif sp is None and self.v_transposed and "qkv" not in self.fp8_set and (B * Nl) % 8 == 0 and (B == 1 or Nl % 2 == 0):
-                # q | k as one GEMM, V^T = (h.W_v^T)^T by a GEMM whose epilogue stores the transpose (round 6; rounds 2-5: the operand roles
-                # swapped, bias along rows - what shapes outside the large tile still run): the attention kernel's V^T operand [D][keys of all
-                # samples] without a transpose pass; K and V^T tiles both go by LDS-DMA
-                if getattr(ws, "vt", None) is None:
-                    ws.vt = torch.zeros((D, ops.vt_columns(B * Nl)), dtype=torch.bfloat16, device=self.dev)  # padding columns stay zero
-                ops.ln_affine(x, mod[li, 0, 1], mod[li, 0, 0], eps, out=ws.h, ab_rows=Nl, ab_stride=6 * D)
-                ops.gemm(ws.h, p.w_qkv[: 2 * D], p.b_qkv[: 2 * D], out=ws.qkv[:, : 2 * D])
-                if _VT_GEMM_SWAPPED:  # (A/B knob of tools: CE_VT_GEMM=row - the rounds-2-5 form of the same product)
-                    ops.gemm(p.w_qkv[2 * D :], ws.h, p.b_qkv[2 * D :], out=ws.vt[:, : B * Nl], epilogue=ops.EPI_BIAS_ROW)
-                else:
-                    ops.gemm(ws.h, p.w_qkv[2 * D :], p.b_qkv[2 * D :], out=ws.vt[:, : B * Nl], epilogue=ops.EPI_BIAS_T)  # (stores the transpose: V^T)
-                ops.rmsnorm_rope_(ws.qkv[:, :D], p.nq1, cs, hd, eps, x2=ws.qkv[:, D : 2 * D], w2=p.nk1)
-                if sparse_st is not None:  # refresh
-                    sparse_st.k[li].copy_(ws.qkv[:, D : 2 * D])
-                    sparse_st.vt[li][:, : B * Nl].copy_(ws.vt[:, : B * Nl])
-                ops.attention_vt(ws.qkv[:, :D], ws.qkv[:, D : 2 * D], ws.vt, H, out=ws.att, batch=B)
-                att = ws.att
+                keep = None if sparse_st is None else (sparse_st.k[li], sparse_st.vt[li])  # refresh
+                att = self._self_attention_vt(ws, x, B * Nl, B, p, mod[li, 0, 1], mod[li, 0, 0], cs, keep)
             elif sp is None:  # all samples in one launch (stacked rows)
                 self._ln_linear(ws, x, mod[li, 0, 1], mod[li, 0, 0], p, "qkv", ws.qkv, ab_rows=Nl, ab_stride=6 * D)
                 ops.rmsnorm_rope_(ws.qkv[:, :D], p.nq1, cs, hd, eps, x2=ws.qkv[:, D : 2 * D], w2=p.nk1)  # q and k, all samples
@@ -1514,51 +1434,15 @@ class DiTEngine:
                 att = ws.att
             else:
                 att = self._self_attention_ulysses(ws, sp, x, mod[li, 0, 1], mod[li, 0, 0], p, cs, N, Nl, B)
-            self._linear(ws, att, p, "o1", x, quantised=q_o1, epilogue=ops.EPI_GATE_RES, gate=gate_msa[li] if B > 1 else mods[0][li, 2],
-                         res=x, gate_rows=grow)
+            self._linear(ws, att, p, "o1", x, quantised=q_o1, epilogue=ops.EPI_GATE_RES, gate=gate_msa[li], res=x, gate_rows=grow)
             if self._tap is not None and li == 0 and not torch.cuda.is_current_stream_capturing():
                 self._tap["x_pre_cross0"] = x.clone()
             # 2. cross-attention (text + image segments)
-            if p.n2w is not None:
-                self._ln_linear(ws, x, p.n2w, p.n2b, p, "q2", ws.q2)
-            else:
-                self._linear(ws, x, p, "q2", ws.q2)
-            q_o2 = bool(ctx.vt and fuse_o2)
-            if ctx.f8:  # MXFP8 (round 5): text segment -> bf16, image segment adds it and emits bf16 or the out-projection's MX operand
-                seg_t, seg_i = ctx.kv[li]
-                ops.rmsnorm_rope_mxfp8(ws.q2, p.nq2, None, hd, eps, out=ws.q8, scale=ws.sq, post_scale=ops.MXFP8_Q_SCALE)
-                if seg_i is None and fuse_o2:
-                    ops.attention_mxfp8(ws.q8, ws.sq, *seg_t, H, batch=B, out8=ws.a8[:, :D], scale8=ws.s8)
-                else:
-                    ops.attention_mxfp8(ws.q8, ws.sq, *seg_t, H, out=ws.att, batch=B)
-                    if seg_i is not None and fuse_o2:
-                        ops.attention_mxfp8(ws.q8, ws.sq, *seg_i, H, batch=B, out8=ws.a8[:, :D], scale8=ws.s8, add=ws.att)
-                    elif seg_i is not None:
-                        ops.attention_mxfp8(ws.q8, ws.sq, *seg_i, H, out=ws.att, batch=B, add=ws.att)
-                q_o2 = fuse_o2
-                self._linear(ws, ws.att, p, "o2", x, quantised=q_o2, epilogue=ops.EPI_GATE_RES, gate=None, res=x)
-                k_t = None
-            else:
-                ops.rmsnorm_rope_(ws.q2, p.nq2, None, hd, eps)
-                k_t, v_t, k_i, v_i = ctx.kv[li]
-            if k_t is None:
-                pass
-            elif ctx.valid is not None:  # compacted text: per-sample valid keys, the padding as one weighted key
-                ops.attention_2seg_vt_weighted(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, valid1=ctx.valid, w1=ctx.w,
-                                               share2=ctx.img_shared, cols1=ctx.c1, cols2=None if ctx.img_shared else ctx.c2)
-            elif ctx.vt and fuse_o2:
-                ops.attention_2seg_vt(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, batch=B, cols1=ctx.c1, cols2=ctx.c2, out8=ws.a8[:, :D], scale8=ws.s8)
-            elif ctx.img_shared:  # one image segment for both samples
-                ops.attention_2seg_vt_shared(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, share2=True, cols1=ctx.c1)
-            elif ctx.vt:  # both segments' K and V^T tiles by LDS-DMA (v_t / v_i are V^T row blocks of this layer)
-                ops.attention_2seg_vt(ws.q2, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=B, cols1=ctx.c1, cols2=ctx.c2)
-            elif k_i is not None:
-                ops.attention(ws.q2, k_t, v_t, H, out=ws.att, k2=k_i, v2=v_i, batch=B)
-            else:
-                ops.attention(ws.q2, k_t, v_t, H, out=ws.att, batch=B)
-            if k_t is not None:
-                self._linear(ws, ws.att, p, "o2", x, quantised=q_o2, epilogue=ops.EPI_GATE_RES, gate=None, res=x)
-            ffn(li, p)
+            self._cross_queries(ws, x, ws.q2, p, ctx)
+            q_o2 = self._cross_attention(ws, ws.q2, ctx, li, B)
+            self._linear(ws, ws.att, p, "o2", x, quantised=q_o2, epilogue=ops.EPI_GATE_RES, gate=None, res=x)
+            # 3. feed-forward
+            self._ffn(ws, x, p, mod[li, 0, 4], mod[li, 0, 3], gate_ffn[li], Nl, grow)
 
         if tea is not None:  # the saved tokens become the residual of this (computed) step
             if tea == "measure" and tea_prev is not None:
@@ -1570,40 +1454,137 @@ class DiTEngine:
             sparse_st.valid = True
         return self._head(ws, x, mod_out, sp, B, T, Hh, Ww, N, Nl, rows)
 
-    def _block0_shared_prefix(self, ws, xs, p, mods0, cs, N: int):
+    def _block0_shared_prefix(self, ws, xs, p, mods0, cs, N: int, ctx):
         """Block 0 from its first LayerNorm to the normed cross-attention queries for ONE sample's N rows (the guidance pair's shared prefix):
-        the launches a B = 1 forward makes, on the first N rows of the workspaces; xs [N, D] is updated in place, ws.q2[:N] receives the queries."""
-        D, H, hd, eps = self.D, self.H, self.cfg.attention_head_dim, self.cfg.eps
-        h, qkv = ws.h[:N], ws.qkv[:N]
-        # V^T goes into sample 0's columns [0, N) of the stacked pair's buffer.  When N % 64 != 0 the kernel's last key strip also reads columns
-        # [N, pad64(N)): zeros after the fill below, sample 1's V^T of the previous stacked block from then on.  That is exactly what sample 0 of
-        # every stacked launch meets (ce_attention_vt_bf16: columns past a sample's keys are finite and meet P = 0), so the result is bit-equal
-        # to a B = 1 forward's, whose strip holds zeros - as long as those columns are finite, which zeros and projected values are.
-        if getattr(ws, "vt", None) is None:
-            ws.vt = torch.zeros((D, ops.vt_columns(2 * N)), dtype=torch.bfloat16, device=self.dev)
-        ops.ln_affine(xs, mods0[0, 1], mods0[0, 0], eps, out=h, ab_rows=N, ab_stride=6 * D)
-        ops.gemm(h, p.w_qkv[: 2 * D], p.b_qkv[: 2 * D], out=qkv[:, : 2 * D])
-        if _VT_GEMM_SWAPPED:
-            ops.gemm(p.w_qkv[2 * D :], h, p.b_qkv[2 * D :], out=ws.vt[:, :N], epilogue=ops.EPI_BIAS_ROW)
-        else:
-            ops.gemm(h, p.w_qkv[2 * D :], p.b_qkv[2 * D :], out=ws.vt[:, :N], epilogue=ops.EPI_BIAS_T)
-        ops.rmsnorm_rope_(qkv[:, :D], p.nq1, cs, hd, eps, x2=qkv[:, D : 2 * D], w2=p.nk1)
-        ops.attention_vt(qkv[:, :D], qkv[:, D : 2 * D], ws.vt, H, out=ws.att[:N], batch=1)
-        ops.gemm(ws.att[:N], p.w_o1, p.b_o1, out=xs, epilogue=ops.EPI_GATE_RES, gate=mods0[0, 2], res=xs)
+        the launches a B = 1 forward makes, on the first N rows of the workspaces; xs [N, D] is updated in place, ws.q2[:N] receives the queries.
+        V^T goes into sample 0's columns [0, N) of the stacked pair's buffer.  When N % 64 != 0 the kernel's last key strip also reads columns
+        [N, pad64(N)): zeros after the first fill, sample 1's V^T of the previous stacked block from then on.  That is exactly what sample 0 of
+        every stacked launch meets (ce_attention_vt_bf16: columns past a sample's keys are finite and meet P = 0), so the result is bit-equal
+        to a B = 1 forward's, whose strip holds zeros - as long as those columns are finite, which zeros and projected values are."""
+        att = self._self_attention_vt(ws, xs, N, 1, p, mods0[0, 1], mods0[0, 0], cs)
+        self._linear(ws, att, p, "o1", xs, epilogue=ops.EPI_GATE_RES, gate=mods0[0, 2], res=xs)
         if self._tap is not None and not torch.cuda.is_current_stream_capturing():
             self._tap["x_pre_cross0"] = xs.clone()
+        self._cross_queries(ws, xs, ws.q2[:N], p, ctx)
+
+    # -- the launch groups of a block, each on the rows it is given -------------------------
+    def _time_tables(self, timestep: torch.Tensor, n: int, B: int, blocks: bool = True):
+        """K2 for the first n samples: sinusoid -> time_embedder (fp32) -> temb (bf16-rounded) -> silu -> time_proj -> AdaLN tables, stacked
+        for B samples (n = B, or n = 1: one set of tables stacked B times).  Returns
+          mods      per computed sample [L, 6, D]: shift, 1 + scale, gate, ... of every block;
+          mod       [L, B, 6, D]: per-sample AdaLN rows (ab_rows / gate_rows = token rows per sample);
+          mod_out   [B, 1, 2, D]: the head's shift, 1 + scale;
+          gate_msa, gate_ffn   the gate rows of the two GEMM epilogues per layer: stacked [L, B, D], or for B = 1 the rows of mods[0].
+        blocks=False (a skipped TeaCache step): mod_out only."""
+        D = self.D
+        # integer timesteps as in the diffusers pipeline; floating-point ones (sibling stacks) keep their fraction
+        timestep = timestep.to(device=self.dev, dtype=torch.float32 if timestep.is_floating_point() else torch.int64).contiguous()
+        mods, mods_out = [], []
+        for b in range(n):
+            sin = ops.timestep_sinusoid(timestep[b : b + 1], self.cfg.freq_dim)
+            h1 = ops.gemv(self.te_w1, sin, self.te_b1, flags=2)
+            temb = ops.gemv(self.te_w2, h1, self.te_b2, flags=4)
+            if blocks:
+                tproj = ops.gemv(self.tp_w, temb, self.tp_b, flags=1 | 4)  # [6*D]
+                mods.append(ops.modulation(self.tables, tproj.view(6, D), one_mask=0b010010))
+            mods_out.append(ops.modulation(self.table_out, temb.view(1, D), one_mask=0b10))
+        if n != B:
+            mods, mods_out = mods * B, mods_out * B
+        mod = torch.stack(mods, dim=1).contiguous() if blocks else None
+        mod_out = torch.stack(mods_out, dim=0).contiguous()
+        if not blocks:
+            return mods, mod, mod_out, None, None
+        if B > 1:
+            return mods, mod, mod_out, mod[:, :, 2].contiguous(), mod[:, :, 5].contiguous()
+        return mods, mod, mod_out, mods[0][:, 2], mods[0][:, 5]
+
+    def _self_attention_vt(self, ws, x, n: int, batch: int, p, a_row, b_row, cs, keep=None):
+        """The bf16 V^T self-attention of the first n rows of the workspace (`batch` samples of n / batch rows): LayerNorm with the AdaLN rows,
+        q | k as one GEMM, V^T = (h.W_v^T)^T by a GEMM whose epilogue stores the transpose - the attention kernel's V^T operand [D][keys of
+        all samples] without a transpose pass; K and V^T tiles both go by LDS-DMA.  keep = (k, vt): the normed K and V^T are also copied
+        there (a refresh step's cache).  Returns the attention output rows."""
+        D, hd, eps = self.D, self.cfg.attention_head_dim, self.cfg.eps
+        h, qkv, att = ws.h[:n], ws.qkv[:n], ws.att[:n]
+        if getattr(ws, "vt", None) is None:  # (all rows of the workspace, whichever range comes first)
+            ws.vt = torch.zeros((D, ops.vt_columns(ws.x.shape[0])), dtype=torch.bfloat16, device=self.dev)  # padding columns stay zero
+        ops.ln_affine(x, a_row, b_row, eps, out=h, ab_rows=n // batch, ab_stride=6 * D)
+        ops.gemm(h, p.w_qkv[: 2 * D], p.b_qkv[: 2 * D], out=qkv[:, : 2 * D])
+        ops.gemm(h, p.w_qkv[2 * D :], p.b_qkv[2 * D :], out=ws.vt[:, :n], epilogue=ops.EPI_BIAS_T)
+        ops.rmsnorm_rope_(qkv[:, :D], p.nq1, cs, hd, eps, x2=qkv[:, D : 2 * D], w2=p.nk1)
+        if keep is not None:
+            keep[0].copy_(qkv[:, D : 2 * D])
+            keep[1][:, :n].copy_(ws.vt[:, :n])
+        ops.attention_vt(qkv[:, :D], qkv[:, D : 2 * D], ws.vt, self.H, out=att, batch=batch)
+        return att
+
+    def _cross_queries(self, ws, x, q2, p, ctx):
+        """The cross-attention queries of the rows of x into q2: norm2 (where the model has one), the projection, the RMS norm - for an
+        MXFP8 context into the quantised ws.q8 / ws.sq instead of in place."""
+        hd, eps = self.cfg.attention_head_dim, self.cfg.eps
         if p.n2w is not None:
-            ops.ln_affine(xs, p.n2w, p.n2b, eps, out=h)
-            ops.gemm(h, p.w_q2, p.b_q2, out=ws.q2[:N])
+            self._ln_linear(ws, x, p.n2w, p.n2b, p, "q2", q2)
         else:
-            ops.gemm(xs, p.w_q2, p.b_q2, out=ws.q2[:N])
-        ops.rmsnorm_rope_(ws.q2[:N], p.nq2, None, hd, eps)
+            self._linear(ws, x, p, "q2", q2)
+        if ctx.f8:
+            ops.rmsnorm_rope_mxfp8(q2, p.nq2, None, hd, eps, out=ws.q8, scale=ws.sq, post_scale=ops.MXFP8_Q_SCALE)
+        else:
+            ops.rmsnorm_rope_(q2, p.nq2, None, hd, eps)
+
+    def _cross_attention(self, ws, q, ctx, li: int, batch: int, share_q: bool = False) -> bool:
+        """Layer li's cross-attention (text + image segments) of the queries q into ws.att, by the kernel the context's form asks for.
+        share_q: q holds ONE sample's queries for all `batch` samples.  Returns whether the output is the out-projection's MX operand in
+        ws.a8 / ws.s8 (the fused quantisation of the fp8 mode) instead of bf16 rows in ws.att."""
+        D, H, Tt, Ti, fuse = self.D, self.H, ctx.Tt, ctx.Ti, self.fuse_o2
+        if ctx.f8:  # MXFP8 (round 5): text segment -> bf16, image segment adds it and emits bf16 or the out-projection's MX operand
+            seg_t, seg_i = ctx.kv[li]
+            if seg_i is None and fuse:
+                ops.attention_mxfp8(ws.q8, ws.sq, *seg_t, H, batch=batch, out8=ws.a8[:, :D], scale8=ws.s8)
+            else:
+                ops.attention_mxfp8(ws.q8, ws.sq, *seg_t, H, out=ws.att, batch=batch)
+                if seg_i is not None and fuse:
+                    ops.attention_mxfp8(ws.q8, ws.sq, *seg_i, H, batch=batch, out8=ws.a8[:, :D], scale8=ws.s8, add=ws.att)
+                elif seg_i is not None:
+                    ops.attention_mxfp8(ws.q8, ws.sq, *seg_i, H, out=ws.att, batch=batch, add=ws.att)
+            return fuse
+        k_t, v_t, k_i, v_i = ctx.kv[li]
+        if ctx.valid is not None:  # compacted text: per-sample valid keys, the padding as one weighted key
+            ops.attention_2seg_vt_weighted(q, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=batch, valid1=ctx.valid, w1=ctx.w,
+                                           share_q=share_q, share2=ctx.img_shared, cols1=ctx.c1, cols2=None if ctx.img_shared else ctx.c2)
+        elif ctx.vt and fuse:
+            ops.attention_2seg_vt(q, k_t, v_t, Tt, k_i, v_i, Ti, H, batch=batch, cols1=ctx.c1, cols2=ctx.c2, out8=ws.a8[:, :D], scale8=ws.s8)
+            return True
+        elif ctx.img_shared:  # one image segment for all samples
+            ops.attention_2seg_vt_shared(q, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=batch, share_q=share_q, share2=True, cols1=ctx.c1)
+        elif ctx.vt:  # both segments' K and V^T tiles by LDS-DMA (v_t / v_i are V^T row blocks of this layer)
+            ops.attention_2seg_vt(q, k_t, v_t, Tt, k_i, v_i, Ti, H, out=ws.att, batch=batch, cols1=ctx.c1, cols2=ctx.c2)
+        elif k_i is not None:
+            ops.attention(q, k_t, v_t, H, out=ws.att, k2=k_i, v2=v_i, batch=batch)
+        else:
+            ops.attention(q, k_t, v_t, H, out=ws.att, batch=batch)
+        return False
+
+    def _ffn(self, ws, x, p, a_row, b_row, gate, ab_rows: int, gate_rows: int):
+        """The feed-forward of the rows of x, in place: LayerNorm with the AdaLN rows, up-projection + GELU, gated down-projection + residual."""
+        D, eps = self.D, self.cfg.eps
+        if self.mx and self.fuse_quant and "f1" in self.fp8_set and "f2" in self.fp8_set:
+            # MX: the up-projection's bias + GELU epilogue emits the down-projection's fp8 operand and its block scales directly (a
+            # block = 32 consecutive output columns: no row-wide reduction) - no bf16 [N, F] matrix, no quantisation pass
+            aq = ws.a8[:, :D]
+            ops.ln_affine_mxfp8(x, a_row, b_row, eps, out=aq, scale=ws.s8, ab_rows=ab_rows, ab_stride=6 * D)
+            ops.gemm_mxfp8_gelu_quant(aq, ws.s8, *p.q_f1, p.b_f1, out=ws.a8b, scale=ws.s8b)
+            ops.gemm_mxfp8(ws.a8b, ws.s8b, *p.q_f2, p.b_f2, out=x, epilogue=ops.EPI_GATE_RES, gate=gate, res=x, gate_rows=gate_rows)
+        else:
+            self._ln_linear(ws, x, a_row, b_row, p, "f1", ws.ffn, ab_rows=ab_rows, ab_stride=6 * D, epilogue=ops.EPI_BIAS_GELU)
+            self._linear(ws, ws.ffn, p, "f2", x, epilogue=ops.EPI_GATE_RES, gate=gate, res=x, gate_rows=gate_rows)
+
+    def _head_rows(self, ws, x, mod_out, ab_rows: int):
+        """K18 on the rows of x: the head's LayerNorm with its AdaLN rows and the output projection, into ws.head."""
+        ops.ln_affine(x, mod_out[0, 0, 1], mod_out[0, 0, 0], self.cfg.eps, out=ws.h, ab_rows=ab_rows, ab_stride=2 * self.D)
+        ops.gemm(ws.h, self.w_out, self.b_out, out=ws.head)
 
     def _head(self, ws, x, mod_out, sp, B, T, Hh, Ww, N, Nl, rows):
-        cfg, D, eps = self.cfg, self.D, self.cfg.eps
-        # K18
-        ops.ln_affine(x, mod_out[0, 0, 1], mod_out[0, 0, 0], eps, out=ws.h, ab_rows=Nl, ab_stride=2 * D)
-        ops.gemm(ws.h, self.w_out, self.b_out, out=ws.head)
+        cfg = self.cfg
+        self._head_rows(ws, x, mod_out, Nl)
         out = torch.empty((B, cfg.out_channels, T, Hh, Ww), dtype=torch.bfloat16, device=self.dev)
         if sp is None:
             for b in range(B):

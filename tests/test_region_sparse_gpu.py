@@ -1,4 +1,6 @@
 """Sparse region edits on the device (chronoedit_amd/sparse_region.py, DiTEngine.sparse_begin / _forward_sparse, pipeline.denoise).
+`_forward_sparse` owns the sparse self-attention half (fused q|k|v, the two scatters); its time tables, cross-attention, FFN and head rows
+are the dense forward's own methods (`_time_tables`, `_cross_queries`, `_cross_attention`, `_ffn`, `_head_rows`).
 
 Latents 1 x 16 x 2 x 16 x 20 - N = 160 tokens, 2.5 key tiles - with a guidance pair and 6 steps on the tiny model of tests/test_region_gpu.py
 (2 heads x 128, 2 layers, ffn 512).  The mask is 128 x 160 with a rectangle over latent rows 4..9 and columns 6..13: with margin 1 that is 60
