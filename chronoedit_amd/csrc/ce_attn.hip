@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "ce_common.h"
+#include "ce_internal.h"
 
 namespace {
 
@@ -1486,7 +1487,6 @@ __global__ __launch_bounds__(256) void v_transpose_kernel(const bf16* __restrict
 // of the parity tests).  The other loop bodies of round 1 (XOR-swizzled pipeline, ping-pong, one wave per SIMD) and their
 // ablation build lost every A/B and were removed in round 2; git history has them.
 #ifdef CE_DIAGNOSTICS
-extern "C" int ce_diag_mx_exact_hits(unsigned long long* out, int reset);
 // hits[0] = waves x key tiles that took the exact route in the bf16 software-pipelined kernels (attn_fwd_sp_kernel, attn_fwd_w4_kernel) since
 // the last reset, hits[1] = the same for the MXFP8 kernel; reset != 0 zeroes both.  Synchronises the device (a diagnostic, not a launcher).
 CE_API int ce_diag_attention_exact_route_hits(unsigned long long* hits, int reset) {
@@ -1595,12 +1595,6 @@ CE_API int ce_v_transpose_blocked_bf16(const void* v, int ldv, void* vt, int ldv
                      blk_rows, blk_stride, vt_sample_cols);
   return (int)hipGetLastError();
 }
-
-// the 16 x 16 x 32 body of the plain-layout V^T attention (ce_attn16.hip; ce_set_attention_waves(16))
-#ifdef CE_DIAGNOSTICS
-extern "C" int ce_attn16_launch(const void* Q, const void* K, const void* Vt, int len, int ldk, int ldvt, void* O, int Nq, int H, int ldq, int ldo,
-                                float sl2, int batch, int cus, hipStream_t stream);
-#endif
 
 /* Self-attention with V handed over TRANSPOSED (V^T [H * 128][ldvt]): both K and V^T tiles reach LDS by LDS-DMA, no register
  * staging.  One KV segment, software-pipelined kernel only.  blk_rows == 0: plain layout (sample b's token g in row b N + g of Q / K / O,

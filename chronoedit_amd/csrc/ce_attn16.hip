@@ -31,6 +31,7 @@
 //    ce_v_transpose_bf16 and the CE_EPI_BIAS_ROW projection write zeros there): masked keys get P = 0, and 0 x NaN garbage would still be NaN.
 //  * Built into libchronoedit_hip_diag.so ONLY (round 6): the product library neither contains nor dispatches to this body.
 #include "ce_common.h"
+#include "ce_internal.h"
 
 namespace {
 

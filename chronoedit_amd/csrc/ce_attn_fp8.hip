@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "ce_common.h"
+#include "ce_internal.h"
 
 namespace {
 #ifdef CE_DIAGNOSTICS

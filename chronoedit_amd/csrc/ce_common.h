@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ce_gemm_plan.h"  // error codes; the host arithmetic of the GEMM launchers (no HIP in it)
+
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -33,12 +35,6 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 #define CE_DIAG_COUNT_EXACT(counter) do { } while (0)
 #endif
 
-// error codes returned by every extern "C" launcher (include/chronoedit_hip.h)
-#define CE_OK 0
-#define CE_ERR_ARG (-1)
-#define CE_ERR_SHAPE (-2)
-#define CE_ERR_ALIGN (-3)
-
 // hipFuncSetAttribute applies to the CURRENT device only: launchers remember "attribute set" per device, not per process
 #define CE_MAX_DEVICES 16
 inline int ce_device_slot() {
@@ -56,27 +52,6 @@ inline int ce_device_cus() {
     cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
   }
   return cus;
-}
-
-// Split-K plan of the large-tile GEMMs: the `tail` workgroups of a partially filled last round (tiles % cus) are cut along K into `split`
-// pieces, each writing an fp32 slab of slab_bytes that a second launch sums.  The largest split <= min(cus / tail, 8) that gives every piece
-// an even number of the kt K-tiles and whose slabs fit in ws_bytes (0: no scratch); 1: the tail runs whole.
-inline int ce_split_k(int tail, int kt, int cus, long long slab_bytes, long long ws_bytes) {
-  if (tail <= 0) return 1;
-  for (int s = cus / tail < 8 ? cus / tail : 8; s >= 2; --s)
-    if (kt % (2 * s) == 0 && tail * s * slab_bytes <= ws_bytes) return s;
-  return 1;
-}
-
-// K-segmented operand of the large-tile GEMMs: the kernels find the segment of K-tile t as (t * magic) >> 16, i.e. t / tps for tps = seg_k / bk
-// K-tiles per segment.  The magic when seg_k is a whole number of K-tiles and the product is exact for every t < kt, 0 otherwise.
-inline uint32_t ce_seg_magic(int seg_k, int bk, int kt) {
-  if (seg_k <= 0 || seg_k % bk) return 0;
-  const int tps = seg_k / bk;
-  const uint32_t magic = 65536u / (uint32_t)tps + 1u;
-  for (int t = 0; t < kt; ++t)
-    if ((int)((uint32_t)t * magic >> 16) != t / tps) return 0;
-  return magic;
 }
 
 __device__ __forceinline__ float bf16_bits_to_f32(uint32_t bits16) { return __uint_as_float(bits16 << 16); }

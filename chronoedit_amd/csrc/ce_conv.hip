@@ -14,6 +14,7 @@
 //   LDS tiles (16-B chunk XOR swizzle), epilogue through LDS for 16-B stores.  Bound: bf16 MFMA for >= 192 channels,
 //   HBM for the 96-channel full-resolution layers.
 #include "ce_common.h"
+#include "ce_internal.h"
 
 namespace {
 
@@ -704,10 +705,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 }  // namespace
-
-extern "C" int ce_gemm256w4_seg2_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const void* res, int M, int N,
-                                        int K, int lda, int ldw, int ldc, int ldres, int a_seg_k, long long a_seg_stride, int a_seg2_k,
-                                        long long a_seg2_stride, int n_tile, hipStream_t stream);
 
 static int conv3d_gemm_launch(const void* in_stack, const void* weight, int ldw, const float* bias, void* out_stack, const void* res_stack,
                               int T_out, int H, int W, int Cin, int Cout, int KT, int out_cstride, int n_tile, const float* gamma, int apply_silu,

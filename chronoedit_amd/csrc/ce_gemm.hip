@@ -22,6 +22,8 @@
 #include <cmath>
 
 #include "ce_common.h"
+#include "ce_gemm_launch.h"
+#include "ce_internal.h"
 
 #define EPI_BIAS 0
 #define EPI_BIAS_GELU 1
@@ -224,26 +226,6 @@ __global__ __launch_bounds__(256) void gemm_bf16_128(const bf16* __restrict__ A,
 
 }  // namespace
 
-extern "C" int ce_gemm256_supported(int M, int N, int K, int lda, int ldw);
-extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
-                                 hipStream_t stream);
-
-extern "C" void ce_gemm256_set_staggered(int on);
-extern "C" int ce_gemm384_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
-                                 hipStream_t stream);
-extern "C" int ce_gemm288_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
-                                 hipStream_t stream);
-extern "C" int ce_gemm256w4_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                   const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
-                                   int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, int nsa, float* ws,
-                                   size_t ws_bytes, hipStream_t stream);
-
 // kernel selection: -1 = automatic (for large shapes the one-wave-per-SIMD LDS-DMA kernels, macro tile 384 x 256 or 256 x 256 by
 // the round count of the shape: ce_gemm_bf16_tile_rows), 0 = always the
 // 128-tile kernel; whenever the shape allows the 256-tile kernel: 1 = its 8-wave / 8-phase main loop, 2 = the same staggered (two
@@ -279,18 +261,14 @@ CE_API int ce_gemm_bf16_tile_rows(int M, int N, int K, int cus, long long ws_byt
   // power budget); one that can costs its K share plus the fp32 slabs, written and read back at ~6 TB/s (the round-3 form charged an eighth of
   // a round whatever K and the slab volume were).  On the 41 shapes the picks lose 0.4 % of the summed best-tile time (round-3 form: 2.3 %).
   auto cost = [&](int bm) -> double {
-    const long long nwg = (long long)((M + bm - 1) / bm) * ((N + 255) / 256);
-    const long long full = nwg / cus;
-    const int tail = (int)(nwg % cus);
+    const CeGemmPlan p = ce_gemm_plan(M, N, bm, 256, kt, cus, ws_bytes, true);
+    const long long full = ((long long)p.tiles_m * p.tiles_n) / cus;
     // (288 x 256, round 6: 1.125 x the area of the 256-row tile, a twentieth fewer operand bytes per flop; priced between the other two)
     const double llc = (double)M * K * 2.0 > 128.0 * 1048576.0 ? 1.04 : 1.0;
     const double c = bm == 256 ? 1.40 : bm == 288 ? 1.40 * 1.125 * 0.985 * llc : 1.40 * 1.5 * 0.96 * llc;
     double t = (double)full * kt * c;
-    if (tail > 0) {
-      const int split = ce_split_k(tail, kt, cus, bm * 256 * (long long)sizeof(float), ws_bytes);
-      if (split > 1) t += (double)kt / split * c + (double)tail * split * bm * 256.0 * 8.0 / 6.0e6;
-      else t += (double)kt * c * pow((double)tail / cus, 0.3);
-    }
+    if (p.split > 1) t += (double)kt / p.split * c + (double)p.tail * p.split * bm * 256.0 * 8.0 / 6.0e6;
+    else if (p.last_round > 0) t += (double)kt * c * pow((double)p.last_round / cus, 0.3);
     return t;
   };
   const double c384 = cost(384), c256 = cost(256);
@@ -299,8 +277,7 @@ CE_API int ce_gemm_bf16_tile_rows(int M, int N, int K, int cus, long long ws_byt
   // out-projections and the cross-attention's q of the distilled B = 1 step): 500 workgroups = 1.95 rounds against 380 = 1.48 rounds whose tail
   // goes through 97 MB of fp32 slabs: 0.267 against 0.314 ms.  Elsewhere its main loop is 2-6 % behind the larger tile's.
   if (M % 288 == 0) {
-    const long long nwg = (long long)(M / 288) * ((N + 255) / 256);
-    const int tail = (int)(nwg % cus);
+    const int tail = ce_gemm_plan(M, N, 288, 256, 0, cus, 0, false).last_round;  // only the fill of the last round is wanted (no split: kt and scratch do not enter)
     if (tail == 0 || tail * 10 >= cus * 9) {
       const double c288 = cost(288);
       if (c288 < 0.97 * (c384 < c256 ? c384 : c256)) return 288;
@@ -334,8 +311,7 @@ CE_API int ce_gemm_bf16_res(const void* A, const void* W, void* C, const float* 
         ce_gemm256_supported(M, N, K, lda, ldw) && (g_gemm_variant == -1 || g_gemm_variant == 6 || g_gemm_variant == 7)) {
       const int rows = g_gemm_variant == 6 ? 384 : g_gemm_variant == 7 ? 288 : ce_gemm_bf16_tile_rows(M, N, K, cus, scratch_bytes);
       if (rows == 384 || rows == 288) {
-        const long long nwg = (long long)((M + rows - 1) / rows) * ((N + 255) / 256);
-        const int tail = (int)(nwg % cus);
+        const int tail = ce_gemm_plan(M, N, rows, 256, 0, cus, 0, false).last_round;  // only the fill of the last round (no split: kt and scratch do not enter)
         if (g_gemm_variant != -1 || tail == 0 || tail * 10 >= cus * 9)
           return (rows == 384 ? ce_gemm384_launch : ce_gemm288_launch)(A, W, C, bias, EPI_BIAS_T, nullptr, nullptr, M, N, K, lda, ldw, ldc, 0, 0, 0, 0, 0, 0, 0,
                                                                       slabs, ws_bytes, stream);
@@ -378,22 +354,11 @@ CE_API int ce_gemm_bf16_res(const void* A, const void* W, void* C, const float* 
   const long long a_seg_extra = a_seg_k > 0 ? a_seg_stride - a_seg_k : 0;
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   dim3 grid(tiles_m * tiles_n), block(256);
-#define CE_LAUNCH(E)                                                                                              \
-  hipLaunchKernelGGL(gemm_bf16_128<E>, grid, block, 0, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                     (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, 1, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll, \
-                     a_seg_tiles, a_seg_extra)
-  switch (epilogue) {
-    case EPI_BIAS: CE_LAUNCH(EPI_BIAS); break;
-    case EPI_BIAS_GELU: CE_LAUNCH(EPI_BIAS_GELU); break;
-    case EPI_GATE_RES: CE_LAUNCH(EPI_GATE_RES); break;
-    case EPI_BIAS_GELU_ERF: CE_LAUNCH(EPI_BIAS_GELU_ERF); break;
-    case EPI_F32: CE_LAUNCH(EPI_F32); break;
-    case EPI_MUL: CE_LAUNCH(EPI_MUL); break;
-    case EPI_BIAS_ROW: CE_LAUNCH(EPI_BIAS_ROW); break;
-    default: return CE_ERR_ARG;
-  }
-#undef CE_LAUNCH
-  return (int)hipGetLastError();
+  return ce_dispatch_epilogue<EPI_BIAS, EPI_BIAS_GELU, EPI_GATE_RES, EPI_BIAS_GELU_ERF, EPI_F32, EPI_MUL, EPI_BIAS_ROW>(epilogue, [&](auto e) {
+    hipLaunchKernelGGL(gemm_bf16_128<decltype(e)::value>, grid, block, 0, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, (const bf16*)res,
+                       M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, 1, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll, a_seg_tiles, a_seg_extra);
+    return (int)hipGetLastError();
+  });
 }
 
 // The entry point as it was before the residual row period existed: every output row reads its own residual row.
@@ -419,10 +384,9 @@ CE_API int ce_gemm_batched_bf16(const void* A, const void* W, void* C, const flo
   if (epilogue != EPI_BIAS && epilogue != EPI_F32) return CE_ERR_ARG;
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   dim3 grid(tiles_m * tiles_n, batch0 * batch1), block(256);
-#define CE_LAUNCH(E)                                                                                                 \
-  hipLaunchKernelGGL(gemm_bf16_128<E>, grid, block, 0, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, nullptr, \
-                     nullptr, M, N, K, lda, ldw, ldc, 0, 0, 0, tiles_m, tiles_n, batch0, sA0, sA1, sW0, sW1, sC0, sC1, 0, 0ll)
-  if (epilogue == EPI_BIAS) CE_LAUNCH(EPI_BIAS); else CE_LAUNCH(EPI_F32);
-#undef CE_LAUNCH
-  return (int)hipGetLastError();
+  return ce_dispatch_epilogue<EPI_BIAS, EPI_F32>(epilogue, [&](auto e) {
+    hipLaunchKernelGGL(gemm_bf16_128<decltype(e)::value>, grid, block, 0, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, nullptr, nullptr, M, N,
+                       K, lda, ldw, ldc, 0, 0, 0, tiles_m, tiles_n, batch0, sA0, sA1, sW0, sW1, sC0, sC1, 0, 0ll);
+    return (int)hipGetLastError();
+  });
 }

@@ -28,6 +28,8 @@
 //    math and the global stores run on 16-B row-contiguous chunks (same rounding points as ce_gemm.hip).
 #include "ce_common.h"
 #include "ce_gemm_epi.h"
+#include "ce_gemm_launch.h"
+#include "ce_internal.h"
 
 namespace {
 
@@ -454,57 +456,28 @@ extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const fl
                                  const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
                                  int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
                                  hipStream_t stream) {
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int nwg = tiles_m * tiles_n, kt = K / BK;
+  const int kt = K / BK;
   // segmented operand: column k lives at base + (k / seg_k) * seg_stride + row * ld + k % seg_k (elements)
-  uint32_t a_seg_magic = 0, a_seg_extra = 0, w_seg_magic = 0, w_seg_extra = 0;
-  auto seg = [&](int seg_k, long long seg_stride, uint32_t& magic, uint32_t& extra_out) -> int {
-    if (seg_k <= 0 || seg_k >= K) return CE_OK;
-    magic = ce_seg_magic(seg_k, BK, kt);
-    const long long extra = (seg_stride - seg_k) * 2;  // bytes on top of the contiguous advance
-    if (!magic || extra < 0 || extra * (K / seg_k) >= (1ll << 32)) return CE_ERR_SHAPE;
-    extra_out = (uint32_t)extra;
-    return CE_OK;
-  };
-  if (int rc = seg(a_seg_k, a_seg_stride, a_seg_magic, a_seg_extra)) return rc;
-  if (int rc = seg(w_seg_k, w_seg_stride, w_seg_magic, w_seg_extra)) return rc;
+  CeSeg a_seg, w_seg;
+  if (int rc = ce_seg_encode(a_seg_k, a_seg_stride, K, BK, kt, CE_SEG_U32_EXTRA, a_seg)) return rc;
+  if (int rc = ce_seg_encode(w_seg_k, w_seg_stride, K, BK, kt, CE_SEG_U32_EXTRA, w_seg)) return rc;
   // split-K only for the tail of the last, partially filled round of workgroups
-  const int cus = ce_device_cus();
-  int tail = nwg % cus;
-  const int split = ce_split_k(tail, kt, cus, BM * BN * sizeof(float), ws ? (long long)ws_bytes : 0);
-  if (split == 1) tail = 0;
-  const int t_full2 = nwg - tail;
-  dim3 grid(t_full2 + tail * split), block(512);
-  static bool attr_done_[CE_MAX_DEVICES][8] = {};
-  bool* attr_done = attr_done_[ce_device_slot()];
-#define CE_LAUNCH(E)                                                                                                  \
-  do {                                                                                                                \
-    if (!attr_done[E]) {                                                                                              \
-      (void)hipFuncSetAttribute((const void*)gemm_bf16_256<E, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); \
-      (void)hipFuncSetAttribute((const void*)gemm_bf16_256<E, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);  \
-      (void)hipFuncSetAttribute((const void*)gemm256_reduce<E>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * QROW);     \
-      attr_done[E] = true;                                                                                            \
-    }                                                                                                                 \
-    if (staggered)                                                                                                    \
-      hipLaunchKernelGGL((gemm_bf16_256<E, true>), grid, block, LDS_BYTES, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, \
-                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n,    \
-                         t_full2, split, ws, a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra);                                             \
-    else                                                                                                              \
-      hipLaunchKernelGGL((gemm_bf16_256<E, false>), grid, block, LDS_BYTES, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, \
-                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n,    \
-                         t_full2, split, ws, a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra);                                             \
-    if (tail)                                                                                                         \
-      hipLaunchKernelGGL((gemm256_reduce<E>), dim3(4 * tail), block, 128 * QROW, stream, (bf16*)C, bias, gate,        \
-                         (const bf16*)res, M, N, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws);      \
-  } while (0)
-  switch (epilogue) {
-    case EPI_BIAS: CE_LAUNCH(EPI_BIAS); break;
-    case EPI_BIAS_GELU: CE_LAUNCH(EPI_BIAS_GELU); break;
-    case EPI_GATE_RES: CE_LAUNCH(EPI_GATE_RES); break;
-    case EPI_BIAS_GELU_ERF: CE_LAUNCH(EPI_BIAS_GELU_ERF); break;
-    case EPI_BIAS_ROW: CE_LAUNCH(EPI_BIAS_ROW); break;
-    default: return CE_ERR_ARG;
-  }
-#undef CE_LAUNCH
-  return (int)hipGetLastError();
+  const CeGemmPlan p = ce_gemm_plan(M, N, BM, BN, kt, ce_device_cus(), ws ? (long long)ws_bytes : 0, true);
+  const dim3 block(512);
+  return ce_dispatch_epilogue<EPI_BIAS, EPI_BIAS_GELU, EPI_GATE_RES, EPI_BIAS_GELU_ERF, EPI_BIAS_ROW>(epilogue, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    ce_once_per_device([] {
+      (void)ce_raise_dynamic_lds(LDS_BYTES, gemm_bf16_256<E, false>, gemm_bf16_256<E, true>);
+      (void)ce_raise_dynamic_lds(128 * QROW, gemm256_reduce<E>);
+      return true;
+    });
+    const auto kernel = staggered ? gemm_bf16_256<E, true> : gemm_bf16_256<E, false>;
+    hipLaunchKernelGGL(kernel, dim3(p.grid), block, LDS_BYTES, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, (const bf16*)res, M,
+                       N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, p.tiles_m, p.tiles_n, p.t_full, p.split, ws, a_seg.magic, a_seg.extra,
+                       w_seg.magic, w_seg.extra);
+    if (p.tail)
+      hipLaunchKernelGGL(gemm256_reduce<E>, dim3(p.reduce_grid), block, 128 * QROW, stream, (bf16*)C, bias, gate, (const bf16*)res, M, N, ldc,
+                         ldres, gate_rows, res_rows, p.tiles_m, p.tiles_n, p.t_full, p.split, ws);
+    return (int)hipGetLastError();
+  });
 }

@@ -23,6 +23,8 @@
 //    every wave's counted vmcnt for it.  Every piece has >= 2 units (NSA = 3: A pieces >= 3) between issue and first use.
 #include "ce_common.h"
 #include "ce_gemm_epi.h"
+#include "ce_gemm_launch.h"
+#include "ce_internal.h"
 
 namespace {
 
@@ -509,12 +511,7 @@ __global__ __launch_bounds__(256) void gemm256w4_reduce(bf16* __restrict__ C, co
 
 }  // namespace
 
-// nsa: 3 = A ring of three K-tile stages (160 KiB of LDS), 2 = two (128 KiB), 1 = three stages and ONE barrier per K-tile
-extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
-                                 hipStream_t stream);
-
+// nsa: ce_internal.h (ce_gemm256w4_launch); ng: column fragments per wave (8, or 4 / 3 for the narrow tiles of the two-level form)
 static int w4_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate, const void* res, int M, int N,
                      int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows, int a_seg_k, long long a_seg_stride, int w_seg_k,
                      long long w_seg_stride, int a_seg2_k, long long a_seg2_stride, int nsa, int ng, float* ws, size_t ws_bytes,
@@ -533,100 +530,57 @@ static int w4_launch(const void* A, const void* W, void* C, const float* bias, i
   if (ng == 8 && ((long long)M * ldc * 2 >= (1ll << 32) || (epilogue == EPI_BIAS_ROW && (M & 3))))
     return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, a_seg_k, a_seg_stride, w_seg_k,
                              w_seg_stride, ws, ws_bytes, stream);
-  const int bn = 32 * ng;
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + bn - 1) / bn;
-  const int nwg = tiles_m * tiles_n, kt = K / BK;
-  uint32_t a_seg_magic = 0, a_seg_extra = 0, w_seg_magic = 0, w_seg_extra = 0;
-  auto seg = [&](int seg_k, long long seg_stride, uint32_t& magic, uint32_t& extra_out) -> int {
-    if (seg_k <= 0 || seg_k >= K) return CE_OK;
-    magic = ce_seg_magic(seg_k, BK, kt);
-    const long long extra = (seg_stride - seg_k) * 2;
-    if (!magic || extra < 0 || extra * ((K + seg_k - 1) / seg_k) + (long long)K * 2 >= (1ll << 31)) return CE_ERR_SHAPE;  // the K-tile offset is a signed scalar
-    extra_out = (uint32_t)extra;
-    return CE_OK;
-  };
-  if (int rc = seg(a_seg_k, a_seg_stride, a_seg_magic, a_seg_extra)) return rc;
-  if (int rc = seg(w_seg_k, w_seg_stride, w_seg_magic, w_seg_extra)) return rc;
-  uint32_t a_seg2_magic = 0, a_seg2_extra = 0;
-  if (seg2 && a_seg2_k < K) {  // second level: every a_seg2_k columns the source jumps to a_seg2_stride (both in elements), nested in the first
-    a_seg2_magic = ce_seg_magic(a_seg2_k, BK, kt);
-    if (!a_seg2_magic) return CE_ERR_SHAPE;
-    const long long extra = (a_seg2_stride - (long long)(a_seg2_k / a_seg_k) * a_seg_stride) * 2;
-    const long long reach = ((long long)(K - 1) / a_seg2_k) * a_seg2_stride * 2 + (long long)(a_seg2_k / a_seg_k) * a_seg_stride * 2 + (long long)a_seg_k * 2;
-    if (extra < 0 || reach >= (1ll << 31)) return CE_ERR_SHAPE;
-    a_seg2_extra = (uint32_t)extra;
-  }
-  const int cus = ce_device_cus();
-  int tail = nwg % cus;
-  const int split = seg2 ? 1 : ce_split_k(tail, kt, cus, BM * BN * sizeof(float), ws ? (long long)ws_bytes : 0);
-  if (split == 1) tail = 0;
-  const int t_full2 = nwg - tail;
-  dim3 grid(t_full2 + tail * split), block(256);
+  const int kt = K / BK;
+  CeSeg a_seg, w_seg, a_seg2;
+  if (int rc = ce_seg_encode(a_seg_k, a_seg_stride, K, BK, kt, CE_SEG_I32_OFFSET, a_seg)) return rc;
+  if (int rc = ce_seg_encode(w_seg_k, w_seg_stride, K, BK, kt, CE_SEG_I32_OFFSET, w_seg)) return rc;
+  // second level: every a_seg2_k columns the source jumps to a_seg2_stride (both in elements), nested in the first
+  if (seg2)
+    if (int rc = ce_seg2_encode(a_seg_k, a_seg_stride, a_seg2_k, a_seg2_stride, K, BK, kt, a_seg2)) return rc;
+  // (the two-level form has no reduce kernel: its last round runs whole)
+  const CeGemmPlan p = ce_gemm_plan(M, N, BM, 32 * ng, kt, ce_device_cus(), ws ? (long long)ws_bytes : 0, !seg2);
+  const dim3 block(256);
   const int lds3 = 5 * TILE, lds2 = 4 * TILE;
+  // one argument list for every instantiation of the kernel
+  auto launch = [&](auto kernel, int lds) {
+    hipLaunchKernelGGL(kernel, dim3(p.grid), block, lds, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, (const bf16*)res, M, N, K, lda,
+                       ldw, ldc, ldres, gate_rows, res_rows, p.tiles_m, p.tiles_n, p.t_full, p.split, ws, a_seg.magic, a_seg.extra, w_seg.magic,
+                       w_seg.extra, a_seg2.magic, a_seg2.extra);
+  };
   if (seg2) {
     const int lds2n = 2 * TILE + 2 * (128 * BK * 2);  // 256 x 128 tile: W stages of 16 KiB
     const int lds2m = 2 * TILE + 2 * (96 * BK * 2);   // 256 x 96 tile: W stages of 12 KiB
-    static bool seg2_done_[CE_MAX_DEVICES] = {};
-    bool& seg2_done = seg2_done_[ce_device_slot()];
-    if (!seg2_done) {
-      if (hipFuncSetAttribute((const void*)gemm_bf16_w4<EPI_BIAS, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2) != hipSuccess ||
-          hipFuncSetAttribute((const void*)gemm_bf16_w4<EPI_GATE_RES, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2) != hipSuccess ||
-          hipFuncSetAttribute((const void*)gemm_bf16_w4<EPI_BIAS, 2, false, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2n) != hipSuccess ||
-          hipFuncSetAttribute((const void*)gemm_bf16_w4<EPI_GATE_RES, 2, false, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2n) != hipSuccess ||
-          hipFuncSetAttribute((const void*)gemm_bf16_w4<EPI_BIAS, 2, false, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2m) != hipSuccess ||
-          hipFuncSetAttribute((const void*)gemm_bf16_w4<EPI_GATE_RES, 2, false, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2m) != hipSuccess)
-        return CE_ERR_ARG;
-      seg2_done = true;
-    }
-#define CE_LAUNCH_SEG2(E, NGV, LDS)                                                                                                     \
-  hipLaunchKernelGGL((gemm_bf16_w4<E, 2, false, true, NGV>), grid, block, LDS, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                     (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws, a_seg_magic,   \
-                     a_seg_extra, w_seg_magic, w_seg_extra, a_seg2_magic, a_seg2_extra)
-    if (epilogue == EPI_BIAS) {
-      if (ng == 8) CE_LAUNCH_SEG2(EPI_BIAS, 8, lds2); else if (ng == 4) CE_LAUNCH_SEG2(EPI_BIAS, 4, lds2n); else CE_LAUNCH_SEG2(EPI_BIAS, 3, lds2m);
-    } else {
-      if (ng == 8) CE_LAUNCH_SEG2(EPI_GATE_RES, 8, lds2); else if (ng == 4) CE_LAUNCH_SEG2(EPI_GATE_RES, 4, lds2n); else CE_LAUNCH_SEG2(EPI_GATE_RES, 3, lds2m);
-    }
-#undef CE_LAUNCH_SEG2
+    if (!ce_once_per_device([&] {
+          return ce_raise_dynamic_lds(lds2, gemm_bf16_w4<EPI_BIAS, 2, false, true>, gemm_bf16_w4<EPI_GATE_RES, 2, false, true>) &&
+                 ce_raise_dynamic_lds(lds2n, gemm_bf16_w4<EPI_BIAS, 2, false, true, 4>, gemm_bf16_w4<EPI_GATE_RES, 2, false, true, 4>) &&
+                 ce_raise_dynamic_lds(lds2m, gemm_bf16_w4<EPI_BIAS, 2, false, true, 3>, gemm_bf16_w4<EPI_GATE_RES, 2, false, true, 3>);
+        }))
+      return CE_ERR_ARG;
+    return ce_dispatch_epilogue<EPI_BIAS, EPI_GATE_RES>(epilogue, [&](auto e) {
+      constexpr int E = decltype(e)::value;
+      if (ng == 8) launch(gemm_bf16_w4<E, 2, false, true, 8>, lds2);
+      else if (ng == 4) launch(gemm_bf16_w4<E, 2, false, true, 4>, lds2n);
+      else launch(gemm_bf16_w4<E, 2, false, true, 3>, lds2m);
+      return (int)hipGetLastError();
+    });
+  }
+  return ce_dispatch_epilogue<EPI_BIAS, EPI_BIAS_GELU, EPI_GATE_RES, EPI_BIAS_GELU_ERF, EPI_BIAS_ROW>(epilogue, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (!ce_once_per_device([&] {
+          if (!ce_raise_dynamic_lds(lds3, gemm_bf16_w4<E, 3, false>, gemm_bf16_w4<E, 3, true>) || !ce_raise_dynamic_lds(lds2, gemm_bf16_w4<E, 2, false>))
+            return false;
+          (void)ce_raise_dynamic_lds(128 * QROW, gemm256w4_reduce<E>);
+          return true;
+        }))
+      return CE_ERR_ARG;
+    if (nsa == 1) launch(gemm_bf16_w4<E, 3, true>, lds3);
+    else if (nsa == 3) launch(gemm_bf16_w4<E, 3, false>, lds3);
+    else launch(gemm_bf16_w4<E, 2, false>, lds2);
+    if (p.tail)
+      hipLaunchKernelGGL(gemm256w4_reduce<E>, dim3(p.reduce_grid), block, 128 * QROW, stream, (bf16*)C, bias, gate, (const bf16*)res, M, N, ldc, ldres,
+                         gate_rows, res_rows, p.tiles_m, p.tiles_n, p.t_full, p.split, ws);
     return (int)hipGetLastError();
-  }
-  static bool attr_done_[CE_MAX_DEVICES][8] = {};
-  bool* attr_done = attr_done_[ce_device_slot()];
-#define CE_LAUNCH(E)                                                                                                       \
-  do {                                                                                                                     \
-    if (!attr_done[E]) {                                                                                                   \
-      if (hipFuncSetAttribute((const void*)gemm_bf16_w4<E, 3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds3) != hipSuccess) return CE_ERR_ARG; \
-      if (hipFuncSetAttribute((const void*)gemm_bf16_w4<E, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds3) != hipSuccess) return CE_ERR_ARG; \
-      if (hipFuncSetAttribute((const void*)gemm_bf16_w4<E, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2) != hipSuccess) return CE_ERR_ARG; \
-      (void)hipFuncSetAttribute((const void*)gemm256w4_reduce<E>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * QROW); \
-      attr_done[E] = true;                                                                                                 \
-    }                                                                                                                      \
-    if (nsa == 1)                                                                                                          \
-      hipLaunchKernelGGL((gemm_bf16_w4<E, 3, true>), grid, block, lds3, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws, \
-                         a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra, 0u, 0u);                                      \
-    else if (nsa == 3)                                                                                                     \
-      hipLaunchKernelGGL((gemm_bf16_w4<E, 3, false>), grid, block, lds3, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws, \
-                         a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra, 0u, 0u);                                      \
-    else                                                                                                                   \
-      hipLaunchKernelGGL((gemm_bf16_w4<E, 2, false>), grid, block, lds2, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                         (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws, \
-                         a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra, 0u, 0u);                                      \
-    if (tail)                                                                                                              \
-      hipLaunchKernelGGL((gemm256w4_reduce<E>), dim3(4 * tail), block, 128 * QROW, stream, (bf16*)C, bias, gate,           \
-                         (const bf16*)res, M, N, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws);           \
-  } while (0)
-  switch (epilogue) {
-    case EPI_BIAS: CE_LAUNCH(EPI_BIAS); break;
-    case EPI_BIAS_GELU: CE_LAUNCH(EPI_BIAS_GELU); break;
-    case EPI_GATE_RES: CE_LAUNCH(EPI_GATE_RES); break;
-    case EPI_BIAS_GELU_ERF: CE_LAUNCH(EPI_BIAS_GELU_ERF); break;
-    case EPI_BIAS_ROW: CE_LAUNCH(EPI_BIAS_ROW); break;
-    default: return CE_ERR_ARG;
-  }
-#undef CE_LAUNCH
-  return (int)hipGetLastError();
+  });
 }
 
 extern "C" int ce_gemm256w4_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
@@ -652,23 +606,14 @@ extern "C" int ce_gemm256w4_seg2_launch(const void* A, const void* W, void* C, c
 extern "C" int ce_gemm256w4_reduce_launch(int epilogue, void* C, const float* bias, const float* gate, const void* res, int M, int N, int ldc,
                                           int ldres, int gate_rows, int res_rows, int tiles_m, int tiles_n, int t_full, int split, const float* ws, int tail,
                                           hipStream_t stream) {
-  static bool done_[CE_MAX_DEVICES][8] = {};
-  bool* done = done_[ce_device_slot()];
-#define CE_RED(E)                                                                                                            \
-  do {                                                                                                                       \
-    if (!done[E]) {                                                                                                          \
-      (void)hipFuncSetAttribute((const void*)gemm256w4_reduce<E>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * QROW);    \
-      done[E] = true;                                                                                                        \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((gemm256w4_reduce<E>), dim3(4 * tail), dim3(256), 128 * QROW, stream, (bf16*)C, bias, gate, (const bf16*)res, M, N, \
-                       ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full, split, ws);                                          \
-  } while (0)
-  switch (epilogue) {
-    case EPI_BIAS: CE_RED(EPI_BIAS); break;
-    case EPI_BIAS_GELU: CE_RED(EPI_BIAS_GELU); break;
-    case EPI_GATE_RES: CE_RED(EPI_GATE_RES); break;
-    default: return CE_ERR_ARG;
-  }
-#undef CE_RED
-  return (int)hipGetLastError();
+  return ce_dispatch_epilogue<EPI_BIAS, EPI_BIAS_GELU, EPI_GATE_RES>(epilogue, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    ce_once_per_device([] {
+      (void)ce_raise_dynamic_lds(128 * QROW, gemm256w4_reduce<E>);
+      return true;
+    });
+    hipLaunchKernelGGL(gemm256w4_reduce<E>, dim3(4 * tail), dim3(256), 128 * QROW, stream, (bf16*)C, bias, gate, (const bf16*)res, M, N, ldc, ldres,
+                       gate_rows, res_rows, tiles_m, tiles_n, t_full, split, ws);
+    return (int)hipGetLastError();
+  });
 }

@@ -19,6 +19,8 @@
 //    (its last piece was issued seven groups = ~900 MFMA cycles earlier) (=> its fragments may be read from here on).
 #include "ce_common.h"
 #include "ce_gemm_epi.h"
+#include "ce_gemm_launch.h"
+#include "ce_internal.h"
 
 namespace {
 
@@ -460,11 +462,6 @@ __global__ __launch_bounds__(256) void gemm384_reduce(bf16* __restrict__ C, cons
 
 }  // namespace
 
-extern "C" int ce_gemm256_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,
-                                 const void* res, int M, int N, int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows,
-                                 int a_seg_k, long long a_seg_stride, int w_seg_k, long long w_seg_stride, float* ws, size_t ws_bytes,
-                                 hipStream_t stream);
-
 template <int NF>
 static int gemm384_launch_impl(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate, const void* res, int M, int N,
                                int K, int lda, int ldw, int ldc, int ldres, int gate_rows, int res_rows, int a_seg_k, long long a_seg_stride, int w_seg_k,
@@ -477,65 +474,31 @@ static int gemm384_launch_impl(const void* A, const void* W, void* C, const floa
       (epilogue == EPI_BIAS_ROW && (M & 3)))  // (the register-direct epilogue stores through 32-bit buffer offsets and reads four row biases at once)
     return ce_gemm256_launch(A, W, C, bias, epilogue, gate, res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, a_seg_k, a_seg_stride, w_seg_k,
                              w_seg_stride, ws, ws_bytes, stream);
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int nwg = tiles_m * tiles_n, kt = K / BK;
-  uint32_t a_seg_magic = 0, a_seg_extra = 0, w_seg_magic = 0, w_seg_extra = 0;
-  auto seg = [&](int seg_k, long long seg_stride, uint32_t& magic, uint32_t& extra_out) -> int {
-    if (seg_k <= 0 || seg_k >= K) return CE_OK;
-    magic = ce_seg_magic(seg_k, BK, kt);
-    const long long extra = (seg_stride - seg_k) * 2;
-    if (!magic || extra < 0 || extra * (K / seg_k) + (long long)K * 2 >= (1ll << 31)) return CE_ERR_SHAPE;
-    extra_out = (uint32_t)extra;
-    return CE_OK;
-  };
-  if (int rc = seg(a_seg_k, a_seg_stride, a_seg_magic, a_seg_extra)) return rc;
-  if (int rc = seg(w_seg_k, w_seg_stride, w_seg_magic, w_seg_extra)) return rc;
-  const int cus = ce_device_cus();
-  int tail = nwg % cus;
+  const int kt = K / BK;
+  CeSeg a_seg, w_seg;
+  if (int rc = ce_seg_encode(a_seg_k, a_seg_stride, K, BK, kt, CE_SEG_I32_OFFSET, a_seg)) return rc;
+  if (int rc = ce_seg_encode(w_seg_k, w_seg_stride, K, BK, kt, CE_SEG_I32_OFFSET, w_seg)) return rc;
   // (the transposed store has no reduce form: its last round runs whole)
-  const int split = epilogue == EPI_BIAS_T ? 1 : ce_split_k(tail, kt, cus, BM * BN * sizeof(float), ws ? (long long)ws_bytes : 0);
-  if (split == 1) tail = 0;
-  const int t_full2 = nwg - tail;
-  dim3 grid(t_full2 + tail * split), block(256);
+  const CeGemmPlan p = ce_gemm_plan(M, N, BM, BN, kt, ce_device_cus(), ws ? (long long)ws_bytes : 0, epilogue != EPI_BIAS_T);
+  const dim3 block(256);
   const int lds = 2 * STAGE;
-  static bool attr_done_[CE_MAX_DEVICES][8] = {};
-  bool* attr_done = attr_done_[ce_device_slot()];
-#define CE_LAUNCH(E)                                                                                                       \
-  do {                                                                                                                     \
-    if (!attr_done[E]) {                                                                                                   \
-      if (hipFuncSetAttribute((const void*)gemm_bf16_384<E, NF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return CE_ERR_ARG; \
-      (void)hipFuncSetAttribute((const void*)gemm384_reduce<E, NF>, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * NF * QROW); \
-      attr_done[E] = true;                                                                                                 \
-    }                                                                                                                      \
-    hipLaunchKernelGGL((gemm_bf16_384<E, NF>), grid, block, lds, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, \
-                       (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws, \
-                       a_seg_magic, a_seg_extra, w_seg_magic, w_seg_extra);                                                \
-    if (tail)                                                                                                              \
-      hipLaunchKernelGGL((gemm384_reduce<E, NF>), dim3(4 * tail), block, 16 * NF * QROW, stream, (bf16*)C, bias, gate,     \
-                         (const bf16*)res, M, N, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws);           \
-  } while (0)
-  switch (epilogue) {
-    case EPI_BIAS: CE_LAUNCH(EPI_BIAS); break;
-    case EPI_BIAS_GELU: CE_LAUNCH(EPI_BIAS_GELU); break;
-    case EPI_GATE_RES: CE_LAUNCH(EPI_GATE_RES); break;
-    case EPI_BIAS_GELU_ERF: CE_LAUNCH(EPI_BIAS_GELU_ERF); break;
-    case EPI_BIAS_ROW: CE_LAUNCH(EPI_BIAS_ROW); break;
-    case EPI_BIAS_T: {
-      static bool t_done_[CE_MAX_DEVICES] = {};
-      bool& t_done = t_done_[ce_device_slot()];
-      if (!t_done) {
-        if (hipFuncSetAttribute((const void*)gemm_bf16_384<EPI_BIAS_T, NF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return CE_ERR_ARG;
-        t_done = true;
-      }
-      hipLaunchKernelGGL((gemm_bf16_384<EPI_BIAS_T, NF>), grid, block, lds, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, (const bf16*)res,
-                         M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, tiles_m, tiles_n, t_full2, split, ws, a_seg_magic, a_seg_extra, w_seg_magic,
-                         w_seg_extra);
-      break;
-    }
-    default: return CE_ERR_ARG;
-  }
-#undef CE_LAUNCH
-  return (int)hipGetLastError();
+  return ce_dispatch_epilogue<EPI_BIAS, EPI_BIAS_GELU, EPI_GATE_RES, EPI_BIAS_GELU_ERF, EPI_BIAS_ROW, EPI_BIAS_T>(epilogue, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (!ce_once_per_device([&] {
+          if (!ce_raise_dynamic_lds(lds, gemm_bf16_384<E, NF>)) return false;
+          if constexpr (E != EPI_BIAS_T) (void)ce_raise_dynamic_lds(16 * NF * QROW, gemm384_reduce<E, NF>);
+          return true;
+        }))
+      return CE_ERR_ARG;
+    hipLaunchKernelGGL((gemm_bf16_384<E, NF>), dim3(p.grid), block, lds, stream, (const bf16*)A, (const bf16*)W, (bf16*)C, bias, gate, (const bf16*)res,
+                       M, N, K, lda, ldw, ldc, ldres, gate_rows, res_rows, p.tiles_m, p.tiles_n, p.t_full, p.split, ws, a_seg.magic, a_seg.extra,
+                       w_seg.magic, w_seg.extra);
+    if constexpr (E != EPI_BIAS_T)
+      if (p.tail)
+        hipLaunchKernelGGL((gemm384_reduce<E, NF>), dim3(p.reduce_grid), block, 16 * NF * QROW, stream, (bf16*)C, bias, gate, (const bf16*)res, M, N,
+                           ldc, ldres, gate_rows, res_rows, p.tiles_m, p.tiles_n, p.t_full, p.split, ws);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int ce_gemm384_launch(const void* A, const void* W, void* C, const float* bias, int epilogue, const float* gate,

@@ -11,6 +11,8 @@
 // two 16-B chunks 2g and 2g + 1 of the LDS row.  Any packing that is the same for A and W is correct (sum over k).
 #include "ce_common.h"
 #include "ce_gemm_epi.h"
+#include "ce_gemm_launch.h"
+#include "ce_internal.h"
 
 namespace {
 
@@ -380,10 +382,6 @@ CE_API int ce_quant_rows_fp8(const void* x, void* q, float* scale, int M, int K,
   return (int)hipGetLastError();
 }
 
-extern "C" int ce_gemm_fp8w4_launch(const void* Aq, const void* Wq, void* C, const float* sa, const float* sw, const float* bias,
-                                    int epilogue, const float* gate, const void* res, int M, int N, int K, int lda, int ldw, int ldc,
-                                    int ldres, int gate_rows, float* ws, size_t ws_bytes, hipStream_t stream);
-
 // main loop of ce_gemm_fp8: 1 = one wave per SIMD (ce_gemm_fp8w4.hip; the default: +2 ... +8 % on the step's shapes,
 // profiles/r03_gemm_fp8_variants_ab.txt), 0 = the 8-wave / 4-phase loop of this file
 CE_KNOB g_fp8_variant = 1;
@@ -410,23 +408,14 @@ CE_API int ce_gemm_fp8(const void* Aq, const void* Wq, void* C, const float* sa,
                                 stream);
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   dim3 grid(tiles_m * tiles_n), block(512);
-  static bool attr_done_[CE_MAX_DEVICES][3] = {};
-  bool* attr_done = attr_done_[ce_device_slot()];
-#define F8_LAUNCH(E)                                                                                                        \
-  do {                                                                                                                      \
-    if (!attr_done[E]) {                                                                                                    \
-      (void)hipFuncSetAttribute((const void*)gemm_fp8_256<E>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);       \
-      attr_done[E] = true;                                                                                                  \
-    }                                                                                                                       \
-    hipLaunchKernelGGL((gemm_fp8_256<E>), grid, block, LDS_BYTES, stream, (const unsigned char*)Aq, (const unsigned char*)Wq, \
-                       (bf16*)C, sa, sw, bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n); \
-  } while (0)
-  switch (epilogue) {
-    case EPI_BIAS: F8_LAUNCH(EPI_BIAS); break;
-    case EPI_BIAS_GELU: F8_LAUNCH(EPI_BIAS_GELU); break;
-    case EPI_GATE_RES: F8_LAUNCH(EPI_GATE_RES); break;
-    default: return CE_ERR_ARG;
-  }
-#undef F8_LAUNCH
-  return (int)hipGetLastError();
+  return ce_dispatch_epilogue<EPI_BIAS, EPI_BIAS_GELU, EPI_GATE_RES>(epilogue, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    ce_once_per_device([] {
+      (void)ce_raise_dynamic_lds(LDS_BYTES, gemm_fp8_256<E>);
+      return true;
+    });
+    hipLaunchKernelGGL(gemm_fp8_256<E>, grid, block, LDS_BYTES, stream, (const unsigned char*)Aq, (const unsigned char*)Wq, (bf16*)C, sa, sw, bias,
+                       gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n);
+    return (int)hipGetLastError();
+  });
 }

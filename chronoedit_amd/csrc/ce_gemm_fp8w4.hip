@@ -32,6 +32,8 @@
 // per fragment covering four K-tiles - needed 32 registers and spilled.)
 #include "ce_common.h"
 #include "ce_gemm_epi.h"
+#include "ce_gemm_launch.h"
+#include "ce_internal.h"
 
 // F8_A3 = 1: an A ring of THREE K-tile stages beside the W ring of two (160 KiB of LDS, as ce_gemm256w4.hip).  The A pieces of tile T+2 then go out in
 // groups 1..4 of tile T (nine groups of flight) and the W pieces of tile T+2 in groups 5, 6, 7 of T and group 0 of T+1 (five): TWO pieces per group
@@ -858,25 +860,20 @@ __global__ __launch_bounds__(256) void gemm_fp8w4_reduce_gelu_q(unsigned char* _
 
 }  // namespace
 
-extern "C" int ce_gemm256w4_reduce_launch(int epilogue, void* C, const float* bias, const float* gate, const void* res, int M, int N, int ldc,
-                                          int ldres, int gate_rows, int res_rows, int tiles_m, int tiles_n, int t_full, int split, const float* ws, int tail,
-                                          hipStream_t stream);
-
-// The split-K plan of ce_split_k, kept only where it pays.  An fp8 round is short (1.7 us per K-tile): cutting the last round only pays when
-// the time it saves clearly exceeds what the slabs cost (256 KiB written and read back per piece at ~4 TB/s, plus the reduce launch).
+// The last-round plan of ce_gemm_plan, cut along K only where it pays.  An fp8 round is short (1.7 us per K-tile): cutting the last round only
+// pays when the time it saves clearly exceeds what the slabs cost (256 KiB written and read back per piece at ~4 TB/s, plus the reduce launch).
 // Measured: 116 tail tiles of a K = 5120 product cut in two were 1.5 % SLOWER than run whole; 6 tiles cut in eight, or K = 13824, gain 3 %.
-static int fp8_split_k(int tail, int kt, const void* ws, size_t ws_bytes) {
-  const int split = ce_split_k(tail, kt, ce_device_cus(), BM * BN * sizeof(float), ws ? (long long)ws_bytes : 0);
-  if (split == 1) return 1;
-  const double saving_us = (1.0 - 1.0 / split) * kt * 1.7, slabs_us = (double)tail * split * 0.128 + 8.0;
-  return saving_us < 1.5 * slabs_us ? 1 : split;
+static CeGemmPlan fp8_plan(int M, int N, int kt, const void* ws, size_t ws_bytes) {
+  const int cus = ce_device_cus();
+  const CeGemmPlan p = ce_gemm_plan(M, N, BM, BN, kt, cus, ws ? (long long)ws_bytes : 0, true);
+  if (p.split == 1) return p;
+  const double saving_us = (1.0 - 1.0 / p.split) * kt * 1.7, slabs_us = (double)p.tail * p.split * 0.128 + 8.0;
+  return saving_us < 1.5 * slabs_us ? ce_gemm_plan(M, N, BM, BN, kt, cus, 0, false) : p;
 }
 
 static int fp8w4_launch(bool mx, const void* Aq, const void* Wq, void* C, const float* sa, const float* sw, const float* bias,
                         int epilogue, const float* gate, const void* res, int M, int N, int K, int lda, int ldw, int ldc,
                         int ldres, int gate_rows, float* ws, size_t ws_bytes, hipStream_t stream) {
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int nwg = tiles_m * tiles_n, kt = K / BKB;
   // (the prefetched gated-residual epilogue holds ONE or TWO samples' gate rows per tile and stores through 32-bit offsets)
 #if F8_EPI_LDS
   const bool gate_prefetch = epilogue != EPI_GATE_RES || ((gate == nullptr || gate_rows <= 0 || gate_rows >= BM) && (long long)M * ldc * 2 < (1ll << 32));
@@ -884,43 +881,21 @@ static int fp8w4_launch(bool mx, const void* Aq, const void* Wq, void* C, const 
   // (register-direct epilogue: every form stores through a buffer descriptor's 32-bit offsets when C fits them)
   const bool gate_prefetch = (long long)M * ldc * 2 < (1ll << 32) && (epilogue != EPI_GATE_RES || gate == nullptr || gate_rows <= 0 || gate_rows >= BM);
 #endif
-  int tail = nwg % ce_device_cus();
-  const int split = fp8_split_k(tail, kt, ws, ws_bytes);
-  if (split == 1) tail = 0;
-  const int t_full = nwg - tail;
-  dim3 grid(t_full + tail * split), block(256);
+  const CeGemmPlan p = fp8_plan(M, N, K / BKB, ws, ws_bytes);
   const int lds = LDS_BYTES;
-  static bool attr_done_[CE_MAX_DEVICES][3] = {};
-  bool* attr_done = attr_done_[ce_device_slot()];
-#define F8_LAUNCH(E)                                                                                                          \
-  do {                                                                                                                        \
-    if (!attr_done[E]) {                                                                                                      \
-      if (hipFuncSetAttribute((const void*)gemm_fp8_w4<E>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return CE_ERR_ARG; \
-      if (hipFuncSetAttribute((const void*)gemm_fp8_w4<E, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return CE_ERR_ARG; \
-      if (hipFuncSetAttribute((const void*)gemm_fp8_w4<E, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return CE_ERR_ARG; \
-      attr_done[E] = true;                                                                                                    \
-    }                                                                                                                         \
-    if (mx && !gate_prefetch)                                                                                                 \
-      hipLaunchKernelGGL((gemm_fp8_w4<E, true, false>), grid, block, lds, stream, (const unsigned char*)Aq, (const unsigned char*)Wq, (bf16*)C, sa, sw, \
-                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, ws, nullptr); \
-    else if (mx)                                                                                                              \
-      hipLaunchKernelGGL((gemm_fp8_w4<E, true>), grid, block, lds, stream, (const unsigned char*)Aq, (const unsigned char*)Wq, (bf16*)C, sa, sw, \
-                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, ws, nullptr); \
-    else                                                                                                                      \
-      hipLaunchKernelGGL((gemm_fp8_w4<E>), grid, block, lds, stream, (const unsigned char*)Aq, (const unsigned char*)Wq, (bf16*)C, sa, sw, \
-                         bias, gate, (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, tiles_m, tiles_n, t_full, split, ws, nullptr); \
-  } while (0)
-  switch (epilogue) {
-    case EPI_BIAS: F8_LAUNCH(EPI_BIAS); break;
-    case EPI_BIAS_GELU: F8_LAUNCH(EPI_BIAS_GELU); break;
-    case EPI_GATE_RES: F8_LAUNCH(EPI_GATE_RES); break;
-    default: return CE_ERR_ARG;
-  }
-#undef F8_LAUNCH
-  if (tail) {
-    const int rc = ce_gemm256w4_reduce_launch(epilogue, C, bias, gate, res, M, N, ldc, ldres, gate_rows, 0, tiles_m, tiles_n, t_full, split, ws,
-                                              tail, stream);
-    if (rc != CE_OK) return rc;
+  const int rc = ce_dispatch_epilogue<EPI_BIAS, EPI_BIAS_GELU, EPI_GATE_RES>(epilogue, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (!ce_once_per_device([&] { return ce_raise_dynamic_lds(lds, gemm_fp8_w4<E>, gemm_fp8_w4<E, true>, gemm_fp8_w4<E, true, false>); })) return CE_ERR_ARG;
+    const auto kernel = !mx ? gemm_fp8_w4<E> : gate_prefetch ? gemm_fp8_w4<E, true> : gemm_fp8_w4<E, true, false>;
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), lds, stream, (const unsigned char*)Aq, (const unsigned char*)Wq, (bf16*)C, sa, sw, bias, gate,
+                       (const bf16*)res, M, N, K, lda, ldw, ldc, ldres, gate_rows, p.tiles_m, p.tiles_n, p.t_full, p.split, ws, nullptr);
+    return CE_OK;
+  });
+  if (rc != CE_OK) return rc;
+  if (p.tail) {
+    const int rc2 = ce_gemm256w4_reduce_launch(epilogue, C, bias, gate, res, M, N, ldc, ldres, gate_rows, 0, p.tiles_m, p.tiles_n, p.t_full, p.split, ws,
+                                               p.tail, stream);
+    if (rc2 != CE_OK) return rc2;
   }
   return (int)hipGetLastError();
 }
@@ -955,30 +930,17 @@ CE_API int ce_gemm_mxfp8_gelu_quant(const void* Aq, const void* Wq, const void* 
   if (M <= 0 || N <= 0 || K <= 0 || (K % (2 * BKB)) || (N & 127)) return CE_ERR_SHAPE;
   if ((lda & 15) || (ldw & 15) || (ldq & 7)) return CE_ERR_ALIGN;
   if ((long long)M * lda >= (1ll << 32) || (long long)N * ldw >= (1ll << 32)) return CE_ERR_SHAPE;
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int nwg = tiles_m * tiles_n, kt = K / BKB;
-  int tail = nwg % ce_device_cus();
-  const int split = fp8_split_k(tail, kt, ws, ws_bytes);
-  if (split == 1) tail = 0;
-  const int t_full = nwg - tail;
-  static bool done_[CE_MAX_DEVICES] = {};
-  bool& done = done_[ce_device_slot()];
-  if (!done) {
-    if (hipFuncSetAttribute((const void*)gemm_fp8_w4<EPI_BIAS_GELU_Q, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return CE_ERR_ARG;
-    if (hipFuncSetAttribute((const void*)gemm_fp8_w4<EPI_BIAS_GELU_Q, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return CE_ERR_ARG;
-    done = true;
-  }
-  if ((long long)M * ldq < (1ll << 32))
-    hipLaunchKernelGGL((gemm_fp8_w4<EPI_BIAS_GELU_Q, true>), dim3(t_full + tail * split), dim3(256), LDS_BYTES, stream, (const unsigned char*)Aq,
-                       (const unsigned char*)Wq, (bf16*)q_out, reinterpret_cast<const float*>(sa8), reinterpret_cast<const float*>(sw8), bias, nullptr,
-                       nullptr, M, N, K, lda, ldw, ldq, 0, 0, tiles_m, tiles_n, t_full, split, static_cast<float*>(ws), (unsigned char*)qs_out);
-  else  // (a q_out beyond 32-bit byte offsets: 64-bit store addresses)
-    hipLaunchKernelGGL((gemm_fp8_w4<EPI_BIAS_GELU_Q, true, false>), dim3(t_full + tail * split), dim3(256), LDS_BYTES, stream, (const unsigned char*)Aq,
-                       (const unsigned char*)Wq, (bf16*)q_out, reinterpret_cast<const float*>(sa8), reinterpret_cast<const float*>(sw8), bias, nullptr,
-                       nullptr, M, N, K, lda, ldw, ldq, 0, 0, tiles_m, tiles_n, t_full, split, static_cast<float*>(ws), (unsigned char*)qs_out);
-  if (tail)
-    hipLaunchKernelGGL(gemm_fp8w4_reduce_gelu_q, dim3(4 * tail), dim3(256), 0, stream, (unsigned char*)q_out, (unsigned char*)qs_out, bias, M, N, ldq,
-                       tiles_m, tiles_n, t_full, split, static_cast<const float*>(ws));
+  const CeGemmPlan p = fp8_plan(M, N, K / BKB, ws, ws_bytes);
+  if (!ce_once_per_device([] { return ce_raise_dynamic_lds(LDS_BYTES, gemm_fp8_w4<EPI_BIAS_GELU_Q, true>, gemm_fp8_w4<EPI_BIAS_GELU_Q, true, false>); }))
+    return CE_ERR_ARG;
+  // (a q_out beyond 32-bit byte offsets: 64-bit store addresses)
+  const auto kernel = (long long)M * ldq < (1ll << 32) ? gemm_fp8_w4<EPI_BIAS_GELU_Q, true> : gemm_fp8_w4<EPI_BIAS_GELU_Q, true, false>;
+  hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), LDS_BYTES, stream, (const unsigned char*)Aq, (const unsigned char*)Wq, (bf16*)q_out,
+                     reinterpret_cast<const float*>(sa8), reinterpret_cast<const float*>(sw8), bias, nullptr, nullptr, M, N, K, lda, ldw, ldq, 0, 0,
+                     p.tiles_m, p.tiles_n, p.t_full, p.split, static_cast<float*>(ws), (unsigned char*)qs_out);
+  if (p.tail)
+    hipLaunchKernelGGL(gemm_fp8w4_reduce_gelu_q, dim3(p.reduce_grid), dim3(256), 0, stream, (unsigned char*)q_out, (unsigned char*)qs_out, bias, M, N,
+                       ldq, p.tiles_m, p.tiles_n, p.t_full, p.split, static_cast<const float*>(ws));
   return (int)hipGetLastError();
 }
 

@@ -1694,7 +1694,7 @@ def rms_mx_case(D: int, head_dim: int, R, post_scale: float, mistake=None) -> Ca
     return c
 
 
-# ---- the split-K plan of the fp8 GEMMs, restated (ce_common.h ce_split_k, ce_gemm_fp8w4.hip fp8_split_k) ---------------------------------
+# ---- the split-K plan of the fp8 GEMMs, restated (ce_gemm_plan.h ce_split_k, ce_gemm_fp8w4.hip fp8_plan) ------------------------------------
 FP8_BM = FP8_BN = 256
 FP8_BK = 128
 FP8_GROUP = 4

@@ -230,6 +230,19 @@ def test_macro_tile_choice_of_the_step_shapes():
     assert lib.ce_gemm_bf16_tile_rows(7200, 5120, 13824, 256, 64 << 20) != 384  # the 64 MiB scratch of rounds 1-5: 384 cannot cut its tail (-13 %)
 
 
+def test_gemm_plan_header_against_brute_force():
+    """csrc/ce_gemm_plan.h - the last-round (split-K) plan and the K-segmented operand encoding every large-tile GEMM launcher shares -
+    checked by tools/gemm_plan_host_check.cpp: a stand-alone host program built with AddressSanitizer and UBSan (no HIP, nothing loaded
+    into this process) that replays the kernels' K-tile offsets in their registers' widths against the operand's definition and sweeps
+    the plans' invariants over all five tile geometries."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "gemm_plan_host_check.py")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip().splitlines()[-1].endswith(": OK")
+
+
 def test_mx_scale_layout_helpers_agree_with_the_kernels_offset_formula():
     """The tiled E8M0 scale layout of the MX fp8 GEMM operands ([rows / 128][K / 128][4 blocks][16 rows][8 row groups], ce_common.h
     `mx_gemm_scale_offset`): `ops.mx_scale_bytes` sizes it and `ops.mx_scales_to_rows` undoes it - replayed here against the device
