@@ -16,8 +16,11 @@ sample and its `focus.FocusPlan` with box (l, t, r, b):
 The crops of one editor value chain into one canvas in the plain paste's order.  A box of exactly the edit's size has nothing to lift: its
 frames are pasted as they are ("reason": "same").  `reference` (PIL and `lift.reference` on the CPU) is the definition and the host path;
 on the device the three grid passes of the lift run per crop, and csrc/ce_boxlift.hip fuses the apply with the paste, in place on the
-canvas - the same bytes.  The fit window knows nothing of the mask: along a feathered rim the residual rises and the gate hands the rim
-to the upsample, so the lift never does worse there than the plain paste."""
+canvas - the same bytes.  By default the fit window knows nothing of the mask: along a feathered rim the residual rises and the gate hands
+the rim to the upsample, so the lift never does worse there than the plain paste.  With `mask_aware=True` (`enable_detail_lift(focus=True,
+mask_aware=True)`) a crop that is pasted through a mask is fitted under the edit-size weight plane M = mask.crop(box).resize((width,
+height), BILINEAR) (`plan.lift_M`, the mask the region edit blended with): chronoedit_amd/rimlift.py replaces the fit and the smoothing,
+the gate, the apply and the paste stay - the rim then carries the untapered edit and the paste's mask tapers it once."""
 from __future__ import annotations
 
 from typing import List, Optional, Tuple
@@ -26,16 +29,21 @@ import numpy as np
 import torch
 
 from . import lift as _lf
+from . import rimlift as _rl
 
 ENTRY_POINTS = ("ce_boxlift_apply_paste_u8",)
 
 Box = Tuple[int, int, int, int]
 
 
-def report_entry(plan, edit_size, reason: str) -> dict:
-    """One crop's `lift_report` entry under focus=True: lift.report_entry's keys with the BOX's size, plus "box" and "scale"."""
+def report_entry(plan, edit_size, reason: str, mask_aware: Optional[bool] = None) -> dict:
+    """One crop's `lift_report` entry under focus=True: lift.report_entry's keys with the BOX's size, plus "box" and "scale" - and, while the
+    mask-aware switch is on (mask_aware not None), "mask_aware": whether this crop was fitted under its weight plane."""
     l, t, r, b = plan.box
-    return dict(_lf.report_entry((r - l, b - t), edit_size, reason), box=plan.box, scale=plan.report["scale"])
+    entry = dict(_lf.report_entry((r - l, b - t), edit_size, reason), box=plan.box, scale=plan.report["scale"])
+    if mask_aware is not None:
+        entry["mask_aware"] = bool(mask_aware)
+    return entry
 
 
 def gate_means(means: List[torch.Tensor]) -> List[float]:
@@ -48,9 +56,18 @@ def _t(image) -> torch.Tensor:
     return torch.from_numpy(np.array(image, dtype=np.uint8))
 
 
-def lift_crop(image, L: torch.Tensor, frames: list, box: Box, cfg: _lf.LiftConfig):
+def weight_plane(mask: torch.Tensor, box: Box, width: int, height: int) -> torch.Tensor:
+    """The edit-size weight plane of a crop, uint8 [height, width] on the host: mask.crop(box).resize((width, height), BILINEAR) - the region
+    mask `focus.inputs` hands the edit (`focus.host_inputs`' expression; `focus.device_inputs` gives the same bytes on the device)."""
+    from PIL import Image
+    return _t(Image.fromarray(mask.numpy()).crop(box).resize((int(width), int(height)), Image.BILINEAR))
+
+
+def lift_crop(image, L: torch.Tensor, frames: list, box: Box, cfg: _lf.LiftConfig, mask: Optional[torch.Tensor] = None, mask_aware: bool = False):
     """One crop: image = the PIL image the VAE saw, L uint8 [H, W, 3], frames = the sample's PIL frames (the edit's size) -> (Q uint8
-    [F, bh, bw, 3] on the host, the mean of g as a 0-d float64 tensor - or (the frames' bytes, None) for a box of the edit's size)."""
+    [F, bh, bw, 3] on the host, the mean of g as a 0-d float64 tensor - or (the frames' bytes, None) for a box of the edit's size).
+    mask_aware with a mask (the crop's photo-size mask uint8 [SH, SW] on the host): the fit runs under `weight_plane(mask, box)`
+    (rimlift.reference); without a mask there is no taper to undo and the plain fit runs."""
     from PIL import Image
     l, t, r, b = box
     E = torch.stack([_t(f) for f in frames])
@@ -58,7 +75,10 @@ def lift_crop(image, L: torch.Tensor, frames: list, box: Box, cfg: _lf.LiftConfi
         return E, None
     P = _t(image.convert("RGB").crop(box))
     U = None if cfg.gate is None else torch.stack([_t(f.resize((r - l, b - t), Image.LANCZOS)) for f in frames])
-    Q, coef = _lf.reference(P, L, E, U, cfg, return_coef=True)
+    if mask_aware and mask is not None:
+        Q, coef = _rl.reference(P, L, E, weight_plane(mask, box, E.shape[2], E.shape[1]), U, cfg, return_coef=True)
+    else:
+        Q, coef = _lf.reference(P, L, E, U, cfg, return_coef=True)
     return Q, coef[..., 6].double().mean()
 
 
@@ -77,19 +97,21 @@ def host_paste(source, lifted: List[torch.Tensor], masks: Optional[list], boxes:
     return out
 
 
-def reference(source, crops: list, cfg: _lf.LiftConfig):
+def reference(source, crops: list, cfg: _lf.LiftConfig, mask_aware: bool = False):
     """THE definition for one canvas.  source: the paste source (PIL); crops: per crop, in paste order, (the image the VAE saw (PIL), L uint8
     [H, W, 3], the sample's frames (PIL, the edit's size), its photo-size mask uint8 [SH, SW] on the host or None, its box) -> (per frame a
-    PIL image of the photo's size, per crop the mean of g or None for a box of the edit's size)."""
-    done = [lift_crop(im, L, frames, box, cfg) for im, L, frames, _, box in crops]
+    PIL image of the photo's size, per crop the mean of g or None for a box of the edit's size).  mask_aware: every crop that has a mask is
+    fitted under its edit-size weight plane (`lift_crop`)."""
+    done = [lift_crop(im, L, frames, box, cfg, m, mask_aware) for im, L, frames, m, box in crops]
     masks = [m for _, _, _, m, _ in crops]
     return host_paste(source, [q for q, _ in done], None if all(m is None for m in masks) else masks, [c[4] for c in crops]), [v for _, v in done]
 
 
 # ---- the device form -----------------------------------------------------------------------------------------------------------------
-def device_lift_paste(canvas: torch.Tensor, plan, E: torch.Tensor, cfg: _lf.LiftConfig, composite: bool):
+def device_lift_paste(canvas: torch.Tensor, plan, E: torch.Tensor, cfg: _lf.LiftConfig, composite: bool, mask_aware: bool = False):
     """One crop into canvas uint8 [F, SH, SW, 3] IN PLACE: the grid passes of the lift on (L, E), then ce_boxlift_apply_paste_u8; a box of
-    the edit's size through ce_clusters_paste_u8 -> the mean of g where it lies, or None.  Nothing is read back here."""
+    the edit's size through ce_clusters_paste_u8 -> the mean of g where it lies, or None.  mask_aware under a composite: the fit and the
+    smoothing are csrc/ce_rimlift.hip's, under `plan.lift_M`.  Nothing is read back here."""
     from . import image_io, ops
     l, t, r, b = plan.box
     bw, bh = r - l, b - t
@@ -99,8 +121,13 @@ def device_lift_paste(canvas: torch.Tensor, plan, E: torch.Tensor, cfg: _lf.Lift
         ops.clusters_paste_u8(E, mask, canvas, l, t)
         return None
     L = plan.lift_L.contiguous()
-    AB = ops.lift_fit_q16(L, E, cfg.radius, cfg.eps_q, cfg.max_gain)
-    coef, R = ops.lift_smooth(L, E, AB, cfg.radius)
+    if mask_aware and composite:
+        M = plan.lift_M.contiguous()
+        AB = ops.rimlift_fit_q16(L, E, M, cfg.radius, cfg.eps_q, cfg.max_gain)
+        coef, R = ops.rimlift_smooth(L, E, M, AB, cfg.radius)
+    else:
+        AB = ops.lift_fit_q16(L, E, cfg.radius, cfg.eps_q, cfg.max_gain)
+        coef, R = ops.lift_smooth(L, E, AB, cfg.radius)
     U = None
     if cfg.gate is not None:
         ops.lift_gate(R, coef, cfg.radius, *cfg.gate)
@@ -111,11 +138,12 @@ def device_lift_paste(canvas: torch.Tensor, plan, E: torch.Tensor, cfg: _lf.Lift
 
 
 # ---- the output stage of a focused, lifted call ---------------------------------------------------------------------------------------
-def output(video: torch.Tensor, plans: list, image_of, crop_of, cfg: _lf.LiftConfig, output_type: str, composite: bool):
+def output(video: torch.Tensor, plans: list, image_of, crop_of, cfg: _lf.LiftConfig, output_type: str, composite: bool, mask_aware: bool = False):
     """What focus.paste / clusters.paste do under `lift=`: their paste with every crop lifted inside its box -> (the frames at the photos'
     sizes in postprocess_video's layouts, the `lift_report`: one entry per sample).  video: [B, 3, F, height, width], the edit's size.
     crop_of None: sample b edits plans[image_of(b)] and is a canvas of its own; else sample b is plans[b], crop crop_of[b] = (value, g) of
-    its editor value, and the crops of a value chain into one canvas in ascending g.  The gate means of all crops are read back once."""
+    its editor value, and the crops of a value chain into one canvas in ascending g.  The gate means of all crops are read back once.
+    mask_aware: under a composite every lifted crop is fitted under its plan's `lift_M`, and every entry says "mask_aware"."""
     from . import image_io, ops
     image_io.check_output_type(output_type)
     B, height, width = video.shape[0], int(video.shape[-2]), int(video.shape[-1])
@@ -127,6 +155,8 @@ def output(video: torch.Tensor, plans: list, image_of, crop_of, cfg: _lf.LiftCon
     missing = [b for b in range(B) if plan_of(b).lift_L is None]
     if missing:
         raise RuntimeError(f"detail lift inside focus boxes: the pre-processing kept no edit-size source for sample(s) {missing}")
+    if mask_aware and composite and any(plan_of(b).lift_M is None for b in range(B)):
+        raise RuntimeError("mask-aware detail lift: the pre-processing kept no edit-size weight plane")
     on_device = plans[0].src_u8 is not None and image_io.device_video(video)
     u8 = ops.video_to_u8(video.contiguous()) if on_device else None
     out, means = [], {}
@@ -136,7 +166,7 @@ def output(video: torch.Tensor, plans: list, image_of, crop_of, cfg: _lf.LiftCon
             src = first.src_u8 if first.paste_u8 is None else first.paste_u8
             canvas = src.unsqueeze(0).repeat(u8.shape[1], 1, 1, 1)  # the paste source under every frame
             for b in members:
-                means[b] = device_lift_paste(canvas, plan_of(b), u8[b], cfg, composite)
+                means[b] = device_lift_paste(canvas, plan_of(b), u8[b], cfg, composite, mask_aware)
             out.append(canvas.cpu().numpy())
         else:
             crops = []
@@ -144,10 +174,11 @@ def output(video: torch.Tensor, plans: list, image_of, crop_of, cfg: _lf.LiftCon
                 p = plan_of(b)
                 frames = image_io.postprocess_video(video[b:b + 1], "pil")[0]
                 crops.append((p.image, p.lift_L.cpu(), frames, p.host_mask() if composite else None, p.box))
-            pasted, vals = reference(first.image if first.paste_image is None else first.paste_image, crops, cfg)
+            pasted, vals = reference(first.image if first.paste_image is None else first.paste_image, crops, cfg, mask_aware)
             means.update(zip(members, vals))
             out.append(np.stack([np.asarray(f, dtype=np.uint8) for f in pasted]))
-    report = [report_entry(plan_of(b), (width, height), "same" if means[b] is None else "ok") for b in range(B)]
+    report = [report_entry(plan_of(b), (width, height), "same" if means[b] is None else "ok",
+                           (composite and means[b] is not None) if mask_aware else None) for b in range(B)]
     lifted = [b for b in range(B) if means[b] is not None]
     for b, v in zip(lifted, gate_means([means[b] for b in lifted])):
         report[b]["fallback_fraction"] = v

@@ -244,18 +244,19 @@ def host_paste(background, frames_of_group: list, masks: Optional[list], boxes: 
     return out
 
 
-def paste(video: torch.Tensor, plans: list, crop_of: List[Tuple[int, int]], output_type: str, composite: bool, lift=None, report: Optional[list] = None):
+def paste(video: torch.Tensor, plans: list, crop_of: List[Tuple[int, int]], output_type: str, composite: bool, lift=None, report: Optional[list] = None,
+          mask_aware: bool = False):
     """focus.paste for a flat list of crops: sample b is crop crop_of[b] = (value, g) of its editor value, g counting from 0 in paste order;
     the crops of one value are chained into ONE video at the photo's size (`host_paste`; on the device ce_focus_paste_u8 builds the canvas
     from the background with the first crop, ce_clusters_paste_u8 adds the others in place) -> one entry per value, in postprocess_video's
     layouts.  lift: a lift.LiftConfig - every crop is lifted inside its box from its plan's `lift_L` before the paste (boxlift.output), in
-    the same order, and `report` receives one `lift_report` entry per crop."""
+    the same order, and `report` receives one `lift_report` entry per crop; mask_aware: the fits run under the plans' `lift_M`."""
     from . import focus as _fc
     from . import image_io, ops
     image_io.check_output_type(output_type)
     if lift is not None:
         from . import boxlift
-        frames, entries = boxlift.output(video, plans, None, crop_of, lift, output_type, composite)
+        frames, entries = boxlift.output(video, plans, None, crop_of, lift, output_type, composite, mask_aware)
         if report is not None:
             report.extend(entries)
         return frames

@@ -179,6 +179,7 @@ class FocusPlan:
     paste_image: Any = None  # a second source the frames are pasted into (a sketch edit's background); None: `image`
     paste_u8: Optional[torch.Tensor] = None  # its bytes on the device
     lift_L: Optional[torch.Tensor] = None  # the crop at the edit's size uint8 [height, width, 3] as the VAE got it, where the passes run: kept for boxlift.py
+    lift_M: Optional[torch.Tensor] = None  # the edit's region mask uint8 [height, width] beside it: the weight plane of the mask-aware fit (rimlift.py)
 
     @classmethod
     def make(cls, image, report: dict, mask: torch.Tensor, device=None, paste_image=None, uploaded=None) -> "FocusPlan":
@@ -222,8 +223,8 @@ def setup(image, masks, height: int, width: int, context: float, output_type, de
 
 def inputs(plans: List[FocusPlan], height: int, width: int, device, keep_L: bool = False):
     """(img bf16 [n, 3, height, width] as preprocessing leaves it, the edit-size region masks uint8 [height, width] on the device) of
-    the crops: the device passes, or PIL itself (`host_inputs`).  keep_L: every plan keeps the resized crop's bytes (`lift_L`: the detail
-    lift inside the box works from them) - on the host the crop is then resized here, once, and preprocessing takes it as it is."""
+    the crops: the device passes, or PIL itself (`host_inputs`).  keep_L: every plan keeps the resized crop's bytes and the edit-size mask (`lift_L`,
+    `lift_M`: the detail lift inside the box works from them) - on the host the crop is then resized here, once, and preprocessing takes it as it is."""
     from . import image_io, ops
     if plans[0].src_u8 is not None:
         img = torch.empty((len(plans), 3, height, width), dtype=torch.bfloat16, device=device)
@@ -233,29 +234,31 @@ def inputs(plans: List[FocusPlan], height: int, width: int, device, keep_L: bool
             ops.image_u8_lut_planar(crop, image_io.vae_lut(torch.device(device)), img[j])
             masks.append(m)
             if keep_L:
-                p.lift_L = crop
+                p.lift_L, p.lift_M = crop, m
         return img, masks
     host = [host_inputs(p.image, p.host_mask(), p.box, width, height) for p in plans]
     if keep_L:
         import numpy as np
         from PIL import Image
         host = [(c.resize((int(width), int(height)), Image.LANCZOS), m) for c, m in host]
-        for p, (c, _) in zip(plans, host):
-            p.lift_L = torch.from_numpy(np.array(c, dtype=np.uint8))
+        for p, (c, m) in zip(plans, host):
+            p.lift_L, p.lift_M = torch.from_numpy(np.array(c, dtype=np.uint8)), m
     img = image_io.preprocess_image([c for c, _ in host], height, width).to(device=device, dtype=torch.bfloat16)
     return img, [m.to(device) for _, m in host]
 
 
-def paste(video: torch.Tensor, plans: List[FocusPlan], image_of, output_type: str, composite: bool, lift=None, report: Optional[list] = None):
+def paste(video: torch.Tensor, plans: List[FocusPlan], image_of, output_type: str, composite: bool, lift=None, report: Optional[list] = None,
+          mask_aware: bool = False):
     """The source-size paste-back of every sample's frames (reasoning frames included), in postprocess_video's layouts: through the mask
     (composite), or the whole box.  A plan with a second source is pasted into that one.  lift: a lift.LiftConfig - every sample is lifted
-    inside its box from its plan's `lift_L` before the paste (boxlift.output), and `report` receives one `lift_report` entry per sample."""
+    inside its box from its plan's `lift_L` before the paste (boxlift.output), and `report` receives one `lift_report` entry per sample;
+    mask_aware: the fit runs under the plan's `lift_M` (boxlift.py)."""
     import numpy as np
     from . import image_io, ops
     image_io.check_output_type(output_type)
     if lift is not None:
         from . import boxlift
-        frames, entries = boxlift.output(video, plans, image_of, None, lift, output_type, composite)
+        frames, entries = boxlift.output(video, plans, image_of, None, lift, output_type, composite, mask_aware)
         if report is not None:
             report.extend(entries)
         return frames

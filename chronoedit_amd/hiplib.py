@@ -26,7 +26,7 @@ DIAG_HEADER = os.path.join(ROOT, "include", "chronoedit_hip_diag.h")
 DIAG_SOURCES = ["ce_gemm.hip", "ce_gemm256.hip", "ce_attn.hip", "ce_attn_fp8.hip", "ce_gemm_fp8.hip", "ce_gemm_fp8w4.hip"]
 # measured-and-closed experiments kept as opt-in bodies: in the diagnostic library only
 DIAG_ONLY_SOURCES = ["ce_attn16.hip"]
-SOURCES = ["ce_rowops.hip", "ce_gemm.hip", "ce_gemm256.hip", "ce_gemm256w4.hip", "ce_gemm384.hip", "ce_attn.hip", "ce_attn16.hip", "ce_attn_fp8.hip", "ce_sched.hip", "ce_conv.hip", "ce_enc.hip", "ce_gemm_fp8.hip", "ce_gemm_fp8w4.hip", "ce_comm.hip", "ce_lora.hip", "ce_tea.hip", "ce_image.hip", "ce_region.hip", "ce_sparse.hip", "ce_region_auto.hip", "ce_focus.hip", "ce_autofocus.hip", "ce_preview.hip", "ce_lift.hip", "ce_sketch.hip", "ce_components.hip", "ce_clusters.hip", "ce_layers.hip", "ce_boxlift.hip"]
+SOURCES = ["ce_rowops.hip", "ce_gemm.hip", "ce_gemm256.hip", "ce_gemm256w4.hip", "ce_gemm384.hip", "ce_attn.hip", "ce_attn16.hip", "ce_attn_fp8.hip", "ce_sched.hip", "ce_conv.hip", "ce_enc.hip", "ce_gemm_fp8.hip", "ce_gemm_fp8w4.hip", "ce_comm.hip", "ce_lora.hip", "ce_tea.hip", "ce_image.hip", "ce_region.hip", "ce_sparse.hip", "ce_region_auto.hip", "ce_focus.hip", "ce_autofocus.hip", "ce_preview.hip", "ce_lift.hip", "ce_sketch.hip", "ce_components.hip", "ce_clusters.hip", "ce_layers.hip", "ce_boxlift.hip", "ce_rimlift.hip"]
 
 _c = ctypes
 _P, _I, _F = _c.c_void_p, _c.c_int, _c.c_float
@@ -134,6 +134,8 @@ SIGNATURES: Dict[str, List] = {
     "ce_layers_strokes_u8": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P],
     "ce_layers_over_u8": [_P, _I, _I, _I, _I, _P, _I, _I, _P],
     "ce_boxlift_apply_paste_u8": [_P] * 11 + [_I] * 9 + [_P],
+    "ce_rimlift_fit_q16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "ce_rimlift_smooth_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "ce_build_info": [],
 }
 # the selectors only libchronoedit_hip_diag.so exports (include/chronoedit_hip_diag.h)

@@ -1547,6 +1547,52 @@ def boxlift_apply_paste_u8(P: torch.Tensor, coef: torch.Tensor, tables, U: Optio
     return canvas
 
 
+# ---- mask-aware detail lift (csrc/ce_rimlift.hip) --------------------------------------------------------------------------
+def _rimlift_planes(L: torch.Tensor, E: torch.Tensor, M: torch.Tensor):
+    F, H, W = _lift_planes(L, E)
+    _dev(M, torch.uint8, "M")
+    if tuple(M.shape) != (H, W) or not M.is_contiguous():
+        raise ValueError(f"M: need a contiguous [{H}, {W}] tensor, got shape {tuple(M.shape)} stride {M.stride()}")
+    return F, H, W
+
+
+def rimlift_fit_q16(L: torch.Tensor, E: torch.Tensor, M: torch.Tensor, radius: int, eps_q: int, max_gain: float,
+                    out: Optional[torch.Tensor] = None):
+    """Stage 1 of rimlift.py: L uint8 [H, W, 3], E uint8 [F, H, W, 3], M uint8 [H, W] (the edit-size weight plane) -> int32 [F, H, W, 6] =
+    rint(65536 a_rgb), rint(65536 b_rgb) of the untapered map."""
+    F, H, W = _rimlift_planes(L, E, M)
+    if out is None:
+        out = torch.empty((F, H, W, 6), dtype=torch.int32, device=L.device)
+    _dev(out, torch.int32, "out")
+    assert out.is_contiguous() and tuple(out.shape) == (F, H, W, 6)
+    st = _prof_begin()
+    _check(lib().ce_rimlift_fit_q16(_ptr(L), _ptr(E), _ptr(M), _ptr(out), F, H, W, int(radius), int(eps_q), float(max_gain), _stream()),
+           "ce_rimlift_fit_q16")
+    _prof_end(st, f"rimlift_fit_{F}x{H}x{W}_r{radius}", float(L.numel() + E.numel() + F * M.numel() + 4 * out.numel()))
+    return out
+
+
+def rimlift_smooth(L: torch.Tensor, E: torch.Tensor, M: torch.Tensor, AB: torch.Tensor, radius: int, coef: Optional[torch.Tensor] = None,
+                   R: Optional[torch.Tensor] = None):
+    """Stage 2 of rimlift.py: -> (the cells fp32 [F, H, W, 8]: the M-weighted box means of a and b, slots 6 and 7 zeroed; R int32 [F, H, W] =
+    rint(256 min(res, 255)), the residual of the tapered model)."""
+    F, H, W = _rimlift_planes(L, E, M)
+    _dev(AB, torch.int32, "AB")
+    if not AB.is_contiguous() or tuple(AB.shape) != (F, H, W, 6):
+        raise ValueError(f"AB: need a contiguous [{F}, {H}, {W}, 6] tensor, got shape {tuple(AB.shape)} stride {AB.stride()}")
+    if coef is None:
+        coef = torch.empty((F, H, W, LIFT_CELL), dtype=torch.float32, device=L.device)
+    if R is None:
+        R = torch.empty((F, H, W), dtype=torch.int32, device=L.device)
+    _dev(coef, torch.float32, "coef"), _dev(R, torch.int32, "R")
+    assert coef.is_contiguous() and tuple(coef.shape) == (F, H, W, LIFT_CELL) and R.is_contiguous() and tuple(R.shape) == (F, H, W)
+    st = _prof_begin()
+    _check(lib().ce_rimlift_smooth_f32(_ptr(L), _ptr(E), _ptr(M), _ptr(AB), _ptr(coef), _ptr(R), F, H, W, int(radius), _stream()),
+           "ce_rimlift_smooth_f32")
+    _prof_end(st, f"rimlift_smooth_{F}x{H}x{W}_r{radius}", float(4 * (AB.numel() + coef.numel() + R.numel()) + F * M.numel()))
+    return coef, R
+
+
 # ---- Wan VAE ------------------------------------------------------------------------------------------------------
 # ---- sparse region edits (csrc/ce_sparse.hip) ----------------------------------------------------------------------------
 def _sparse_ids(ids: torch.Tensor):

@@ -105,6 +105,7 @@ class EditSources:
     auto_focus: Any = None  # the autofocus.AutoFocusConfig when this pass is a scout
     lift: Any = None  # the lift.LiftConfig while the detail lift is on (a focused pass only reports it, unless lift_focus)
     lift_focus: bool = False  # enable_detail_lift(focus=True): a focused pass lifts every crop inside its box before the paste (boxlift.py)
+    lift_mask_aware: bool = False  # enable_detail_lift(focus=True, mask_aware=True): those fits run under the crops' edit-size masks (rimlift.py)
     crop_of: Optional[list] = None  # per focus plan (editor value, crop) when the crops of a value are chained into one video (clusters.paste)
 
 
@@ -175,6 +176,7 @@ class ChronoEditPipeline:
         self.preview_fit_gram = None  # float64 [20, 20] on the CPU: the Gram matrix the last fit solved
         self._detail_lift = None  # the lift.LiftConfig while enable_detail_lift is in force
         self._detail_lift_focus = False  # enable_detail_lift(focus=True): focused passes lift inside their boxes
+        self._detail_lift_mask_aware = False  # enable_detail_lift(focus=True, mask_aware=True): ... fitted under the region's weights
         self.lift_report = None  # the last call's detail-lift report, one dict per sample; None when the switch is off (or "latent" was asked for)
         self._sketch_region = None  # the sketch.SketchConfig while enable_sketch_region is in force
         self.sketch_report = None  # the last call's sketch plans, one dict per editor value; None when the call got no editor value
@@ -792,7 +794,8 @@ class ChronoEditPipeline:
         return _cl.crop_reports(crops, single)
 
     # Guided detail lift (chronoedit_amd/lift.py): whole-image edits returned at the photo's size.  Off by default
-    def enable_detail_lift(self, radius: int = 4, eps: float = 26.0, gate=(4.0, 12.0), max_gain: float = 8.0, focus: bool = False):
+    def enable_detail_lift(self, radius: int = 4, eps: float = 26.0, gate=(4.0, 12.0), max_gain: float = 8.0, focus: bool = False,
+                           mask_aware: bool = False):
         """While on, a call with PIL input (one image, or a list with one per prompt) and output_type "pil" / "np" / "pt" returns every frame
         - reasoning frames included, behind the edit-size region composite if there is one - at the IMAGE's own size: per edit-size
         neighbourhood and colour an affine map from the resized photo to the edit's change is fitted (window radius `radius` cells,
@@ -812,16 +815,28 @@ class ChronoEditPipeline:
         pre-processing fed it, and the lifted box goes through the photo-size mask into the paste source (csrc/ce_boxlift.hip fuses the
         apply with the paste; `boxlift.reference` on the host, the same bytes).  `lift_report` then holds one entry per sample - per
         crop - with "size" = the box's size, "reason" "ok" or "same" (a box of exactly the edit's size: the plain paste), and "box" and
-        "scale" on top.  `focus_report` / `sketch_report`, and everything a focused edit composes with or refuses, stay as they are."""
+        "scale" on top.  `focus_report` / `sketch_report`, and everything a focused edit composes with or refuses, stay as they are.
+        mask_aware=True (needs focus=True): a region edit blends its latents with the source, so a crop's frames carry the change TAPERED by
+        the region's weight, and the plain fit misreads the feathered rim.  Every crop that is lifted inside its box and pasted through
+        its mask is then fitted under its edit-size mask (chronoedit_amd/rimlift.py, csrc/ce_rimlift.hip): the lift recovers the untapered
+        edit and applies it at full strength, and the paste's photo-size mask tapers it once.  `composite=False` and boxes of the edit's
+        size keep the plain path.  While it is on every `lift_report` entry says "mask_aware": whether that sample was fitted this way.  A
+        rising `fallback_fraction` under the switch means the frames' taper does not follow the mask; the fallback is the plain upsample."""
         if not isinstance(focus, bool):
             raise ValueError(f"detail lift: focus must be True or False, got {focus!r}")
+        if not isinstance(mask_aware, bool):
+            raise ValueError(f"detail lift: mask_aware must be True or False, got {mask_aware!r}")
+        if mask_aware and not focus:
+            raise ValueError("detail lift: mask_aware=True needs focus=True (the masked fit runs on the crops of focused edits)")
         self._detail_lift = _lf.LiftConfig(radius, eps, None if gate is None else tuple(gate) if isinstance(gate, (tuple, list)) else gate, max_gain)
         self._detail_lift_focus = focus
+        self._detail_lift_mask_aware = mask_aware
         return self
 
     def disable_detail_lift(self):
         self._detail_lift = None
         self._detail_lift_focus = False
+        self._detail_lift_mask_aware = False
         return self
 
     def _measure_kwargs(self) -> dict:
@@ -1141,7 +1156,7 @@ class ChronoEditPipeline:
             if pil is None:
                 raise ValueError("detail lift needs PIL input (one image or a list): an array or tensor `image` has no full-resolution bytes to "
                                  "lift the edit onto - pass PIL images, or disable_detail_lift()")
-            what.lift, what.lift_focus = self._detail_lift, self._detail_lift_focus
+            what.lift, what.lift_focus, what.lift_mask_aware = self._detail_lift, self._detail_lift_focus, self._detail_lift_mask_aware
             if what.focus is None and a.output_type in ("np", "pt") and len({im.size for im in pil}) > 1:
                 raise ValueError(f"detail lift returns frames of the images' sizes {[im.size for im in pil]}: output_type={a.output_type!r} "
                                  'needs images of one size, use "pil"')
@@ -1254,14 +1269,18 @@ class ChronoEditPipeline:
             video = torch.cat(self._composited(video.to(device), img, masks, image_of), dim=0)
         if what.lift is not None and what.focus is None:
             lifted, self.lift_report = _lf.output(video, what.lift, lift_kept, what.pil, image_of, a.height, a.width, a.output_type)
+            if what.lift_mask_aware:  # (a whole-photo lift has no crop to fit under a mask)
+                for entry in self.lift_report:
+                    entry["mask_aware"] = False
             if lifted is not None:
                 return lifted
         if what.focus is not None:  # the source-size paste replaces the edit-size composite
             boxed, lifted = (what.lift if what.lift_focus else None), []  # focus=True: every crop is lifted inside its box (boxlift.py)
+            masked = boxed is not None and what.lift_mask_aware
             if what.crop_of is not None:  # the crops of an editor value, chained into one video
-                video = _cl.paste(video, what.focus, what.crop_of, a.output_type, what.composite, lift=boxed, report=lifted)
+                video = _cl.paste(video, what.focus, what.crop_of, a.output_type, what.composite, lift=boxed, report=lifted, mask_aware=masked)
             else:
-                video = _fc.paste(video, what.focus, image_of, a.output_type, what.composite, lift=boxed, report=lifted)
+                video = _fc.paste(video, what.focus, image_of, a.output_type, what.composite, lift=boxed, report=lifted, mask_aware=masked)
             if boxed is not None:
                 self.lift_report = lifted
             elif what.lift is not None:

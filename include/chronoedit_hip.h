@@ -788,6 +788,28 @@ int ce_boxlift_apply_paste_u8(const void* P, const void* U, const float* coef, c
                               const int* iy1, const float* ty, const void* mask, void* canvas, int F, int src_h, int src_w, int left, int top,
                               int bw, int bh, int H, int W, hipStream_t stream);
 
+/* ---- mask-aware detail lift (csrc/ce_rimlift.hip; chronoedit_amd/rimlift.py is the definition and both passes give its bits): stages 1 and
+ * 2 of the lift inside a focus box, fitted under the region's weights, so that the apply stage writes the edit at full strength and the
+ * paste's mask tapers it once.  L, E, AB, coef, R and radius are ce_lift_fit_q16's / ce_lift_smooth_f32's; M = uint8 [H][W], the edit-size
+ * weight plane m, shared by the frames and the colours; box() is the sum over the window [y - r, y + r] x [x - r, x + r] clipped to the image.
+ * ce_rimlift_fit_q16: per frame, cell and colour, I = L_c, d = E_c - I; the exact integer sums T_q = box(m m), T_md = box(m d) (int32),
+ *   T_qI = box(m m I), T_qII = box(m m I I), T_mId = box(m I d) (int64; all below 2^53) - the normal equations of 255 d ~ a (m I) + b m.
+ *   In double, every operation rounded on its own:  num = T_q * T_mId - T_qI * T_md;  den = (T_q * T_qII - T_qI * T_qI) + (T_q * eps_q) * T_q;
+ *   where T_q > 0 (den > 0 there: the eps term exceeds the rounding error of the products 2^30 times):
+ *   a = fp32(clamp((num * 255) / den, -max_gain, max_gain)),  b = fp32(clamp((T_md * 255 - double(a) * T_qI) / T_q, -4096, 4096));
+ *   where T_q == 0: a = b = 0.  AB = int32 [F][H][W][6] = rint(65536 a_rgb), rint(65536 b_rgb).
+ * ce_rimlift_smooth_f32: n_m = box(m); abar = fp32(double(box(m A)) / double(65536 n_m)) where n_m > 0, else 0, bbar likewise (int64 sums);
+ *   w = fp32(m) / 255;  res = max over colours of |float(d) - (abar * float(I) + bbar) * w| - the residual of the TAPERED model;
+ *   coef = fp32 [F][H][W][8] = abar_rgb, bbar_rgb, 0, 0 (16-byte aligned);  R = int32 [F][H][W] = rint(256 min(res, 255)).
+ * ce_lift_gate_f32 and ce_boxlift_apply_paste_u8 follow, unchanged: q = p + (a_up * p + b_up) is then the untapered edit.
+ * What follows from the arithmetic: M == 0 gives zero cells and R = 256 min(|d|, 255) maximised over the colours; E == L gives a = b = 0.
+ * No state, nothing allocated, no host read: every call is capturable.  F <= 65535; radius 1..16, eps_q 1..2^30, max_gain 1..8, sizes > 0 and
+ * no NULL pointer (otherwise -1).  A plane of 2^31 bytes or more (H * W * 3) returns -2; AB and R 4-byte, coef 16-byte aligned (otherwise -3). */
+int ce_rimlift_fit_q16(const void* L, const void* E, const void* M, int* AB, int F, int H, int W, int radius, int eps_q, float max_gain,
+                       hipStream_t stream);
+int ce_rimlift_smooth_f32(const void* L, const void* E, const void* M, const int* AB, float* coef, int* R, int F, int H, int W, int radius,
+                          hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
