@@ -29,130 +29,63 @@ DIAG_ONLY_SOURCES = ["ce_attn16.hip"]
 SOURCES = ["ce_rowops.hip", "ce_gemm.hip", "ce_gemm256.hip", "ce_gemm256w4.hip", "ce_gemm384.hip", "ce_attn.hip", "ce_attn16.hip", "ce_attn_fp8.hip", "ce_sched.hip", "ce_conv.hip", "ce_enc.hip", "ce_gemm_fp8.hip", "ce_gemm_fp8w4.hip", "ce_comm.hip", "ce_lora.hip", "ce_tea.hip", "ce_image.hip", "ce_region.hip", "ce_sparse.hip", "ce_region_auto.hip", "ce_focus.hip", "ce_autofocus.hip", "ce_preview.hip", "ce_lift.hip", "ce_sketch.hip", "ce_components.hip", "ce_clusters.hip", "ce_layers.hip", "ce_boxlift.hip", "ce_rimlift.hip"]
 
 _c = ctypes
-_P, _I, _F = _c.c_void_p, _c.c_int, _c.c_float
+# scalar parameter types of the C ABI; every pointer is passed as an address (see _ctype)
+_SCALARS = {"int": _c.c_int, "float": _c.c_float, "long long": _c.c_longlong, "size_t": _c.c_size_t, "hipStream_t": _c.c_void_p}
 
-# symbol -> argtypes (restype is always int)
-SIGNATURES: Dict[str, List] = {
-    "ce_ln_affine_bf16": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P],
-    "ce_rmsnorm_rope_bf16": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
-    "ce_gemm_bf16": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _c.c_longlong, _I, _c.c_longlong, _P, _c.c_size_t, _P],
-    "ce_gemm_bf16_res": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _c.c_longlong, _I, _c.c_longlong, _P, _c.c_size_t, _P],
-    "ce_rmsnorm_rope_mxfp8": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _F, _P],
-    "ce_v_mxfp8_transpose": [_P, _I, _P, _P, _I, _I, _I, _I, _P],
-    "ce_attention_mxfp8": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ce_attention_mxfp8_quant": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ce_attention_mxfp8_add": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ce_rope_scatter_bf16": [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _F, _I, _P],
-    "ce_patchify_rows_bf16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ce_comm_load": [ctypes.c_char_p],
-    "ce_comm_unique_id": [_P],
-    "ce_comm_init": [ctypes.POINTER(ctypes.c_void_p), _P, _I, _I],
-    "ce_comm_destroy": [_P],
-    "ce_comm_all_to_all": [_P, _P, _P, ctypes.c_size_t, _P],
-    "ce_comm_all_gather": [_P, _P, _P, ctypes.c_size_t, _P],
-    "ce_ln_affine_fp8": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P],
-    "ce_quant_rows_fp8": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "ce_gemm_fp8": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
-    "ce_quant_rows_mxfp8": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "ce_quant_rows_mxfp8_w": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "ce_ln_affine_mxfp8": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P],
-    "ce_gemm_mxfp8": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
-    "ce_gemm_mxfp8_gelu_quant": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _c.c_size_t, _P],
-    "ce_gemm_batched_bf16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I] + [ctypes.c_longlong] * 6 + [_P],
-    "ce_im2col_patch2d_bf16": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ce_gather_rows_bf16": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ce_rmsnorm_bf16": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
-    "ce_softmax_t5_bf16": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "ce_attention_bf16": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P],
-    "ce_attention_batched_bf16": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P],
-    "ce_attention_vt_bf16": [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P],
-    "ce_attention_2seg_vt_bf16": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P],
-    "ce_attention_2seg_vt_strided_bf16": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I, _P],
-    "ce_attention_2seg_vt_weighted_bf16": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I, _P, _P, _P],
-    "ce_attention_2seg_vt_quant_bf16": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
-    "ce_v_transpose_bf16": [_P, _I, _P, _I, _I, _I, _P],
-    "ce_attention_vt_blocked_bf16": [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I, _P],
-    "ce_v_transpose_blocked_bf16": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ce_timestep_sinusoid": [_P, _P, _I, _P],
-    "ce_timestep_sinusoid_f32": [_P, _P, _I, _P],
-    "ce_gemv": [_P, _I, _P, _P, _P, _I, _I, _I, _P],
-    "ce_modulation": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ce_patchify_bf16": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "ce_unpatchify_bf16": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "ce_conv_igemm_bf16": [_P, _I, _P, _P, _P, _I, _P] + [_I] * 16 + [_P],
-    "ce_conv3d_head_bf16": [_P, _I, _P, _P, _P, _I] + [_I] * 10 + [_P],
-    "ce_gemm_bf16_tile_rows": [_I, _I, _I, _I, _c.c_longlong],
-    "ce_zero_border_bf16": [_P, _I, _I, _I, _I, _I, _P],
-    "ce_conv3d_gemm_bf16": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ce_conv3d_gemm_rms_silu_bf16": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P],
-    "ce_rms_silu_bf16": [_P, _P, _P, _c.c_longlong, _I, _I, _I, _I, _I, _I, _P],
-    "ce_upsample2x_bf16": [_P, _P, _I, _I, _I, _I, _P],
-    "ce_softmax_rows_f32_bf16": [_P, _P, _I, _I, _I, _I, _I, _F, _P],
-    "ce_attention_1head_bf16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _c.c_longlong, _P],
-    "ce_cfg_unipc_step": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_longlong, _I, _P],
-    "ce_cfg_unipc_step_delta": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_longlong, _I, _I, _I, _P, _c.c_longlong, _P, _I, _P],
-    "ce_lora_merge_bf16": [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "ce_tea_rel_l1_bf16": [_P, _I, _I, _P, _P],
-    "ce_tea_store_bf16": [_P, _P, _c.c_longlong, _P],
-    "ce_tea_apply_bf16": [_P, _P, _c.c_longlong, _P],
-    "ce_tea_store_dist_bf16": [_P, _P, _P, _P, _P, _c.c_longlong, _c.c_longlong, _P],
-    "ce_image_resample_u8": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P],
-    "ce_image_u8_lut_planar": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P],
-    "ce_video_to_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "ce_region_weights_u8": [_P, _P, _I, _I, _P],
-    "ce_region_blend_f32": [_P, _P, _P, _P, _P, _c.c_longlong, _c.c_longlong, _I, _P],
-    "ce_region_composite": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
-    "ce_auto_region_change_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ce_auto_region_otsu_f32": [_P, _I, _F, _P, _P, _P],
-    "ce_auto_region_ramp_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "ce_auto_region_mask_u8": [_P, _P, _I, _I, _P],
-    "ce_sparse_patchify_bf16": [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ce_sparse_scatter_rows_bf16": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P],
-    "ce_sparse_scatter_vt_bf16": [_P, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P],
-    "ce_sparse_unpatchify_bf16": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P],
-    "ce_focus_resample_l8": [_P, _c.c_longlong, _P, _I, _I, _I, _I, _P, _P, _I, _P],
-    "ce_focus_paste_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ce_autofocus_bbox_u8": [_P, _c.c_longlong, _I, _I, _P, _P],
-    "ce_autofocus_restart_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P],
-    "ce_preview_rgb_u8": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ce_preview_gram_f64": [_P, _I, _P, _I, _P, _P, _c.c_size_t, _I, _I, _I, _I, _P],
-    "ce_lift_fit_q16": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
-    "ce_lift_smooth_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "ce_lift_gate_f32": [_P, _P, _I, _I, _I, _I, _F, _F, _P],
-    "ce_lift_apply_u8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ce_sketch_changed_u8": [_P, _P, _P, _c.c_longlong, _I, _P],
-    "ce_sketch_dilate_u8": [_P, _P, _I, _I, _I, _I, _P, _c.c_size_t, _P],
-    "ce_sketch_box_u8": [_P, _P, _I, _I, _I, _I, _P, _c.c_size_t, _P],
-    "ce_components_roots_i32": [_P, _P, _I, _I, _P],
-    "ce_components_sums_i32": [_P, _P, _P, _I, _I, _P],
-    "ce_components_keep_u8": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ce_components_seeds_f32": [_P, _P, _P, _I, _P],
-    "ce_components_masked_f32": [_P, _P, _P, _I, _P],
-    "ce_clusters_table_i32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "ce_clusters_select_u8": [_P, _P, _P, _P, _I, _P, _I, _I, _P],
-    "ce_clusters_paste_u8": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ce_layers_strokes_u8": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P],
-    "ce_layers_over_u8": [_P, _I, _I, _I, _I, _P, _I, _I, _P],
-    "ce_boxlift_apply_paste_u8": [_P] * 11 + [_I] * 9 + [_P],
-    "ce_rimlift_fit_q16": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
-    "ce_rimlift_smooth_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "ce_build_info": [],
-}
+
+def _header_text(diag: bool, text: str = None) -> str:
+    return open(DIAG_HEADER if diag else HEADER).read() if text is None else text
+
+
+def header_symbols(diag: bool = False, text: str = None) -> List[str]:
+    """Every function declared in include/chronoedit_hip.h (diag: in include/chronoedit_hip_diag.h; text: in that header text instead)."""
+    return re.findall(r"^int (ce_\w+)\(", _header_text(diag, text), flags=re.M)
+
+
+def _ctype(sym: str, param: str):
+    """The ctypes type of one parameter declaration: the text up to the parameter's name, looked up - never guessed."""
+    m = re.fullmatch(r"(.*?)\w+", param.strip(), flags=re.S)
+    ctype = re.sub(r"\s*\*\s*", "*", " ".join(m.group(1).split())) if m else ""
+    if ctype in _SCALARS:
+        return _SCALARS[ctype]
+    if ctype == "const char*":
+        return _c.c_char_p
+    if ctype == "void**":                     # a handle the callee writes (ce_comm_init)
+        return _c.POINTER(_c.c_void_p)
+    if ctype.endswith("*"):                   # device pointers and host arrays of them: an address
+        return _c.c_void_p
+    raise ValueError(f"{sym}: no ctypes type for parameter {param.strip()!r}")
+
+
+def header_signatures(diag: bool = False, text: str = None) -> Dict[str, List]:
+    """symbol -> argtypes (restype is always int) of every prototype of the header, in header order: the one signature table, parsed from the
+    ABI's own definition.  Raises on a parameter type it does not know and on a declaration header_symbols() sees whose prototype it cannot
+    read (a parameter list that holds a `)`, say) - a wrong argtype does not fail at the call, it shifts the arguments the kernel reads."""
+    txt = _header_text(diag, text)
+    code = re.sub(r"/\*.*?\*/|//[^\n]*", " ", txt, flags=re.S)
+    protos = re.findall(r"^int (ce_\w+)\(([^)]*)\);", code, flags=re.M | re.S)
+    declared = header_symbols(diag, txt)
+    if [sym for sym, _ in protos] != declared:
+        unread = [re.search(r"^int %s\([^;]*" % s, txt, flags=re.M).group(0) for s in declared if s not in dict(protos)]
+        raise ValueError(f"{len(protos)} prototypes read where {len(declared)} are declared; not read: {unread}")
+    return {sym: [_ctype(sym, p) for p in ([] if params.strip() in ("", "void") else params.split(","))] for sym, params in protos}
+
+
+SIGNATURES: Dict[str, List] = header_signatures()
 # the selectors only libchronoedit_hip_diag.so exports (include/chronoedit_hip_diag.h)
-DIAG_SIGNATURES: Dict[str, List] = {
-    "ce_set_gemm_variant": [_I],
-    "ce_set_attention_waves": [_I],
-    "ce_set_gemm_fp8_variant": [_I],
-    "ce_set_attention_mxfp8_variant": [_I],
-    "ce_set_attention_mxfp8_persistent": [_I],
-    "ce_diag_attention_exact_route_hits": [_P, _I],
-}
+DIAG_SIGNATURES: Dict[str, List] = header_signatures(diag=True)
 
 
-def header_symbols(diag: bool = False) -> List[str]:
-    """Every function declared in include/chronoedit_hip.h (diag: in include/chronoedit_hip_diag.h)."""
-    txt = open(DIAG_HEADER if diag else HEADER).read()
-    return re.findall(r"^int (ce_\w+)\(", txt, flags=re.M)
+def bind(lib: ctypes.CDLL, diag: bool = False) -> ctypes.CDLL:
+    """Set argtypes / restype on every declared entry point `lib` has (diag: the selectors too) and return `lib`.  An entry point the library
+    lacks - an A/B build from before it existed - is skipped.  Only correct for a build of THIS header: nothing here can tell that an
+    older build takes other arguments under the same name, and such a build is then called with shifted arguments."""
+    for name, argtypes in dict(SIGNATURES, **(DIAG_SIGNATURES if diag else {})).items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = argtypes
+            fn.restype = _c.c_int
+    return lib
 
 
 def exported_symbols(path: str) -> List[str]:
@@ -237,12 +170,7 @@ def _open(path: str, diag: bool) -> ctypes.CDLL:
     if missing or unknown:
         raise RuntimeError(f"{path} does not match include/chronoedit_hip{'_diag' if diag else ''}.h: missing {sorted(missing)}, "
                            f"not declared {sorted(unknown)}")
-    lib = ctypes.CDLL(path)
-    for name, argtypes in dict(SIGNATURES, **(DIAG_SIGNATURES if diag else {})).items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = _c.c_int
-    return lib
+    return bind(ctypes.CDLL(path), diag)
 
 
 def load() -> ctypes.CDLL:

@@ -129,6 +129,11 @@ def _check(rc: int, name: str):
         raise HipKernelError(f"{name} failed: {kind}")
 
 
+def _launch(name: str, *args):
+    """Call entry point `name` of the library launches go through; a non-zero return raises under that name."""
+    _check(getattr(lib(), name)(*args), name)
+
+
 def _stream() -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -160,8 +165,8 @@ def ln_affine(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, eps: float, out
         out = torch.empty((M, D), dtype=torch.bfloat16, device=x.device)
     _, _, ldy = _rows(out, "out")
     st = _prof_begin()
-    _check(lib().ce_ln_affine_bf16(_ptr(x), _ptr(out), _ptr(a), _ptr(b), M, D, ldx, ldy, float(eps), int(ab_rows), int(ab_stride),
-                                   _stream()), "ce_ln_affine_bf16")
+    _launch("ce_ln_affine_bf16", _ptr(x), _ptr(out), _ptr(a), _ptr(b), M, D, ldx, ldy, float(eps), int(ab_rows), int(ab_stride),
+            _stream())
     _prof_end(st, f"ln_affine_{M}x{D}", 4.0 * M * D)
     return out
 
@@ -181,8 +186,8 @@ def rmsnorm_rope_(x: torch.Tensor, w: torch.Tensor, cos_sin: Optional[torch.Tens
         _dev(x2, torch.bfloat16, "x2"), _dev(w2, torch.float32, "w2")
         assert _rows(x2, "x2") == (M, D, ld)
     st = _prof_begin()
-    _check(lib().ce_rmsnorm_rope_bf16(_ptr(x), _ptr(w), _ptr(x2), _ptr(w2), _ptr(cos_sin), M, D, ld, head_dim, float(eps), rope_rows,
-                                      _stream()), "ce_rmsnorm_rope_bf16")
+    _launch("ce_rmsnorm_rope_bf16", _ptr(x), _ptr(w), _ptr(x2), _ptr(w2), _ptr(cos_sin), M, D, ld, head_dim, float(eps), rope_rows,
+            _stream())
     _prof_end(st, f"rmsnorm_rope_{M}x{D}" + ("x2" if x2 is not None else ""), (8.0 if x2 is not None else 4.0) * M * D)
     return x
 
@@ -236,12 +241,12 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: Op
     ws, ws_bytes = _gemm_scratch(a.device)
     st = _prof_begin()
     if res_rows > 0:
-        _check(lib().ce_gemm_bf16_res(_ptr(a), _ptr(w), _ptr(out), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K, lda, ldw, ldc, ldres,
-                                      int(gate_rows), int(res_rows), int(a_seg_k), int(a_seg_stride), 0, 0, ws, ws_bytes, _stream()), "ce_gemm_bf16_res")
+        _launch("ce_gemm_bf16_res", _ptr(a), _ptr(w), _ptr(out), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K, lda, ldw, ldc, ldres,
+                int(gate_rows), int(res_rows), int(a_seg_k), int(a_seg_stride), 0, 0, ws, ws_bytes, _stream())
         _prof_end(st, f"gemm_{M}x{N}x{K}_epi{epilogue}_res{res_rows}", 2.0 * M * N * K)
         return out
-    _check(lib().ce_gemm_bf16(_ptr(a), _ptr(w), _ptr(out), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K, lda, ldw, ldc, ldres,
-                              int(gate_rows), int(a_seg_k), int(a_seg_stride), 0, 0, ws, ws_bytes, _stream()), "ce_gemm_bf16")
+    _launch("ce_gemm_bf16", _ptr(a), _ptr(w), _ptr(out), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K, lda, ldw, ldc, ldres,
+            int(gate_rows), int(a_seg_k), int(a_seg_stride), 0, 0, ws, ws_bytes, _stream())
     _prof_end(st, f"gemm_{M}x{N}x{K}_epi{epilogue}", 2.0 * M * N * K)
     return out
 
@@ -270,8 +275,8 @@ def rope_scatter(x: torch.Tensor, cols, weights, D: int, world: int, cos_sin: Op
     c = list(cols) + [0] * (3 - nt)
     w = list(weights) + [None] * (3 - nt)
     st = _prof_begin()
-    _check(lib().ce_rope_scatter_bf16(_ptr(x), ldx, _ptr(out), M, D, world, nt, c[0], _ptr(w[0]), c[1], _ptr(w[1]), c[2], _ptr(w[2]),
-                                      _ptr(cos_sin), head_dim, float(eps), rope_rows, _stream()), "ce_rope_scatter_bf16")
+    _launch("ce_rope_scatter_bf16", _ptr(x), ldx, _ptr(out), M, D, world, nt, c[0], _ptr(w[0]), c[1], _ptr(w[1]), c[2], _ptr(w[2]),
+            _ptr(cos_sin), head_dim, float(eps), rope_rows, _stream())
     _prof_end(st, f"rope_scatter_{M}x{D}x{nt}", 4.0 * M * D * nt)
     return out
 
@@ -365,8 +370,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, out
         scale = head_dim ** -0.5
     st = _prof_begin()
     nq, l1, l2 = Nq // batch, L1 // batch, L2 // batch
-    _check(lib().ce_attention_batched_bf16(_ptr(q), _ptr(k), _ptr(v), l1, ldk, ldv, _ptr(k2), _ptr(v2), l2, ldk2, ldv2, _ptr(out),
-                                           nq, heads, head_dim, ldq, ldo, float(scale), batch, _stream()), "ce_attention_bf16")
+    _launch("ce_attention_batched_bf16", _ptr(q), _ptr(k), _ptr(v), l1, ldk, ldv, _ptr(k2), _ptr(v2), l2, ldk2, ldv2, _ptr(out),
+            nq, heads, head_dim, ldq, ldo, float(scale), batch, _stream())
     _prof_end(st, f"attention_{nq}x{l1}+{l2}_h{heads}" + (f"_b{batch}" if batch > 1 else ""),
               4.0 * nq * (l1 + l2) * head_dim * heads * batch)
     return out
@@ -388,7 +393,7 @@ def v_transpose(v: torch.Tensor, heads: int, out: Optional[torch.Tensor] = None)
     _dev(out, torch.bfloat16, "vt")
     assert out.shape[0] == D and out.is_contiguous() and out.shape[1] >= n
     st = _prof_begin()
-    _check(lib().ce_v_transpose_bf16(_ptr(v), ldv, _ptr(out), out.shape[1], n, heads, _stream()), "ce_v_transpose_bf16")
+    _launch("ce_v_transpose_bf16", _ptr(v), ldv, _ptr(out), out.shape[1], n, heads, _stream())
     _prof_end(st, f"v_transpose_{n}x{D}", 4.0 * n * D)
     return out
 
@@ -411,8 +416,8 @@ def attention_vt(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int,
         scale = 128 ** -0.5
     st = _prof_begin()
     nq, l1 = Nq // batch, L1 // batch
-    _check(lib().ce_attention_vt_bf16(_ptr(q), _ptr(k), _ptr(vt), l1, ldk, vt.stride(0), _ptr(out), nq, heads, 128, ldq, ldo, float(scale),
-                                      batch, _stream()), "ce_attention_vt_bf16")
+    _launch("ce_attention_vt_bf16", _ptr(q), _ptr(k), _ptr(vt), l1, ldk, vt.stride(0), _ptr(out), nq, heads, 128, ldq, ldo, float(scale),
+            batch, _stream())
     _prof_end(st, f"attention_{nq}x{l1}+0_h{heads}" + (f"_b{batch}" if batch > 1 else ""), 4.0 * nq * l1 * 128 * heads * batch)
     return out
 
@@ -445,9 +450,9 @@ def attention_2seg_vt(q: torch.Tensor, k1: torch.Tensor, v1t: torch.Tensor, len1
         _, D8, ld8 = _rows(out8, "out8")
         assert out8.shape[0] == Nq and D8 == Dq and scale8.is_contiguous() and scale8.numel() >= mx_scale_bytes(Nq, Dq)
         st = _prof_begin()
-        _check(lib().ce_attention_2seg_vt_quant_bf16(_ptr(q), _ptr(k1), _ptr(v1t), len1, ldk1, v1t.stride(0), int(cols1), _ptr(k2), _ptr(v2t),
-                                                     len2, ldk2, v2t.stride(0), int(cols2), _ptr(out8), _ptr(scale8), nq, heads, 128, ldq, ld8,
-                                                     float(scale), batch, _stream()), "ce_attention_2seg_vt_quant_bf16")
+        _launch("ce_attention_2seg_vt_quant_bf16", _ptr(q), _ptr(k1), _ptr(v1t), len1, ldk1, v1t.stride(0), int(cols1), _ptr(k2), _ptr(v2t),
+                len2, ldk2, v2t.stride(0), int(cols2), _ptr(out8), _ptr(scale8), nq, heads, 128, ldq, ld8,
+                float(scale), batch, _stream())
         _prof_end(st, f"attention_{nq}x{len1}+{len2}_h{heads}" + (f"_b{batch}" if batch > 1 else "") + "_mxq",
                   4.0 * nq * (len1 + len2) * 128 * heads * batch)
         return out8
@@ -455,9 +460,9 @@ def attention_2seg_vt(q: torch.Tensor, k1: torch.Tensor, v1t: torch.Tensor, len1
         out = torch.empty((Nq, Dq), dtype=torch.bfloat16, device=q.device)
     _, _, ldo = _rows(out, "out")
     st = _prof_begin()
-    _check(lib().ce_attention_2seg_vt_bf16(_ptr(q), _ptr(k1), _ptr(v1t), len1, ldk1, v1t.stride(0), int(cols1), _ptr(k2), _ptr(v2t),
-                                           len2, ldk2, v2t.stride(0), int(cols2), _ptr(out), nq, heads, 128, ldq, ldo,
-                                           float(scale), batch, _stream()), "ce_attention_2seg_vt_bf16")
+    _launch("ce_attention_2seg_vt_bf16", _ptr(q), _ptr(k1), _ptr(v1t), len1, ldk1, v1t.stride(0), int(cols1), _ptr(k2), _ptr(v2t),
+            len2, ldk2, v2t.stride(0), int(cols2), _ptr(out), nq, heads, 128, ldq, ldo,
+            float(scale), batch, _stream())
     _prof_end(st, f"attention_{nq}x{len1}+{len2}_h{heads}" + (f"_b{batch}" if batch > 1 else ""), 4.0 * nq * (len1 + len2) * 128 * heads * batch)
     return out
 
@@ -488,10 +493,9 @@ def attention_2seg_vt_shared(q: torch.Tensor, k1: torch.Tensor, v1t: torch.Tenso
     if scale is None:
         scale = 128 ** -0.5
     st = _prof_begin()
-    _check(lib().ce_attention_2seg_vt_strided_bf16(_ptr(q), _ptr(k1), _ptr(v1t), len1, ldk1, v1t.stride(0), int(cols1), _ptr(k2), _ptr(v2t),
-                                                   len2, ldk2, v2t.stride(0), int(cols2), _ptr(out), nq, heads, 128, ldq, ldo, float(scale), batch,
-                                                   0 if share_q else nq, 0 if share1 else len1, 0 if share2 else len2, _stream()),
-           "ce_attention_2seg_vt_strided_bf16")
+    _launch("ce_attention_2seg_vt_strided_bf16", _ptr(q), _ptr(k1), _ptr(v1t), len1, ldk1, v1t.stride(0), int(cols1), _ptr(k2), _ptr(v2t),
+            len2, ldk2, v2t.stride(0), int(cols2), _ptr(out), nq, heads, 128, ldq, ldo, float(scale), batch,
+            0 if share_q else nq, 0 if share1 else len1, 0 if share2 else len2, _stream())
     tag = ("_sq" if share_q else "") + ("_s1" if share1 else "") + ("_s2" if share2 else "")
     _prof_end(st, f"attention_{nq}x{len1}+{len2}_h{heads}" + (f"_b{batch}" if batch > 1 else "") + tag, 4.0 * nq * (len1 + len2) * 128 * heads * batch)
     return out
@@ -525,10 +529,9 @@ def attention_2seg_vt_weighted(q: torch.Tensor, k1: torch.Tensor, v1t: torch.Ten
     if scale is None:
         scale = 128 ** -0.5
     st = _prof_begin()
-    _check(lib().ce_attention_2seg_vt_weighted_bf16(_ptr(q), _ptr(k1), _ptr(v1t), len1, ldk1, v1t.stride(0), int(cols1), _ptr(k2), _ptr(v2t),
-                                                    len2, ldk2, v2t.stride(0), int(cols2), _ptr(out), nq, heads, 128, ldq, ldo, float(scale), batch,
-                                                    0 if share_q else nq, len1, 0 if share2 else len2, _ptr(valid1), _ptr(w1), _stream()),
-           "ce_attention_2seg_vt_weighted_bf16")
+    _launch("ce_attention_2seg_vt_weighted_bf16", _ptr(q), _ptr(k1), _ptr(v1t), len1, ldk1, v1t.stride(0), int(cols1), _ptr(k2), _ptr(v2t),
+            len2, ldk2, v2t.stride(0), int(cols2), _ptr(out), nq, heads, 128, ldq, ldo, float(scale), batch,
+            0 if share_q else nq, len1, 0 if share2 else len2, _ptr(valid1), _ptr(w1), _stream())
     tag = ("_sq" if share_q else "") + ("_s2" if share2 else "") + "_w"
     _prof_end(st, f"attention_{nq}x{len1}+{len2}_h{heads}" + (f"_b{batch}" if batch > 1 else "") + tag, 4.0 * nq * (len1 + len2) * 128 * heads * batch)
     return out
@@ -545,8 +548,8 @@ def v_transpose_blocked(v: torch.Tensor, heads: int, batch: int, blk_rows: int, 
         out = torch.empty((D, batch * cols), dtype=torch.bfloat16, device=v.device)
     assert out.shape == (D, batch * cols) and out.is_contiguous()
     st = _prof_begin()
-    _check(lib().ce_v_transpose_blocked_bf16(_ptr(v), ldv, _ptr(out), out.shape[1], n_keys, heads, batch, blk_rows, batch * blk_rows, cols,
-                                             _stream()), "ce_v_transpose_blocked_bf16")
+    _launch("ce_v_transpose_blocked_bf16", _ptr(v), ldv, _ptr(out), out.shape[1], n_keys, heads, batch, blk_rows, batch * blk_rows, cols,
+            _stream())
     _prof_end(st, f"v_transpose_{batch * n_keys}x{D}", 4.0 * batch * n_keys * D)
     return out
 
@@ -568,8 +571,8 @@ def attention_vt_blocked(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, hea
     if scale is None:
         scale = 128 ** -0.5
     st = _prof_begin()
-    _check(lib().ce_attention_vt_blocked_bf16(_ptr(q), _ptr(k), _ptr(vt), n_keys, ldk, vt.stride(0), _ptr(out), nq, heads, 128, ldq, ldo,
-                                              float(scale), batch, blk_rows, batch * blk_rows, cols, _stream()), "ce_attention_vt_blocked_bf16")
+    _launch("ce_attention_vt_blocked_bf16", _ptr(q), _ptr(k), _ptr(vt), n_keys, ldk, vt.stride(0), _ptr(out), nq, heads, 128, ldq, ldo,
+            float(scale), batch, blk_rows, batch * blk_rows, cols, _stream())
     _prof_end(st, f"attention_{nq}x{n_keys}+0_h{heads}" + (f"_b{batch}" if batch > 1 else ""), 4.0 * nq * n_keys * 128 * heads * batch)
     return out
 
@@ -583,9 +586,9 @@ def timestep_sinusoid(t: torch.Tensor, dim: int, out: Optional[torch.Tensor] = N
     if out is None:
         out = torch.empty((dim,), dtype=torch.float32, device=t.device)
     if t.dtype == torch.float32:
-        _check(lib().ce_timestep_sinusoid_f32(_ptr(t), _ptr(out), dim, _stream()), "ce_timestep_sinusoid_f32")
+        _launch("ce_timestep_sinusoid_f32", _ptr(t), _ptr(out), dim, _stream())
     else:
-        _check(lib().ce_timestep_sinusoid(_ptr(t), _ptr(out), dim, _stream()), "ce_timestep_sinusoid")
+        _launch("ce_timestep_sinusoid", _ptr(t), _ptr(out), dim, _stream())
     return out
 
 
@@ -599,7 +602,7 @@ def gemv(w: torch.Tensor, x: torch.Tensor, bias: Optional[torch.Tensor], flags: 
         _dev(bias, torch.float32, "bias")
     if out is None:
         out = torch.empty((N,), dtype=torch.float32, device=x.device)
-    _check(lib().ce_gemv(_ptr(w), int(w.dtype == torch.bfloat16), _ptr(x), _ptr(bias), _ptr(out), N, K, flags, _stream()), "ce_gemv")
+    _launch("ce_gemv", _ptr(w), int(w.dtype == torch.bfloat16), _ptr(x), _ptr(bias), _ptr(out), N, K, flags, _stream())
     return out
 
 
@@ -611,7 +614,7 @@ def modulation(table: torch.Tensor, v: torch.Tensor, one_mask: int, out: Optiona
     assert table.is_contiguous() and v.is_contiguous() and v_rows in (1, J)
     if out is None:
         out = torch.empty_like(table)
-    _check(lib().ce_modulation(_ptr(table), _ptr(v), _ptr(out), L, J, D, v_rows, one_mask, _stream()), "ce_modulation")
+    _launch("ce_modulation", _ptr(table), _ptr(v), _ptr(out), L, J, D, v_rows, one_mask, _stream())
     return out
 
 
@@ -624,7 +627,7 @@ def patchify(x: torch.Tensor, kpad: int, out: Optional[torch.Tensor] = None, row
     if out is None:
         out = torch.empty((n, kpad), dtype=torch.bfloat16, device=x.device)
     assert out.is_contiguous() and out.shape == (n, kpad)
-    _check(lib().ce_patchify_rows_bf16(_ptr(x), _ptr(out), C, T, H, W, kpad, int(row0), n, _stream()), "ce_patchify_rows_bf16")
+    _launch("ce_patchify_rows_bf16", _ptr(x), _ptr(out), C, T, H, W, kpad, int(row0), n, _stream())
     return out
 
 
@@ -633,7 +636,7 @@ def unpatchify(y: torch.Tensor, cout: int, T: int, H: int, W: int, out: Optional
     _, _, ldy = _rows(y, "y")
     if out is None:
         out = torch.empty((cout, T, H, W), dtype=torch.bfloat16, device=y.device)
-    _check(lib().ce_unpatchify_bf16(_ptr(y), _ptr(out), cout, T, H, W, ldy, _stream()), "ce_unpatchify_bf16")
+    _launch("ce_unpatchify_bf16", _ptr(y), _ptr(out), cout, T, H, W, ldy, _stream())
     return out
 
 
@@ -652,8 +655,8 @@ def cfg_unipc_step(v_cond: torch.Tensor, v_uncond: Optional[torch.Tensor], x: to
     assert v_cond.is_contiguous() and coef.numel() >= 10
     n = x.numel()
     assert v_cond.numel() == n == x_last.numel() == m0.numel() == m1.numel()
-    _check(lib().ce_cfg_unipc_step(_ptr(v_cond), _ptr(v_uncond), _ptr(x), _ptr(x_last), _ptr(m0), _ptr(m1), _ptr(x0_out), _ptr(coef),
-                                   _ptr(None), n, int(round_sigma_v) | (2 if bf16_state else 0), _stream()), "ce_cfg_unipc_step")
+    _launch("ce_cfg_unipc_step", _ptr(v_cond), _ptr(v_uncond), _ptr(x), _ptr(x_last), _ptr(m0), _ptr(m1), _ptr(x0_out), _ptr(coef),
+            _ptr(None), n, int(round_sigma_v) | (2 if bf16_state else 0), _stream())
     return x
 
 
@@ -685,8 +688,8 @@ def cfg_unipc_step_delta(v_cond: torch.Tensor, v_uncond: Optional[torch.Tensor],
     if slot is None and table is None:
         if delta.numel() != n:
             raise ValueError(f"delta: need {n} elements, got shape {tuple(delta.shape)}")
-        _check(lib().ce_cfg_unipc_step_delta(_ptr(v_cond), _ptr(v_uncond), _ptr(x), _ptr(x_last), _ptr(m0), _ptr(m1), _ptr(x0_out), _ptr(coef),
-                                             _ptr(delta), n, flags, 0, 0, _ptr(None), 0, _ptr(None), 0, _stream()), "ce_cfg_unipc_step_delta")
+        _launch("ce_cfg_unipc_step_delta", _ptr(v_cond), _ptr(v_uncond), _ptr(x), _ptr(x_last), _ptr(m0), _ptr(m1), _ptr(x0_out), _ptr(coef),
+                _ptr(delta), n, flags, 0, 0, _ptr(None), 0, _ptr(None), 0, _stream())
         return x
     if v_uncond is None or slot is None or table is None:
         raise ValueError("measuring is an option of the store mode: it needs v_uncond, slot and table")
@@ -699,9 +702,8 @@ def cfg_unipc_step_delta(v_cond: torch.Tensor, v_uncond: Optional[torch.Tensor],
     if not 0 <= int(slot) < A:
         raise ValueError(f"slot {slot} is outside the ring of {A}")
     scratch = torch.empty((CFG_MAX_AGE + 1) * 2048, dtype=torch.float32, device=x.device)  # five sums per workgroup, at most 2048 of them
-    _check(lib().ce_cfg_unipc_step_delta(_ptr(v_cond), _ptr(v_uncond), _ptr(x), _ptr(x_last), _ptr(m0), _ptr(m1), _ptr(x0_out), _ptr(coef),
-                                         _ptr(delta), n, flags, A, int(slot), _ptr(scratch), scratch.numel() * 4, _ptr(table), int(row), _stream()),
-           "ce_cfg_unipc_step_delta")
+    _launch("ce_cfg_unipc_step_delta", _ptr(v_cond), _ptr(v_uncond), _ptr(x), _ptr(x_last), _ptr(m0), _ptr(m1), _ptr(x0_out), _ptr(coef),
+            _ptr(delta), n, flags, A, int(slot), _ptr(scratch), scratch.numel() * 4, _ptr(table), int(row), _stream())
     return x
 
 
@@ -717,7 +719,7 @@ def tea_rel_l1(rows: torch.Tensor, out: Optional[torch.Tensor] = None):
         out = torch.empty((S, 2), dtype=torch.float32, device=rows.device)
     _dev(out, torch.float32, "out")
     assert out.is_contiguous() and out.shape == (S, 2)
-    _check(lib().ce_tea_rel_l1_bf16(_ptr(rows), S, n, _ptr(out), _stream()), "ce_tea_rel_l1_bf16")
+    _launch("ce_tea_rel_l1_bf16", _ptr(rows), S, n, _ptr(out), _stream())
     return out
 
 
@@ -732,7 +734,7 @@ def tea_store_(x: torch.Tensor, r: torch.Tensor):
     """r <- bf16(x - r), in place: r enters as the tokens saved in front of the block stack and leaves as the stack's residual."""
     n = _tea_pair(x, r)
     st = _prof_begin()
-    _check(lib().ce_tea_store_bf16(_ptr(x), _ptr(r), n, _stream()), "ce_tea_store_bf16")
+    _launch("ce_tea_store_bf16", _ptr(x), _ptr(r), n, _stream())
     _prof_end(st, f"tea_store_{n}", 6.0 * n)
     return r
 
@@ -755,7 +757,7 @@ def tea_store_dist_(x: torch.Tensor, r: torch.Tensor, prev: torch.Tensor, sums: 
         raise ValueError("prev: the previous residual must not alias r or x (it is read after r has been written)")
     scratch = torch.empty(2 * 2048, dtype=torch.float32, device=x.device)  # one pair per workgroup, at most 2048 of them (csrc/ce_tea.hip)
     st = _prof_begin()
-    _check(lib().ce_tea_store_dist_bf16(_ptr(x), _ptr(r), _ptr(prev), _ptr(sums), _ptr(scratch), scratch.numel() * 4, n, _stream()), "ce_tea_store_dist_bf16")
+    _launch("ce_tea_store_dist_bf16", _ptr(x), _ptr(r), _ptr(prev), _ptr(sums), _ptr(scratch), scratch.numel() * 4, n, _stream())
     _prof_end(st, f"tea_store_dist_{n}", 8.0 * n)
     return r
 
@@ -764,7 +766,7 @@ def tea_apply_(x: torch.Tensor, r: torch.Tensor):
     """x <- bf16(x + r), in place: the cached residual added to the patch-embedded tokens of a skipped step."""
     n = _tea_pair(x, r)
     st = _prof_begin()
-    _check(lib().ce_tea_apply_bf16(_ptr(x), _ptr(r), n, _stream()), "ce_tea_apply_bf16")
+    _launch("ce_tea_apply_bf16", _ptr(x), _ptr(r), n, _stream())
     _prof_end(st, f"tea_apply_{n}", 6.0 * n)
     return x
 
@@ -788,7 +790,7 @@ def image_resample_u8(src: torch.Tensor, axis: int, coeff: torch.Tensor, bounds:
     _dev(out, torch.uint8, "out")
     assert out.is_contiguous() and tuple(out.shape) == shape and out.data_ptr() != src.data_ptr()
     st = _prof_begin()
-    _check(lib().ce_image_resample_u8(_ptr(src), _ptr(out), axis, H, W, n, _ptr(coeff), _ptr(bounds), ksize, _stream()), "ce_image_resample_u8")
+    _launch("ce_image_resample_u8", _ptr(src), _ptr(out), axis, H, W, n, _ptr(coeff), _ptr(bounds), ksize, _stream())
     _prof_end(st, f"image_resample_{'hv'[axis]}_{H}x{W}_{n}", float(src.numel() + out.numel()))
     return out
 
@@ -810,8 +812,7 @@ def image_u8_lut_planar(src: torch.Tensor, lut: torch.Tensor, out: torch.Tensor,
     if top < 0 or left < 0 or top + h > H or left + w > W:
         raise ValueError(f"the {h}x{w} crop at ({top}, {left}) does not lie inside the {H}x{W} source")
     st = _prof_begin()
-    _check(lib().ce_image_u8_lut_planar(_ptr(src), H, W, int(top), int(left), h, w, _ptr(lut), _ptr(out), int(lut.dtype == torch.float32), _stream()),
-           "ce_image_u8_lut_planar")
+    _launch("ce_image_u8_lut_planar", _ptr(src), H, W, int(top), int(left), h, w, _ptr(lut), _ptr(out), int(lut.dtype == torch.float32), _stream())
     _prof_end(st, f"image_lut_{h}x{w}", float(3 * h * w * (1 + out.element_size())))
     return out
 
@@ -829,7 +830,7 @@ def video_to_u8(video: torch.Tensor, out: Optional[torch.Tensor] = None):
     _dev(out, torch.uint8, "out")
     assert out.is_contiguous() and tuple(out.shape) == (B, F, H, W, 3)
     st = _prof_begin()
-    _check(lib().ce_video_to_u8(_ptr(video), _ptr(out), B, F, H, W, int(video.dtype == torch.float32), _stream()), "ce_video_to_u8")
+    _launch("ce_video_to_u8", _ptr(video), _ptr(out), B, F, H, W, int(video.dtype == torch.float32), _stream())
     _prof_end(st, f"video_to_u8_{B}x{F}x{H}x{W}", float(video.numel() * (video.element_size() + 1)))
     return out
 
@@ -846,7 +847,7 @@ def region_weights_u8(mask: torch.Tensor, out: Optional[torch.Tensor] = None):
     _dev(out, torch.float32, "out")
     assert out.is_contiguous() and out.numel() == (H // 8) * (W // 8)
     st = _prof_begin()
-    _check(lib().ce_region_weights_u8(_ptr(mask), _ptr(out), H, W, _stream()), "ce_region_weights_u8")
+    _launch("ce_region_weights_u8", _ptr(mask), _ptr(out), H, W, _stream())
     _prof_end(st, f"region_weights_{H}x{W}", float(mask.numel() + 4 * out.numel()))
     return out
 
@@ -865,8 +866,7 @@ def region_blend_(x: torch.Tensor, z_src: torch.Tensor, eps: torch.Tensor, w: to
     if w.dim() != 2 or x.dim() < 2 or tuple(x.shape[-2:]) != tuple(w.shape):
         raise ValueError(f"w: need [h, w] = the last two axes of x {tuple(x.shape)}, got {tuple(w.shape)}")
     st = _prof_begin()
-    _check(lib().ce_region_blend_f32(_ptr(x), _ptr(z_src), _ptr(eps), _ptr(w), _ptr(sigma_next), n, plane, 2 if bf16_state else 0, _stream()),
-           "ce_region_blend_f32")
+    _launch("ce_region_blend_f32", _ptr(x), _ptr(z_src), _ptr(eps), _ptr(w), _ptr(sigma_next), n, plane, 2 if bf16_state else 0, _stream())
     _prof_end(st, f"region_blend_{n}", 16.0 * n)
     return x
 
@@ -889,8 +889,7 @@ def region_composite(video: torch.Tensor, src: torch.Tensor, mask: torch.Tensor,
     _dev(out, torch.float32, "out")
     assert out.is_contiguous() and out.shape == video.shape and out.data_ptr() != video.data_ptr()
     st = _prof_begin()
-    _check(lib().ce_region_composite(_ptr(video), int(video.dtype == torch.bfloat16), _ptr(src), _ptr(mask), _ptr(out), B, F, H, W, _stream()),
-           "ce_region_composite")
+    _launch("ce_region_composite", _ptr(video), int(video.dtype == torch.bfloat16), _ptr(src), _ptr(mask), _ptr(out), B, F, H, W, _stream())
     _prof_end(st, f"region_composite_{B}x{F}x{H}x{W}", float(video.numel() * (video.element_size() + 4) + src.numel() * 2 + mask.numel()))
     return out
 
@@ -915,8 +914,7 @@ def focus_resample_l8(src: torch.Tensor, axis: int, coeff: torch.Tensor, bounds:
     _dev(out, torch.uint8, "out")
     assert out.is_contiguous() and tuple(out.shape) == shape and out.data_ptr() != src.data_ptr()
     st = _prof_begin()
-    _check(lib().ce_focus_resample_l8(_ptr(src), src.stride(0), _ptr(out), axis, H, W, n, _ptr(coeff), _ptr(bounds), ksize, _stream()),
-           "ce_focus_resample_l8")
+    _launch("ce_focus_resample_l8", _ptr(src), src.stride(0), _ptr(out), axis, H, W, n, _ptr(coeff), _ptr(bounds), ksize, _stream())
     _prof_end(st, f"focus_resample_{'hv'[axis]}_{H}x{W}_{n}", float(src.numel() + out.numel()))
     return out
 
@@ -942,7 +940,7 @@ def focus_paste_u8(edit: torch.Tensor, src: torch.Tensor, mask: Optional[torch.T
     _dev(out, torch.uint8, "out")
     assert out.is_contiguous() and tuple(out.shape) == (F, SH, SW, 3) and out.data_ptr() not in (edit.data_ptr(), src.data_ptr())
     st = _prof_begin()
-    _check(lib().ce_focus_paste_u8(_ptr(edit), _ptr(src), _ptr(mask), _ptr(out), F, SH, SW, int(left), int(top), bw, bh, _stream()), "ce_focus_paste_u8")
+    _launch("ce_focus_paste_u8", _ptr(edit), _ptr(src), _ptr(mask), _ptr(out), F, SH, SW, int(left), int(top), bw, bh, _stream())
     _prof_end(st, f"focus_paste_{F}x{SH}x{SW}", float(out.numel() + src.numel() + edit.numel()))
     return out
 
@@ -961,7 +959,7 @@ def autofocus_bbox_u8(mask: torch.Tensor, out: Optional[torch.Tensor] = None):
     assert out.is_contiguous() and out.numel() == 5
     H, W = mask.shape
     st = _prof_begin()
-    _check(lib().ce_autofocus_bbox_u8(_ptr(mask), mask.stride(0), H, W, _ptr(out), _stream()), "ce_autofocus_bbox_u8")
+    _launch("ce_autofocus_bbox_u8", _ptr(mask), mask.stride(0), H, W, _ptr(out), _stream())
     _prof_end(st, f"autofocus_bbox_{H}x{W}", float(mask.numel()))
     return out
 
@@ -985,8 +983,8 @@ def autofocus_restart(x0: torch.Tensor, eps: torch.Tensor, tables, s: float, bf1
     _f32c(out, "out")
     assert out.shape == x0.shape and out.data_ptr() != x0.data_ptr()
     st = _prof_begin()
-    _check(lib().ce_autofocus_restart_f32(_ptr(x0), _ptr(eps), _ptr(out), _ptr(ix0), _ptr(ix1), _ptr(fx), _ptr(iy0), _ptr(iy1), _ptr(fy), float(s),
-                                          x0.numel() // (h * w), h, w, int(bool(bf16_state)), _stream()), "ce_autofocus_restart_f32")
+    _launch("ce_autofocus_restart_f32", _ptr(x0), _ptr(eps), _ptr(out), _ptr(ix0), _ptr(ix1), _ptr(fx), _ptr(iy0), _ptr(iy1), _ptr(fy), float(s),
+            x0.numel() // (h * w), h, w, int(bool(bf16_state)), _stream())
     _prof_end(st, f"autofocus_restart_{x0.numel()}", 12.0 * x0.numel())
     return out
 
@@ -1015,7 +1013,7 @@ def sketch_changed_u8(background: torch.Tensor, composite: torch.Tensor, thresho
     _plane(out, "out")
     assert tuple(out.shape) == (SH, SW) and out.data_ptr() not in (background.data_ptr(), composite.data_ptr())
     st = _prof_begin()
-    _check(lib().ce_sketch_changed_u8(_ptr(background), _ptr(composite), _ptr(out), SH * SW, int(threshold), _stream()), "ce_sketch_changed_u8")
+    _launch("ce_sketch_changed_u8", _ptr(background), _ptr(composite), _ptr(out), SH * SW, int(threshold), _stream())
     _prof_end(st, f"sketch_changed_{SH}x{SW}", 7.0 * SH * SW)
     return out
 
@@ -1042,8 +1040,7 @@ def _sketch_filter(fn_name: str, src: torch.Tensor, axis: int, radius: int, out:
         _dev(scratch, torch.uint8, "scratch")
         assert scratch.is_contiguous()
     st = _prof_begin()
-    _check(getattr(lib(), fn_name)(_ptr(src), _ptr(out), H, W, int(axis), int(radius), _ptr(scratch), 0 if scratch is None else scratch.numel(),
-                                   _stream()), fn_name)
+    _launch(fn_name, _ptr(src), _ptr(out), H, W, int(axis), int(radius), _ptr(scratch), 0 if scratch is None else scratch.numel(), _stream())
     _prof_end(st, f"{fn_name[3:-3]}_{'hv'[axis]}_{H}x{W}_r{int(radius)}", 2.0 * src.numel())
     return out
 
@@ -1084,7 +1081,7 @@ def components_roots_i32(plane: torch.Tensor, out: Optional[torch.Tensor] = None
         out = torch.empty((H, W), dtype=torch.int32, device=plane.device)
     _iplane(out, "out", (H, W))
     st = _prof_begin()
-    _check(lib().ce_components_roots_i32(_ptr(plane), _ptr(out), H, W, _stream()), "ce_components_roots_i32")
+    _launch("ce_components_roots_i32", _ptr(plane), _ptr(out), H, W, _stream())
     _prof_end(st, f"components_roots_{H}x{W}", 13.0 * H * W)
     return out
 
@@ -1105,7 +1102,7 @@ def components_sums_i32(roots: torch.Tensor, weight: Optional[torch.Tensor] = No
     _iplane(out, "out", (H, W))
     assert out.data_ptr() != roots.data_ptr()
     st = _prof_begin()
-    _check(lib().ce_components_sums_i32(_ptr(roots), _ptr(weight), _ptr(out), H, W, _stream()), "ce_components_sums_i32")
+    _launch("ce_components_sums_i32", _ptr(roots), _ptr(weight), _ptr(out), H, W, _stream())
     _prof_end(st, f"components_sums_{H}x{W}", 9.0 * H * W)
     return out
 
@@ -1127,8 +1124,8 @@ def components_keep_u8(plane: torch.Tensor, roots: torch.Tensor, sums: torch.Ten
     if not ((den == 0 and min_weight >= 1) or (0 < num < den <= 65536)):
         raise ValueError(f"need min_weight >= 1, or a fraction 0 < num / den < 1 with den <= 65536, got {min_weight}, {num} / {den}")
     st = _prof_begin()
-    _check(lib().ce_components_keep_u8(_ptr(plane), _ptr(roots), _ptr(sums), _ptr(out), _ptr(counters), int(min_weight), int(num), int(den), H, W,
-                                       _stream()), "ce_components_keep_u8")
+    _launch("ce_components_keep_u8", _ptr(plane), _ptr(roots), _ptr(sums), _ptr(out), _ptr(counters), int(min_weight), int(num), int(den), H, W,
+            _stream())
     _prof_end(st, f"components_keep_{H}x{W}", 14.0 * H * W)
     return out, counters
 
@@ -1142,7 +1139,7 @@ def components_seeds(d: torch.Tensor, thr: torch.Tensor, out: Optional[torch.Ten
         out = torch.empty(tuple(d.shape), dtype=torch.uint8, device=d.device)
     _plane(out, "out")
     assert out.shape == d.shape
-    _check(lib().ce_components_seeds_f32(_ptr(d), _ptr(thr), _ptr(out), d.numel(), _stream()), "ce_components_seeds_f32")
+    _launch("ce_components_seeds_f32", _ptr(d), _ptr(thr), _ptr(out), d.numel(), _stream())
     return out
 
 
@@ -1155,7 +1152,7 @@ def components_masked(d: torch.Tensor, kept: torch.Tensor, out: Optional[torch.T
         out = torch.empty_like(d)
     _f32c(out, "out")
     assert out.shape == d.shape and out.data_ptr() != d.data_ptr()
-    _check(lib().ce_components_masked_f32(_ptr(d), _ptr(kept), _ptr(out), d.numel(), _stream()), "ce_components_masked_f32")
+    _launch("ce_components_masked_f32", _ptr(d), _ptr(kept), _ptr(out), d.numel(), _stream())
     return out
 
 
@@ -1182,8 +1179,7 @@ def clusters_table_i32(roots: torch.Tensor, sums: torch.Tensor, kept: torch.Tens
         counters = torch.empty(1 + CLUSTERS_ROWS, dtype=torch.int32, device=roots.device)
     _iplane(table, "table", (CLUSTERS_ROWS, 8)), _iplane(counters, "counters", (1 + CLUSTERS_ROWS,))
     st = _prof_begin()
-    _check(lib().ce_clusters_table_i32(_ptr(roots), _ptr(sums), _ptr(kept), _ptr(table), _ptr(counters), CLUSTERS_ROWS, H, W, _stream()),
-           "ce_clusters_table_i32")
+    _launch("ce_clusters_table_i32", _ptr(roots), _ptr(sums), _ptr(kept), _ptr(table), _ptr(counters), CLUSTERS_ROWS, H, W, _stream())
     _prof_end(st, f"clusters_table_{H}x{W}", 10.0 * H * W)
     return table, counters
 
@@ -1206,8 +1202,7 @@ def clusters_select_u8(roots: torch.Tensor, kept: torch.Tensor, table: torch.Ten
     _plane(out, "out")
     assert tuple(out.shape) == (H, W) and out.data_ptr() != kept.data_ptr()
     st = _prof_begin()
-    _check(lib().ce_clusters_select_u8(_ptr(roots), _ptr(kept), _ptr(table), _ptr(group_of_row), int(g), _ptr(out), H, W, _stream()),
-           "ce_clusters_select_u8")
+    _launch("ce_clusters_select_u8", _ptr(roots), _ptr(kept), _ptr(table), _ptr(group_of_row), int(g), _ptr(out), H, W, _stream())
     _prof_end(st, f"clusters_select_{H}x{W}", 6.0 * H * W)
     return out
 
@@ -1230,7 +1225,7 @@ def clusters_paste_u8(edit: torch.Tensor, mask: Optional[torch.Tensor], canvas: 
         raise ValueError(f"the {bw}x{bh} box at ({left}, {top}) does not lie inside the {SW}x{SH} canvas")
     assert canvas.data_ptr() != edit.data_ptr()
     st = _prof_begin()
-    _check(lib().ce_clusters_paste_u8(_ptr(edit), _ptr(mask), _ptr(canvas), F, SH, SW, int(left), int(top), bw, bh, _stream()), "ce_clusters_paste_u8")
+    _launch("ce_clusters_paste_u8", _ptr(edit), _ptr(mask), _ptr(canvas), F, SH, SW, int(left), int(top), bw, bh, _stream())
     _prof_end(st, f"clusters_paste_{F}x{bh}x{bw}", 7.0 * F * bh * bw)
     return canvas
 
@@ -1255,7 +1250,7 @@ def layers_strokes_u8(layer: torch.Tensor, left: int, top: int, plane: torch.Ten
     if isinstance(threshold, bool) or not 0 <= int(threshold) <= 254:
         raise ValueError(f"threshold: an int in 0..254, got {threshold!r}")
     st = _prof_begin()
-    _check(lib().ce_layers_strokes_u8(_ptr(layer), bw, bh, int(left), int(top), _ptr(plane), SW, SH, int(threshold), _stream()), "ce_layers_strokes_u8")
+    _launch("ce_layers_strokes_u8", _ptr(layer), bw, bh, int(left), int(top), _ptr(plane), SW, SH, int(threshold), _stream())
     _prof_end(st, f"layers_strokes_{bh}x{bw}", 5.0 * bh * bw)
     return plane
 
@@ -1269,7 +1264,7 @@ def layers_over_u8(layer: torch.Tensor, left: int, top: int, canvas: torch.Tenso
     SH, SW, _ = canvas.shape
     bw, bh = _layer_box(layer, left, top, SW, SH)
     st = _prof_begin()
-    _check(lib().ce_layers_over_u8(_ptr(layer), bw, bh, int(left), int(top), _ptr(canvas), SW, SH, _stream()), "ce_layers_over_u8")
+    _launch("ce_layers_over_u8", _ptr(layer), bw, bh, int(left), int(top), _ptr(canvas), SW, SH, _stream())
     _prof_end(st, f"layers_over_{bh}x{bw}", 10.0 * bh * bw)
     return canvas
 
@@ -1296,7 +1291,7 @@ def auto_region_change(x0: torch.Tensor, z_src: torch.Tensor, frame: int = -1, o
     _f32c(out, "out")
     assert out.numel() == h * w
     st = _prof_begin()
-    _check(lib().ce_auto_region_change_f32(_ptr(x0), _ptr(z_src), _ptr(out), B, C, T, h, w, f, _stream()), "ce_auto_region_change_f32")
+    _launch("ce_auto_region_change_f32", _ptr(x0), _ptr(z_src), _ptr(out), B, C, T, h, w, f, _stream())
     _prof_end(st, f"auto_region_change_{B}x{C}x{h}x{w}", float(8 * B * C * h * w + 4 * h * w))
     return out
 
@@ -1312,7 +1307,7 @@ def auto_region_otsu(d: torch.Tensor, floor: float = 0.0, thr: Optional[torch.Te
     _f32c(thr, "thr"), _f32c(dmax, "dmax")
     assert thr.numel() == 1 and dmax.numel() == 1
     st = _prof_begin()
-    _check(lib().ce_auto_region_otsu_f32(_ptr(d), d.numel(), float(floor), _ptr(thr), _ptr(dmax), _stream()), "ce_auto_region_otsu_f32")
+    _launch("ce_auto_region_otsu_f32", _ptr(d), d.numel(), float(floor), _ptr(thr), _ptr(dmax), _stream())
     _prof_end(st, f"auto_region_otsu_{d.numel()}", float(8 * d.numel()))
     return thr, dmax
 
@@ -1330,8 +1325,7 @@ def auto_region_ramp(d: torch.Tensor, thr: torch.Tensor, dilate: int, feather: i
     _f32c(out, "out")
     assert out.numel() == d.numel() and out.data_ptr() != d.data_ptr()
     st = _prof_begin()
-    _check(lib().ce_auto_region_ramp_f32(_ptr(d), _ptr(thr), _ptr(out), d.shape[0], d.shape[1], int(dilate), int(feather), _stream()),
-           "ce_auto_region_ramp_f32")
+    _launch("ce_auto_region_ramp_f32", _ptr(d), _ptr(thr), _ptr(out), d.shape[0], d.shape[1], int(dilate), int(feather), _stream())
     _prof_end(st, f"auto_region_ramp_{d.shape[0]}x{d.shape[1]}_r{dilate + feather}", float(8 * d.numel()))
     return out
 
@@ -1347,7 +1341,7 @@ def auto_region_mask_u8(w: torch.Tensor, out: Optional[torch.Tensor] = None):
     _dev(out, torch.uint8, "out")
     assert out.is_contiguous() and out.numel() == 64 * h * wl
     st = _prof_begin()
-    _check(lib().ce_auto_region_mask_u8(_ptr(w), _ptr(out), h, wl, _stream()), "ce_auto_region_mask_u8")
+    _launch("ce_auto_region_mask_u8", _ptr(w), _ptr(out), h, wl, _stream())
     _prof_end(st, f"auto_region_mask_{h}x{wl}", float(4 * w.numel() + out.numel()))
     return out
 
@@ -1385,7 +1379,7 @@ def preview_rgb_u8(x0: torch.Tensor, factors: torch.Tensor, scale: int = 2, fram
     _dev(out, torch.uint8, "out")
     assert out.is_contiguous() and out.numel() == B * h * s * wl * s * 3
     st = _prof_begin()
-    _check(lib().ce_preview_rgb_u8(_ptr(x0), _ptr(z_src), _ptr(w), _ptr(factors), _ptr(out), B, C, T, f, h, wl, s, _stream()), "ce_preview_rgb_u8")
+    _launch("ce_preview_rgb_u8", _ptr(x0), _ptr(z_src), _ptr(w), _ptr(factors), _ptr(out), B, C, T, f, h, wl, s, _stream())
     _prof_end(st, f"preview_rgb_{B}x{h}x{wl}_s{s}", float((1 if w is None else 2) * 64 * B * h * wl + out.numel()))
     return out
 
@@ -1413,8 +1407,8 @@ def preview_gram(z: torch.Tensor, y: torch.Tensor, frame: int = -1, out: Optiona
         scratch = torch.empty(PREVIEW_GRAM_SCRATCH, dtype=torch.uint8, device=z.device)
     _dev(scratch, torch.uint8, "scratch")
     st = _prof_begin()
-    _check(lib().ce_preview_gram_f64(_ptr(z), f, _ptr(y), int(y.dtype == torch.bfloat16), _ptr(out), _ptr(scratch), scratch.numel(), B, T, h, wl,
-                                     _stream()), "ce_preview_gram_f64")
+    _launch("ce_preview_gram_f64", _ptr(z), f, _ptr(y), int(y.dtype == torch.bfloat16), _ptr(out), _ptr(scratch), scratch.numel(), B, T, h, wl,
+            _stream())
     _prof_end(st, f"preview_gram_{B}x{h}x{wl}", float(64 * B * h * wl + y.numel() * y.element_size()))
     return out
 
@@ -1440,7 +1434,7 @@ def lift_fit_q16(L: torch.Tensor, E: torch.Tensor, radius: int, eps_q: int, max_
     _dev(out, torch.int32, "out")
     assert out.is_contiguous() and tuple(out.shape) == (F, H, W, 6)
     st = _prof_begin()
-    _check(lib().ce_lift_fit_q16(_ptr(L), _ptr(E), _ptr(out), F, H, W, int(radius), int(eps_q), float(max_gain), _stream()), "ce_lift_fit_q16")
+    _launch("ce_lift_fit_q16", _ptr(L), _ptr(E), _ptr(out), F, H, W, int(radius), int(eps_q), float(max_gain), _stream())
     _prof_end(st, f"lift_fit_{F}x{H}x{W}_r{radius}", float(L.numel() + E.numel() + 4 * out.numel()))
     return out
 
@@ -1459,7 +1453,7 @@ def lift_smooth(L: torch.Tensor, E: torch.Tensor, AB: torch.Tensor, radius: int,
     _dev(coef, torch.float32, "coef"), _dev(R, torch.int32, "R")
     assert coef.is_contiguous() and tuple(coef.shape) == (F, H, W, LIFT_CELL) and R.is_contiguous() and tuple(R.shape) == (F, H, W)
     st = _prof_begin()
-    _check(lib().ce_lift_smooth_f32(_ptr(L), _ptr(E), _ptr(AB), _ptr(coef), _ptr(R), F, H, W, int(radius), _stream()), "ce_lift_smooth_f32")
+    _launch("ce_lift_smooth_f32", _ptr(L), _ptr(E), _ptr(AB), _ptr(coef), _ptr(R), F, H, W, int(radius), _stream())
     _prof_end(st, f"lift_smooth_{F}x{H}x{W}_r{radius}", float(4 * (AB.numel() + coef.numel() + R.numel())))
     return coef, R
 
@@ -1471,7 +1465,7 @@ def lift_gate(R: torch.Tensor, coef: torch.Tensor, radius: int, t0: float, t1: f
         raise ValueError(f"R / coef: need contiguous [F, H, W] and [F, H, W, 8], got {tuple(R.shape)} and {tuple(coef.shape)}")
     F, H, W = R.shape
     st = _prof_begin()
-    _check(lib().ce_lift_gate_f32(_ptr(R), _ptr(coef), F, H, W, int(radius), float(t0), float(t1), _stream()), "ce_lift_gate_f32")
+    _launch("ce_lift_gate_f32", _ptr(R), _ptr(coef), F, H, W, int(radius), float(t0), float(t1), _stream())
     _prof_end(st, f"lift_gate_{F}x{H}x{W}_r{radius}", float(8 * R.numel()))
     return coef
 
@@ -1501,8 +1495,8 @@ def lift_apply_u8(P: torch.Tensor, coef: torch.Tensor, tables, U: Optional[torch
     _dev(out, torch.uint8, "out")
     assert out.is_contiguous() and tuple(out.shape) == (F, SH, SW, 3) and not _overlap(out, P) and (U is None or not _overlap(out, U))
     st = _prof_begin()
-    _check(lib().ce_lift_apply_u8(_ptr(P), _ptr(U), _ptr(coef), _ptr(ix0), _ptr(ix1), _ptr(tx), _ptr(iy0), _ptr(iy1), _ptr(ty), _ptr(out),
-                                  F, SH, SW, H, W, _stream()), "ce_lift_apply_u8")
+    _launch("ce_lift_apply_u8", _ptr(P), _ptr(U), _ptr(coef), _ptr(ix0), _ptr(ix1), _ptr(tx), _ptr(iy0), _ptr(iy1), _ptr(ty), _ptr(out),
+            F, SH, SW, H, W, _stream())
     _prof_end(st, f"lift_apply_{F}x{SH}x{SW}", float(out.numel() + P.numel() + (0 if U is None else U.numel())))
     return out
 
@@ -1541,8 +1535,8 @@ def boxlift_apply_paste_u8(P: torch.Tensor, coef: torch.Tensor, tables, U: Optio
             raise ValueError(f"mask: need a contiguous [{SH}, {SW}] tensor, got shape {tuple(mask.shape)} stride {mask.stride()}")
     assert not _overlap(canvas, P) and (U is None or not _overlap(canvas, U)) and (mask is None or not _overlap(canvas, mask))
     st = _prof_begin()
-    _check(lib().ce_boxlift_apply_paste_u8(_ptr(P), _ptr(U), _ptr(coef), _ptr(ix0), _ptr(ix1), _ptr(tx), _ptr(iy0), _ptr(iy1), _ptr(ty), _ptr(mask),
-                                           _ptr(canvas), F, SH, SW, left, top, bw, bh, H, W, _stream()), "ce_boxlift_apply_paste_u8")
+    _launch("ce_boxlift_apply_paste_u8", _ptr(P), _ptr(U), _ptr(coef), _ptr(ix0), _ptr(ix1), _ptr(tx), _ptr(iy0), _ptr(iy1), _ptr(ty), _ptr(mask),
+            _ptr(canvas), F, SH, SW, left, top, bw, bh, H, W, _stream())
     _prof_end(st, f"boxlift_apply_paste_{F}x{bh}x{bw}", float(F * bh * bw * (9 if U is not None else 6) + bh * bw * 4))
     return canvas
 
@@ -1566,8 +1560,7 @@ def rimlift_fit_q16(L: torch.Tensor, E: torch.Tensor, M: torch.Tensor, radius: i
     _dev(out, torch.int32, "out")
     assert out.is_contiguous() and tuple(out.shape) == (F, H, W, 6)
     st = _prof_begin()
-    _check(lib().ce_rimlift_fit_q16(_ptr(L), _ptr(E), _ptr(M), _ptr(out), F, H, W, int(radius), int(eps_q), float(max_gain), _stream()),
-           "ce_rimlift_fit_q16")
+    _launch("ce_rimlift_fit_q16", _ptr(L), _ptr(E), _ptr(M), _ptr(out), F, H, W, int(radius), int(eps_q), float(max_gain), _stream())
     _prof_end(st, f"rimlift_fit_{F}x{H}x{W}_r{radius}", float(L.numel() + E.numel() + F * M.numel() + 4 * out.numel()))
     return out
 
@@ -1587,8 +1580,7 @@ def rimlift_smooth(L: torch.Tensor, E: torch.Tensor, M: torch.Tensor, AB: torch.
     _dev(coef, torch.float32, "coef"), _dev(R, torch.int32, "R")
     assert coef.is_contiguous() and tuple(coef.shape) == (F, H, W, LIFT_CELL) and R.is_contiguous() and tuple(R.shape) == (F, H, W)
     st = _prof_begin()
-    _check(lib().ce_rimlift_smooth_f32(_ptr(L), _ptr(E), _ptr(M), _ptr(AB), _ptr(coef), _ptr(R), F, H, W, int(radius), _stream()),
-           "ce_rimlift_smooth_f32")
+    _launch("ce_rimlift_smooth_f32", _ptr(L), _ptr(E), _ptr(M), _ptr(AB), _ptr(coef), _ptr(R), F, H, W, int(radius), _stream())
     _prof_end(st, f"rimlift_smooth_{F}x{H}x{W}_r{radius}", float(4 * (AB.numel() + coef.numel() + R.numel()) + F * M.numel()))
     return coef, R
 
@@ -1617,7 +1609,7 @@ def sparse_patchify(x: torch.Tensor, ids: torch.Tensor, kpad: int, out: Optional
     _dev(out, torch.bfloat16, "out")
     assert out.is_contiguous() and out.shape == (na, kpad)
     st = _prof_begin()
-    _check(lib().ce_sparse_patchify_bf16(_ptr(x), _ptr(ids), i64, _ptr(out), C, T, H, W, kpad, na, _stream()), "ce_sparse_patchify_bf16")
+    _launch("ce_sparse_patchify_bf16", _ptr(x), _ptr(ids), i64, _ptr(out), C, T, H, W, kpad, na, _stream())
     _prof_end(st, f"sparse_patchify_{na}x{kpad}", 4.0 * na * kpad)
     return out
 
@@ -1631,8 +1623,7 @@ def sparse_scatter_rows_(dst: torch.Tensor, src: torch.Tensor, ids: torch.Tensor
     if batch < 1 or Ds != D or Ms != batch * na or Md % batch or na > Md // batch:
         raise ValueError(f"sparse_scatter_rows_: src {tuple(src.shape)} / dst {tuple(dst.shape)} do not fit {na} ids and batch={batch}")
     st = _prof_begin()
-    _check(lib().ce_sparse_scatter_rows_bf16(_ptr(src), lds, _ptr(dst), ldd, _ptr(ids), i64, na, Md // batch, batch, D, _stream()),
-           "ce_sparse_scatter_rows_bf16")
+    _launch("ce_sparse_scatter_rows_bf16", _ptr(src), lds, _ptr(dst), ldd, _ptr(ids), i64, na, Md // batch, batch, D, _stream())
     _prof_end(st, f"sparse_scatter_rows_{Ms}x{D}", 4.0 * Ms * D)
     return dst
 
@@ -1649,8 +1640,8 @@ def sparse_scatter_vt_(vt: torch.Tensor, src: torch.Tensor, ids: torch.Tensor, n
         raise ValueError(f"sparse_scatter_vt_: src {tuple(src.shape)} (expected {want}) / vt {tuple(vt.shape)} do not fit {na} ids of "
                          f"{n_tokens} tokens and batch={batch}")
     st = _prof_begin()
-    _check(lib().ce_sparse_scatter_vt_bf16(_ptr(src), lds, int(bool(src_rows)), _ptr(vt), ldvt, _ptr(ids), i64, na, int(n_tokens), batch, D,
-                                           _stream()), "ce_sparse_scatter_vt_bf16")
+    _launch("ce_sparse_scatter_vt_bf16", _ptr(src), lds, int(bool(src_rows)), _ptr(vt), ldvt, _ptr(ids), i64, na, int(n_tokens), batch, D,
+            _stream())
     _prof_end(st, f"sparse_scatter_vt_{batch * na}x{D}" + ("_rows" if src_rows else ""), 4.0 * batch * na * D)
     return vt
 
@@ -1663,7 +1654,7 @@ def sparse_unpatchify_(out: torch.Tensor, y: torch.Tensor, ids: torch.Tensor):
     assert out.is_contiguous() and out.dim() == 4 and Ms == na, (out.shape, y.shape, na)
     cout, T, H, W = out.shape
     st = _prof_begin()
-    _check(lib().ce_sparse_unpatchify_bf16(_ptr(y), ldy, _ptr(ids), i64, _ptr(out), cout, T, H, W, na, _stream()), "ce_sparse_unpatchify_bf16")
+    _launch("ce_sparse_unpatchify_bf16", _ptr(y), ldy, _ptr(ids), i64, _ptr(out), cout, T, H, W, na, _stream())
     _prof_end(st, f"sparse_unpatchify_{na}x{4 * cout}", 16.0 * na * cout)
     return out
 
@@ -1682,8 +1673,8 @@ def conv3d_gemm(in_stack: torch.Tensor, weight: torch.Tensor, bias: Optional[tor
         _dev(res_stack, torch.bfloat16, "res_stack")
         assert res_stack.is_contiguous() and res_stack.shape[1:] == out_stack.shape[1:] and res_stack.shape[0] >= T_out
     st_ev = _prof_begin()
-    _check(lib().ce_conv3d_gemm_bf16(_ptr(in_stack), _ptr(weight), weight.shape[1], _ptr(bias), _ptr(out_stack), _ptr(res_stack), T_out, H, W,
-                                     Cin, Cout, KT, out_stack.shape[3], n_tile, _stream()), "ce_conv3d_gemm_bf16")
+    _launch("ce_conv3d_gemm_bf16", _ptr(in_stack), _ptr(weight), weight.shape[1], _ptr(bias), _ptr(out_stack), _ptr(res_stack), T_out, H, W,
+            Cin, Cout, KT, out_stack.shape[3], n_tile, _stream())
     _prof_end(st_ev, f"conv_{KT}x3x3_{Cin}->{Cout}_{T_out}x{H}x{W}", 2.0 * T_out * H * W * Cout * Cin * KT * 9)
 
 
@@ -1706,9 +1697,8 @@ def conv3d_gemm_rms_silu(in_stack: torch.Tensor, weight: torch.Tensor, bias: Opt
             assert t.is_contiguous() and t.shape[1:] == normed_stack.shape[1:] and t.shape[0] >= T_out, (nm, t.shape)
     assert res_stack is None or out_stack is not None
     st_ev = _prof_begin()
-    _check(lib().ce_conv3d_gemm_rms_silu_bf16(_ptr(in_stack), _ptr(weight), weight.shape[1], _ptr(bias), _ptr(out_stack), _ptr(res_stack), _ptr(normed_stack),
-                                              T_out, H, W, Cin, Cout, KT, normed_stack.shape[3], _ptr(gamma), int(bool(silu)), _stream()),
-           "ce_conv3d_gemm_rms_silu_bf16")
+    _launch("ce_conv3d_gemm_rms_silu_bf16", _ptr(in_stack), _ptr(weight), weight.shape[1], _ptr(bias), _ptr(out_stack), _ptr(res_stack), _ptr(normed_stack),
+            T_out, H, W, Cin, Cout, KT, normed_stack.shape[3], _ptr(gamma), int(bool(silu)), _stream())
     _prof_end(st_ev, f"conv_{KT}x3x3_{Cin}->{Cout}_{T_out}x{H}x{W}+norm", 2.0 * T_out * H * W * Cout * Cin * KT * 9)
 
 
@@ -1730,9 +1720,9 @@ def conv_igemm(in_frames, weight: torch.Tensor, bias: Optional[torch.Tensor], ou
     ia, oa = _ptr_array(in_frames), _ptr_array(out_frames)
     ra = _ptr_array(res_frames) if res_frames else None
     st_ev = _prof_begin()
-    _check(lib().ce_conv_igemm_bf16(ia, len(in_frames), _ptr(weight), _ptr(bias), oa, len(out_frames), ra, Cin, Cout, KT, KH, KW,
-                                    st, ss, H_out, W_out, in_Wp, in_off, in_off, out_Wp, out_border, out_cstride, out_coff,
-                                    _stream()), "ce_conv_igemm_bf16")
+    _launch("ce_conv_igemm_bf16", ia, len(in_frames), _ptr(weight), _ptr(bias), oa, len(out_frames), ra, Cin, Cout, KT, KH, KW,
+            st, ss, H_out, W_out, in_Wp, in_off, in_off, out_Wp, out_border, out_cstride, out_coff,
+            _stream())
     _prof_end(st_ev, f"conv_{KT}x{KH}x{KW}_{Cin}->{Cout}_{len(out_frames)}x{H_out}x{W_out}",
               2.0 * len(out_frames) * H_out * W_out * Cout * Cin * KT * KH * KW)
 
@@ -1746,8 +1736,8 @@ def conv3d_head(in_frames, weight: torch.Tensor, bias: Optional[torch.Tensor], o
     assert weight.is_contiguous() and weight.numel() >= Cout * KT * 9 * Cin
     ia, oa = _ptr_array(in_frames), _ptr_array(out_frames)
     st_ev = _prof_begin()
-    _check(lib().ce_conv3d_head_bf16(ia, len(in_frames), _ptr(weight), _ptr(bias), oa, len(out_frames), Cin, Cout, KT, H_out, W_out, in_Wp,
-                                     out_Wp, out_border, out_cstride, out_coff, _stream()), "ce_conv3d_head_bf16")
+    _launch("ce_conv3d_head_bf16", ia, len(in_frames), _ptr(weight), _ptr(bias), oa, len(out_frames), Cin, Cout, KT, H_out, W_out, in_Wp,
+            out_Wp, out_border, out_cstride, out_coff, _stream())
     _prof_end(st_ev, f"conv_head_{KT}x3x3_{Cin}->{Cout}_{len(out_frames)}x{H_out}x{W_out}", 2.0 * len(out_frames) * H_out * W_out * Cout * Cin * KT * 9)
 
 
@@ -1755,8 +1745,7 @@ def rms_silu(x: torch.Tensor, gamma: torch.Tensor, out: torch.Tensor, T: int, C:
              out_border: int, silu: bool = True):
     _dev(x, torch.bfloat16, "x"), _dev(out, torch.bfloat16, "out"), _dev(gamma, torch.float32, "gamma")
     st = _prof_begin()
-    _check(lib().ce_rms_silu_bf16(_ptr(x), _ptr(out), _ptr(gamma), T * H * W, C, H, W, in_border, out_border, int(silu), _stream()),
-           "ce_rms_silu_bf16")
+    _launch("ce_rms_silu_bf16", _ptr(x), _ptr(out), _ptr(gamma), T * H * W, C, H, W, in_border, out_border, int(silu), _stream())
     _prof_end(st, f"rms_silu_{C}ch_{T}x{H}x{W}", 4.0 * T * H * W * C)  # (work: bytes read + written, bf16)
     return out
 
@@ -1766,7 +1755,7 @@ def zero_border(frames: torch.Tensor, T: int, H: int, W: int, C: int):
     _dev(frames, torch.bfloat16, "frames")
     assert frames.is_contiguous() and tuple(frames.shape[:3]) == (T, H + 2, W + 2)
     st = _prof_begin()
-    _check(lib().ce_zero_border_bf16(_ptr(frames), T, H, W, C, frames.shape[3], _stream()), "ce_zero_border_bf16")
+    _launch("ce_zero_border_bf16", _ptr(frames), T, H, W, C, frames.shape[3], _stream())
     _prof_end(st, f"zero_border_{C}ch_{T}x{H}x{W}", 2.0 * T * (2 * (W + 2) + 2 * H) * C)
     return frames
 
@@ -1774,7 +1763,7 @@ def zero_border(frames: torch.Tensor, T: int, H: int, W: int, C: int):
 def upsample2x(x: torch.Tensor, out: torch.Tensor, T: int, C: int, H: int, W: int):
     _dev(x, torch.bfloat16, "x"), _dev(out, torch.bfloat16, "out")
     st = _prof_begin()
-    _check(lib().ce_upsample2x_bf16(_ptr(x), _ptr(out), T, C, H, W, _stream()), "ce_upsample2x_bf16")
+    _launch("ce_upsample2x_bf16", _ptr(x), _ptr(out), T, C, H, W, _stream())
     _prof_end(st, f"upsample2x_{C}ch_{T}x{H}x{W}", 2.0 * T * H * W * C * 5)  # (read once, written four times)
     return out
 
@@ -1783,8 +1772,7 @@ def softmax_rows(scores: torch.Tensor, probs: torch.Tensor, n: int, scale: float
     _dev(scores, torch.float32, "scores"), _dev(probs, torch.bfloat16, "probs")
     M, _, ld = _rows(scores, "scores")
     _, npad, ldp = _rows(probs, "probs")
-    _check(lib().ce_softmax_rows_f32_bf16(_ptr(scores), _ptr(probs), M, n, npad, ld, ldp, float(scale), _stream()),
-           "ce_softmax_rows_f32_bf16")
+    _launch("ce_softmax_rows_f32_bf16", _ptr(scores), _ptr(probs), M, n, npad, ld, ldp, float(scale), _stream())
     return probs
 
 
@@ -1816,8 +1804,8 @@ def attention_1head(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, scale: f
             ws = _attn1_ws[(dev, need)] = torch.empty(need, dtype=torch.float32, device=q.device)
         # (first seen under capture: no scratch - one workgroup per query block walks all keys)
     st = _prof_begin()
-    _check(lib().ce_attention_1head_bf16(_ptr(q), _ptr(k), _ptr(vt), _ptr(out), Nq, Nk, C, ldq, ldk, ldvt, ldo, float(scale), _ptr(ws),
-                                         0 if ws is None else ws.numel() * 4, _stream()), "ce_attention_1head_bf16")
+    _launch("ce_attention_1head_bf16", _ptr(q), _ptr(k), _ptr(vt), _ptr(out), Nq, Nk, C, ldq, ldk, ldvt, ldo, float(scale), _ptr(ws),
+            0 if ws is None else ws.numel() * 4, _stream())
     _prof_end(st, f"attention_1head_{Nq}x{Nk}x{C}", 4.0 * Nq * Nk * C)
     return out
 
@@ -1832,8 +1820,8 @@ def gemm_f32(a: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = Non
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
     _, _, ldc = _rows(out, "out")
     ws, ws_bytes = _gemm_scratch(a.device)
-    _check(lib().ce_gemm_bf16(_ptr(a), _ptr(w), _ptr(out), _ptr(None), 4, _ptr(None), _ptr(None), M, N, K, lda, ldw, ldc, 0, 0, 0, 0, 0, 0,
-                              ws, ws_bytes, _stream()), "ce_gemm_bf16(f32)")
+    _launch("ce_gemm_bf16", _ptr(a), _ptr(w), _ptr(out), _ptr(None), 4, _ptr(None), _ptr(None), M, N, K, lda, ldw, ldc, 0, 0, 0, 0, 0, 0,
+            ws, ws_bytes, _stream())
     return out
 
 
@@ -1850,9 +1838,9 @@ def gemm_batched(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, M: int, N:
     if bias is not None:
         _dev(bias, torch.float32, "bias")
     st = _prof_begin()
-    _check(lib().ce_gemm_batched_bf16(_ptr(a), _ptr(w), _ptr(out), _ptr(bias), EPI_F32 if f32_out else EPI_BIAS, M, N, K, lda, ldw, ldc,
-                                      batch[0], batch[1], stride_a[0], stride_a[1], stride_w[0], stride_w[1], stride_c[0], stride_c[1],
-                                      _stream()), "ce_gemm_batched_bf16")
+    _launch("ce_gemm_batched_bf16", _ptr(a), _ptr(w), _ptr(out), _ptr(bias), EPI_F32 if f32_out else EPI_BIAS, M, N, K, lda, ldw, ldc,
+            batch[0], batch[1], stride_a[0], stride_a[1], stride_w[0], stride_w[1], stride_c[0], stride_c[1],
+            _stream())
     _prof_end(st, f"gemm_batched_{batch[0] * batch[1]}x{M}x{N}x{K}", 2.0 * M * N * K * batch[0] * batch[1])
     return out
 
@@ -1865,7 +1853,7 @@ def im2col_patch2d(img: torch.Tensor, patch: int, kpad: int, out: Optional[torch
     B, C, H, W = img.shape
     if out is None:
         out = torch.empty((B * (H // patch) * (W // patch), kpad), dtype=torch.bfloat16, device=img.device)
-    _check(lib().ce_im2col_patch2d_bf16(_ptr(img), _ptr(out), B, C, H, W, patch, kpad, _stream()), "ce_im2col_patch2d_bf16")
+    _launch("ce_im2col_patch2d_bf16", _ptr(img), _ptr(out), B, C, H, W, patch, kpad, _stream())
     return out
 
 
@@ -1877,7 +1865,7 @@ def gather_rows(table: torch.Tensor, ids: torch.Tensor, out: Optional[torch.Tens
     if out is None:
         out = torch.empty((ids.numel(), D), dtype=torch.bfloat16, device=table.device)
     _, _, ldo = _rows(out, "out")
-    _check(lib().ce_gather_rows_bf16(_ptr(table), _ptr(ids), _ptr(out), ids.numel(), D, ldt, ldo, V, _stream()), "ce_gather_rows_bf16")
+    _launch("ce_gather_rows_bf16", _ptr(table), _ptr(ids), _ptr(out), ids.numel(), D, ldt, ldo, V, _stream())
     return out
 
 
@@ -1890,7 +1878,7 @@ def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, out: Optional[torch.Te
         out = torch.empty((M, D), dtype=torch.bfloat16, device=x.device)
     _, _, ldy = _rows(out, "out")
     st = _prof_begin()
-    _check(lib().ce_rmsnorm_bf16(_ptr(x), _ptr(out), _ptr(w), M, D, ldx, ldy, float(eps), _stream()), "ce_rmsnorm_bf16")
+    _launch("ce_rmsnorm_bf16", _ptr(x), _ptr(out), _ptr(w), M, D, ldx, ldy, float(eps), _stream())
     _prof_end(st, f"rmsnorm_{M}x{D}", 4.0 * M * D)
     return out
 
@@ -1909,8 +1897,8 @@ def softmax_t5(scores: torch.Tensor, probs: torch.Tensor, batch: int, heads: int
             assert t.is_contiguous()
     if table is not None:
         assert bucket_lut.numel() == Lq + Lk - 1 and table.shape[-1] == heads
-    _check(lib().ce_softmax_t5_bf16(_ptr(scores), _ptr(probs), batch, heads, Lq, Lk, ld, ldp, _ptr(bucket_lut), _ptr(table),
-                                    _ptr(valid_len), _stream()), "ce_softmax_t5_bf16")
+    _launch("ce_softmax_t5_bf16", _ptr(scores), _ptr(probs), batch, heads, Lq, Lk, ld, ldp, _ptr(bucket_lut), _ptr(table),
+            _ptr(valid_len), _stream())
     return probs
 
 
@@ -1928,7 +1916,7 @@ def quant_rows_fp8(x: torch.Tensor, out: Optional[torch.Tensor] = None, scale: O
     _dev(out, torch.uint8, "out"), _dev(scale, torch.float32, "scale")
     _, _, ldq = _rows(out, "out")
     st = _prof_begin()
-    _check(lib().ce_quant_rows_fp8(_ptr(x), _ptr(out), _ptr(scale), M, K, ldx, ldq, _stream()), "ce_quant_rows_fp8")
+    _launch("ce_quant_rows_fp8", _ptr(x), _ptr(out), _ptr(scale), M, K, ldx, ldq, _stream())
     _prof_end(st, f"quant_fp8_{M}x{K}", 3.0 * M * K)
     return out, scale
 
@@ -1941,8 +1929,8 @@ def ln_affine_fp8(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, eps: float,
     M, D, ldx = _rows(x, "x")
     _, _, ldq = _rows(out, "out")
     st = _prof_begin()
-    _check(lib().ce_ln_affine_fp8(_ptr(x), _ptr(out), _ptr(scale), _ptr(a), _ptr(b), M, D, ldx, ldq, float(eps), int(ab_rows),
-                                  int(ab_stride), _stream()), "ce_ln_affine_fp8")
+    _launch("ce_ln_affine_fp8", _ptr(x), _ptr(out), _ptr(scale), _ptr(a), _ptr(b), M, D, ldx, ldq, float(eps), int(ab_rows),
+            int(ab_stride), _stream())
     _prof_end(st, f"ln_affine_fp8_{M}x{D}", 3.0 * M * D)
     return out, scale
 
@@ -1978,8 +1966,8 @@ def quant_rows_mxfp8(x: torch.Tensor, out: Optional[torch.Tensor] = None, scale:
     _, _, ldq = _rows(out, "out")
     st = _prof_begin()
     # (an A/B build with the staged epilogue of rounds 3-5, -DF8_EPI_LDS=1 = ce_build_info bit 2, reads the W scales in the A order)
-    fn = lib().ce_quant_rows_mxfp8_w if (w_order and not lib().ce_build_info() & 4) else lib().ce_quant_rows_mxfp8
-    _check(fn(_ptr(x), _ptr(out), _ptr(scale), M, K, ldx, ldq, _stream()), "ce_quant_rows_mxfp8")
+    w_order = w_order and not getattr(lib(), "ce_build_info")() & 4  # (returns flags, not a status: not a _launch)
+    _launch("ce_quant_rows_mxfp8_w" if w_order else "ce_quant_rows_mxfp8", _ptr(x), _ptr(out), _ptr(scale), M, K, ldx, ldq, _stream())
     _prof_end(st, f"quant_mxfp8_{M}x{K}", 3.0 * M * K)
     return out, scale
 
@@ -1993,8 +1981,8 @@ def ln_affine_mxfp8(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, eps: floa
     assert scale.is_contiguous() and scale.numel() >= mx_scale_bytes(M, D)
     _, _, ldq = _rows(out, "out")
     st = _prof_begin()
-    _check(lib().ce_ln_affine_mxfp8(_ptr(x), _ptr(out), _ptr(scale), _ptr(a), _ptr(b), M, D, ldx, ldq, float(eps), int(ab_rows),
-                                    int(ab_stride), _stream()), "ce_ln_affine_mxfp8")
+    _launch("ce_ln_affine_mxfp8", _ptr(x), _ptr(out), _ptr(scale), _ptr(a), _ptr(b), M, D, ldx, ldq, float(eps), int(ab_rows),
+            int(ab_stride), _stream())
     _prof_end(st, f"ln_affine_mxfp8_{M}x{D}", 3.0 * M * D)
     return out, scale
 
@@ -2025,8 +2013,8 @@ def gemm_mxfp8(aq: torch.Tensor, sa: torch.Tensor, wq: torch.Tensor, sw: torch.T
             _dev(gate, torch.float32, "gate")
     ws, ws_bytes = _gemm_scratch(aq.device)
     st = _prof_begin()
-    _check(lib().ce_gemm_mxfp8(_ptr(aq), _ptr(wq), _ptr(out), _ptr(sa), _ptr(sw), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K, lda, ldw,
-                               ldc, ldres, int(gate_rows), ws, ws_bytes, _stream()), "ce_gemm_mxfp8")
+    _launch("ce_gemm_mxfp8", _ptr(aq), _ptr(wq), _ptr(out), _ptr(sa), _ptr(sw), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K, lda, ldw,
+            ldc, ldres, int(gate_rows), ws, ws_bytes, _stream())
     _prof_end(st, f"gemm_mxfp8_{M}x{N}x{K}_epi{epilogue}", 2.0 * M * N * K)
     return out
 
@@ -2046,8 +2034,8 @@ def gemm_mxfp8_gelu_quant(aq: torch.Tensor, sa: torch.Tensor, wq: torch.Tensor, 
         _dev(bias, torch.float32, "bias")
     ws, ws_bytes = _gemm_scratch(aq.device)
     st = _prof_begin()
-    _check(lib().ce_gemm_mxfp8_gelu_quant(_ptr(aq), _ptr(wq), _ptr(sa), _ptr(sw), _ptr(bias), _ptr(out), _ptr(scale), M, N, K, lda, ldw, ldq,
-                                          ws, ws_bytes, _stream()), "ce_gemm_mxfp8_gelu_quant")
+    _launch("ce_gemm_mxfp8_gelu_quant", _ptr(aq), _ptr(wq), _ptr(sa), _ptr(sw), _ptr(bias), _ptr(out), _ptr(scale), M, N, K, lda, ldw, ldq,
+            ws, ws_bytes, _stream())
     _prof_end(st, f"gemm_mxfp8_{M}x{N}x{K}_gelu_quant", 2.0 * M * N * K)
     return out, scale
 
@@ -2082,8 +2070,8 @@ def gemm_fp8(aq: torch.Tensor, sa: torch.Tensor, wq: torch.Tensor, sw: torch.Ten
             _dev(gate, torch.float32, "gate")
     ws, ws_bytes = _gemm_scratch(aq.device)  # the one-wave-per-SIMD loop cuts a partially filled last round of tiles along K (as ce_gemm_bf16)
     st = _prof_begin()
-    _check(lib().ce_gemm_fp8(_ptr(aq), _ptr(wq), _ptr(out), _ptr(sa), _ptr(sw), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K,
-                             lda, ldw, ldc, ldres, int(gate_rows), ws, ws_bytes, _stream()), "ce_gemm_fp8")
+    _launch("ce_gemm_fp8", _ptr(aq), _ptr(wq), _ptr(out), _ptr(sa), _ptr(sw), _ptr(bias), epilogue, _ptr(gate), _ptr(res), M, N, K,
+            lda, ldw, ldc, ldres, int(gate_rows), ws, ws_bytes, _stream())
     _prof_end(st, f"gemm_fp8_{M}x{N}x{K}_epi{epilogue}", 2.0 * M * N * K)
     return out
 
@@ -2114,8 +2102,8 @@ def rmsnorm_rope_mxfp8(x: torch.Tensor, w: torch.Tensor, cos_sin: Optional[torch
     assert scale.is_contiguous() and scale.shape == (M, D // 32)
     _, _, ldq = _rows(out, "out")
     st = _prof_begin()
-    _check(lib().ce_rmsnorm_rope_mxfp8(_ptr(x), _ptr(w), _ptr(cos_sin), _ptr(out), _ptr(scale), M, D, ldx, ldq, head_dim, float(eps), rope_rows,
-                                       float(post_scale), _stream()), "ce_rmsnorm_rope_mxfp8")
+    _launch("ce_rmsnorm_rope_mxfp8", _ptr(x), _ptr(w), _ptr(cos_sin), _ptr(out), _ptr(scale), M, D, ldx, ldq, head_dim, float(eps), rope_rows,
+            float(post_scale), _stream())
     _prof_end(st, f"rmsnorm_rope_mxfp8_{M}x{D}", 3.0 * M * D)
     return out, scale
 
@@ -2135,7 +2123,7 @@ def v_mxfp8_transpose(v: torch.Tensor, n_tokens: int, batch: int, heads: int, ou
         scale = torch.empty((batch, heads, npad // 64, 128, 2), dtype=torch.uint8, device=v.device)
     assert out.is_contiguous() and scale.is_contiguous() and out.shape == (batch, heads, 128, npad) and scale.shape == (batch, heads, npad // 64, 128, 2)
     st = _prof_begin()
-    _check(lib().ce_v_mxfp8_transpose(_ptr(v), ldv, _ptr(out), _ptr(scale), n_tokens, batch, heads, npad, _stream()), "ce_v_mxfp8_transpose")
+    _launch("ce_v_mxfp8_transpose", _ptr(v), ldv, _ptr(out), _ptr(scale), n_tokens, batch, heads, npad, _stream())
     _prof_end(st, f"v_mxfp8_transpose_{Mv}x{Dv}", 3.0 * Mv * Dv)
     return out, scale
 
@@ -2184,9 +2172,9 @@ def attention_mxfp8(q8: torch.Tensor, sq: torch.Tensor, k8: torch.Tensor, sk: to
             _dev(out, torch.bfloat16, "out")
             _, _, ldo = _rows(out, "out")
         st = _prof_begin()
-        _check(lib().ce_attention_mxfp8_add(_ptr(q8), _ptr(sq), _ptr(k8), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(add), lda, _ptr(out) if out8 is None else None,
-                                            ldo, _ptr(out8), _ptr(scale8) if out8 is not None else None, ld8, nq, nkv, npad, heads, 128, ldq, ldk, batch,
-                                            _stream()), "ce_attention_mxfp8_add")
+        _launch("ce_attention_mxfp8_add", _ptr(q8), _ptr(sq), _ptr(k8), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(add), lda, _ptr(out) if out8 is None else None,
+                ldo, _ptr(out8), _ptr(scale8) if out8 is not None else None, ld8, nq, nkv, npad, heads, 128, ldq, ldk, batch,
+                _stream())
         _prof_end(st, f"attention_mxfp8_{nq}x{nkv}_h{heads}" + (f"_b{batch}" if batch > 1 else "") + "_add" + ("_mxq" if out8 is not None else ""),
                   4.0 * nq * nkv * 128 * heads * batch)
         return out8 if out8 is not None else out
@@ -2195,8 +2183,8 @@ def attention_mxfp8(q8: torch.Tensor, sq: torch.Tensor, k8: torch.Tensor, sk: to
         _, D8, ld8 = _rows(out8, "out8")
         assert out8.shape[0] == Mq and D8 == D and scale8.is_contiguous() and scale8.numel() >= mx_scale_bytes(Mq, D)
         st = _prof_begin()
-        _check(lib().ce_attention_mxfp8_quant(_ptr(q8), _ptr(sq), _ptr(k8), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out8), _ptr(scale8), nq, nkv, npad,
-                                              heads, 128, ldq, ldk, ld8, batch, _stream()), "ce_attention_mxfp8_quant")
+        _launch("ce_attention_mxfp8_quant", _ptr(q8), _ptr(sq), _ptr(k8), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out8), _ptr(scale8), nq, nkv, npad,
+                heads, 128, ldq, ldk, ld8, batch, _stream())
         _prof_end(st, f"attention_mxfp8_{nq}x{nkv}_h{heads}" + (f"_b{batch}" if batch > 1 else "") + "_mxq", 4.0 * nq * nkv * 128 * heads * batch)
         return out8
     if out is None:
@@ -2204,8 +2192,8 @@ def attention_mxfp8(q8: torch.Tensor, sq: torch.Tensor, k8: torch.Tensor, sk: to
     _dev(out, torch.bfloat16, "out")
     _, _, ldo = _rows(out, "out")
     st = _prof_begin()
-    _check(lib().ce_attention_mxfp8(_ptr(q8), _ptr(sq), _ptr(k8), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out), nq, nkv, npad, heads, 128, ldq, ldk, ldo,
-                                    batch, _stream()), "ce_attention_mxfp8")
+    _launch("ce_attention_mxfp8", _ptr(q8), _ptr(sq), _ptr(k8), _ptr(sk), _ptr(v8t), _ptr(sv), _ptr(out), nq, nkv, npad, heads, 128, ldq, ldk, ldo,
+            batch, _stream())
     _prof_end(st, f"attention_mxfp8_{nq}x{nkv}_h{heads}" + (f"_b{batch}" if batch > 1 else ""), 4.0 * nq * nkv * 128 * heads * batch)
     return out
 
@@ -2263,7 +2251,7 @@ def lora_merge(w0: torch.Tensor, adapters, out: Optional[torch.Tensor] = None):
         scales.append(float(s))
     n = len(keep)
     st = _prof_begin()
-    _check(lib().ce_lora_merge_bf16(_ptr(w0), ldw0, _ptr(out), ldw, N, K, n, _ptr_array([b for _, b in keep]), _ptr_array([a for a, _ in keep]),
-                                    (ctypes.c_int * max(n, 1))(*ranks), (ctypes.c_float * max(n, 1))(*scales), _stream()), "ce_lora_merge_bf16")
+    _launch("ce_lora_merge_bf16", _ptr(w0), ldw0, _ptr(out), ldw, N, K, n, _ptr_array([b for _, b in keep]), _ptr_array([a for a, _ in keep]),
+            (ctypes.c_int * max(n, 1))(*ranks), (ctypes.c_float * max(n, 1))(*scales), _stream())
     _prof_end(st, f"lora_merge_{N}x{K}_r{sum(ranks)}", 4.0 * N * K)
     return out

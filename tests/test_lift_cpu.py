@@ -1,7 +1,6 @@
 """Guided detail lift, host side (chronoedit_amd/lift.py): the entry points in the header and the signature table, the config's validation,
 the box sums and axis tables against brute force and exact rationals, the three guarantees of the arithmetic on `lift.reference`, and the
 quality of the lift on a synthetic photo against the plain Lanczos upsample.  No GPU."""
-import re
 from fractions import Fraction
 
 import numpy as np
@@ -17,12 +16,9 @@ ENTRY_POINTS = ("ce_lift_fit_q16", "ce_lift_smooth_f32", "ce_lift_gate_f32", "ce
 
 def test_the_c_abi_declares_the_lift_entry_points():
     declared = hiplib.header_symbols()
-    text = open(hiplib.HEADER).read()
     for name in ENTRY_POINTS:
         assert declared.count(name) == 1, name
         assert name in hiplib.SIGNATURES, name
-        params = re.search(r"^int " + name + r"\((.*?)\);", text, flags=re.M | re.S).group(1)
-        assert len(hiplib.SIGNATURES[name]) == params.count(",") + 1, (name, params)  # one ctypes argument per parameter
     assert [n for n in declared if n.startswith("ce_lift_")] == list(ENTRY_POINTS)
     assert "ce_lift.hip" in hiplib.SOURCES
 

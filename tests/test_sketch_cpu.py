@@ -1,7 +1,5 @@
 """Sketch edits, host side (chronoedit_amd/sketch.py): the entry points in the header and the signature table, `sketch.reference` against
 the installed PIL's own filters byte for byte, the three guarantees of the arithmetic, the fraction rule, and every refusal.  No GPU."""
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -15,12 +13,9 @@ ENTRY_POINTS = ("ce_sketch_changed_u8", "ce_sketch_dilate_u8", "ce_sketch_box_u8
 
 def test_the_c_abi_declares_the_sketch_entry_points():
     declared = hiplib.header_symbols()
-    text = open(hiplib.HEADER).read()
     for name in ENTRY_POINTS:
         assert declared.count(name) == 1, name
         assert name in hiplib.SIGNATURES, name
-        params = re.search(r"^int " + name + r"\((.*?)\);", text, flags=re.M | re.S).group(1)
-        assert len(hiplib.SIGNATURES[name]) == params.count(",") + 1, (name, params)  # one ctypes argument per parameter
     assert [n for n in declared if n.startswith("ce_sketch_")] == list(ENTRY_POINTS) == list(sketch.ENTRY_POINTS)
     assert "ce_sketch.hip" in hiplib.SOURCES
 

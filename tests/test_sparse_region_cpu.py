@@ -1,7 +1,5 @@
 """Sparse region edits, host side (chronoedit_amd/sparse_region.py): the active token set of a mask, the compute / refresh / sparse plan,
 and the C ABI of the four gather / scatter passes (csrc/ce_sparse.hip).  No GPU."""
-import re
-
 import pytest
 import torch
 
@@ -153,12 +151,9 @@ def test_config_validation_and_report():
 
 def test_the_c_abi_declares_the_four_entry_points():
     declared = hiplib.header_symbols()
-    text = open(hiplib.HEADER).read()
     for name in ENTRY_POINTS:
         assert declared.count(name) == 1, name
         assert name in hiplib.SIGNATURES, name
-        params = re.search(r"^int " + name + r"\((.*?)\);", text, flags=re.M | re.S).group(1)
-        assert len(hiplib.SIGNATURES[name]) == params.count(",") + 1, (name, params)  # one ctypes argument per parameter
     assert [n for n in declared if n.startswith("ce_sparse_")] == list(ENTRY_POINTS)
     assert "ce_sparse.hip" in hiplib.SOURCES
     from chronoedit_amd import ops

@@ -17,14 +17,10 @@ def bind(path):
     knob = None
     if "@" in path:  # <lib.so>@<knob>: select a loop body through ce_set_attention_waves
         path, knob = path.split("@")
-    lib = ctypes.CDLL(path)
+    lib = hiplib.bind(ctypes.CDLL(path), diag=True)
     if knob is not None:
         lib.ce_set_attention_waves(int(knob))
-    f = lib.ce_attention_batched_bf16
-    f.restype = ctypes.c_int
-    f.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_void_p] + \
-        [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
-    return f
+    return lib.ce_attention_batched_bf16
 
 
 def main():

@@ -7,8 +7,10 @@ import sys
 
 import torch
 
+sys.path.insert(0, ".")
+from chronoedit_amd import hiplib  # noqa: E402
+
 BF = torch.bfloat16
-P, I = ctypes.c_void_p, ctypes.c_int
 _libs = {}
 
 
@@ -16,13 +18,7 @@ def bind(spec):
     path, _, knob = spec.partition("@")
     lib = _libs.get(path)
     if lib is None:
-        lib = _libs[path] = ctypes.CDLL(path)
-        lib.ce_attention_vt_bf16.restype = I
-        lib.ce_attention_vt_bf16.argtypes = [P, P, P, I, I, I, P, I, I, I, I, I, ctypes.c_float, I, P]
-        lib.ce_v_transpose_bf16.restype = I
-        lib.ce_v_transpose_bf16.argtypes = [P, I, P, I, I, I, P]
-        lib.ce_set_attention_waves.restype = I
-        lib.ce_set_attention_waves.argtypes = [I]
+        lib = _libs[path] = hiplib.bind(ctypes.CDLL(path), diag=True)
     return lib, int(knob or 0), spec.split("/")[-1].replace("lib", "").replace(".so", "")
 
 

@@ -6,19 +6,15 @@ import sys
 
 import torch
 
+sys.path.insert(0, ".")
+from chronoedit_amd import hiplib  # noqa: E402
+
 BF = torch.bfloat16
 
 
 def bind(path):
-    lib = ctypes.CDLL(path)
-    P, I = ctypes.c_void_p, ctypes.c_int
-    f = lib.ce_attention_vt_bf16
-    f.restype = I
-    f.argtypes = [P, P, P, I, I, I, P, I, I, I, I, I, ctypes.c_float, I, P]
-    t = lib.ce_v_transpose_bf16
-    t.restype = I
-    t.argtypes = [P, I, P, I, I, I, P]
-    return f, t
+    lib = hiplib.bind(ctypes.CDLL(path))
+    return lib.ce_attention_vt_bf16, lib.ce_v_transpose_bf16
 
 
 def main():

@@ -7,16 +7,15 @@ import sys
 
 import torch
 
+sys.path.insert(0, ".")
+from chronoedit_amd import hiplib  # noqa: E402
+
 BF = torch.bfloat16
 
 
 def bind(path):
-    lib = ctypes.CDLL(path)
-    P, I = ctypes.c_void_p, ctypes.c_int
-    f = lib.ce_gemm_bf16
-    f.restype = I
-    f.argtypes = [P, P, P, P, I, P, P] + [I] * 9 + [ctypes.c_longlong, I, ctypes.c_longlong, P, ctypes.c_size_t, P]
-    return lib, f
+    lib = hiplib.bind(ctypes.CDLL(path))
+    return lib, lib.ce_gemm_bf16
 
 
 def main():

@@ -6,19 +6,15 @@ import sys
 
 import torch
 
+sys.path.insert(0, ".")
+from chronoedit_amd import hiplib  # noqa: E402
+
 BF = torch.bfloat16
 
 
 def bind(path):
-    lib = ctypes.CDLL(path)
-    P, I = ctypes.c_void_p, ctypes.c_int
-    f = lib.ce_gemm_fp8
-    f.restype = I
-    f.argtypes = [P, P, P, P, P, P, I, P, P] + [I] * 8 + [P, ctypes.c_size_t, P]
-    q = lib.ce_quant_rows_fp8
-    q.restype = I
-    q.argtypes = [P, P, P, I, I, I, I, P]
-    return lib, f, q
+    lib = hiplib.bind(ctypes.CDLL(path))
+    return lib, lib.ce_gemm_fp8, lib.ce_quant_rows_fp8
 
 
 def main():

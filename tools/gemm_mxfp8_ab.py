@@ -9,28 +9,18 @@ import sys
 
 import torch
 
+sys.path.insert(0, ".")
+from chronoedit_amd import hiplib  # noqa: E402
+
 BF = torch.bfloat16
 
 
 def bind(path):
-    lib = ctypes.CDLL(path)
-    P, I = ctypes.c_void_p, ctypes.c_int
-    g = lib.ce_gemm_mxfp8
-    g.restype = I
-    g.argtypes = [P, P, P, P, P, P, I, P, P] + [I] * 8 + [P, ctypes.c_size_t, P]
-    gq = lib.ce_gemm_mxfp8_gelu_quant
-    gq.restype = I
-    gq.argtypes = [P, P, P, P, P, P, P] + [I] * 6 + [P, ctypes.c_size_t, P]
-    q = lib.ce_quant_rows_mxfp8
-    q.restype = I
-    q.argtypes = [P, P, P, I, I, I, I, P]
+    lib = hiplib.bind(ctypes.CDLL(path))
     # round 6: the register-direct epilogue takes the W scales in the W order (ce_quant_rows_mxfp8_w); a -DF8_EPI_LDS=1 build (ce_build_info bit 2)
     # or a library from before round 6 (no ce_build_info / no _w entry) takes them in the A order
     lib.w_order = hasattr(lib, "ce_quant_rows_mxfp8_w") and not (lib.ce_build_info() & 4)
-    if lib.w_order:
-        lib.ce_quant_rows_mxfp8_w.restype = I
-        lib.ce_quant_rows_mxfp8_w.argtypes = q.argtypes
-    return lib, g, gq, q
+    return lib, lib.ce_gemm_mxfp8, lib.ce_gemm_mxfp8_gelu_quant, lib.ce_quant_rows_mxfp8
 
 
 def scale_bytes(rows, K):

@@ -5,15 +5,14 @@ import sys
 
 import torch
 
+sys.path.insert(0, ".")
+from chronoedit_amd import hiplib  # noqa: E402
+
 BF = torch.bfloat16
 
 
 def bind(path):
-    lib = ctypes.CDLL(path)
-    P, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    lib.ce_ln_affine_bf16.argtypes = [P, P, P, P, I, I, I, I, F, I, I, P]
-    lib.ce_rmsnorm_rope_bf16.argtypes = [P, P, P, P, P, I, I, I, I, F, I, P]
-    return lib
+    return hiplib.bind(ctypes.CDLL(path))
 
 
 def main():
