@@ -26,7 +26,7 @@ DIAG_HEADER = os.path.join(ROOT, "include", "chronoedit_hip_diag.h")
 DIAG_SOURCES = ["ce_gemm.hip", "ce_gemm256.hip", "ce_attn.hip", "ce_attn_fp8.hip", "ce_gemm_fp8.hip", "ce_gemm_fp8w4.hip"]
 # measured-and-closed experiments kept as opt-in bodies: in the diagnostic library only
 DIAG_ONLY_SOURCES = ["ce_attn16.hip"]
-SOURCES = ["ce_rowops.hip", "ce_gemm.hip", "ce_gemm256.hip", "ce_gemm256w4.hip", "ce_gemm384.hip", "ce_attn.hip", "ce_attn16.hip", "ce_attn_fp8.hip", "ce_sched.hip", "ce_conv.hip", "ce_enc.hip", "ce_gemm_fp8.hip", "ce_gemm_fp8w4.hip", "ce_comm.hip", "ce_lora.hip", "ce_tea.hip", "ce_image.hip", "ce_region.hip", "ce_sparse.hip", "ce_region_auto.hip", "ce_focus.hip", "ce_autofocus.hip", "ce_preview.hip", "ce_lift.hip", "ce_sketch.hip", "ce_components.hip", "ce_clusters.hip", "ce_layers.hip", "ce_boxlift.hip", "ce_rimlift.hip"]
+SOURCES = ["ce_rowops.hip", "ce_gemm.hip", "ce_gemm256.hip", "ce_gemm256w4.hip", "ce_gemm384.hip", "ce_attn.hip", "ce_attn16.hip", "ce_attn_fp8.hip", "ce_sched.hip", "ce_conv.hip", "ce_enc.hip", "ce_gemm_fp8.hip", "ce_gemm_fp8w4.hip", "ce_comm.hip", "ce_lora.hip", "ce_tea.hip", "ce_image.hip", "ce_region.hip", "ce_sparse.hip", "ce_region_auto.hip", "ce_focus.hip", "ce_autofocus.hip", "ce_preview.hip", "ce_lift.hip", "ce_sketch.hip", "ce_components.hip", "ce_clusters.hip", "ce_layers.hip", "ce_boxlift.hip", "ce_rimlift.hip", "ce_tiles.hip"]
 
 _c = ctypes
 # scalar parameter types of the C ABI; every pointer is passed as an address (see _ctype)

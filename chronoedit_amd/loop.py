@@ -8,7 +8,8 @@ on the device for the whole trajectory; the CFG combine and the UniPC update are
 A step has a KIND (`step_kinds`): `_run_step` is the one place that turns a kind into forwards and a `step_cfg` call, `_step_modes` the one
 place that sets the engine's per-forward mode flags for it; `denoise_step` (eager) and `GraphedDenoiser` (captured) both go through them.
 What a feature of the loop keeps per edit lives in a state object next to the feature's code (guidance.GuidanceState,
-teacache.TeaCacheState, sparse_region.SparseRegionState, auto_region.AutoRegionState, region.RegionState, preview.PreviewDelivery);
+teacache.TeaCacheState, sparse_region.SparseRegionState, auto_region.AutoRegionState, region.RegionState, preview.PreviewDelivery,
+tiles.TileState);
 `denoise` calls their moments in order.  `chronoedit_amd.pipeline` re-exports every name here.
 """
 from __future__ import annotations
@@ -266,7 +267,7 @@ class GraphedDenoiser:
 
     def __init__(self, transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds,
                  guidance_scale: float, batch_cfg: bool = True, warm: bool = False, keep_warmup_step: bool = True, tea_plan=None,
-                 guidance_plan=None, delta: Optional[torch.Tensor] = None, region=None, sparse_plan=None):
+                 guidance_plan=None, delta: Optional[torch.Tensor] = None, region=None, sparse_plan=None, tiles=None):
         """warm: this process has already run a step of exactly this shape / guidance form through `transformer` (packed weights,
         workspaces, kernel attributes exist), so no un-captured step is needed in front of the capture; only the step-invariant context
         projections are computed eagerly so that the graph holds the cache HIT (`cache_context`), not the projections.
@@ -275,7 +276,9 @@ class GraphedDenoiser:
         temporal-reasoning edit at 28 800 tokens, 12 % of an 8-step edit.  keep_warmup_step=False: run it on saved state and put the
         state back (a caller that wants every `step()` to be a replay: bench.py).
         region: the edit's region.RegionState, or None.  Every kind of step then ends with the region blend, inside its graph; the blend
-        reads its sigma from the state's staging float, which `_stage` fills next to the coefficient row."""
+        reads its sigma from the state's staging float, which `_stage` fills next to the coefficient row.
+        tiles: the edit's tiles.TileState, or None.  The latents' samples are then the tiles of one canvas, and every kind of step ends with the
+        fusion (two launches), inside its graph."""
         assert latents.dtype == torch.float32 and latents.is_contiguous()
         if not _capturable(transformer):
             # Measured on this stack (ROCm 7.0 / RCCL 2.26 / torch 2.10: tools/rccl_graph_probe.py, profiles/r03_rccl_graph_probe.txt): ONE
@@ -288,7 +291,7 @@ class GraphedDenoiser:
             raise NotImplementedError("hipGraph capture of a step with torch.distributed exchanges is not usable on this torch / RCCL build: "
                                       "enable_sequence_parallel(owned_comm=True) or run the sharded loop eagerly")
         self.tr, self.sch, self.latents, self.condition = transformer, scheduler, latents, condition
-        self.region = region
+        self.region, self.tiles = region, tiles
         self._ran_eagerly = set()  # sample counts (1: the single sample, 2: the stacked pair) this object has run an eager step of
         self.prompt, self.negative, self.image, self.g, self.batch_cfg = prompt_embeds, negative_prompt_embeds, image_embeds, guidance_scale, batch_cfg
         dev = latents.device
@@ -428,11 +431,13 @@ class GraphedDenoiser:
 
     def _body(self, kind: str = "compute"):
         """One step of any kind, captured or eager, under its mode flags: the model and the scheduler update, then, with a region, the blend
-        (chronoedit_amd/region.py)."""
+        (chronoedit_amd/region.py), or, with tiles, their fusion (chronoedit_amd/tiles.py)."""
         with _step_modes(self.tr, kind, tea=self.tea_plan is not None):
             self._model_step(kind)
             if self.region is not None:
                 self.region.blend(self.latents)
+            if self.tiles is not None:
+                self.tiles.fuse(self.latents)
 
     def _model_step(self, kind: str = "compute"):
         """The captured caller of `_run_step`: the timestep and the coefficient row come from the staging buffers."""
@@ -490,7 +495,7 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
             num_temporal_reasoning_steps: int = 0, use_graph: bool = False, on_step_end=None, interrupted=None, graph_warm=None,
             teacache=None, teacache_measure: bool = False, guidance_reuse=None, guidance_measure: Optional[int] = None,
             keep_deltas: bool = False, region=None, sparse_region=None, auto_region=None, start_step: int = 0, start_eps=None,
-            preview=None):
+            preview=None, tiles=None):
     """The whole loop, including the temporal-reasoning truncation 8 -> 2 latent frames (pipeline_chronoedit.py:700-709).
     Per step i, in this order: `interrupted()` -> True skips this and every remaining step (`self.interrupt`, :697-698); at
     i == num_temporal_reasoning_steps the truncation - latents, condition, the scheduler history and every feature's latent-shaped state
@@ -521,12 +526,20 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
     auto_region (an auto_region.AutoRegion; an explicit `region=` wins): auto_region.AutoRegionState - the detection behind step k that
     turns the edit into a region-limited one, or the per-step measurement.
     preview (a preview.PreviewConfig): preview.PreviewDelivery - per-step RGB estimates, handed to `on_preview`.
+    tiles (a tiles.TileState): the latents' samples are the overlapping tiles of one canvas, and `tiles.fuse(latents)` makes them agree behind
+    every step's scheduler update (inside the graph of a graphed step); the scheduler's history stays per tile.  It goes with none of the
+    features above, nor with temporal reasoning or start_step (ValueError), nor sharded (NotImplementedError).
 
     Refusals, in the order they are raised (a call that earns two gets the first): start_step with temporal reasoning or a detecting
     auto_region (ValueError); previews, then an auto region, then a region, sharded (NotImplementedError) and what their states refuse;
     `sparse_region=` without a region; a sparse region with TeaCache or guidance reuse; a TeaCache plan with measuring (ValueError each);
     then what GuidanceState.begin, TeaCacheState.begin and SparseRegionState.begin refuse, each in its own documented order."""
     start_step = int(start_step)
+    if tiles is not None:
+        if start_step or enable_temporal_reasoning or region is not None or auto_region is not None or preview is not None:
+            raise ValueError("denoise: tiles go with neither start_step, temporal reasoning, a region, an auto region nor previews")
+        from . import tiles as _tl
+        refuse_sharded(transformer, _tl.SHARDED)
     if start_step:
         if enable_temporal_reasoning or (auto_region is not None and region is None):
             raise ValueError("denoise: start_step > 0 goes with neither temporal reasoning nor a detecting auto_region (their step indices "
@@ -573,6 +586,8 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                                  tea_active=tea_cfg is not None or measure)
     tea = _tea.TeaCacheState.begin(transformer, scheduler.timesteps, tea_cfg, measure, forced)
     sparse = _sr.SparseRegionState.begin(transformer, sr if region is not None or detecting else None, n_steps)
+    if tiles is not None and (gs is not None or tea is not None):
+        raise ValueError("denoise: tiles go with neither TeaCache nor guidance reuse (enabled or measuring)")
     if sparse is not None and region is not None:
         truncates = enable_temporal_reasoning and 0 <= int(num_temporal_reasoning_steps) < n_steps
         # with reasoning every step up to and including the truncation step is dense: the cache is never built at the 8-frame shape
@@ -623,10 +638,11 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                     # (with guidance reuse: which forms - the stacked pair, the single sample - the rest of the plan runs; GraphedDenoiser
                     # asks the engine per form on top of this)
                     forms = None if gs is None else tuple(sorted({1 if k in ("reuse", "off") else 2 for k in gs.plan[i:]}))
-                    return (tuple(latents.shape), guided, gen, tea is not None and tea.plan is not None, forms, region_state is not None)
+                    return (tuple(latents.shape), guided, gen, tea is not None and tea.plan is not None, forms, tiles is not None,
+                            region_state is not None)
                 graphed = GraphedDenoiser(transformer, scheduler, latents, condition, prompt_embeds, negative_prompt_embeds,
                                           image_embeds, guidance_scale, batch_cfg=not sharded, warm=graph_warm is not None and warm_key() in graph_warm,
-                                          delta=None if gs is None else gs.delta, region=region_state, **plans())
+                                          delta=None if gs is None else gs.delta, region=region_state, tiles=tiles, **plans())
                 if graph_warm is not None:
                     graph_warm.add(warm_key())  # (taken AFTER the construction: the first step of a process creates the engine)
             latents = graphed.step(i)
@@ -635,6 +651,8 @@ def denoise(transformer, scheduler, latents, condition, prompt_embeds, negative_
                 latents = _run_step(transformer, scheduler, latents, condition, t, prompt_embeds, negative_prompt_embeds, image_embeds, cfg_inputs,
                                     guidance_scale, not sharded, kinds[i], delta=None if gs is None else gs.delta,
                                     delta_measure=None if gs is None else gs.delta_measure, cfgp=getattr(transformer, "_cfgp", None))
+            if tiles is not None:  # (a graphed step fuses inside its graph)
+                tiles.fuse(latents)
         if gs is not None:
             gs.after_step(i)
         if pv is not None and preview.lag > 0:

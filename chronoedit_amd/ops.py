@@ -1585,6 +1585,68 @@ def rimlift_smooth(L: torch.Tensor, E: torch.Tensor, M: torch.Tensor, AB: torch.
     return coef, R
 
 
+# ---- tiled edits (csrc/ce_tiles.hip) ---------------------------------------------------------------------------------------
+def _tile_origins(xs, ys):
+    """The origins as the host int arrays the launchers read (they check the geometry; a bad one is a HipKernelError 'bad argument')."""
+    xs, ys = [int(v) for v in xs], [int(v) for v in ys]
+    return len(xs), len(ys), (ctypes.c_int * max(len(xs), 1))(*xs), (ctypes.c_int * max(len(ys), 1))(*ys)
+
+
+def _tile_latents(tiles: torch.Tensor, canvas: torch.Tensor, nx: int, ny: int):
+    _dev(tiles, torch.float32, "tiles"), _dev(canvas, torch.float32, "canvas")
+    if tiles.dim() < 3 or canvas.dim() < 2 or not tiles.is_contiguous() or not canvas.is_contiguous():
+        raise ValueError(f"tiles / canvas: need contiguous [n, ..., th, tw] and [..., ch, cw], got {tuple(tiles.shape)} stride {tiles.stride()} and "
+                         f"{tuple(canvas.shape)} stride {canvas.stride()}")
+    if tiles.shape[0] != nx * ny or tuple(tiles.shape[1:-2]) != tuple(canvas.shape[:-2]):
+        raise ValueError(f"tiles {tuple(tiles.shape)}: need {nx * ny} tiles whose middle axes are the canvas's {tuple(canvas.shape[:-2])}")
+    planes = 1
+    for s in canvas.shape[:-2]:
+        planes *= int(s)
+    return planes, int(tiles.shape[-2]), int(tiles.shape[-1]), int(canvas.shape[-2]), int(canvas.shape[-1])
+
+
+def tiles_fuse(tiles: torch.Tensor, canvas: torch.Tensor, xs, ys):
+    """tiles fp32 [n, ..., th, tw] (row-major over ys x xs, origins in cells) -> canvas fp32 [..., ch, cw], overwritten: per cell the mean of
+    the covering tiles under integer tent weights, summed in double in ascending tile index (tiles.reference_fuse, bit for bit)."""
+    nx, ny, ox, oy = _tile_origins(xs, ys)
+    planes, th, tw, ch, cw = _tile_latents(tiles, canvas, nx, ny)
+    st = _prof_begin()
+    _launch("ce_tiles_fuse_f32", _ptr(tiles), _ptr(canvas), nx, ny, ox, oy, planes, th, tw, ch, cw, _stream())
+    _prof_end(st, f"tiles_fuse_{nx}x{ny}_{planes}x{ch}x{cw}", 4.0 * (tiles.numel() + canvas.numel()))
+    return canvas
+
+
+def tiles_scatter(canvas: torch.Tensor, tiles: torch.Tensor, xs, ys):
+    """canvas fp32 [..., ch, cw] -> tiles fp32 [n, ..., th, tw], overwritten: every tile cell takes its canvas cell (tiles.reference_scatter)."""
+    nx, ny, ox, oy = _tile_origins(xs, ys)
+    planes, th, tw, ch, cw = _tile_latents(tiles, canvas, nx, ny)
+    st = _prof_begin()
+    _launch("ce_tiles_scatter_f32", _ptr(canvas), _ptr(tiles), nx, ny, ox, oy, planes, th, tw, ch, cw, _stream())
+    _prof_end(st, f"tiles_scatter_{nx}x{ny}_{planes}x{ch}x{cw}", 8.0 * tiles.numel())
+    return tiles
+
+
+def tiles_blend_u8(frames: torch.Tensor, xs, ys, target, out: Optional[torch.Tensor] = None):
+    """frames uint8 [n, F, TH, TW, 3] (the decoded tiles, row-major over ys x xs, origins in pixels), target = (W, H) -> uint8 [F, H, W, 3]: the
+    tent-weighted mean in exact integers, the canvas cropped to the target (tiles.reference_blend, the same bytes)."""
+    _dev(frames, torch.uint8, "frames")
+    if frames.dim() != 5 or frames.shape[4] != 3 or not frames.is_contiguous():
+        raise ValueError(f"frames: need a contiguous [n, F, TH, TW, 3] tensor, got shape {tuple(frames.shape)} stride {frames.stride()}")
+    nx, ny, ox, oy = _tile_origins(xs, ys)
+    n, F, TH, TW, _ = frames.shape
+    W, H = int(target[0]), int(target[1])
+    if n != nx * ny:
+        raise ValueError(f"frames: {n} tiles for a {nx}x{ny} grid")
+    if out is None:
+        out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=frames.device)
+    _dev(out, torch.uint8, "out")
+    assert out.is_contiguous() and tuple(out.shape) == (F, H, W, 3)
+    st = _prof_begin()
+    _launch("ce_tiles_blend_u8", _ptr(frames), _ptr(out), nx, ny, ox, oy, F, TH, TW, H, W, _stream())
+    _prof_end(st, f"tiles_blend_{nx}x{ny}_{F}x{H}x{W}", float(frames.numel() + out.numel()))
+    return out
+
+
 # ---- Wan VAE ------------------------------------------------------------------------------------------------------
 # ---- sparse region edits (csrc/ce_sparse.hip) ----------------------------------------------------------------------------
 def _sparse_ids(ids: torch.Tensor):

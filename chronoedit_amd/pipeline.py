@@ -15,9 +15,9 @@ from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
-from . import auto_region as _ar, autofocus as _af, clusters as _cl, focus as _fc, image_io, layers as _ly, lift as _lf, preview as _pv, region as _rg, sketch as _sk
+from . import auto_region as _ar, autofocus as _af, clusters as _cl, focus as _fc, image_io, layers as _ly, lift as _lf, preview as _pv, region as _rg, sketch as _sk, tiles as _tl
 from .loop import (GraphedDenoiser, _capturable, _sharded_batchable, _shared_inputs, _token_sharded, _warmup_stream,  # noqa: F401
-                   compact_text_context, denoise, denoise_step, make_cfg_inputs, text_compaction_plan, text_real_lengths)
+                   compact_text_context, denoise, denoise_step, make_cfg_inputs, refuse_sharded, text_compaction_plan, text_real_lengths)
 from .scheduler import FlowUniPCMultistepScheduler
 from .transformer import ChronoEditTransformer3DModel
 
@@ -75,6 +75,12 @@ def decode_latents(vae, latents: torch.Tensor, enable_temporal_reasoning: bool =
         reason = vae.decode(latents[:, :, :-1], return_dict=False)[0]
         return torch.cat([reason, edit[:, :, 1:]], dim=2)
     return vae.decode(latents, return_dict=False)[0]
+
+
+def _blend_tiles(video: torch.Tensor, p) -> torch.Tensor:
+    """The decoded tiles [n, 3, F, TH, TW] on the device -> the target's frames uint8 [F, H, W, 3]: ce_video_to_u8, then ce_tiles_blend_u8."""
+    from . import ops
+    return ops.tiles_blend_u8(ops.video_to_u8(video.contiguous()), p.xs, p.ys, p.target)
 
 
 @dataclass
@@ -180,6 +186,8 @@ class ChronoEditPipeline:
         self.lift_report = None  # the last call's detail-lift report, one dict per sample; None when the switch is off (or "latent" was asked for)
         self._sketch_region = None  # the sketch.SketchConfig while enable_sketch_region is in force
         self.sketch_report = None  # the last call's sketch plans, one dict per editor value; None when the call got no editor value
+        self._tiled = None  # the tiles.TileConfig while enable_tiled_edit is in force
+        self.tile_report = None  # the last call's tile plan (tiles.TilePlan.report) plus "reason"; None when tiled edits were off
 
     # -- properties of the reference pipeline (:458-478) ---------------------------------------------------------------
     @property
@@ -822,6 +830,9 @@ class ChronoEditPipeline:
         edit and applies it at full strength, and the paste's photo-size mask tapers it once.  `composite=False` and boxes of the edit's
         size keep the plain path.  While it is on every `lift_report` entry says "mask_aware": whether that sample was fitted this way.  A
         rising `fallback_fraction` under the switch means the frames' taper does not follow the mask; the fallback is the plain upsample."""
+        if self._tiled is not None:
+            raise ValueError("enable_detail_lift while tiled edits are on (enable_tiled_edit): two ways to reach the photo's size - "
+                             "disable_tiled_edit() first")
         if not isinstance(focus, bool):
             raise ValueError(f"detail lift: focus must be True or False, got {focus!r}")
         if not isinstance(mask_aware, bool):
@@ -838,6 +849,54 @@ class ChronoEditPipeline:
         self._detail_lift_focus = False
         self._detail_lift_mask_aware = False
         return self
+
+    # Tiled edits (chronoedit_amd/tiles.py): a whole photo at full size as overlapping model-size tiles, fused per step.  Off by default
+    def enable_tiled_edit(self, size=None, overlap=0.25, clip: str = "tile", max_tiles: int = _tl.MAX_TILES):
+        """While on, `__call__(image, prompt, height=, width=)` with ONE PIL image edits the whole photo at the TARGET's size - `size` None: the
+        photo's own, (W, H): that size, a float > 0: that scale of the photo's size (a photo of another size is first resized to the target,
+        Lanczos, on the device or by PIL as `enable_device_image_io` says) - as overlapping tiles of width x height: height x width is the TILE.
+        The target's sides rounded up to multiples of 16 are the canvas (the image is padded right and bottom by edge replication); per axis
+        the fewest tiles cover it whose neighbours share at least `overlap` - a float in (0, 0.5]: that fraction of the tile's side, rounded
+        up to a multiple of 16 px; an int: pixels, a multiple of 16 - at origins that are multiples of 16 (tiles.axis_origins; `tile_plan`
+        shows the plan before an edit is spent, `tile_report` holds it afterwards plus "reason": "tiled" or "single").  The tiles run as the
+        samples of ONE batched pass, each from the prompt's row, its own VAE condition and - clip="tile" - CLIP on its own pixels
+        (clip="photo": CLIP once on the target image, the row repeated); `generator` draws ONE canvas of noise [1, 16, T, CH / 8, CW / 8]
+        (`latents=` is taken at that shape) that is cut into the tiles.  Behind every scheduler update the tiles' latents are averaged on the
+        canvas under integer tent weights and cut again (two launches, inside the captured step; csrc/ce_tiles.hip); the scheduler's history
+        stays per tile.  All tiles are decoded and blended in exact integers under the same tents in pixels, straight into the target's
+        frame: "pil" / "np" / "pt" frames have the TARGET's size ("np" / "pt": the bytes / 255), "latent" returns the canvas latents
+        [1, 16, T, CH / 8, CW / 8].  With `enable_device_image_io(False)` the blend is tiles.reference_blend on the CPU, the same bytes.
+        A canvas that equals one tile ("single") is the plain call on the image, bit for bit - its frames then have the TILE's size, which
+        is the canvas's, also where the target is smaller (a 90x60 photo under a 96x64 tile); `tile_report["frames"]` says which size came
+        back.  More than `max_tiles` (1..16) tiles, or a
+        canvas side below the tile's, is a ValueError.  `callback_on_step_end` sees the tiles' latents [n, 16, T, th, tw] behind the fusion;
+        latents it returns go into the next step as they are and are fused behind it, and behind the last step they are fused once more before
+        they are decoded or returned.
+        Refused while the switch is on, before anything runs - NotImplementedError: a list of images or prompts, num_videos_per_prompt > 1,
+        temporal reasoning, previews, TeaCache, guidance reuse, offload_model, sharded tokens or CFG parallelism, a measuring edit
+        (measure_guidance_reuse, measure_auto_region, calibrate_teacache); ValueError: an array or
+        tensor image, an edit region in force (an explicit mask, auto region, auto focus, a sketch editor value) and `enable_detail_lift`.
+        Whether a checkpoint edits the tiles of one photo consistently is the checkpoint's business."""
+        cfg = _tl.TileConfig(tuple(size) if isinstance(size, list) else size, overlap, clip, max_tiles)
+        if self._detail_lift is not None:
+            raise ValueError("enable_tiled_edit while the detail lift is on (enable_detail_lift): two ways to reach the photo's size - "
+                             "disable_detail_lift() first")
+        self._tiled = cfg
+        return self
+
+    def disable_tiled_edit(self):
+        self._tiled = None
+        return self
+
+    def tile_plan(self, image_size, height: int, width: int) -> dict:
+        """The plan a tiled call at width x height would run for a photo of image_size = (W, H) with the enabled parameters, without running
+        anything: {"source_size", "target", "canvas", "tile" (all (width, height)), "origins" (row-major, the batch order), "grid",
+        "overlaps" (per axis, between neighbours), "min_overlap", "count", "frames" (the size of the returned frames: the target's, or - one
+        tile - the tile's)} - `tile_report`'s entries."""
+        if self._tiled is None:
+            raise ValueError("tile_plan needs the parameters of enable_tiled_edit(): the switch is off")
+        c = self._tiled
+        return _tl.plan(image_size, height, width, c.size, c.overlap, c.max_tiles).report
 
     def _measure_kwargs(self) -> dict:
         """What `denoise` gets on top while measure_guidance_reuse runs."""
@@ -864,6 +923,9 @@ class ChronoEditPipeline:
         (`scheduler.trajectory_dtype = torch.bfloat16` restores the reference's bf16 rounding of latents and history)."""
         args = CallArgs(**{k: v for k, v in locals().items() if k != "self"})  # (the first statement: the locals are the arguments)
         self.sketch_report = None
+        if self._tiled is not None:  # tiled edits (chronoedit_amd/tiles.py): the whole photo at the target's size - or the refusal
+            return self._tiled_edit(args)
+        self.tile_report = None
         if _sk.is_editor_value(image):  # an image editor's value: the sketch edit (chronoedit_amd/sketch.py) - or its refusal
             return self._sketch_edit(args)
         return self._edit(args)
@@ -1020,6 +1082,115 @@ class ChronoEditPipeline:
         a = replace(a, image=[q.image for q in flat], prompt=None, negative_prompt=None, prompt_embeds=repeat(prompt_embeds),
                     negative_prompt_embeds=repeat(negative_prompt_embeds), image_embeds=image_embeds, latents=repeat(noise), generator=None)
         return self._edit(a, FocusPass(flat, cfg.composite, guarded=True, crop_of=crop_of))
+
+    def _tiled_refusals(self, a: CallArgs):
+        """What a tiled edit does not compose with, refused before anything runs; every message names the switch."""
+        off = "disable_tiled_edit() first"
+        if _sk.is_editor_value(a.image) or self._edit_region is not None or getattr(self.transformer, "_auto_region", None) is not None \
+                or self._auto_focus is not None:
+            raise ValueError("tiled edits (enable_tiled_edit) edit the whole photo: an edit region - set_edit_region, enable_auto_region, "
+                             f"enable_auto_focus or a sketch editor value - is a second way to decide what is edited; clear it, or {off}")
+        if self._detail_lift is not None:
+            raise ValueError("tiled edits (enable_tiled_edit) and enable_detail_lift are two ways to reach the photo's size: "
+                             f"disable_detail_lift(), or {off}")
+        if isinstance(a.image, (list, tuple)) or isinstance(a.prompt, (list, tuple)) or (a.prompt_embeds is not None and a.prompt_embeds.shape[0] != 1):
+            raise NotImplementedError(f"tiled edits (enable_tiled_edit) take ONE image and ONE prompt per call: run a list one call each, or {off}")
+        if not image_io._is_pil(a.image):
+            raise ValueError("tiled edits (enable_tiled_edit) need ONE PIL image: an array or tensor `image` has no full-resolution bytes to "
+                             f"cut into tiles - pass a PIL image, or {off}")
+        for bad, what in ((a.num_videos_per_prompt != 1, "num_videos_per_prompt > 1"), (a.enable_temporal_reasoning, "temporal reasoning"),
+                          (self._preview is not None, "live previews (enable_preview)"),
+                          (getattr(self.transformer, "_teacache", None) is not None, "TeaCache (enable_teacache)"),
+                          (getattr(self.transformer, "_guidance_reuse", None) is not None, "guidance reuse (enable_guidance_reuse)"),
+                          (a.offload_model, "offload_model"),
+                          (self._guidance_measure is not None, "a measuring edit (measure_guidance_reuse)"),
+                          (self._auto_region_measure is not None, "a measuring edit (measure_auto_region)"),
+                          (bool(getattr(self.transformer, "_tea_measure", False)), "a measuring edit (calibrate_teacache)")):
+            if bad:
+                raise NotImplementedError(f"tiled edits (enable_tiled_edit) with {what} are not implemented: switch it off, or {off}")
+        refuse_sharded(self.transformer, _tl.SHARDED)
+
+    def _tiled_edit(self, a: CallArgs):
+        """`__call__` while `enable_tiled_edit` is in force: the plan, the tiles as the samples of one batched pass fused behind every step
+        (`denoise(tiles=)`), the weighted blend of the decoded tiles into the target's frame."""
+        cfg = self._tiled
+        self.tile_report = self.focus_report = self.lift_report = self.auto_region_report = None
+        self._tiled_refusals(a)
+        p = _tl.plan(a.image.size, a.height, a.width, cfg.size, cfg.overlap, cfg.max_tiles)
+        if p.single:  # the canvas is one tile: the plain call on the image, no tiling code on the path
+            out = self._edit(a)
+            self.tile_report = dict(p.report, reason="single")
+            return out
+        a, device = self._begin(a, guarded=False)
+        _, prompt_embeds, negative_prompt_embeds = self._encode_text(a, device)
+        on_device = image_io.on_device(self.device_image_io, device)
+        n = p.count
+        target = _tl.target_image(a.image, p.target, device if on_device else None)
+        crops = _tl.tile_images(target, p)
+        image_embeds = a.image_embeds
+        if image_embeds is None:  # clip="tile": the conditioning shows what the model edits; "photo": the whole target image, once
+            image_embeds = self.encode_image(crops if cfg.clip == "tile" else target, device)
+        image_embeds = image_embeds.to(device=device, dtype=self.transformer.dtype)
+        if image_embeds.shape[0] not in (1, n):
+            raise ValueError(f"`image_embeds` carry {image_embeds.shape[0]} samples, expected 1 or one per tile ({n})")
+        if image_embeds.shape[0] != n:
+            image_embeds = image_embeds.repeat(n, 1, 1)
+        if hasattr(self.vae, "use_graph"):
+            self.vae.use_graph = bool(self.use_graph)
+        if on_device:
+            img = image_io.preprocess_pil(crops, a.height, a.width, device)
+        else:
+            img = self.preprocess_image(crops, a.height, a.width).to(device=device, dtype=torch.bfloat16)
+        z = self.vae.config.z_dim
+        T = (a.num_frames - 1) // self.vae_scale_factor_temporal + 1
+        state = _tl.TileState(p, z, T, device)
+        shape = (1,) + tuple(state.canvas.shape)
+        if a.latents is None:  # ONE canvas of noise
+            if isinstance(a.generator, (list, tuple)) and len(a.generator) != 1:
+                raise ValueError(f"You have passed a list of generators of length {len(a.generator)}, but requested an effective batch"
+                                 f" size of 1. Make sure the batch size matches the length of the generators.")
+            noise = _randn_tensor(shape, a.generator, device, torch.bfloat16)
+        elif tuple(a.latents.shape) != shape:
+            raise ValueError(f"tiled edits (enable_tiled_edit) take `latents` at the canvas shape {shape}, got {tuple(a.latents.shape)}")
+        else:
+            noise = a.latents
+        latents = state.cut(noise.to(device=device, dtype=torch.float32))
+        _, condition = prepare_latents(self.vae, img, a.num_frames, latents=latents)
+        repeat = lambda t: None if t is None else t.repeat(n, 1, 1)
+        embeds = {"prompt_embeds": repeat(prompt_embeds), "negative_prompt_embeds": repeat(negative_prompt_embeds)}
+
+        self._num_timesteps = a.num_inference_steps
+        lora_scale = getattr(self.transformer, "lora_scale", None)
+        scaled = lora_scale((a.attention_kwargs or {}).get("scale")) if lora_scale is not None else contextlib.nullcontext()
+        with scaled:
+            latents = denoise(self.transformer, self.scheduler, latents, condition, embeds["prompt_embeds"],
+                              embeds["negative_prompt_embeds"] if self.do_classifier_free_guidance else None, image_embeds,
+                              a.num_inference_steps, a.guidance_scale, use_graph=self.use_graph, on_step_end=self._step_hook(a, embeds),
+                              interrupted=lambda: self._interrupt, graph_warm=self._graph_warm, tiles=state)
+        # once more behind the loop: the canvas and the tiles then agree whatever happened last - a callback that replaced the latents behind
+        # the last step, an interrupt before the first (the canvas is then the noise); after an ordinary last step it changes no bit
+        latents = state.fuse(latents)
+        self._current_timestep = None
+        self.tile_report = dict(p.report, reason="tiled")
+        if a.output_type == "latent":
+            video = state.canvas[None].clone()
+        else:
+            video = decode_latents(self.vae, latents)
+            if self.video_guardrail_runner is not None:  # :784-799, on the tiles' frames
+                video = self.video_guardrail_runner(video)
+                if video is None:
+                    raise Exception("Guardrail blocked video2world generation.")
+            if on_device and image_io.device_video(video):
+                blended = _blend_tiles(video, p).cpu().numpy()
+            else:
+                import numpy as np
+                tiles_u8 = np.stack([np.stack([np.asarray(f) for f in sample]) for sample in self.postprocess_video(video, output_type="pil")])
+                blended = _tl.reference_blend(torch.from_numpy(tiles_u8), p.xs, p.ys, p.target).numpy()
+            video = image_io.frames_from_u8([blended], a.output_type)
+        self.maybe_free_model_hooks()
+        if not a.return_dict:
+            return (video,)
+        return WanPipelineOutput(frames=video)
 
     def _edit(self, a: CallArgs, fpass: Optional[FocusPass] = None):
         """The body of every call.  fpass: this is a focused pass somebody planned (a sketch edit, or the scout of an auto-focused call);
@@ -1207,6 +1378,23 @@ class ChronoEditPipeline:
                 weights[id(m)] = _rg.latent_weights(m)
         return [(m, _rg.RegionConfig(w=weights[id(m)], z_src=z_src[j:j + 1])) for j, m in enumerate(masks)], None
 
+    def _step_hook(self, a: CallArgs, embeds: dict):
+        """`denoise`'s on_step_end for one run of the loop: `callback_on_step_end` gets that run's tensors - the latents and `embeds`
+        ({"prompt_embeds", "negative_prompt_embeds"}, updated in place when the callback replaces them) - and what it returns anew goes back
+        to the loop (:741-749)."""
+        def on_step_end(i, t, lat):
+            self._current_timestep = t
+            if a.callback_on_step_end is None:
+                return None
+            pool = {"latents": lat, **embeds}
+            outs = a.callback_on_step_end(self, i, t, {k: pool[k] for k in a.callback_on_step_end_tensor_inputs})
+            if not outs:
+                return None
+            new = {k: outs[k] for k in ("latents", "prompt_embeds", "negative_prompt_embeds") if k in outs and outs[k] is not pool[k]}
+            embeds.update({k: v for k, v in new.items() if k != "latents"})
+            return new or None
+        return on_step_end
+
     def _denoise_samples(self, a: CallArgs, latents, condition, prompt_embeds, negative_prompt_embeds, image_embeds, regions, autos,
                          start_step: int, start_eps, preview_tag, crop_of=None) -> torch.Tensor:
         """The loop, sample by sample (regions, autos: per sample, or None; crop_of: per sample its (editor value, crop), or None) -> the
@@ -1223,23 +1411,10 @@ class ChronoEditPipeline:
         with scaled:
             for b in range(prompt_embeds.shape[0]):
                 embeds = {"prompt_embeds": prompt_embeds[b:b + 1], "negative_prompt_embeds": None if negative_prompt_embeds is None else negative_prompt_embeds[b:b + 1]}
-
-                def on_step_end(i, t, lat, embeds=embeds):
-                    self._current_timestep = t
-                    if a.callback_on_step_end is None:
-                        return None
-                    pool = {"latents": lat, **embeds}
-                    outs = a.callback_on_step_end(self, i, t, {k: pool[k] for k in a.callback_on_step_end_tensor_inputs})
-                    if not outs:
-                        return None
-                    new = {k: outs[k] for k in ("latents", "prompt_embeds", "negative_prompt_embeds") if k in outs and outs[k] is not pool[k]}
-                    embeds.update({k: v for k, v in new.items() if k != "latents"})
-                    return new or None
-
                 done.append(denoise(self.transformer, self.scheduler, latents[b:b + 1], condition[b:b + 1], embeds["prompt_embeds"],
                                     embeds["negative_prompt_embeds"] if self.do_classifier_free_guidance else None, image_embeds[b:b + 1],
                                     a.num_inference_steps, a.guidance_scale, a.enable_temporal_reasoning, a.num_temporal_reasoning_steps,
-                                    use_graph=self.use_graph, on_step_end=on_step_end, interrupted=lambda: self._interrupt,
+                                    use_graph=self.use_graph, on_step_end=self._step_hook(a, embeds), interrupted=lambda: self._interrupt,
                                     graph_warm=self._graph_warm, region=None if regions is None else regions[b],
                                     auto_region=None if autos is None else autos[b], start_step=start_step,
                                     start_eps=None if start_eps is None else start_eps[b:b + 1],

@@ -810,6 +810,33 @@ int ce_rimlift_fit_q16(const void* L, const void* E, const void* M, int* AB, int
 int ce_rimlift_smooth_f32(const void* L, const void* E, const void* M, const int* AB, float* coef, int* R, int F, int H, int W, int radius,
                           hipStream_t stream);
 
+/* ---- tiled edits (csrc/ce_tiles.hip; chronoedit_amd/tiles.py is the definition and the three passes give its bits): one canvas of latents is
+ * denoised as overlapping model-size tiles, the samples of one batched pass.  The tiles form a separable grid: nx origins on x, ny on y,
+ * tile t = iy * nx + ix (row-major: the batch order) at (ox[ix], oy[iy]).  ox = int [nx], oy = int [ny] are HOST arrays, read by the launcher
+ * and passed to the kernel by value; per axis, for tiles of side T on a canvas side C: 1 <= n, o[0] = 0, o[n - 1] + T = C, strictly
+ * increasing, o[i + 1] <= o[i] + T (no gap); nx * ny <= 16 - anything else returns -1 before a launch.  A tile's weight at its own
+ * coordinates (x, y) is wx * wy with the integer tent w(x) = min(x + 1, T - x): any number of tiles may cover a cell.
+ * ce_tiles_fuse_f32: tiles = fp32 [nx * ny][planes][th][tw] -> canvas = fp32 [planes][ch][cw].  Per canvas cell, in double:
+ *   acc = sum over the covering tiles in ascending t of double(w_t) * double(x_t), every product and every add rounded on its own (the first
+ *   product is taken as it is), one division by double(sum of w_t), one rounding to fp32.  A cell under one tile keeps that tile's value
+ *   (w x / w is exact in double; a NaN stays a NaN), and tiles that agree on a cell return it bit for bit (the sum of w_t x is exact too).
+ * ce_tiles_scatter_f32: canvas -> tiles, every tile cell takes its canvas cell: a copy (also cuts the noise canvas into the tiles).
+ *   Both: one lane per four consecutive cells of a row as one 16-byte access where tw, cw and every ox are multiples of 4 and both bases are
+ *   16-byte aligned, one cell per lane otherwise - the same bits.  tiles == canvas or a NULL returns -1; planes * ch * cw or n * planes * th *
+ *   tw of 2^31 or more returns -2; a base that is not 4-byte aligned returns -3.
+ * ce_tiles_blend_u8: frames = uint8 [nx * ny][F][TH][TW][3] (the decoded tiles, ce_video_to_u8's layout) -> out = uint8 [F][H][W][3], the
+ *   top left H x W of the canvas the tiles span (H <= oy[ny - 1] + TH, W <= ox[nx - 1] + TW, origins in pixels).  Per pixel, channel and
+ *   frame out = (sum of w_t e_t + Wt / 2) / Wt with Wt = sum of w_t, tents in pixels, integer division, 64-bit sums.  One lane per four
+ *   consecutive bytes of a frame, stored as one dword where H * W * 3 is a multiple of 4 and out is 4-byte aligned, byte by byte otherwise:
+ *   any base address.  F <= 65535 (otherwise -1); a frame of 2^31 bytes or more returns -2.
+ * No atomics, no state, nothing allocated, no device-side read of the host: every call is capturable, every loop bounded by 16. */
+int ce_tiles_fuse_f32(const float* tiles, float* canvas, int nx, int ny, const int* ox, const int* oy, int planes, int th, int tw, int ch,
+                      int cw, hipStream_t stream);
+int ce_tiles_scatter_f32(const float* canvas, float* tiles, int nx, int ny, const int* ox, const int* oy, int planes, int th, int tw, int ch,
+                         int cw, hipStream_t stream);
+int ce_tiles_blend_u8(const void* frames, void* out, int nx, int ny, const int* ox, const int* oy, int F, int TH, int TW, int H, int W,
+                      hipStream_t stream);
+
 /* ---- a RCCL communicator owned by the library (csrc/ce_comm.hip): the exchanges of the sequence-parallel forward as C-ABI calls on the
  * caller's stream.  Replaces the torch.distributed collectives of the reference's sequence-parallel path (xfuser's Ulysses all-to-all behind
  * chronoedit_diffsynth/wan_video_new_chronoedit.py:330-355, the final all_gather :1495-1498) where the caller needs a step with
